@@ -213,6 +213,58 @@ def have_ref():
     return os.path.exists(REF_SO)
 
 
+# The reference's answers at every comparison of the oracle-vs-reference tests (test_oracle_vs_ref.py, test_halfpel_oracle.py,
+# test_blocksize_oracle.py), recorded from the compiled reference by tools/make_goldens.py: where oracle/_ref exists those tests
+# compare the oracle with the reference itself AND the reference with its stored answer; elsewhere the oracle with the stored answer.
+REF_ANSWERS = os.path.join(ROOT, "tests", "golden", "ref_answers.json")
+_answers = {}
+
+
+def _answer(v):
+    if isinstance(v, (bytes, bytearray)):
+        return hashlib.sha256(v).hexdigest()
+    if isinstance(v, (int, np.integer)):
+        return int(v)
+    return sha(v)
+
+
+def known_answer(key, value):
+    """`value` (an array, bytes or an int: the reference's own where oracle/_ref exists, else the oracle's) must be the reference's
+    answer stored for `key`.  With DSV1_RECORD_REF_ANSWERS=<file> (tools/make_goldens.py) the reference's values are recorded instead."""
+    rec = os.environ.get("DSV1_RECORD_REF_ANSWERS")
+    if rec:
+        assert have_ref(), "recording the reference's answers needs oracle/_ref"
+        if "recorded" not in _answers:
+            import atexit
+            import json
+            _answers["recorded"] = {}
+
+            def write():
+                with open(rec, "w") as f:
+                    json.dump(_answers["recorded"], f, indent=0, sort_keys=True)
+                    f.write("\n")
+            atexit.register(write)
+        _answers["recorded"][key] = _answer(value)
+        return
+    if "stored" not in _answers:
+        import json
+        with open(REF_ANSWERS) as f:
+            _answers["stored"] = json.load(f)
+    assert key in _answers["stored"], "no stored answer of the reference for %s (tests/golden/ref_answers.json)" % key
+    assert _answer(value) == _answers["stored"][key], "%s differs from the reference's answer" % key
+
+
+def check_ref(key, want, got, what=None):
+    """the oracle's `got` against the reference's `want` -- computed now where oracle/_ref exists, None elsewhere: then against the
+    reference's answer stored for `key`"""
+    if want is not None:
+        if isinstance(want, (bytes, bytearray, int, np.integer)):
+            assert want == got, what or key
+        else:
+            assert np.array_equal(want, got), what or key
+    known_answer(key, got if want is None else want)
+
+
 def load_ref():
     if "ref" not in _libs:
         _libs["ref"] = C.CDLL(REF_SO)

@@ -4,13 +4,16 @@ and ABR.  Encode must be byte-identical to the oracle's stream; the GPU decoder 
 import importlib
 import json
 import os
+import subprocess
+import sys
+import tempfile
 
 import numpy as np
 import pytest
 
 import _cabi as A
 import golden_cases as G
-from test_gpu_stream import _decode_and_compare, explain
+from test_gpu_stream import _decode_and_compare, explain, product_decode
 
 pytestmark = pytest.mark.gpu
 
@@ -24,23 +27,88 @@ def pkg():
 
 CASES = G.fuzz_cases()
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_crash_skips.json")) as _f:
-    _SKIPS = json.load(_f)      # inputs on which the REFERENCE itself dies, probed by tools/make_goldens.py in the build container
+    _CRASHES = json.load(_f)    # inputs on which the REFERENCE itself dies, probed by tools/make_goldens.py where the reference lives
 
 
-def _skip_if_reference_dies(case_id):
-    """The reference itself dies on a few inputs (SIGFPE: a 1-pixel-wide chroma edge block has a 0x0 quadrant,
-    bmc.c:176-189; heap overflow of the picture buffer when binary noise is coded at top quality, bs.c:53) and the
-    oracle restates that faithfully.  tools/make_goldens.py probes every case in a child process where the reference
-    lives and commits the list: there is no answer to be bit-exact with."""
-    if case_id in _SKIPS:
-        pytest.skip("the reference crashes on this input (%s)" % _SKIPS[case_id])
+# The oracle restates the reference's crash (below), so on these inputs it runs in a child process of its own: frame by frame, the
+# stream so far written out after every frame.  Only the oracle runs there, on the CPU.
+_ORACLE_CHILD = r"""
+import ctypes as C, sys
+sys.path.insert(0, %(here)r)
+import numpy as np
+import _cabi as A
+w, h, fmt, kw, path = %(w)d, %(h)d, %(fmt)d, %(kw)r, %(path)r
+clip = np.load(path + ".clip.npy")
+if %(decode)r:
+    for t, f in enumerate(A.orc_decode(open(path, "rb").read(), w, h, fmt)):
+        np.save(path + ".dec%%d.npy" %% t, f)
+    print("DECODED", flush=True)
+    sys.exit(0)
+L = A.load_orc()
+cfg = A.orc_cfg(w, h, fmt, **kw)
+e = L.orc_enc_open(C.byref(cfg))
+out, n, cap = C.c_void_p(None), C.c_size_t(0), C.c_size_t(0)
+for t in range(clip.shape[0]):
+    L.orc_enc_frame(e, clip[t].ctypes.data, C.byref(out), C.byref(n), C.byref(cap), None)
+    with open(path, "wb") as f:
+        f.write(C.string_at(out.value, n.value))
+    print("FRAMES", t + 1, flush=True)
+"""
+
+
+def _oracle_child(clip, w, h, fmt, kw, td, decode=None):
+    path = os.path.join(td, "s.dsv")
+    np.save(path + ".clip.npy", clip)
+    if decode is not None:
+        with open(path, "wb") as f:
+            f.write(decode)
+    src = _ORACLE_CHILD % dict(here=os.path.dirname(os.path.abspath(__file__)), w=w, h=h, fmt=fmt, kw=kw, path=path, decode=decode is not None)
+    r = subprocess.run([sys.executable, "-c", src], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    return r, path
+
+
+def _check_where_the_reference_dies(pkg, case_id, clip, w, h, fmt, kw):
+    """The reference itself dies on a few inputs (SIGFPE: a 1-pixel-wide chroma edge block has a 0x0 quadrant, bmc.c:176-189;
+    heap overflow of the picture buffer when binary noise is coded at top quality, bs.c:53), and the oracle restates that faithfully
+    (tools/make_goldens.py probes every case where the reference lives and commits the list).  The reference codes frame by frame,
+    so the frames before the one it dies on have an answer: the GPU path must code that prefix bit-exactly, and its decoder must
+    decode it as the oracle does.  Where not even the first frame has an answer, the product must end in a library error code
+    or in a stream that its decoder and the oracle decoder read alike (tests/test_gpu_robustness.py: no fault, no hang)."""
+    with tempfile.TemporaryDirectory() as td:
+        r, path = _oracle_child(clip, w, h, fmt, kw, td)
+        assert r.returncode < 0, "the oracle no longer dies on %s (rc %d): tests/golden/ref_crash_skips.json is stale" % (case_id, r.returncode)
+        done = [int(l.split()[1]) for l in r.stdout.splitlines() if l.startswith("FRAMES ")]
+        k = done[-1] if done else 0
+        assert k < clip.shape[0]
+        if k:
+            want = open(path, "rb").read()
+            got = pkg.encode_clip(clip[:k], w, h, fmt, eos=False, **kw)
+            assert got == want, explain(got, want)
+            dec, ref = product_decode(pkg, want), A.orc_decode(want, w, h, fmt)
+            assert len(dec) == len(ref) == k
+            for t in range(k):
+                A.assert_same("decoded frame %d" % t, dec[t], ref[t])
+            return
+        try:
+            got = pkg.encode_clip(clip, w, h, fmt, **kw)
+        except RuntimeError as e:
+            assert "rc=-" in str(e) or "DSVG" in str(e), "not a library error code: %s" % e
+            return
+        dec = product_decode(pkg, got)
+        r, path = _oracle_child(clip, w, h, fmt, kw, td, decode=bytes(got))
+        assert r.returncode == 0 and "DECODED" in r.stdout, "the oracle decoder died on the product's stream (rc %d)" % r.returncode
+        assert len(dec) == clip.shape[0] and os.path.exists(path + ".dec%d.npy" % (len(dec) - 1))
+        assert not os.path.exists(path + ".dec%d.npy" % len(dec)), "the oracle decoder gives more frames than the product's"
+        for t in range(len(dec)):
+            A.assert_same("decoded frame %d" % t, dec[t], np.load(path + ".dec%d.npy" % t))
 
 
 @pytest.mark.parametrize("case", range(len(CASES)), ids=[G.fuzz_id(c) for c in CASES])
 def test_fuzz_encode_decode(pkg, orc, case):
     w, h, fmt, n, style, kw, seed = CASES[case]
-    _skip_if_reference_dies("fuzz:" + G.fuzz_id(CASES[case]))
     clip = A.gen_clip(w, h, fmt, seed, n, style=style)
+    if "fuzz:" + G.fuzz_id(CASES[case]) in _CRASHES:
+        return _check_where_the_reference_dies(pkg, "fuzz:" + G.fuzz_id(CASES[case]), clip, w, h, fmt, kw)
     want, _ = A.orc_encode(clip, A.orc_cfg(w, h, fmt, **kw))
     got = pkg.encode_clip(clip, w, h, fmt, **kw)
     assert got == want, explain(got, want)
@@ -52,10 +120,11 @@ def test_fuzz_encode_decode(pkg, orc, case):
 def test_extreme_content(pkg, orc, kind, qp):
     """residuals at the edge of the 8-bit range (the packed int16 level-1 inverse and the int16 symbol planes must
     hold the largest coefficients a real input can produce)"""
-    _skip_if_reference_dies("extreme:%s:%d" % (kind, qp))
     w, h, fmt, n = G.EXTREME_GEOM
     clip = G.extreme_clip(kind, qp)
     kw = G.EXTREME_KW(qp)
+    if "extreme:%s:%d" % (kind, qp) in _CRASHES:
+        return _check_where_the_reference_dies(pkg, "extreme:%s:%d" % (kind, qp), clip, w, h, fmt, kw)
     want, _ = A.orc_encode(clip, A.orc_cfg(w, h, fmt, **kw))
     got = pkg.encode_clip(clip, w, h, fmt, **kw)
     assert got == want, explain(got, want)

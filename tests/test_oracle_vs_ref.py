@@ -1,6 +1,7 @@
-"""Pins the oracle (oracle/liborc.so, our restatement) against the REAL reference compiled from
-/root/reference into oracle/_ref/ -- operator by operator and for whole .dsv streams.
-CPU only.  Skipped where oracle/_ref is absent."""
+"""Pins the oracle (oracle/liborc.so, our restatement) against the REAL reference -- operator by operator and for whole
+.dsv streams.  CPU only.  Where the reference was compiled into oracle/_ref/ it runs beside the oracle on every input (and
+must still give the answers stored in tests/golden/ref_answers.json); elsewhere the oracle is checked against those stored
+answers (_cabi.check_ref)."""
 import ctypes as C
 import tempfile
 
@@ -9,7 +10,11 @@ import pytest
 
 import _cabi as A
 
-pytestmark = pytest.mark.ref
+
+@pytest.fixture(scope="module")
+def ref():
+    """the compiled reference (oracle/_ref/libdsv1ref.so), or None where it was not built"""
+    return A.load_ref() if A.have_ref() else None
 
 
 def rnd_plane(rng, w, h, smooth):
@@ -38,27 +43,31 @@ SBT_SIZES = [(16, 16), (18, 22), (176, 144), (352, 288), (250, 130), (960, 540)]
 def test_sbt_roundtrip_matches_ref(ref, orc, w, h, isP):
     rng = np.random.default_rng(w * 131 + h * 7 + isP)
     fmt = A.SUBSAMP_444
-    f = mk_frame_with(rng, w, h, fmt, extend_with=ref.dsv_extend_frame)
+    key = "sbt_%dx%d_P%d" % (w, h, isP)
+    f = mk_frame_with(rng, w, h, fmt, extend_with=ref.dsv_extend_frame if ref else orc.orc_frame_extend)
+    A.known_answer(key + "/input", f.raw())
     for c in (0, 1):
         cw, ch = w, h
         a = np.zeros(cw * ch, dtype=np.int32)
         b = np.zeros(cw * ch, dtype=np.int32)
         ca = A.Coefs(A.i32p(a), cw, ch)
         cb = A.Coefs(A.i32p(b), cw, ch)
-        ref.dsv_fwd_sbt(C.byref(f.c.planes[c]), C.byref(ca), isP)
+        if ref:
+            ref.dsv_fwd_sbt(C.byref(f.c.planes[c]), C.byref(ca), isP)
         orc.orc_fwd_sbt(C.byref(f.c.planes[c]), C.byref(cb), isP)
-        assert np.array_equal(a, b), "fwd_sbt differs c=%d" % c
+        A.check_ref("%s/c%d/fwd" % (key, c), a if ref else None, b, "fwd_sbt differs c=%d" % c)
         for q in (40, 313, 1500):
-            a2, b2 = a.copy(), a.copy()
+            a2, b2 = b.copy(), b.copy()
             # coarse "quantisation" so the smoothing filter has something to do
             a2[1:] = (a2[1:] // 16) * 16
             b2[:] = a2
             fa = A.BorderedFrame(w, h, fmt)
             fb = A.BorderedFrame(w, h, fmt)
-            ref.dsv_inv_sbt(C.byref(fa.c.planes[c]), C.byref(A.Coefs(A.i32p(a2), cw, ch)), q, isP, c)
+            if ref:
+                ref.dsv_inv_sbt(C.byref(fa.c.planes[c]), C.byref(A.Coefs(A.i32p(a2), cw, ch)), q, isP, c)
             orc.orc_inv_sbt(C.byref(fb.c.planes[c]), C.byref(A.Coefs(A.i32p(b2), cw, ch)), q, isP, c)
-            assert np.array_equal(fa.plane(c), fb.plane(c)), "inv_sbt differs c=%d q=%d" % (c, q)
-            assert np.array_equal(a2, b2)
+            A.check_ref("%s/c%d/inv_q%d" % (key, c, q), fa.plane(c) if ref else None, fb.plane(c), "inv_sbt differs c=%d q=%d" % (c, q))
+            A.check_ref("%s/c%d/inv_q%d_coefs" % (key, c, q), a2 if ref else None, b2)
 
 
 def _stab(rng, w, h, isP, cur_plane, all_flags=None):
@@ -87,21 +96,26 @@ def test_hzcc_encode_decode_matches_ref(ref, orc, w, h, isP, q):
         bufb = np.zeros_like(bufa)
         bsa = A.BS(A.u8p(bufa), 0)
         bsb = A.BS(A.u8p(bufb), 0)
-        ref.dsv_encode_plane(C.byref(bsa), C.byref(A.Coefs(A.i32p(a), w, h)), q, C.byref(st))
+        key = "hzcc_%dx%d_P%d_q%d/plane%d" % (w, h, isP, q, cur_plane)
+        if ref:
+            ref.dsv_encode_plane(C.byref(bsa), C.byref(A.Coefs(A.i32p(a), w, h)), q, C.byref(st))
         orc.orc_encode_plane(C.byref(bsb), C.byref(A.Coefs(A.i32p(b), w, h)), q, C.byref(st))
-        assert bsa.pos == bsb.pos
-        n = bsa.pos // 8
-        assert np.array_equal(bufa[:n], bufb[:n]), "bitstream differs"
-        assert np.array_equal(a, b), "dequantised coefficients differ"
+        A.check_ref(key + "/bits", bsa.pos if ref else None, bsb.pos)
+        n = bsb.pos // 8
+        A.check_ref(key + "/stream", bufa[:n] if ref else None, bufb[:n], "bitstream differs")
+        A.check_ref(key + "/dequant", a if ref else None, b, "dequantised coefficients differ")
         # decode: payload starts after the 4-byte length
-        plen = int.from_bytes(bufa[:4].tobytes(), "big")
+        src = bufa if ref else bufb
+        plen = int.from_bytes(src[:4].tobytes(), "big")
         da = np.zeros(w * h, dtype=np.int32)
         db = np.zeros(w * h, dtype=np.int32)
-        pa = bufa[4:4 + plen + 8].copy()
+        pa = src[4:4 + plen + 8].copy()
+        A.known_answer(key + "/payload", pa)
         pb = pa.copy()
-        ref.dsv_decode_plane(A.u8p(pa), plen, C.byref(A.Coefs(A.i32p(da), w, h)), q, C.byref(st))
+        if ref:
+            ref.dsv_decode_plane(A.u8p(pa), plen, C.byref(A.Coefs(A.i32p(da), w, h)), q, C.byref(st))
         orc.orc_decode_plane(A.u8p(pb), plen, C.byref(A.Coefs(A.i32p(db), w, h)), q, C.byref(st))
-        assert np.array_equal(da, db)
+        A.check_ref(key + "/decoded", da if ref else None, db)
 
 
 def rnd_mvs(rng, nbh, nbv, span):
@@ -121,45 +135,57 @@ def test_bmc_matches_ref(ref, orc, w, h, fmt):
     bw, bh, nbh, nbv = A.block_dims(w, h)
     meta = A.Meta(w, h, fmt, 30, 1, 1, 1)
     prm = A.Params(C.pointer(meta), 1, 1, bw, bh, nbh, nbv)
-    reff = mk_frame_with(rng, w, h, fmt, extend_with=ref.dsv_extend_frame)
+    extend = ref.dsv_extend_frame if ref else orc.orc_frame_extend
+    key = "bmc_%dx%d_fmt%d" % (w, h, fmt)
+    reff = mk_frame_with(rng, w, h, fmt, extend_with=extend)
+    A.known_answer(key + "/ref_frame", reff.raw())
     for span in (3, 40, 400):
+        k = "%s/span%d" % (key, span)
         mv = rnd_mvs(rng, nbh, nbv, span)
         mvp = mv.ctypes.data_as(C.POINTER(A.MV))
-        inp = mk_frame_with(rng, w, h, fmt, extend_with=ref.dsv_extend_frame)
+        inp = mk_frame_with(rng, w, h, fmt, extend_with=extend)
+        A.known_answer(k + "/input", inp.raw())
         ia, ib = A.BorderedFrame(w, h, fmt), A.BorderedFrame(w, h, fmt)
         ia.buf[:] = inp.buf
         ib.buf[:] = inp.buf
         da, db = A.BorderedFrame(w, h, fmt), A.BorderedFrame(w, h, fmt)
-        ref.dsv_sub_pred(mvp, C.byref(prm), da.ptr(), ia.ptr(), reff.ptr())
+        if ref:
+            ref.dsv_sub_pred(mvp, C.byref(prm), da.ptr(), ia.ptr(), reff.ptr())
         orc.orc_sub_pred(mvp, C.byref(prm), db.ptr(), ib.ptr(), reff.ptr())
-        assert np.array_equal(da.raw(), db.raw()), "prediction differs"
-        assert np.array_equal(ia.raw(), ib.raw()), "residual differs"
+        A.check_ref(k + "/pred", da.raw() if ref else None, db.raw(), "prediction differs")
+        A.check_ref(k + "/resid", ia.raw() if ref else None, ib.raw(), "residual differs")
         oa, ob = A.BorderedFrame(w, h, fmt), A.BorderedFrame(w, h, fmt)
-        ref.dsv_add_pred(mvp, C.byref(prm), ia.ptr(), oa.ptr(), reff.ptr())
+        if ref:
+            ref.dsv_add_pred(mvp, C.byref(prm), ia.ptr(), oa.ptr(), reff.ptr())
         orc.orc_add_pred(mvp, C.byref(prm), ib.ptr(), ob.ptr(), reff.ptr())
-        assert np.array_equal(oa.raw(), ob.raw())
-        ref.dsv_frame_add(ia.ptr(), da.ptr())
+        A.check_ref(k + "/add_pred", oa.raw() if ref else None, ob.raw())
+        if ref:
+            ref.dsv_frame_add(ia.ptr(), da.ptr())
         orc.orc_frame_add(ib.ptr(), db.ptr())
-        assert np.array_equal(ia.raw(), ib.raw())
+        A.check_ref(k + "/frame_add", ia.raw() if ref else None, ib.raw())
 
 
 def test_frame_ops_match_ref(ref, orc):
     rng = np.random.default_rng(5)
     for (w, h, fmt) in [(352, 288, A.SUBSAMP_420), (101, 77, A.SUBSAMP_420), (64, 48, A.SUBSAMP_444)]:
+        key = "frame_ops_%dx%d_fmt%d" % (w, h, fmt)
         fa = mk_frame_with(rng, w, h, fmt)
+        A.known_answer(key + "/input", fa.raw())
         fb = A.BorderedFrame(w, h, fmt)
         fb.buf[:] = fa.buf
-        ref.dsv_extend_frame(fa.ptr())
+        if ref:
+            ref.dsv_extend_frame(fa.ptr())
         orc.orc_frame_extend(fb.ptr())
-        assert np.array_equal(fa.raw(), fb.raw())
-        assert ref.dsv_frame_avg_luma(fa.ptr()) == orc.orc_frame_avg_luma(fb.ptr())
+        A.check_ref(key + "/extend", fa.raw() if ref else None, fb.raw())
+        A.check_ref(key + "/avg_luma", ref.dsv_frame_avg_luma(fa.ptr()) if ref else None, orc.orc_frame_avg_luma(fb.ptr()))
         w2, h2 = A.rshift_up(w, 1), A.rshift_up(h, 1)
         da, db = A.BorderedFrame(w2, h2, fmt), A.BorderedFrame(w2, h2, fmt)
-        ref.dsv_ds2x_frame_luma(da.ptr(), fa.ptr())
-        ref.dsv_extend_frame_luma(da.ptr())
+        if ref:
+            ref.dsv_ds2x_frame_luma(da.ptr(), fa.ptr())
+            ref.dsv_extend_frame_luma(da.ptr())
         orc.orc_frame_ds2x_luma(db.ptr(), fb.ptr())
         orc.orc_frame_extend_luma(db.ptr())
-        assert np.array_equal(da.raw(), db.raw())
+        A.check_ref(key + "/ds2x", da.raw() if ref else None, db.raw())
 
 
 def build_pyramid(lib_ds, lib_ext, f0, levels):
@@ -181,12 +207,20 @@ def test_hme_matches_ref(ref, orc, w, h, style):
     meta = A.Meta(w, h, fmt, 30, 1, 1, 1)
     prm = A.Params(C.pointer(meta), 1, 1, bw, bh, nbh, nbv)
     levels = 3
+    key = "hme_%dx%d_style%d" % (w, h, style)
     frames = []
     for t in range(3):
         f = A.BorderedFrame(w, h, fmt)
         f.load_planar(clip[t])
-        ref.dsv_extend_frame(f.ptr())
-        frames.append(build_pyramid(ref.dsv_ds2x_frame_luma, ref.dsv_extend_frame_luma, f, levels))
+        if ref:
+            ref.dsv_extend_frame(f.ptr())
+            frames.append(build_pyramid(ref.dsv_ds2x_frame_luma, ref.dsv_extend_frame_luma, f, levels))
+        else:
+            orc.orc_frame_extend(f.ptr())
+            frames.append(build_pyramid(orc.orc_frame_ds2x_luma, orc.orc_frame_extend_luma, f, levels))
+        for l in range(levels + 1):
+            A.known_answer("%s/frame%d/level%d" % (key, t, l), frames[t][l].raw())
+    fields = ("x", "y", "mode", "submask", "lo_var", "lo_tex", "high_detail")
     for t in (1, 2):
         ha, hb = A.HME(), A.HME()
         for hm in (ha, hb):
@@ -195,17 +229,19 @@ def test_hme_matches_ref(ref, orc, w, h, style):
             for l in range(levels + 1):
                 hm.src[l] = C.pointer(frames[t][l].c)
                 hm.ref[l] = C.pointer(frames[t - 1][l].c)
-        pa = ref.dsv_hme(C.byref(ha))
+        pa = ref.dsv_hme(C.byref(ha)) if ref else None
         pb = orc.orc_hme_run(C.byref(hb))
-        assert pa == pb
+        A.check_ref("%s/frame%d/hme" % (key, t), pa, pb)
         for l in range(levels + 1):
-            a = np.ctypeslib.as_array(C.cast(ha.mvf[l], C.POINTER(C.c_uint8)), shape=(nbh * nbv * 12,)).copy()
-            b = np.ctypeslib.as_array(C.cast(hb.mvf[l], C.POINTER(C.c_uint8)), shape=(nbh * nbv * 12,)).copy()
-            a = a.view(A.MV_DTYPE)
-            b = b.view(A.MV_DTYPE)
-            for k in ("x", "y", "mode", "submask", "lo_var", "lo_tex", "high_detail"):
-                assert np.array_equal(a[k], b[k]), "mv field %s differs at level %d frame %d" % (k, l, t)
-            ref.dsv_free(C.cast(ha.mvf[l], C.c_void_p))
+            b = np.ctypeslib.as_array(C.cast(hb.mvf[l], C.POINTER(C.c_uint8)), shape=(nbh * nbv * 12,)).copy().view(A.MV_DTYPE)
+            if ref:
+                a = np.ctypeslib.as_array(C.cast(ha.mvf[l], C.POINTER(C.c_uint8)), shape=(nbh * nbv * 12,)).copy().view(A.MV_DTYPE)
+                for k in fields:
+                    assert np.array_equal(a[k], b[k]), "mv field %s differs at level %d frame %d" % (k, l, t)
+                ref.dsv_free(C.cast(ha.mvf[l], C.c_void_p))
+            # the compared fields, one after the other
+            A.known_answer("%s/frame%d/mv_level%d" % (key, t, l),
+                           np.concatenate([np.ascontiguousarray((a if ref else b)[k]).view(np.uint8).ravel() for k in fields]))
             C.CDLL(None).free(hb.mvf[l])
 
 
@@ -234,21 +270,21 @@ STREAMS = [
 
 @pytest.mark.parametrize("case", range(len(STREAMS)))
 def test_stream_matches_ref_cli(orc, case):
-    if not A.have_ref():
-        pytest.skip("no reference build")
     w, h, fmt, n, style, flags, kw = STREAMS[case]
+    key = "stream_%d" % case
     clip = A.gen_clip(w, h, fmt, 0xABC000 + case, n, style=style)
     with tempfile.TemporaryDirectory() as td:
-        want = A.ref_cli_encode(clip, w, h, A.FMT_CLI[fmt], flags, td)
+        want = A.ref_cli_encode(clip, w, h, A.FMT_CLI[fmt], flags, td) if A.have_ref() else None
         got, recs = A.orc_encode(clip, A.orc_cfg(w, h, fmt, **kw), want_recon=True)
-        assert len(got) == len(want), "stream length %d vs %d" % (len(got), len(want))
-        assert got == want
+        if want is not None:
+            assert len(got) == len(want), "stream length %d vs %d" % (len(got), len(want))
+        A.check_ref(key + "/dsv", want, got)
         # decoder parity + "decoder output == encoder reconstruction" 
-        dec_ref = A.ref_cli_decode(want, td).reshape(n, -1)
+        dec_ref = A.ref_cli_decode(want, td).reshape(n, -1) if want is not None else [None] * n
         dec_orc = A.orc_decode(got, w, h, fmt)
         assert len(dec_orc) == n
         for t in range(n):
-            assert np.array_equal(dec_ref[t], dec_orc[t]), "decoded frame %d differs" % t
+            A.check_ref("%s/decoded%d" % (key, t), dec_ref[t], dec_orc[t], "decoded frame %d differs" % t)
             assert np.array_equal(recs[t], dec_orc[t]), "recon != decode at frame %d" % t
 
 
@@ -271,8 +307,8 @@ def test_parameter_changes_between_frames_match_ref_library(ref, orc, case):
     w, h, fmt, n = 352, 288, A.SUBSAMP_420, 31
     clip = A.gen_clip(w, h, fmt, 0x9A7A + case, n, style=2)
     enc = pkg.make_encoder_cfg(w, h, fmt, **cli)
-    want, _ = A.drive_dsv_enc(ref, enc, clip, w, h, fmt, changes=changes)
+    want = A.drive_dsv_enc(ref, enc, clip, w, h, fmt, changes=changes)[0] if ref else None
     got, _ = A.orc_encode(clip, A.orc_cfg(w, h, fmt, **cli), changes=changes)
-    assert got == want
+    A.check_ref("param_changes_%d/dsv" % case, want, got)
     plain, _ = A.orc_encode(clip, A.orc_cfg(w, h, fmt, **cli))
-    assert plain != want                                                  # (the changes do change the stream)
+    assert plain != got                                                   # (the changes do change the stream)

@@ -13,11 +13,14 @@ test time from (w,h,fmt,seed,style)), expected outputs are produced here by the 
   * cif_gop12.dsv  -- one complete small stream kept verbatim (config-1 size, 6 frames)
   * ops.json       -- operator-level known answers: sha256 of dsv_fwd_sbt / dsv_inv_sbt / dsv_encode_plane
                       / dsv_sub_pred / dsv_hme outputs on seeded inputs
+  * ref_answers.json -- the reference's answer at every comparison of the oracle-vs-reference tests (REF_ANSWER_TESTS), recorded
+                      by running them against the reference (_cabi.known_answer); only this file: --ref-answers-only
 """
 import ctypes as C
 import hashlib
 import json
 import os
+import subprocess
 import sys
 import tempfile
 
@@ -58,8 +61,28 @@ def ref_encode_clip(clip, w, h, fmt, kw):
     return out
 
 
+REF_ANSWER_TESTS = ("test_oracle_vs_ref.py", "test_halfpel_oracle.py", "test_blocksize_oracle.py")
+
+
+def ref_answers():
+    path = os.path.join(OUT, "ref_answers.json")
+    if os.path.exists(path):
+        os.remove(path)
+    r = subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider"] + [os.path.join(ROOT, "tests", t) for t in REF_ANSWER_TESTS],
+                        cwd=ROOT, env=dict(os.environ, DSV1_RECORD_REF_ANSWERS=path))
+    if r != 0:                                   # (the oracle differs from the reference somewhere: no answers are kept)
+        if os.path.exists(path):
+            os.remove(path)
+        raise SystemExit("the oracle-vs-reference tests failed: %s not written" % path)
+    with open(path) as f:
+        print("ref_answers.json:", len(json.load(f)), "answers")
+
+
 def main():
     assert A.have_ref(), "build oracle/_ref first (make -C oracle ref)"
+    if "--ref-answers-only" in sys.argv:
+        ref_answers()
+        return
     os.makedirs(OUT, exist_ok=True)
     ref = A.load_ref()
     streams = {}
@@ -127,6 +150,7 @@ def main():
             probe("extreme:%s:%d" % (kind, qp), G.extreme_clip(kind, qp), w, h, fmt, G.EXTREME_KW(qp))
     with open(os.path.join(OUT, "ref_crash_skips.json"), "w") as f:
         json.dump(skips, f, indent=1, sort_keys=True)
+    ref_answers()
 
 
 if __name__ == "__main__":
