@@ -53,6 +53,8 @@ def lib():
         L.dsv1_batch_set_fnum.argtypes = [_C.c_void_p, _C.c_int, _C.c_uint32]
         L.dsv1_batch_dropped_recons.restype = _C.c_long
         L.dsv1_batch_recon_all.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_batch_sse_enable.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_batch_get_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
         L.dsv1_batch_dropped_recons.argtypes = [_C.c_void_p, _C.POINTER(_C.c_long)]
         L.dsv1_batch_encode.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
         L.dsv1_batch_submit.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
@@ -193,6 +195,7 @@ class Batch:
         self.ctx = self.L.dsv1_batch_ctx(self.h)
         m = cfg.vidmeta
         self.frame_bytes = m.width * m.height + 2 * _chroma_size(m.width, m.height, m.subsamp)
+        self.width, self.height, self.fmt = m.width, m.height, m.subsamp
         self._dev = []
         self._pin = []
 
@@ -209,6 +212,23 @@ class Batch:
     def recon_all(self, on=True):
         """reconstruct every reference picture (on) / drop the ones nobody predicts from (off, the default); between batches"""
         _chk(self.L.dsv1_batch_recon_all(self.h, 1 if on else 0), "dsv1_batch_recon_all")
+
+    def sse_enable(self, on=True):
+        """measure the pictures of the batches submitted from now on (on) / stop measuring (off); between batches only.
+        The packets are the same either way (include/dsv1_api.h, dsv1_batch_sse_enable)"""
+        _chk(self.L.dsv1_batch_sse_enable(self.h, 1 if on else 0), "dsv1_batch_sse_enable")
+        self._sse_on = bool(on)
+
+    def sse(self):
+        """the batch collected last: per stream, frame (submitted order) and plane Y, U, V the exact sum of squared errors
+        source vs reconstruction over the picture area -> numpy.uint64 [nstreams, F, 3].  Raises if it was not measured."""
+        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.uint64)
+        _chk(self.L.dsv1_batch_get_sse(self.h, out.ctypes.data_as(_C.POINTER(_C.c_uint64)), out.size), "dsv1_batch_get_sse")
+        return out
+
+    def psnr(self):
+        """the same as PSNR in dB, float64 [nstreams, F, 4]: planes Y, U, V, then the whole picture (inf where SSE is 0)"""
+        return psnr_db(self.sse(), self.width, self.height, self.fmt)
 
     def encoder(self, stream):
         """the stream's DSV_ENCODER (owned by the batch): its public parameter fields may be changed between submits"""
@@ -462,6 +482,26 @@ def _chroma_size(w, h, fmt):
     """chroma plane samples for a DSV_SUBSAMP_* format code (dsv.h:62-75: bits 2-3 horizontal, 0-1 vertical shift)"""
     hs, vs = (fmt >> 2) & 3, fmt & 3
     return ((w + (1 << hs) - 1) >> hs) * ((h + (1 << vs) - 1) >> vs)
+
+
+def plane_samples(w, h, fmt):
+    """samples of the planes Y, U, V of a w x h picture in DSV_SUBSAMP_* format fmt (chroma rounded up, as the codec sizes it)"""
+    c = _chroma_size(w, h, fmt)
+    return w * h, c, c
+
+
+def psnr_db(sse, w, h, fmt):
+    """PSNR in dB from per-plane sums of squared errors (any array whose last axis is Y, U, V) of w x h pictures in format fmt:
+    float64 array with the last axis Y, U, V, whole picture -- 10 log10(255^2 N / SSE) per plane and sum SSE / sum N over the
+    picture; inf where the SSE is 0"""
+    e = _np.asarray(sse, dtype=_np.uint64)
+    if e.shape[-1:] != (3,):
+        raise ValueError("the last axis of sse must hold the three planes")
+    n = _np.array(plane_samples(w, h, fmt), dtype=_np.float64)
+    num = _np.concatenate([_np.broadcast_to(n, e.shape), _np.full(e.shape[:-1] + (1,), n.sum())], axis=-1) * (255.0 * 255.0)
+    den = _np.concatenate([e, e.sum(axis=-1, dtype=_np.uint64, keepdims=True)], axis=-1).astype(_np.float64)
+    with _np.errstate(divide="ignore"):
+        return _np.where(den == 0, _np.inf, 10.0 * _np.log10(num / _np.where(den == 0, 1.0, den)))
 
 
 def encode_clip(clip, w, h, fmt, device=0, eos=True, start_fnum=0, **cli):

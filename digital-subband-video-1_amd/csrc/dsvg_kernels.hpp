@@ -85,5 +85,8 @@ void launch_ds2x(hipStream_t st, const uint8_t *sslab, const FrameLayout &SL, ui
 bool level_sides_ok(const uint8_t *slab, const FrameLayout &L);
 void launch_luma_sum(hipStream_t st, const uint8_t *slab, const FrameLayout &L, int first, int n, unsigned *sums, Prof *pf = nullptr, const int *slot_tab = nullptr);
 void launch_frame_add(hipStream_t st, uint8_t *dst, const FrameLayout &DL, const uint8_t *src, const FrameLayout &SL);
+// k_quality.hip: per-plane sum of squared errors source vs reconstruction of every job, added into sse[3 * out slot + plane]
+// (the out slot found from JobDev.psum = psum0 + 3 * out slot); one launch per frame step and coding stream, after its reconstruction
+void launch_sse(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const HzPlaneSum *psum0, unsigned long long *sse);
 // k_hme.hip
 void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf = nullptr);

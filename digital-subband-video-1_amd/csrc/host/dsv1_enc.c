@@ -85,6 +85,14 @@ struct dsv1_batch {
     int chains;
     int *ch_start, *ch_len, *ch_pair, *ch_cur;   /* per chain of the call: first picture, length, reconstruction slot pair, slot of the pair that holds its newest reconstruction */
     int carry_pair, carry_cur;       /* the pair / slot that holds the reconstruction of the call's last picture (the next call may predict from it) */
+    /* Quality measurement (dsv1_batch_sse_enable): the device sums the squared errors of every picture per plane into its out slot
+     * (dsvg_ctx_sse_enable).  The two batches in flight use the two halves of the out slots, so batch i's sums stay on the device
+     * until its collect copies them here, whatever batch i+1 does meanwhile; a remedied picture (remedy_dropped) is coded into the
+     * half of the batch being submitted, whose own call zeroes those sums again before it codes its pictures. */
+    int sse_on;
+    int sse_sub[2];                  /* per pending slot: its batch was submitted with the measurement on */
+    uint64_t *sse;                   /* [nstreams][frames][3] of the batch collected last */
+    size_t sse_n;                    /* values in sse; 0 = that batch was not measured (or nothing has been collected) */
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -172,7 +180,7 @@ void dsv1_batch_close(dsv1_batch *b)
     free(b->slots_cur); free(b->slots_ref); free(b->pair_pic); free(b->out_slots);
     free(b->luma); free(b->mv_tmp); free(b->jobs); free(b->outs); free(b->rcjobs); free(b->sc0.pkt); free(b->rpar); free(b->has_recon); free(b->border_skipped); free(b->recon_dropped);
     free(b->ch_start); free(b->ch_len); free(b->ch_pair); free(b->ch_cur);
-    free(b->rc_dev); free(b->rc_par);
+    free(b->rc_dev); free(b->rc_par); free(b->sse);
     free(b);
 }
 
@@ -811,6 +819,24 @@ int dsv1_batch_recon_all(dsv1_batch *b, int on)
     b->keep_all = on != 0;
     return DSVG_OK;
 }
+int dsv1_batch_sse_enable(dsv1_batch *b, int on)
+{
+    int rc;
+    if (!b) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_sse_enable with batches in flight"); return DSVG_ERR_ARG; }
+    if (on && !b->sse && !(b->sse = (uint64_t *)malloc(sizeof(uint64_t) * 3 * (size_t)b->nstreams * (size_t)b->F))) return DSVG_ERR_NOMEM;
+    if ((rc = dsvg_ctx_sse_enable(b->ctx, on))) return rc;
+    b->sse_on = on != 0;
+    return DSVG_OK;
+}
+int dsv1_batch_get_sse(const dsv1_batch *b, uint64_t *sse, size_t n)
+{
+    if (!b || !sse) return DSVG_ERR_ARG;
+    if (!b->sse_n) { dsv1_log(1, "dsv1_batch_get_sse: the batch collected last was not measured (or none was collected)"); return DSVG_ERR_ARG; }
+    if (n < b->sse_n) { dsv1_log(1, "dsv1_batch_get_sse: %zu values needed, room for %zu", b->sse_n, n); return DSVG_ERR_ARG; }
+    memcpy(sse, b->sse, sizeof(uint64_t) * b->sse_n);
+    return DSVG_OK;
+}
 long dsv1_batch_dropped_recons(const dsv1_batch *b, long *remedied)
 {
     if (!b) return 0;
@@ -1045,6 +1071,7 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
         }
         if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
         b->pending[par] = serial ? 2 : 1;               /* 2 = already assembled */
+        b->sse_sub[par] = b->sse_on;
         b->nf_pending[par] = nf;
     }
     HP_MARK(HP_PREFIX);
@@ -1084,6 +1111,7 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
     S = b->nstreams; F = b->F;
     par = b->pending[b->parity] ? b->parity : (b->parity ^ 1);   /* oldest first */
     if (!b->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
+    b->sse_n = 0;                                       /* (dsv1_batch_get_sse: from here on about this batch) */
     pics = b->pics + (size_t)par * S * F;
     nf = b->nf_pending[par];
     if (b->bg_on[par]) {
@@ -1113,6 +1141,12 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
             if (ac.rc) return ac.rc;
         }
         HP_MARK(HP_FETCH);
+    }
+    if (b->sse_sub[par]) {
+        /* the batch's measurement, in submitted frame order ([stream][frame]: pics[s * F + t], a short batch has a single stream) */
+        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
+        if ((rc = dsvg_fetch_sse(b->ctx, S * nf, b->out_slots, b->sse))) return rc;
+        b->sse_n = (size_t)3 * S * nf;
     }
     b->pending[par] = 0;
     return DSVG_OK;

@@ -202,6 +202,17 @@ void dsv1_batch_set_fnum(dsv1_batch *b, int stream, DSV_FNUM next_fnum);
 long dsv1_batch_dropped_recons(const dsv1_batch *b, long *remedied);
 /* the same switch as a call (between batches: nothing in flight): on != 0 reconstructs every reference picture from the next submit on */
 int  dsv1_batch_recon_all(dsv1_batch *b, int on);
+/* Quality measurement (opt-in): with it on, the device also sums, for every picture of the batches submitted afterwards, the squared
+ * errors between the source and the reconstruction (what a decoder shows: DSV1 is closed-loop) per plane over the picture area,
+ * borders excluded, chroma at its subsampled size -- an exact uint64_t, computed inside the frame steps (dsvg_ctx_sse_enable); the
+ * packets are the same with it on or off.  PSNR = 10 log10(255^2 N / SSE) per plane, +inf for SSE 0; over the picture: sum SSE /
+ * sum N.  Batch and chain mode (dsv1_stream_open), CRF and ABR, every input form.  dsv1_batch_sse_enable: only between batches
+ * (nothing in flight, as dsv1_batch_recon_all), else DSVG_ERR_ARG.  dsv1_batch_get_sse: the sums of the batch returned by the
+ * last dsv1_batch_collect / dsv1_batch_encode, sse[(s * frames_per_call + t) * 3 + p] for stream s (chain mode: one stream), frame t
+ * in submitted order, plane p; n = room in values (>= nstreams * frames_per_call * 3); DSVG_ERR_ARG when that batch was not
+ * measured or none has been collected.  Not offered: the drop-in dsv_enc and the decoders. */
+int  dsv1_batch_sse_enable(dsv1_batch *b, int on);
+int  dsv1_batch_get_sse(const dsv1_batch *b, uint64_t *sse, size_t n);
 /* stream s's encoder struct (the batch owns it).  Its public parameter fields -- quality, bitrate, min_ / max_quality,
  * min_I_frame_quality, max_q_step, rc_high_motion_nudge; dsv_enc_force_metadata -- may be changed between submits, as a caller of
  * the reference changes them between dsv_enc calls; geometry, GOP structure and rate-control mode may not. */

@@ -278,6 +278,15 @@ int dsvg_fetch_pictures(dsvg_ctx *ctx, int n, const int *out_slots, dsvg_pic_out
  * later pieces are still being copied -- the caller's packet assembly overlaps the link. */
 typedef void (*dsvg_fetch_cb)(void *arg, int first, int count);
 int dsvg_fetch_pictures_cb(dsvg_ctx *ctx, int n, const int *out_slots, dsvg_pic_out *outs, int nchunks, int align, dsvg_fetch_cb cb, void *arg);
+/* Quality measurement (opt-in, encoder): with it on, every picture coded by a dsvg_code_batch / dsvg_code_batch_rc /
+ * dsvg_code_pictures call that STARTS afterwards also gets, on the device, the sum of squared errors between its source and its
+ * reconstruction -- what a decoder will show -- per plane over the picture area (borders excluded; chroma at its subsampled
+ * size): SSE[p] = sum (src - recon)^2, exact.  Pictures nobody predicts from are reconstructed for it in a work frame (the
+ * packets stay byte-identical).  With it off nothing of this runs.  PSNR = 10 log10(255^2 N / SSE), +inf for SSE 0.
+ * dsvg_fetch_sse: sse_out[3 i + p] for out_slots[i] -- valid after dsvg_fetch_pictures of those slots and until they are coded
+ * again; DSVG_ERR_ARG for a slot whose picture was coded with the measurement off.  Waits for the calls that coded them. */
+int dsvg_ctx_sse_enable(dsvg_ctx *ctx, int on);
+int dsvg_fetch_sse(dsvg_ctx *ctx, int n, const int *out_slots, uint64_t *sse_out);
 int dsvg_download_recon(dsvg_ctx *ctx, int recon_slot, uint8_t *yuv_out);            /* syncs */
 /* the first `bytes` bytes of the slot's whole frame allocation in the reference layout (dsv_mk_frame frame.c:63-120:
  * Y,U,V back to back, 64-px replicated borders): what the next picture's motion compensation reads.  Syncs. */
