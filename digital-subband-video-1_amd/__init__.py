@@ -55,6 +55,8 @@ def lib():
         L.dsv1_batch_recon_all.argtypes = [_C.c_void_p, _C.c_int]
         L.dsv1_batch_sse_enable.argtypes = [_C.c_void_p, _C.c_int]
         L.dsv1_batch_get_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
+        L.dsv1_batch_ssim_enable.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_batch_get_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
         L.dsv1_batch_dropped_recons.argtypes = [_C.c_void_p, _C.POINTER(_C.c_long)]
         L.dsv1_batch_encode.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
         L.dsv1_batch_submit.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
@@ -229,6 +231,22 @@ class Batch:
     def psnr(self):
         """the same as PSNR in dB, float64 [nstreams, F, 4]: planes Y, U, V, then the whole picture (inf where SSE is 0)"""
         return psnr_db(self.sse(), self.width, self.height, self.fmt)
+
+    def ssim_enable(self, on=True):
+        """measure the SSIM of the pictures of the batches submitted from now on (on) / stop (off); between batches only, independent
+        of sse_enable.  The packets are the same either way (include/dsv1_api.h, dsv1_batch_ssim_enable)"""
+        _chk(self.L.dsv1_batch_ssim_enable(self.h, 1 if on else 0), "dsv1_batch_ssim_enable")
+
+    def ssim_fx(self):
+        """the batch collected last: per stream, frame (submitted order) and plane Y, U, V the exact fixed-point SSIM -- the sum over
+        the plane's 8x8 windows at stride 4 of rint(2^32 SSIM) -> numpy.int64 [nstreams, F, 3].  Raises if it was not measured."""
+        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.int64)
+        _chk(self.L.dsv1_batch_get_ssim(self.h, out.ctypes.data_as(_C.POINTER(_C.c_int64)), out.size), "dsv1_batch_get_ssim")
+        return out
+
+    def ssim(self):
+        """the same as mean SSIM, float64 [nstreams, F, 4]: planes Y, U, V, then the whole picture (weighted by window count)"""
+        return ssim_mean(self.ssim_fx(), self.width, self.height, self.fmt)
 
     def encoder(self, stream):
         """the stream's DSV_ENCODER (owned by the batch): its public parameter fields may be changed between submits"""
@@ -502,6 +520,41 @@ def psnr_db(sse, w, h, fmt):
     den = _np.concatenate([e, e.sum(axis=-1, dtype=_np.uint64, keepdims=True)], axis=-1).astype(_np.float64)
     with _np.errstate(divide="ignore"):
         return _np.where(den == 0, _np.inf, 10.0 * _np.log10(num / _np.where(den == 0, 1.0, den)))
+
+
+SSIM_ONE = 1 << 32   # DSVG_SSIM_ONE: the fixed-point scale of one window's SSIM
+
+
+def ssim_windows(w, h, fmt):
+    """8x8 SSIM windows at stride 4 of the planes Y, U, V of a w x h picture in format fmt: ((pw - 8) // 4 + 1) * ((ph - 8) // 4 + 1)
+    per plane of pw x ph samples (chroma at its subsampled size), 0 where the plane is narrower or shorter than 8"""
+    hs, vs = (fmt >> 2) & 3, fmt & 3
+    cw, ch = (w + (1 << hs) - 1) >> hs, (h + (1 << vs) - 1) >> vs
+
+    def n(pw, ph):
+        return ((pw - 8) // 4 + 1) * ((ph - 8) // 4 + 1) if pw >= 8 and ph >= 8 else 0
+    return n(w, h), n(cw, ch), n(cw, ch)
+
+
+def ssim_mean(fx, w, h, fmt):
+    """mean SSIM from fixed-point per-plane sums (any array whose last axis is Y, U, V; Batch.ssim_fx()) of w x h pictures in format
+    fmt: float64 array with the last axis Y, U, V, whole picture -- fx / (2^32 nwin) per plane and sum fx / (2^32 sum nwin) over
+    the picture; NaN where there is no window"""
+    f = _np.asarray(fx, dtype=_np.int64)
+    if f.shape[-1:] != (3,):
+        raise ValueError("the last axis of fx must hold the three planes")
+    n = _np.array(ssim_windows(w, h, fmt), dtype=_np.float64)
+    num = _np.concatenate([f, f.sum(axis=-1, keepdims=True)], axis=-1).astype(_np.float64)
+    den = _np.concatenate([_np.broadcast_to(n, f.shape), _np.full(f.shape[:-1] + (1,), n.sum())], axis=-1) * float(SSIM_ONE)
+    with _np.errstate(divide="ignore", invalid="ignore"):
+        return _np.where(den == 0, _np.nan, num / _np.where(den == 0, 1.0, den))
+
+
+def ssim_db(x):
+    """SSIM in dB: -10 log10(1 - x), +inf at 1 (float64, elementwise)"""
+    x = _np.asarray(x, dtype=_np.float64)
+    with _np.errstate(divide="ignore"):
+        return -10.0 * _np.log10(1.0 - x)
 
 
 def encode_clip(clip, w, h, fmt, device=0, eos=True, start_fnum=0, **cli):

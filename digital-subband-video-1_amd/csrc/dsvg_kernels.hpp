@@ -88,5 +88,9 @@ void launch_frame_add(hipStream_t st, uint8_t *dst, const FrameLayout &DL, const
 // k_quality.hip: per-plane sum of squared errors source vs reconstruction of every job, added into sse[3 * out slot + plane]
 // (the out slot found from JobDev.psum = psum0 + 3 * out slot); one launch per frame step and coding stream, after its reconstruction
 void launch_sse(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const HzPlaneSum *psum0, unsigned long long *sse);
+// the same jobs' per-plane SSIM (8x8 windows at stride 4, fixed point: sum of rint(2^32 s)) added into ssim[3 * out slot + plane];
+// sse != nullptr: the sums of squared errors too, in the same pass (k_sse's figures: launch one or the other)
+void launch_ssim(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const HzPlaneSum *psum0, unsigned long long *ssim,
+                 unsigned long long *sse);
 // k_hme.hip
 void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf = nullptr);

@@ -183,6 +183,10 @@ struct dsvg_ctx {
     bool sse_on = false;
     unsigned long long *sse_d = nullptr, *sse_h = nullptr;   // [out_slots][3] device / pinned host
     std::vector<char> slot_sse;
+    // the same for SSIM (dsvg_ctx_ssim_enable): per out slot the three planes' fixed-point window sums (int64 as two's complement)
+    bool ssim_on = false;
+    unsigned long long *ssim_d = nullptr, *ssim_h = nullptr; // [out_slots][3] device / pinned host
+    std::vector<char> slot_ssim;
     // device-resident rate control (dsvg_code_batch_rc): per-stream state, per-job tables (indexed like jobs_h / jobs_d)
     dsvg_rc_state *rc_state_d = nullptr;
     RcJobDev *rcj_d = nullptr, *rcj_h = nullptr;
@@ -410,9 +414,9 @@ static void ctx_free(dsvg_ctx *c)
     for (int i = 0; i < 6; i++) c->src[i].release();
     c->recon.release(); c->xf.release(); c->pred.release();
     void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->ptab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d};
+                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->ptab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d, c->ssim_d};
     for (void *p : d) if (p) (void)hipFree(p);
-    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, c->sse_h};
+    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, c->sse_h, c->ssim_h};
     for (void *p : hh) if (p) (void)hipHostFree(p);
     if (c->st) (void)hipStreamDestroy(c->st);
     for (int i = 0; i < 2; i++) if (c->ev_mark[i]) (void)hipEventDestroy(c->ev_mark[i]);
@@ -1265,6 +1269,7 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
         }
     HIPCHK(hipSetDevice(c->device));
     const bool sse = c->sse_on;                              // quality measurement of this call's pictures (dsvg_ctx_sse_enable)
+    const bool ssim = c->ssim_on;                            // (dsvg_ctx_ssim_enable)
     static const bool cprof = getenv("DSV1_HOST_PROF") != nullptr;
     const auto cnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = cprof ? cnow() : 0.0;
@@ -1362,6 +1367,8 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             c->slot_isP[(size_t)j.out_slot] = (char)isP;
             if (c->slot_sse.size() != (size_t)c->out_slots) c->slot_sse.assign((size_t)c->out_slots, 0);
             c->slot_sse[(size_t)j.out_slot] = (char)sse;
+            if (c->slot_ssim.size() != (size_t)c->out_slots) c->slot_ssim.assign((size_t)c->out_slots, 0);
+            c->slot_ssim[(size_t)j.out_slot] = (char)ssim;
             if (rcj) dpos[(size_t)t * njobs + order[k]] = k;
             if (isP && !c->mc_fused) noint[NG * t + g] = 0;
             if (isP && c->mc_fused && !j.no_intra_blocks) {
@@ -1463,8 +1470,9 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
     HIPCHK(hipMemcpyAsync(c->mvs + (size_t)base * c->nblk, c->mv_h + (size_t)base * c->nblk, (size_t)c->nblk * total * sizeof(DMV), hipMemcpyHostToDevice, c->st));
     }
     HIPCHK(hipMemcpyAsync(c->slots_d + 2 * c->out_slots + base, c->slots_h + base, sizeof(int) * total, hipMemcpyHostToDevice, c->st));
-    // the measurement's sums of the call's out slots start at zero (k_sse adds into them); before the fork: every coding stream is behind it
+    // the measurements' sums of the call's out slots start at zero (k_sse / k_ssim add into them); before the fork: every coding stream is behind it
     if (sse) HIPCHK(hipMemsetAsync(c->sse_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
+    if (ssim) HIPCHK(hipMemsetAsync(c->ssim_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
     tl_mark(c, c->st, "code0");
     if (NG > 1) {
         if (!c->ev_fork) HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -1521,11 +1529,13 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             }
             // (pictures nobody predicts from -- intra-only streams -- have no reconstruction to make (dsv_encoder.c:665); a group without a single kept reconstruction skips the inverse transform altogether)
             // Measured pictures all need theirs: a job without a kept slot gets it in its work frame (JobDev.xf), where the inverse
-            // kernels put it; k_sse reads it there, in stream order behind the reconstruction and before anything can overwrite it
-            bool keeps = sse;
+            // kernels put it; k_sse / k_ssim read it there, in stream order behind the reconstruction and before anything can overwrite it.
+            // With both measurements on, k_ssim makes the SSE too: one pass over the pictures
+            bool keeps = sse || ssim;
             for (int k = k0; k < k0 + n && !keeps; k++) keeps = dj[(size_t)t * njobs + k]->recon_slot >= 0;
             if (keeps) OPCHK(enqueue_recon(c, nI, n, d0, 7, st, true, c->llq));
-            if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->sse_d);
+            if (ssim) launch_ssim(st, jd, n, c->L[0], c->psum, c->ssim_d, sse ? c->sse_d : nullptr);
+            else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->sse_d);
             launch_hz_pack(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
             // rate control: the sizes of these packets -> the quantiser tables of the same streams' pictures of the next step
             if (rcj) launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, d0, n, 1);
@@ -1771,27 +1781,28 @@ extern "C" int dsvg_fetch_pictures_cb(dsvg_ctx *c, int n, const int *out_slots, 
     return DSVG_OK;
 }
 
-extern "C" int dsvg_ctx_sse_enable(dsvg_ctx *c, int on)
+// the two measurements' switches and fetches (dsvg_ctx_sse_enable / dsvg_fetch_sse, dsvg_ctx_ssim_enable / dsvg_fetch_ssim): per out
+// slot three 64-bit sums on the device (dev), a pinned copy (host) and whether the picture coded into the slot last was measured
+static int quality_enable(dsvg_ctx *c, bool &flag, unsigned long long *&dev, unsigned long long *&host, int on)
 {
-    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
-    if (on && !c->sse_d) {                      // (every call zeroes the sums of its out slots itself)
+    if (on && !dev) {                           // (every call zeroes the sums of its out slots itself)
         HIPCHK(hipSetDevice(c->device));
-        OPCHK(dmalloc(&c->sse_d, (size_t)3 * c->out_slots, false));
-        OPCHK(hmalloc(&c->sse_h, (size_t)3 * c->out_slots));
+        OPCHK(dmalloc(&dev, (size_t)3 * c->out_slots, false));
+        OPCHK(hmalloc(&host, (size_t)3 * c->out_slots));
     }
-    c->sse_on = on != 0;
+    flag = on != 0;
     return DSVG_OK;
 }
 
-extern "C" int dsvg_fetch_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out)
+static int quality_fetch(dsvg_ctx *c, const char *what, const unsigned long long *dev, unsigned long long *host,
+                         const std::vector<char> &measured, int n, const int *out_slots, void *out)
 {
-    if (!c || n < 0 || (n > 0 && (!out_slots || !sse_out))) { dsvg_set_error("bad dsvg_fetch_sse arguments"); return DSVG_ERR_ARG; }
     int lo = c->out_slots, hi = -1;
     for (int i = 0; i < n; i++) {
         const int s = out_slots[i];
-        if (s < 0 || s >= c->out_slots) { dsvg_set_error("dsvg_fetch_sse: out slot %d out of range", s); return DSVG_ERR_ARG; }
-        if (!c->sse_d || (size_t)s >= c->slot_sse.size() || !c->slot_sse[(size_t)s]) {
-            dsvg_set_error("dsvg_fetch_sse: the picture in out slot %d was coded with the measurement off", s); return DSVG_ERR_ARG;
+        if (s < 0 || s >= c->out_slots) { dsvg_set_error("%s: out slot %d out of range", what, s); return DSVG_ERR_ARG; }
+        if (!dev || (size_t)s >= measured.size() || !measured[(size_t)s]) {
+            dsvg_set_error("%s: the picture in out slot %d was coded with the measurement off", what, s); return DSVG_ERR_ARG;
         }
         lo = std::min(lo, s); hi = std::max(hi, s);
     }
@@ -1803,10 +1814,34 @@ extern "C" int dsvg_fetch_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t
         const int e = c->slot_ev[(size_t)out_slots[i]];
         if (e >= 0 && !seen[(size_t)e]) { seen[(size_t)e] = 1; HIPCHK(hipStreamWaitEvent(c->st_c, c->ev_coded[(size_t)e], 0)); }
     }
-    HIPCHK(hipMemcpyAsync(c->sse_h + (size_t)3 * lo, c->sse_d + (size_t)3 * lo, sizeof(unsigned long long) * 3 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, c->st_c));
+    HIPCHK(hipMemcpyAsync(host + (size_t)3 * lo, dev + (size_t)3 * lo, sizeof(unsigned long long) * 3 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, c->st_c));
     HIPCHK(hipStreamSynchronize(c->st_c));
-    for (int i = 0; i < n; i++) memcpy(sse_out + (size_t)3 * i, c->sse_h + (size_t)3 * out_slots[i], 3 * sizeof(uint64_t));
+    for (int i = 0; i < n; i++) memcpy((unsigned long long *)out + (size_t)3 * i, host + (size_t)3 * out_slots[i], 3 * sizeof(unsigned long long));
     return DSVG_OK;
+}
+
+extern "C" int dsvg_ctx_sse_enable(dsvg_ctx *c, int on)
+{
+    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
+    return quality_enable(c, c->sse_on, c->sse_d, c->sse_h, on);
+}
+
+extern "C" int dsvg_fetch_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out)
+{
+    if (!c || n < 0 || (n > 0 && (!out_slots || !sse_out))) { dsvg_set_error("bad dsvg_fetch_sse arguments"); return DSVG_ERR_ARG; }
+    return quality_fetch(c, "dsvg_fetch_sse", c->sse_d, c->sse_h, c->slot_sse, n, out_slots, sse_out);
+}
+
+extern "C" int dsvg_ctx_ssim_enable(dsvg_ctx *c, int on)
+{
+    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
+    return quality_enable(c, c->ssim_on, c->ssim_d, c->ssim_h, on);
+}
+
+extern "C" int dsvg_fetch_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t *ssim_out)
+{
+    if (!c || n < 0 || (n > 0 && (!out_slots || !ssim_out))) { dsvg_set_error("bad dsvg_fetch_ssim arguments"); return DSVG_ERR_ARG; }
+    return quality_fetch(c, "dsvg_fetch_ssim", c->ssim_d, c->ssim_h, c->slot_ssim, n, out_slots, ssim_out);
 }
 
 extern "C" int dsvg_fetch_pictures(dsvg_ctx *c, int n, const int *out_slots, dsvg_pic_out *outs)

@@ -93,6 +93,11 @@ struct dsv1_batch {
     int sse_sub[2];                  /* per pending slot: its batch was submitted with the measurement on */
     uint64_t *sse;                   /* [nstreams][frames][3] of the batch collected last */
     size_t sse_n;                    /* values in sse; 0 = that batch was not measured (or nothing has been collected) */
+    /* SSIM (dsv1_batch_ssim_enable): the same bookkeeping, its own switch (dsvg_ctx_ssim_enable) */
+    int ssim_on;
+    int ssim_sub[2];
+    int64_t *ssim;                   /* [nstreams][frames][3] fixed-point SSIM of the batch collected last */
+    size_t ssim_n;
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -180,7 +185,7 @@ void dsv1_batch_close(dsv1_batch *b)
     free(b->slots_cur); free(b->slots_ref); free(b->pair_pic); free(b->out_slots);
     free(b->luma); free(b->mv_tmp); free(b->jobs); free(b->outs); free(b->rcjobs); free(b->sc0.pkt); free(b->rpar); free(b->has_recon); free(b->border_skipped); free(b->recon_dropped);
     free(b->ch_start); free(b->ch_len); free(b->ch_pair); free(b->ch_cur);
-    free(b->rc_dev); free(b->rc_par); free(b->sse);
+    free(b->rc_dev); free(b->rc_par); free(b->sse); free(b->ssim);
     free(b);
 }
 
@@ -837,6 +842,24 @@ int dsv1_batch_get_sse(const dsv1_batch *b, uint64_t *sse, size_t n)
     memcpy(sse, b->sse, sizeof(uint64_t) * b->sse_n);
     return DSVG_OK;
 }
+int dsv1_batch_ssim_enable(dsv1_batch *b, int on)
+{
+    int rc;
+    if (!b) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_ssim_enable with batches in flight"); return DSVG_ERR_ARG; }
+    if (on && !b->ssim && !(b->ssim = (int64_t *)malloc(sizeof(int64_t) * 3 * (size_t)b->nstreams * (size_t)b->F))) return DSVG_ERR_NOMEM;
+    if ((rc = dsvg_ctx_ssim_enable(b->ctx, on))) return rc;
+    b->ssim_on = on != 0;
+    return DSVG_OK;
+}
+int dsv1_batch_get_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n)
+{
+    if (!b || !ssim_fx) return DSVG_ERR_ARG;
+    if (!b->ssim_n) { dsv1_log(1, "dsv1_batch_get_ssim: the batch collected last was not measured (or none was collected)"); return DSVG_ERR_ARG; }
+    if (n < b->ssim_n) { dsv1_log(1, "dsv1_batch_get_ssim: %zu values needed, room for %zu", b->ssim_n, n); return DSVG_ERR_ARG; }
+    memcpy(ssim_fx, b->ssim, sizeof(int64_t) * b->ssim_n);
+    return DSVG_OK;
+}
 long dsv1_batch_dropped_recons(const dsv1_batch *b, long *remedied)
 {
     if (!b) return 0;
@@ -1072,6 +1095,7 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
         if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
         b->pending[par] = serial ? 2 : 1;               /* 2 = already assembled */
         b->sse_sub[par] = b->sse_on;
+        b->ssim_sub[par] = b->ssim_on;
         b->nf_pending[par] = nf;
     }
     HP_MARK(HP_PREFIX);
@@ -1111,7 +1135,7 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
     S = b->nstreams; F = b->F;
     par = b->pending[b->parity] ? b->parity : (b->parity ^ 1);   /* oldest first */
     if (!b->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
-    b->sse_n = 0;                                       /* (dsv1_batch_get_sse: from here on about this batch) */
+    b->sse_n = b->ssim_n = 0;                           /* (dsv1_batch_get_sse / _ssim: from here on about this batch) */
     pics = b->pics + (size_t)par * S * F;
     nf = b->nf_pending[par];
     if (b->bg_on[par]) {
@@ -1147,6 +1171,11 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
         for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
         if ((rc = dsvg_fetch_sse(b->ctx, S * nf, b->out_slots, b->sse))) return rc;
         b->sse_n = (size_t)3 * S * nf;
+    }
+    if (b->ssim_sub[par]) {
+        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
+        if ((rc = dsvg_fetch_ssim(b->ctx, S * nf, b->out_slots, b->ssim))) return rc;
+        b->ssim_n = (size_t)3 * S * nf;
     }
     b->pending[par] = 0;
     return DSVG_OK;

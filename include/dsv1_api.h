@@ -213,6 +213,13 @@ int  dsv1_batch_recon_all(dsv1_batch *b, int on);
  * measured or none has been collected.  Not offered: the drop-in dsv_enc and the decoders. */
 int  dsv1_batch_sse_enable(dsv1_batch *b, int on);
 int  dsv1_batch_get_sse(const dsv1_batch *b, uint64_t *sse, size_t n);
+/* SSIM of the same pictures (opt-in, independent of the SSE: any combination): per picture and plane the fixed-point sum of
+ * the 8x8 windows' SSIM at stride 4 (dsvg_ctx_ssim_enable, DSVG_SSIM_ONE) -- an exact int64; mean SSIM = ssim_fx /
+ * (DSVG_SSIM_ONE * nwin[p]), over the picture sum ssim_fx / (DSVG_SSIM_ONE * sum nwin).  The packets are the same with it on
+ * or off.  Same contract as the SSE pair: ssim_fx[(s * frames_per_call + t) * 3 + p]; enable only between batches; DSVG_ERR_ARG
+ * when the batch collected last was not measured, none has been collected, or n is short. */
+int  dsv1_batch_ssim_enable(dsv1_batch *b, int on);
+int  dsv1_batch_get_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n);
 /* stream s's encoder struct (the batch owns it).  Its public parameter fields -- quality, bitrate, min_ / max_quality,
  * min_I_frame_quality, max_q_step, rc_high_motion_nudge; dsv_enc_force_metadata -- may be changed between submits, as a caller of
  * the reference changes them between dsv_enc calls; geometry, GOP structure and rate-control mode may not. */

@@ -287,6 +287,15 @@ int dsvg_fetch_pictures_cb(dsvg_ctx *ctx, int n, const int *out_slots, dsvg_pic_
  * again; DSVG_ERR_ARG for a slot whose picture was coded with the measurement off.  Waits for the calls that coded them. */
 int dsvg_ctx_sse_enable(dsvg_ctx *ctx, int on);
 int dsvg_fetch_sse(dsvg_ctx *ctx, int n, const int *out_slots, uint64_t *sse_out);
+/* SSIM (opt-in, encoder, independent of the SSE): per picture and plane the sum over the 8x8 windows at stride 4 (top-left
+ * (4i, 4j) with 4i <= w - 8, 4j <= h - 8; uniform weights, population statistics) of rint(s * DSVG_SSIM_ONE), s evaluated in
+ * binary64 from the window's int32 sums exactly as k_quality.hip states it -- an exact int64, negative where the picture is.
+ * Mean SSIM of a plane = SSIM_FX / (DSVG_SSIM_ONE * nwin), nwin = ((w - 8) / 4 + 1) * ((h - 8) / 4 + 1) (0 below 8 x 8).
+ * Same scope and timing as the SSE pair: dsvg_fetch_ssim gives ssim_out[3 i + p] for out_slots[i]; DSVG_ERR_ARG for a slot
+ * whose picture was coded with SSIM off.  With SSE and SSIM both on, one pass over the pictures makes both. */
+#define DSVG_SSIM_ONE 4294967296LL   /* 2^32: the fixed-point scale of one window's SSIM */
+int dsvg_ctx_ssim_enable(dsvg_ctx *ctx, int on);
+int dsvg_fetch_ssim(dsvg_ctx *ctx, int n, const int *out_slots, int64_t *ssim_out);
 int dsvg_download_recon(dsvg_ctx *ctx, int recon_slot, uint8_t *yuv_out);            /* syncs */
 /* the first `bytes` bytes of the slot's whole frame allocation in the reference layout (dsv_mk_frame frame.c:63-120:
  * Y,U,V back to back, 64-px replicated borders): what the next picture's motion compensation reads.  Syncs. */
