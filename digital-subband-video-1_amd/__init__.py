@@ -50,6 +50,8 @@ def lib():
         L.dsvg_last_error.restype = _C.c_char_p
         L.dsv1_batch_open.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Encoder), _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_batch_close.argtypes = [_C.c_void_p]
+        L.dsv1_ladder_open.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Encoder), _C.c_int, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_batch_rungs.argtypes = [_C.c_void_p]
         L.dsv1_batch_set_fnum.argtypes = [_C.c_void_p, _C.c_int, _C.c_uint32]
         L.dsv1_batch_dropped_recons.restype = _C.c_long
         L.dsv1_batch_recon_all.argtypes = [_C.c_void_p, _C.c_int]
@@ -189,17 +191,29 @@ class Batch:
         self.L = lib()
         self.h = _C.c_void_p(None)
         self.nstreams, self.F = nstreams, frames_per_call
+        self.nsources = nstreams                 # (input frames come per source: a Ladder has fewer sources than output streams)
         if chains:
             assert nstreams == 1
             _chk(self.L.dsv1_stream_open(_C.byref(self.h), _C.byref(cfg), device, frames_per_call, chains), "dsv1_stream_open")
         else:
             _chk(self.L.dsv1_batch_open(_C.byref(self.h), _C.byref(cfg), device, nstreams, frames_per_call), "dsv1_batch_open")
+        self._opened(cfg)
+
+    def _opened(self, cfg):
         self.ctx = self.L.dsv1_batch_ctx(self.h)
         m = cfg.vidmeta
         self.frame_bytes = m.width * m.height + 2 * _chroma_size(m.width, m.height, m.subsamp)
         self.width, self.height, self.fmt = m.width, m.height, m.subsamp
         self._dev = []
         self._pin = []
+
+    def _input(self, yuv):
+        """a host clip as the C entry points read it: nsources x F frames, whatever it is given (checked here)"""
+        a = _np.ascontiguousarray(yuv, dtype=_np.uint8)
+        if a.size != self.nsources * self.F * self.frame_bytes:
+            raise ValueError("a batch is %d %s x %d frames x %d bytes, got %d bytes" % (
+                self.nsources, "streams" if self.nsources == self.nstreams else "sources", self.F, self.frame_bytes, a.size))
+        return a
 
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
@@ -285,9 +299,7 @@ class Batch:
         if on_device:
             ptr = yuv
         else:
-            a = _np.ascontiguousarray(yuv, dtype=_np.uint8)
-            if a.size != self.nstreams * self.F * self.frame_bytes:      # (the C entry point reads nstreams x F frames whatever it is given)
-                raise ValueError("a batch is %d streams x %d frames x %d bytes, got %d bytes" % (self.nstreams, self.F, self.frame_bytes, a.size))
+            a = self._input(yuv)
             ptr = a.ctypes.data
         _chk(self.L.dsv1_batch_encode(self.h, ptr, 1 if on_device else 0, bufs), "dsv1_batch_encode")
         if eos:
@@ -304,9 +316,7 @@ class Batch:
         if on_device:
             ptr = yuv
         else:
-            self._keep = _np.ascontiguousarray(yuv, dtype=_np.uint8)
-            if self._keep.size != self.nstreams * self.F * self.frame_bytes:
-                raise ValueError("a batch is %d streams x %d frames x %d bytes, got %d bytes" % (self.nstreams, self.F, self.frame_bytes, self._keep.size))
+            self._keep = self._input(yuv)
             ptr = self._keep.ctypes.data
         if not hasattr(self, "_abr"):
             self._abr = []
@@ -418,6 +428,37 @@ class Batch:
             self.close()
         except Exception:
             pass
+
+
+class Ladder(Batch):
+    """A quality ladder (dsv1_ladder_open): nsources sources, each coded at every rung of `rungs` (configs from make_encoder_cfg that
+    differ only in their rate-control fields) from one upload and one analysis.  Input is [source][frame] (nsources x F frames);
+    results -- encode() / collect() streams, sse(), ssim(), encoder(k), eos -- are per output stream k = source * nrungs + rung.
+    set_fnum(k, n) renumbers every rung of k's source.  Otherwise the methods of Batch."""
+
+    def __init__(self, rungs, nsources, frames_per_call, device=0):
+        rungs = list(rungs)
+        if not 1 <= len(rungs) <= MAX_RUNGS:
+            raise ValueError("a ladder has 1 to %d rungs, got %d" % (MAX_RUNGS, len(rungs)))
+        self.L = lib()
+        self.h = _C.c_void_p(None)
+        self.nrungs, self.nsources, self.F = len(rungs), nsources, frames_per_call
+        self.nstreams = nsources * self.nrungs
+        arr = (Encoder * self.nrungs)(*rungs)
+        _chk(self.L.dsv1_ladder_open(_C.byref(self.h), arr, self.nrungs, device, nsources, frames_per_call), "dsv1_ladder_open")
+        self._opened(rungs[0])
+
+    def stage(self, yuv):
+        """Batch.stage(), the clip checked for nsources x F frames (the upload reads that many)"""
+        self._input(yuv)
+        Batch.stage(self, yuv)
+
+    def stream(self, source, rung):
+        """output stream index k of (source, rung)"""
+        return source * self.nrungs + rung
+
+
+MAX_RUNGS = 16   # DSV1_MAX_RUNGS
 
 
 class DecBatch:
@@ -590,6 +631,18 @@ def encode_stream(clip, w, h, fmt, frames_per_call, chains, device=0, eos=True, 
             _chk(b.L.dsv1_batch_eos(b.h, 0, _C.byref(e)), "dsv1_batch_eos")
             out += _take(e)
         return out
+    finally:
+        b.close()
+
+
+def encode_ladder(clip, w, h, fmt, rungs, device=0, eos=True, **cli):
+    """one source coded at several rungs in one call (a Ladder of one source): clip [frames][frame_bytes]; rungs: a list of dicts of
+    make_encoder_cfg arguments that override `cli` per rung (e.g. [dict(qp=95), dict(qp=70)]) -> one .dsv bytes object per rung,
+    each byte for byte the stream the serial encoder writes with that rung's settings"""
+    n = clip.shape[0]
+    b = Ladder([make_encoder_cfg(w, h, fmt, **dict(cli, **r)) for r in rungs], 1, n, device)
+    try:
+        return b.encode(clip.reshape(1, n, -1), eos=eos)
     finally:
         b.close()
 

@@ -7,6 +7,7 @@
 // results.  The host only ever sees: MV fields, mean luma, per-plane (DC, nruns, payload bytes).
 #include <stdlib.h>
 #include <algorithm>
+#include <unordered_map>
 #include <cstddef>
 #include "dsvg_host.hpp"
 #include <ctime>
@@ -548,7 +549,9 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
     c->nz_total = nzo; c->chunks_per_job = cho; c->bits_per_job = bo;
 
     int rc = DSVG_OK;
-    auto fail = [&](int r) { ctx_free(c); return r; };
+    // (a failed allocation also leaves HIP's per-thread last error set: it is taken here, or the next context's first
+    // hipGetLastError check -- a smaller ladder tried after one that did not fit -- would report this failure as its own)
+    auto fail = [&](int r) { (void)hipGetLastError(); ctx_free(c); return r; };
     if (max_jobs >= 16) {
         // throughput contexts (several coding streams will run): coding, analysis, further coding streams on hardware
         // queues of their own; the fetch stream (idle most of the time) takes what is left.  The probe costs ~30 ms.
@@ -1381,9 +1384,39 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             icnt[NG * t + g] = iln - ioff[NG * t + g];
         }
     }
+    // Block tables shared between jobs (quality ladders, dsv1_ladder_open: every rung of a source passes the SAME host arrays for
+    // the source's motion field and stability flags): jobs of the call that pass the same pointer get one device copy.  Keyed on
+    // the pointer, not the content -- a call that shares no pointer keeps the layout it always had (device job base + i's tables
+    // at table index i) and uploads the same bytes.  mvu / stu: table index of job i; mvcp / stcp: job i is the one copied.
+    // (Several jobs may now read one source slot: no coding kernel writes it -- JobDev.src / srcp are const, and the in-place
+    // luma / chroma of slot_y / slot_cu / slot_cv is the caller's clip, read only.)
+    std::vector<int> mvu((size_t)total), stu((size_t)total);
+    std::vector<char> mvcp((size_t)total, 0), stcp((size_t)total, 0);
+    int nmv = 0, nst = 0;
+    {
+        std::unordered_map<const void *, int> mvk, stk;
+        std::vector<char> mvdone((size_t)total, 0);
+        for (int i = 0; i < total; i++) {
+            const dsvg_pic_job &j = *dj[(size_t)i];
+            const auto s = stk.emplace(j.stable_blocks, nst);
+            if (s.second) { stcp[(size_t)i] = 1; nst++; }
+            stu[(size_t)i] = s.first->second;
+            if (!j.mvs) mvu[(size_t)i] = nmv++;                          // (I pictures need none: never shared)
+            else {
+                const auto m = mvk.emplace(j.mvs, nmv);
+                if (m.second) nmv++;
+                mvu[(size_t)i] = m.first->second;
+            }
+            if (j.ref_recon_slot >= 0 && !mvdone[(size_t)mvu[(size_t)i]]) { mvdone[(size_t)mvu[(size_t)i]] = 1; mvcp[(size_t)i] = 1; }
+        }
+    }
+    const bool mv_contig = nmv == total;                     // the vectors of consecutive device jobs lie back to back (mvs0 of the kernels)
     {   // the job records themselves (quantiser tables of three planes, pointers, copies of the block tables): independent per
         // job, built on the session layer's worker pool (1 920 jobs: 1.5 ms on one thread)
-        struct BuildCtx { dsvg_ctx *c; const std::vector<const dsvg_pic_job *> *dj; int base, njobs; } bc = {c, &dj, base, njobs};
+        struct BuildCtx {
+            dsvg_ctx *c; const std::vector<const dsvg_pic_job *> *dj; int base, njobs;
+            const std::vector<int> *mvu, *stu; const std::vector<char> *mvcp, *stcp;
+        } bc = {c, &dj, base, njobs, &mvu, &stu, &mvcp, &stcp};
         dsv1_par_for(total, [](void *vp, int idx, int) {
             BuildCtx &B = *static_cast<BuildCtx *>(vp);
             dsvg_ctx *c = B.c;
@@ -1413,8 +1446,11 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             // inverse transform only touches the tiles that carry a residual (ping-pong slots, see dsv1_enc.c)
             if (isP && jb.recon && j.recon_slot != j.ref_recon_slot && !c->no_inplace_pred) jb.pred = jb.recon;
             c->slots_h[d] = j.recon_slot;
-            memcpy(c->stable_h + (size_t)d * c->nblk, j.stable_blocks, (size_t)c->nblk);
-            if (isP) memcpy(c->mv_h + (size_t)d * c->nblk, j.mvs, (size_t)c->nblk * sizeof(DMV));
+            const size_t um = (size_t)B.base + (size_t)(*B.mvu)[(size_t)idx], us = (size_t)B.base + (size_t)(*B.stu)[(size_t)idx];
+            jb.mvs = c->mvs + um * c->nblk;
+            jb.stable = c->stable + us * c->nblk;
+            if ((*B.stcp)[(size_t)idx]) memcpy(c->stable_h + us * c->nblk, j.stable_blocks, (size_t)c->nblk);
+            if ((*B.mvcp)[(size_t)idx]) memcpy(c->mv_h + um * c->nblk, j.mvs, (size_t)c->nblk * sizeof(DMV));
         }, &bc);
     }
     if (!c->no_lazy_border) {
@@ -1466,8 +1502,8 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
     if (iln) HIPCHK(hipMemcpyAsync(c->ilist_d + (size_t)base * c->nblk, il, sizeof(int) * (size_t)iln, hipMemcpyHostToDevice, c->st));
     for (int r = 0; r < link_repeat(); r++) {
     HIPCHK(hipMemcpyAsync(c->jobs_d + base, c->jobs_h + base, sizeof(JobDev) * total, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->stable + (size_t)base * c->nblk, c->stable_h + (size_t)base * c->nblk, (size_t)c->nblk * total, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->mvs + (size_t)base * c->nblk, c->mv_h + (size_t)base * c->nblk, (size_t)c->nblk * total * sizeof(DMV), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->stable + (size_t)base * c->nblk, c->stable_h + (size_t)base * c->nblk, (size_t)c->nblk * nst, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->mvs + (size_t)base * c->nblk, c->mv_h + (size_t)base * c->nblk, (size_t)c->nblk * nmv * sizeof(DMV), hipMemcpyHostToDevice, c->st));
     }
     HIPCHK(hipMemcpyAsync(c->slots_d + 2 * c->out_slots + base, c->slots_h + base, sizeof(int) * total, hipMemcpyHostToDevice, c->st));
     // the measurements' sums of the call's out slots start at zero (k_sse / k_ssim add into them); before the fork: every coding stream is behind it
@@ -1504,7 +1540,7 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             }
             if (n > nI) {
                 const int nP = n - nI;
-                const DMV *mv0 = c->mvs + (size_t)(d0 + nI) * c->nblk;
+                const DMV *mv0 = mv_contig ? c->mvs + (size_t)(d0 + nI) * c->nblk : nullptr;     // (shared tables: JobDev.mvs)
                 if (c->mc_fused) {
                     // inter blocks are predicted inside the forward transform; k_mc only serves the intra blocks (block means)
                     if (icnt[NG * t + g]) launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0, c->ilist_d + (size_t)base * c->nblk + ioff[NG * t + g], icnt[NG * t + g]);

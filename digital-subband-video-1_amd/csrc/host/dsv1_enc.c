@@ -36,14 +36,20 @@ struct dsv1_batch {
     dsvg_ctx *ctx;
     dsvg_geom g;
     int nstreams, F, own_enc, nblk, prefix_cap, small_w, small_h;
-    int rows;                   /* source-slot ring: rows x nstreams slots, rows = 2F+1 */
+    /* QUALITY LADDER (dsv1_ladder_open): nsrc sources x R rungs, output stream k = s * R + r; a plain batch is R = 1.  nstreams counts
+     * OUTPUT streams (encoders, reconstructions, quantisers, packets: everything per output is indexed by k); what depends on the source
+     * pixels alone -- source slots, mean luma, GOP / scene-change / intra decisions, motion fields, stability flags, packet prefixes --
+     * is worked out once per source, on the source's first rung (the LEAD, k = s * R: its encoder holds the source's decision state,
+     * its pics[] entries own the pool memory) and copied to the other rungs, whose pics[] entries point at the lead's tables */
+    int nsrc, R;
+    int rows;                   /* source-slot ring: rows x nsrc slots, rows = 2F+1 */
     unsigned gcount;            /* frames submitted so far per stream (ring position) */
     int parity;                 /* which half of the double-buffered per-batch state the next submit uses */
     int nf_cur;                 /* frames per stream of the batch being submitted (F, or fewer for a single stream's tail) */
     int nf_pending[2];          /* the same for the batches in flight */
     int pending[2];             /* batch submitted (device work enqueued) but not yet collected */
     DSV_ENCODER *enc;
-    pic_t *pics;                /* [2][nstreams*F] */
+    pic_t *pics;                /* [2][nstreams*F] (pool memory: the leads' entries, [2][nsrc][F]) */
     DSV_MV *mvpool;
     unsigned char *stabpool;
     uint8_t *prefixpool;
@@ -146,7 +152,7 @@ const char *dsv1_host_prof_name(int k) { return k >= 0 && k < HP_N ? hp_nm[k] : 
  * parallel loop over them on the worker pool (dsv1_par_for).  Workers: DSV1_HOST_THREADS, else min(12, cores / ranks on the node / 2); never more than streams. */
 #include <pthread.h>
 #include <unistd.h>
-static int slot_of(const dsv1_batch *b, int s, unsigned g) { return (int)(g % (unsigned)b->rows) * b->nstreams + s; }
+static int slot_of(const dsv1_batch *b, int s, unsigned g) { return (int)(g % (unsigned)b->rows) * b->nsrc + s; }     /* s: source */
 
 void *dsv1_batch_ctx(dsv1_batch *b) { return b ? (void *)b->ctx : NULL; }
 int dsv1_batch_recon_slot(const dsv1_batch *b, int stream)
@@ -189,15 +195,17 @@ void dsv1_batch_close(dsv1_batch *b)
     free(b);
 }
 
-static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int device, int nstreams, int F, int chains)
+/* encs: nsrc * R encoders, output stream k = s * R + r (a plain batch: R = 1) */
+static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int device, int nsrc, int R, int F, int chains)
 {
     dsv1_batch *b;
     const DSV_META *m = &encs[0].vidmeta;
-    int rc, i, np;
-    if (!out || nstreams < 1 || F < 1 || chains < 0 || (chains && nstreams != 1)) return DSVG_ERR_ARG;
+    const int nstreams = nsrc * R;
+    int rc, i, np, t;
+    if (!out || nsrc < 1 || R < 1 || F < 1 || chains < 0 || (chains && nstreams != 1)) return DSVG_ERR_ARG;
     b = (dsv1_batch *)b_calloc(1, sizeof(*b));
     if (!b) return DSVG_ERR_NOMEM;
-    b->nstreams = nstreams; b->F = F; b->enc = encs; b->own_enc = own;
+    b->nstreams = nstreams; b->nsrc = nsrc; b->R = R; b->F = F; b->enc = encs; b->own_enc = own;
     if (chains > F) chains = F;
     b->chains = chains; b->carry_pair = -1; b->carry_cur = -1;
     np = nstreams * F;
@@ -205,7 +213,7 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     /* chain mode: `chains` pictures per frame step, a pair of reconstruction slots per chain + one pair for the chain the
      * call before left open */
     rc = dsvg_ctx_create(&b->ctx, device, m->width, m->height, m->subsamp, encs[0].pyramid_levels,
-                         b->rows * nstreams, chains ? 2 * (chains + 1) : 2 * nstreams, chains ? chains : nstreams, 2 * np);
+                         b->rows * nsrc, chains ? 2 * (chains + 1) : 2 * nstreams, chains ? chains : nstreams, 2 * np);
     if (rc) { b->enc = NULL; dsv1_batch_close(b); return rc; }       /* the caller still owns encs */
     dsvg_ctx_geom(b->ctx, &b->g);
     b->nblk = b->g.nblocks_h * b->g.nblocks_v;
@@ -215,9 +223,9 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     /* every allocation checked (verdict round 4): one failure unwinds the whole batch, context included */
 #define B_ALLOC(field, type, n, sz) do { b->field = (type *)b_calloc((size_t)(n), (size_t)(sz)); if (!b->field) goto nomem; } while (0)
     B_ALLOC(pics, pic_t, 2 * (size_t)np, sizeof(pic_t));
-    B_ALLOC(mvpool, DSV_MV, 2 * (size_t)np * b->nblk, sizeof(DSV_MV));
-    B_ALLOC(stabpool, unsigned char, 2 * (size_t)np * b->nblk, 1);
-    B_ALLOC(prefixpool, uint8_t, 2 * (size_t)np, b->prefix_cap);
+    B_ALLOC(mvpool, DSV_MV, 2 * (size_t)nsrc * F * b->nblk, sizeof(DSV_MV));
+    B_ALLOC(stabpool, unsigned char, 2 * (size_t)nsrc * F * b->nblk, 1);
+    B_ALLOC(prefixpool, uint8_t, 2 * (size_t)nsrc * F, b->prefix_cap);
     B_ALLOC(slots_cur, int, np, sizeof(int));
     B_ALLOC(slots_ref, int, np, sizeof(int));
     B_ALLOC(pair_pic, int, np, sizeof(int));
@@ -226,8 +234,8 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     B_ALLOC(has_recon, unsigned char, nstreams, 1);
     B_ALLOC(border_skipped, unsigned char, nstreams, 1);
     B_ALLOC(recon_dropped, unsigned char, nstreams, 1);
-    B_ALLOC(luma, unsigned, (size_t)b->rows * nstreams, sizeof(unsigned));
-    B_ALLOC(mv_tmp, DSV_MV, (size_t)np * b->nblk, sizeof(DSV_MV));
+    B_ALLOC(luma, unsigned, (size_t)b->rows * nsrc, sizeof(unsigned));
+    B_ALLOC(mv_tmp, DSV_MV, (size_t)nsrc * F * b->nblk, sizeof(DSV_MV));
     B_ALLOC(jobs, dsvg_pic_job, np, sizeof(dsvg_pic_job));
     B_ALLOC(outs, dsvg_pic_out, np, sizeof(dsvg_pic_out));
     B_ALLOC(rcjobs, dsvg_rc_job, np, sizeof(dsvg_rc_job));
@@ -245,11 +253,14 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     b->sc0.pkt = (uint8_t *)b_calloc(1, b->sc0.cap);
     if (!b->sc0.pkt) goto nomem;
 #undef B_ALLOC
-    for (i = 0; i < 2 * np; i++) {
-        b->pics[i].mvs = b->mvpool + (size_t)i * b->nblk;
-        b->pics[i].stable = b->stabpool + (size_t)i * b->nblk;
-        b->pics[i].prefix = b->prefixpool + (size_t)i * b->prefix_cap;
-    }
+    for (i = 0; i < 2 * nsrc; i++)                      /* (half, source) */
+        for (t = 0; t < F; t++) {
+            pic_t *pc = &b->pics[((size_t)(i / nsrc) * nstreams + (size_t)(i % nsrc) * R) * F + t];
+            const size_t u = (size_t)i * F + t;
+            pc->mvs = b->mvpool + u * b->nblk;
+            pc->stable = b->stabpool + u * b->nblk;
+            pc->prefix = b->prefixpool + u * b->prefix_cap;
+        }
     dsv1_recycle_hold(+1);
     b->holds_recycler = 1;
     *out = b;
@@ -273,7 +284,7 @@ int dsv1_batch_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int ns
         encs[s].ref = NULL; encs[s].stability = NULL; encs[s].stable_blocks = NULL;
         dsv_enc_start(&encs[s]);
     }
-    rc = batch_open_on(out, encs, 1, device, nstreams, frames_per_call, 0);
+    rc = batch_open_on(out, encs, 1, device, nstreams, 1, frames_per_call, 0);
     if (rc) {
         for (s = 0; s < nstreams; s++) {                /* what dsv_enc_start gave every stream */
             if (encs[s].stability) dsv_free(encs[s].stability);
@@ -283,6 +294,46 @@ int dsv1_batch_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int ns
     }
     return rc;
 }
+
+/* the fields the source-only analysis reads: every rung of a ladder must agree on them */
+static int ladder_rungs_agree(const DSV_ENCODER *a, const DSV_ENCODER *b)
+{
+    return !memcmp(&a->vidmeta, &b->vidmeta, sizeof(DSV_META)) && a->gop == b->gop && a->do_scd == b->do_scd &&
+           a->scene_change_delta == b->scene_change_delta && a->intra_pct_thresh == b->intra_pct_thresh &&
+           a->stable_refresh == b->stable_refresh && a->pyramid_levels == b->pyramid_levels && a->rc_mode == b->rc_mode;
+}
+
+int dsv1_ladder_open(dsv1_batch **out, const DSV_ENCODER *rungs, int nrungs, int device, int nsources, int frames_per_call)
+{
+    DSV_ENCODER *encs;
+    int s, r, rc, n;
+    if (!out || !rungs || nrungs < 1 || nrungs > DSV1_MAX_RUNGS || nsources < 1 || nsources > INT_MAX / DSV1_MAX_RUNGS || frames_per_call < 1) return DSVG_ERR_ARG;
+    n = nsources * nrungs;
+    for (r = 1; r < nrungs; r++)
+        if (!ladder_rungs_agree(&rungs[0], &rungs[r])) {
+            dsv1_log(1, "dsv1_ladder_open: rung %d differs from rung 0 in a field the analysis reads (geometry, GOP, scene cuts, intra / stability thresholds, pyramid, rate-control mode)", r);
+            return DSVG_ERR_ARG;
+        }
+    encs = (DSV_ENCODER *)b_calloc((size_t)n, sizeof(DSV_ENCODER));
+    if (!encs) return DSVG_ERR_NOMEM;
+    for (s = 0; s < nsources; s++)
+        for (r = 0; r < nrungs; r++) {
+            DSV_ENCODER *e = &encs[s * nrungs + r];
+            *e = rungs[r];
+            e->ref = NULL; e->stability = NULL; e->stable_blocks = NULL;
+            dsv_enc_start(e);
+        }
+    rc = batch_open_on(out, encs, 1, device, nsources, nrungs, frames_per_call, 0);
+    if (rc) {
+        for (s = 0; s < n; s++) {
+            if (encs[s].stability) dsv_free(encs[s].stability);
+            if (encs[s].stable_blocks) dsv_free(encs[s].stable_blocks);
+        }
+        free(encs);
+    }
+    return rc;
+}
+int dsv1_batch_rungs(const dsv1_batch *b) { return b ? b->R : DSVG_ERR_ARG; }
 
 /* ONE stream, frames_per_call consecutive frames per call, residual coding GOP-parallel (chain mode, see struct dsv1_batch):
  * the same bytes as the frame-serial encoder for ANY CRF configuration -- scene changes, forced-intra P pictures, a
@@ -298,7 +349,7 @@ int dsv1_stream_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int f
     *enc = *cfg;
     enc->ref = NULL; enc->stability = NULL; enc->stable_blocks = NULL;
     dsv_enc_start(enc);
-    rc = batch_open_on(out, enc, 1, device, 1, frames_per_call, max_chains);
+    rc = batch_open_on(out, enc, 1, device, 1, 1, frames_per_call, max_chains);
     if (rc) {
         if (enc->stability) dsv_free(enc->stability);
         if (enc->stable_blocks) dsv_free(enc->stable_blocks);
@@ -310,7 +361,9 @@ int dsv1_stream_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int f
 DSV_ENCODER *dsv1_batch_encoder(dsv1_batch *b, int stream) { return b && stream >= 0 && stream < b->nstreams ? &b->enc[stream] : NULL; }
 void dsv1_batch_set_fnum(dsv1_batch *b, int stream, DSV_FNUM next_fnum)
 {
-    if (b && stream >= 0 && stream < b->nstreams) b->enc[stream].next_fnum = next_fnum;
+    int r;
+    if (b && stream >= 0 && stream < b->nstreams)          /* (a ladder: every rung of the stream's source) */
+        for (r = 0; r < b->R; r++) b->enc[stream - stream % b->R + r].next_fnum = next_fnum;
 }
 
 /* ---- rate control: quality2quant dsv_encoder.c:70-168 and the statistics of dsv_enc :816-848 live in include/dsvg_rc.h -- one
@@ -579,11 +632,11 @@ static void side_stream(void *ctx, int s, int tid)
     side_ctx *c = (side_ctx *)ctx;
     dsv1_batch *b = c->b;
     const int F = b->F, nblk = b->nblk;
-    DSV_ENCODER *e = &b->enc[s];
+    DSV_ENCODER *e = &b->enc[s * b->R];                 /* (s: a source; its lead rung) */
     int t;
     (void)tid;
     for (t = 0; t < b->nf_cur; t++) {
-        pic_t *pc = &c->pics[s * F + t];
+        pic_t *pc = &c->pics[s * b->R * F + t];
         if (pc->has_ref) {
             int nintra = 0, i;
             int x0 = 0, x1 = 0, y0 = 0, y1 = 0;           /* full-pel reach of the inter blocks' vectors */
@@ -618,7 +671,7 @@ static void prefix_stream(void *ctx, int s, int tid)
     int t;
     (void)tid;
     if (!tmp) { c->rc = DSVG_ERR_ARG; return; }         /* (a stale prefix would go out as a corrupt packet: the submit fails instead) */
-    for (t = 0; t < c->nf; t++) prefix_one(b, &c->pics[s * F + t], tmp);
+    for (t = 0; t < c->nf; t++) prefix_one(b, &c->pics[s * b->R * F + t], tmp);      /* (s: a source) */
     free(tmp);
 }
 
@@ -649,7 +702,7 @@ static void prefix_picture(void *ctx, int t, int tid)
     uint8_t *tmp = (uint8_t *)malloc(((size_t)c->b->nblk * 8 + 64) * 4 + 64);
     (void)tid;
     if (!tmp) { c->rc = DSVG_ERR_ARG; return; }
-    prefix_one(c->b, &c->pics[t], tmp);
+    prefix_one(c->b, &c->pics[(t / c->nf) * c->b->R * c->b->F + t % c->nf], tmp);      /* (t: source x nf + frame) */
     free(tmp);
 }
 
@@ -755,6 +808,8 @@ static void asm_stream(void *ctx, int s, int tid)
     (void)tid;
     for (t = 0; t < c->nf; t++) {
         const dsvg_pic_out *po = &b->outs[s * F + t];
+        /* the prefix is the source's: written into the lead's entry (by a loop that may have run after this entry was copied) */
+        if (s % b->R) c->pics[s * F + t].prefix_len = c->pics[(s - s % b->R) * F + t].prefix_len;
         need += (size_t)c->pics[s * F + t].prefix_len + 192;
         for (p = 0; p < 3; p++) need += po->nbytes[p] + 32;
     }
@@ -867,9 +922,10 @@ long dsv1_batch_dropped_recons(const dsv1_batch *b, long *remedied)
     return b->n_dropped;
 }
 
+/* A ladder (struct dsv1_batch): steps 1-4 run per SOURCE (S sources, lead rung s * R), step 5 per OUTPUT stream (N = S * R) */
 static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *abr_out, int nf, int inplace_ok)
 {
-    int S, F, nblk, with_pyr, s, t, k, rc, npairs = 0, par, nremedy = 0;
+    int S, N, R, F, nblk, with_pyr, s, r, t, k, rc, npairs = 0, par, nremedy = 0;
     size_t fb;
     const DSV_ENCODER *e0;
     const uint8_t *dyuv = (const uint8_t *)yuv;
@@ -878,15 +934,15 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
     if (!b || !yuv) return DSVG_ERR_ARG;
     if (hp_on < 0) hp_on = getenv("DSV1_HOST_PROF") != NULL;
     HP_BEGIN();
-    S = b->nstreams; F = b->F; nblk = b->nblk; fb = b->g.frame_bytes;
+    S = b->nsrc; N = b->nstreams; R = b->R; F = b->F; nblk = b->nblk; fb = b->g.frame_bytes;
     if (nf <= 0) nf = F;
-    if (nf > F || (nf < F && S != 1)) { dsv1_log(1, "a short batch needs a single stream"); return DSVG_ERR_ARG; }
+    if (nf > F || (nf < F && N != 1)) { dsv1_log(1, "a short batch needs a single stream"); return DSVG_ERR_ARG; }
     b->nf_cur = nf;
     e0 = &b->enc[0];
     with_pyr = e0->gop != DSV_GOP_INTRA;
     par = b->parity;
     if (b->pending[par]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
-    pics = b->pics + (size_t)par * S * F;
+    pics = b->pics + (size_t)par * N * F;
     if (!yuv_on_device) {
         /* host frames go through the context's double-buffered ingest (copy stream of its own): nothing here waits
          * for the device, and a clip announced with dsv1_batch_stage() is already on its way */
@@ -920,20 +976,21 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
         if ((rc = dsvg_get_luma_sums(b->ctx, 0, b->rows * S, b->luma))) return rc;
 
     HP_MARK(HP_LOAD);
-    /* 2. per stream, in coding order: GOP / scene-change decisions; collect ME pairs */
+    /* 2. per source, in coding order: GOP / scene-change decisions; collect ME pairs */
     for (s = 0; s < S; s++) {
-        DSV_ENCODER *e = &b->enc[s];
+        DSV_ENCODER *e = &b->enc[s * R];                    /* the lead rung keeps the source's decision state */
+        for (r = 1; r < R; r++) e->force_metadata |= b->enc[s * R + r].force_metadata;     /* (forced on any rung: a GOP start on all) */
         if (!e->stability) {
             e->stability = (struct DSV_STAB_ACC *)dsv_alloc((int)(sizeof(*e->stability) * nblk));
             e->stable_blocks = (unsigned char *)dsv_alloc(nblk);
         }
         if (e->pyramid_levels == 0) e->pyramid_levels = b->g.pyramid_levels;
         for (t = 0; t < nf; t++) {
-            pic_t *pc = &pics[s * F + t];
+            pic_t *pc = &pics[s * R * F + t];
             pc->fnum = e->next_fnum++;
             pc->cur_slot = slot_of(b, s, b->gcount + (unsigned)t);
             pc->ref_slot = slot_of(b, s, b->gcount + (unsigned)t + (unsigned)b->rows - 1u);
-            pc->out_slot = par * S * F + t * S + s;
+            pc->out_slot = par * N * F + t * N + s * R;
             pc->gop_start = 0; pc->forced_intra = 0;
             if (e->force_metadata || (DSV_FNUM)(e->prev_gop + (DSV_FNUM)e->gop) <= pc->fnum) {
                 pc->gop_start = 1;
@@ -951,23 +1008,30 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
                     e->prev_avg_luma = al;
                 }
             }
-            if (pc->has_ref && t == 0 && b->border_skipped[s]) {
-                /* the batch before promised a GOP start here (border_hint) and the caller changed the frame numbering
-                 * in between (dsv1_batch_set_fnum): give the reference its whole border after all */
-                if ((rc = dsvg_extend_recon(b->ctx, b->chains ? b->carry_cur : s + S * b->rpar[s]))) return rc;
-            }
-            if (t == 0) b->border_skipped[s] = 0;
-            if (t == 0 && b->recon_dropped[s]) {
-                /* ... and a reconstruction it dropped: coded once more below, kept this time */
-                if (pc->has_ref) b->out_slots[nremedy++] = s;
-                b->recon_dropped[s] = 0;
+            for (k = s * R; t == 0 && k < s * R + R; k++) {     /* (every rung of the source) */
+                if (pc->has_ref && b->border_skipped[k]) {
+                    /* the batch before promised a GOP start here (border_hint) and the caller changed the frame numbering
+                     * in between (dsv1_batch_set_fnum): give the reference its whole border after all */
+                    if ((rc = dsvg_extend_recon(b->ctx, b->chains ? b->carry_cur : k + N * b->rpar[k]))) return rc;
+                }
+                b->border_skipped[k] = 0;
+                if (b->recon_dropped[k]) {
+                    /* ... and a reconstruction it dropped: coded once more below, kept this time */
+                    if (pc->has_ref) b->out_slots[nremedy++] = k;
+                    b->recon_dropped[k] = 0;
+                }
             }
             if (pc->has_ref) {
                 b->slots_cur[npairs] = pc->cur_slot;
                 b->slots_ref[npairs] = pc->ref_slot;
-                b->pair_pic[npairs] = s * F + t;
+                b->pair_pic[npairs] = s * R * F + t;
                 npairs++;
             }
+        }
+        for (r = 1; r < R; r++) {                           /* the other rungs follow the lead's decision state */
+            DSV_ENCODER *o = &b->enc[s * R + r];
+            o->next_fnum = e->next_fnum; o->prev_gop = e->prev_gop; o->force_metadata = e->force_metadata;
+            o->prev_avg_luma = e->prev_avg_luma; o->pyramid_levels = e->pyramid_levels;
         }
     }
     if (nremedy && (rc = remedy_dropped(b, nremedy, par))) return rc;
@@ -979,11 +1043,13 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
             memcpy(pics[b->pair_pic[k]].mvs, b->mv_tmp + (size_t)k * nblk, (size_t)nblk * sizeof(DSV_MV));
     }
     HP_MARK(HP_ANALYSE);
-    /* 4. per stream, in coding order: forced intra, stability + motion side info -> packet prefix */
+    /* 4. per source, in coding order: forced intra, stability + motion side info -> packet prefix */
     {
         side_ctx sc_;
         sc_.b = b; sc_.pics = pics;
         dsv1_par_for(S, side_stream, &sc_);
+        for (s = 0; s < S; s++)
+            for (r = 1; r < R; r++) b->enc[s * R + r].refresh_ctr = b->enc[s * R].refresh_ctr;
     }
     HP_MARK(HP_SIDEINFO);
     /* 5. residual coding, frame step by frame step across all streams */
@@ -1002,20 +1068,29 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
             else dsv1_par_for(S, prefix_stream, &sc_);
             if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
         }
+        /* every rung of a source codes the lead's picture: its decisions, slots and tables (the pointers: one copy of each table,
+         * and one device copy -- dsvg_code_batch keys on them); the out slot is the rung's own */
+        for (s = 0; s < S && R > 1; s++)
+            for (r = 1; r < R; r++)
+                for (t = 0; t < nf; t++) {
+                    pic_t *pc = &pics[(s * R + r) * F + t];
+                    *pc = pics[s * R * F + t];
+                    pc->out_slot += r;
+                }
         if (b->chains) {
             if ((rc = code_chains(b, pics, nf, par))) return rc;
         } else
         for (t = 0; t < nf; t++) {
-            for (s = 0; s < S; s++) {
+            for (s = 0; s < N; s++) {                           /* (s: an output stream from here on) */
                 pic_t *pc = &pics[s * F + t];
-                dsvg_pic_job *j = &b->jobs[(serial ? 0 : t * S) + s];
+                dsvg_pic_job *j = &b->jobs[(serial ? 0 : t * N) + s];
                 pc->quant = devrc ? 0 : pick_quant(&b->enc[s], pc->isP, pc->forced_intra);
-                if (devrc) { dsvg_rc_job *q = &b->rcjobs[t * S + s]; q->rc_slot = s; q->prefix_len = pc->prefix_len; q->forced_intra = pc->forced_intra; }
+                if (devrc) { dsvg_rc_job *q = &b->rcjobs[t * N + s]; q->rc_slot = s; q->prefix_len = pc->prefix_len; q->forced_intra = pc->forced_intra; }
                 j->src_slot = pc->cur_slot;
                 /* two reconstruction slots per stream, used alternately: a P picture's prediction is written straight
                  * into the slot its reconstruction will live in (the reference sits in the other one), so the inverse
                  * transform only touches the tiles that carry a residual (dsvg_code_batch) */
-                j->ref_recon_slot = pc->isP ? s + S * b->rpar[s] : -1;
+                j->ref_recon_slot = pc->isP ? s + N * b->rpar[s] : -1;
                 {
                     /* who predicts from this picture?  The stream's next one -- when it has a reference at all.  Nobody: no reconstruction
                      * (struct dsv1_batch, recon_dropped; the reference builds it and never looks at it, dsv_encoder.c:665-700) */
@@ -1030,7 +1105,7 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
                     if (pc->is_ref && !dead) {
                         b->rpar[s] ^= 1;
                         b->has_recon[s] = 1;
-                        j->recon_slot = s + S * b->rpar[s];
+                        j->recon_slot = s + N * b->rpar[s];
                     } else j->recon_slot = -1;
                 }
                 j->quant = pc->quant;
@@ -1047,34 +1122,34 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
                 if (t + 1 == nf) b->border_skipped[s] = (unsigned char)(j->border_hint && j->recon_slot >= 0);
             }
             if (serial) {
-                if ((rc = dsvg_code_pictures(b->ctx, S, b->jobs))) return rc;
-                for (s = 0; s < S; s++) b->out_slots[s] = pics[s * F + t].out_slot;
-                if ((rc = dsvg_fetch_pictures(b->ctx, S, b->out_slots, b->outs))) return rc;
-                for (s = 0; s < S; s++)
+                if ((rc = dsvg_code_pictures(b->ctx, N, b->jobs))) return rc;
+                for (s = 0; s < N; s++) b->out_slots[s] = pics[s * F + t].out_slot;
+                if ((rc = dsvg_fetch_pictures(b->ctx, N, b->out_slots, b->outs))) return rc;
+                for (s = 0; s < N; s++)
                     if ((rc = assemble(b, s, &pics[s * F + t], &b->outs[s], &abr_out[s], &b->sc0, NULL))) return rc;
             }
         }
         if (devrc) {
             if (!b->rc_seeded) {                                /* the device takes over the streams' rate-control state */
-                for (s = 0; s < S; s++) rc_load(&b->rc_dev[s], &b->enc[s]);
-                if ((rc = dsvg_rc_upload(b->ctx, 0, S, b->rc_dev))) return rc;
+                for (s = 0; s < N; s++) rc_load(&b->rc_dev[s], &b->enc[s]);
+                if ((rc = dsvg_rc_upload(b->ctx, 0, N, b->rc_dev))) return rc;
                 b->rc_seeded = 1;
             } else {
                 /* the caller may have changed a stream's parameters since (bitrate, quality bounds, max_q_step, the nudge: the reference reads
                  * them per frame, dsv_encoder.c:84-165): the pictures of THIS batch and later ones are coded with the new values -- the device's
                  * parameter fields are rewritten behind the batches already enqueued, the state fields stay the device's (advisor round 4) */
                 int s0 = -1, s1 = -1;
-                for (s = 0; s < S; s++) {
+                for (s = 0; s < N; s++) {
                     dsvg_rc_state now;
                     rc_load(&now, &b->enc[s]);
                     if (rc_par_differs(&now, &b->rc_dev[s])) { rc_par_set(&b->rc_dev[s], &now); if (s0 < 0) s0 = s; s1 = s; }
                 }
                 if (s0 >= 0 && (rc = dsvg_rc_set_params(b->ctx, s0, s1 - s0 + 1, b->rc_dev + s0))) return rc;
             }
-            memcpy(b->rc_par + (size_t)par * S, b->rc_dev, (size_t)S * sizeof(dsvg_rc_state));     /* what this batch's replay uses */
-            if ((rc = dsvg_code_batch_rc(b->ctx, nf, S, b->jobs, b->rcjobs))) return rc;
+            memcpy(b->rc_par + (size_t)par * N, b->rc_dev, (size_t)N * sizeof(dsvg_rc_state));     /* what this batch's replay uses */
+            if ((rc = dsvg_code_batch_rc(b->ctx, nf, N, b->jobs, b->rcjobs))) return rc;
         } else
-        if (!serial && !b->chains && (rc = dsvg_code_batch(b->ctx, nf, S, b->jobs))) return rc;   /* whole batch, one upload */
+        if (!serial && !b->chains && (rc = dsvg_code_batch(b->ctx, nf, N, b->jobs))) return rc;   /* whole batch, one upload */
         HP_MARK(HP_ENQUEUE);
         /* the bits of the packet prefixes: nobody waits for them before the packets are assembled, and the GPU is busy now */
 #ifdef AB_SYNC_PREFIX                                                 /* (A/B: tools/ab/variant.sh syncprefix host_dsv1_enc "" -DAB_SYNC_PREFIX) */
@@ -1089,7 +1164,7 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
             b->bg_sc[par] = sc_;
             b->bg_on[par] = 1;
             if (b->chains) dsv1_par_bg_begin(nf, prefix_picture, &b->bg_sc[par]);      /* (one stream: the pictures are the independent items) */
-            else dsv1_par_bg_begin(S, prefix_stream, &b->bg_sc[par]);      /* (one loop at a time: this joins the loop of the batch before, if it still runs) */
+            else dsv1_par_bg_begin(S, prefix_stream, &b->bg_sc[par]);      /* (per source; one loop at a time: this joins the loop of the batch before, if it still runs) */
             b->bg_on[par ^ 1] = 0;
         }
         if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
@@ -1111,7 +1186,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
     int rc;
     if (!b || !yuv_host) return DSVG_ERR_ARG;
     if (b->nstaged == 2) { dsv1_log(1, "two clips are staged already"); return DSVG_ERR_ARG; }
-    if ((rc = dsvg_ingest_begin(b->ctx, yuv_host, b->g.frame_bytes * (size_t)b->nstreams * (size_t)nf, &b->staged_dev[b->nstaged]))) return rc;
+    if ((rc = dsvg_ingest_begin(b->ctx, yuv_host, b->g.frame_bytes * (size_t)b->nsrc * (size_t)nf, &b->staged_dev[b->nstaged]))) return rc;
     b->staged_host[b->nstaged++] = yuv_host;
     return DSVG_OK;
 }
@@ -1569,7 +1644,7 @@ int dsv_enc(DSV_ENCODER *enc, DSV_FRAME *frame, DSV_BUF *bufs)
             ss->F = (int)want;
             ss->gathered = ss->F > 1;
         }
-        if ((rc = batch_open_on(&ss->b, enc, 0, dsv1_device, 1, ss->F, chains))) {
+        if ((rc = batch_open_on(&ss->b, enc, 0, dsv1_device, 1, 1, ss->F, chains))) {
             dsv1_log(1, "GPU session could not be opened: %s", dsvg_last_error());
             free(ss);
             dsv_frame_ref_dec(frame);

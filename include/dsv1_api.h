@@ -192,6 +192,18 @@ int  dsv1_batch_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int n
  * the frame-serial encoder's for every CRF configuration (dsv_encoder.c:345-399,538-552,624-653); ABR is refused.  Used
  * with dsv1_batch_encode / submit / collect / eos / close like a batch of one stream. */
 int  dsv1_stream_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int frames_per_call, int max_chains);
+/* QUALITY LADDER: nsources sources, each coded at nrungs rate settings (rungs[r], 1 <= nrungs <= DSV1_MAX_RUNGS) from ONE upload
+ * and ONE analysis.  Output stream k = s * nrungs + r is byte for byte the stream the reference encoder writes for source s with
+ * rungs[r].  The rungs must agree on everything the source-only analysis reads -- vidmeta, gop, do_scd, scene_change_delta,
+ * intra_pct_thresh, stable_refresh, pyramid_levels, rc_mode -- else DSVG_ERR_ARG before any device work; they may differ in the
+ * rate-control fields (quality, bitrate, max_q_step, min_ / max_quality, min_I_frame_quality, rc_high_motion_nudge).  Every
+ * dsv1_batch_* call works on a ladder: input (encode / submit / stage, every input form) is [source][frame], nsources x
+ * frames_per_call frames; output buffers, eos, recon_slot, get_sse / get_ssim (sse[(k * frames_per_call + t) * 3 + p]) and
+ * dsv1_batch_encoder are per output stream k.  dsv_enc_force_metadata on any rung starts a GOP on every rung of that source;
+ * dsv1_batch_set_fnum(b, k, n) renumbers every rung of k's source.  A plain batch is a ladder of one rung. */
+#define DSV1_MAX_RUNGS 16
+int  dsv1_ladder_open(dsv1_batch **out, const DSV_ENCODER *rungs, int nrungs, int device, int nsources, int frames_per_call);
+int  dsv1_batch_rungs(const dsv1_batch *b);   /* rungs per source: 1 for a plain batch */
 void dsv1_batch_close(dsv1_batch *b);
 void dsv1_batch_set_fnum(dsv1_batch *b, int stream, DSV_FNUM next_fnum);
 /* Round 5: reference pictures nobody predicts from are coded without their reconstruction (no inverse transform; the packets are the
