@@ -41,6 +41,11 @@ class Buf(_C.Structure):
     _fields_ = [("data", _C.POINTER(_C.c_uint8)), ("len", _C.c_uint)]
 
 
+class ResRung(_C.Structure):
+    """dsv1_res_rung: one geometry of a resolution ladder and its rate rungs"""
+    _fields_ = [("width", _C.c_int), ("height", _C.c_int), ("nrates", _C.c_int), ("rates", _C.POINTER(Encoder))]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -110,6 +115,28 @@ def lib():
         L.dsvg_prof_get.argtypes = [_C.c_void_p, _C.c_int, _C.POINTER(_C.c_double), _C.POINTER(_C.c_long),
                                     _C.POINTER(_C.c_double)]
         L.dsvg_prof_kernel_name.restype = _C.c_char_p
+        L.dsv1_scale_taps.argtypes = [_C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_scale_weights.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_int]
+        L.dsv1_scale_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int, _C.c_int,
+                                      _C.c_int, _C.c_int]
+        L.dsv1_resladder_open.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(ResRung), _C.c_int, _C.c_int, _C.c_int,
+                                          _C.c_int, _C.c_int]
+        L.dsv1_resladder_close.argtypes = [_C.c_void_p]
+        L.dsv1_resladder_close.restype = None
+        L.dsv1_resladder_nstreams.argtypes = [_C.c_void_p]
+        L.dsv1_resladder_batch.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_batch.restype = _C.c_void_p
+        L.dsv1_resladder_encoder.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_encoder.restype = _C.c_void_p
+        for f in ("encode", "submit"):
+            getattr(L, "dsv1_resladder_" + f).argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
+        L.dsv1_resladder_collect.argtypes = [_C.c_void_p, _C.POINTER(Buf)]
+        L.dsv1_resladder_eos.argtypes = [_C.c_void_p, _C.c_int, _C.POINTER(Buf)]
+        L.dsv1_resladder_sse_enable.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_ssim_enable.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_get_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
+        L.dsv1_resladder_get_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
+        L.dsv1_resladder_uploads.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.POINTER(_C.c_long)]
         _lib = L
     return _lib
 
@@ -459,6 +486,192 @@ class Ladder(Batch):
 
 
 MAX_RUNGS = 16   # DSV1_MAX_RUNGS
+MAX_GEOMS = 16   # DSV1_MAX_GEOMS
+SCALE_TENT, SCALE_CUBIC = 0, 1   # DSV1_SCALE_TENT, DSV1_SCALE_CUBIC
+
+
+def scale_taps(S, D, filt):
+    """taps of one axis of the resampler (dsv1_scale_taps); ValueError outside 1 <= S / D <= 8"""
+    t = lib().dsv1_scale_taps(S, D, filt)
+    if t < 0:
+        raise ValueError("no scale from %d to %d samples with filter %d" % (S, D, filt))
+    return t
+
+
+def scale_weights(S, D, filt):
+    """the resampler's weight table of one axis (dsv1_scale_weights, computed on the host): (start int32 [D], q int16 [D, T])"""
+    T = scale_taps(S, D, filt)
+    start = _np.zeros(D, dtype=_np.int32)
+    q = _np.zeros((D, T), dtype=_np.int16)
+    _chk(lib().dsv1_scale_weights(S, D, filt, start.ctypes.data, q.ctypes.data, T), "dsv1_scale_weights")
+    return start, q
+
+
+def scale_clip(clip, sw, sh, fmt, dw, dh, filt=SCALE_CUBIC, device=0, n=None, out=None):
+    """scale packed planar frames on the GPU (dsv1_scale_clip): clip numpy uint8 [frames][frame_bytes] (host), or a device pointer with
+    n frames and `out` a device pointer for the result.  Host input returns numpy uint8 [frames][scaled frame_bytes]."""
+    L = lib()
+    sfb = sw * sh + 2 * _chroma_size(sw, sh, fmt)
+    dfb = dw * dh + 2 * _chroma_size(dw, dh, fmt)
+    if n is not None:
+        _chk(L.dsv1_scale_clip(device, clip, sw, sh, fmt, n, out, dw, dh, filt, 1), "dsv1_scale_clip")
+        return out
+    a = _np.ascontiguousarray(clip, dtype=_np.uint8)
+    if a.size % sfb or not a.size:
+        raise ValueError("a clip of %dx%d frames is a whole number of %d-byte frames, got %d bytes" % (sw, sh, sfb, a.size))
+    frames = a.size // sfb
+    res = _np.zeros((frames, dfb), dtype=_np.uint8)
+    _chk(L.dsv1_scale_clip(device, a.ctypes.data, sw, sh, fmt, frames, res.ctypes.data, dw, dh, filt, 0), "dsv1_scale_clip")
+    return res
+
+
+class ResLadder:
+    """A resolution ladder (dsv1_resladder_open): nsources sources of w x h in format fmt, each scaled on the GPU to every geometry of
+    `geoms` and coded there at every rate rung.  geoms: list of (width, height, [Encoder cfg of that geometry, ...]).  Input is the
+    SOURCE clip [source][frame] (nsources x F frames of w x h: one upload per call); results are per output stream
+    k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
+
+    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0):
+        geoms = [(gw, gh, list(rates)) for gw, gh, rates in geoms]
+        self.L = lib()
+        self.h = _C.c_void_p(None)
+        self.width, self.height, self.fmt = w, h, fmt
+        self.nsources, self.F = nsources, frames_per_call
+        self.geoms = [(gw, gh, len(rates)) for gw, gh, rates in geoms]
+        self._arrs = [(Encoder * max(len(r), 1))(*r) for _, _, r in geoms]
+        rr = (ResRung * max(len(geoms), 1))(*[ResRung(gw, gh, len(r), a) for (gw, gh, r), a in zip(geoms, self._arrs)])
+        meta = Meta()
+        meta.width, meta.height, meta.subsamp = w, h, fmt
+        _chk(self.L.dsv1_resladder_open(_C.byref(self.h), _C.byref(meta), rr, len(geoms), device, nsources, frames_per_call, filt),
+             "dsv1_resladder_open")
+        self.ntot = sum(n for _, _, n in self.geoms)
+        self.nstreams = self.L.dsv1_resladder_nstreams(self.h)
+        self.frame_bytes = w * h + 2 * _chroma_size(w, h, fmt)
+        self.ctx = self.L.dsv1_batch_ctx(self.L.dsv1_resladder_batch(self.h, 0))
+        self._dev, self._pin, self._pending = [], [], []
+
+    def stream(self, source, geom, rate):
+        """output stream index k of (source, geometry, rate rung)"""
+        return source * self.ntot + sum(n for _, _, n in self.geoms[:geom]) + rate
+
+    def stream_dims(self, k):
+        """(width, height) of output stream k"""
+        o = k % self.ntot
+        for gw, gh, n in self.geoms:
+            if o < n:
+                return gw, gh
+            o -= n
+
+    def batch(self, g):
+        """geometry g's quality ladder handle (dsv1_resladder_batch)"""
+        return self.L.dsv1_resladder_batch(self.h, g)
+
+    def _input(self, yuv):
+        a = _np.ascontiguousarray(yuv, dtype=_np.uint8)
+        if a.size != self.nsources * self.F * self.frame_bytes:
+            raise ValueError("a resolution ladder call is %d sources x %d frames x %d bytes, got %d bytes" % (
+                self.nsources, self.F, self.frame_bytes, a.size))
+        return a
+
+    def _form(self, on_device, held):
+        return (2 if held else 1) if on_device else 0
+
+    def encode(self, yuv, on_device=False, eos=False):
+        bufs = (Buf * self.nstreams)()
+        a = None if on_device else self._input(yuv)
+        _chk(self.L.dsv1_resladder_encode(self.h, yuv if on_device else a.ctypes.data, self._form(on_device, False), bufs),
+             "dsv1_resladder_encode")
+        if eos:
+            for k in range(self.nstreams):
+                _chk(self.L.dsv1_resladder_eos(self.h, k, _C.byref(bufs[k])), "dsv1_resladder_eos")
+        return [_take(bufs[k]) for k in range(self.nstreams)]
+
+    def submit(self, yuv, on_device=False, held=False):
+        """enqueue one call (at most two in flight: submit(i+1); collect(i)); device clips as Batch.submit"""
+        a = None if on_device else self._input(yuv)
+        bufs = (Buf * self.nstreams)()
+        _chk(self.L.dsv1_resladder_submit(self.h, yuv if on_device else a.ctypes.data, self._form(on_device, held), bufs),
+             "dsv1_resladder_submit")
+        self._pending.append((bufs, a))
+
+    def collect(self):
+        bufs, _ = self._pending.pop(0)
+        _chk(self.L.dsv1_resladder_collect(self.h, bufs), "dsv1_resladder_collect")
+        return [_take(bufs[k]) for k in range(self.nstreams)]
+
+    def eos(self, k):
+        b = Buf()
+        _chk(self.L.dsv1_resladder_eos(self.h, k, _C.byref(b)), "dsv1_resladder_eos")
+        return _take(b)
+
+    def encoder(self, k):
+        p = self.L.dsv1_resladder_encoder(self.h, k)
+        if not p:
+            raise IndexError("no stream %d" % k)
+        return Encoder.from_address(p)
+
+    def sse_enable(self, on=True):
+        _chk(self.L.dsv1_resladder_sse_enable(self.h, 1 if on else 0), "dsv1_resladder_sse_enable")
+
+    def ssim_enable(self, on=True):
+        _chk(self.L.dsv1_resladder_ssim_enable(self.h, 1 if on else 0), "dsv1_resladder_ssim_enable")
+
+    def sse(self):
+        """numpy.uint64 [nstreams, F, 3] of the call collected last (against each stream's scaled source)"""
+        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.uint64)
+        _chk(self.L.dsv1_resladder_get_sse(self.h, out.ctypes.data_as(_C.POINTER(_C.c_uint64)), out.size), "dsv1_resladder_get_sse")
+        return out
+
+    def ssim_fx(self):
+        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.int64)
+        _chk(self.L.dsv1_resladder_get_ssim(self.h, out.ctypes.data_as(_C.POINTER(_C.c_int64)), out.size), "dsv1_resladder_get_ssim")
+        return out
+
+    def psnr(self):
+        """float64 [nstreams, F, 4] in dB, each stream at its own geometry"""
+        e = self.sse()
+        return _np.stack([psnr_db(e[k], *self.stream_dims(k), self.fmt) for k in range(self.nstreams)])
+
+    def ssim(self):
+        """mean SSIM float64 [nstreams, F, 4], each stream at its own geometry"""
+        f = self.ssim_fx()
+        return _np.stack([ssim_mean(f[k], *self.stream_dims(k), self.fmt) for k in range(self.nstreams)])
+
+    def code_streams(self, n=0):
+        """set (n >= 1) / query (n = 0) the coding streams of every geometry's ladder; returns the previous value of geometry 0's"""
+        prev = [self.L.dsvg_ctx_code_streams(self.L.dsv1_batch_ctx(self.batch(g)), n) for g in range(len(self.geoms))]
+        return prev[0]
+
+    def uploads(self):
+        """(bytes, calls) the resladder uploaded itself (host input: one source clip per call)"""
+        b, c = _C.c_uint64(0), _C.c_long(0)
+        _chk(self.L.dsv1_resladder_uploads(self.h, _C.byref(b), _C.byref(c)), "dsv1_resladder_uploads")
+        return b.value, c.value
+
+    def upload(self, clip):
+        """a raw source clip resident in HBM (device pointer)"""
+        return Batch.upload(self, clip)
+
+    def pinned(self, shape):
+        return Batch.pinned(self, shape)
+
+    def close(self):
+        if self.h:
+            self.L.dsvg_ctx_sync(self.ctx)
+            for p in self._dev:
+                self.L.dsvg_dev_free(self.ctx, p)
+            self._dev = []
+            for p in self._pin:
+                self.L.dsvg_host_free(self.ctx, p)
+            self._pin = []
+            self.L.dsv1_resladder_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class DecBatch:
@@ -641,6 +854,19 @@ def encode_ladder(clip, w, h, fmt, rungs, device=0, eos=True, **cli):
     each byte for byte the stream the serial encoder writes with that rung's settings"""
     n = clip.shape[0]
     b = Ladder([make_encoder_cfg(w, h, fmt, **dict(cli, **r)) for r in rungs], 1, n, device)
+    try:
+        return b.encode(clip.reshape(1, n, -1), eos=eos)
+    finally:
+        b.close()
+
+
+def encode_resolution_ladder(clip, w, h, fmt, rungs, filt=SCALE_CUBIC, device=0, eos=True, **cli):
+    """one source coded at several geometries and rates in one call: clip [frames][frame_bytes] of w x h; rungs: a list of
+    dict(w=, h=, rates=[dict of make_encoder_cfg arguments overriding `cli`, ...]) -> one .dsv bytes object per (geometry, rate), in
+    that order, each the stream the serial encoder writes for the clip scaled to that geometry (scale_clip)"""
+    n = clip.shape[0]
+    geoms = [(r["w"], r["h"], [make_encoder_cfg(r["w"], r["h"], fmt, **dict(cli, **q)) for q in r["rates"]]) for r in rungs]
+    b = ResLadder(w, h, fmt, geoms, 1, n, filt, device)
     try:
         return b.encode(clip.reshape(1, n, -1), eos=eos)
     finally:

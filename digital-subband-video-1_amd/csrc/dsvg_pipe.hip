@@ -460,6 +460,31 @@ template <typename T> static int hmalloc(T **p, size_t n)
 
 extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int height, int subsamp,
                                    int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots, int blk_w, int blk_h);
+// What dsvg_ctx_create (encoder block size) answers for a geometry, without a device: the resolution ladder refuses a geometry before
+// it allocates anything (dsv1_resladder_open).  The same checks, in the same order, as the context creation below.
+extern "C" int dsvg_geom_check(int width, int height, int subsamp)
+{
+    if (width < 32 || height < 32) { dsvg_set_error("bad ctx_create arguments"); return DSVG_ERR_ARG; }
+    if (subsamp != 0x0 && subsamp != 0x4 && subsamp != 0x5 && subsamp != 0x8) { dsvg_set_error("bad subsampling"); return DSVG_ERR_ARG; }
+    int bw, bh, nbh, nbv;
+    block_geometry(width, height, &bw, &bh, &nbh, &nbv);
+    FrameLayout L;
+    CoefLayout CL;
+    make_frame_layout(L, subsamp, width, height);
+    make_coef_layout(CL, subsamp, width, height);
+    for (int p = 0; p < 3; p++) {
+        SbtGeo g;
+        make_sbt_geo(g, CL.w[p], CL.h[p], L.w[p], L.h[p], L.stride[p], L.off[p], CL.off[p], CL.s3off[p], CL.s1off[p], CL.s5off[p]);
+        if (!sbt_tail_supported(g)) { dsvg_set_error("plane %dx%d: LL5 band does not fit the LDS tail kernel", CL.w[p], CL.h[p]); return DSVG_ERR_UNSUPPORTED; }
+    }
+    if ((width | height) & 1) { dsvg_set_error("odd luma dimensions are not supported (intra B4T needs even planes)"); return DSVG_ERR_UNSUPPORTED; }
+    for (int p = 0; p < 3; p++) {
+        HzPlane hp; make_hz_plane(hp, CL.w[p], CL.h[p], 100, 0, p, nbh, nbv);
+        if (hp.nchunks > hz_scan_items_max()) { dsvg_set_error("plane too large for the scan kernel"); return DSVG_ERR_UNSUPPORTED; }
+    }
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_ctx_create(dsvg_ctx **out, int device, int width, int height, int subsamp,
                                int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots)
 {
@@ -777,6 +802,14 @@ static int join_pack(dsvg_ctx *c)
     return DSVG_OK;
 }
 extern "C" void *dsvg_ctx_stream(dsvg_ctx *c) { return c && join_pack(c) == DSVG_OK ? (void *)c->st : nullptr; }
+// the frame-load stream waits, on the device, for a HIP event of the caller's (the resolution ladder's scale of this context's frames)
+extern "C" int dsvg_ctx_load_wait(dsvg_ctx *c, void *event)
+{
+    if (!c || !event) { dsvg_set_error("bad load_wait arguments"); return DSVG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamWaitEvent(c->st_l, (hipEvent_t)event, 0));
+    return DSVG_OK;
+}
 extern "C" int dsvg_ctx_join(dsvg_ctx *c, void *stream)
 {
     if (!c) { dsvg_set_error("no context"); return DSVG_ERR_ARG; }

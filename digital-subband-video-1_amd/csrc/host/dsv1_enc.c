@@ -296,7 +296,7 @@ int dsv1_batch_open(dsv1_batch **out, const DSV_ENCODER *cfg, int device, int ns
 }
 
 /* the fields the source-only analysis reads: every rung of a ladder must agree on them */
-static int ladder_rungs_agree(const DSV_ENCODER *a, const DSV_ENCODER *b)
+int dsv1_ladder_rungs_agree(const DSV_ENCODER *a, const DSV_ENCODER *b)
 {
     return !memcmp(&a->vidmeta, &b->vidmeta, sizeof(DSV_META)) && a->gop == b->gop && a->do_scd == b->do_scd &&
            a->scene_change_delta == b->scene_change_delta && a->intra_pct_thresh == b->intra_pct_thresh &&
@@ -310,7 +310,7 @@ int dsv1_ladder_open(dsv1_batch **out, const DSV_ENCODER *rungs, int nrungs, int
     if (!out || !rungs || nrungs < 1 || nrungs > DSV1_MAX_RUNGS || nsources < 1 || nsources > INT_MAX / DSV1_MAX_RUNGS || frames_per_call < 1) return DSVG_ERR_ARG;
     n = nsources * nrungs;
     for (r = 1; r < nrungs; r++)
-        if (!ladder_rungs_agree(&rungs[0], &rungs[r])) {
+        if (!dsv1_ladder_rungs_agree(&rungs[0], &rungs[r])) {
             dsv1_log(1, "dsv1_ladder_open: rung %d differs from rung 0 in a field the analysis reads (geometry, GOP, scene cuts, intra / stability thresholds, pyramid, rate-control mode)", r);
             return DSVG_ERR_ARG;
         }

@@ -103,6 +103,23 @@ int dsv1_par_bg_pending(void);
 /* the default size of that pool as a function of the host (dsv1_util.c); exported so that the rule can be tested without the host it is for */
 int dsv1_host_threads_rule(long online, long allowed, long ranks, int pinned_by_launcher);
 
+/* dsv1_enc.c: the fields every rung of a quality ladder must agree on (dsv1_ladder_open) */
+int dsv1_ladder_rungs_agree(const DSV_ENCODER *a, const DSV_ENCODER *b);
+/* dsvg_pipe.hip: what dsvg_ctx_create would answer for the geometry, without a device (DSVG_OK, DSVG_ERR_ARG, DSVG_ERR_UNSUPPORTED) */
+int dsvg_geom_check(int width, int height, int subsamp);
+/* k_scale.hip: the device side of the resampler.  A scaler holds the weight tables of ngeom destination geometries of one source
+ * geometry (uploaded once), a stream of its own and two upload buffers; _order makes a context's frame-load stream wait, on the
+ * device, for everything enqueued on the scaler so far. */
+typedef struct dsvg_scaler dsvg_scaler;
+int  dsvg_scaler_create(dsvg_scaler **out, int device, int sw, int sh, int subsamp, int ngeom, const int *dw, const int *dh, int filter);
+void dsvg_scaler_destroy(dsvg_scaler *s);
+int  dsvg_scaler_upload(dsvg_scaler *s, int buf, const void *host, size_t bytes, void **dptr);
+int  dsvg_scaler_run(dsvg_scaler *s, int g, const void *src_dev, int nframes, void *dst_dev);
+int  dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx);
+int  dsvg_scaler_sync(dsvg_scaler *s);
+int  dsvg_scaler_alloc(dsvg_scaler *s, void **dptr, size_t bytes);
+int  dsvg_scaler_download(dsvg_scaler *s, void *host, const void *dptr, size_t bytes);
+
 #define CLAMPI(v, lo, hi) ((v) < (lo) ? (lo) : ((v) > (hi) ? (hi) : (v)))
 
 #endif

@@ -1,0 +1,361 @@
+/* dsv1_scale.c -- the resampler's weight tables, the standalone scaler and resolution ladders (include/dsv1_api.h).
+ *
+ * The weight tables are the definition of the scaler (tests/_scale.py states the same in numpy): binary64, the order written
+ * below, no contraction -- the Makefile compiles this file with -ffp-contract=off (gcc does not implement the STDC FP_CONTRACT
+ * pragma), and tests/test_scale_host.py checks the object for fused multiply-adds and the tables against numpy.
+ *
+ * A resolution ladder is one quality ladder (dsv1_ladder_open) per geometry plus a scaler (k_scale.hip).  A call uploads the source
+ * clip once on the scaler's stream, scales it there for every geometry whose size differs from the source's, and makes each
+ * geometry's frame-load stream wait for that on the device (dsvg_scaler_order) before the geometry's submit; the scaled clips go to
+ * the ladders as held device clips (DSV1_CLIP_HELD), one buffer per geometry and call parity, which the next submit of the same
+ * parity -- after that geometry's collect -- overwrites. */
+#include <math.h>
+#include "dsv1_host.h"
+
+int dsv1_scale_taps(int S, int D, int filter)
+{
+    const long long sup = filter == DSV1_SCALE_TENT ? 1 : filter == DSV1_SCALE_CUBIC ? 2 : 0;
+    if (!sup || D < 1 || S < D || (long long)S > 8LL * D) return DSVG_ERR_ARG;
+    return (int)(2 * ((sup * S + D - 1) / D) + 2);
+}
+
+static double scale_kernel(double x, int filter)
+{
+    if (filter == DSV1_SCALE_TENT) return x < 1.0 ? 1.0 - x : 0.0;       /* max(0, 1 - x) */
+    if (x < 1.0) return ((1.5 * x - 2.5) * x) * x + 1.0;
+    if (x < 2.0) return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
+    return 0.0;
+}
+
+int dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T)
+{
+    double w[2 * (2 * 8 + 1) + 2];                                      /* T <= 2 ceil(2 * 8) + 2 = 34 */
+    const int Tn = dsv1_scale_taps(S, D, filter);
+    int i, t;
+    if (Tn < 0 || T != Tn || !start || !q) return DSVG_ERR_ARG;
+    for (i = 0; i < D; i++) {
+        const double c = (double)((2LL * i + 1) * S - D) / (double)(2LL * D);
+        const double inv = (double)D / (double)S;
+        const long long j0 = (long long)floor(c) - (T - 2) / 2;
+        double sum = 0.0;
+        int s = 0, best = 0;
+        for (t = 0; t < T; t++) {
+            const double x = fabs(((double)(j0 + t) - c) * inv);
+            w[t] = scale_kernel(x, filter);
+            sum += w[t];
+        }
+        for (t = 0; t < T; t++) {
+            const int v = (int)rint(w[t] * 16384.0 / sum);             /* round half to even (the default rounding mode) */
+            q[(size_t)i * T + t] = (int16_t)v;
+            s += v;
+            if (v > q[(size_t)i * T + best]) best = t;
+        }
+        q[(size_t)i * T + best] = (int16_t)(q[(size_t)i * T + best] + 16384 - s);
+        start[i] = (int32_t)j0;
+    }
+    return DSVG_OK;
+}
+
+/* every axis of every plane within the ratio limits: DSVG_OK or DSVG_ERR_ARG */
+static int scale_dims_ok(int sw, int sh, int fmt, int dw, int dh, int filter)
+{
+    const int hs = (fmt >> 2) & 3, vs = fmt & 3;
+    if (fmt != DSV_SUBSAMP_444 && fmt != DSV_SUBSAMP_422 && fmt != DSV_SUBSAMP_420 && fmt != DSV_SUBSAMP_411) return DSVG_ERR_ARG;
+    if (dsv1_scale_taps(sw, dw, filter) < 0 || dsv1_scale_taps(sh, dh, filter) < 0) return DSVG_ERR_ARG;
+    if (dsv1_scale_taps((sw + (1 << hs) - 1) >> hs, (dw + (1 << hs) - 1) >> hs, filter) < 0) return DSVG_ERR_ARG;
+    if (dsv1_scale_taps((sh + (1 << vs) - 1) >> vs, (dh + (1 << vs) - 1) >> vs, filter) < 0) return DSVG_ERR_ARG;
+    return DSVG_OK;
+}
+
+static size_t frame_bytes_of(int w, int h, int fmt)
+{
+    const int hs = (fmt >> 2) & 3, vs = fmt & 3;
+    return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
+}
+
+int dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter, int on_device)
+{
+    dsvg_scaler *sc = NULL;
+    void *dsrc = NULL, *ddst = NULL;
+    const size_t sfb = frame_bytes_of(sw, sh, subsamp), dfb = frame_bytes_of(dw, dh, subsamp);
+    int rc;
+    if (!src || !dst || n < 1 || device < 0 || sw < 1 || sh < 1) return DSVG_ERR_ARG;
+    if ((rc = scale_dims_ok(sw, sh, subsamp, dw, dh, filter))) return rc;
+    if ((rc = dsvg_scaler_create(&sc, device, sw, sh, subsamp, 1, &dw, &dh, filter))) return rc;
+    if (on_device) rc = dsvg_scaler_run(sc, 0, src, n, dst);
+    else {
+        rc = dsvg_scaler_upload(sc, 0, src, sfb * (size_t)n, &dsrc);
+        if (!rc) rc = dsvg_scaler_alloc(sc, &ddst, dfb * (size_t)n);
+        if (!rc) rc = dsvg_scaler_run(sc, 0, dsrc, n, ddst);
+        if (!rc) rc = dsvg_scaler_download(sc, dst, ddst, dfb * (size_t)n);
+    }
+    if (!rc) rc = dsvg_scaler_sync(sc);
+    dsvg_scaler_destroy(sc);                            /* (frees ddst: the scaler owns what it allocated) */
+    return rc;
+}
+
+/* ---- resolution ladders ------------------------------------------------------------------------------------------------- */
+struct dsv1_resladder {
+    int ngeom, nsrc, F, ntot;
+    int w[DSV1_MAX_GEOMS], h[DSV1_MAX_GEOMS], nr[DSV1_MAX_GEOMS], off[DSV1_MAX_GEOMS + 1];
+    int same[DSV1_MAX_GEOMS];           /* geometry of the source's size: fed the source itself, no scale */
+    size_t sfb, gfb[DSV1_MAX_GEOMS];
+    dsv1_batch *lad[DSV1_MAX_GEOMS];
+    dsvg_scaler *sc;
+    int scale_idx[DSV1_MAX_GEOMS];      /* the scaler's table of geometry g (-1: same size) */
+    void *clip[DSV1_MAX_GEOMS][2];      /* scaled clips, per call parity */
+    int parity, pending[2];
+    DSV_BUF *tmp;                       /* [max nsrc * nrates]: a geometry's view of the caller's output buffers */
+    uint64_t up_bytes;
+    long up_calls;
+    uint64_t *sse;
+    int64_t *ssim;
+    size_t sse_n, ssim_n;
+};
+
+void dsv1_resladder_close(dsv1_resladder *r)
+{
+    int g;
+    if (!r) return;
+    for (g = 0; g < r->ngeom; g++) dsv1_batch_close(r->lad[g]);
+    dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated) */
+    free(r->tmp); free(r->sse); free(r->ssim);
+    free(r);
+}
+
+int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
+                        int frames_per_call, int filter)
+{
+    dsv1_resladder *r;
+    int g, k, rc, ntot = 0, nscaled = 0, maxr = 0, dw[DSV1_MAX_GEOMS], dh[DSV1_MAX_GEOMS];
+    if (out) *out = NULL;
+    /* arguments first: nothing below touches a device until every geometry has passed */
+    if (!out || !src || !rungs || ngeoms < 1 || ngeoms > DSV1_MAX_GEOMS || nsources < 1 || frames_per_call < 1) return DSVG_ERR_ARG;
+    if (filter != DSV1_SCALE_TENT && filter != DSV1_SCALE_CUBIC) return DSVG_ERR_ARG;
+    if (src->width < 1 || src->height < 1) return DSVG_ERR_ARG;
+    for (g = 0; g < ngeoms; g++) {
+        const dsv1_res_rung *G = &rungs[g];
+        if (!G->rates || G->nrates < 1 || G->nrates > DSV1_MAX_RUNGS) {
+            dsv1_log(1, "dsv1_resladder_open: geometry %d needs 1 to %d rate rungs", g, DSV1_MAX_RUNGS);
+            return DSVG_ERR_ARG;
+        }
+        if (scale_dims_ok(src->width, src->height, src->subsamp, G->width, G->height, filter)) {
+            dsv1_log(1, "dsv1_resladder_open: geometry %d (%dx%d) is not a downscale of %dx%d by at most 8 on every axis and plane", g, G->width,
+                     G->height, src->width, src->height);
+            return DSVG_ERR_ARG;
+        }
+        for (k = 0; k < G->nrates; k++) {
+            const DSV_META *m = &G->rates[k].vidmeta;
+            if (m->width != G->width || m->height != G->height || m->subsamp != src->subsamp) {
+                dsv1_log(1, "dsv1_resladder_open: rate rung %d of geometry %d is not %dx%d in the source's format", k, g, G->width, G->height);
+                return DSVG_ERR_ARG;
+            }
+            if (k && !dsv1_ladder_rungs_agree(&G->rates[0], &G->rates[k])) {
+                dsv1_log(1, "dsv1_resladder_open: rate rung %d of geometry %d differs from its rung 0 in a field the analysis reads", k, g);
+                return DSVG_ERR_ARG;
+            }
+        }
+        ntot += G->nrates;
+        if (G->nrates > maxr) maxr = G->nrates;
+    }
+    if (nsources > INT_MAX / ntot / frames_per_call / 3) return DSVG_ERR_ARG;
+    for (g = 0; g < ngeoms; g++)
+        if ((rc = dsvg_geom_check(rungs[g].width, rungs[g].height, src->subsamp))) {
+            dsv1_log(1, "dsv1_resladder_open: geometry %d (%dx%d) is one the encoder does not take", g, rungs[g].width, rungs[g].height);
+            return rc;
+        }
+    r = (dsv1_resladder *)calloc(1, sizeof(*r));
+    if (!r) return DSVG_ERR_NOMEM;
+    r->ngeom = ngeoms; r->nsrc = nsources; r->F = frames_per_call; r->ntot = ntot;
+    r->sfb = frame_bytes_of(src->width, src->height, src->subsamp);
+    r->tmp = (DSV_BUF *)calloc((size_t)nsources * maxr, sizeof(DSV_BUF));
+    r->sse = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
+    r->ssim = (int64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(int64_t));
+    if (!r->tmp || !r->sse || !r->ssim) { dsv1_resladder_close(r); return DSVG_ERR_NOMEM; }
+    for (g = 0; g < ngeoms; g++) {
+        r->w[g] = rungs[g].width; r->h[g] = rungs[g].height; r->nr[g] = rungs[g].nrates;
+        r->off[g + 1] = r->off[g] + rungs[g].nrates;
+        r->gfb[g] = frame_bytes_of(r->w[g], r->h[g], src->subsamp);
+        r->same[g] = r->w[g] == src->width && r->h[g] == src->height;
+        r->scale_idx[g] = -1;
+        if (!r->same[g]) { r->scale_idx[g] = nscaled; dw[nscaled] = r->w[g]; dh[nscaled] = r->h[g]; nscaled++; }
+    }
+    /* the scaler exists even when no geometry is scaled: host input is uploaded through it */
+    if ((rc = dsvg_scaler_create(&r->sc, device, src->width, src->height, src->subsamp, nscaled, dw, dh, filter))) { dsv1_resladder_close(r); return rc; }
+    for (g = 0; g < ngeoms; g++) {
+        if ((rc = dsv1_ladder_open(&r->lad[g], rungs[g].rates, rungs[g].nrates, device, nsources, frames_per_call))) break;
+        r->ngeom = g + 1;
+        if (!r->same[g])
+            for (k = 0; k < 2 && !rc; k++) rc = dsvg_scaler_alloc(r->sc, &r->clip[g][k], r->gfb[g] * (size_t)nsources * frames_per_call);
+        if (rc) break;
+    }
+    if (rc) { r->ngeom = g + (g < ngeoms && r->lad[g] ? 1 : 0); dsv1_resladder_close(r); return rc; }
+    *out = r;
+    return DSVG_OK;
+}
+
+int dsv1_resladder_nstreams(const dsv1_resladder *r) { return r ? r->nsrc * r->ntot : DSVG_ERR_ARG; }
+dsv1_batch *dsv1_resladder_batch(dsv1_resladder *r, int g) { return r && g >= 0 && g < r->ngeom ? r->lad[g] : NULL; }
+
+/* output stream k -> (geometry, that ladder's stream) */
+static int res_split(const dsv1_resladder *r, int k, int *kg)
+{
+    int s, o, g;
+    if (!r || k < 0 || k >= r->nsrc * r->ntot) return -1;
+    s = k / r->ntot; o = k % r->ntot;
+    for (g = 0; o >= r->off[g + 1]; g++) ;
+    *kg = s * r->nr[g] + (o - r->off[g]);
+    return g;
+}
+
+DSV_ENCODER *dsv1_resladder_encoder(dsv1_resladder *r, int k)
+{
+    int kg, g = res_split(r, k, &kg);
+    return g < 0 ? NULL : dsv1_batch_encoder(r->lad[g], kg);
+}
+
+int dsv1_resladder_eos(dsv1_resladder *r, int k, DSV_BUF *out)
+{
+    int kg, g = res_split(r, k, &kg);
+    if (g < 0 || !out) return DSVG_ERR_ARG;
+    return dsv1_batch_eos(r->lad[g], kg, out);
+}
+
+/* geometry g's view of the caller's buffers (out[s * Ntot + off[g] + rate]) into r->tmp, and back */
+static void view_in(dsv1_resladder *r, int g, DSV_BUF *out)
+{
+    int s, q;
+    for (s = 0; s < r->nsrc; s++)
+        for (q = 0; q < r->nr[g]; q++) r->tmp[s * r->nr[g] + q] = out[s * r->ntot + r->off[g] + q];
+}
+static void view_out(dsv1_resladder *r, int g, DSV_BUF *out)
+{
+    int s, q;
+    for (s = 0; s < r->nsrc; s++)
+        for (q = 0; q < r->nr[g]; q++) out[s * r->ntot + r->off[g] + q] = r->tmp[s * r->nr[g] + q];
+}
+
+int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out)
+{
+    const uint8_t *dsrc = (const uint8_t *)yuv;
+    const int nfr = r ? r->nsrc * r->F : 0;
+    int g, rc, par;
+    if (!r || !yuv || !out || yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
+    par = r->parity;
+    if (r->pending[par]) { dsv1_log(1, "resolution ladder submitted twice without collect"); return DSVG_ERR_ARG; }
+    if (!yuv_on_device) {
+        /* the source crosses the link once, on the scaler's stream; its buffer (per parity) is held until this call's collect: a
+         * geometry of the source's size reads it in place */
+        void *d;
+        const size_t bytes = r->sfb * (size_t)nfr;
+        if ((rc = dsvg_scaler_upload(r->sc, par, yuv, bytes, &d))) return rc;
+        r->up_bytes += bytes;
+        r->up_calls++;
+        dsrc = (const uint8_t *)d;
+    }
+    for (g = 0; g < r->ngeom; g++) {
+        const void *clip = dsrc;
+        int form = yuv_on_device ? yuv_on_device : DSV1_CLIP_HELD;
+        if (!r->same[g]) {
+            if ((rc = dsvg_scaler_run(r->sc, r->scale_idx[g], dsrc, nfr, r->clip[g][par]))) return rc;
+            clip = r->clip[g][par];
+            form = DSV1_CLIP_HELD;
+        }
+        if ((rc = dsvg_scaler_order(r->sc, (dsvg_ctx *)dsv1_batch_ctx(r->lad[g])))) return rc;
+        view_in(r, g, out);
+        rc = dsv1_batch_submit(r->lad[g], clip, form, r->tmp);
+        view_out(r, g, out);
+        if (rc) return rc;
+    }
+    /* a plain device clip is the caller's again when submit returns: the scales that read it must have run */
+    if (yuv_on_device == 1 && (rc = dsvg_scaler_sync(r->sc))) return rc;
+    r->pending[par] = 1;
+    r->parity ^= 1;
+    return DSVG_OK;
+}
+
+int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)
+{
+    int g, par, s, q, t, rc;
+    size_t n;
+    if (!r || !out) return DSVG_ERR_ARG;
+    par = r->pending[r->parity] ? r->parity : (r->parity ^ 1);      /* oldest first */
+    if (!r->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
+    r->pending[par] = 0;
+    r->sse_n = r->ssim_n = 0;
+    for (g = 0; g < r->ngeom; g++) {
+        const size_t per = (size_t)3 * r->F;
+        view_in(r, g, out);
+        rc = dsv1_batch_collect(r->lad[g], r->tmp);
+        view_out(r, g, out);
+        if (rc) return rc;
+        n = (size_t)r->nsrc * r->nr[g] * per;
+        /* the geometry's figures [s * nr + q][t][p] go to [s * Ntot + off + q][t][p] (a ladder measured ... or not) */
+        {
+            uint64_t *tmp = (uint64_t *)malloc(sizeof(uint64_t) * n);
+            int64_t *tmp2 = (int64_t *)malloc(sizeof(int64_t) * n);
+            int have_sse, have_ssim;
+            if (!tmp || !tmp2) { free(tmp); free(tmp2); return DSVG_ERR_NOMEM; }
+            have_sse = dsv1_batch_get_sse(r->lad[g], tmp, n) == DSVG_OK;
+            have_ssim = dsv1_batch_get_ssim(r->lad[g], tmp2, n) == DSVG_OK;
+            for (s = 0; s < r->nsrc; s++)
+                for (q = 0; q < r->nr[g]; q++)
+                    for (t = 0; t < (int)per; t++) {
+                        const size_t from = (size_t)(s * r->nr[g] + q) * per + t, to = (size_t)(s * r->ntot + r->off[g] + q) * per + t;
+                        if (have_sse) r->sse[to] = tmp[from];
+                        if (have_ssim) r->ssim[to] = tmp2[from];
+                    }
+            free(tmp); free(tmp2);
+            if (g == 0) { r->sse_n = have_sse; r->ssim_n = have_ssim; }
+            else { r->sse_n &= (size_t)have_sse; r->ssim_n &= (size_t)have_ssim; }
+        }
+    }
+    if (r->sse_n) r->sse_n = (size_t)3 * r->nsrc * r->ntot * r->F;
+    if (r->ssim_n) r->ssim_n = (size_t)3 * r->nsrc * r->ntot * r->F;
+    return DSVG_OK;
+}
+
+int dsv1_resladder_encode(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out)
+{
+    int rc;
+    if (!r || !out) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_encode with calls in flight"); return DSVG_ERR_ARG; }
+    if ((rc = dsv1_resladder_submit(r, yuv, yuv_on_device, out))) return rc;
+    return dsv1_resladder_collect(r, out);
+}
+
+int dsv1_resladder_sse_enable(dsv1_resladder *r, int on)
+{
+    int g, rc;
+    if (!r) return DSVG_ERR_ARG;
+    for (g = 0; g < r->ngeom; g++)
+        if ((rc = dsv1_batch_sse_enable(r->lad[g], on))) return rc;
+    return DSVG_OK;
+}
+int dsv1_resladder_ssim_enable(dsv1_resladder *r, int on)
+{
+    int g, rc;
+    if (!r) return DSVG_ERR_ARG;
+    for (g = 0; g < r->ngeom; g++)
+        if ((rc = dsv1_batch_ssim_enable(r->lad[g], on))) return rc;
+    return DSVG_OK;
+}
+int dsv1_resladder_get_sse(const dsv1_resladder *r, uint64_t *sse, size_t n)
+{
+    if (!r || !sse || !r->sse_n || n < r->sse_n) { dsv1_log(1, "dsv1_resladder_get_sse: nothing measured, or no room"); return DSVG_ERR_ARG; }
+    memcpy(sse, r->sse, sizeof(uint64_t) * r->sse_n);
+    return DSVG_OK;
+}
+int dsv1_resladder_get_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n)
+{
+    if (!r || !ssim_fx || !r->ssim_n || n < r->ssim_n) { dsv1_log(1, "dsv1_resladder_get_ssim: nothing measured, or no room"); return DSVG_ERR_ARG; }
+    memcpy(ssim_fx, r->ssim, sizeof(int64_t) * r->ssim_n);
+    return DSVG_OK;
+}
+int dsv1_resladder_uploads(const dsv1_resladder *r, uint64_t *bytes, long *calls)
+{
+    if (!r) return DSVG_ERR_ARG;
+    if (bytes) *bytes = r->up_bytes;
+    if (calls) *calls = r->up_calls;
+    return DSVG_OK;
+}

@@ -280,6 +280,59 @@ void *dsv1_batch_ctx(dsv1_batch *b);          /* the dsvg_ctx* (profiling hooks)
  * for dsvg_download_recon / dsvg_download_recon_raw; -1 if the stream has none yet */
 int   dsv1_batch_recon_slot(const dsv1_batch *b, int stream);
 
+/* ---- extension: the resampler of resolution ladders (csrc/k_scale.hip; stated in numpy in tests/_scale.py) ----
+ * Downscale or identity: on each axis of each plane 1 <= S / D <= 8 (S source length, D destination length); every plane is scaled
+ * on its own, from the source's chroma dims to the destination's (rshift_up); the format is kept.  Centre-aligned sample grids;
+ * chroma siting is not modelled.  Filters, stretched by S / D (anti-aliasing): DSV1_SCALE_TENT (linear, support 1) and
+ * DSV1_SCALE_CUBIC (Catmull-Rom, a = -0.5, support 2).  Weight table of one axis: output sample i reads the T = 2 ceil(support S / D)
+ * + 2 source samples start[i] .. start[i] + T - 1 (clamped to [0, S - 1]) with the integer weights q[i * T + t], which sum to 16384;
+ * built in binary64 in a fixed order, no contraction (dsv1_scale.c).  Arithmetic, horizontal pass first: H = sum qh P (int32),
+ * Hs = (H + 128) >> 8; V = sum qv Hs (int32); out = clamp((V + 2^19) >> 20, 0, 255).  S == D is the identity for both filters. */
+#define DSV1_SCALE_TENT  0
+#define DSV1_SCALE_CUBIC 1
+int  dsv1_scale_taps(int S, int D, int filter);              /* T of an axis, or DSVG_ERR_ARG outside the limits */
+int  dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T);   /* start[D], q[D * T]; host only */
+/* n packed planar frames sw x sh -> dw x dh (any sizes within the ratio limits, odd ones included), host or device memory
+ * (on_device: src and dst are device pointers).  Synchronous: the frames are in dst when it returns. */
+int  dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter,
+                     int on_device);
+
+/* RESOLUTION LADDER: nsources sources of geometry *src, each coded at ngeoms (1..DSV1_MAX_GEOMS) geometries, at every rate rung of
+ * that geometry.  rungs[g]: width x height (the format of the source) and nrates (1..DSV1_MAX_RUNGS) DSV_ENCODER rate rungs whose
+ * vidmeta is that geometry, with the agreement rules of dsv1_ladder_open among them.  Built as one quality ladder per geometry
+ * (dsv1_resladder_batch: every dsv1_batch_* call works on it); the source crosses the link once per call, each geometry's scale
+ * (filter: DSV1_SCALE_*) is ordered on the device before that geometry's frame load, and the scaled clips are held by the resladder
+ * (double-buffered) until that geometry's collect.  A geometry of the source's size is not scaled.  Output stream
+ * k = s * Ntot + off[g] + rate, Ntot = sum of nrates, off[g] = sum of nrates of the geometries before g; output buffers, eos, encoder(k)
+ * and get_sse / get_ssim (sse[(k * frames_per_call + t) * 3 + p], against the SCALED source that stream's encoder saw) are per k.
+ * Input: [source][frame], nsources x frames_per_call frames of the source geometry, the three forms of dsv1_batch_submit.
+ * Refused before any device allocation: a rung larger than the source or below 1 / 8 of it on an axis of a plane, another format,
+ * a bad filter, ngeoms outside 1..16, an empty rate list (DSVG_ERR_ARG); a geometry dsv1_batch_open would not accept (its code).
+ * Not offered: stage, chain mode, the drop-in dsv_enc, the decoders, upscaling. */
+#define DSV1_MAX_GEOMS 16
+typedef struct {
+    int width, height;
+    int nrates;
+    const DSV_ENCODER *rates;
+} dsv1_res_rung;
+typedef struct dsv1_resladder dsv1_resladder;
+int  dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
+                         int frames_per_call, int filter);
+void dsv1_resladder_close(dsv1_resladder *r);
+int  dsv1_resladder_nstreams(const dsv1_resladder *r);       /* nsources * Ntot */
+dsv1_batch *dsv1_resladder_batch(dsv1_resladder *r, int g);  /* geometry g's quality ladder (its streams: s * nrates[g] + rate) */
+DSV_ENCODER *dsv1_resladder_encoder(dsv1_resladder *r, int k);
+int  dsv1_resladder_encode(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out);
+int  dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out);   /* at most two in flight */
+int  dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out);
+int  dsv1_resladder_eos(dsv1_resladder *r, int k, DSV_BUF *out);
+int  dsv1_resladder_sse_enable(dsv1_resladder *r, int on);
+int  dsv1_resladder_ssim_enable(dsv1_resladder *r, int on);
+int  dsv1_resladder_get_sse(const dsv1_resladder *r, uint64_t *sse, size_t n);
+int  dsv1_resladder_get_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n);
+/* host-to-device bytes the resladder uploaded itself so far (host input: one source clip per call, whatever ngeoms is) and calls */
+int  dsv1_resladder_uploads(const dsv1_resladder *r, uint64_t *bytes, long *calls);
+
 /* ---- extension: batched decoding (dsv_dec decodes one picture per call, dsv_decoder.c:286-472) ----
  * nstreams independent streams of one geometry; every call takes ONE packet per stream (packets[s]: not freed, not
  * modified) and decodes all picture packets among them as one device batch.  status[s] = DSV_DEC_OK (a frame was
