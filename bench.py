@@ -7,9 +7,12 @@ over one batch of synthetic input: --gops closed GOPs x 12 frames of 1920x1080 4
 already resident in HBM when the timed region starts; the output of a step is the finished .dsv bytes
 of every GOP.  GOPs are independent (closed, CRF) so N GPUs shard them with no collective ("weak").
 
-One JSON line on rank 0, see the keys at the bottom.  The CPU baseline is the REAL reference encoder
-(oracle/_ref, compiled from /root/reference where it exists; otherwise our scalar port in oracle/),
-single thread, on a bounded sample of the same clips, and is only a reported number.
+One JSON line on rank 0, see the keys at the bottom.  A plain run does what that line's headline needs and no more: it
+sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Everything else the benchmark measures or
+checks runs with --full, after the headline: the CPU baseline (the REAL reference encoder, oracle/_ref where it was built,
+otherwise our scalar port in oracle/, single thread, on a bounded sample of the same clips -- only a reported number), the
+bit-exact checks of the timed output against the reference, the per-kernel roofline, the NUMA placement measured over
+the link, the host-fed figure, the other shapes and config 4's sharded leg.
 """
 import argparse
 import ctypes as C
@@ -457,11 +460,14 @@ def main():
                                                           "measures other sizes on the same box -- DESIGN.md section 7 has the round's table)")
     ap.add_argument("--distinct", type=int, default=16, help="distinct synthetic GOP clips generated per rank (round 6: 16, was 4 -- the timed batch's branch behaviour is 16-valued; "
                                                                  "every one of them is checked against the reference's encode; `shapes.headline_mixed16` mixes clip STYLES as well)")
-    ap.add_argument("--cpu-gops", type=int, default=32, help="GOP encodes in the CPU baseline sample, ~0.3 s each (0 = skip)")
-    ap.add_argument("--prof-kernel", default="auto", help="kernel whose launches are timed with HIP events (auto = the largest; none = no brackets, no roofline: counter passes)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the PCIe-inclusive figure and the other shapes (configs 2, 4, 5, batched decode) reported after the headline")
-    ap.add_argument("--cfg4-gops", type=int, default=64, help="closed 4K GOPs of the config-4 leg that runs sharded over the ranks when --gpus > 1 (or with --cfg4-sharded); 0 = skip")
-    ap.add_argument("--cfg4-sharded", action="store_true", help="run the sharded config-4 leg on one GPU too (all its GOPs on this GPU)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else the benchmark measures or checks: the NUMA placement measured over the link, "
+                                                        "the per-kernel roofline, the CPU baseline and the bit-exact checks against the reference, and (unless --no-extras) "
+                                                        "the every-picture-reconstructed loop, the host-fed figure, the other shapes and config 4's sharded leg")
+    ap.add_argument("--cpu-gops", type=int, default=32, help="with --full: GOP encodes in the CPU baseline sample, ~0.3 s each (0 = skip the baseline and the bit-exact checks)")
+    ap.add_argument("--prof-kernel", default="auto", help="with --full: kernel whose launches are timed with HIP events (auto = the largest; none = no brackets, no roofline: counter passes)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the PCIe-inclusive figure and the other shapes (configs 2, 4, 5, batched decode) reported after the headline")
+    ap.add_argument("--cfg4-gops", type=int, default=64, help="with --full: closed 4K GOPs of the config-4 leg that runs sharded over the ranks when --gpus > 1 (or with --cfg4-sharded); 0 = skip")
+    ap.add_argument("--cfg4-sharded", action="store_true", help="with --full: run the sharded config-4 leg on one GPU too (all its GOPs on this GPU)")
     ap.add_argument("--input", choices=["hbm", "host", "pinned"], default="hbm",
                     help="where the raw frames are when a step starts: hbm (the metric), or host memory (pageable / pinned) "
                          "uploaded over PCIe inside the timed region (diagnostic, DESIGN.md section 7)")
@@ -473,6 +479,8 @@ def main():
         ap.error("--gpus must be >= 1")
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if not args.full and (args.cfg4_sharded or args.prof_kernel not in ("auto", "none")):
+        ap.error("--cfg4-sharded and --prof-kernel <name> ask for legs of a --full run")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started plainly with --gpus N: be the launcher (verdict round 5: the flag was parsed and never used).  Nothing has touched the
         # GPU yet, and the ranks are CHILDREN of this process (one per GPU, torch.distributed.run over 127.0.0.1), never an exec.
@@ -501,8 +509,8 @@ def main():
         forced = os.environ.get("DSV1_BENCH_NUMA_NODE")            # diagnostic: pin to THIS node whatever sysfs says (tools/ab/r06_repro.sh)
         if forced not in (None, ""):
             my_cores, numa_node = shard.pin_single_rank(local_rank, node=int(forced))
-        elif os.environ.get("DSV1_BENCH_SYSFS_PIN", "0") not in ("", "0"):
-            my_cores, numa_node = shard.pin_single_rank(local_rank)       # round 5: trust sysfs
+        elif not args.full or os.environ.get("DSV1_BENCH_SYSFS_PIN", "0") not in ("", "0"):
+            my_cores, numa_node = shard.pin_single_rank(local_rank)       # round 5: trust sysfs (a plain run: the node sysfs names, no link measured)
         else:
             # round 6: ask the LINK -- the host <-> device rates from fresh child processes on the sysfs node's cores, on the other node's, and
             # unpinned, before this process touches the GPU; the process moves to the best (the sysfs node unless another is > 5 % better)
@@ -568,6 +576,12 @@ def main():
     tiles = None
     prof_kernel = args.prof_kernel
     nstreams = b.code_streams(0)
+    if rank == 0 and prof_kernel != "none" and not args.full:
+        # a plain run codes the two untimed steps below unmeasured, so that its timed steps code the same frame numbers -- and
+        # therefore the same bytes -- as a --full run's; no kernel is selected, no launch of the timed region is bracketed
+        for _ in range(2):
+            b.encode(src, on_device=ondev)
+        prof_kernel = "none"
     if rank == 0 and prof_kernel != "none":     # "none": no event brackets at all (the counter passes of tools/collect_profiles.sh)
         b.code_streams(1)
         b.prof_enable(names)
@@ -615,7 +629,10 @@ def main():
             # `fused_border_bytes`, tallied on the host from the jobs' extents in the same counting step) -- output it cannot avoid writing
             table[kname] = (m_, n_, npatch * 5.0 + (fl + mv) * 128.0 + fl * 126.0 + float(tiles.get("fused_border_bytes", 0)))
         if prof_kernel == "auto":
-            prof_kernel = max(table, key=lambda k: table[k][0])
+            # the largest of the kernels whose bytes are priced: on small batches the top kernels are within a percent of each other, and
+            # one without algorithmic bytes (k_fwd_mc_pix) would put the roofline at 0
+            priced = [k for k in table if table[k][2] > 0] or list(table)
+            prof_kernel = max(priced, key=lambda k: table[k][0])
         b.code_streams(nstreams)
         b.prof_enable([prof_kernel])
     b.submit(src, on_device=ondev, held=True)                  # fill the pipeline
@@ -641,7 +658,7 @@ def main():
     # the bytes the LAST TIMED step produced (all streams, in stream order), hashed before anything reuses their buffers;
     # compared further down with bytes derived from the reference encoder's output for the same clips and frame numbers
     timed_sha = timed_fnum = None
-    if rank == 0:
+    if rank == 0 and args.full:
         hh = hashlib.sha256()
         for o in outs:
             hh.update(o.view())
@@ -654,7 +671,7 @@ def main():
     # the same loop with EVERY reference picture reconstructed (verdict round 5: the headline drops the inverse transform of each closed GOP's
     # last picture -- 320 of 3 840 --, which nobody predicts from; same packets): a few steps, never `value`
     recon_all = None
-    if rank == 0 and world == 1 and not args.no_extras and args.input == "hbm":
+    if rank == 0 and world == 1 and args.full and not args.no_extras and args.input == "hbm":
         b.sync()
         b.recon_all(True)
         b.submit(src, on_device=True, held=True)
@@ -759,7 +776,7 @@ def main():
 
     # ---- after the headline, outside its timed region: the same loop fed from pinned HOST memory ("frames
     # pre-loaded in host RAM"; the upload of each batch over PCIe rides inside the step), never `value`
-    extras = rank == 0 and world == 1 and not args.no_extras and args.input == "hbm" and os.environ.get("DSV1_BENCH_SKIP_SHAPES") != "1"
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras and args.input == "hbm" and os.environ.get("DSV1_BENCH_SKIP_SHAPES") != "1"
     host_pinned = None
     link = None
     if extras:
@@ -807,7 +824,7 @@ def main():
     bit_exact = None
     timed_check = None
     if rank == 0:
-        ncpu = min(args.cpu_gops, nd)
+        ncpu = min(args.cpu_gops, nd) if args.full else 0
         if ncpu > 0:
             # fresh GPU streams for the same GOP clips with the same frame numbers as the CPU run -- 16 of them (every
             # clip several times) so that the check goes through the same two-coding-stream path as the timed region
@@ -848,6 +865,7 @@ def main():
             "unit": "Mpix/s",
             "n_gpus": world,
             "steps": args.steps,
+            "full": args.full,
             "timed_region": {"host_clock_s": round(dt, 4), "gpu_events_s": round(gpu_ms / 1e3, 4),
                              "note": "the K timed steps by the host clock (barrier + sync on both sides: what `value` uses) and by HIP events recorded on the first "
                                      "coding stream at the region's start and behind its last coding work"},
@@ -962,7 +980,7 @@ def main():
     b.close()
     # BASELINE config 4 (64 closed 4K GOPs over the node's GPUs): runs sharded over the ranks whenever there is more than one
     # (every rank takes part; the headline's context is closed first so the leg has each GPU to itself)
-    if (world > 1 or args.cfg4_sharded) and args.cfg4_gops > 0 and not args.no_extras and args.input == "hbm":
+    if (world > 1 or args.cfg4_sharded) and args.full and args.cfg4_gops > 0 and not args.no_extras and args.input == "hbm":
         try:
             c4 = cfg4_sharded(pkg, A, shard, torch, dist, dev, rank, world, shared, max(2, min(args.steps, 4)), args.cfg4_gops)
         except Exception as e:                               # the headline stands on its own

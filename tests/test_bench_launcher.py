@@ -25,6 +25,15 @@ def test_gpus_zero_is_refused():
     assert p.returncode != 0
 
 
+def test_legs_of_a_full_run_need_full():
+    """the sharded config-4 leg and a named kernel's brackets belong to --full: asked for in a plain run, refused before anything runs"""
+    for extra in (["--cfg4-sharded"], ["--prof-kernel", "k_hme"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1"] + extra, cwd=ROOT,
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
+        assert p.returncode != 0 and "--full" in p.stderr, extra
+        assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(1200)
 def test_plain_start_with_gpus_2_launches_two_ranks():
@@ -32,7 +41,7 @@ def test_plain_start_with_gpus_2_launches_two_ranks():
     env["DSV1_BENCH_DEBUG_SHARED_GPU"] = "1"
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gops", "4", "--cpu-gops", "2",
-                        "--cfg4-gops", "0"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1100)
+                        "--full", "--cfg4-gops", "0"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1100)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

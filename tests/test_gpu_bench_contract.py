@@ -1,5 +1,5 @@
-"""bench.py keeps its contract: one JSON line with the driver's keys, the roofline and cpu_baseline objects, and the
-bit-exactness spot check -- run small (8 GOPs per step, one timed step)."""
+"""bench.py keeps its contract: one JSON line with the driver's keys; with --full, the roofline and cpu_baseline objects
+and the bit-exactness spot check -- run small (8 GOPs per step, one timed step)."""
 import json
 import os
 import subprocess
@@ -11,9 +11,31 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def test_plain_run_is_the_headline_alone():
+    """without --full: set-up, warm-up, the timed steps and the line -- the headline's keys, nothing measured or checked besides"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--gops", "8"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config", "step_breakdown", "timed_region"):
+        assert k in d, k
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "Mpix/s" and "int16" in d["dtype"] and "int32" in d["dtype"]
+    pix = 8 * 12 * 1920 * 1080
+    assert abs(d["value"] - pix / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "bit_exact_vs_cpu", "bit_exact_timed_output", "value_recon_all"):
+        assert d[k] is None, k
+    assert d["box"]["placement"] is None
+    for k in ("shapes", "value_host_pinned", "link", "cfg4_sharded"):
+        assert k not in d, k
+
+
 def test_bench_line_has_the_contract_fields():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                        "--gops", "8", "--cpu-gops", "2", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--gops", "8", "--cpu-gops", "2", "--no-extras", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -42,7 +64,7 @@ def test_bench_line_has_the_contract_fields():
 def test_bench_line_carries_the_other_shapes():
     """after the headline: the PCIe-inclusive figure, configs 2 / 4 / 5 and the batched decoder, each bit-exact"""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-                        "--gops", "8", "--cpu-gops", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--gops", "8", "--cpu-gops", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert d["value_host_pinned"]["value"] > 0 and d["value_host_pinned"]["value"] < d["value"] * 1.5
@@ -73,7 +95,7 @@ def test_cfg4_sharded_leg_on_one_gpu():
     """BASELINE config 4's own harness (closed 4K GOPs sharded by shard.gop_range, gathered, joined, compared with the serial
     stream derived from one reference encode) on the one GPU of the box: 6 GOPs instead of 64"""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--gops", "4", "--cpu-gops", "0",
-                        "--cfg4-sharded", "--cfg4-gops", "6"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--full", "--cfg4-sharded", "--cfg4-gops", "6"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, DSV1_BENCH_SKIP_SHAPES="1"))
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])

@@ -45,7 +45,7 @@ def test_bench_ranks_on_one_gpu(ranks, gops):
     steps = 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(A.ROOT, "bench.py"), "--gpus", str(ranks), "--steps", str(steps), "--warmup", "1",
-           "--gops", str(gops), "--cpu-gops", "2", "--cfg4-gops", "16"]
+           "--gops", str(gops), "--cpu-gops", "2", "--full", "--cfg4-gops", "16"]
     r = subprocess.run(cmd, cwd=A.ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

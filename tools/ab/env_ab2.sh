@@ -1,7 +1,7 @@
 #!/bin/bash
-# same-box A/B of an environment switch: bench.py --steps 6 --no-extras twice each way; usage: env_ab2.sh VAR "<kernel substrings>"
+# same-box A/B of an environment switch: bench.py --full --steps 6 --no-extras twice each way; usage: env_ab2.sh VAR "<kernel substrings>"
 V=$1; export KS="$2"
-one() { python3 bench.py --cpu-gops 4 --steps 6 --no-extras | python3 -c "
+one() { python3 bench.py --full --cpu-gops 4 --steps 6 --no-extras | python3 -c "
 import sys,json,os
 d=json.loads(sys.stdin.read()); t=d['roofline']['all_kernels_ms_one_step']
 ks=os.environ['KS'].split()

@@ -6,7 +6,7 @@ mkdir -p $OUT
 cat /proc/loadavg > $OUT/loadavg.txt
 timeout 1500 python3 -m pytest tests/test_gpu_stream.py tests/test_bench_launcher.py tests/test_gpu_bench_contract.py tests/test_gpu_pipeline_abi.py -x -q -m gpu > $OUT/pytest.txt 2>&1
 tail -5 $OUT/pytest.txt
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 tail -3 $OUT/bench.err
 python3 - $OUT/bench.json <<'P'
 import json,sys

@@ -3,7 +3,7 @@
 OUT=gpurun_out/${1:-r06g}; mkdir -p $OUT
 timeout 2400 python3 -m pytest tests -x -q -m gpu > $OUT/pytest.txt 2>&1; grep -E "passed|failed" $OUT/pytest.txt | tail -1
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 python3 - $OUT/bench.json <<'P'
 import json,sys
 p=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

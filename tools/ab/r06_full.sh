@@ -2,7 +2,7 @@
 # round 6: the driver's exact bench command, then the whole GPU suite; output under gpurun_out/$1
 TAG=${1:-r06d}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 cat /proc/loadavg > $OUT/loadavg.txt
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err
 python3 - $OUT/bench.json <<'P'
 import json,sys
 p=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -33,6 +33,6 @@ run nopin DSV1_BENCH_NO_NUMA_PIN=1
 run node0 DSV1_BENCH_NUMA_NODE=0
 run node1 DSV1_BENCH_NUMA_NODE=1
 cat /proc/loadavg
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/full.json" 2> "$OUT/full.err"
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/full.json" 2> "$OUT/full.err"
 tail -c 3000 "$OUT/full.json"
 grep "dsv1 host" "$OUT/a1.err" "$OUT/node0.err" "$OUT/node1.err"

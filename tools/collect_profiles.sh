@@ -2,7 +2,7 @@
 # Collect the round's evidence on the GPU box (run through gpurun from the repo root):
 #   1. PMC passes over `bench.py --steps 1`: FETCH_SIZE and WRITE_SIZE in separate runs (they do not fit one
 #      pass), one SQ pass -> per-kernel summaries -> pmc_traffic.json (what bench.py reads for `traffic`);
-#   2. the default bench line; 3. rocprofv3 --kernel-trace --stats of the same command.
+#   2. the --full bench line; 3. rocprofv3 --kernel-trace --stats of the same command.
 # Everything lands in gpurun_out/$TAG/ ; copy what should be judged into profiles/.
 TAG=${1:-r01}
 GOPS=${2:-320}
@@ -23,9 +23,9 @@ rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INST_CY
 python3 $REPO/tools/pmc_summary.py "/tmp/pr/**/*counter_collection.csv" > "$OUT/pmc_roof_per_kernel.csv"
 python3 $REPO/tools/make_pmc_traffic.py "$OUT/pmc_hbm_per_kernel.csv" $GOPS "$OUT/pmc_traffic.json" "$OUT/pmc_sq_per_kernel.csv" "$OUT/pmc_roof_per_kernel.csv"
 cp "$OUT/pmc_traffic.json" $REPO/profiles/pmc_traffic.json
-cd $REPO && python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+cd $REPO && python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python3 $REPO/bench.py --cpu-gops 0 --no-extras > "$OUT/bench_under_rocprof.json" 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python3 $REPO/bench.py --full --cpu-gops 0 --no-extras > "$OUT/bench_under_rocprof.json" 2>/dev/null
 f=$(ls /tmp/kt/*/*kernel_stats.csv | head -1); cp "$f" "$OUT/rocprofv3_kernel_stats.csv"
 t=$(ls /tmp/kt/*/*kernel_trace.csv | head -1); python3 $REPO/tools/trace_summary.py "$t" > "$OUT/kernel_trace_summary.txt"
 # the same with ONE coding stream: every kernel alone on the chip, one launch = all pictures of a frame step -- the averages
