@@ -137,6 +137,12 @@ def lib():
         L.dsv1_resladder_get_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
         L.dsv1_resladder_get_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
         L.dsv1_resladder_uploads.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.POINTER(_C.c_long)]
+        L.dsv1_resample_taps.argtypes = [_C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_resample_weights.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_int]
+        L.dsv1_resample_clip.argtypes = L.dsv1_scale_clip.argtypes
+        L.dsv1_resladder_src_quality_enable.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_resladder_get_src_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
+        L.dsv1_resladder_get_src_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
         _lib = L
     return _lib
 
@@ -525,6 +531,40 @@ def scale_clip(clip, sw, sh, fmt, dw, dh, filt=SCALE_CUBIC, device=0, n=None, ou
     return res
 
 
+def resample_taps(S, D, filt):
+    """taps of one axis of the resampler in either direction (dsv1_resample_taps); ValueError outside 1/8 <= S / D <= 8"""
+    t = lib().dsv1_resample_taps(S, D, filt)
+    if t < 0:
+        raise ValueError("no resample from %d to %d samples with filter %d" % (S, D, filt))
+    return t
+
+
+def resample_weights(S, D, filt):
+    """the resampler's weight table of one axis, either direction (dsv1_resample_weights): (start int32 [D], q int16 [D, T])"""
+    T = resample_taps(S, D, filt)
+    start = _np.zeros(D, dtype=_np.int32)
+    q = _np.zeros((D, T), dtype=_np.int16)
+    _chk(lib().dsv1_resample_weights(S, D, filt, start.ctypes.data, q.ctypes.data, T), "dsv1_resample_weights")
+    return start, q
+
+
+def resample_clip(clip, sw, sh, fmt, dw, dh, filt=SCALE_CUBIC, device=0, n=None, out=None):
+    """resample packed planar frames on the GPU, every axis of every plane up or down (dsv1_resample_clip); arguments as scale_clip"""
+    L = lib()
+    sfb = sw * sh + 2 * _chroma_size(sw, sh, fmt)
+    dfb = dw * dh + 2 * _chroma_size(dw, dh, fmt)
+    if n is not None:
+        _chk(L.dsv1_resample_clip(device, clip, sw, sh, fmt, n, out, dw, dh, filt, 1), "dsv1_resample_clip")
+        return out
+    a = _np.ascontiguousarray(clip, dtype=_np.uint8)
+    if a.size % sfb or not a.size:
+        raise ValueError("a clip of %dx%d frames is a whole number of %d-byte frames, got %d bytes" % (sw, sh, sfb, a.size))
+    frames = a.size // sfb
+    res = _np.zeros((frames, dfb), dtype=_np.uint8)
+    _chk(L.dsv1_resample_clip(device, a.ctypes.data, sw, sh, fmt, frames, res.ctypes.data, dw, dh, filt, 0), "dsv1_resample_clip")
+    return res
+
+
 class ResLadder:
     """A resolution ladder (dsv1_resladder_open): nsources sources of w x h in format fmt, each scaled on the GPU to every geometry of
     `geoms` and coded there at every rate rung.  geoms: list of (width, height, [Encoder cfg of that geometry, ...]).  Input is the
@@ -636,6 +676,31 @@ class ResLadder:
         """mean SSIM float64 [nstreams, F, 4], each stream at its own geometry"""
         f = self.ssim_fx()
         return _np.stack([ssim_mean(f[k], *self.stream_dims(k), self.fmt) for k in range(self.nstreams)])
+
+    def src_quality_enable(self, sse=True, ssim=True, filt=SCALE_CUBIC):
+        """measure every rung at the SOURCE resolution (dsv1_resladder_src_quality_enable): reconstructions upscaled with filter
+        `filt` and compared with the original source; only between calls"""
+        _chk(self.L.dsv1_resladder_src_quality_enable(self.h, 1 if sse else 0, 1 if ssim else 0, filt), "dsv1_resladder_src_quality_enable")
+
+    def src_sse(self):
+        """numpy.uint64 [nstreams, F, 3] of the call collected last, over the source's plane areas"""
+        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.uint64)
+        _chk(self.L.dsv1_resladder_get_src_sse(self.h, out.ctypes.data_as(_C.POINTER(_C.c_uint64)), out.size), "dsv1_resladder_get_src_sse")
+        return out
+
+    def src_ssim_fx(self):
+        """numpy.int64 [nstreams, F, 3]: SSIM_FX over the windows of the source's plane dims"""
+        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.int64)
+        _chk(self.L.dsv1_resladder_get_src_ssim(self.h, out.ctypes.data_as(_C.POINTER(_C.c_int64)), out.size), "dsv1_resladder_get_src_ssim")
+        return out
+
+    def src_psnr(self):
+        """float64 [nstreams, F, 4] in dB, every stream at the source geometry"""
+        return psnr_db(self.src_sse(), self.width, self.height, self.fmt)
+
+    def src_ssim(self):
+        """mean SSIM float64 [nstreams, F, 4], every stream over the source geometry's windows"""
+        return ssim_mean(self.src_ssim_fx(), self.width, self.height, self.fmt)
 
     def code_streams(self, n=0):
         """set (n >= 1) / query (n = 0) the coding streams of every geometry's ladder; returns the previous value of geometry 0's"""

@@ -92,5 +92,27 @@ void launch_sse(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout
 // sse != nullptr: the sums of squared errors too, in the same pass (k_sse's figures: launch one or the other)
 void launch_ssim(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const HzPlaneSum *psum0, unsigned long long *ssim,
                  unsigned long long *sse);
+// source-resolution quality (dsvg_ctx_xres_enable): every job's reconstruction upscaled to the reference geometry (dsv1_resample_*
+// tables) and compared with the reference frame of its out slot (xref[out slot], nullptr: not measured), per-plane SSE and SSIM_FX
+// added into xsse / xssim[3 * out slot + plane] (either may be nullptr); same launch point as launch_sse / launch_ssim
+struct XresPlane {               // one plane: reconstruction sw x sh -> reference dw x dh, tables in device memory
+    int sw, sh, dw, dh;
+    int th, tv, tx, tile0;       // taps per axis, tiles across, first tile of the plane in blockIdx.x
+    long long doff;              // plane offset inside a packed reference frame
+    const int *hs;
+    const short *hq;
+    const int *vs;
+    const short *vq;
+};
+struct XresGeo {
+    XresPlane *planes_d = nullptr;   // [3] + tables, one allocation
+    int ntiles = 0, rows_cap = 0, th_cap = 0, tv_cap = 0, span_cap = 0;
+    size_t lds = 0, rfb = 0;         // LDS of a workgroup; bytes of a packed reference frame
+    int rw = 0, rh = 0, filter = -1;
+};
+int xres_geo_build(XresGeo &G, const FrameLayout &L, int rw, int rh, int filter);   // replaces G's tables only on success
+void xres_geo_free(XresGeo &G);
+void launch_xres(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const XresGeo &G, const uint8_t *const *xref,
+                 const HzPlaneSum *psum0, unsigned long long *xsse, unsigned long long *xssim);
 // k_hme.hip
 void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf = nullptr);

@@ -188,6 +188,15 @@ struct dsvg_ctx {
     bool ssim_on = false;
     unsigned long long *ssim_d = nullptr, *ssim_h = nullptr; // [out_slots][3] device / pinned host
     std::vector<char> slot_ssim;
+    // source-resolution quality (dsvg_ctx_xres_enable, k_xres_quality): the reference geometry's upscale tables, per out slot the
+    // reference frame the next call measures against (xref_next, set by dsvg_ctx_xres_refs and consumed by the call that codes the
+    // slot; its pinned staging and device copy xref_h / xref_d), the sums, and whether the picture coded into the slot last was measured
+    bool xsse_on = false, xssim_on = false;
+    XresGeo xg;
+    unsigned long long *xsse_d = nullptr, *xsse_h = nullptr, *xssim_d = nullptr, *xssim_h = nullptr;
+    const uint8_t **xref_d = nullptr, **xref_h = nullptr;
+    std::vector<const uint8_t *> xref_next;
+    std::vector<char> slot_xsse, slot_xssim;
     // device-resident rate control (dsvg_code_batch_rc): per-stream state, per-job tables (indexed like jobs_h / jobs_d)
     dsvg_rc_state *rc_state_d = nullptr;
     RcJobDev *rcj_d = nullptr, *rcj_h = nullptr;
@@ -414,10 +423,11 @@ static void ctx_free(dsvg_ctx *c)
     if (c->dec_flag_h) (void)hipHostFree(c->dec_flag_h);
     for (int i = 0; i < 6; i++) c->src[i].release();
     c->recon.release(); c->xf.release(); c->pred.release();
+    xres_geo_free(c->xg);
     void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->ptab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d, c->ssim_d};
+                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->ptab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d, c->ssim_d, c->xsse_d, c->xssim_d, (void *)c->xref_d};
     for (void *p : d) if (p) (void)hipFree(p);
-    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, c->sse_h, c->ssim_h};
+    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, c->sse_h, c->ssim_h, c->xsse_h, c->xssim_h, (void *)c->xref_h};
     for (void *p : hh) if (p) (void)hipHostFree(p);
     if (c->st) (void)hipStreamDestroy(c->st);
     for (int i = 0; i < 2; i++) if (c->ev_mark[i]) (void)hipEventDestroy(c->ev_mark[i]);
@@ -1306,6 +1316,7 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
     HIPCHK(hipSetDevice(c->device));
     const bool sse = c->sse_on;                              // quality measurement of this call's pictures (dsvg_ctx_sse_enable)
     const bool ssim = c->ssim_on;                            // (dsvg_ctx_ssim_enable)
+    const bool xres = c->xsse_on || c->xssim_on;             // (dsvg_ctx_xres_enable)
     static const bool cprof = getenv("DSV1_HOST_PROF") != nullptr;
     const auto cnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = cprof ? cnow() : 0.0;
@@ -1405,6 +1416,16 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             c->slot_sse[(size_t)j.out_slot] = (char)sse;
             if (c->slot_ssim.size() != (size_t)c->out_slots) c->slot_ssim.assign((size_t)c->out_slots, 0);
             c->slot_ssim[(size_t)j.out_slot] = (char)ssim;
+            if (xres) {
+                // the reference frame dsvg_ctx_xres_refs set for the slot, taken by this call (none: the picture is not measured)
+                const uint8_t *r = c->xref_next[(size_t)j.out_slot];
+                c->xref_next[(size_t)j.out_slot] = nullptr;
+                c->xref_h[j.out_slot] = r;
+                c->slot_xsse[(size_t)j.out_slot] = (char)(c->xsse_on && r);
+                c->slot_xssim[(size_t)j.out_slot] = (char)(c->xssim_on && r);
+            } else if (!c->slot_xsse.empty()) {
+                c->slot_xsse[(size_t)j.out_slot] = c->slot_xssim[(size_t)j.out_slot] = 0;
+            }
             if (rcj) dpos[(size_t)t * njobs + order[k]] = k;
             if (isP && !c->mc_fused) noint[NG * t + g] = 0;
             if (isP && c->mc_fused && !j.no_intra_blocks) {
@@ -1542,6 +1563,11 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
     // the measurements' sums of the call's out slots start at zero (k_sse / k_ssim add into them); before the fork: every coding stream is behind it
     if (sse) HIPCHK(hipMemsetAsync(c->sse_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
     if (ssim) HIPCHK(hipMemsetAsync(c->ssim_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
+    if (xres) {
+        HIPCHK(hipMemcpyAsync(c->xref_d + base, c->xref_h + base, sizeof(const uint8_t *) * total, hipMemcpyHostToDevice, c->st));
+        if (c->xsse_on) HIPCHK(hipMemsetAsync(c->xsse_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
+        if (c->xssim_on) HIPCHK(hipMemsetAsync(c->xssim_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
+    }
     tl_mark(c, c->st, "code0");
     if (NG > 1) {
         if (!c->ev_fork) HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -1600,11 +1626,13 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             // Measured pictures all need theirs: a job without a kept slot gets it in its work frame (JobDev.xf), where the inverse
             // kernels put it; k_sse / k_ssim read it there, in stream order behind the reconstruction and before anything can overwrite it.
             // With both measurements on, k_ssim makes the SSE too: one pass over the pictures
-            bool keeps = sse || ssim;
+            bool keeps = sse || ssim || xres;
             for (int k = k0; k < k0 + n && !keeps; k++) keeps = dj[(size_t)t * njobs + k]->recon_slot >= 0;
             if (keeps) OPCHK(enqueue_recon(c, nI, n, d0, 7, st, true, c->llq));
             if (ssim) launch_ssim(st, jd, n, c->L[0], c->psum, c->ssim_d, sse ? c->sse_d : nullptr);
             else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->sse_d);
+            // (the same place and ordering argument: the reconstruction upscaled to the reference geometry, k_xres_quality)
+            if (xres) launch_xres(st, jd, n, c->L[0], c->xg, c->xref_d, c->psum, c->xsse_on ? c->xsse_d : nullptr, c->xssim_on ? c->xssim_d : nullptr);
             launch_hz_pack(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
             // rate control: the sizes of these packets -> the quantiser tables of the same streams' pictures of the next step
             if (rcj) launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, d0, n, 1);
@@ -1911,6 +1939,56 @@ extern "C" int dsvg_fetch_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t
 {
     if (!c || n < 0 || (n > 0 && (!out_slots || !ssim_out))) { dsvg_set_error("bad dsvg_fetch_ssim arguments"); return DSVG_ERR_ARG; }
     return quality_fetch(c, "dsvg_fetch_ssim", c->ssim_d, c->ssim_h, c->slot_ssim, n, out_slots, ssim_out);
+}
+
+extern "C" int dsvg_ctx_xres_enable(dsvg_ctx *c, int sse_on, int ssim_on, int ref_w, int ref_h, int filter)
+{
+    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
+    if (!sse_on && !ssim_on) { c->xsse_on = c->xssim_on = false; return DSVG_OK; }     // (the tables stay for the next switch-on)
+    if (filter != 0 && filter != 1) { dsvg_set_error("dsvg_ctx_xres_enable: bad filter %d", filter); return DSVG_ERR_ARG; }
+    if (ref_w < 1 || ref_h < 1) { dsvg_set_error("dsvg_ctx_xres_enable: bad reference geometry"); return DSVG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->xg.planes_d || c->xg.rw != ref_w || c->xg.rh != ref_h || c->xg.filter != filter) {
+        HIPCHK(hipDeviceSynchronize());             // (no call in flight may still read the tables being replaced)
+        OPCHK(xres_geo_build(c->xg, c->L[0], ref_w, ref_h, filter));
+        c->xref_next.assign((size_t)c->out_slots, nullptr);                 // (frames of another geometry: set them again)
+    }
+    if (!c->xref_d) {
+        OPCHK(dmalloc(&c->xref_d, (size_t)c->out_slots, true));
+        OPCHK(hmalloc(&c->xref_h, (size_t)c->out_slots));
+        c->xref_next.assign((size_t)c->out_slots, nullptr);
+        c->slot_xsse.assign((size_t)c->out_slots, 0);
+        c->slot_xssim.assign((size_t)c->out_slots, 0);
+    }
+    bool on = false;
+    OPCHK(quality_enable(c, on, c->xsse_d, c->xsse_h, sse_on));
+    OPCHK(quality_enable(c, on, c->xssim_d, c->xssim_h, ssim_on));
+    c->xsse_on = sse_on != 0;
+    c->xssim_on = ssim_on != 0;
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_ctx_xres_refs(dsvg_ctx *c, const void *ref_clip, int n, const int *out_slots, const int *frames)
+{
+    if (!c || n < 0 || (n > 0 && (!out_slots || !frames))) { dsvg_set_error("bad dsvg_ctx_xres_refs arguments"); return DSVG_ERR_ARG; }
+    if (!c->xg.planes_d) { dsvg_set_error("dsvg_ctx_xres_refs: the measurement was never switched on"); return DSVG_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        if (out_slots[i] < 0 || out_slots[i] >= c->out_slots || frames[i] < 0) { dsvg_set_error("dsvg_ctx_xres_refs: entry %d out of range", i); return DSVG_ERR_ARG; }
+    for (int i = 0; i < n; i++)
+        c->xref_next[(size_t)out_slots[i]] = ref_clip ? (const uint8_t *)ref_clip + (size_t)frames[i] * c->xg.rfb : nullptr;
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_fetch_xres_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out)
+{
+    if (!c || n < 0 || (n > 0 && (!out_slots || !sse_out))) { dsvg_set_error("bad dsvg_fetch_xres_sse arguments"); return DSVG_ERR_ARG; }
+    return quality_fetch(c, "dsvg_fetch_xres_sse", c->xsse_d, c->xsse_h, c->slot_xsse, n, out_slots, sse_out);
+}
+
+extern "C" int dsvg_fetch_xres_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t *ssim_out)
+{
+    if (!c || n < 0 || (n > 0 && (!out_slots || !ssim_out))) { dsvg_set_error("bad dsvg_fetch_xres_ssim arguments"); return DSVG_ERR_ARG; }
+    return quality_fetch(c, "dsvg_fetch_xres_ssim", c->xssim_d, c->xssim_h, c->slot_xssim, n, out_slots, ssim_out);
 }
 
 extern "C" int dsvg_fetch_pictures(dsvg_ctx *c, int n, const int *out_slots, dsvg_pic_out *outs)

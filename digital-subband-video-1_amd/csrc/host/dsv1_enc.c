@@ -104,6 +104,13 @@ struct dsv1_batch {
     int ssim_sub[2];
     int64_t *ssim;                   /* [nstreams][frames][3] fixed-point SSIM of the batch collected last */
     size_t ssim_n;
+    /* source-resolution figures (dsv1_batch_xres_enable): the same bookkeeping per measure, and the reference clip of the next submit */
+    int xsse_on, xssim_on;
+    int xsse_sub[2], xssim_sub[2];
+    const void *xres_clip;
+    uint64_t *xsse;
+    int64_t *xssim;
+    size_t xsse_n, xssim_n;
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -191,7 +198,7 @@ void dsv1_batch_close(dsv1_batch *b)
     free(b->slots_cur); free(b->slots_ref); free(b->pair_pic); free(b->out_slots);
     free(b->luma); free(b->mv_tmp); free(b->jobs); free(b->outs); free(b->rcjobs); free(b->sc0.pkt); free(b->rpar); free(b->has_recon); free(b->border_skipped); free(b->recon_dropped);
     free(b->ch_start); free(b->ch_len); free(b->ch_pair); free(b->ch_cur);
-    free(b->rc_dev); free(b->rc_par); free(b->sse); free(b->ssim);
+    free(b->rc_dev); free(b->rc_par); free(b->sse); free(b->ssim); free(b->xsse); free(b->xssim);
     free(b);
 }
 
@@ -907,6 +914,38 @@ int dsv1_batch_ssim_enable(dsv1_batch *b, int on)
     b->ssim_on = on != 0;
     return DSVG_OK;
 }
+int dsv1_batch_xres_enable(dsv1_batch *b, int sse_on, int ssim_on, int ref_w, int ref_h, int filter)
+{
+    int rc;
+    const size_t n = b ? (size_t)3 * b->nstreams * b->F : 0;
+    if (!b) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_xres_enable with batches in flight"); return DSVG_ERR_ARG; }
+    if (sse_on && !b->xsse && !(b->xsse = (uint64_t *)malloc(sizeof(uint64_t) * n))) return DSVG_ERR_NOMEM;
+    if (ssim_on && !b->xssim && !(b->xssim = (int64_t *)malloc(sizeof(int64_t) * n))) return DSVG_ERR_NOMEM;
+    if ((rc = dsvg_ctx_xres_enable(b->ctx, sse_on, ssim_on, ref_w, ref_h, filter))) return rc;
+    b->xsse_on = sse_on != 0;
+    b->xssim_on = ssim_on != 0;
+    return DSVG_OK;
+}
+int dsv1_batch_xres_source(dsv1_batch *b, const void *ref_clip_dev)
+{
+    if (!b) return DSVG_ERR_ARG;
+    b->xres_clip = ref_clip_dev;
+    return DSVG_OK;
+}
+int dsv1_batch_get_xres_sse(const dsv1_batch *b, uint64_t *sse, size_t n)
+{
+    if (!b || !sse || !b->xsse_n || n < b->xsse_n) return DSVG_ERR_ARG;
+    memcpy(sse, b->xsse, sizeof(uint64_t) * b->xsse_n);
+    return DSVG_OK;
+}
+int dsv1_batch_get_xres_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n)
+{
+    if (!b || !ssim_fx || !b->xssim_n || n < b->xssim_n) return DSVG_ERR_ARG;
+    memcpy(ssim_fx, b->xssim, sizeof(int64_t) * b->xssim_n);
+    return DSVG_OK;
+}
+
 int dsv1_batch_get_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n)
 {
     if (!b || !ssim_fx) return DSVG_ERR_ARG;
@@ -1077,6 +1116,17 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
                     *pc = pics[s * R * F + t];
                     pc->out_slot += r;
                 }
+        if ((b->xsse_on || b->xssim_on) && !b->chains) {
+            /* the reference frame of every picture of the call: stream s (source s / R), frame t -> frame (s / R) * F + t */
+            int *fr = (int *)malloc(sizeof(int) * (size_t)N * nf), *os = (int *)malloc(sizeof(int) * (size_t)N * nf);
+            if (!fr || !os) { free(fr); free(os); return DSVG_ERR_NOMEM; }
+            for (s = 0; s < N; s++)
+                for (t = 0; t < nf; t++) { os[s * nf + t] = pics[s * F + t].out_slot; fr[s * nf + t] = (s / R) * F + t; }
+            rc = b->xres_clip ? dsvg_ctx_xres_refs(b->ctx, b->xres_clip, N * nf, os, fr) : DSVG_ERR_ARG;
+            free(fr); free(os);
+            b->xres_clip = NULL;
+            if (rc) { dsv1_log(1, "source-resolution figures on, but no reference clip named for this submit"); return rc; }
+        }
         if (b->chains) {
             if ((rc = code_chains(b, pics, nf, par))) return rc;
         } else
@@ -1171,6 +1221,8 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
         b->pending[par] = serial ? 2 : 1;               /* 2 = already assembled */
         b->sse_sub[par] = b->sse_on;
         b->ssim_sub[par] = b->ssim_on;
+        b->xsse_sub[par] = b->xsse_on && !b->chains;
+        b->xssim_sub[par] = b->xssim_on && !b->chains;
         b->nf_pending[par] = nf;
     }
     HP_MARK(HP_PREFIX);
@@ -1211,6 +1263,7 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
     par = b->pending[b->parity] ? b->parity : (b->parity ^ 1);   /* oldest first */
     if (!b->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
     b->sse_n = b->ssim_n = 0;                           /* (dsv1_batch_get_sse / _ssim: from here on about this batch) */
+    b->xsse_n = b->xssim_n = 0;
     pics = b->pics + (size_t)par * S * F;
     nf = b->nf_pending[par];
     if (b->bg_on[par]) {
@@ -1251,6 +1304,16 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
         for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
         if ((rc = dsvg_fetch_ssim(b->ctx, S * nf, b->out_slots, b->ssim))) return rc;
         b->ssim_n = (size_t)3 * S * nf;
+    }
+    if (b->xsse_sub[par]) {
+        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
+        if ((rc = dsvg_fetch_xres_sse(b->ctx, S * nf, b->out_slots, b->xsse))) return rc;
+        b->xsse_n = (size_t)3 * S * nf;
+    }
+    if (b->xssim_sub[par]) {
+        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
+        if ((rc = dsvg_fetch_xres_ssim(b->ctx, S * nf, b->out_slots, b->xssim))) return rc;
+        b->xssim_n = (size_t)3 * S * nf;
     }
     b->pending[par] = 0;
     return DSVG_OK;

@@ -119,6 +119,16 @@ int  dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx);
 int  dsvg_scaler_sync(dsvg_scaler *s);
 int  dsvg_scaler_alloc(dsvg_scaler *s, void **dptr, size_t bytes);
 int  dsvg_scaler_download(dsvg_scaler *s, void *host, const void *dptr, size_t bytes);
+/* device clip -> upload buffer `buf` (0 / 1) on the scaler's stream, as dsvg_scaler_upload (a resolution ladder's plain device clip
+ * that must outlive its submit) */
+int  dsvg_scaler_copy_in(dsvg_scaler *s, int buf, const void *dev, size_t bytes, void **dptr);
+/* dsv1_enc.c: source-resolution figures of a batch (dsvg_ctx_xres_enable; resolution ladders): stream k = s * R + r, frame t of a
+ * call is measured against frame s * frames_per_call + t of the reference clip named for the next submit (device memory, kept until
+ * that batch's collect); the figures of the batch collected last, [(k * F + t) * 3 + p].  Enable only between batches. */
+int  dsv1_batch_xres_enable(dsv1_batch *b, int sse_on, int ssim_on, int ref_w, int ref_h, int filter);
+int  dsv1_batch_xres_source(dsv1_batch *b, const void *ref_clip_dev);
+int  dsv1_batch_get_xres_sse(const dsv1_batch *b, uint64_t *sse, size_t n);
+int  dsv1_batch_get_xres_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n);
 
 #define CLAMPI(v, lo, hi) ((v) < (lo) ? (lo) : ((v) > (hi) ? (hi) : (v)))
 

@@ -14,9 +14,16 @@
 
 int dsv1_scale_taps(int S, int D, int filter)
 {
+    if (D < 1 || S < D) return DSVG_ERR_ARG;
+    return dsv1_resample_taps(S, D, filter);
+}
+
+/* either direction, 1/8 <= S / D <= 8: r = ceil(support max(1, S / D)), T = 2r + 2 (for S >= D what dsv1_scale_taps always gave) */
+int dsv1_resample_taps(int S, int D, int filter)
+{
     const long long sup = filter == DSV1_SCALE_TENT ? 1 : filter == DSV1_SCALE_CUBIC ? 2 : 0;
-    if (!sup || D < 1 || S < D || (long long)S > 8LL * D) return DSVG_ERR_ARG;
-    return (int)(2 * ((sup * S + D - 1) / D) + 2);
+    if (!sup || D < 1 || S < 1 || (long long)S > 8LL * D || (long long)D > 8LL * S) return DSVG_ERR_ARG;
+    return (int)(2 * (S >= D ? (sup * S + D - 1) / D : sup) + 2);
 }
 
 static double scale_kernel(double x, int filter)
@@ -27,15 +34,14 @@ static double scale_kernel(double x, int filter)
     return 0.0;
 }
 
-int dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T)
+/* one axis's table in either direction (T checked by the caller): inv = min(1, D / S) -- the kernel is stretched only to downscale */
+static void resample_table(int S, int D, int filter, int32_t *start, int16_t *q, int T)
 {
     double w[2 * (2 * 8 + 1) + 2];                                      /* T <= 2 ceil(2 * 8) + 2 = 34 */
-    const int Tn = dsv1_scale_taps(S, D, filter);
     int i, t;
-    if (Tn < 0 || T != Tn || !start || !q) return DSVG_ERR_ARG;
     for (i = 0; i < D; i++) {
         const double c = (double)((2LL * i + 1) * S - D) / (double)(2LL * D);
-        const double inv = (double)D / (double)S;
+        const double inv = S >= D ? (double)D / (double)S : 1.0;
         const long long j0 = (long long)floor(c) - (T - 2) / 2;
         double sum = 0.0;
         int s = 0, best = 0;
@@ -53,19 +59,37 @@ int dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, int
         q[(size_t)i * T + best] = (int16_t)(q[(size_t)i * T + best] + 16384 - s);
         start[i] = (int32_t)j0;
     }
+}
+
+int dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T)
+{
+    const int Tn = dsv1_scale_taps(S, D, filter);
+    if (Tn < 0 || T != Tn || !start || !q) return DSVG_ERR_ARG;
+    resample_table(S, D, filter, start, q, T);
     return DSVG_OK;
 }
 
-/* every axis of every plane within the ratio limits: DSVG_OK or DSVG_ERR_ARG */
-static int scale_dims_ok(int sw, int sh, int fmt, int dw, int dh, int filter)
+int dsv1_resample_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T)
+{
+    const int Tn = dsv1_resample_taps(S, D, filter);
+    if (Tn < 0 || T != Tn || !start || !q) return DSVG_ERR_ARG;
+    resample_table(S, D, filter, start, q, T);
+    return DSVG_OK;
+}
+
+/* every axis of every plane within the ratio limits (taps: dsv1_scale_taps, downscale only, or dsv1_resample_taps): DSVG_OK or
+ * DSVG_ERR_ARG */
+static int dims_ok(int (*taps)(int, int, int), int sw, int sh, int fmt, int dw, int dh, int filter)
 {
     const int hs = (fmt >> 2) & 3, vs = fmt & 3;
     if (fmt != DSV_SUBSAMP_444 && fmt != DSV_SUBSAMP_422 && fmt != DSV_SUBSAMP_420 && fmt != DSV_SUBSAMP_411) return DSVG_ERR_ARG;
-    if (dsv1_scale_taps(sw, dw, filter) < 0 || dsv1_scale_taps(sh, dh, filter) < 0) return DSVG_ERR_ARG;
-    if (dsv1_scale_taps((sw + (1 << hs) - 1) >> hs, (dw + (1 << hs) - 1) >> hs, filter) < 0) return DSVG_ERR_ARG;
-    if (dsv1_scale_taps((sh + (1 << vs) - 1) >> vs, (dh + (1 << vs) - 1) >> vs, filter) < 0) return DSVG_ERR_ARG;
+    if (taps(sw, dw, filter) < 0 || taps(sh, dh, filter) < 0) return DSVG_ERR_ARG;
+    if (taps((sw + (1 << hs) - 1) >> hs, (dw + (1 << hs) - 1) >> hs, filter) < 0) return DSVG_ERR_ARG;
+    if (taps((sh + (1 << vs) - 1) >> vs, (dh + (1 << vs) - 1) >> vs, filter) < 0) return DSVG_ERR_ARG;
     return DSVG_OK;
 }
+static int scale_dims_ok(int sw, int sh, int fmt, int dw, int dh, int filter) { return dims_ok(dsv1_scale_taps, sw, sh, fmt, dw, dh, filter); }
+static int resample_dims_ok(int sw, int sh, int fmt, int dw, int dh, int filter) { return dims_ok(dsv1_resample_taps, sw, sh, fmt, dw, dh, filter); }
 
 static size_t frame_bytes_of(int w, int h, int fmt)
 {
@@ -73,14 +97,15 @@ static size_t frame_bytes_of(int w, int h, int fmt)
     return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
 }
 
-int dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter, int on_device)
+/* the standalone clip call of both directions (the scaler's tables are dsv1_resample_weights, which are dsv1_scale_weights where
+ * S >= D); the caller has checked the dims against its own limits */
+static int resample_clip_impl(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter,
+                              int on_device)
 {
     dsvg_scaler *sc = NULL;
     void *dsrc = NULL, *ddst = NULL;
     const size_t sfb = frame_bytes_of(sw, sh, subsamp), dfb = frame_bytes_of(dw, dh, subsamp);
     int rc;
-    if (!src || !dst || n < 1 || device < 0 || sw < 1 || sh < 1) return DSVG_ERR_ARG;
-    if ((rc = scale_dims_ok(sw, sh, subsamp, dw, dh, filter))) return rc;
     if ((rc = dsvg_scaler_create(&sc, device, sw, sh, subsamp, 1, &dw, &dh, filter))) return rc;
     if (on_device) rc = dsvg_scaler_run(sc, 0, src, n, dst);
     else {
@@ -92,6 +117,22 @@ int dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, in
     if (!rc) rc = dsvg_scaler_sync(sc);
     dsvg_scaler_destroy(sc);                            /* (frees ddst: the scaler owns what it allocated) */
     return rc;
+}
+
+int dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter, int on_device)
+{
+    int rc;
+    if (!src || !dst || n < 1 || device < 0 || sw < 1 || sh < 1) return DSVG_ERR_ARG;
+    if ((rc = scale_dims_ok(sw, sh, subsamp, dw, dh, filter))) return rc;
+    return resample_clip_impl(device, src, sw, sh, subsamp, n, dst, dw, dh, filter, on_device);
+}
+
+int dsv1_resample_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter, int on_device)
+{
+    int rc;
+    if (!src || !dst || n < 1 || device < 0 || sw < 1 || sh < 1) return DSVG_ERR_ARG;
+    if ((rc = resample_dims_ok(sw, sh, subsamp, dw, dh, filter))) return rc;
+    return resample_clip_impl(device, src, sw, sh, subsamp, n, dst, dw, dh, filter, on_device);
 }
 
 /* ---- resolution ladders ------------------------------------------------------------------------------------------------- */
@@ -111,6 +152,11 @@ struct dsv1_resladder {
     uint64_t *sse;
     int64_t *ssim;
     size_t sse_n, ssim_n;
+    /* source-resolution figures (dsv1_resladder_src_quality_enable): every geometry's ladder measures against the source clip */
+    int sw, sh, xsse_on, xssim_on;
+    uint64_t *xsse;
+    int64_t *xssim;
+    size_t xsse_n, xssim_n;
 };
 
 void dsv1_resladder_close(dsv1_resladder *r)
@@ -119,7 +165,7 @@ void dsv1_resladder_close(dsv1_resladder *r)
     if (!r) return;
     for (g = 0; g < r->ngeom; g++) dsv1_batch_close(r->lad[g]);
     dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated) */
-    free(r->tmp); free(r->sse); free(r->ssim);
+    free(r->tmp); free(r->sse); free(r->ssim); free(r->xsse); free(r->xssim);
     free(r);
 }
 
@@ -167,6 +213,7 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
     r = (dsv1_resladder *)calloc(1, sizeof(*r));
     if (!r) return DSVG_ERR_NOMEM;
     r->ngeom = ngeoms; r->nsrc = nsources; r->F = frames_per_call; r->ntot = ntot;
+    r->sw = src->width; r->sh = src->height;
     r->sfb = frame_bytes_of(src->width, src->height, src->subsamp);
     r->tmp = (DSV_BUF *)calloc((size_t)nsources * maxr, sizeof(DSV_BUF));
     r->sse = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
@@ -238,7 +285,7 @@ static void view_out(dsv1_resladder *r, int g, DSV_BUF *out)
 int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
     const uint8_t *dsrc = (const uint8_t *)yuv;
-    const int nfr = r ? r->nsrc * r->F : 0;
+    const int nfr = r ? r->nsrc * r->F : 0, plain_dev = yuv_on_device == 1;
     int g, rc, par;
     if (!r || !yuv || !out || yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     par = r->parity;
@@ -252,10 +299,18 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         r->up_bytes += bytes;
         r->up_calls++;
         dsrc = (const uint8_t *)d;
+    } else if (yuv_on_device == 1 && (r->xsse_on || r->xssim_on)) {
+        /* the source-resolution figures read the source until collect, and a plain device clip is the caller's again when submit
+         * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip (held) */
+        void *d;
+        if ((rc = dsvg_scaler_copy_in(r->sc, par, yuv, r->sfb * (size_t)nfr, &d))) return rc;
+        dsrc = (const uint8_t *)d;
+        yuv_on_device = DSV1_CLIP_HELD;
     }
     for (g = 0; g < r->ngeom; g++) {
         const void *clip = dsrc;
         int form = yuv_on_device ? yuv_on_device : DSV1_CLIP_HELD;
+        if ((r->xsse_on || r->xssim_on) && (rc = dsv1_batch_xres_source(r->lad[g], dsrc))) return rc;
         if (!r->same[g]) {
             if ((rc = dsvg_scaler_run(r->sc, r->scale_idx[g], dsrc, nfr, r->clip[g][par]))) return rc;
             clip = r->clip[g][par];
@@ -267,8 +322,8 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         view_out(r, g, out);
         if (rc) return rc;
     }
-    /* a plain device clip is the caller's again when submit returns: the scales that read it must have run */
-    if (yuv_on_device == 1 && (rc = dsvg_scaler_sync(r->sc))) return rc;
+    /* a plain device clip is the caller's again when submit returns: the scales (or the copy) that read it must have run */
+    if (plain_dev && (rc = dsvg_scaler_sync(r->sc))) return rc;
     r->pending[par] = 1;
     r->parity ^= 1;
     return DSVG_OK;
@@ -283,6 +338,7 @@ int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)
     if (!r->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
     r->pending[par] = 0;
     r->sse_n = r->ssim_n = 0;
+    r->xsse_n = r->xssim_n = 0;
     for (g = 0; g < r->ngeom; g++) {
         const size_t per = (size_t)3 * r->F;
         view_in(r, g, out);
@@ -292,26 +348,32 @@ int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)
         n = (size_t)r->nsrc * r->nr[g] * per;
         /* the geometry's figures [s * nr + q][t][p] go to [s * Ntot + off + q][t][p] (a ladder measured ... or not) */
         {
-            uint64_t *tmp = (uint64_t *)malloc(sizeof(uint64_t) * n);
-            int64_t *tmp2 = (int64_t *)malloc(sizeof(int64_t) * n);
-            int have_sse, have_ssim;
-            if (!tmp || !tmp2) { free(tmp); free(tmp2); return DSVG_ERR_NOMEM; }
+            uint64_t *tmp = (uint64_t *)malloc(sizeof(uint64_t) * n), *tmp3 = (uint64_t *)malloc(sizeof(uint64_t) * n);
+            int64_t *tmp2 = (int64_t *)malloc(sizeof(int64_t) * n), *tmp4 = (int64_t *)malloc(sizeof(int64_t) * n);
+            int have_sse, have_ssim, have_xsse, have_xssim;
+            if (!tmp || !tmp2 || !tmp3 || !tmp4) { free(tmp); free(tmp2); free(tmp3); free(tmp4); return DSVG_ERR_NOMEM; }
             have_sse = dsv1_batch_get_sse(r->lad[g], tmp, n) == DSVG_OK;
             have_ssim = dsv1_batch_get_ssim(r->lad[g], tmp2, n) == DSVG_OK;
+            have_xsse = r->xsse && dsv1_batch_get_xres_sse(r->lad[g], tmp3, n) == DSVG_OK;
+            have_xssim = r->xssim && dsv1_batch_get_xres_ssim(r->lad[g], tmp4, n) == DSVG_OK;
             for (s = 0; s < r->nsrc; s++)
                 for (q = 0; q < r->nr[g]; q++)
                     for (t = 0; t < (int)per; t++) {
                         const size_t from = (size_t)(s * r->nr[g] + q) * per + t, to = (size_t)(s * r->ntot + r->off[g] + q) * per + t;
                         if (have_sse) r->sse[to] = tmp[from];
                         if (have_ssim) r->ssim[to] = tmp2[from];
+                        if (have_xsse) r->xsse[to] = tmp3[from];
+                        if (have_xssim) r->xssim[to] = tmp4[from];
                     }
-            free(tmp); free(tmp2);
-            if (g == 0) { r->sse_n = have_sse; r->ssim_n = have_ssim; }
-            else { r->sse_n &= (size_t)have_sse; r->ssim_n &= (size_t)have_ssim; }
+            free(tmp); free(tmp2); free(tmp3); free(tmp4);
+            if (g == 0) { r->sse_n = have_sse; r->ssim_n = have_ssim; r->xsse_n = have_xsse; r->xssim_n = have_xssim; }
+            else { r->sse_n &= (size_t)have_sse; r->ssim_n &= (size_t)have_ssim; r->xsse_n &= (size_t)have_xsse; r->xssim_n &= (size_t)have_xssim; }
         }
     }
     if (r->sse_n) r->sse_n = (size_t)3 * r->nsrc * r->ntot * r->F;
     if (r->ssim_n) r->ssim_n = (size_t)3 * r->nsrc * r->ntot * r->F;
+    if (r->xsse_n) r->xsse_n = (size_t)3 * r->nsrc * r->ntot * r->F;
+    if (r->xssim_n) r->xssim_n = (size_t)3 * r->nsrc * r->ntot * r->F;
     return DSVG_OK;
 }
 
@@ -350,6 +412,34 @@ int dsv1_resladder_get_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n)
 {
     if (!r || !ssim_fx || !r->ssim_n || n < r->ssim_n) { dsv1_log(1, "dsv1_resladder_get_ssim: nothing measured, or no room"); return DSVG_ERR_ARG; }
     memcpy(ssim_fx, r->ssim, sizeof(int64_t) * r->ssim_n);
+    return DSVG_OK;
+}
+/* every geometry's ladder measures its pictures upscaled to the source's dims against the source clip (dsv1_batch_xres_*) */
+int dsv1_resladder_src_quality_enable(dsv1_resladder *r, int sse_on, int ssim_on, int filter)
+{
+    int g, rc;
+    const size_t n = r ? (size_t)3 * r->nsrc * r->ntot * r->F : 0;
+    if (!r) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_src_quality_enable with calls in flight"); return DSVG_ERR_ARG; }
+    if (filter != DSV1_SCALE_TENT && filter != DSV1_SCALE_CUBIC) { dsv1_log(1, "dsv1_resladder_src_quality_enable: bad filter %d", filter); return DSVG_ERR_ARG; }
+    if (sse_on && !r->xsse && !(r->xsse = (uint64_t *)calloc(n, sizeof(uint64_t)))) return DSVG_ERR_NOMEM;
+    if (ssim_on && !r->xssim && !(r->xssim = (int64_t *)calloc(n, sizeof(int64_t)))) return DSVG_ERR_NOMEM;
+    for (g = 0; g < r->ngeom; g++)
+        if ((rc = dsv1_batch_xres_enable(r->lad[g], sse_on, ssim_on, r->sw, r->sh, filter))) return rc;
+    r->xsse_on = sse_on != 0;
+    r->xssim_on = ssim_on != 0;
+    return DSVG_OK;
+}
+int dsv1_resladder_get_src_sse(const dsv1_resladder *r, uint64_t *sse, size_t n)
+{
+    if (!r || !sse || !r->xsse_n || n < r->xsse_n) { dsv1_log(1, "dsv1_resladder_get_src_sse: nothing measured, or no room"); return DSVG_ERR_ARG; }
+    memcpy(sse, r->xsse, sizeof(uint64_t) * r->xsse_n);
+    return DSVG_OK;
+}
+int dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n)
+{
+    if (!r || !ssim_fx || !r->xssim_n || n < r->xssim_n) { dsv1_log(1, "dsv1_resladder_get_src_ssim: nothing measured, or no room"); return DSVG_ERR_ARG; }
+    memcpy(ssim_fx, r->xssim, sizeof(int64_t) * r->xssim_n);
     return DSVG_OK;
 }
 int dsv1_resladder_uploads(const dsv1_resladder *r, uint64_t *bytes, long *calls)

@@ -6,7 +6,10 @@
 //     Hs = (H + 128) >> 8                          |Hs| < 2^15 (a row's weights sum to 16384, its negative ones to less than 16384 / 2)
 //     V  = sum_t qv[t] Hs[clamp(sy + t)][x]        |V| <= 2^15 * sum |qv| < 2^15 * 2^15 = 2^30: int32
 //     out = clamp((V + 2^19) >> 20, 0, 255)
-// (tests/test_scale_host.py checks the tighter bound of the worst cubic row: sum |q| of every table generated is far below 2 * 16384.)
+// (tests/test_scale_host.py checks the tighter bound of the worst cubic row: sum |q| of every table generated is far below 2 * 16384;
+// scaler_geo asserts sum |q| < 2 * 16384 for every row it builds.)  The same kernel upscales (dsv1_resample_clip: tables of
+// dsv1_resample_weights, S < D on an axis): a tile then needs at most TH + T rows and 64 + T columns, the bounds hold unchanged
+// (tests/test_resample_host.py), and scaler_geo's exact LDS bound and tile-height choice read the tables whichever way they go.
 //
 // One launch scales every frame and all three planes of a call: blockIdx.y = frame, blockIdx.x = an output tile of 64 x TH samples
 // of one plane (the planes' tiles one after the other).  TH is 64, 32 or 16: the tallest whose LDS fits 64 KB, chosen per geometry
@@ -23,6 +26,7 @@
 // A 16-byte load is issued only for an aligned chunk that holds at least one byte of the row's needed columns: it never leaves the
 // 16-byte block of a sample that exists.
 #include <algorithm>
+#include <cstdlib>
 #include "dsvg_host.hpp"
 
 #define SC_TW 64
@@ -124,8 +128,8 @@ __global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restri
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-extern "C" int dsv1_scale_taps(int S, int D, int filter);
-extern "C" int dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T);
+extern "C" int dsv1_resample_taps(int S, int D, int filter);
+extern "C" int dsv1_resample_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T);
 extern "C" int dsvg_ctx_load_wait(dsvg_ctx *ctx, void *event);
 
 struct ScaleGeo {
@@ -162,14 +166,25 @@ static int scaler_geo(dsvg_scaler *s, int dw, int dh, ScaleGeo &G)
     int tile0 = 0, th_cap = 1, tv_cap = 1;
     long long so = 0, dof = 0;
     for (int p = 0; p < 3; p++) {
-        const int th = dsv1_scale_taps(SW[p], DW[p], s->filter), tv = dsv1_scale_taps(SH[p], DH[p], s->filter);
-        if (th < 0 || tv < 0) { dsvg_set_error("scale %dx%d -> %dx%d: ratio outside 1..8", SW[p], SH[p], DW[p], DH[p]); return DSVG_ERR_ARG; }
+        // (dsv1_resample_*: for a downscale the tables are dsv1_scale_weights'; the callers have checked the direction they allow)
+        const int th = dsv1_resample_taps(SW[p], DW[p], s->filter), tv = dsv1_resample_taps(SH[p], DH[p], s->filter);
+        if (th < 0 || tv < 0) { dsvg_set_error("scale %dx%d -> %dx%d: ratio outside 1/8..8", SW[p], SH[p], DW[p], DH[p]); return DSVG_ERR_ARG; }
         hs[p].resize(DW[p]); hq[p].resize((size_t)DW[p] * th); vs[p].resize(DH[p]); vq[p].resize((size_t)DH[p] * tv);
-        if (dsv1_scale_weights(SW[p], DW[p], s->filter, hs[p].data(), hq[p].data(), th) ||
-            dsv1_scale_weights(SH[p], DH[p], s->filter, vs[p].data(), vq[p].data(), tv)) { dsvg_set_error("weight tables"); return DSVG_ERR_ARG; }
-        // (the kernel's row and column ranges need starts that never decrease)
+        if (dsv1_resample_weights(SW[p], DW[p], s->filter, hs[p].data(), hq[p].data(), th) ||
+            dsv1_resample_weights(SH[p], DH[p], s->filter, vs[p].data(), vq[p].data(), tv)) { dsvg_set_error("weight tables"); return DSVG_ERR_ARG; }
+        // (the kernel's row and column ranges need starts that never decrease; its int32 bounds need sum |q| < 2 * 16384 in every row,
+        // which Catmull-Rom's negative lobes keep in both directions -- asserted for every table built)
         for (int i = 1; i < DW[p]; i++) if (hs[p][i] < hs[p][i - 1]) { dsvg_set_error("weight table starts decrease"); return DSVG_ERR_ARG; }
         for (int i = 1; i < DH[p]; i++) if (vs[p][i] < vs[p][i - 1]) { dsvg_set_error("weight table starts decrease"); return DSVG_ERR_ARG; }
+        for (int tb = 0; tb < 2; tb++) {
+            const std::vector<int16_t> &q = tb ? vq[p] : hq[p];
+            const int T = tb ? tv : th;
+            for (size_t i = 0; i < q.size(); i += (size_t)T) {
+                int a = 0;
+                for (int k = 0; k < T; k++) a += std::abs((int)q[i + k]);
+                if (a >= 2 * 16384) { dsvg_set_error("weight table row outside the kernel's int32 bounds"); return DSVG_ERR_ARG; }
+            }
+        }
         pl[p].sw = SW[p]; pl[p].sh = SH[p]; pl[p].dw = DW[p]; pl[p].dh = DH[p]; pl[p].th = th; pl[p].tv = tv;
         pl[p].soff = so; pl[p].doff = dof;
         so += (long long)SW[p] * SH[p]; dof += (long long)DW[p] * DH[p];
@@ -276,19 +291,28 @@ extern "C" int dsvg_scaler_alloc(dsvg_scaler *s, void **dptr, size_t bytes)
 }
 
 // host clip -> upload buffer `buf` (0 / 1) on the scaler's stream: behind the scales that read the buffer last, in stream order
-extern "C" int dsvg_scaler_upload(dsvg_scaler *s, int buf, const void *host, size_t bytes, void **dptr)
+static int scaler_copy(dsvg_scaler *s, int buf, const void *from, size_t bytes, void **dptr, hipMemcpyKind kind)
 {
-    if (!s || !host || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad scaler upload arguments"); return DSVG_ERR_ARG; }
+    if (!s || !from || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad scaler upload arguments"); return DSVG_ERR_ARG; }
     HIPCHK(hipSetDevice(s->device));
     if (s->up_bytes[buf] < bytes) {
         if (s->up[buf]) { HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipFree(s->up[buf])); s->up[buf] = nullptr; s->up_bytes[buf] = 0; }
         HIPCHK(hipMalloc((void **)&s->up[buf], bytes + 256));
         s->up_bytes[buf] = bytes;
     }
-    HIPCHK(hipMemcpyAsync(s->up[buf], host, bytes, hipMemcpyHostToDevice, s->st));
+    HIPCHK(hipMemcpyAsync(s->up[buf], from, bytes, kind, s->st));
     HIPCHK(hipEventRecord(s->ev, s->st));
     *dptr = s->up[buf];
     return DSVG_OK;
+}
+extern "C" int dsvg_scaler_upload(dsvg_scaler *s, int buf, const void *host, size_t bytes, void **dptr)
+{
+    return scaler_copy(s, buf, host, bytes, dptr, hipMemcpyHostToDevice);
+}
+// the same from device memory (a copy the caller's clip need not outlive)
+extern "C" int dsvg_scaler_copy_in(dsvg_scaler *s, int buf, const void *dev, size_t bytes, void **dptr)
+{
+    return scaler_copy(s, buf, dev, bytes, dptr, hipMemcpyDeviceToDevice);
 }
 
 extern "C" int dsvg_scaler_run(dsvg_scaler *s, int g, const void *src_dev, int nframes, void *dst_dev)

@@ -296,6 +296,16 @@ int  dsv1_scale_weights(int S, int D, int filter, int32_t *start, int16_t *q, in
  * (on_device: src and dst are device pointers).  Synchronous: the frames are in dst when it returns. */
 int  dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter,
                      int on_device);
+/* The same resampler in both directions: on each axis of each plane 1/8 <= S / D <= 8, anamorphic included (an axis may go up while
+ * the other goes down).  The kernel is stretched only to downscale: inv = min(1, D / S), r = ceil(support max(1, S / D)),
+ * T = 2r + 2, taps floor(c) - r .. floor(c) + r + 1 with c = ((2i+1) S - D) / (2D), w = K(|j - c| inv); the same binary64 build,
+ * rint and remainder rule, clamped source indices and two-pass integer arithmetic as above.  Where S >= D the tables ARE
+ * dsv1_scale_weights', bit for bit; S == D is the identity.  Stated in numpy in tests/_resample.py.  dsv1_scale_* keep refusing
+ * S < D. */
+int  dsv1_resample_taps(int S, int D, int filter);           /* T of an axis, or DSVG_ERR_ARG outside the limits */
+int  dsv1_resample_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T);   /* start[D], q[D * T]; host only */
+int  dsv1_resample_clip(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter,
+                        int on_device);               /* as dsv1_scale_clip, every axis of every plane either way */
 
 /* RESOLUTION LADDER: nsources sources of geometry *src, each coded at ngeoms (1..DSV1_MAX_GEOMS) geometries, at every rate rung of
  * that geometry.  rungs[g]: width x height (the format of the source) and nrates (1..DSV1_MAX_RUNGS) DSV_ENCODER rate rungs whose
@@ -308,7 +318,8 @@ int  dsv1_scale_clip(int device, const void *src, int sw, int sh, int subsamp, i
  * Input: [source][frame], nsources x frames_per_call frames of the source geometry, the three forms of dsv1_batch_submit.
  * Refused before any device allocation: a rung larger than the source or below 1 / 8 of it on an axis of a plane, another format,
  * a bad filter, ngeoms outside 1..16, an empty rate list (DSVG_ERR_ARG); a geometry dsv1_batch_open would not accept (its code).
- * Not offered: stage, chain mode, the drop-in dsv_enc, the decoders, upscaling. */
+ * Not offered: stage, chain mode, the drop-in dsv_enc, the decoders, rungs larger than the source.  (Upscaling as such:
+ * dsv1_resample_clip; measuring rungs at the source resolution: dsv1_resladder_src_quality_enable below.) */
 #define DSV1_MAX_GEOMS 16
 typedef struct {
     int width, height;
@@ -332,6 +343,21 @@ int  dsv1_resladder_get_sse(const dsv1_resladder *r, uint64_t *sse, size_t n);
 int  dsv1_resladder_get_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n);
 /* host-to-device bytes the resladder uploaded itself so far (host input: one source clip per call, whatever ngeoms is) and calls */
 int  dsv1_resladder_uploads(const dsv1_resladder *r, uint64_t *bytes, long *calls);
+/* Rungs measured at the SOURCE resolution (opt-in, off after open; the packets are the same with it on or off): every picture's
+ * reconstruction upscaled to the source's plane dims with the dsv1_resample_* tables of `filter` (DSV1_SCALE_*; a geometry of the
+ * source's size goes through the identity tables) and compared with the ORIGINAL source frame of its (source, frame), on the GPU
+ * right behind the picture's reconstruction (k_xres_quality, one pass): per plane the SSE over the source plane area (uint64) and
+ * SSIM_FX over the 8x8 windows at stride 4 of the source plane dims (the definition of dsv1_batch_get_ssim), so the figures of
+ * every geometry are comparable.  Independent of the rung-resolution get_sse / get_ssim: any combination may be on.
+ * src_quality_enable: only between calls (nothing in flight), else DSVG_ERR_ARG; DSVG_ERR_ARG for a bad filter.  get_src_*: the
+ * figures of the call collected last, [(k * frames_per_call + t) * 3 + p]; DSVG_ERR_ARG when that call was not measured or n is
+ * short.  The source is read until the call's collect: host input from the resladder's upload buffer, a DSV1_CLIP_HELD clip in
+ * place (the caller's promise); a plain device clip (yuv_on_device = 1) is the caller's again when submit returns, so with the
+ * measurement on submit first copies it device to device into the resladder's buffer of the call's parity (one clip's bytes of
+ * HBM traffic each way per call; off, nothing is copied). */
+int  dsv1_resladder_src_quality_enable(dsv1_resladder *r, int sse_on, int ssim_on, int filter);
+int  dsv1_resladder_get_src_sse(const dsv1_resladder *r, uint64_t *sse, size_t n);
+int  dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n);
 
 /* ---- extension: batched decoding (dsv_dec decodes one picture per call, dsv_decoder.c:286-472) ----
  * nstreams independent streams of one geometry; every call takes ONE packet per stream (packets[s]: not freed, not

@@ -296,6 +296,20 @@ int dsvg_fetch_sse(dsvg_ctx *ctx, int n, const int *out_slots, uint64_t *sse_out
 #define DSVG_SSIM_ONE 4294967296LL   /* 2^32: the fixed-point scale of one window's SSIM */
 int dsvg_ctx_ssim_enable(dsvg_ctx *ctx, int on);
 int dsvg_fetch_ssim(dsvg_ctx *ctx, int n, const int *out_slots, int64_t *ssim_out);
+/* Source-resolution quality (opt-in, encoder; resolution ladders, dsv1_resladder_src_quality_enable): every picture of a call that
+ * starts afterwards is, for each out slot given a reference frame with dsvg_ctx_xres_refs before that call, upscaled on the device
+ * from its reconstruction to the reference geometry ref_w x ref_h (the same format; at least the picture's size on every axis of
+ * every plane, at most 8 times it) with the dsv1_resample_* tables of `filter`, and compared with that frame: per plane the SSE over
+ * the reference plane and the SSIM_FX over its windows, with the definitions of the two pairs above.  Independent of them.  Off
+ * (sse_on = ssim_on = 0) nothing of it runs.  A change of geometry or filter rebuilds the tables and forgets the frames set.
+ * dsvg_ctx_xres_refs: out slot out_slots[i] of the next call that codes it is measured against the packed planar frame
+ * ref_clip + frames[i] * (reference frame bytes), device memory the caller keeps unchanged until that call's pictures are fetched;
+ * the call takes the setting (a slot not set again is not measured next time).  Fetch as dsvg_fetch_sse / _ssim; DSVG_ERR_ARG for
+ * a slot whose picture was not measured. */
+int dsvg_ctx_xres_enable(dsvg_ctx *ctx, int sse_on, int ssim_on, int ref_w, int ref_h, int filter);
+int dsvg_ctx_xres_refs(dsvg_ctx *ctx, const void *ref_clip, int n, const int *out_slots, const int *frames);
+int dsvg_fetch_xres_sse(dsvg_ctx *ctx, int n, const int *out_slots, uint64_t *sse_out);
+int dsvg_fetch_xres_ssim(dsvg_ctx *ctx, int n, const int *out_slots, int64_t *ssim_out);
 int dsvg_download_recon(dsvg_ctx *ctx, int recon_slot, uint8_t *yuv_out);            /* syncs */
 /* the first `bytes` bytes of the slot's whole frame allocation in the reference layout (dsv_mk_frame frame.c:63-120:
  * Y,U,V back to back, 64-px replicated borders): what the next picture's motion compensation reads.  Syncs. */
