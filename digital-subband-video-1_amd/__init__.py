@@ -41,6 +41,17 @@ class Buf(_C.Structure):
     _fields_ = [("data", _C.POINTER(_C.c_uint8)), ("len", _C.c_uint)]
 
 
+class Dispatch(_C.Structure):
+    """dsvg_dispatch (include/dsvg.h): the branches the encoder's forward launchers take"""
+    _fields_ = [("blk_w", _C.c_int), ("blk_h", _C.c_int), ("fusable", _C.c_int), ("fwd", _C.c_int * 2), ("hme_levels", _C.c_int),
+                ("hme", (_C.c_int * 4) * 6), ("csum", _C.c_int), ("tail_threads", _C.c_int), ("scan_threads", _C.c_int)]
+
+    def as_dict(self):
+        n = self.hme_levels + 1
+        return {"blk": (self.blk_w, self.blk_h), "fusable": self.fusable, "fwd": tuple(self.fwd), "csum": self.csum, "threads": (self.tail_threads, self.scan_threads),
+                "hme": tuple(tuple(self.hme[l]) for l in range(max(n, 0)))}
+
+
 class ResRung(_C.Structure):
     """dsv1_res_rung: one geometry of a resolution ladder and its rate rungs"""
     _fields_ = [("width", _C.c_int), ("height", _C.c_int), ("nrates", _C.c_int), ("rates", _C.POINTER(Encoder))]
@@ -143,6 +154,8 @@ def lib():
         L.dsv1_resladder_src_quality_enable.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_resladder_get_src_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
         L.dsv1_resladder_get_src_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
+        L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
+        L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         _lib = L
     return _lib
 
@@ -150,6 +163,20 @@ def lib():
 def _chk(rc, what):
     if rc != 0:
         raise RuntimeError("%s failed rc=%d: %s" % (what, rc, lib().dsvg_last_error().decode()))
+
+
+def dispatch_last():
+    """what launch_fwd_sbt / launch_hme last decided in this process (dict, see Dispatch)"""
+    d = Dispatch()
+    _chk(lib().dsvg_dispatch_last(_C.byref(d)), "dsvg_dispatch_last")
+    return d.as_dict()
+
+
+def dispatch_plan(w, h, fmt):
+    """what they decide for an encoder of this geometry; needs no device"""
+    d = Dispatch()
+    _chk(lib().dsvg_dispatch_plan(w, h, fmt, _C.byref(d)), "dsvg_dispatch_plan")
+    return d.as_dict()
 
 
 def make_encoder_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1, kbps=0, scd=1, ipct=50, pyrlevels=0, stabref=0,

@@ -1,6 +1,7 @@
 // dsvg_common.hip -- geometry / quantiser derivation and small runtime helpers (host side of the shim).
 #include <stdarg.h>
 #include <stdlib.h>
+#include <atomic>
 #include "dsvg_host.hpp"
 
 static thread_local char g_err[512] = "";
@@ -217,6 +218,41 @@ int auto_pyramid_levels(int w, int h, int nbh, int nbv)
     const int nb = nbh > nbv ? nbh : nbv;
     while ((1 << lv) > nb) lv--;
     return lv < 3 ? 3 : (lv > DSVG_MAX_PYRAMID ? DSVG_MAX_PYRAMID : lv);
+}
+
+// What launch_fwd_sbt / launch_hme last decided (dsvg_dispatch_last): plain ints behind relaxed atomics -- the coding streams'
+// enqueue threads note the same values side by side
+static struct {
+    std::atomic<int> blk_w{-1}, blk_h{-1}, fwd[2] = {{-1}, {-1}}, hme_levels{-1}, hme[DSVG_MAX_PYRAMID + 1][4], csum{-1}, tail_threads{-1}, scan_threads{-1};
+} g_dispatch;
+void dispatch_note_fwd(int group, int mask) { g_dispatch.fwd[group].store(mask, std::memory_order_relaxed); }
+void dispatch_note_threads(int tail, int scan)
+{
+    if (tail > 0) g_dispatch.tail_threads.store(tail, std::memory_order_relaxed);
+    if (scan > 0) g_dispatch.scan_threads.store(scan, std::memory_order_relaxed);
+}
+void dispatch_note_csum(int csum) { g_dispatch.csum.store(csum, std::memory_order_relaxed); }
+void dispatch_note_hme(const HmeArgs &A, int level, const HmeLevelPlan &P)
+{
+    if (level < 0 || level > DSVG_MAX_PYRAMID) return;
+    g_dispatch.blk_w.store(A.blk_w, std::memory_order_relaxed); g_dispatch.blk_h.store(A.blk_h, std::memory_order_relaxed);
+    g_dispatch.hme_levels.store(A.levels, std::memory_order_relaxed);
+    const int v[4] = {P.nkbf, P.fullx, P.fully, P.parts};
+    for (int i = 0; i < 4; i++) g_dispatch.hme[level][i].store(v[i], std::memory_order_relaxed);
+}
+extern "C" int dsvg_dispatch_last(dsvg_dispatch *out)
+{
+    if (!out) { dsvg_set_error("null argument"); return DSVG_ERR_ARG; }
+    out->blk_w = g_dispatch.blk_w.load(std::memory_order_relaxed); out->blk_h = g_dispatch.blk_h.load(std::memory_order_relaxed);
+    for (int g = 0; g < 2; g++) out->fwd[g] = g_dispatch.fwd[g].load(std::memory_order_relaxed);
+    out->fusable = out->fwd[0] >= 0;                 // (the fused path notes a mask, the other one -1)
+    out->hme_levels = g_dispatch.hme_levels.load(std::memory_order_relaxed);
+    for (int l = 0; l <= DSVG_MAX_PYRAMID; l++)
+        for (int i = 0; i < 4; i++) out->hme[l][i] = l <= out->hme_levels ? g_dispatch.hme[l][i].load(std::memory_order_relaxed) : 0;
+    out->csum = g_dispatch.csum.load(std::memory_order_relaxed);
+    out->tail_threads = g_dispatch.tail_threads.load(std::memory_order_relaxed);
+    out->scan_threads = g_dispatch.scan_threads.load(std::memory_order_relaxed);
+    return DSVG_OK;
 }
 
 int Slab::alloc(size_t n, bool zero)

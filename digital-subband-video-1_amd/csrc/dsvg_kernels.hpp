@@ -43,6 +43,16 @@ void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3
                     const struct McGeo *mc = nullptr, const DMV *mvs0 = nullptr,    // mc: motion compensation fused into the P forward transform
                     int general_whole = 1);   // mc: 0 = the caller knows that no block of these pictures is intra (the general kernel then only runs on the strips of the grid the geometry asks for)
 bool mc_fusable(const struct McGeo &MG);
+// the decisions of launch_fwd_sbt (general kernel: a mask of DSVG_FWD_*) and launch_hme (per level; csum: see dsvg_dispatch), as
+// functions of the geometry alone, and where the launchers note what they last decided (dsvg_dispatch_last / dsvg_dispatch_plan)
+int  fwd_general_mask(const SbtGeo3 &G, const struct McGeo &mc, int c0, int npl, int general_whole);
+struct HmeLevelPlan { int nkbf, fullx, fully, nfull, nrest, parts; };
+HmeLevelPlan hme_level_plan(const struct HmeArgs &A, int level);
+int  hme_csum_plan(const struct HmeArgs &A, int *fullx, int *fully);
+void dispatch_note_fwd(int group, int mask);
+void dispatch_note_hme(const struct HmeArgs &A, int level, const HmeLevelPlan &P);
+void dispatch_note_csum(int csum);
+void dispatch_note_threads(int tail, int scan);      // the workgroup sizes launch_tail_q / the k_hz_scan launch took (0: not this one)
 void launch_inv_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, Prof *pf = nullptr, int with_tail = 1,
                     int insym = 0, int patch_kernel = 0,    // patch_kernel: sparse P pictures (flags valid, prediction given): unfiltered planes take k_inv_patch_c
                     int fuse_border = 0);                   // the kernels also write the reconstruction's border (JobDev.ext) where inv_sbt_fuses_border says they can

@@ -495,6 +495,44 @@ extern "C" int dsvg_geom_check(int width, int height, int subsamp)
     return DSVG_OK;
 }
 
+// What the forward launchers decide for an encoder context of this geometry (default block size and pyramid depth, the chroma
+// table of the motion search on): the geometry tables of dsvg_ctx_create_blk below, handed to the launchers' own decision functions
+extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out)
+{
+    if (!out) { dsvg_set_error("null argument"); return DSVG_ERR_ARG; }
+    const int rc = dsvg_geom_check(width, height, subsamp);
+    if (rc) return rc;
+    memset(out, 0, sizeof(*out));
+    int nbh, nbv;
+    block_geometry(width, height, &out->blk_w, &out->blk_h, &nbh, &nbv);
+    HmeArgs A; memset(&A, 0, sizeof(A));
+    A.levels = auto_pyramid_levels(width, height, nbh, nbv);
+    make_frame_layout(A.L[0], subsamp, width, height);
+    for (int l = 1; l <= A.levels; l++) make_frame_layout(A.L[l], subsamp, rsu(width, l), rsu(height, l));
+    A.nxb = nbh; A.nyb = nbv; A.nblk = nbh * nbv; A.blk_w = out->blk_w; A.blk_h = out->blk_h;
+    CoefLayout CL;
+    make_coef_layout(CL, subsamp, width, height);
+    SbtGeo3 G;
+    McGeo MG; memset(&MG, 0, sizeof(MG));
+    MG.blk_w = out->blk_w; MG.blk_h = out->blk_h; MG.nbh = nbh; MG.nbv = nbv; MG.hs = A.L[0].hs; MG.vs = A.L[0].vs;
+    for (int p = 0; p < 3; p++) {
+        make_sbt_geo(G.g[p], CL.w[p], CL.h[p], A.L[0].w[p], A.L[0].h[p], A.L[0].stride[p], A.L[0].off[p], CL.off[p], CL.s3off[p], CL.s1off[p], CL.s5off[p]);
+        MG.w[p] = A.L[0].w[p]; MG.h[p] = A.L[0].h[p]; MG.stride[p] = A.L[0].stride[p];
+    }
+    out->fusable = mc_fusable(MG) ? 1 : 0;
+    // (code_batch_impl passes general_whole from the pictures' intra blocks; with FWD_FAST_INTRA it does not enter the decision)
+    for (int g = 0; g < 2; g++) out->fwd[g] = out->fusable ? fwd_general_mask(G, MG, g ? 1 : 0, g ? 2 : 1, 0) : -1;
+    out->hme_levels = A.levels;
+    for (int l = 0; l <= A.levels; l++) {
+        const HmeLevelPlan P = hme_level_plan(A, l);
+        out->hme[l][0] = P.nkbf; out->hme[l][1] = P.fullx; out->hme[l][2] = P.fully; out->hme[l][3] = P.parts;
+    }
+    int fullx, fully;
+    out->csum = hme_csum_plan(A, &fullx, &fully);
+    out->tail_threads = out->scan_threads = -1;      // (a function of the jobs per launch, not of the geometry)
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_ctx_create(dsvg_ctx **out, int device, int width, int height, int subsamp,
                                int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots)
 {

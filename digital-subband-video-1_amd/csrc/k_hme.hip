@@ -1462,18 +1462,48 @@ __global__ __launch_bounds__(256) void k_hme_detail(HmeArgs A)
     mf[b].high_detail = (tex > thr_tex && var > thr_var) ? 1 : 0;
 }
 
+// The decisions of launch_hme as functions of the geometry alone (dsvg_dispatch_plan asks them without a device).
+// k_hme_csum: 0 = not launched (no table, or no full level-0 blocks, as the level loop defines them), 1 = launched, 2 = launched
+// and every workgroup returns at once (the part of the kernel's own test that the host can see)
+int hme_csum_plan(const HmeArgs &A, int *fullx, int *fully)
+{
+    const bool fullb = A.blk_w == 64 && (A.blk_h == 64 || A.blk_h == 48 || A.blk_h == 32) && (A.L[0].stride[0] & 3) == 0;
+    *fullx = fullb ? std::min(A.nxb, A.L[0].w[0] / 64) : 0; *fully = fullb ? std::min(A.nyb, A.L[0].h[0] / A.blk_h) : 0;
+    if (!(*fullx > 0 && *fully > 0)) return 0;
+    return (((A.blk_w >> A.L[0].hs) & 15) || *fullx > 64) ? 2 : 1;
+}
+
+HmeLevelPlan hme_level_plan(const HmeArgs &A, int level)
+{
+    const int step = 1 << level;
+    const int nvx = (A.nxb + step - 1) / step, nvy = (A.nyb + step - 1) / step;
+    HmeLevelPlan P;
+    // rows per lane of a full block (64 wide, blk_h = 4 * rows): those blocks take the specialised body, in a launch of
+    // their own; the partial blocks at the right / bottom edge of the level's frame the generic one
+    P.nkbf = (A.blk_w == 64 && (A.blk_h == 64 || A.blk_h == 48 || A.blk_h == 32) && (A.L[level].stride[0] & 3) == 0) ? A.blk_h / 4 : 0;
+    const int fw = A.L[level].w[0], fh = A.L[level].h[0];
+    P.fullx = P.nkbf ? std::min(nvx, fw / 64) : 0; P.fully = P.nkbf ? std::min(nvy, fh / A.blk_h) : 0;
+    P.nfull = P.fullx * P.fully; P.nrest = nvx * nvy - P.nfull;
+    if (P.nfull > 0 && level > 0) P.parts = 1 << 3;
+    else if (P.nfull > 0) P.parts = (1 << 1) | (P.nrest > 0 ? 1 << 2 : 0);
+    else P.parts = 1 << 0;
+    return P;
+}
+
 void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf)
 {
+    int csum = 0;
     if (A.csum) {
         // (full level-0 blocks, as the level loop below defines them)
-        const bool fullb = A.blk_w == 64 && (A.blk_h == 64 || A.blk_h == 48 || A.blk_h == 32) && (A.L[0].stride[0] & 3) == 0;
-        const int fullx = fullb ? std::min(A.nxb, A.L[0].w[0] / 64) : 0, fully = fullb ? std::min(A.nyb, A.L[0].h[0] / A.blk_h) : 0;
-        if (fullx > 0 && fully > 0) {
+        int fullx, fully;
+        csum = hme_csum_plan(A, &fullx, &fully);
+        if (csum) {
             if (pf) pf->begin(st, KID_HME_CSUM, (double)npairs * ((double)A.L[0].w[1] * A.L[0].h[1] + (double)A.L[0].w[2] * A.L[0].h[2]));      // every frame's chroma once
             hipLaunchKernelGGL(k_hme_csum, dim3(fully, 2 * npairs), dim3(256), 0, st, A, fullx, fully);
             if (pf) pf->end(st);
         }
     }
+    dispatch_note_csum(csum);
     for (int level = A.levels; level >= 0; level--) {
         const int step = 1 << level;
         const int nvx = (A.nxb + step - 1) / step, nvy = (A.nyb + step - 1) / step;
@@ -1482,19 +1512,16 @@ void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf)
             px += 2.0 * npairs * ((double)A.L[0].w[1] * A.L[0].h[1] + (double)A.L[0].w[2] * A.L[0].h[2]);
         if (pf) pf->begin(st, level > 0 ? KID_HME_LEVEL : KID_HME_LEVEL0, px);
         const dim3 blk(NT * HME_WPG);
-        // rows per lane of a full block (64 wide, blk_h = 4 * rows): those blocks take the specialised body, in a launch of
-        // their own; the partial blocks at the right / bottom edge of the level's frame the generic one
-        const int nkbf = (A.blk_w == 64 && (A.blk_h == 64 || A.blk_h == 48 || A.blk_h == 32) && (A.L[level].stride[0] & 3) == 0) ? A.blk_h / 4 : 0;
-        const int fw = A.L[level].w[0], fh = A.L[level].h[0];
-        const int fullx = nkbf ? std::min(nvx, fw / 64) : 0, fully = nkbf ? std::min(nvy, fh / A.blk_h) : 0;
-        const int nfull = fullx * fully, nrest = nvx * nvy - nfull;
+        const HmeLevelPlan lp = hme_level_plan(A, level);
+        dispatch_note_hme(A, level, lp);
+        const int nkbf = lp.nkbf, fullx = lp.fullx, fully = lp.fully, nfull = lp.nfull, nrest = lp.nrest;
         auto uinv = [](int d) { return (unsigned)std::min<unsigned long long>(0x100000000ull / (unsigned long long)std::max(d, 1), 0xffffffffull); };
         // (inv_row: the row length the launch's block index is split by -- PART 1: fullx; PART 0 / 3: nvx; PART 2 divides by its two strip widths itself)
 #define HME_LAUNCH(L0, N, P, cnt) hipLaunchKernelGGL((k_hme_level<L0, N, P>), dim3(xcd_grid(((cnt) * npairs + HME_WPG - 1) / HME_WPG)), blk, 0, st, A, level, npairs, fullx, fully, \
                                                      uinv(cnt), uinv((P) == 1 ? fullx : nvx))
 #define HME_FULL(L0) do { switch (nkbf) { case 16: HME_LAUNCH(L0, 16, 1, nfull); break; case 12: HME_LAUNCH(L0, 12, 1, nfull); break; \
                                           default: HME_LAUNCH(L0, 8, 1, nfull); } } while (0)
-        (void)nrest;
+        // (the branches below are the ones hme_level_plan names in its `parts`)
         if (nfull > 0 && level > 0) {
             switch (nkbf) { case 16: HME_LAUNCH(false, 16, 3, nvx * nvy); break; case 12: HME_LAUNCH(false, 12, 3, nvx * nvy); break;
                             default: HME_LAUNCH(false, 8, 3, nvx * nvy); }

@@ -1761,6 +1761,7 @@ void launch_hz_pack(hipStream_t st, const JobDev *jobs, int njobs, int job_chunk
     }
     PB(KID_HZ_SCAN, 0.0);
     // few workgroups (small batches: a link of a latency-bound chain): 1024 threads per plane; many: 256 (see above)
+    dispatch_note_threads(0, 3 * njobs <= 96 ? 1024 : SCAN_THREADS);
     if (3 * njobs <= 96) hipLaunchKernelGGL((k_hz_scan<1024>), dim3(3, njobs), dim3(1024), 0, st, jobs);
     else hipLaunchKernelGGL((k_hz_scan<SCAN_THREADS>), dim3(3, njobs), dim3(SCAN_THREADS), 0, st, jobs);
     PE();

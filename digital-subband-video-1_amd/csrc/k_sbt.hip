@@ -3284,6 +3284,27 @@ void launch_fwd_mid4(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo
     PE();
 }
 
+// Where launch_fwd_sbt sends the general kernel of planes [c0, c0+npl) of a P picture: a mask of DSVG_FWD_* (include/dsvg.h)
+int fwd_general_mask(const SbtGeo3 &G, const McGeo &mc, int c0, int npl, int general_whole)
+{
+    bool whole = general_whole != 0 && !FWD_FAST_INTRA, top = false, bottom = false, left = false, right = false;
+    for (int c = c0; c < c0 + npl; c++) {
+        const SbtGeo &gc = G.g[c];
+        const int sw0 = DSVG_RSU(gc.W, 3), sw1 = DSVG_RSU(gc.W, 2), sw2 = DSVG_RSU(gc.W, 1);
+        const int sh0 = DSVG_RSU(gc.H, 3), sh1 = DSVG_RSU(gc.H, 2), sh2 = DSVG_RSU(gc.H, 1);
+        left = left || 2 * sw0 > sw1 || 2 * sw1 > sw2;
+        top = top || 2 * sh0 > sh1 || 2 * sh1 > sh2;
+        right = right || (mc.w[c] & 7);
+        bottom = bottom || (gc.ph & 7);
+        const int d1 = (mc.nbh << 14) / sw2, d2 = (mc.nbh << 14) / sw1;       // HzRegion.dbx of transform levels 1, 2
+        for (int I = 0; I < gc.w3 && !whole; I++)
+            whole = ((4 * I * d1) >> 14) != (((4 * I + 3) * d1) >> 14) || ((2 * I * d2) >> 14) != (((2 * I + 1) * d2) >> 14);
+    }
+    const dim3 full = grid3(G.g[c0].w3, G.g[c0].h3, 1);
+    return (whole ? DSVG_FWD_WHOLE : 0) | (top ? DSVG_FWD_TOP : 0) | (bottom ? DSVG_FWD_BOTTOM : 0) | (left ? DSVG_FWD_LEFT : 0) |
+           (right ? DSVG_FWD_RIGHT : 0) | (full.y == 1 ? DSVG_FWD_ROW1 : 0) | (full.x == 1 ? DSVG_FWD_COL1 : 0);
+}
+
 void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP,
                     int from_src, Prof *pf, int with_tail, int fused, const McGeo *mc, const DMV *mvs0, int general_whole)
 {
@@ -3305,19 +3326,9 @@ void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3
         // last row or column of patches (cells shared between scan regions, a ragged picture edge) -- unless a patch can
         // span two columns of the stability map, which depends on the geometry alone.  The general kernel is launched
         // over the whole grid, over the strips that can hold such patches, or not at all.
-        bool whole = general_whole != 0 && !FWD_FAST_INTRA, top = false, bottom = false, left = false, right = false;
-        for (int c = c0; c < c0 + npl; c++) {
-            const SbtGeo &gc = G.g[c];
-            const int sw0 = DSVG_RSU(gc.W, 3), sw1 = DSVG_RSU(gc.W, 2), sw2 = DSVG_RSU(gc.W, 1);
-            const int sh0 = DSVG_RSU(gc.H, 3), sh1 = DSVG_RSU(gc.H, 2), sh2 = DSVG_RSU(gc.H, 1);
-            left = left || 2 * sw0 > sw1 || 2 * sw1 > sw2;
-            top = top || 2 * sh0 > sh1 || 2 * sh1 > sh2;
-            right = right || (mc->w[c] & 7);
-            bottom = bottom || (gc.ph & 7);
-            const int d1 = (mc->nbh << 14) / sw2, d2 = (mc->nbh << 14) / sw1;       // HzRegion.dbx of transform levels 1, 2
-            for (int I = 0; I < gc.w3 && !whole; I++)
-                whole = ((4 * I * d1) >> 14) != (((4 * I + 3) * d1) >> 14) || ((2 * I * d2) >> 14) != (((2 * I + 1) * d2) >> 14);
-        }
+        const int gm = fwd_general_mask(G, *mc, c0, npl, general_whole);
+        dispatch_note_fwd(c0 != 0, gm);
+        const bool whole = gm & DSVG_FWD_WHOLE, top = gm & DSVG_FWD_TOP, bottom = gm & DSVG_FWD_BOTTOM, left = gm & DSVG_FWD_LEFT, right = gm & DSVG_FWD_RIGHT;
         const dim3 full = grid3(g.w3, g.h3, nz);
         auto general = [&](dim3 gr, int bxo, int byo, int bxs, int bys) {
             PB(c0 == 0 ? KID_FWD_MC_PIX_Y : KID_FWD_MC_PIX_C, 0.0);
@@ -3339,6 +3350,7 @@ void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3
             else if (right) general(dim3(1, full.y, nz), fx - 1, 0, 1, 1);
         }
     } else if (isP) {
+        dispatch_note_fwd(c0 != 0, -1);
         PB(fused ? KID_FWD_HAAR_PIX_Q : KID_FWD_HAAR_PIX, smp * (fused ? 3.0 : 5.0));   // 1 B/sample in, 4 B/sample out (details + LL3); fused: 2 B symbols
         if (fused) hipLaunchKernelGGL((k_fwd_haar_pix<true>), grid3(g.w3, g.h3, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, from_src);
         else       hipLaunchKernelGGL((k_fwd_haar_pix<false>), grid3(g.w3, g.h3, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, from_src);
@@ -3390,6 +3402,7 @@ void launch_tail_q(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 
     PB(KID_TAIL_Q, s3 * 8.0);
     // few workgroups (a small batch: the kernel is a link of a latency-bound chain): 1024 threads per band; many: 256 -- a
     // 16-wave workgroup would wait for a whole CU's worth of free wave slots beside the other coding stream's kernels
+    dispatch_note_threads(njobs * npl <= 96 ? 1024 : TAIL_THREADS, 0);
     if (njobs * npl <= 96) hipLaunchKernelGGL((k_tail_q<1024>), dim3(njobs * npl), dim3(1024), lds, st, jobs, G, c0, npl);
     else hipLaunchKernelGGL((k_tail_q<TAIL_THREADS>), dim3(njobs * npl), dim3(TAIL_THREADS), lds, st, jobs, G, c0, npl);
     PE();

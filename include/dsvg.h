@@ -377,6 +377,38 @@ int dsvg_prof_enable(dsvg_ctx *ctx, unsigned long long kernel_mask);
 int dsvg_prof_reset(dsvg_ctx *ctx);
 int dsvg_prof_get(dsvg_ctx *ctx, int kid, double *ms, long *launches, double *alg_bytes);
 
+/* Which branch the encoder's forward launchers take (tests): read-only, host side, no effect on coding.
+ * fwd[g]: the general kernel (k_fwd_mc_pix) of a P picture's plane group g (0 luma, 1 the chroma pair) -- a mask of DSVG_FWD_*:
+ * the facts (WHOLE, or the strips TOP / BOTTOM / LEFT / RIGHT that can hold patches the lean kernel leaves) and the shape of the
+ * grid (ROW1 / COL1: one row / one column of thread blocks, which a strip pair collapses to); -1: not decided (no P picture yet,
+ * or motion compensation not fused).  hme[l] = {NKBF of the register body or 0, fullx, fully, mask of the PARTs launched (bit p =
+ * PART p)} of motion-search level l; csum: 0 = k_hme_csum not launched, 1 = launched, 2 = launched and every workgroup returns
+ * at once for reasons the host knows (fullx > 64, chroma block width not a multiple of 16), -1: not decided.
+ * tail_threads / scan_threads: the workgroup size of the last k_tail_q / k_hz_scan launch (1024 for few jobs per launch, else 256).
+ * dsvg_dispatch_last: what launch_fwd_sbt / launch_hme / launch_tail_q / the scan launch last decided in this process (the
+ * launchers fill it in; fusable: whether the last P plane group took the fused kernels).
+ * dsvg_dispatch_plan: what they decide for an encoder context of this geometry, without a device -- the launchers' own decision
+ * functions on geometry tables built as dsvg_ctx_create builds them (a second set-up of the same tables: what ties it to a live
+ * context is the comparison of both queries on the GPU); tail_threads / scan_threads = -1 (they depend on the jobs per launch). */
+#define DSVG_FWD_WHOLE  1
+#define DSVG_FWD_TOP    2
+#define DSVG_FWD_BOTTOM 4
+#define DSVG_FWD_LEFT   8
+#define DSVG_FWD_RIGHT  16
+#define DSVG_FWD_ROW1   32
+#define DSVG_FWD_COL1   64
+typedef struct dsvg_dispatch {
+    int blk_w, blk_h;
+    int fusable;                              /* mc_fusable: P pictures take k_fwd_mc_fast + k_fwd_mc_pix */
+    int fwd[2];
+    int hme_levels;                           /* the pyramid's levels above level 0 */
+    int hme[DSVG_MAX_PYRAMID + 1][4];
+    int csum;
+    int tail_threads, scan_threads;
+} dsvg_dispatch;
+int dsvg_dispatch_last(dsvg_dispatch *out);
+int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out);
+
 #ifdef __cplusplus
 }
 #endif
