@@ -57,6 +57,18 @@ class ResRung(_C.Structure):
     _fields_ = [("width", _C.c_int), ("height", _C.c_int), ("nrates", _C.c_int), ("rates", _C.POINTER(Encoder))]
 
 
+PIX_PLANAR, PIX_SEMIPLANAR_UV, PIX_SEMIPLANAR_VU, PIX_PACKED_YUYV, PIX_PACKED_UYVY = 0, 1, 2, 3, 4   # DSV1_PIX_*
+
+
+class PixFormat(_C.Structure):
+    """dsv1_pix_format: how a source clip lies in memory -- layout (PIX_*), depth (8, 10, 12, 16; above 8: little-endian 16-bit words),
+    msb_aligned (P010: 1, yuv420p10le: 0), row pitches in bytes (0 = tight) and the bytes from frame to frame (0 = tight)"""
+    _fields_ = [("layout", _C.c_int), ("depth", _C.c_int), ("msb_aligned", _C.c_int), ("pitch", _C.c_int * 3), ("frame_bytes", _C.c_size_t)]
+
+    def __init__(self, layout=PIX_PLANAR, depth=8, msb_aligned=0, pitch=(0, 0, 0), frame_bytes=0):
+        super().__init__(layout, depth, msb_aligned, (_C.c_int * 3)(*pitch), frame_bytes)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -154,6 +166,12 @@ def lib():
         L.dsv1_resladder_src_quality_enable.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_resladder_get_src_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
         L.dsv1_resladder_get_src_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
+        L.dsv1_pix_frame_bytes.restype = _C.c_size_t
+        L.dsv1_pix_frame_bytes.argtypes = [_C.POINTER(PixFormat), _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_convert_clip.argtypes = [_C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int]
+        L.dsv1_batch_set_source_format.argtypes = [_C.c_void_p, _C.POINTER(PixFormat)]
+        L.dsv1_resladder_open_src.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(PixFormat), _C.POINTER(ResRung), _C.c_int,
+                                              _C.c_int, _C.c_int, _C.c_int, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         _lib = L
@@ -277,6 +295,13 @@ class Batch:
 
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
+
+    def set_source_format(self, pf):
+        """from the next submit on, encode() / submit() take clips of PixFormat pf (dsv1_batch_set_source_format), converted on the
+        GPU; None switches back to packed planar 8-bit.  Between batches only.  The input-length check follows the format."""
+        _chk(self.L.dsv1_batch_set_source_format(self.h, _C.byref(pf) if pf is not None else None), "dsv1_batch_set_source_format")
+        planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, self.fmt)
+        self.frame_bytes = pix_frame_bytes(pf, self.width, self.height, self.fmt) if pf is not None else planar
 
     def dropped_recons(self):
         """(dropped, remedied): reference pictures coded without a reconstruction because nobody predicts from them / coded again
@@ -523,6 +548,33 @@ MAX_GEOMS = 16   # DSV1_MAX_GEOMS
 SCALE_TENT, SCALE_CUBIC = 0, 1   # DSV1_SCALE_TENT, DSV1_SCALE_CUBIC
 
 
+def pix_frame_bytes(pf, w, h, fmt):
+    """bytes from frame to frame of a clip of PixFormat pf (dsv1_pix_frame_bytes); ValueError for an invalid combination"""
+    n = lib().dsv1_pix_frame_bytes(_C.byref(pf), w, h, fmt)
+    if not n:
+        raise ValueError("not a valid pixel format for %dx%d frames of subsampling 0x%x" % (w, h, fmt))
+    return int(n)
+
+
+def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None):
+    """convert frames of PixFormat pf to packed planar 8-bit on the GPU (dsv1_convert_clip): clip numpy uint8 [frames][frame bytes]
+    (host), or a device pointer with n frames and `out` a device pointer for the result.  Host input returns numpy uint8
+    [frames][planar frame_bytes]."""
+    L = lib()
+    sfb = pix_frame_bytes(pf, w, h, fmt)
+    dfb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_convert_clip(device, clip, _C.byref(pf), w, h, fmt, n, out, 1), "dsv1_convert_clip")
+        return out
+    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
+    if a.size % sfb or not a.size:
+        raise ValueError("a clip of this format is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
+    frames = a.size // sfb
+    res = _np.zeros((frames, dfb), dtype=_np.uint8)
+    _chk(L.dsv1_convert_clip(device, a.ctypes.data, _C.byref(pf), w, h, fmt, frames, res.ctypes.data, 0), "dsv1_convert_clip")
+    return res
+
+
 def scale_taps(S, D, filt):
     """taps of one axis of the resampler (dsv1_scale_taps); ValueError outside 1 <= S / D <= 8"""
     t = lib().dsv1_scale_taps(S, D, filt)
@@ -598,7 +650,8 @@ class ResLadder:
     SOURCE clip [source][frame] (nsources x F frames of w x h: one upload per call); results are per output stream
     k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
 
-    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0):
+    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None):
+        """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit)"""
         geoms = [(gw, gh, list(rates)) for gw, gh, rates in geoms]
         self.L = lib()
         self.h = _C.c_void_p(None)
@@ -609,11 +662,15 @@ class ResLadder:
         rr = (ResRung * max(len(geoms), 1))(*[ResRung(gw, gh, len(r), a) for (gw, gh, r), a in zip(geoms, self._arrs)])
         meta = Meta()
         meta.width, meta.height, meta.subsamp = w, h, fmt
-        _chk(self.L.dsv1_resladder_open(_C.byref(self.h), _C.byref(meta), rr, len(geoms), device, nsources, frames_per_call, filt),
-             "dsv1_resladder_open")
+        if src_format is None:
+            _chk(self.L.dsv1_resladder_open(_C.byref(self.h), _C.byref(meta), rr, len(geoms), device, nsources, frames_per_call, filt),
+                 "dsv1_resladder_open")
+        else:
+            _chk(self.L.dsv1_resladder_open_src(_C.byref(self.h), _C.byref(meta), _C.byref(src_format), rr, len(geoms), device, nsources,
+                                                frames_per_call, filt), "dsv1_resladder_open_src")
         self.ntot = sum(n for _, _, n in self.geoms)
         self.nstreams = self.L.dsv1_resladder_nstreams(self.h)
-        self.frame_bytes = w * h + 2 * _chroma_size(w, h, fmt)
+        self.frame_bytes = w * h + 2 * _chroma_size(w, h, fmt) if src_format is None else pix_frame_bytes(src_format, w, h, fmt)
         self.ctx = self.L.dsv1_batch_ctx(self.L.dsv1_resladder_batch(self.h, 0))
         self._dev, self._pin, self._pending = [], [], []
 

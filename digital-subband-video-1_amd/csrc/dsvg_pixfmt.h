@@ -1,0 +1,55 @@
+/* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
+ * the device side of the converter (k_pixfmt.hip).  Read by the C session layer and by the HIP plumbing. */
+#ifndef DSVG_PIXFMT_H
+#define DSVG_PIXFMT_H
+
+#include "../../include/dsv1_api.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* a SEGMENT is one source plane and the output planes it feeds */
+enum { DSV1_PIXSEG_PLAIN, DSV1_PIXSEG_PAIR, DSV1_PIXSEG_YUYV, DSV1_PIXSEG_UYVY };
+typedef struct {
+    int kind;                   /* PLAIN: one sample -> one byte of one plane; PAIR: interleaved (a, b) samples -> two planes; YUYV / UYVY:
+                                   macro-pixels -> Y, U, V */
+    int rows;
+    int width;                  /* output bytes per row of the first output plane (PLAIN / PAIR: samples / pairs per row; packed: w) */
+    int cwidth;                 /* packed: macro-pixels per row = bytes per row of the U and V planes */
+    int nout;
+    int dpitch[3];              /* output planes: row pitch (tight) and offset inside the packed planar frame */
+    size_t doff[3];
+    size_t soff, spitch;        /* the source plane inside a source frame */
+} dsv1_pix_seg;
+typedef struct {
+    int nseg;
+    int wide;                   /* 16-bit words */
+    int shift;                  /* wide: (x >> shift) & 0x1ff are the sample's 9 leading significant bits t; output min(255, (t + 1) >> 1) */
+    size_t frame_bytes;         /* source frame to frame */
+    size_t planes_bytes;        /* what a source frame holds: the last frame need not be longer */
+    size_t out_frame_bytes;
+    dsv1_pix_seg seg[3];
+} dsv1_pix_layout;
+/* DSVG_OK, or DSVG_ERR_ARG for every combination include/dsv1_api.h calls invalid; no device is looked at */
+int dsv1_pix_layout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, dsv1_pix_layout *L);
+int dsv1_pix_is_default(const dsv1_pix_format *pf, int w, int h, int subsamp);      /* NULL, or planar / 8 bits / tight */
+
+/* A converter of one (geometry, subsampling, format): a stream and an event of its own, two raw upload buffers (per call parity),
+ * the clips it allocated.  _run converts on its own stream and records the event; _run_on on a stream of the caller's (the resolution
+ * ladder's scaler); _order makes a context's frame-load stream wait, on the device, for everything run so far. */
+typedef struct dsvg_pixconv dsvg_pixconv;
+int  dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pix_layout *L);
+void dsvg_pixconv_destroy(dsvg_pixconv *c);
+int  dsvg_pixconv_upload(dsvg_pixconv *c, int buf, const void *host, size_t bytes, void **dptr);
+int  dsvg_pixconv_alloc(dsvg_pixconv *c, void **dptr, size_t bytes);
+int  dsvg_pixconv_run(dsvg_pixconv *c, const void *src_dev, int nframes, void *dst_dev);
+int  dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev);
+int  dsvg_pixconv_order(dsvg_pixconv *c, dsvg_ctx *ctx);
+int  dsvg_pixconv_sync(dsvg_pixconv *c);
+int  dsvg_pixconv_download(dsvg_pixconv *c, void *host, const void *dptr, size_t bytes);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -111,6 +111,12 @@ struct dsv1_batch {
     uint64_t *xsse;
     int64_t *xssim;
     size_t xsse_n, xssim_n;
+    /* source pixel format (dsv1_batch_set_source_format): the converter and the converted clips, one per call parity (a batch of that
+     * parity reads its clip, as a held clip, until its collect); pc == NULL: clips are packed planar 8-bit, nothing is converted */
+    int device;
+    dsvg_pixconv *pc;
+    size_t pc_raw_fb;
+    void *pc_clip[2];
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -186,6 +192,7 @@ void dsv1_batch_close(dsv1_batch *b)
     if (b->bg_on[0] || b->bg_on[1]) dsv1_par_bg_end();  /* a background prefix loop still reads this batch's pictures */
     if (b->holds_recycler) dsv1_recycle_hold(-1);       /* the last batch out gives the parked packet buffers back */
     if (b->ctx) dsvg_ctx_destroy(b->ctx);
+    dsvg_pixconv_destroy(b->pc);                        /* (after the context, whose kernels read the converted clips) */
     if (b->own_enc && b->enc) {
         int s;
         for (s = 0; s < b->nstreams; s++) {
@@ -213,6 +220,7 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     b = (dsv1_batch *)b_calloc(1, sizeof(*b));
     if (!b) return DSVG_ERR_NOMEM;
     b->nstreams = nstreams; b->nsrc = nsrc; b->R = R; b->F = F; b->enc = encs; b->own_enc = own;
+    b->device = device;
     if (chains > F) chains = F;
     b->chains = chains; b->carry_pair = -1; b->carry_cur = -1;
     np = nstreams * F;
@@ -1242,10 +1250,65 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
     b->staged_host[b->nstaged++] = yuv_host;
     return DSVG_OK;
 }
-int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host) { return stage_n(b, yuv_host, b ? b->F : 0); }
+int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
+{
+    if (b && b->pc) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format is set"); return DSVG_ERR_ARG; }
+    return stage_n(b, yuv_host, b ? b->F : 0);
+}
+
+int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
+{
+    dsv1_pix_layout L;
+    const DSV_META *m;
+    int rc, k;
+    if (!b) return DSVG_ERR_ARG;
+    m = &b->enc[0].vidmeta;
+    if (pf && dsv1_pix_layout_of(pf, m->width, m->height, m->subsamp, &L)) {
+        dsv1_log(1, "dsv1_batch_set_source_format: not a valid pixel format for %dx%d, subsampling 0x%x", m->width, m->height, m->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_format with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    /* nothing in flight: every batch that read a converted clip has been collected */
+    dsvg_pixconv_destroy(b->pc);
+    b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL;
+    if (dsv1_pix_is_default(pf, m->width, m->height, m->subsamp)) return DSVG_OK;
+    if ((rc = dsvg_pixconv_create(&b->pc, b->device, &L))) return rc;
+    for (k = 0; k < 2 && !rc; k++) rc = dsvg_pixconv_alloc(b->pc, &b->pc_clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
+    if (rc) { dsvg_pixconv_destroy(b->pc); b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL; return rc; }
+    b->pc_raw_fb = L.frame_bytes;
+    return DSVG_OK;
+}
+
+/* a clip of the batch's source format -> the converted clip of the next submit's parity (device memory the batch owns, read as a held
+ * clip until that batch's collect); the context's frame-load stream waits for the conversion on the device */
+static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
+{
+    const int par = b->parity, nfr = b->nsrc * b->F;
+    const void *raw = *yuv;
+    void *d;
+    int rc;
+    if (!raw) return DSVG_ERR_ARG;
+    if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
+    if (b->pending[par]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
+    if (!yuv_on_device) {
+        if ((rc = dsvg_pixconv_upload(b->pc, par, raw, b->pc_raw_fb * (size_t)nfr, &d))) return rc;
+        raw = d;
+    }
+    if ((rc = dsvg_pixconv_run(b->pc, raw, nfr, b->pc_clip[par]))) return rc;
+    if ((rc = dsvg_pixconv_order(b->pc, b->ctx))) return rc;
+    /* a plain device clip is the caller's again when submit returns */
+    if (yuv_on_device == 1 && (rc = dsvg_pixconv_sync(b->pc))) return rc;
+    *yuv = b->pc_clip[par];
+    return DSVG_OK;
+}
 
 int dsv1_batch_submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
+    if (b && b->pc) {
+        int rc;
+        if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
+        return batch_submit_impl(b, yuv, 1, out, 0, 1);
+    }
     /* a device clip's chroma stays where it is (the coding kernels read it until the batch is collected) only when the caller
      * said it holds the clip that long: DSV1_CLIP_HELD.  A plain device clip is copied whole -- the call is done with it when
      * it returns, as it was before round 3 (advisor, round 3) */
@@ -1324,6 +1387,10 @@ int dsv1_batch_encode(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF
     int rc;
     if (!b || !out) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_encode with batches in flight"); return DSVG_ERR_ARG; }
+    if (b->pc) {
+        if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
+        yuv_on_device = 1;
+    }
     if ((rc = batch_submit_impl(b, yuv, yuv_on_device, out, 0, 1))) return rc;
     return dsv1_batch_collect(b, out);
 }

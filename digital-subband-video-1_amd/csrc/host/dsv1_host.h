@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../../include/dsv1_api.h"
+#include "../dsvg_pixfmt.h"       /* source pixel formats: the layout of a format and the device converter (k_pixfmt.hip) */
 
 /* `end` bounds the READER (bits): past it every bit reads as 1 -- which ends any exp-Golomb prefix -- and `over` is set,
  * so a truncated or hostile packet can neither run the reader off its buffer nor loop; the writer ignores it */
@@ -122,6 +123,8 @@ int  dsvg_scaler_download(dsvg_scaler *s, void *host, const void *dptr, size_t b
 /* device clip -> upload buffer `buf` (0 / 1) on the scaler's stream, as dsvg_scaler_upload (a resolution ladder's plain device clip
  * that must outlive its submit) */
 int  dsvg_scaler_copy_in(dsvg_scaler *s, int buf, const void *dev, size_t bytes, void **dptr);
+/* a source of another pixel format: converted on the scaler's stream (in front of the scales that read dst_dev) */
+int  dsvg_scaler_convert(dsvg_scaler *s, dsvg_pixconv *pc, const void *src_dev, int nframes, void *dst_dev);
 /* dsv1_enc.c: source-resolution figures of a batch (dsvg_ctx_xres_enable; resolution ladders): stream k = s * R + r, frame t of a
  * call is measured against frame s * frames_per_call + t of the reference clip named for the next submit (device memory, kept until
  * that batch's collect); the figures of the batch collected last, [(k * F + t) * 3 + p].  Enable only between batches. */

@@ -1,0 +1,111 @@
+/* dsv1_pixfmt.c -- source pixel formats (include/dsv1_api.h, dsv1_pix_format): what a format works out to for one geometry -- the
+ * definition tests/_pixfmt.py states in numpy -- and the standalone converter.  The kernel and its device plumbing: k_pixfmt.hip. */
+#include "dsv1_host.h"
+
+int dsv1_pix_layout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, dsv1_pix_layout *L)
+{
+    int hs, vs, cw, ch, bps, p, nsp;
+    size_t rowb[3], rows[3], off = 0;
+    if (!pf || !L || w < 1 || h < 1) return DSVG_ERR_ARG;
+    if (subsamp != DSV_SUBSAMP_444 && subsamp != DSV_SUBSAMP_422 && subsamp != DSV_SUBSAMP_420 && subsamp != DSV_SUBSAMP_411) return DSVG_ERR_ARG;
+    if (pf->depth != 8 && pf->depth != 10 && pf->depth != 12 && pf->depth != 16) return DSVG_ERR_ARG;
+    if (pf->depth > 8 && pf->msb_aligned != 0 && pf->msb_aligned != 1) return DSVG_ERR_ARG;
+    hs = (subsamp >> 2) & 3; vs = subsamp & 3;
+    cw = (w + (1 << hs) - 1) >> hs; ch = (h + (1 << vs) - 1) >> vs;
+    bps = pf->depth > 8 ? 2 : 1;
+    memset(L, 0, sizeof(*L));
+    L->wide = bps == 2;
+    L->shift = !L->wide ? 0 : pf->msb_aligned ? 7 : pf->depth - 9;
+    switch (pf->layout) {
+    case DSV1_PIX_PLANAR:
+        nsp = 3;
+        rowb[0] = (size_t)w * bps; rowb[1] = rowb[2] = (size_t)cw * bps;
+        rows[0] = (size_t)h; rows[1] = rows[2] = (size_t)ch;
+        break;
+    case DSV1_PIX_SEMIPLANAR_UV:
+    case DSV1_PIX_SEMIPLANAR_VU:
+        if (subsamp != DSV_SUBSAMP_420 && subsamp != DSV_SUBSAMP_422) return DSVG_ERR_ARG;
+        nsp = 2;
+        rowb[0] = (size_t)w * bps; rowb[1] = 2 * (size_t)cw * bps;
+        rows[0] = (size_t)h; rows[1] = (size_t)ch;
+        break;
+    case DSV1_PIX_PACKED_YUYV:
+    case DSV1_PIX_PACKED_UYVY:
+        if (subsamp != DSV_SUBSAMP_422 || pf->depth != 8) return DSVG_ERR_ARG;
+        nsp = 1;
+        rowb[0] = 4 * (size_t)cw;
+        rows[0] = (size_t)h;
+        break;
+    default:
+        return DSVG_ERR_ARG;
+    }
+    L->nseg = nsp;
+    for (p = 0; p < nsp; p++) {
+        dsv1_pix_seg *S = &L->seg[p];
+        if (pf->pitch[p] < 0 || (pf->pitch[p] && (size_t)pf->pitch[p] < rowb[p])) return DSVG_ERR_ARG;
+        S->spitch = pf->pitch[p] ? (size_t)pf->pitch[p] : rowb[p];
+        S->soff = off;
+        S->rows = (int)rows[p];
+        off += S->spitch * rows[p];
+    }
+    L->planes_bytes = off;
+    if (pf->frame_bytes && pf->frame_bytes < off) return DSVG_ERR_ARG;
+    L->frame_bytes = pf->frame_bytes ? pf->frame_bytes : off;
+    L->out_frame_bytes = (size_t)w * h + 2 * (size_t)cw * ch;
+    {
+        /* the output planes of the packed planar 8-bit frame */
+        const size_t yo = 0, uo = (size_t)w * h, vo = uo + (size_t)cw * ch;
+        dsv1_pix_seg *S = L->seg;
+        if (nsp == 3) {
+            for (p = 0; p < 3; p++) { S[p].kind = DSV1_PIXSEG_PLAIN; S[p].nout = 1; S[p].width = p ? cw : w; S[p].dpitch[0] = p ? cw : w; }
+            S[0].doff[0] = yo; S[1].doff[0] = uo; S[2].doff[0] = vo;
+        } else if (nsp == 2) {
+            const int vu = pf->layout == DSV1_PIX_SEMIPLANAR_VU;
+            S[0].kind = DSV1_PIXSEG_PLAIN; S[0].nout = 1; S[0].width = w; S[0].dpitch[0] = w; S[0].doff[0] = yo;
+            S[1].kind = DSV1_PIXSEG_PAIR; S[1].nout = 2; S[1].width = cw; S[1].dpitch[0] = S[1].dpitch[1] = cw;
+            S[1].doff[0] = vu ? vo : uo; S[1].doff[1] = vu ? uo : vo;       /* the pair's first sample goes to doff[0] */
+        } else {
+            S[0].kind = pf->layout == DSV1_PIX_PACKED_YUYV ? DSV1_PIXSEG_YUYV : DSV1_PIXSEG_UYVY;
+            S[0].nout = 3; S[0].width = w; S[0].cwidth = cw;
+            S[0].dpitch[0] = w; S[0].dpitch[1] = S[0].dpitch[2] = cw;
+            S[0].doff[0] = yo; S[0].doff[1] = uo; S[0].doff[2] = vo;
+        }
+    }
+    return DSVG_OK;
+}
+
+size_t dsv1_pix_frame_bytes(const dsv1_pix_format *pf, int w, int h, int subsamp)
+{
+    dsv1_pix_layout L;
+    return dsv1_pix_layout_of(pf, w, h, subsamp, &L) ? 0 : L.frame_bytes;
+}
+
+int dsv1_pix_is_default(const dsv1_pix_format *pf, int w, int h, int subsamp)
+{
+    dsv1_pix_layout L;
+    if (!pf) return 1;
+    if (pf->layout != DSV1_PIX_PLANAR || pf->depth != 8 || dsv1_pix_layout_of(pf, w, h, subsamp, &L)) return 0;
+    return L.frame_bytes == L.out_frame_bytes && L.planes_bytes == L.out_frame_bytes;      /* every pitch a row, no stride beyond */
+}
+
+int dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, int w, int h, int subsamp, int n, void *dst, int on_device)
+{
+    dsv1_pix_layout L;
+    dsvg_pixconv *pc = NULL;
+    void *dsrc = NULL, *ddst = NULL;
+    int rc;
+    if (!src || !dst || !pf || n < 1 || device < 0) return DSVG_ERR_ARG;
+    if ((rc = dsv1_pix_layout_of(pf, w, h, subsamp, &L))) return rc;
+    if ((rc = dsvg_pixconv_create(&pc, device, &L))) return rc;
+    if (on_device) rc = dsvg_pixconv_run(pc, src, n, dst);
+    else {
+        /* the last frame ends with its planes: a caller's buffer need not hold the stride's padding behind them */
+        rc = dsvg_pixconv_upload(pc, 0, src, L.frame_bytes * (size_t)(n - 1) + L.planes_bytes, &dsrc);
+        if (!rc) rc = dsvg_pixconv_alloc(pc, &ddst, L.out_frame_bytes * (size_t)n);
+        if (!rc) rc = dsvg_pixconv_run(pc, dsrc, n, ddst);
+        if (!rc) rc = dsvg_pixconv_download(pc, dst, ddst, L.out_frame_bytes * (size_t)n);
+    }
+    if (!rc) rc = dsvg_pixconv_sync(pc);
+    dsvg_pixconv_destroy(pc);                           /* (frees ddst: the converter owns what it allocated) */
+    return rc;
+}

@@ -8,7 +8,11 @@
  * clip once on the scaler's stream, scales it there for every geometry whose size differs from the source's, and makes each
  * geometry's frame-load stream wait for that on the device (dsvg_scaler_order) before the geometry's submit; the scaled clips go to
  * the ladders as held device clips (DSV1_CLIP_HELD), one buffer per geometry and call parity, which the next submit of the same
- * parity -- after that geometry's collect -- overwrites. */
+ * parity -- after that geometry's collect -- overwrites.
+ *
+ * A source of another pixel format (dsv1_resladder_open_src): the raw clip is what crosses the link; it is converted on the scaler's
+ * stream, in front of the scales, into a packed planar 8-bit clip the resladder holds per call parity, and that clip stands for the
+ * source from there on (scales, a geometry of the source's size, the source-resolution figures). */
 #include <math.h>
 #include "dsv1_host.h"
 
@@ -157,6 +161,10 @@ struct dsv1_resladder {
     uint64_t *xsse;
     int64_t *xssim;
     size_t xsse_n, xssim_n;
+    /* source pixel format (dsv1_resladder_open_src): the converter and the converted clips, per call parity; pc == NULL: the default */
+    dsvg_pixconv *pc;
+    size_t raw_fb;
+    void *conv[2];
 };
 
 void dsv1_resladder_close(dsv1_resladder *r)
@@ -164,7 +172,8 @@ void dsv1_resladder_close(dsv1_resladder *r)
     int g;
     if (!r) return;
     for (g = 0; g < r->ngeom; g++) dsv1_batch_close(r->lad[g]);
-    dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated) */
+    dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated; it waits for its stream) */
+    dsvg_pixconv_destroy(r->pc);
     free(r->tmp); free(r->sse); free(r->ssim); free(r->xsse); free(r->xssim);
     free(r);
 }
@@ -172,13 +181,25 @@ void dsv1_resladder_close(dsv1_resladder *r)
 int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
                         int frames_per_call, int filter)
 {
+    return dsv1_resladder_open_src(out, src, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs, int ngeoms,
+                            int device, int nsources, int frames_per_call, int filter)
+{
     dsv1_resladder *r;
+    dsv1_pix_layout pl;
     int g, k, rc, ntot = 0, nscaled = 0, maxr = 0, dw[DSV1_MAX_GEOMS], dh[DSV1_MAX_GEOMS];
     if (out) *out = NULL;
     /* arguments first: nothing below touches a device until every geometry has passed */
     if (!out || !src || !rungs || ngeoms < 1 || ngeoms > DSV1_MAX_GEOMS || nsources < 1 || frames_per_call < 1) return DSVG_ERR_ARG;
     if (filter != DSV1_SCALE_TENT && filter != DSV1_SCALE_CUBIC) return DSVG_ERR_ARG;
     if (src->width < 1 || src->height < 1) return DSVG_ERR_ARG;
+    if (pf && dsv1_pix_layout_of(pf, src->width, src->height, src->subsamp, &pl)) {
+        dsv1_log(1, "dsv1_resladder_open_src: not a valid pixel format for %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (pf && dsv1_pix_is_default(pf, src->width, src->height, src->subsamp)) pf = NULL;
     for (g = 0; g < ngeoms; g++) {
         const dsv1_res_rung *G = &rungs[g];
         if (!G->rates || G->nrates < 1 || G->nrates > DSV1_MAX_RUNGS) {
@@ -229,6 +250,12 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
     }
     /* the scaler exists even when no geometry is scaled: host input is uploaded through it */
     if ((rc = dsvg_scaler_create(&r->sc, device, src->width, src->height, src->subsamp, nscaled, dw, dh, filter))) { dsv1_resladder_close(r); return rc; }
+    if (pf) {
+        r->raw_fb = pl.frame_bytes;
+        if ((rc = dsvg_pixconv_create(&r->pc, device, &pl))) { dsv1_resladder_close(r); return rc; }
+        for (k = 0; k < 2; k++)
+            if ((rc = dsvg_scaler_alloc(r->sc, &r->conv[k], r->sfb * (size_t)nsources * frames_per_call))) { dsv1_resladder_close(r); return rc; }
+    }
     for (g = 0; g < ngeoms; g++) {
         if ((rc = dsv1_ladder_open(&r->lad[g], rungs[g].rates, rungs[g].nrates, device, nsources, frames_per_call))) break;
         r->ngeom = g + 1;
@@ -290,7 +317,21 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
     if (!r || !yuv || !out || yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     par = r->parity;
     if (r->pending[par]) { dsv1_log(1, "resolution ladder submitted twice without collect"); return DSVG_ERR_ARG; }
-    if (!yuv_on_device) {
+    if (r->pc) {
+        /* another pixel format: the RAW clip crosses the link (host input), and the conversion, on the scaler's stream, writes the
+         * clip of this call's parity, which the resladder holds until collect and which stands for the source from here on */
+        if (!yuv_on_device) {
+            void *d;
+            const size_t bytes = r->raw_fb * (size_t)nfr;
+            if ((rc = dsvg_scaler_upload(r->sc, par, yuv, bytes, &d))) return rc;
+            r->up_bytes += bytes;
+            r->up_calls++;
+            dsrc = (const uint8_t *)d;
+        }
+        if ((rc = dsvg_scaler_convert(r->sc, r->pc, dsrc, nfr, r->conv[par]))) return rc;
+        dsrc = (const uint8_t *)r->conv[par];
+        yuv_on_device = DSV1_CLIP_HELD;                 /* (a plain device clip: the sync below waits for the conversion that read it) */
+    } else if (!yuv_on_device) {
         /* the source crosses the link once, on the scaler's stream; its buffer (per parity) is held until this call's collect: a
          * geometry of the source's size reads it in place */
         void *d;

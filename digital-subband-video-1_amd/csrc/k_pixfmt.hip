@@ -1,0 +1,334 @@
+// k_pixfmt.hip -- source pixel formats -> tightly packed planar 8-bit frames (include/dsv1_api.h dsv1_pix_format; stated in numpy in
+// tests/_pixfmt.py).  A pure streaming pass in front of the scaler / the frame load.
+//
+// A source frame is one to three SEGMENTS (dsvg_pixfmt.h): a source plane and the output planes it feeds -- planar: Y, U, V, each one
+// to one; semi-planar: Y one to one, the interleaved chroma plane to U and V; packed 4:2:2: the one plane to Y, U and V.  One launch
+// converts every frame and segment of a clip: blockIdx.y = frame, blockIdx.x = 256 ITEMS of one segment (the segments' blocks one
+// after the other, so a block's segment is uniform).  An item is one STEP of one row: 16 output bytes of each output plane (8 of U
+// and V for the packed layouts), that is
+//     8-bit plane             16 source bytes -> one 16-byte store
+//     16-bit plane            32 source bytes -> one 16-byte store
+//     8-bit interleaved UV    32 source bytes -> 16 U + 16 V
+//     16-bit interleaved UV   64 source bytes -> 16 U + 16 V
+//     YUYV / UYVY             32 source bytes -> 16 Y + 8 U + 8 V
+// read with aligned 16-byte non-temporal loads (the source is read once), de-interleaved with v_perm_b32.
+// Depth reduction (d > 8 bits, x the 16-bit word): v = msb_aligned ? x >> (16 - d) : x & (2^d - 1), out = min(255, (v + 2^(d-9)) >>
+// (d - 8)).  With t = v >> (d - 9), the sample's 9 leading bits, (v + 2^(d-9)) >> (d - 8) = (t + 1) >> 1 (the bits below t cannot
+// carry), and t = (x >> k) & 0x1ff with k = 7 (msb-aligned) or d - 9: the same for every depth, done on both 16-bit halves of a dword
+// at once -- t + 1 <= 512 stays inside its half, the result is at most 256, and 256 becomes 255 by subtracting its own bit 8.
+// The 16-byte path needs every row of the segment aligned, source and destination (16 bytes; 8 for the packed layouts' U and V):
+// decided on the host per segment and launch from the pointers, offsets, pitches and frame strides -- uniform, no per-lane test.
+// It takes the whole steps of a row; the row's tail, and every step of a segment that is not aligned, takes the byte path, which
+// loads exactly the bytes of the samples it converts: nothing outside the frame is ever read, whatever the pitch or the width.
+#include <algorithm>
+#include "dsvg_host.hpp"
+#include "dsvg_pixfmt.h"
+
+#define PX_THREADS 256
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+struct PixSeg {
+    int kind, rows, width, cwidth;
+    int cpr, block0, fast, nout;         // steps per row, first block of the segment in blockIdx.x, every row on the 16-byte path
+    int dpitch[3], pad;
+    long long doff[3];
+    long long soff, spitch;
+};
+struct PixParams {
+    PixSeg seg[3];
+    long long sfb, dfb;
+    int nseg, shift;
+};
+
+enum { PXL_PLANAR, PXL_SEMI, PXL_YUYV, PXL_UYVY };
+
+// two 16-bit words -> their 8-bit values in bytes 0 and 2
+static __device__ __forceinline__ unsigned px_reduce2(unsigned dw, int shift)
+{
+    unsigned t = (dw >> shift) & 0x01ff01ffu;
+    t = ((t + 0x00010001u) >> 1) & 0x01ff01ffu;
+    return t - ((t >> 8) & 0x00010001u);
+}
+// v_perm_b32: selector bytes 0..3 pick from lo, 4..7 from hi
+static __device__ __forceinline__ unsigned px_perm(unsigned hi, unsigned lo, unsigned sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+#define PX_EVEN 0x06040200u              // lo.b0 lo.b2 hi.b0 hi.b2
+#define PX_ODD  0x07050301u              // lo.b1 lo.b3 hi.b1 hi.b3
+#define PX_ZIP  0x06020400u              // lo.b0 hi.b0 lo.b2 hi.b2
+#define PX_LOW  0x05040100u              // lo.b0 lo.b1 hi.b0 hi.b1
+#define PX_HIGH 0x07060302u              // lo.b2 lo.b3 hi.b2 hi.b3
+
+static __device__ __forceinline__ u32x4 px_load(const uint8_t *p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p)); }
+static __device__ __forceinline__ void px_store(uint8_t *p, u32x4 v) { *reinterpret_cast<u32x4 *>(p) = v; }
+
+// byte path: sample i of a row
+template <bool WIDE> static __device__ __forceinline__ unsigned px_sample(const uint8_t *row, long long i, int shift)
+{
+    if (!WIDE) return row[i];
+    const unsigned x = (unsigned)row[2 * i] | ((unsigned)row[2 * i + 1] << 8);
+    const unsigned t = (x >> shift) & 0x1ffu;
+    return min(255u, (t + 1u) >> 1);
+}
+
+template <int LAYOUT, bool WIDE>
+__global__ __launch_bounds__(PX_THREADS) void k_pixfmt(const PixParams P, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst)
+{
+    const int bx = blockIdx.x;
+    const int si = (LAYOUT == PXL_PLANAR) ? (bx >= P.seg[2].block0 ? 2 : (bx >= P.seg[1].block0 ? 1 : 0))
+                 : (LAYOUT == PXL_SEMI)   ? (bx >= P.seg[1].block0 ? 1 : 0) : 0;
+    const PixSeg &S = P.seg[si];
+    const int item = (bx - S.block0) * PX_THREADS + (int)threadIdx.x;
+    const int cpr = S.cpr;
+    const int y = item / cpr, c = item - y * cpr;
+    if (y >= S.rows) return;
+    const int shift = P.shift;
+    const uint8_t *row = src + (long long)blockIdx.y * P.sfb + S.soff + (long long)y * S.spitch;
+    uint8_t *frame = dst + (long long)blockIdx.y * P.dfb;
+    uint8_t *o0 = frame + S.doff[0] + (long long)y * S.dpitch[0];
+    const bool whole = S.fast && 16 * c + 16 <= S.width;
+    if (LAYOUT == PXL_PLANAR || (LAYOUT == PXL_SEMI && si == 0)) {
+        if (whole) {
+            if (!WIDE) px_store(o0 + 16 * c, px_load(row + 16 * c));
+            else {
+                const u32x4 a = px_load(row + 32 * c), b = px_load(row + 32 * c + 16);
+                u32x4 o;
+                o.x = px_perm(px_reduce2(a.y, shift), px_reduce2(a.x, shift), PX_EVEN);
+                o.y = px_perm(px_reduce2(a.w, shift), px_reduce2(a.z, shift), PX_EVEN);
+                o.z = px_perm(px_reduce2(b.y, shift), px_reduce2(b.x, shift), PX_EVEN);
+                o.w = px_perm(px_reduce2(b.w, shift), px_reduce2(b.z, shift), PX_EVEN);
+                px_store(o0 + 16 * c, o);
+            }
+        } else {
+            const int n = min(16, S.width - 16 * c);
+            for (int i = 0; i < n; i++) o0[16 * c + i] = (uint8_t)px_sample<WIDE>(row, 16 * c + i, shift);
+        }
+    } else if (LAYOUT == PXL_SEMI) {
+        uint8_t *o1 = frame + S.doff[1] + (long long)y * S.dpitch[1];
+        if (whole) {
+            u32x4 u, v;
+            if (!WIDE) {
+                const u32x4 a = px_load(row + 32 * c), b = px_load(row + 32 * c + 16);
+                u.x = px_perm(a.y, a.x, PX_EVEN); u.y = px_perm(a.w, a.z, PX_EVEN); u.z = px_perm(b.y, b.x, PX_EVEN); u.w = px_perm(b.w, b.z, PX_EVEN);
+                v.x = px_perm(a.y, a.x, PX_ODD);  v.y = px_perm(a.w, a.z, PX_ODD);  v.z = px_perm(b.y, b.x, PX_ODD);  v.w = px_perm(b.w, b.z, PX_ODD);
+            } else {
+                unsigned uo[4], vo[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {           // 16 source bytes = four (a, b) pairs -> four bytes of each plane
+                    const u32x4 a = px_load(row + 64 * c + 16 * q);
+                    const unsigned p0 = px_perm(px_reduce2(a.y, shift), px_reduce2(a.x, shift), PX_ZIP);     // a0 a1 b0 b1
+                    const unsigned p1 = px_perm(px_reduce2(a.w, shift), px_reduce2(a.z, shift), PX_ZIP);     // a2 a3 b2 b3
+                    uo[q] = px_perm(p1, p0, PX_LOW);
+                    vo[q] = px_perm(p1, p0, PX_HIGH);
+                }
+                u.x = uo[0]; u.y = uo[1]; u.z = uo[2]; u.w = uo[3];
+                v.x = vo[0]; v.y = vo[1]; v.z = vo[2]; v.w = vo[3];
+            }
+            px_store(o0 + 16 * c, u);
+            px_store(o1 + 16 * c, v);
+        } else {
+            const int n = min(16, S.width - 16 * c);
+            for (int i = 0; i < n; i++) {
+                const long long x = 16 * c + i;
+                o0[x] = (uint8_t)px_sample<WIDE>(row, 2 * x, shift);
+                o1[x] = (uint8_t)px_sample<WIDE>(row, 2 * x + 1, shift);
+            }
+        }
+    } else {
+        // packed 4:2:2, 8 bits: a macro-pixel is Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY)
+        uint8_t *o1 = frame + S.doff[1] + (long long)y * S.dpitch[1];
+        uint8_t *o2 = frame + S.doff[2] + (long long)y * S.dpitch[2];
+        const unsigned ysel = LAYOUT == PXL_YUYV ? PX_EVEN : PX_ODD, csel = LAYOUT == PXL_YUYV ? PX_ODD : PX_EVEN;
+        if (whole) {
+            const u32x4 a = px_load(row + 32 * c), b = px_load(row + 32 * c + 16);
+            u32x4 yy;
+            yy.x = px_perm(a.y, a.x, ysel); yy.y = px_perm(a.w, a.z, ysel); yy.z = px_perm(b.y, b.x, ysel); yy.w = px_perm(b.w, b.z, ysel);
+            const unsigned c0 = px_perm(a.y, a.x, csel), c1 = px_perm(a.w, a.z, csel), c2 = px_perm(b.y, b.x, csel), c3 = px_perm(b.w, b.z, csel);   // U V U V
+            u32x2 u, v;
+            u.x = px_perm(c1, c0, PX_EVEN); u.y = px_perm(c3, c2, PX_EVEN);
+            v.x = px_perm(c1, c0, PX_ODD);  v.y = px_perm(c3, c2, PX_ODD);
+            px_store(o0 + 16 * c, yy);
+            *reinterpret_cast<u32x2 *>(o1 + 8 * c) = u;
+            *reinterpret_cast<u32x2 *>(o2 + 8 * c) = v;
+        } else {
+            const int yo = LAYOUT == PXL_YUYV ? 0 : 1, uo = 1 - yo;
+            const int n = min(16, S.width - 16 * c), m = min(8, S.cwidth - 8 * c);
+            for (int i = 0; i < n; i++) o0[16 * c + i] = row[2 * (long long)(16 * c + i) + yo];
+            for (int i = 0; i < m; i++) {
+                o1[8 * c + i] = row[4 * (long long)(8 * c + i) + uo];
+                o2[8 * c + i] = row[4 * (long long)(8 * c + i) + uo + 2];
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+extern "C" int dsvg_ctx_load_wait(dsvg_ctx *ctx, void *event);
+
+struct dsvg_pixconv {
+    int device = 0;
+    int layout = 0;                      // PXL_*
+    dsv1_pix_layout L;
+    PixParams P;
+    int nblocks = 0;
+    hipStream_t st = nullptr;
+    hipEvent_t ev = nullptr;
+    uint8_t *up[2] = {nullptr, nullptr};
+    size_t up_bytes[2] = {0, 0};
+    std::vector<void *> owned;
+};
+
+extern "C" void dsvg_pixconv_destroy(dsvg_pixconv *c)
+{
+    if (!c) return;
+    if (hipSetDevice(c->device) == hipSuccess) {
+        if (c->st) (void)hipStreamSynchronize(c->st);
+        for (void *p : c->owned) (void)hipFree(p);
+        for (int k = 0; k < 2; k++) if (c->up[k]) (void)hipFree(c->up[k]);
+        if (c->ev) (void)hipEventDestroy(c->ev);
+        if (c->st) (void)hipStreamDestroy(c->st);
+    }
+    (void)hipGetLastError();
+    delete c;
+}
+
+static int pixconv_streams(dsvg_pixconv *c)
+{
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pix_layout *L)
+{
+    if (!out || !L || L->nseg < 1 || L->nseg > 3) { dsvg_set_error("bad converter arguments"); return DSVG_ERR_ARG; }
+    *out = nullptr;
+    if (dsvg_device_count() <= device || device < 0) { dsvg_set_error("HIP device %d not present", device); (void)hipGetLastError(); return DSVG_ERR_NODEVICE; }
+    dsvg_pixconv *c = new dsvg_pixconv();
+    c->device = device; c->L = *L;
+    const int k0 = L->seg[0].kind;
+    c->layout = k0 == DSV1_PIXSEG_YUYV ? PXL_YUYV : k0 == DSV1_PIXSEG_UYVY ? PXL_UYVY : L->nseg == 2 ? PXL_SEMI : PXL_PLANAR;
+    memset(&c->P, 0, sizeof c->P);
+    long long blocks = 0;
+    for (int s = 0; s < 3; s++) {
+        PixSeg &S = c->P.seg[s];
+        if (s >= L->nseg) { S.block0 = INT_MAX; continue; }     // (never chosen)
+        const dsv1_pix_seg &G = L->seg[s];
+        S.kind = G.kind; S.rows = G.rows; S.width = G.width; S.cwidth = G.cwidth; S.nout = G.nout;
+        S.cpr = (G.width + 15) / 16;
+        S.block0 = (int)blocks;
+        for (int o = 0; o < 3; o++) { S.dpitch[o] = G.dpitch[o]; S.doff[o] = (long long)G.doff[o]; }
+        S.soff = (long long)G.soff; S.spitch = (long long)G.spitch;
+        blocks += ((long long)S.cpr * S.rows + PX_THREADS - 1) / PX_THREADS;
+        if (blocks > INT_MAX / 2) { delete c; dsvg_set_error("frame too large for the converter's grid"); return DSVG_ERR_UNSUPPORTED; }
+    }
+    c->nblocks = (int)blocks;
+    c->P.nseg = L->nseg; c->P.shift = L->shift;
+    c->P.sfb = (long long)L->frame_bytes; c->P.dfb = (long long)L->out_frame_bytes;
+    const int rc = pixconv_streams(c);
+    if (rc) { dsvg_pixconv_destroy(c); return rc; }
+    *out = c;
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_pixconv_alloc(dsvg_pixconv *c, void **dptr, size_t bytes)
+{
+    if (!c || !dptr) return DSVG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    const hipError_t e = hipMalloc(dptr, bytes + 256);
+    if (e != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; dsvg_set_error("hipMalloc of %zu bytes failed", bytes); return DSVG_ERR_HIP; }
+    c->owned.push_back(*dptr);
+    return DSVG_OK;
+}
+
+// raw host clip -> upload buffer `buf` (0 / 1) on the converter's stream: behind the conversion that read the buffer last
+extern "C" int dsvg_pixconv_upload(dsvg_pixconv *c, int buf, const void *host, size_t bytes, void **dptr)
+{
+    if (!c || !host || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad converter upload arguments"); return DSVG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (c->up_bytes[buf] < bytes) {
+        if (c->up[buf]) { HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipFree(c->up[buf])); c->up[buf] = nullptr; c->up_bytes[buf] = 0; }
+        HIPCHK(hipMalloc((void **)&c->up[buf], bytes + 256));
+        c->up_bytes[buf] = bytes;
+    }
+    HIPCHK(hipMemcpyAsync(c->up[buf], host, bytes, hipMemcpyHostToDevice, c->st));
+    *dptr = c->up[buf];
+    return DSVG_OK;
+}
+
+template <int LAYOUT, bool WIDE> static void pix_launch(const PixParams &P, dim3 grid, hipStream_t st, const uint8_t *src, uint8_t *dst)
+{
+    hipLaunchKernelGGL((k_pixfmt<LAYOUT, WIDE>), grid, dim3(PX_THREADS), 0, st, P, src, dst);
+}
+
+// the 16-byte path of a segment: every row of every frame aligned, source and destination
+static int seg_fast(const PixParams &P, const PixSeg &S, const void *src, const void *dst)
+{
+    const bool packed = S.kind == DSV1_PIXSEG_YUYV || S.kind == DSV1_PIXSEG_UYVY;
+    if ((((uintptr_t)src) | (uintptr_t)P.sfb | (uintptr_t)S.soff | (uintptr_t)S.spitch) & 15) return 0;
+    for (int o = 0; o < S.nout; o++) {
+        const uintptr_t m = packed && o > 0 ? 7 : 15;
+        if ((((uintptr_t)dst) | (uintptr_t)P.dfb | (uintptr_t)S.doff[o] | (uintptr_t)S.dpitch[o]) & m) return 0;
+    }
+    return 1;
+}
+
+extern "C" int dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev)
+{
+    if (!c || !src_dev || !dst_dev || nframes < 1) { dsvg_set_error("bad convert arguments"); return DSVG_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    PixParams P = c->P;
+    for (int s = 0; s < P.nseg; s++) P.seg[s].fast = seg_fast(P, P.seg[s], src_dev, dst_dev);
+    const bool wide = c->L.wide != 0;
+    for (int f0 = 0; f0 < nframes; f0 += 65535) {        // (gridDim.y; one launch for any call the batches make)
+        const int n = std::min(65535, nframes - f0);
+        const uint8_t *s = (const uint8_t *)src_dev + (size_t)f0 * c->L.frame_bytes;
+        uint8_t *d = (uint8_t *)dst_dev + (size_t)f0 * c->L.out_frame_bytes;
+        const dim3 grid(c->nblocks, n);
+        switch (c->layout * 2 + (wide ? 1 : 0)) {
+        case PXL_PLANAR * 2:     pix_launch<PXL_PLANAR, false>(P, grid, st, s, d); break;
+        case PXL_PLANAR * 2 + 1: pix_launch<PXL_PLANAR, true>(P, grid, st, s, d); break;
+        case PXL_SEMI * 2:       pix_launch<PXL_SEMI, false>(P, grid, st, s, d); break;
+        case PXL_SEMI * 2 + 1:   pix_launch<PXL_SEMI, true>(P, grid, st, s, d); break;
+        case PXL_YUYV * 2:       pix_launch<PXL_YUYV, false>(P, grid, st, s, d); break;
+        case PXL_UYVY * 2:       pix_launch<PXL_UYVY, false>(P, grid, st, s, d); break;
+        default: dsvg_set_error("no converter kernel for this format"); return DSVG_ERR_UNSUPPORTED;
+        }
+    }
+    HIPCHK(hipGetLastError());
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_pixconv_run(dsvg_pixconv *c, const void *src_dev, int nframes, void *dst_dev)
+{
+    if (!c) return DSVG_ERR_ARG;
+    const int rc = dsvg_pixconv_run_on(c, (void *)c->st, src_dev, nframes, dst_dev);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(c->ev, c->st));
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_pixconv_order(dsvg_pixconv *c, dsvg_ctx *ctx)
+{
+    if (!c || !ctx) return DSVG_ERR_ARG;
+    return dsvg_ctx_load_wait(ctx, (void *)c->ev);
+}
+
+extern "C" int dsvg_pixconv_sync(dsvg_pixconv *c)
+{
+    if (!c) return DSVG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return DSVG_OK;
+}
+
+extern "C" int dsvg_pixconv_download(dsvg_pixconv *c, void *host, const void *dptr, size_t bytes)
+{
+    if (!c || !host || !dptr) return DSVG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(host, dptr, bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return DSVG_OK;
+}

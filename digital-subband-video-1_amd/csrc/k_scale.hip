@@ -331,6 +331,18 @@ extern "C" int dsvg_scaler_run(dsvg_scaler *s, int g, const void *src_dev, int n
     return DSVG_OK;
 }
 
+// a source of another pixel format (k_pixfmt.hip): converted on this stream, so that the scales enqueued next read the result
+struct dsvg_pixconv;
+extern "C" int dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev);
+extern "C" int dsvg_scaler_convert(dsvg_scaler *s, dsvg_pixconv *pc, const void *src_dev, int nframes, void *dst_dev)
+{
+    if (!s || !pc) { dsvg_set_error("bad scaler convert arguments"); return DSVG_ERR_ARG; }
+    const int rc = dsvg_pixconv_run_on(pc, (void *)s->st, src_dev, nframes, dst_dev);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(s->ev, s->st));
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx)
 {
     if (!s || !ctx) return DSVG_ERR_ARG;

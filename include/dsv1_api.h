@@ -359,6 +359,55 @@ int  dsv1_resladder_src_quality_enable(dsv1_resladder *r, int sse_on, int ssim_o
 int  dsv1_resladder_get_src_sse(const dsv1_resladder *r, uint64_t *sse, size_t n);
 int  dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n);
 
+/* ---- extension: source pixel formats (csrc/k_pixfmt.hip; stated in numpy in tests/_pixfmt.py) ----
+ * What a decoder- or capture-fed caller has: NV12 / NV16 / NV21 / NV61, P010 / P210, planar 10 / 12 / 16 bits, YUY2 / UYVY, with row
+ * pitches and a frame stride.  Converted on the device to the tightly packed planar 8-bit frames every other entry point reads; the
+ * subsampling is kept.  With cw x ch the chroma dims (rshift_up):
+ *   planar:      Y w x h, U and V cw x ch samples;
+ *   semi-planar: Y w x h, then ONE plane of ch rows of cw (U, V) pairs -- or (V, U) pairs;
+ *   packed:      h rows of cw macro-pixels Y0 U Y1 V (YUYV) or U Y0 V Y1 (UYVY); the second luma of the last macro-pixel of an
+ *                odd-width row is padding.
+ * A sample of depth 8 is its byte.  A sample word x (little-endian 16 bits) of depth d > 8: v = msb_aligned ? x >> (16 - d) :
+ * x & (2^d - 1), output min(255, (v + 2^(d-9)) >> (d - 8)) -- round half up, clamp; one rule, no dither.
+ * Valid: planar with any subsampling and depth; semi-planar with 4:2:0 or 4:2:2, any depth; packed with 4:2:2 and depth 8.  A pitch
+ * below a row's bytes, a frame_bytes below the planes, an unknown layout or depth, msb_aligned outside 0 / 1 at a depth above 8, or
+ * any other combination is invalid: dsv1_pix_frame_bytes returns 0 and every entry point DSVG_ERR_ARG before any device work.
+ * Padding bytes (pitch beyond the row, frame stride beyond the planes, the unused luma of an odd packed row) never reach the output. */
+#define DSV1_PIX_PLANAR        0
+#define DSV1_PIX_SEMIPLANAR_UV 1     /* NV12 / NV16 / P010 / P210 */
+#define DSV1_PIX_SEMIPLANAR_VU 2     /* NV21 / NV61 */
+#define DSV1_PIX_PACKED_YUYV   3     /* YUY2 */
+#define DSV1_PIX_PACKED_UYVY   4
+typedef struct {
+    int layout;        /* DSV1_PIX_* */
+    int depth;         /* 8, 10, 12 or 16 significant bits; > 8: little-endian 16-bit words */
+    int msb_aligned;   /* depth > 8 only: 1 = value in the upper bits (P010), 0 = in the lower bits (yuv420p10le) */
+    int pitch[3];      /* bytes from row to row of plane 0 / 1 / 2; 0 = tight.  Semi-planar: pitch[1] is the UV plane's, pitch[2]
+                          unused.  Packed: pitch[0] only */
+    size_t frame_bytes;/* bytes from frame to frame; 0 = tight (the planes back to back, each pitch x rows) */
+} dsv1_pix_format;
+size_t dsv1_pix_frame_bytes(const dsv1_pix_format *pf, int w, int h, int subsamp);   /* 0 = invalid combination */
+/* n frames of format *pf, frame_bytes apart -> n tightly packed planar 8-bit frames in dst; host or device memory (on_device: src
+ * and dst are device pointers).  Any w, h >= 1.  Synchronous: the frames are in dst when it returns.  The last frame's frame_bytes
+ * is the end of the source buffer: nothing beyond it is read. */
+int  dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, int w, int h, int subsamp, int n, void *dst,
+                       int on_device);
+/* From the next submit on, dsv1_batch_encode / submit take clips of format *pf ([stream or source][frame], frame_bytes apart); only
+ * between batches (nothing in flight, no clip staged), else DSVG_ERR_ARG.  NULL, or planar / 8 bits / tight, switches back.  Host
+ * input is uploaded raw and converted on the device, with no host synchronisation between upload, conversion and frame load; a
+ * plain device clip (yuv_on_device = 1) is the caller's again when submit returns (submit waits for the conversion); a
+ * DSV1_CLIP_HELD clip stays unchanged until that batch's collect and submit does not wait.  The converted clip lives in buffers
+ * the batch owns (one per call parity) and goes on as a held clip.  Plain batches, quality ladders (per source) and chain mode.
+ * dsv1_batch_stage returns DSVG_ERR_ARG while a format is set.  Not offered: the drop-in dsv_enc, the decoders' output, a change
+ * of subsampling, RGB. */
+int  dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf);
+/* dsv1_resladder_open for sources of format *pf (NULL or the default: dsv1_resladder_open itself).  The conversion runs on the
+ * scaler's stream in front of the scales; a geometry of the source's size and dsv1_resladder_src_quality_enable read the CONVERTED
+ * clip, which the resladder holds (per call parity) until collect -- get_src_sse / get_src_ssim measure against the 8-bit source
+ * the encoders saw.  dsv1_resladder_uploads counts the raw bytes that crossed the link, once per call. */
+int  dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs,
+                             int ngeoms, int device, int nsources, int frames_per_call, int filter);
+
 /* ---- extension: batched decoding (dsv_dec decodes one picture per call, dsv_decoder.c:286-472) ----
  * nstreams independent streams of one geometry; every call takes ONE packet per stream (packets[s]: not freed, not
  * modified) and decodes all picture packets among them as one device batch.  status[s] = DSV_DEC_OK (a frame was
