@@ -172,6 +172,10 @@ def lib():
         L.dsv1_batch_set_source_format.argtypes = [_C.c_void_p, _C.POINTER(PixFormat)]
         L.dsv1_resladder_open_src.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(PixFormat), _C.POINTER(ResRung), _C.c_int,
                                               _C.c_int, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_decbatch_set_output_format.argtypes = [_C.c_void_p, _C.POINTER(PixFormat), _C.c_int]
+        L.dsv1_decbatch_out_frame_bytes.restype = _C.c_size_t
+        L.dsv1_decbatch_out_frame_bytes.argtypes = [_C.c_void_p]
+        L.dsv1_export_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         _lib = L
@@ -575,6 +579,29 @@ def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None):
     return res
 
 
+def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=None):
+    """packed planar 8-bit frames (w x h at subsampling fmt) to frames of PixFormat pf at subsampling out_subsamp (None: fmt) on the
+    GPU (dsv1_export_clip), chroma halved on the way where out_subsamp asks for it: clip numpy uint8 [frames][frame_bytes] (host), or
+    a device pointer with n frames and `out` a device pointer for the result.  Host input returns numpy uint8 [frames][frame bytes
+    of pf]; `out` (a numpy uint8 array of that size) is written in place -- what the format pads stays as it was."""
+    L = lib()
+    osub = fmt if out_subsamp is None else out_subsamp
+    sfb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_export_clip(device, clip, w, h, fmt, n, out, _C.byref(pf), osub, 1), "dsv1_export_clip")
+        return out
+    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
+    if a.size % sfb or not a.size:
+        raise ValueError("a planar clip is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
+    frames = a.size // sfb
+    dfb = pix_frame_bytes(pf, w, h, osub)
+    res = _np.zeros((frames, dfb), dtype=_np.uint8) if out is None else out
+    if res.dtype != _np.uint8 or not res.flags.c_contiguous or res.size < frames * dfb:
+        raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % (frames * dfb))
+    _chk(L.dsv1_export_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(pf), osub, 0), "dsv1_export_clip")
+    return res
+
+
 def scale_taps(S, D, filt):
     """taps of one axis of the resampler (dsv1_scale_taps); ValueError outside 1 <= S / D <= 8"""
     t = lib().dsv1_scale_taps(S, D, filt)
@@ -830,6 +857,7 @@ class DecBatch:
         self.L = lib()
         self.h = _C.c_void_p(None)
         self.nstreams = nstreams
+        self.fmt = fmt
         m = Meta()
         m.width, m.height, m.subsamp = w, h, fmt
         _chk(self.L.dsv1_decbatch_open(_C.byref(self.h), device, _C.byref(m), nstreams), "dsv1_decbatch_open")
@@ -840,6 +868,19 @@ class DecBatch:
     def ctx(self):
         """the device context (not cached: the batch builds a new one when its streams announce another block size)"""
         return self.L.dsv1_decbatch_ctx(self.h)
+
+    def set_output_format(self, pixformat, out_subsamp=None):
+        """from the next decode() on, frames are written as PixFormat pixformat at subsampling out_subsamp (None: the streams' own;
+        dsv1_decbatch_set_output_format); None switches back to packed planar.  frame_bytes follows; ValueError (and the setting as
+        it was) for an invalid combination."""
+        osub = self.fmt if out_subsamp is None else out_subsamp
+        if self.L.dsv1_decbatch_set_output_format(self.h, None if pixformat is None else _C.byref(pixformat), osub) != 0:
+            raise ValueError("not a valid output format for these streams (subsampling 0x%x -> 0x%x)" % (self.fmt, osub))
+        self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))
+        if self._dev is not None:                      # (sized for the frames of the setting before)
+            self.sync()
+            self.L.dsvg_dev_free(self.ctx, self._dev)
+            self._dev = None
 
     def decode(self, packets, out=None, on_device=False):
         """packets: one bytes object per stream.  Host output: returns (frames [nstreams][frame_bytes] uint8, status,

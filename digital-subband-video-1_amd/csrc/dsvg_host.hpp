@@ -70,13 +70,16 @@ struct Slab {
     X(KID_INV_TILE_PIX_F, "void k_inv_haar_tile<true, 0, false>") X(KID_INV_TILE_PIX, "void k_inv_haar_tile<false, 0, false>") \
     X(KID_INV_TILE_S1_F, "void k_inv_haar_tile<true, 1, false>") X(KID_INV_TILE_S1, "void k_inv_haar_tile<false, 1, false>") \
     X(KID_INV_TILE_S1_SYM_F, "void k_inv_haar_tile<true, 1, true>") X(KID_INV_TILE_S1_SYM, "void k_inv_haar_tile<false, 1, true>") \
-    X(KID_INV_B4T, "void k_inv_b4t<false>") X(KID_INV_B4T_SYM, "void k_inv_b4t<true>")
+    X(KID_INV_B4T, "void k_inv_b4t<false>") X(KID_INV_B4T_SYM, "void k_inv_b4t<true>") \
+    X(KID_PIXOUT_PLANAR, "void k_pixout<0, false>") X(KID_PIXOUT_PLANAR16, "void k_pixout<0, true>") X(KID_PIXOUT_SEMI, "void k_pixout<1, false>") \
+    X(KID_PIXOUT_SEMI16, "void k_pixout<1, true>") X(KID_PIXOUT_YUYV, "void k_pixout<2, false>") X(KID_PIXOUT_UYVY, "void k_pixout<3, false>")
 enum {
 #define X(id, name) id,
     DSVG_KERNEL_IDS(X)
 #undef X
     KID_N
 };
+static_assert(KID_N <= 64, "Prof::mask holds one bit per kernel id");
 const char *kid_name(int kid);
 struct Prof {
     unsigned long long mask = 0;
@@ -93,3 +96,10 @@ struct Prof {
     void collect();
     void reset();
 };
+
+// k_pixout.hip: decoded frames -> an output pixel format (dsvg_pixout), chroma halved on the way.  The planes of a source frame and the
+// frames' distance: the bordered slots of a FrameLayout, or tightly packed planar frames.  tab_d: (source frame, output frame) pairs, or
+// null: frame i -> frame i.  DSVG_ERR_ARG (nothing launched) for a format that does not fit the planes or dfb.
+struct PoSource { int w[3], h[3]; long long pitch[3], off[3]; long long fb; };
+int  pixout_check(const dsvg_pixout *F, const PoSource &S, size_t dfb);
+int  launch_pixout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const uint8_t *src, const int *tab_d, int n, uint8_t *dst, size_t dfb, Prof *pf = nullptr);

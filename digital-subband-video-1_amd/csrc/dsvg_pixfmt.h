@@ -34,6 +34,10 @@ typedef struct {
 /* DSVG_OK, or DSVG_ERR_ARG for every combination include/dsv1_api.h calls invalid; no device is looked at */
 int dsv1_pix_layout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, dsv1_pix_layout *L);
 int dsv1_pix_is_default(const dsv1_pix_format *pf, int w, int h, int subsamp);      /* NULL, or planar / 8 bits / tight */
+/* The other direction (decoder output formats, k_pixout.hip): format *pf at subsampling out_subsamp for frames decoded at `subsamp`,
+ * resolved for the output pass.  DSVG_ERR_ARG for an invalid format and for every pair but: the same subsampling, 4:4:4 -> 4:2:2,
+ * 4:4:4 or 4:2:2 -> 4:2:0. */
+int dsv1_pixout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, int out_subsamp, dsvg_pixout *F);
 
 /* A converter of one (geometry, subsampling, format): a stream and an event of its own, two raw upload buffers (per call parity),
  * the clips it allocated.  _run converts on its own stream and records the event; _run_on on a stream of the caller's (the resolution

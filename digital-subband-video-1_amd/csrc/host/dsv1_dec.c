@@ -319,13 +319,16 @@ struct dsv1_decbatch {
     dsvg_dec_job *pj;                /* [nstreams] parsed job of each stream's packet */
     dsvg_dec_job *jobs;              /* compacted: the picture packets of this call */
     int *slots;
+    int *recs;                       /* [nstreams] reconstruction slots of this call's pictures (the output pass) */
+    int out_set;                     /* an output format is in force (dsv1_decbatch_set_output_format); else the packed planar pass */
+    dsvg_pixout out;                 /* ... resolved for the streams' geometry: it does not depend on the block size */
 };
 
 void dsv1_decbatch_close(dsv1_decbatch *d)
 {
     if (!d) return;
     if (d->ctx) dsvg_ctx_destroy(d->ctx);
-    free(d->have_ref); free(d->rpar); free(d->stable); free(d->mvs); free(d->jobs); free(d->pj); free(d->slots);
+    free(d->have_ref); free(d->rpar); free(d->stable); free(d->mvs); free(d->jobs); free(d->pj); free(d->slots); free(d->recs);
     free(d);
 }
 
@@ -355,8 +358,27 @@ int dsv1_decbatch_open(dsv1_decbatch **out, int device, const DSV_META *meta, in
     d->jobs = (dsvg_dec_job *)calloc((size_t)nstreams, sizeof(dsvg_dec_job));
     d->pj = (dsvg_dec_job *)calloc((size_t)nstreams, sizeof(dsvg_dec_job));
     d->slots = (int *)calloc((size_t)nstreams, sizeof(int));
+    d->recs = (int *)calloc((size_t)nstreams, sizeof(int));
     *out = d;
     return DSVG_OK;
+}
+
+int dsv1_decbatch_set_output_format(dsv1_decbatch *d, const dsv1_pix_format *pf, int out_subsamp)
+{
+    dsvg_pixout F;
+    int rc;
+    if (!d) return DSVG_ERR_ARG;
+    if (!pf) { d->out_set = 0; return DSVG_OK; }
+    if ((rc = dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, &F))) return rc;     /* (the setting in force stays) */
+    d->out_set = !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp));
+    d->out = F;
+    return DSVG_OK;
+}
+
+size_t dsv1_decbatch_out_frame_bytes(const dsv1_decbatch *d)
+{
+    if (!d) return 0;
+    return d->out_set ? d->out.frame_bytes : d->g.frame_bytes;
 }
 
 /* host part of one stream's packet: header + side information (a few hundred bytes) -> pj[s], status[s], fnum[s] */
@@ -406,7 +428,8 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
     int s, n = 0, rc;
     parse_ctx pc;
     if (!d || !packets || !yuv_out || !status || !fnum) return DSVG_ERR_ARG;
-    if (out_pitch == 0) out_pitch = d->g.frame_bytes;
+    if (out_pitch == 0) out_pitch = dsv1_decbatch_out_frame_bytes(d);
+    else if (d->out_set && out_pitch < d->out.frame_bytes) return DSVG_ERR_ARG;      /* (the packed planar pass refuses its own) */
     {   /* The block size is the streams' to choose (dsv_decoder.c:335-360); the batch shares one context, so it follows the
          * first picture packet of a call as long as no stream holds a reference picture (i.e. at the streams' start or where
          * every stream restarts with an I picture); a change in mid-GOP is an error of that stream (parse_stream). */
@@ -449,7 +472,10 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
         for (s = 0; s < n; s++) status[d->slots[s]] = DSV_DEC_ERROR;
         return rc;
     }
-    if (n == d->nstreams) {
+    if (d->out_set) {                    /* one pass, straight into the caller's format: picture i to its stream's frame */
+        for (s = 0; s < n; s++) d->recs[s] = d->jobs[s].recon_slot;
+        rc = dsvg_export_recons(d->ctx, n, d->recs, n == d->nstreams ? NULL : d->slots, yuv_out, out_pitch, out_on_device, &d->out);
+    } else if (n == d->nstreams) {
         for (s = 0; s < n; s++) d->slots[s] = d->jobs[s].recon_slot;
         rc = dsvg_pack_recons(d->ctx, n, d->slots, yuv_out, out_pitch, out_on_device);
     } else {                             /* some streams had no picture this call: their output frames stay untouched */

@@ -1,5 +1,6 @@
-/* dsv1_pixfmt.c -- source pixel formats (include/dsv1_api.h, dsv1_pix_format): what a format works out to for one geometry -- the
- * definition tests/_pixfmt.py states in numpy -- and the standalone converter.  The kernel and its device plumbing: k_pixfmt.hip. */
+/* dsv1_pixfmt.c -- pixel formats (include/dsv1_api.h, dsv1_pix_format): what a format works out to for one geometry -- the
+ * definition tests/_pixfmt.py states in numpy -- and the standalone converter; the kernel and its device plumbing: k_pixfmt.hip.
+ * And the way back, decoder output formats (tests/_pixout.py, k_pixout.hip): the same layouts written, chroma halved on the way. */
 #include "dsv1_host.h"
 
 int dsv1_pix_layout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, dsv1_pix_layout *L)
@@ -108,4 +109,48 @@ int dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, in
     if (!rc) rc = dsvg_pixconv_sync(pc);
     dsvg_pixconv_destroy(pc);                           /* (frees ddst: the converter owns what it allocated) */
     return rc;
+}
+
+/* ---- decoder output formats ---- */
+int dsv1_pixout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, int out_subsamp, dsvg_pixout *F)
+{
+    dsv1_pix_layout L;
+    int p, rc;
+    if (!pf || !F) return DSVG_ERR_ARG;
+    if (!(out_subsamp == subsamp || (subsamp == DSV_SUBSAMP_444 && (out_subsamp == DSV_SUBSAMP_422 || out_subsamp == DSV_SUBSAMP_420)) ||
+          (subsamp == DSV_SUBSAMP_422 && out_subsamp == DSV_SUBSAMP_420))) return DSVG_ERR_ARG;
+    if (subsamp != DSV_SUBSAMP_444 && subsamp != DSV_SUBSAMP_422 && subsamp != DSV_SUBSAMP_420 && subsamp != DSV_SUBSAMP_411) return DSVG_ERR_ARG;
+    /* the format's planes at the output subsampling: the converter's source side is this pass's destination */
+    if ((rc = dsv1_pix_layout_of(pf, w, h, out_subsamp, &L))) return rc;
+    memset(F, 0, sizeof(*F));
+    F->nseg = L.nseg;
+    F->wide = L.wide;
+    F->shift = !L.wide ? 0 : pf->msb_aligned ? 8 : pf->depth - 8;       /* v << (d - 8) in the low bits, or moved up to bit 15: v << 8 */
+    F->hd = ((subsamp >> 2) & 3) != ((out_subsamp >> 2) & 3);
+    F->vd = (subsamp & 3) != (out_subsamp & 3);
+    F->frame_bytes = L.frame_bytes;
+    F->planes_bytes = L.planes_bytes;
+    for (p = 0; p < L.nseg; p++) {
+        const dsv1_pix_seg *S = &L.seg[p];
+        dsvg_pixout_seg *G = &F->seg[p];
+        G->rows = S->rows; G->width = S->width; G->cwidth = S->cwidth;
+        G->off = S->soff; G->pitch = S->spitch;
+        G->nin = S->nout;
+        switch (S->kind) {
+        case DSV1_PIXSEG_PLAIN: G->kind = DSVG_PIXOUT_PLAIN; G->in_plane[0] = L.nseg == 3 ? p : 0; break;
+        case DSV1_PIXSEG_PAIR:  G->kind = DSVG_PIXOUT_PAIR; G->in_plane[0] = pf->layout == DSV1_PIX_SEMIPLANAR_VU ? 2 : 1; G->in_plane[1] = 3 - G->in_plane[0]; break;
+        default:                G->kind = S->kind == DSV1_PIXSEG_YUYV ? DSVG_PIXOUT_YUYV : DSVG_PIXOUT_UYVY; G->in_plane[1] = 1; G->in_plane[2] = 2; break;
+        }
+    }
+    return DSVG_OK;
+}
+
+int dsv1_export_clip(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsv1_pix_format *pf, int out_subsamp,
+                     int on_device)
+{
+    dsvg_pixout F;
+    int rc;
+    if (!src || !dst || !pf || n < 1 || device < 0) return DSVG_ERR_ARG;
+    if ((rc = dsv1_pixout_of(pf, w, h, subsamp, out_subsamp, &F))) return rc;
+    return dsvg_export_planar(device, src, w, h, subsamp, n, dst, &F, on_device);
 }

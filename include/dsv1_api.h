@@ -359,7 +359,8 @@ int  dsv1_resladder_src_quality_enable(dsv1_resladder *r, int sse_on, int ssim_o
 int  dsv1_resladder_get_src_sse(const dsv1_resladder *r, uint64_t *sse, size_t n);
 int  dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n);
 
-/* ---- extension: source pixel formats (csrc/k_pixfmt.hip; stated in numpy in tests/_pixfmt.py) ----
+/* ---- extension: pixel formats, in (csrc/k_pixfmt.hip; stated in numpy in tests/_pixfmt.py) and out (csrc/k_pixout.hip;
+ * tests/_pixout.py) ----
  * What a decoder- or capture-fed caller has: NV12 / NV16 / NV21 / NV61, P010 / P210, planar 10 / 12 / 16 bits, YUY2 / UYVY, with row
  * pitches and a frame stride.  Converted on the device to the tightly packed planar 8-bit frames every other entry point reads; the
  * subsampling is kept.  With cw x ch the chroma dims (rshift_up):
@@ -372,7 +373,9 @@ int  dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size
  * Valid: planar with any subsampling and depth; semi-planar with 4:2:0 or 4:2:2, any depth; packed with 4:2:2 and depth 8.  A pitch
  * below a row's bytes, a frame_bytes below the planes, an unknown layout or depth, msb_aligned outside 0 / 1 at a depth above 8, or
  * any other combination is invalid: dsv1_pix_frame_bytes returns 0 and every entry point DSVG_ERR_ARG before any device work.
- * Padding bytes (pitch beyond the row, frame stride beyond the planes, the unused luma of an odd packed row) never reach the output. */
+ * Padding bytes (pitch beyond the row, frame stride beyond the planes, the unused luma of an odd packed row) never reach the output.
+ * The same dsv1_pix_format describes what the batched decoder and dsv1_export_clip WRITE (below: decoder output formats), with an
+ * output subsampling beside it. */
 #define DSV1_PIX_PLANAR        0
 #define DSV1_PIX_SEMIPLANAR_UV 1     /* NV12 / NV16 / P010 / P210 */
 #define DSV1_PIX_SEMIPLANAR_VU 2     /* NV21 / NV61 */
@@ -398,8 +401,8 @@ int  dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, i
  * plain device clip (yuv_on_device = 1) is the caller's again when submit returns (submit waits for the conversion); a
  * DSV1_CLIP_HELD clip stays unchanged until that batch's collect and submit does not wait.  The converted clip lives in buffers
  * the batch owns (one per call parity) and goes on as a held clip.  Plain batches, quality ladders (per source) and chain mode.
- * dsv1_batch_stage returns DSVG_ERR_ARG while a format is set.  Not offered: the drop-in dsv_enc, the decoders' output, a change
- * of subsampling, RGB. */
+ * dsv1_batch_stage returns DSVG_ERR_ARG while a format is set.  Not offered: the drop-in dsv_enc and dsv_dec (it returns a host
+ * DSV_FRAME), RGB, upsampling. */
 int  dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf);
 /* dsv1_resladder_open for sources of format *pf (NULL or the default: dsv1_resladder_open itself).  The conversion runs on the
  * scaler's stream in front of the scales; a geometry of the source's size and dsv1_resladder_src_quality_enable read the CONVERTED
@@ -414,12 +417,37 @@ int  dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const ds
  * written), DSV_DEC_GOT_META, DSV_DEC_EOS or DSV_DEC_ERROR; fnum[s] = frame number (-1 if none).  The decoded frame
  * of stream s is written tightly packed planar (Y, U, V) at yuv_out + s*out_pitch (out_pitch 0 = frame size), in
  * device memory (asynchronous: dsvg_ctx_sync(dsv1_decbatch_ctx(d)) before reading) or host memory (synchronised).
- * Reference pictures stay resident on the device.  Returns 0 or a DSVG_ERR_*. */
+ * Reference pictures stay resident on the device.  Returns 0 or a DSVG_ERR_*.
+ *
+ * DECODER OUTPUT FORMATS (csrc/k_pixout.hip; stated in numpy in tests/_pixout.py).  With a format set, ONE pass reads the decoded
+ * pictures and writes frames of dsv1_pix_format *pf (layouts, pitches and frame stride as for sources) at subsampling out_subsamp,
+ * in the place of the packed planar pass.  out_subsamp: the streams' own; 4:2:2 from 4:4:4 streams; 4:2:0 from 4:4:4 or 4:2:2 streams
+ * (the reference CLI's -out420p, on the device); every other pair -- anything from 4:1:1, any upsampling -- is DSVG_ERR_ARG, and so
+ * is a layout that is not valid at out_subsamp (dsv1_pix_frame_bytes(pf, w, h, out_subsamp) == 0).  Luma is untouched; with cw x ch a
+ * chroma plane of the stream, horizontal halving is o[y][i] = (c[y][2i] + c[y][min(2i+1, cw-1)] + 1) >> 1 for i < (cw+1)/2, vertical
+ * halving o[j][x] = (c[2j][x] + c[min(2j+1, ch-1)][x] + 1) >> 1 for j < (ch+1)/2, 4:4:4 -> 4:2:0 the horizontal step, rounded to 8
+ * bits, then the vertical one (conv444to422 / conv422to420, in the order dsv_main.c applies them).  A sample v of depth 8 is its
+ * byte; of depth d > 8 the little-endian word v << (d - 8), moved up by 16 - d when msb_aligned (v << 8: P010), every other bit
+ * zero -- so dsv1_convert_clip of the output gives the planar frames back.  Never written: the bytes between a row's end and its
+ * pitch, between the planes' end and frame_bytes, beyond the last frame's planes; the second luma byte of the last macro-pixel of
+ * an odd-width packed row repeats the row's last luma sample.
+ * dsv1_decbatch_set_output_format: between calls; from the next decode call on.  pf == NULL, or planar / 8 bits / tight with the
+ * streams' own subsampling, switches back to the packed planar pass.  An invalid combination is DSVG_ERR_ARG and leaves the
+ * setting in force as it was.  The setting outlives the context the batch rebuilds on a change of block size.
+ * dsv1_decbatch_out_frame_bytes: what one output frame occupies under the setting in force -- out_pitch when 0 is passed;
+ * a smaller out_pitch is DSVG_ERR_ARG.  Frame s at yuv_out + s * out_pitch; streams without a picture in a call keep their frame.
+ * dsv1_export_clip: the standalone twin of dsv1_convert_clip: n tightly packed planar 8-bit frames (w x h at subsamp) -> n frames
+ * of *pf at out_subsamp, frame_bytes apart, host or device memory (on_device: both), any w, h >= 1, synchronous; the last frame
+ * ends with its planes. */
 typedef struct dsv1_decbatch dsv1_decbatch;
 int  dsv1_decbatch_open(dsv1_decbatch **out, int device, const DSV_META *meta, int nstreams);
 int  dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out, size_t out_pitch, int out_on_device,
                           int *status, DSV_FNUM *fnum);
 void dsv1_decbatch_close(dsv1_decbatch *d);
+int  dsv1_decbatch_set_output_format(dsv1_decbatch *d, const dsv1_pix_format *pf, int out_subsamp);
+size_t dsv1_decbatch_out_frame_bytes(const dsv1_decbatch *d);
+int  dsv1_export_clip(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsv1_pix_format *pf, int out_subsamp,
+                      int on_device);
 void *dsv1_decbatch_ctx(dsv1_decbatch *d);      /* (ask again after every decode call: the batch builds a new context when its streams
                                                   * announce another block size while none of them holds a reference picture) */
 

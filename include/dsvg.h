@@ -330,6 +330,35 @@ int dsvg_upload_recon_raw(dsvg_ctx *ctx, int recon_slot, const uint8_t *raw, siz
  * Before reading it: dsvg_ctx_sync, or order the consumer behind the pass with dsvg_ctx_join(ctx, consumer_stream) / a dsvg_ctx_stream()
  * handle fetched AFTER this call.  Host output: copied back and synchronised. */
 int dsvg_pack_recons(dsvg_ctx *ctx, int n, const int *recon_slots, void *yuv_out, size_t out_pitch, int out_on_device);
+/* An output pixel format resolved for one geometry (the session layer works it out: include/dsv1_api.h, decoder output formats).  A
+ * SEGMENT is one output plane and the planes of the decoded frame (0 Y, 1 U, 2 V) that feed it, in the order their samples appear:
+ * PLAIN one plane, sample for sample; PAIR two planes interleaved; YUYV / UYVY all three as 4:2:2 macro-pixels.  hd / vd: the chroma
+ * planes are halved horizontally / vertically on the way, o = (a + b + 1) >> 1 with the last column / row repeated, horizontally
+ * first.  wide: a sample v is written as the little-endian 16-bit word v << shift. */
+enum { DSVG_PIXOUT_PLAIN, DSVG_PIXOUT_PAIR, DSVG_PIXOUT_YUYV, DSVG_PIXOUT_UYVY };
+typedef struct {
+    int kind, nin, in_plane[3];
+    int rows;                /* of the output plane */
+    int width;               /* samples per row of the first input plane as they arrive (chroma: after the halving) */
+    int cwidth;              /* YUYV / UYVY: macro-pixels per row */
+    size_t off, pitch;       /* the output plane inside an output frame */
+} dsvg_pixout_seg;
+typedef struct {
+    int nseg, wide, shift, hd, vd;
+    size_t frame_bytes;      /* what one output frame occupies: the least distance from frame to frame */
+    size_t planes_bytes;     /* where its last plane ends */
+    dsvg_pixout_seg seg[3];
+} dsvg_pixout;
+/* dsvg_pack_recons for an output format: slot recon_slots[i] -> frame out_index[i] (NULL: i) at out + out_index[i] * out_pitch, in
+ * ONE pass over the bordered reconstructions (csrc/k_pixout.hip) that writes only the bytes of samples -- never the padding behind a
+ * row, behind the planes or between frames.  Stream placement, ordering and the second pass of a flagged decoder call exactly as
+ * dsvg_pack_recons.  Host output: staged on the device and copied back with one copy where the frames are dense (no padding, every
+ * frame written); else the caller's buffer goes up first so that what the pass does not write comes back as it was. */
+int dsvg_export_recons(dsvg_ctx *ctx, int n, const int *recon_slots, const int *out_index, void *out, size_t out_pitch,
+                       int out_on_device, const dsvg_pixout *fmt);
+/* the same pass over n tightly packed planar frames, frame_bytes apart on the output side; device pointers, or host memory that is
+ * staged (the destination goes up first, as above).  Any w, h >= 1.  Synchronous. */
+int dsvg_export_planar(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsvg_pixout *fmt, int on_device);
 
 /* Decoder side: coefficient (run,value) pairs parsed on the host are scattered + dequantised,
  * inverse transformed and motion compensated on the device (dsv_dec dsv_decoder.c:379-436). */
