@@ -69,6 +69,22 @@ class PixFormat(_C.Structure):
         super().__init__(layout, depth, msb_aligned, (_C.c_int * 3)(*pitch), frame_bytes)
 
 
+RGB_RGB24, RGB_BGR24, RGB_RGBA, RGB_BGRA, RGB_ARGB, RGB_ABGR, RGB_PLANAR_RGB, RGB_PLANAR_GBR = range(8)   # DSV1_RGB_*
+MATRIX_BT601, MATRIX_BT709, MATRIX_BT2020 = 0, 1, 2   # DSV1_MATRIX_*
+CHROMA_REPLICATE, CHROMA_LINEAR = 0, 1   # DSV1_CHROMA_*
+
+
+class RgbFormat(_C.Structure):
+    """dsv1_rgb_format: 8-bit RGB frames -- order (RGB_*), matrix (MATRIX_*), full_range (0: 16..235 / 16..240, 1: 0..255), upsample
+    (CHROMA_*: how chroma reaches the luma grid on output), row pitches in bytes (0 = tight) and the bytes from frame to frame (0 =
+    tight)"""
+    _fields_ = [("order", _C.c_int), ("matrix", _C.c_int), ("full_range", _C.c_int), ("upsample", _C.c_int), ("pitch", _C.c_int * 3),
+                ("frame_bytes", _C.c_size_t)]
+
+    def __init__(self, order=RGB_RGB24, matrix=MATRIX_BT709, full_range=0, upsample=CHROMA_LINEAR, pitch=(0, 0, 0), frame_bytes=0):
+        super().__init__(order, matrix, full_range, upsample, (_C.c_int * 3)(*pitch), frame_bytes)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -176,6 +192,15 @@ def lib():
         L.dsv1_decbatch_out_frame_bytes.restype = _C.c_size_t
         L.dsv1_decbatch_out_frame_bytes.argtypes = [_C.c_void_p]
         L.dsv1_export_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int]
+        L.dsv1_rgb_frame_bytes.restype = _C.c_size_t
+        L.dsv1_rgb_frame_bytes.argtypes = [_C.POINTER(RgbFormat), _C.c_int, _C.c_int]
+        L.dsv1_rgb_tables.argtypes = [_C.c_int, _C.c_int, _C.POINTER(_C.c_int32), _C.POINTER(_C.c_int32)]
+        L.dsv1_rgb_import_clip.argtypes = [_C.c_int, _C.c_void_p, _C.POINTER(RgbFormat), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int]
+        L.dsv1_rgb_export_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(RgbFormat), _C.c_int]
+        L.dsv1_batch_set_source_rgb.argtypes = [_C.c_void_p, _C.POINTER(RgbFormat)]
+        L.dsv1_resladder_open_rgb.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int,
+                                              _C.c_int, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_decbatch_set_output_rgb.argtypes = [_C.c_void_p, _C.POINTER(RgbFormat)]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         _lib = L
@@ -306,6 +331,14 @@ class Batch:
         _chk(self.L.dsv1_batch_set_source_format(self.h, _C.byref(pf) if pf is not None else None), "dsv1_batch_set_source_format")
         planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, self.fmt)
         self.frame_bytes = pix_frame_bytes(pf, self.width, self.height, self.fmt) if pf is not None else planar
+
+    def set_source_rgb(self, rf):
+        """from the next submit on, encode() / submit() take RGB clips of RgbFormat rf (dsv1_batch_set_source_rgb), converted on the
+        GPU to the batch's subsampling; None switches back to packed planar 8-bit.  Between batches only; replaces a source format
+        set before.  The input-length check follows."""
+        _chk(self.L.dsv1_batch_set_source_rgb(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_rgb")
+        planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, self.fmt)
+        self.frame_bytes = rgb_frame_bytes(rf, self.width, self.height) if rf is not None else planar
 
     def dropped_recons(self):
         """(dropped, remedied): reference pictures coded without a reconstruction because nobody predicts from them / coded again
@@ -602,6 +635,64 @@ def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=Non
     return res
 
 
+def rgb_frame_bytes(rf, w, h):
+    """bytes from frame to frame of an RGB clip of RgbFormat rf (dsv1_rgb_frame_bytes); ValueError for an invalid format"""
+    n = lib().dsv1_rgb_frame_bytes(_C.byref(rf), w, h)
+    if not n:
+        raise ValueError("not a valid RGB format for %dx%d frames" % (w, h))
+    return int(n)
+
+
+def rgb_tables(matrix, full_range):
+    """(forward Q16 rows Y, Cb, Cr over R, G, B as int32 [3][3]; inverse Q14 IY, RV, GU, GV, BU as int32 [5]) the library holds
+    (dsv1_rgb_tables; host only); ValueError for an unknown matrix or range"""
+    fwd, inv = (_C.c_int32 * 9)(), (_C.c_int32 * 5)()
+    if lib().dsv1_rgb_tables(matrix, full_range, fwd, inv) != 0:
+        raise ValueError("no such matrix / range: %r, %r" % (matrix, full_range))
+    return _np.array(fwd[:], dtype=_np.int32).reshape(3, 3), _np.array(inv[:], dtype=_np.int32)
+
+
+def rgb_import_clip(clip, rf, w, h, fmt, device=0, n=None, out=None):
+    """RGB frames of RgbFormat rf to packed planar 8-bit Y, Cb, Cr at subsampling fmt on the GPU (dsv1_rgb_import_clip): clip numpy uint8
+    (host; a whole number of frames, the last one may end with its planes), or a device pointer with n frames and `out` a device
+    pointer for the result.  Host input returns numpy uint8 [frames][planar frame_bytes]."""
+    L = lib()
+    sfb = rgb_frame_bytes(rf, w, h)
+    dfb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_rgb_import_clip(device, clip, _C.byref(rf), w, h, fmt, n, out, 1), "dsv1_rgb_import_clip")
+        return out
+    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
+    if a.size % sfb or not a.size:
+        raise ValueError("a clip of this format is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
+    frames = a.size // sfb
+    res = _np.zeros((frames, dfb), dtype=_np.uint8)
+    _chk(L.dsv1_rgb_import_clip(device, a.ctypes.data, _C.byref(rf), w, h, fmt, frames, res.ctypes.data, 0), "dsv1_rgb_import_clip")
+    return res
+
+
+def rgb_export_clip(clip, w, h, fmt, rf, device=0, n=None, out=None):
+    """packed planar 8-bit frames (w x h at subsampling fmt) to RGB frames of RgbFormat rf on the GPU (dsv1_rgb_export_clip), chroma
+    upsampled as rf.upsample says: clip numpy uint8 [frames][frame_bytes] (host), or a device pointer with n frames and `out` a device
+    pointer for the result.  Host input returns numpy uint8 [frames][frame bytes of rf]; `out` (a numpy uint8 array of that size) is
+    written in place -- what the format pads stays as it was."""
+    L = lib()
+    sfb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_rgb_export_clip(device, clip, w, h, fmt, n, out, _C.byref(rf), 1), "dsv1_rgb_export_clip")
+        return out
+    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
+    if a.size % sfb or not a.size:
+        raise ValueError("a planar clip is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
+    frames = a.size // sfb
+    dfb = rgb_frame_bytes(rf, w, h)
+    res = _np.zeros((frames, dfb), dtype=_np.uint8) if out is None else out
+    if res.dtype != _np.uint8 or not res.flags.c_contiguous or res.size < frames * dfb:
+        raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % (frames * dfb))
+    _chk(L.dsv1_rgb_export_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(rf), 0), "dsv1_rgb_export_clip")
+    return res
+
+
 def scale_taps(S, D, filt):
     """taps of one axis of the resampler (dsv1_scale_taps); ValueError outside 1 <= S / D <= 8"""
     t = lib().dsv1_scale_taps(S, D, filt)
@@ -677,8 +768,11 @@ class ResLadder:
     SOURCE clip [source][frame] (nsources x F frames of w x h: one upload per call); results are per output stream
     k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
 
-    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None):
-        """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit)"""
+    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None, src_rgb=None):
+        """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit); src_rgb: their RgbFormat
+        instead (dsv1_resladder_open_rgb)"""
+        if src_format is not None and src_rgb is not None:
+            raise ValueError("src_format and src_rgb exclude each other")
         geoms = [(gw, gh, list(rates)) for gw, gh, rates in geoms]
         self.L = lib()
         self.h = _C.c_void_p(None)
@@ -689,7 +783,10 @@ class ResLadder:
         rr = (ResRung * max(len(geoms), 1))(*[ResRung(gw, gh, len(r), a) for (gw, gh, r), a in zip(geoms, self._arrs)])
         meta = Meta()
         meta.width, meta.height, meta.subsamp = w, h, fmt
-        if src_format is None:
+        if src_rgb is not None:
+            _chk(self.L.dsv1_resladder_open_rgb(_C.byref(self.h), _C.byref(meta), _C.byref(src_rgb), rr, len(geoms), device, nsources,
+                                                frames_per_call, filt), "dsv1_resladder_open_rgb")
+        elif src_format is None:
             _chk(self.L.dsv1_resladder_open(_C.byref(self.h), _C.byref(meta), rr, len(geoms), device, nsources, frames_per_call, filt),
                  "dsv1_resladder_open")
         else:
@@ -698,6 +795,8 @@ class ResLadder:
         self.ntot = sum(n for _, _, n in self.geoms)
         self.nstreams = self.L.dsv1_resladder_nstreams(self.h)
         self.frame_bytes = w * h + 2 * _chroma_size(w, h, fmt) if src_format is None else pix_frame_bytes(src_format, w, h, fmt)
+        if src_rgb is not None:
+            self.frame_bytes = rgb_frame_bytes(src_rgb, w, h)
         self.ctx = self.L.dsv1_batch_ctx(self.L.dsv1_resladder_batch(self.h, 0))
         self._dev, self._pin, self._pending = [], [], []
 
@@ -876,6 +975,18 @@ class DecBatch:
         osub = self.fmt if out_subsamp is None else out_subsamp
         if self.L.dsv1_decbatch_set_output_format(self.h, None if pixformat is None else _C.byref(pixformat), osub) != 0:
             raise ValueError("not a valid output format for these streams (subsampling 0x%x -> 0x%x)" % (self.fmt, osub))
+        self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))
+        if self._dev is not None:                      # (sized for the frames of the setting before)
+            self.sync()
+            self.L.dsvg_dev_free(self.ctx, self._dev)
+            self._dev = None
+
+    def set_output_rgb(self, rf):
+        """from the next decode() on, frames are written as RGB of RgbFormat rf (dsv1_decbatch_set_output_rgb); None switches back to
+        packed planar.  Replaces an output format set before.  frame_bytes follows; ValueError (and the setting as it was) for an
+        invalid format."""
+        if self.L.dsv1_decbatch_set_output_rgb(self.h, None if rf is None else _C.byref(rf)) != 0:
+            raise ValueError("not a valid RGB output format for these streams (subsampling 0x%x)" % self.fmt)
         self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))
         if self._dev is not None:                      # (sized for the frames of the setting before)
             self.sync()

@@ -103,3 +103,6 @@ struct Prof {
 struct PoSource { int w[3], h[3]; long long pitch[3], off[3]; long long fb; };
 int  pixout_check(const dsvg_pixout *F, const PoSource &S, size_t dfb);
 int  launch_pixout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const uint8_t *src, const int *tab_d, int n, uint8_t *dst, size_t dfb, Prof *pf = nullptr);
+// k_rgb.hip: the same for an RGB format (F->rgb.on): pixout_check / launch_pixout hand it over
+int  rgbout_check(const dsvg_pixout *F, const PoSource &S, size_t dfb);
+int  launch_rgbout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const uint8_t *src, const int *tab_d, int n, uint8_t *dst, size_t dfb);

@@ -53,6 +53,34 @@ int  dsvg_pixconv_order(dsvg_pixconv *c, dsvg_ctx *ctx);
 int  dsvg_pixconv_sync(dsvg_pixconv *c);
 int  dsvg_pixconv_download(dsvg_pixconv *c, void *host, const void *dptr, size_t bytes);
 
+
+/* ---- RGB (include/dsv1_api.h, RGB; k_rgb.hip; host side: host/dsv1_rgb.c) ----
+ * An RGB format resolved for one geometry and one subsampling of the YCbCr side: the planes, the position of R, G and B in memory
+ * order, the tables.  One layout serves both directions. */
+typedef struct {
+    int w, h, hs, vs, cw, ch;
+    int nplanes;                /* 1: packed (bpp 3 or 4); 3: planar (bpp 1) */
+    int bpp;
+    int first;                  /* 4-byte orders: the byte of the pixel that holds the first colour component (0 or 1) */
+    int comp[3];                /* memory position k (byte after `first` / plane k) holds 0 R, 1 G, 2 B */
+    int linear;                 /* output: DSV1_CHROMA_LINEAR */
+    int oy;
+    int32_t fwd[9], inv[5];
+    size_t off[3], pitch[3];
+    size_t frame_bytes;         /* RGB frame to frame */
+    size_t planes_bytes;        /* what an RGB frame holds */
+    size_t yuv_frame_bytes;     /* the tightly packed planar frame */
+} dsv1_rgb_layout;
+/* DSVG_OK, or DSVG_ERR_ARG for whatever include/dsv1_api.h calls invalid (4:1:1 included); no device is looked at */
+int dsv1_rgb_layout_of(const dsv1_rgb_format *rf, int w, int h, int subsamp, dsv1_rgb_layout *L);
+/* the output pass's view of it: frames decoded at `subsamp` -> RGB frames */
+int dsv1_rgbout_of(const dsv1_rgb_format *rf, int w, int h, int subsamp, dsvg_pixout *F);
+/* a dsvg_pixconv whose pass is the RGB import (k_rgb.hip) instead of a re-packing: everything else -- streams, upload buffers, _run,
+ * _run_on, _order -- is the converter's */
+int  dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv1_rgb_layout *L);
+/* the pass itself, on a stream of the caller's: nframes RGB frames of layout *L -> tightly packed planar frames (device pointers) */
+int  dsvg_rgb_import_run(void *stream, const dsv1_rgb_layout *L, const void *src_dev, int nframes, void *dst_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -375,6 +375,18 @@ int dsv1_decbatch_set_output_format(dsv1_decbatch *d, const dsv1_pix_format *pf,
     return DSVG_OK;
 }
 
+int dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf)
+{
+    dsvg_pixout F;
+    int rc;
+    if (!d) return DSVG_ERR_ARG;
+    if (!rf) { d->out_set = 0; return DSVG_OK; }
+    if ((rc = dsv1_rgbout_of(rf, d->meta.width, d->meta.height, d->meta.subsamp, &F))) return rc;     /* (the setting in force stays) */
+    d->out_set = 1;
+    d->out = F;
+    return DSVG_OK;
+}
+
 size_t dsv1_decbatch_out_frame_bytes(const dsv1_decbatch *d)
 {
     if (!d) return 0;

@@ -1279,6 +1279,29 @@ int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
     return DSVG_OK;
 }
 
+/* the RGB twin: the same converter object around the RGB import pass; the two setters replace each other */
+int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
+{
+    dsv1_rgb_layout L;
+    const DSV_META *m;
+    int rc, k;
+    if (!b) return DSVG_ERR_ARG;
+    if (!rf) return dsv1_batch_set_source_format(b, NULL);
+    m = &b->enc[0].vidmeta;
+    if (dsv1_rgb_layout_of(rf, m->width, m->height, m->subsamp, &L)) {
+        dsv1_log(1, "dsv1_batch_set_source_rgb: not a valid RGB format for %dx%d, subsampling 0x%x", m->width, m->height, m->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_rgb with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    dsvg_pixconv_destroy(b->pc);
+    b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL;
+    if ((rc = dsvg_pixconv_create_rgb(&b->pc, b->device, &L))) return rc;
+    for (k = 0; k < 2 && !rc; k++) rc = dsvg_pixconv_alloc(b->pc, &b->pc_clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
+    if (rc) { dsvg_pixconv_destroy(b->pc); b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL; return rc; }
+    b->pc_raw_fb = L.frame_bytes;
+    return DSVG_OK;
+}
+
 /* a clip of the batch's source format -> the converted clip of the next submit's parity (device memory the batch owns, read as a held
  * clip until that batch's collect); the context's frame-load stream waits for the conversion on the device */
 static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)

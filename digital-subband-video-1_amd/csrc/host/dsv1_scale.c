@@ -184,11 +184,30 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
     return dsv1_resladder_open_src(out, src, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_rgb_format *rf,
+                              const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter);
+
 int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs, int ngeoms,
                             int device, int nsources, int frames_per_call, int filter)
 {
+    return resladder_open_fmt(out, src, pf, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+/* RGB sources: the RGB import pass (k_rgb.hip) in the converter's place, everything else as dsv1_resladder_open_src */
+int dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms,
+                            int device, int nsources, int frames_per_call, int filter)
+{
+    if (out) *out = NULL;
+    if (!rf) return DSVG_ERR_ARG;
+    return resladder_open_fmt(out, src, NULL, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_rgb_format *rf,
+                              const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter)
+{
     dsv1_resladder *r;
     dsv1_pix_layout pl;
+    dsv1_rgb_layout rl;
     int g, k, rc, ntot = 0, nscaled = 0, maxr = 0, dw[DSV1_MAX_GEOMS], dh[DSV1_MAX_GEOMS];
     if (out) *out = NULL;
     /* arguments first: nothing below touches a device until every geometry has passed */
@@ -200,6 +219,10 @@ int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv
         return DSVG_ERR_ARG;
     }
     if (pf && dsv1_pix_is_default(pf, src->width, src->height, src->subsamp)) pf = NULL;
+    if (rf && dsv1_rgb_layout_of(rf, src->width, src->height, src->subsamp, &rl)) {
+        dsv1_log(1, "dsv1_resladder_open_rgb: not a valid RGB format for %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
+        return DSVG_ERR_ARG;
+    }
     for (g = 0; g < ngeoms; g++) {
         const dsv1_res_rung *G = &rungs[g];
         if (!G->rates || G->nrates < 1 || G->nrates > DSV1_MAX_RUNGS) {
@@ -250,9 +273,9 @@ int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv
     }
     /* the scaler exists even when no geometry is scaled: host input is uploaded through it */
     if ((rc = dsvg_scaler_create(&r->sc, device, src->width, src->height, src->subsamp, nscaled, dw, dh, filter))) { dsv1_resladder_close(r); return rc; }
-    if (pf) {
-        r->raw_fb = pl.frame_bytes;
-        if ((rc = dsvg_pixconv_create(&r->pc, device, &pl))) { dsv1_resladder_close(r); return rc; }
+    if (pf || rf) {
+        r->raw_fb = rf ? rl.frame_bytes : pl.frame_bytes;
+        if ((rc = rf ? dsvg_pixconv_create_rgb(&r->pc, device, &rl) : dsvg_pixconv_create(&r->pc, device, &pl))) { dsv1_resladder_close(r); return rc; }
         for (k = 0; k < 2; k++)
             if ((rc = dsvg_scaler_alloc(r->sc, &r->conv[k], r->sfb * (size_t)nsources * frames_per_call))) { dsv1_resladder_close(r); return rc; }
     }

@@ -171,6 +171,8 @@ struct dsvg_pixconv {
     dsv1_pix_layout L;
     PixParams P;
     int nblocks = 0;
+    bool rgb = false;                    // the pass is the RGB import (k_rgb.hip) of layout R; L, P and nblocks are not used
+    dsv1_rgb_layout R;
     hipStream_t st = nullptr;
     hipEvent_t ev = nullptr;
     uint8_t *up[2] = {nullptr, nullptr};
@@ -232,6 +234,22 @@ extern "C" int dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pi
     return DSVG_OK;
 }
 
+// the converter of an RGB source: the same streams, buffers and ordering around another pass
+extern "C" int dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv1_rgb_layout *R)
+{
+    if (!out || !R || R->w < 1 || R->h < 1 || (R->nplanes != 1 && R->nplanes != 3)) { dsvg_set_error("bad converter arguments"); return DSVG_ERR_ARG; }
+    *out = nullptr;
+    if (dsvg_device_count() <= device || device < 0) { dsvg_set_error("HIP device %d not present", device); (void)hipGetLastError(); return DSVG_ERR_NODEVICE; }
+    dsvg_pixconv *c = new dsvg_pixconv();
+    c->device = device; c->rgb = true; c->R = *R;
+    memset(&c->L, 0, sizeof c->L);
+    memset(&c->P, 0, sizeof c->P);
+    const int rc = pixconv_streams(c);
+    if (rc) { dsvg_pixconv_destroy(c); return rc; }
+    *out = c;
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_pixconv_alloc(dsvg_pixconv *c, void **dptr, size_t bytes)
 {
     if (!c || !dptr) return DSVG_ERR_ARG;
@@ -279,6 +297,7 @@ extern "C" int dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *sr
     if (!c || !src_dev || !dst_dev || nframes < 1) { dsvg_set_error("bad convert arguments"); return DSVG_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
+    if (c->rgb) return dsvg_rgb_import_run(stream, &c->R, src_dev, nframes, dst_dev);
     PixParams P = c->P;
     for (int s = 0; s < P.nseg; s++) P.seg[s].fast = seg_fast(P, P.seg[s], src_dev, dst_dev);
     const bool wide = c->L.wide != 0;

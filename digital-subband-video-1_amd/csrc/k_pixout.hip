@@ -300,6 +300,7 @@ int pixout_check(const dsvg_pixout *F, const PoSource &S, size_t dfb)
 {
     PoParams P;
     int layout, nblocks;
+    if (F && F->rgb.on) return rgbout_check(F, S, dfb);
     return po_params(P, layout, nblocks, F, S, (long long)dfb);
 }
 
@@ -307,6 +308,7 @@ int launch_pixout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const
 {
     PoParams P;
     int layout = 0, nblocks = 0;
+    if (F && F->rgb.on) return launch_rgbout(st, F, S, src, tab_d, n, dst, dfb);     // (k_rgb.hip; not bracketed by the profiler)
     const int rc = po_params(P, layout, nblocks, F, S, (long long)dfb);
     if (rc) { if (rc == DSVG_ERR_ARG) dsvg_set_error("the output format does not fit the frames"); return rc; }
     double bytes = 0;

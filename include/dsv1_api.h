@@ -402,7 +402,7 @@ int  dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, i
  * DSV1_CLIP_HELD clip stays unchanged until that batch's collect and submit does not wait.  The converted clip lives in buffers
  * the batch owns (one per call parity) and goes on as a held clip.  Plain batches, quality ladders (per source) and chain mode.
  * dsv1_batch_stage returns DSVG_ERR_ARG while a format is set.  Not offered: the drop-in dsv_enc and dsv_dec (it returns a host
- * DSV_FRAME), RGB, upsampling. */
+ * DSV_FRAME), upsampling between YCbCr subsamplings.  RGB, in and out: the extension at the end of this file. */
 int  dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf);
 /* dsv1_resladder_open for sources of format *pf (NULL or the default: dsv1_resladder_open itself).  The conversion runs on the
  * scaler's stream in front of the scales; a geometry of the source's size and dsv1_resladder_src_quality_enable read the CONVERTED
@@ -450,6 +450,71 @@ int  dsv1_export_clip(int device, const void *src, int w, int h, int subsamp, in
                       int on_device);
 void *dsv1_decbatch_ctx(dsv1_decbatch *d);      /* (ask again after every decode call: the batch builds a new context when its streams
                                                   * announce another block size while none of them holds a reference picture) */
+
+/* ---- extension: RGB, in and out (csrc/k_rgb.hip; stated in numpy in tests/_rgb.py) ----
+ * What renderers, capture and displays hold: 8-bit RGB, packed or planar.  Unlike the pixel formats above this is no re-packing: a
+ * matrix, a range, chroma downsampling on the way in and upsampling on the way out.  Exact integers, no floating point at run time.
+ * LAYOUTS.  RGB24 / BGR24: 3 bytes per pixel, one plane.  RGBA / BGRA / ARGB / ABGR: 4 bytes per pixel; the A byte is ignored on input
+ * and written as 255 on output.  PLANAR_RGB / PLANAR_GBR: three planes of w x h bytes in that order.  pitch[p]: bytes from row to row
+ * of plane p, 0 = tight (packed orders: pitch[0] only); frame_bytes: frame to frame, 0 = tight.  Any w, h >= 1.  Padding bytes (a
+ * pitch beyond the row, a stride beyond the planes, everything beyond the last frame's planes) are never read into a result and
+ * never written.  A pitch below a row's bytes, a frame_bytes below the planes, an unknown order, matrix or upsampling mode, or
+ * full_range outside 0 / 1: dsv1_rgb_frame_bytes returns 0 and every entry point DSVG_ERR_ARG before any device work.  4:1:1 with RGB
+ * is DSVG_ERR_ARG in both directions.
+ * MATRIX AND RANGE.  BT.601 (Kr 0.299, Kb 0.114), BT.709 (0.2126, 0.0722), BT.2020 non-constant-luminance (0.2627, 0.0593); Kg = 1 -
+ * Kr - Kb.  full_range 0: sy = 219/255, sc = 224/255, oy = 16; 1: sy = sc = 1, oy = 0.  r() rounds an exact rational half up.
+ * Forward, Q16: the Y row (R, G, B) is r(65536 sy Kr), the remainder of r(65536 sy), r(65536 sy Kb); with hf = r(65536 sc / 2) the Cb
+ * row is -r(65536 sc Kr / (2 (1 - Kb))), -(hf + that), hf and the Cr row hf, -(hf + the B coefficient), -r(65536 sc Kb / (2 (1 - Kr))).
+ * Inverse, Q14: IY = r(16384 / sy), RV = r(16384 * 2 (1 - Kr) / sc), GU = -r(16384 * 2 (1 - Kb) Kb / (Kg sc)), GV = -r(16384 * 2 (1 -
+ * Kr) Kr / (Kg sc)), BU = r(16384 * 2 (1 - Kb) / sc).  dsv1_rgb_tables returns the literals the library holds: fwd = the three rows,
+ * inv = IY, RV, GU, GV, BU.
+ * IN.  Per pixel, int32, >> arithmetic: Y = clamp((Yrow . (R, G, B) + (oy << 16) + 32768) >> 16), Cb / Cr = clamp((row . (R, G, B) +
+ * (128 << 16) + 32768) >> 16), clamp to 0..255 (it binds: full-range pure blue and red give 256).  The 8-bit 4:4:4 chroma planes are
+ * then halved as the decoder output pass halves (conv444to422 / conv422to420: (a + b + 1) >> 1 over column pairs, the last column
+ * repeated, rounded to 8 bits, then over row pairs), so import(rgb, S) == dsv1_export_clip(import(rgb, 4:4:4), 4:4:4 -> S).
+ * OUT.  Chroma is brought to the luma grid first (hs / vs the streams' chroma shifts).  DSV1_CHROMA_REPLICATE: c[y >> vs][x >> hs].
+ * DSV1_CHROMA_LINEAR, centre-sited, the mirror of the halving: vertically first where vs = 1, o[2j] = (3 c[j] + c[max(j - 1, 0)] + 2)
+ * >> 2, o[2j+1] = (3 c[j] + c[min(j + 1, ch - 1)] + 2) >> 2, rows at or beyond h dropped; then the same over columns, on that 8-bit
+ * result, where hs = 1.  With y = Y - oy, u = Cb - 128, v = Cr - 128: R = clamp((IY y + RV v + 8192) >> 14), G = clamp((IY y + GU u +
+ * GV v + 8192) >> 14), B = clamp((IY y + BU u + 8192) >> 14).  `upsample` is read on output only (but validated always).
+ * Not offered: chroma siting other than centre, dither, deeper or float RGB, constant-luminance BT.2020, transfer functions. */
+#define DSV1_RGB_RGB24      0
+#define DSV1_RGB_BGR24      1
+#define DSV1_RGB_RGBA       2
+#define DSV1_RGB_BGRA       3
+#define DSV1_RGB_ARGB       4
+#define DSV1_RGB_ABGR       5
+#define DSV1_RGB_PLANAR_RGB 6
+#define DSV1_RGB_PLANAR_GBR 7
+#define DSV1_MATRIX_BT601   0
+#define DSV1_MATRIX_BT709   1
+#define DSV1_MATRIX_BT2020  2        /* non-constant luminance */
+#define DSV1_CHROMA_REPLICATE 0
+#define DSV1_CHROMA_LINEAR    1
+typedef struct { int order, matrix, full_range, upsample; int pitch[3]; size_t frame_bytes; } dsv1_rgb_format;
+size_t dsv1_rgb_frame_bytes(const dsv1_rgb_format *rf, int w, int h);                 /* 0 = invalid */
+int  dsv1_rgb_tables(int matrix, int full_range, int32_t fwd[9], int32_t inv[5]);      /* host only */
+/* n RGB frames -> n tightly packed planar 8-bit frames at `subsamp` (4:4:4, 4:2:2, 4:2:0) and back; host or device memory
+ * (on_device: src and dst are device pointers), synchronous; the last RGB frame ends with its planes. */
+int  dsv1_rgb_import_clip(int device, const void *src, const dsv1_rgb_format *rf, int w, int h, int subsamp, int n, void *dst,
+                          int on_device);
+int  dsv1_rgb_export_clip(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsv1_rgb_format *rf,
+                          int on_device);
+/* dsv1_batch_set_source_format for RGB clips, with its contract (between batches only; host input uploaded raw and converted on the
+ * converter's stream with no host wait; a plain device clip is the caller's again when submit returns; a DSV1_CLIP_HELD clip stays
+ * unchanged until collect; dsv1_batch_stage is refused while set; plain batches, quality ladders, chain mode).  The target
+ * subsampling is the batch's vidmeta.subsamp.  The two setters replace each other; NULL switches back to packed planar.  An invalid
+ * format leaves the setting in force as it was. */
+int  dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf);
+/* dsv1_resladder_open_src with the RGB converter in its place: the converted clip stands for the source (scales, a geometry of the
+ * source's size, get_src_sse / get_src_ssim); dsv1_resladder_uploads counts the raw RGB bytes. */
+int  dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const dsv1_rgb_format *rf, const dsv1_res_rung *rungs,
+                             int ngeoms, int device, int nsources, int frames_per_call, int filter);
+/* dsv1_decbatch_set_output_format for RGB frames, with its contract (ONE pass over the bordered reconstructions in the place of the
+ * packing pass; dsv1_decbatch_out_frame_bytes follows; a smaller out_pitch is refused; streams without a picture keep their frame;
+ * the int32 second pass writes its frames again in the format; the setting outlives a rebuilt context).  The two output setters
+ * replace each other; NULL switches back to packed planar. */
+int  dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf);
 
 #ifdef __cplusplus
 }

@@ -335,7 +335,7 @@ int dsvg_pack_recons(dsvg_ctx *ctx, int n, const int *recon_slots, void *yuv_out
  * PLAIN one plane, sample for sample; PAIR two planes interleaved; YUYV / UYVY all three as 4:2:2 macro-pixels.  hd / vd: the chroma
  * planes are halved horizontally / vertically on the way, o = (a + b + 1) >> 1 with the last column / row repeated, horizontally
  * first.  wide: a sample v is written as the little-endian 16-bit word v << shift. */
-enum { DSVG_PIXOUT_PLAIN, DSVG_PIXOUT_PAIR, DSVG_PIXOUT_YUYV, DSVG_PIXOUT_UYVY };
+enum { DSVG_PIXOUT_PLAIN, DSVG_PIXOUT_PAIR, DSVG_PIXOUT_YUYV, DSVG_PIXOUT_UYVY, DSVG_PIXOUT_RGB };
 typedef struct {
     int kind, nin, in_plane[3];
     int rows;                /* of the output plane */
@@ -343,11 +343,17 @@ typedef struct {
     int cwidth;              /* YUYV / UYVY: macro-pixels per row */
     size_t off, pitch;       /* the output plane inside an output frame */
 } dsvg_pixout_seg;
+/* RGB output (csrc/k_rgb.hip; include/dsv1_api.h, RGB): on != 0 makes the format an RGB one.  Its segments are the RGB planes (kind
+ * DSVG_PIXOUT_RGB, one for the packed orders, three for the planar ones; rows = h, width = w); hs / vs are the chroma shifts of the
+ * decoded frames, which the pass upsamples (linear != 0: centre-sited linear, else replication) before the Q14 inverse matrix
+ * inv = IY, RV, GU, GV, BU with luma offset oy. */
+typedef struct { int on, order, linear, hs, vs, oy; int32_t inv[5]; } dsvg_rgbout;
 typedef struct {
     int nseg, wide, shift, hd, vd;
     size_t frame_bytes;      /* what one output frame occupies: the least distance from frame to frame */
     size_t planes_bytes;     /* where its last plane ends */
     dsvg_pixout_seg seg[3];
+    dsvg_rgbout rgb;
 } dsvg_pixout;
 /* dsvg_pack_recons for an output format: slot recon_slots[i] -> frame out_index[i] (NULL: i) at out + out_index[i] * out_pitch, in
  * ONE pass over the bordered reconstructions (csrc/k_pixout.hip) that writes only the bytes of samples -- never the padding behind a
