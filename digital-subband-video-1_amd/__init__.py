@@ -85,6 +85,18 @@ class RgbFormat(_C.Structure):
         super().__init__(order, matrix, full_range, upsample, (_C.c_int * 3)(*pitch), frame_bytes)
 
 
+DEINT_FRAME, DEINT_FIELD = 0, 1
+
+
+class Deint(_C.Structure):
+    """dsv1_deint: the deinterlacer's mode (DEINT_FRAME: n frames in, n out; DEINT_FIELD: n in, 2n out) and the field order of the
+    source (tff = 1: the top field is the earlier one).  include/dsv1_api.h, Deinterlacing, has the definition."""
+    _fields_ = [("mode", _C.c_int), ("tff", _C.c_int)]
+
+    def __init__(self, mode=DEINT_FRAME, tff=1):
+        super().__init__(mode, tff)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -201,6 +213,13 @@ def lib():
         L.dsv1_resladder_open_rgb.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int,
                                               _C.c_int, _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_decbatch_set_output_rgb.argtypes = [_C.c_void_p, _C.POINTER(RgbFormat)]
+        L.dsv1_deint_out_frames.argtypes = [_C.POINTER(Deint), _C.c_int]
+        L.dsv1_deinterlace_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p,
+                                            _C.POINTER(Deint), _C.c_int]
+        L.dsv1_batch_set_source_deinterlace.argtypes = [_C.c_void_p, _C.POINTER(Deint)]
+        L.dsv1_batch_deinterlace_reset.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_set_deinterlace.argtypes = [_C.c_void_p, _C.POINTER(Deint)]
+        L.dsv1_resladder_deinterlace_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         _lib = L
@@ -317,10 +336,27 @@ class Batch:
     def _input(self, yuv):
         """a host clip as the C entry points read it: nsources x F frames, whatever it is given (checked here)"""
         a = _np.ascontiguousarray(yuv, dtype=_np.uint8)
-        if a.size != self.nsources * self.F * self.frame_bytes:
+        fin = self.in_frames
+        if a.size != self.nsources * fin * self.frame_bytes:
             raise ValueError("a batch is %d %s x %d frames x %d bytes, got %d bytes" % (
-                self.nsources, "streams" if self.nsources == self.nstreams else "sources", self.F, self.frame_bytes, a.size))
+                self.nsources, "streams" if self.nsources == self.nstreams else "sources", fin, self.frame_bytes, a.size))
         return a
+
+    @property
+    def in_frames(self):
+        """input frames per source and call: frames_per_call, or half of it behind a field-rate deinterlacer"""
+        return self.F // 2 if getattr(self, "_deint_field", False) else self.F
+
+    def set_source_deinterlace(self, di):
+        """from the next submit on the clips are interlaced and deinterlaced on the GPU as Deint di says, behind the source format's
+        conversion (dsv1_batch_set_source_deinterlace); None switches it off.  Between batches only; forgets every source's history.
+        frames_per_call counts coded pictures: with DEINT_FIELD a call takes in_frames = frames_per_call / 2 frames per source."""
+        _chk(self.L.dsv1_batch_set_source_deinterlace(self.h, _C.byref(di) if di is not None else None), "dsv1_batch_set_source_deinterlace")
+        self._deint_field = di is not None and di.mode == DEINT_FIELD
+
+    def deinterlace_reset(self, source=-1):
+        """a discontinuity: the next frame of `source` (-1: every source) is deinterlaced as a stream's first (dsv1_batch_deinterlace_reset)"""
+        _chk(self.L.dsv1_batch_deinterlace_reset(self.h, source), "dsv1_batch_deinterlace_reset")
 
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
@@ -612,6 +648,33 @@ def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None):
     return res
 
 
+def deinterlace_clip(clip, w, h, fmt, di, prev=None, device=0, n=None, out=None):
+    """deinterlace packed planar 8-bit frames of one stream on the GPU (dsv1_deinterlace_clip) as Deint di says: clip numpy uint8
+    [frames][frame_bytes] and prev one frame or None (host), or device pointers with n frames and `out` a device pointer for the
+    result.  Host input returns numpy uint8 [frames or 2 x frames][frame_bytes]."""
+    L = lib()
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_deinterlace_clip(device, clip, w, h, fmt, n, prev, out, _C.byref(di), 1), "dsv1_deinterlace_clip")
+        return out
+    a = _np.ascontiguousarray(clip, dtype=_np.uint8).reshape(-1)
+    if a.size % fb or not a.size:
+        raise ValueError("a clip is a whole number of %d-byte frames, got %d bytes" % (fb, a.size))
+    frames = a.size // fb
+    nout = L.dsv1_deint_out_frames(_C.byref(di), frames)
+    if nout < 0:
+        raise ValueError("not a deinterlacer: mode %d, tff %d" % (di.mode, di.tff))
+    p = None
+    if prev is not None:
+        p = _np.ascontiguousarray(prev, dtype=_np.uint8).reshape(-1)
+        if p.size != fb:
+            raise ValueError("prev is one frame of %d bytes, got %d" % (fb, p.size))
+    res = _np.zeros((nout, fb), dtype=_np.uint8)
+    _chk(L.dsv1_deinterlace_clip(device, a.ctypes.data, w, h, fmt, frames, p.ctypes.data if p is not None else None, res.ctypes.data,
+                                 _C.byref(di), 0), "dsv1_deinterlace_clip")
+    return res
+
+
 def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=None):
     """packed planar 8-bit frames (w x h at subsampling fmt) to frames of PixFormat pf at subsampling out_subsamp (None: fmt) on the
     GPU (dsv1_export_clip), chroma halved on the way where out_subsamp asks for it: clip numpy uint8 [frames][frame_bytes] (host), or
@@ -818,10 +881,23 @@ class ResLadder:
 
     def _input(self, yuv):
         a = _np.ascontiguousarray(yuv, dtype=_np.uint8)
-        if a.size != self.nsources * self.F * self.frame_bytes:
+        fin = self.in_frames
+        if a.size != self.nsources * fin * self.frame_bytes:
             raise ValueError("a resolution ladder call is %d sources x %d frames x %d bytes, got %d bytes" % (
-                self.nsources, self.F, self.frame_bytes, a.size))
+                self.nsources, fin, self.frame_bytes, a.size))
         return a
+
+    in_frames = Batch.in_frames
+
+    def set_deinterlace(self, di):
+        """the sources are interlaced: deinterlace them on the GPU as Deint di says, behind the conversion and in front of the scales
+        (dsv1_resladder_set_deinterlace); None switches it off.  Between calls only; contract as Batch.set_source_deinterlace."""
+        _chk(self.L.dsv1_resladder_set_deinterlace(self.h, _C.byref(di) if di is not None else None), "dsv1_resladder_set_deinterlace")
+        self._deint_field = di is not None and di.mode == DEINT_FIELD
+
+    def deinterlace_reset(self, source=-1):
+        """a discontinuity in `source` (-1: every source): dsv1_resladder_deinterlace_reset"""
+        _chk(self.L.dsv1_resladder_deinterlace_reset(self.h, source), "dsv1_resladder_deinterlace_reset")
 
     def _form(self, on_device, held):
         return (2 if held else 1) if on_device else 0

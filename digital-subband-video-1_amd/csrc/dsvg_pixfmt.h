@@ -81,6 +81,29 @@ int  dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv1_rgb_layo
 /* the pass itself, on a stream of the caller's: nframes RGB frames of layout *L -> tightly packed planar frames (device pointers) */
 int  dsvg_rgb_import_run(void *stream, const dsv1_rgb_layout *L, const void *src_dev, int nframes, void *dst_dev);
 
+
+/* ---- deinterlacing (include/dsv1_api.h, Deinterlacing; k_deint.hip; host side: host/dsv1_deint.c) ----
+ * A deinterlacer of one (geometry, subsampling, mode, field order) for nsrc sources: a stream, an event and two upload buffers of
+ * its own (a session with a converter runs the converter's pass on this stream: dsvg_pixconv_run_on), the buffers it allocated, and
+ * -- with_history -- each source's last input frame, which is the next call's prv.  _run deinterlaces a call's clip ([source][nin
+ * frames] -> [source][nin or 2 nin pictures]) on its own stream and records the event; _run_on on a stream of the caller's (the
+ * resolution ladder's scaler); _order makes a context's frame-load stream wait, on the device, for everything recorded so far;
+ * _reset forgets one source's history (-1: all).  _clip is the standalone pass with an explicit prev and no history. */
+int  dsv1_deint_valid(const dsv1_deint *di);            /* 1: mode and tff are ones include/dsv1_api.h knows */
+typedef struct dsvg_deint dsvg_deint;
+int  dsvg_deint_create(dsvg_deint **out, int device, int w, int h, int subsamp, const dsv1_deint *di, int nsrc, int with_history);
+void dsvg_deint_destroy(dsvg_deint *d);
+int  dsvg_deint_alloc(dsvg_deint *d, void **dptr, size_t bytes);
+int  dsvg_deint_upload(dsvg_deint *d, int buf, const void *host, size_t bytes, void **dptr);
+void *dsvg_deint_stream(dsvg_deint *d);
+int  dsvg_deint_run(dsvg_deint *d, const void *src_dev, int nin, void *dst_dev);
+int  dsvg_deint_run_on(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev);
+int  dsvg_deint_clip(dsvg_deint *d, const void *src_dev, int n, const void *prev_dev, void *dst_dev);
+int  dsvg_deint_reset(dsvg_deint *d, int source);
+int  dsvg_deint_order(dsvg_deint *d, dsvg_ctx *ctx);
+int  dsvg_deint_sync(dsvg_deint *d);
+int  dsvg_deint_download(dsvg_deint *d, void *host, const void *dptr, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

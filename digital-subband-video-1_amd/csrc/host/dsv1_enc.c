@@ -117,6 +117,12 @@ struct dsv1_batch {
     dsvg_pixconv *pc;
     size_t pc_raw_fb;
     void *pc_clip[2];
+    /* deinterlacing (dsv1_batch_set_source_deinterlace): dd == NULL: off.  With it on, a call's upload, conversion (the converter's
+     * pass, where one is set, into pc_clip, which nothing else uses then) and deinterlacing run on the deinterlacer's stream; dd_clip is the deinterlaced clip of a
+     * call parity, read as a held clip until that batch's collect */
+    dsvg_deint *dd;
+    dsv1_deint dd_set;
+    void *dd_clip[2];
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -193,6 +199,7 @@ void dsv1_batch_close(dsv1_batch *b)
     if (b->holds_recycler) dsv1_recycle_hold(-1);       /* the last batch out gives the parked packet buffers back */
     if (b->ctx) dsvg_ctx_destroy(b->ctx);
     dsvg_pixconv_destroy(b->pc);                        /* (after the context, whose kernels read the converted clips) */
+    dsvg_deint_destroy(b->dd);
     if (b->own_enc && b->enc) {
         int s;
         for (s = 0; s < b->nstreams; s++) {
@@ -1252,7 +1259,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && b->pc) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format is set"); return DSVG_ERR_ARG; }
+    if (b && (b->pc || b->dd)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format or a deinterlacer is set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1302,17 +1309,70 @@ int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
     return DSVG_OK;
 }
 
-/* a clip of the batch's source format -> the converted clip of the next submit's parity (device memory the batch owns, read as a held
- * clip until that batch's collect); the context's frame-load stream waits for the conversion on the device */
+/* deinterlacing: the setter, and one source's discontinuity */
+int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
+{
+    const DSV_META *m;
+    dsvg_deint *dd = NULL;
+    void *clip[2] = {NULL, NULL};
+    int rc = DSVG_OK, k;
+    if (!b) return DSVG_ERR_ARG;
+    if (di && !dsv1_deint_valid(di)) { dsv1_log(1, "dsv1_batch_set_source_deinterlace: mode %d / tff %d is not a deinterlacer", di->mode, di->tff); return DSVG_ERR_ARG; }
+    if (di && di->mode == DSV1_DEINT_FIELD && (b->F & 1)) {
+        dsv1_log(1, "dsv1_batch_set_source_deinterlace: field rate needs an even frames_per_call (%d)", b->F);
+        return DSVG_ERR_ARG;
+    }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_deinterlace with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (di) {
+        m = &b->enc[0].vidmeta;
+        if ((rc = dsvg_deint_create(&dd, b->device, m->width, m->height, m->subsamp, di, b->nsrc, 1))) return rc;
+        for (k = 0; k < 2 && !rc; k++) rc = dsvg_deint_alloc(dd, &clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
+        if (rc) { dsvg_deint_destroy(dd); return rc; }
+    }
+    /* nothing in flight: every batch that read a deinterlaced clip has been collected */
+    dsvg_deint_destroy(b->dd);
+    b->dd = dd;
+    memset(&b->dd_set, 0, sizeof(b->dd_set));
+    if (di) b->dd_set = *di;
+    for (k = 0; k < 2; k++) b->dd_clip[k] = clip[k];
+    return DSVG_OK;
+}
+
+int dsv1_batch_deinterlace_reset(dsv1_batch *b, int source)
+{
+    if (!b || !b->dd || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_deinterlace_reset with batches in flight"); return DSVG_ERR_ARG; }
+    return dsvg_deint_reset(b->dd, source);
+}
+
+/* a clip of the batch's source format -> the converted (and, with a deinterlacer set, deinterlaced) clip of the next submit's parity
+ * (device memory the batch owns, read as a held clip until that batch's collect); the context's frame-load stream waits for the
+ * passes on the device */
 static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 {
-    const int par = b->parity, nfr = b->nsrc * b->F;
+    const int par = b->parity;
+    const int nfr = b->nsrc * (b->dd && b->dd_set.mode == DSV1_DEINT_FIELD ? b->F / 2 : b->F);
     const void *raw = *yuv;
     void *d;
     int rc;
     if (!raw) return DSVG_ERR_ARG;
     if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     if (b->pending[par]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
+    if (b->dd) {
+        if (!yuv_on_device) {
+            if ((rc = dsvg_deint_upload(b->dd, par, raw, (b->pc ? b->pc_raw_fb : b->g.frame_bytes) * (size_t)nfr, &d))) return rc;
+            raw = d;
+        }
+        if (b->pc) {                                     /* (the converted clip of this parity is free: its last reader was the deinterlacer, on this stream) */
+            if ((rc = dsvg_pixconv_run_on(b->pc, dsvg_deint_stream(b->dd), raw, nfr, b->pc_clip[par]))) return rc;
+            raw = b->pc_clip[par];
+        }
+        if ((rc = dsvg_deint_run(b->dd, raw, nfr / b->nsrc, b->dd_clip[par]))) return rc;
+        if ((rc = dsvg_deint_order(b->dd, b->ctx))) return rc;
+        if (yuv_on_device == 1 && (rc = dsvg_deint_sync(b->dd))) return rc;
+        *yuv = b->dd_clip[par];
+        return DSVG_OK;
+    }
     if (!yuv_on_device) {
         if ((rc = dsvg_pixconv_upload(b->pc, par, raw, b->pc_raw_fb * (size_t)nfr, &d))) return rc;
         raw = d;
@@ -1327,7 +1387,7 @@ static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 
 int dsv1_batch_submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
-    if (b && b->pc) {
+    if (b && (b->pc || b->dd)) {
         int rc;
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
         return batch_submit_impl(b, yuv, 1, out, 0, 1);
@@ -1410,7 +1470,7 @@ int dsv1_batch_encode(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF
     int rc;
     if (!b || !out) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_encode with batches in flight"); return DSVG_ERR_ARG; }
-    if (b->pc) {
+    if (b->pc || b->dd) {
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
         yuv_on_device = 1;
     }

@@ -141,7 +141,7 @@ int dsv1_resample_clip(int device, const void *src, int sw, int sh, int subsamp,
 
 /* ---- resolution ladders ------------------------------------------------------------------------------------------------- */
 struct dsv1_resladder {
-    int ngeom, nsrc, F, ntot;
+    int ngeom, nsrc, F, ntot, device, subsamp;
     int w[DSV1_MAX_GEOMS], h[DSV1_MAX_GEOMS], nr[DSV1_MAX_GEOMS], off[DSV1_MAX_GEOMS + 1];
     int same[DSV1_MAX_GEOMS];           /* geometry of the source's size: fed the source itself, no scale */
     size_t sfb, gfb[DSV1_MAX_GEOMS];
@@ -165,6 +165,11 @@ struct dsv1_resladder {
     dsvg_pixconv *pc;
     size_t raw_fb;
     void *conv[2];
+    /* deinterlacing (dsv1_resladder_set_deinterlace): its pass runs on the scaler's stream behind the conversion; dclip is the
+     * deinterlaced clip of a call parity, which stands for the source from there on; dd == NULL: off */
+    dsvg_deint *dd;
+    dsv1_deint dd_set;
+    void *dclip[2];
 };
 
 void dsv1_resladder_close(dsv1_resladder *r)
@@ -174,6 +179,7 @@ void dsv1_resladder_close(dsv1_resladder *r)
     for (g = 0; g < r->ngeom; g++) dsv1_batch_close(r->lad[g]);
     dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated; it waits for its stream) */
     dsvg_pixconv_destroy(r->pc);
+    dsvg_deint_destroy(r->dd);
     free(r->tmp); free(r->sse); free(r->ssim); free(r->xsse); free(r->xssim);
     free(r);
 }
@@ -257,7 +263,7 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     r = (dsv1_resladder *)calloc(1, sizeof(*r));
     if (!r) return DSVG_ERR_NOMEM;
     r->ngeom = ngeoms; r->nsrc = nsources; r->F = frames_per_call; r->ntot = ntot;
-    r->sw = src->width; r->sh = src->height;
+    r->sw = src->width; r->sh = src->height; r->device = device; r->subsamp = src->subsamp;
     r->sfb = frame_bytes_of(src->width, src->height, src->subsamp);
     r->tmp = (DSV_BUF *)calloc((size_t)nsources * maxr, sizeof(DSV_BUF));
     r->sse = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
@@ -335,7 +341,8 @@ static void view_out(dsv1_resladder *r, int g, DSV_BUF *out)
 int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
     const uint8_t *dsrc = (const uint8_t *)yuv;
-    const int nfr = r ? r->nsrc * r->F : 0, plain_dev = yuv_on_device == 1;
+    /* nfr: the frames that come in; with a field-rate deinterlacer half of the pictures coded */
+    const int nfr = r ? r->nsrc * (r->dd && r->dd_set.mode == DSV1_DEINT_FIELD ? r->F / 2 : r->F) : 0, plain_dev = yuv_on_device == 1;
     int g, rc, par;
     if (!r || !yuv || !out || yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     par = r->parity;
@@ -363,7 +370,7 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         r->up_bytes += bytes;
         r->up_calls++;
         dsrc = (const uint8_t *)d;
-    } else if (yuv_on_device == 1 && (r->xsse_on || r->xssim_on)) {
+    } else if (yuv_on_device == 1 && (r->xsse_on || r->xssim_on) && !r->dd) {
         /* the source-resolution figures read the source until collect, and a plain device clip is the caller's again when submit
          * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip (held) */
         void *d;
@@ -371,12 +378,19 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         dsrc = (const uint8_t *)d;
         yuv_on_device = DSV1_CLIP_HELD;
     }
+    if (r->dd) {
+        /* the deinterlaced clip, in the resladder's memory until collect, is the source of everything below (a plain device clip:
+         * the sync at the end waits for the pass that read it) */
+        if ((rc = dsvg_scaler_deint(r->sc, r->dd, dsrc, nfr / r->nsrc, r->dclip[par]))) return rc;
+        dsrc = (const uint8_t *)r->dclip[par];
+        yuv_on_device = DSV1_CLIP_HELD;
+    }
     for (g = 0; g < r->ngeom; g++) {
         const void *clip = dsrc;
         int form = yuv_on_device ? yuv_on_device : DSV1_CLIP_HELD;
         if ((r->xsse_on || r->xssim_on) && (rc = dsv1_batch_xres_source(r->lad[g], dsrc))) return rc;
         if (!r->same[g]) {
-            if ((rc = dsvg_scaler_run(r->sc, r->scale_idx[g], dsrc, nfr, r->clip[g][par]))) return rc;
+            if ((rc = dsvg_scaler_run(r->sc, r->scale_idx[g], dsrc, r->nsrc * r->F, r->clip[g][par]))) return rc;
             clip = r->clip[g][par];
             form = DSV1_CLIP_HELD;
         }
@@ -391,6 +405,39 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
     r->pending[par] = 1;
     r->parity ^= 1;
     return DSVG_OK;
+}
+
+int dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di)
+{
+    dsvg_deint *dd = NULL;
+    void *clip[2] = {NULL, NULL};
+    int rc = DSVG_OK, k;
+    if (!r) return DSVG_ERR_ARG;
+    if (di && !dsv1_deint_valid(di)) { dsv1_log(1, "dsv1_resladder_set_deinterlace: mode %d / tff %d is not a deinterlacer", di->mode, di->tff); return DSVG_ERR_ARG; }
+    if (di && di->mode == DSV1_DEINT_FIELD && (r->F & 1)) {
+        dsv1_log(1, "dsv1_resladder_set_deinterlace: field rate needs an even frames_per_call (%d)", r->F);
+        return DSVG_ERR_ARG;
+    }
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_deinterlace with calls in flight"); return DSVG_ERR_ARG; }
+    if (di) {
+        if ((rc = dsvg_deint_create(&dd, r->device, r->sw, r->sh, r->subsamp, di, r->nsrc, 1))) return rc;
+        for (k = 0; k < 2 && !rc; k++) rc = dsvg_deint_alloc(dd, &clip[k], r->sfb * (size_t)r->nsrc * (size_t)r->F);
+        if (rc) { dsvg_deint_destroy(dd); return rc; }
+    }
+    if ((rc = dsvg_scaler_sync(r->sc))) { dsvg_deint_destroy(dd); return rc; }      /* (the old one's pass ran on the scaler's stream) */
+    dsvg_deint_destroy(r->dd);
+    r->dd = dd;
+    memset(&r->dd_set, 0, sizeof(r->dd_set));
+    if (di) r->dd_set = *di;
+    r->dclip[0] = clip[0]; r->dclip[1] = clip[1];
+    return DSVG_OK;
+}
+
+int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)
+{
+    if (!r || !r->dd || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_deinterlace_reset with calls in flight"); return DSVG_ERR_ARG; }
+    return dsvg_deint_reset(r->dd, source);
 }
 
 int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)

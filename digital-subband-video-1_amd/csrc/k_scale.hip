@@ -343,6 +343,18 @@ extern "C" int dsvg_scaler_convert(dsvg_scaler *s, dsvg_pixconv *pc, const void 
     return DSVG_OK;
 }
 
+// the deinterlacer's pass (k_deint.hip) on the scaler's stream, behind the conversion and in front of the scales
+struct dsvg_deint;
+extern "C" int dsvg_deint_run_on(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev);
+extern "C" int dsvg_scaler_deint(dsvg_scaler *s, dsvg_deint *dd, const void *src_dev, int nin, void *dst_dev)
+{
+    if (!s || !dd) { dsvg_set_error("bad scaler deinterlace arguments"); return DSVG_ERR_ARG; }
+    const int rc = dsvg_deint_run_on(dd, (void *)s->st, src_dev, nin, dst_dev);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(s->ev, s->st));
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx)
 {
     if (!s || !ctx) return DSVG_ERR_ARG;

@@ -516,6 +516,53 @@ int  dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const ds
  * replace each other; NULL switches back to packed planar. */
 int  dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf);
 
+/* ---- extension: deinterlacing (csrc/k_deint.hip; stated in numpy in tests/_deint.py) ----
+ * DSV1 has no interlaced coding tools; an interlaced source (1080i, 576i, 480i) is deinterlaced in front of the encoder: motion-
+ * adaptive, edge-directed, in exact integers.  Input and output are the tightly packed planar 8-bit frames every other entry point
+ * reads.  Each plane is treated on its own at its own dimensions W x H (the chroma planes of 4:2:0 alternate fields line by line
+ * like luma).  Line y of a plane belongs to field y & 1 (0 = top); tff (0 / 1) says which field of a frame is earlier in time; the
+ * first field's parity is p = tff ? 0 : 1.  cur is frame t of a stream, prv frame t - 1 of the same stream, or absent.
+ * An output picture keeps the lines of one parity q and makes the others.  DSV1_DEINT_FRAME (n frames in, n out): output t keeps
+ * q = p.  DSV1_DEINT_FIELD (n in, 2n out): output 2t keeps q = p (first-field output), output 2t + 1 keeps q = 1 - p (second-field
+ * output).  A plane with H == 1 is copied to every output.  Otherwise, for every x:
+ *   kept line ((y & 1) == q): out[y][x] = cur[y][x].
+ *   made line: up = y - 1 >= 0 ? y - 1 : y + 1; dn = y + 1 <= H - 1 ? y + 1 : y - 1; cx(i) = clamp(i, 0, W - 1);
+ *     c[i] = cur[up][cx(i)], e[i] = cur[dn][cx(i)].
+ *   spatial value, j = -2 .. 2: S(j) = sum over k = -1, 0, 1 of |c[x + k + j] - e[x + k - j]|, P(j) = (c[x + j] + e[x - j]) >> 1.
+ *     best = S(0) - 1, sp = P(0).  If S(-1) < best: best = S(-1), sp = P(-1), and only then, if S(-2) < best: S(-2) / P(-2).  Then,
+ *     against the best reached so far: if S(1) < best: S(1) / P(1), and only then, if S(2) < best: S(2) / P(2).
+ *   temporal value and motion bound.  First-field output: A = prv[y][x], B = cur[y][x], tp = (A + B) >> 1, td0 = |A - B| >> 1.
+ *     Second-field output: tp = cur[y][x], td0 = |cur[y][x] - prv[y][x]| >> 1.  Both: td1 = (|prv[up][x] - c[x]| + |prv[dn][x] -
+ *     e[x]|) >> 1, d = max(td0, td1).  prv absent: tp = cur[y][x], d = 255 (the result is sp).
+ *   out[y][x] = min(max(sp, tp - d), tp + d).
+ * A picture needs its own frame and the one before it; nothing looks ahead, so the result of a stream does not depend on how it is
+ * cut into calls, and a static stream is woven exactly (d = 0) from its second frame on.
+ * SESSIONS.  The deinterlacer runs on the device behind the source converter or the RGB import when one is set (and with neither),
+ * in front of the frame load and, in a resolution ladder, in front of the scales, with no host synchronisation of its own.  Clip
+ * ownership is dsv1_batch_set_source_format's: a plain device clip is the caller's again when submit returns, a DSV1_CLIP_HELD clip
+ * stays unchanged until collect, dsv1_batch_stage is refused while set.  The deinterlaced clip lives in session-owned buffers per call
+ * parity and goes on as a held clip; the session keeps each source's last input frame (after conversion) as the next call's prv.
+ * Setting, changing or clearing the mode forgets the history of every source, _reset that of one source (-1: every source) -- a
+ * discontinuity; both only with nothing in flight (DSVG_ERR_ARG otherwise; _reset with no deinterlacer set too).  frames_per_call
+ * counts coded pictures: in FIELD mode a call takes frames_per_call / 2 input frames per source, and an odd frames_per_call is
+ * DSVG_ERR_ARG at the setter.  The frame rate in vidmeta is the caller's statement.  In a resolution ladder the deinterlaced clip
+ * stands for the source everywhere: the scales, a geometry of the source's size, get_src_sse / get_src_ssim.  An invalid mode or tff
+ * is DSVG_ERR_ARG before any device work and leaves the setting as it was.
+ * Not offered: the drop-in dsv_enc, inverse telecine, field order detection, any lookahead. */
+#define DSV1_DEINT_FRAME 0
+#define DSV1_DEINT_FIELD 1
+typedef struct { int mode; int tff; } dsv1_deint;
+int  dsv1_deint_out_frames(const dsv1_deint *di, int n);      /* n or 2n; DSVG_ERR_ARG for an invalid *di or n < 0; host only */
+/* n frames of one stream -> dsv1_deint_out_frames(di, n) pictures.  prev: one frame that precedes src[0], or NULL for none.  Host or
+ * device memory (on_device: all three pointers are device pointers); any w, h >= 1 and every subsampling the library knows;
+ * synchronous; nothing outside the frames is read or written. */
+int  dsv1_deinterlace_clip(int device, const void *src, int w, int h, int subsamp, int n, const void *prev, void *dst,
+                           const dsv1_deint *di, int on_device);
+int  dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di);          /* NULL = off; batches, ladders, chain mode */
+int  dsv1_batch_deinterlace_reset(dsv1_batch *b, int source);                         /* -1 = every source */
+int  dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di);
+int  dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source);
+
 #ifdef __cplusplus
 }
 #endif
