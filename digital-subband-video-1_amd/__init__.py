@@ -97,6 +97,15 @@ class Deint(_C.Structure):
         super().__init__(mode, tff)
 
 
+class Denoise(_C.Structure):
+    """dsv1_denoise: the temporal noise filter's strengths, luma for plane 0 and chroma for planes 1 and 2, each 0 .. 512 and not both
+    0; a plane with strength 0 is copied.  include/dsv1_api.h, Temporal noise reduction, has the definition."""
+    _fields_ = [("luma", _C.c_int), ("chroma", _C.c_int)]
+
+    def __init__(self, luma=24, chroma=24):
+        super().__init__(luma, chroma)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -220,6 +229,14 @@ def lib():
         L.dsv1_batch_deinterlace_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsv1_resladder_set_deinterlace.argtypes = [_C.c_void_p, _C.POINTER(Deint)]
         L.dsv1_resladder_deinterlace_reset.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_denoise_state_bytes.argtypes = [_C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_denoise_state_bytes.restype = _C.c_size_t
+        L.dsv1_denoise_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_void_p,
+                                        _C.POINTER(Denoise), _C.c_int]
+        L.dsv1_batch_set_source_denoise.argtypes = [_C.c_void_p, _C.POINTER(Denoise)]
+        L.dsv1_batch_denoise_reset.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_set_denoise.argtypes = [_C.c_void_p, _C.POINTER(Denoise)]
+        L.dsv1_resladder_denoise_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         _lib = L
@@ -357,6 +374,16 @@ class Batch:
     def deinterlace_reset(self, source=-1):
         """a discontinuity: the next frame of `source` (-1: every source) is deinterlaced as a stream's first (dsv1_batch_deinterlace_reset)"""
         _chk(self.L.dsv1_batch_deinterlace_reset(self.h, source), "dsv1_batch_deinterlace_reset")
+
+    def set_source_denoise(self, dn):
+        """from the next submit on the clips pass the temporal noise filter on the GPU as Denoise dn says, behind the source format's
+        conversion and the deinterlacer (dsv1_batch_set_source_denoise); None switches it off.  Between batches only; forgets every
+        source's filter state."""
+        _chk(self.L.dsv1_batch_set_source_denoise(self.h, _C.byref(dn) if dn is not None else None), "dsv1_batch_set_source_denoise")
+
+    def denoise_reset(self, source=-1):
+        """a discontinuity: the next picture of `source` (-1: every source) is filtered as a stream's first (dsv1_batch_denoise_reset)"""
+        _chk(self.L.dsv1_batch_denoise_reset(self.h, source), "dsv1_batch_denoise_reset")
 
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
@@ -675,6 +702,31 @@ def deinterlace_clip(clip, w, h, fmt, di, prev=None, device=0, n=None, out=None)
     return res
 
 
+def denoise_clip(clip, w, h, fmt, dn, state=None, device=0, n=None, out=None, state_out=None):
+    """temporal noise reduction of packed planar 8-bit pictures of one stream on the GPU (dsv1_denoise_clip) as Denoise dn says: clip
+    numpy uint8 [pictures][frame_bytes] and state what the call before returned or None (host), which returns (numpy uint8
+    [pictures][frame_bytes], state numpy uint8 [3 x frame_bytes]); or device pointers with n pictures, `out` a device pointer for the
+    result and state / state_out device pointers or None, which returns out."""
+    L = lib()
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_denoise_clip(device, clip, w, h, fmt, n, state, state_out, out, _C.byref(dn), 1), "dsv1_denoise_clip")
+        return out
+    a = _np.ascontiguousarray(clip, dtype=_np.uint8).reshape(-1)
+    if a.size % fb or not a.size:
+        raise ValueError("a clip is a whole number of %d-byte frames, got %d bytes" % (fb, a.size))
+    p = None
+    if state is not None:
+        p = _np.ascontiguousarray(state, dtype=_np.uint8).reshape(-1)
+        if p.size != 3 * fb:
+            raise ValueError("a state is %d bytes, got %d" % (3 * fb, p.size))
+    res = _np.zeros((a.size // fb, fb), dtype=_np.uint8)
+    new = _np.zeros(3 * fb, dtype=_np.uint8)
+    _chk(L.dsv1_denoise_clip(device, a.ctypes.data, w, h, fmt, a.size // fb, p.ctypes.data if p is not None else None, new.ctypes.data,
+                             res.ctypes.data, _C.byref(dn), 0), "dsv1_denoise_clip")
+    return res, new
+
+
 def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=None):
     """packed planar 8-bit frames (w x h at subsampling fmt) to frames of PixFormat pf at subsampling out_subsamp (None: fmt) on the
     GPU (dsv1_export_clip), chroma halved on the way where out_subsamp asks for it: clip numpy uint8 [frames][frame_bytes] (host), or
@@ -898,6 +950,15 @@ class ResLadder:
     def deinterlace_reset(self, source=-1):
         """a discontinuity in `source` (-1: every source): dsv1_resladder_deinterlace_reset"""
         _chk(self.L.dsv1_resladder_deinterlace_reset(self.h, source), "dsv1_resladder_deinterlace_reset")
+
+    def set_denoise(self, dn):
+        """the sources pass the temporal noise filter on the GPU as Denoise dn says, behind the conversion and the deinterlacer and in
+        front of the scales (dsv1_resladder_set_denoise); None switches it off.  Between calls only; contract as Batch.set_source_denoise."""
+        _chk(self.L.dsv1_resladder_set_denoise(self.h, _C.byref(dn) if dn is not None else None), "dsv1_resladder_set_denoise")
+
+    def denoise_reset(self, source=-1):
+        """a discontinuity in `source` (-1: every source): dsv1_resladder_denoise_reset"""
+        _chk(self.L.dsv1_resladder_denoise_reset(self.h, source), "dsv1_resladder_denoise_reset")
 
     def _form(self, on_device, held):
         return (2 if held else 1) if on_device else 0

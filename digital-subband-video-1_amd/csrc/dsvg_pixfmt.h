@@ -104,6 +104,29 @@ int  dsvg_deint_order(dsvg_deint *d, dsvg_ctx *ctx);
 int  dsvg_deint_sync(dsvg_deint *d);
 int  dsvg_deint_download(dsvg_deint *d, void *host, const void *dptr, size_t bytes);
 
+/* ---- temporal noise reduction (include/dsv1_api.h, Temporal noise reduction; k_denoise.hip; host side: host/dsv1_denoise.c) ----
+ * A noise filter of one (geometry, subsampling, strengths) for nsrc sources: a stream, an event and two upload buffers of its own (a
+ * session runs the converter's and the deinterlacer's passes on this stream: dsvg_pixconv_run_on, dsvg_deint_run_on), the buffers it
+ * allocated, and -- with_state -- each source's state in device memory: pin, the last input picture (two buffers, read from one and
+ * written to the other), and S.  _run filters a call's clip ([source][n pictures] -> the same) on its own stream and records the
+ * event; _run_on on a stream of the caller's (the resolution ladder's scaler); _order makes a context's frame-load stream wait, on the
+ * device, for everything recorded so far; _reset forgets one source's state (-1: all).  _clip is the standalone pass with explicit
+ * states (3 frames' bytes each, device memory, either may be NULL, they may be the same) and none kept. */
+int  dsv1_denoise_valid(const dsv1_denoise *dn);        /* 1: both strengths in 0 .. 512 and not both 0 */
+typedef struct dsvg_denoise dsvg_denoise;
+int  dsvg_denoise_create(dsvg_denoise **out, int device, int w, int h, int subsamp, const dsv1_denoise *dn, int nsrc, int with_state);
+void dsvg_denoise_destroy(dsvg_denoise *d);
+int  dsvg_denoise_alloc(dsvg_denoise *d, void **dptr, size_t bytes);
+int  dsvg_denoise_upload(dsvg_denoise *d, int buf, const void *host, size_t bytes, void **dptr);
+void *dsvg_denoise_stream(dsvg_denoise *d);
+int  dsvg_denoise_run(dsvg_denoise *d, const void *src_dev, int n, void *dst_dev);
+int  dsvg_denoise_run_on(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev);
+int  dsvg_denoise_clip(dsvg_denoise *d, const void *src_dev, int n, const void *state_in_dev, void *state_out_dev, void *dst_dev);
+int  dsvg_denoise_reset(dsvg_denoise *d, int source);
+int  dsvg_denoise_order(dsvg_denoise *d, dsvg_ctx *ctx);
+int  dsvg_denoise_sync(dsvg_denoise *d);
+int  dsvg_denoise_download(dsvg_denoise *d, void *host, const void *dptr, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,12 @@ struct dsv1_batch {
     dsvg_deint *dd;
     dsv1_deint dd_set;
     void *dd_clip[2];
+    /* temporal noise reduction (dsv1_batch_set_source_denoise): dn == NULL: off.  With it on, a call's upload, the conversion and the
+     * deinterlacing (where set, into pc_clip / dd_clip, which nothing else reads then) and the filter run on the filter's stream;
+     * dn_clip is the filtered clip of a call parity, read as a held clip until that batch's collect */
+    dsvg_denoise *dn;
+    dsv1_denoise dn_set;
+    void *dn_clip[2];
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -200,6 +206,7 @@ void dsv1_batch_close(dsv1_batch *b)
     if (b->ctx) dsvg_ctx_destroy(b->ctx);
     dsvg_pixconv_destroy(b->pc);                        /* (after the context, whose kernels read the converted clips) */
     dsvg_deint_destroy(b->dd);
+    dsvg_denoise_destroy(b->dn);
     if (b->own_enc && b->enc) {
         int s;
         for (s = 0; s < b->nstreams; s++) {
@@ -1259,7 +1266,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && (b->pc || b->dd)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format or a deinterlacer is set"); return DSVG_ERR_ARG; }
+    if (b && (b->pc || b->dd || b->dn)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer or a noise filter is set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1335,6 +1342,7 @@ int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
     memset(&b->dd_set, 0, sizeof(b->dd_set));
     if (di) b->dd_set = *di;
     for (k = 0; k < 2; k++) b->dd_clip[k] = clip[k];
+    if (b->dn) return dsvg_denoise_reset(b->dn, -1);    /* the pictures the noise filter sees change meaning */
     return DSVG_OK;
 }
 
@@ -1343,6 +1351,41 @@ int dsv1_batch_deinterlace_reset(dsv1_batch *b, int source)
     if (!b || !b->dd || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_deinterlace_reset with batches in flight"); return DSVG_ERR_ARG; }
     return dsvg_deint_reset(b->dd, source);
+}
+
+/* temporal noise reduction: the setter, and one source's discontinuity */
+int dsv1_batch_set_source_denoise(dsv1_batch *b, const dsv1_denoise *dn)
+{
+    const DSV_META *m;
+    dsvg_denoise *nd = NULL;
+    void *clip[2] = {NULL, NULL};
+    int rc = DSVG_OK, k;
+    if (!b) return DSVG_ERR_ARG;
+    if (dn && !dsv1_denoise_valid(dn)) { dsv1_log(1, "dsv1_batch_set_source_denoise: luma %d / chroma %d is not a noise filter", dn->luma, dn->chroma); return DSVG_ERR_ARG; }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_denoise with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (dn) {
+        m = &b->enc[0].vidmeta;
+        if ((rc = dsvg_denoise_create(&nd, b->device, m->width, m->height, m->subsamp, dn, b->nsrc, 1))) return rc;
+        for (k = 0; k < 2 && !rc; k++) rc = dsvg_denoise_alloc(nd, &clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
+        if (rc) { dsvg_denoise_destroy(nd); return rc; }
+    }
+    /* nothing in flight: every batch that read a filtered clip has been collected; the passes in front of the filter move to the
+     * new filter's stream (or back to their own), so theirs run dry first */
+    if (b->dd && (rc = dsvg_deint_sync(b->dd))) { dsvg_denoise_destroy(nd); return rc; }
+    if (b->pc && (rc = dsvg_pixconv_sync(b->pc))) { dsvg_denoise_destroy(nd); return rc; }
+    dsvg_denoise_destroy(b->dn);                        /* (waits for its stream) */
+    b->dn = nd;
+    memset(&b->dn_set, 0, sizeof(b->dn_set));
+    if (dn) b->dn_set = *dn;
+    for (k = 0; k < 2; k++) b->dn_clip[k] = clip[k];
+    return DSVG_OK;
+}
+
+int dsv1_batch_denoise_reset(dsv1_batch *b, int source)
+{
+    if (!b || !b->dn || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_denoise_reset with batches in flight"); return DSVG_ERR_ARG; }
+    return dsvg_denoise_reset(b->dn, source);
 }
 
 /* a clip of the batch's source format -> the converted (and, with a deinterlacer set, deinterlaced) clip of the next submit's parity
@@ -1358,6 +1401,28 @@ static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
     if (!raw) return DSVG_ERR_ARG;
     if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     if (b->pending[par]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
+    if (b->dn) {
+        /* everything on the noise filter's stream: upload, conversion, deinterlacing, the filter (the clips of this parity are free:
+         * their last readers ran on this stream, or were collected before the filter was set) */
+        void *st = dsvg_denoise_stream(b->dn);
+        if (!yuv_on_device) {
+            if ((rc = dsvg_denoise_upload(b->dn, par, raw, (b->pc ? b->pc_raw_fb : b->g.frame_bytes) * (size_t)nfr, &d))) return rc;
+            raw = d;
+        }
+        if (b->pc) {
+            if ((rc = dsvg_pixconv_run_on(b->pc, st, raw, nfr, b->pc_clip[par]))) return rc;
+            raw = b->pc_clip[par];
+        }
+        if (b->dd) {
+            if ((rc = dsvg_deint_run_on(b->dd, st, raw, nfr / b->nsrc, b->dd_clip[par]))) return rc;
+            raw = b->dd_clip[par];
+        }
+        if ((rc = dsvg_denoise_run(b->dn, raw, b->F, b->dn_clip[par]))) return rc;
+        if ((rc = dsvg_denoise_order(b->dn, b->ctx))) return rc;
+        if (yuv_on_device == 1 && (rc = dsvg_denoise_sync(b->dn))) return rc;
+        *yuv = b->dn_clip[par];
+        return DSVG_OK;
+    }
     if (b->dd) {
         if (!yuv_on_device) {
             if ((rc = dsvg_deint_upload(b->dd, par, raw, (b->pc ? b->pc_raw_fb : b->g.frame_bytes) * (size_t)nfr, &d))) return rc;
@@ -1387,7 +1452,7 @@ static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 
 int dsv1_batch_submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
-    if (b && (b->pc || b->dd)) {
+    if (b && (b->pc || b->dd || b->dn)) {
         int rc;
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
         return batch_submit_impl(b, yuv, 1, out, 0, 1);
@@ -1470,7 +1535,7 @@ int dsv1_batch_encode(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF
     int rc;
     if (!b || !out) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_encode with batches in flight"); return DSVG_ERR_ARG; }
-    if (b->pc || b->dd) {
+    if (b->pc || b->dd || b->dn) {
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
         yuv_on_device = 1;
     }

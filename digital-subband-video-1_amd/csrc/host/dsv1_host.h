@@ -126,6 +126,7 @@ int  dsvg_scaler_copy_in(dsvg_scaler *s, int buf, const void *dev, size_t bytes,
 /* a source of another pixel format: converted on the scaler's stream (in front of the scales that read dst_dev) */
 int  dsvg_scaler_convert(dsvg_scaler *s, dsvg_pixconv *pc, const void *src_dev, int nframes, void *dst_dev);
 int  dsvg_scaler_deint(dsvg_scaler *s, dsvg_deint *dd, const void *src_dev, int nin, void *dst_dev);     /* the same for the deinterlacer's pass */
+int  dsvg_scaler_denoise(dsvg_scaler *s, dsvg_denoise *dn, const void *src_dev, int n, void *dst_dev);            /* and for the noise filter's */
 /* dsv1_enc.c: source-resolution figures of a batch (dsvg_ctx_xres_enable; resolution ladders): stream k = s * R + r, frame t of a
  * call is measured against frame s * frames_per_call + t of the reference clip named for the next submit (device memory, kept until
  * that batch's collect); the figures of the batch collected last, [(k * F + t) * 3 + p].  Enable only between batches. */

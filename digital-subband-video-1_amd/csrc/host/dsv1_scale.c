@@ -170,6 +170,11 @@ struct dsv1_resladder {
     dsvg_deint *dd;
     dsv1_deint dd_set;
     void *dclip[2];
+    /* temporal noise reduction (dsv1_resladder_set_denoise): its pass runs on the scaler's stream behind the deinterlacer; nclip is the
+     * filtered clip of a call parity, which stands for the source from there on; dn == NULL: off */
+    dsvg_denoise *dn;
+    dsv1_denoise dn_set;
+    void *nclip[2];
 };
 
 void dsv1_resladder_close(dsv1_resladder *r)
@@ -180,6 +185,7 @@ void dsv1_resladder_close(dsv1_resladder *r)
     dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated; it waits for its stream) */
     dsvg_pixconv_destroy(r->pc);
     dsvg_deint_destroy(r->dd);
+    dsvg_denoise_destroy(r->dn);
     free(r->tmp); free(r->sse); free(r->ssim); free(r->xsse); free(r->xssim);
     free(r);
 }
@@ -370,7 +376,7 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         r->up_bytes += bytes;
         r->up_calls++;
         dsrc = (const uint8_t *)d;
-    } else if (yuv_on_device == 1 && (r->xsse_on || r->xssim_on) && !r->dd) {
+    } else if (yuv_on_device == 1 && (r->xsse_on || r->xssim_on) && !r->dd && !r->dn) {
         /* the source-resolution figures read the source until collect, and a plain device clip is the caller's again when submit
          * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip (held) */
         void *d;
@@ -383,6 +389,11 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
          * the sync at the end waits for the pass that read it) */
         if ((rc = dsvg_scaler_deint(r->sc, r->dd, dsrc, nfr / r->nsrc, r->dclip[par]))) return rc;
         dsrc = (const uint8_t *)r->dclip[par];
+        yuv_on_device = DSV1_CLIP_HELD;
+    }
+    if (r->dn) {                                        /* the same for the filtered clip */
+        if ((rc = dsvg_scaler_denoise(r->sc, r->dn, dsrc, r->F, r->nclip[par]))) return rc;
+        dsrc = (const uint8_t *)r->nclip[par];
         yuv_on_device = DSV1_CLIP_HELD;
     }
     for (g = 0; g < r->ngeom; g++) {
@@ -430,6 +441,7 @@ int dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di)
     memset(&r->dd_set, 0, sizeof(r->dd_set));
     if (di) r->dd_set = *di;
     r->dclip[0] = clip[0]; r->dclip[1] = clip[1];
+    if (r->dn) return dsvg_denoise_reset(r->dn, -1);    /* the pictures the noise filter sees change meaning */
     return DSVG_OK;
 }
 
@@ -438,6 +450,35 @@ int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)
     if (!r || !r->dd || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_deinterlace_reset with calls in flight"); return DSVG_ERR_ARG; }
     return dsvg_deint_reset(r->dd, source);
+}
+
+int dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn)
+{
+    dsvg_denoise *nd = NULL;
+    void *clip[2] = {NULL, NULL};
+    int rc = DSVG_OK, k;
+    if (!r) return DSVG_ERR_ARG;
+    if (dn && !dsv1_denoise_valid(dn)) { dsv1_log(1, "dsv1_resladder_set_denoise: luma %d / chroma %d is not a noise filter", dn->luma, dn->chroma); return DSVG_ERR_ARG; }
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_denoise with calls in flight"); return DSVG_ERR_ARG; }
+    if (dn) {
+        if ((rc = dsvg_denoise_create(&nd, r->device, r->sw, r->sh, r->subsamp, dn, r->nsrc, 1))) return rc;
+        for (k = 0; k < 2 && !rc; k++) rc = dsvg_denoise_alloc(nd, &clip[k], r->sfb * (size_t)r->nsrc * (size_t)r->F);
+        if (rc) { dsvg_denoise_destroy(nd); return rc; }
+    }
+    if ((rc = dsvg_scaler_sync(r->sc))) { dsvg_denoise_destroy(nd); return rc; }    /* (the old one's pass ran on the scaler's stream) */
+    dsvg_denoise_destroy(r->dn);
+    r->dn = nd;
+    memset(&r->dn_set, 0, sizeof(r->dn_set));
+    if (dn) r->dn_set = *dn;
+    r->nclip[0] = clip[0]; r->nclip[1] = clip[1];
+    return DSVG_OK;
+}
+
+int dsv1_resladder_denoise_reset(dsv1_resladder *r, int source)
+{
+    if (!r || !r->dn || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_denoise_reset with calls in flight"); return DSVG_ERR_ARG; }
+    return dsvg_denoise_reset(r->dn, source);
 }
 
 int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)

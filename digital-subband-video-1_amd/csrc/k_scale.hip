@@ -355,6 +355,18 @@ extern "C" int dsvg_scaler_deint(dsvg_scaler *s, dsvg_deint *dd, const void *src
     return DSVG_OK;
 }
 
+// the noise filter's pass (k_denoise.hip) on the scaler's stream, behind the deinterlacer and in front of the scales
+struct dsvg_denoise;
+extern "C" int dsvg_denoise_run_on(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev);
+extern "C" int dsvg_scaler_denoise(dsvg_scaler *s, dsvg_denoise *dn, const void *src_dev, int n, void *dst_dev)
+{
+    if (!s || !dn) { dsvg_set_error("bad scaler noise filter arguments"); return DSVG_ERR_ARG; }
+    const int rc = dsvg_denoise_run_on(dn, (void *)s->st, src_dev, n, dst_dev);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(s->ev, s->st));
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx)
 {
     if (!s || !ctx) return DSVG_ERR_ARG;

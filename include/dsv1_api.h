@@ -563,6 +563,54 @@ int  dsv1_batch_deinterlace_reset(dsv1_batch *b, int source);                   
 int  dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di);
 int  dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source);
 
+/* ---- extension: temporal noise reduction (csrc/k_denoise.hip; stated in numpy in tests/_denoise.py) ----
+ * Camera and film noise is uncorrelated from picture to picture: motion compensation cannot predict it and every P picture codes it
+ * again.  This is a motion-adaptive, recursive temporal filter in exact integers in front of the encoder: causal, no lookahead.  Input
+ * and output are the tightly packed planar 8-bit frames every other entry point reads, n pictures in and n out.  Every plane is treated
+ * on its own at its own dimensions W x H; the strength T is `luma` for plane 0 and `chroma` for planes 1 and 2; a plane with T == 0 is
+ * copied and keeps no state.  Per plane and stream the filter carries from picture to picture pin, the previous INPUT picture of the
+ * plane (uint8), and S, the filter state (uint16: the filtered value times 16, always within 0 .. 4080).  For picture t, with
+ * c = cur[y][x], for every sample:
+ *   first picture of a stream (no history): S' = 16 c.
+ *   otherwise: cl(a, y, x) = a[clamp(y, 0, H - 1)][clamp(x, 0, W - 1)];
+ *     m0   = sum over dy, dx in {-1, 0, 1} of |cl(cur, y + dy, x + dx) - cl(pin, y + dy, x + dx)|      (3x3 SAD of the inputs)
+ *     pout = (S + 8) >> 4
+ *     m    = max(m0, 3 |c - pout|)
+ *     k    = 4 if m <= T;  16 if m >= 2 T;  4 + (12 (m - T) + T / 2) / T otherwise      (integer division, both operands >= 0; 4 .. 16)
+ *     S'   = S + (((16 c - S) k + 8) >> 4)                                               (arithmetic shift: floor)
+ *   out = (S' + 8) >> 4;  pin' = cur;  S <- S'.
+ * Consequences: a noiseless static stream passes through unchanged (m = 0, S = 16 c stays); a sample in motion (m >= 2 T) is the input
+ * sample and its state restarts from it (k = 16: S' = 16 c); S never leaves 0 .. 4080 (S' lies between S and 16 c); nothing looks
+ * ahead and the state is all a picture needs of the past, so the result of a stream does not depend on how it is cut into calls.
+ * A stream's STATE is 3 * frame_bytes bytes: pin in the frame's layout, then S in the frame's layout as little-endian uint16; the
+ * state of a plane with T == 0 is written as zeros and ignored when read.
+ * SESSIONS.  The filter runs on the device behind the source converter or the RGB import and behind the deinterlacer when those are
+ * set (and with none of them) -- in DSV1_DEINT_FIELD mode it filters the 2n deinterlaced pictures --, in front of the frame load and,
+ * in a resolution ladder, in front of the scales, with no host synchronisation of its own.  Clip ownership is
+ * dsv1_batch_set_source_format's: a plain device clip is the caller's again when submit returns, a DSV1_CLIP_HELD clip stays unchanged
+ * until collect, dsv1_batch_stage is refused while set.  The filtered clip lives in session-owned buffers per call parity and goes on
+ * as a held clip; the session keeps each source's state (pin of the last picture the filter saw, and S).  Setting, changing or clearing
+ * the filter forgets the state of every source, and so does setting, changing or clearing the deinterlacer underneath it (the pictures
+ * change meaning); _reset forgets that of one source (-1: every source) -- a discontinuity: its next picture is a first picture.  The
+ * setters and _reset only with nothing in flight (DSVG_ERR_ARG otherwise; _reset with no filter set too).  An invalid dsv1_denoise is
+ * DSVG_ERR_ARG before any device work and leaves the setting as it was.  In a resolution ladder the filtered clip stands for the
+ * source everywhere: the scales, a geometry of the source's size, get_src_sse / get_src_ssim.
+ * Not offered: the drop-in dsv_enc, spatial filtering (a 3x3 threshold-average stage was tried and lost PSNR), motion-compensated
+ * filtering, noise-level estimation, any lookahead. */
+#define DSV1_DENOISE_MAX 512
+typedef struct { int luma; int chroma; } dsv1_denoise;      /* each 0 .. DSV1_DENOISE_MAX; both 0, or anything outside: DSVG_ERR_ARG */
+size_t dsv1_denoise_state_bytes(int w, int h, int subsamp);  /* 3 * frame_bytes; 0 for w, h < 1 or an unknown subsampling; host only */
+/* n pictures of one stream -> n pictures.  state_in: the state the call before left, or NULL: the stream starts here.  state_out: receives
+ * the state the clip leaves, or NULL: discarded; it may be state_in.  Host or device memory (on_device: all four pointers are device
+ * pointers); dst must not overlap src; any w, h >= 1 and every subsampling the library knows; synchronous; nothing outside the frames
+ * and the states is read or written. */
+int  dsv1_denoise_clip(int device, const void *src, int w, int h, int subsamp, int n, const void *state_in, void *state_out, void *dst,
+                       const dsv1_denoise *dn, int on_device);
+int  dsv1_batch_set_source_denoise(dsv1_batch *b, const dsv1_denoise *dn);            /* NULL = off; batches, ladders, chain mode */
+int  dsv1_batch_denoise_reset(dsv1_batch *b, int source);                             /* -1 = every source */
+int  dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn);
+int  dsv1_resladder_denoise_reset(dsv1_resladder *r, int source);
+
 #ifdef __cplusplus
 }
 #endif
