@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the converter (k_pixfmt.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_denoise.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -39,19 +39,32 @@ int dsv1_pix_is_default(const dsv1_pix_format *pf, int w, int h, int subsamp);  
  * 4:4:4 or 4:2:2 -> 4:2:0. */
 int dsv1_pixout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, int out_subsamp, dsvg_pixout *F);
 
-/* A converter of one (geometry, subsampling, format): a stream and an event of its own, two raw upload buffers (per call parity),
- * the clips it allocated.  _run converts on its own stream and records the event; _run_on on a stream of the caller's (the resolution
- * ladder's scaler); _order makes a context's frame-load stream wait, on the device, for everything run so far. */
+/* ---- the lane: where a session's source-side work is enqueued (dsvg_lane.hip) ----
+ * One non-blocking stream, one event, two raw upload buffers (per call parity, grown on demand) and the device memory handed out.
+ * The passes below own none of that: they take the stream to launch on.  _upload / _copy_in put host / device bytes into upload
+ * buffer `buf` on the stream, behind the pass that read it last; _download is the copy and the wait; _order records everything
+ * enqueued so far and makes a context's frame-load stream wait for it, on the device; _free waits for the stream and gives one
+ * allocation back; _destroy waits for the stream and frees everything. */
+typedef struct dsvg_lane dsvg_lane;
+int  dsvg_lane_create(dsvg_lane **out, int device);
+void dsvg_lane_destroy(dsvg_lane *l);
+int  dsvg_lane_alloc(dsvg_lane *l, void **dptr, size_t bytes);
+int  dsvg_lane_free(dsvg_lane *l, void *dptr);
+int  dsvg_lane_upload(dsvg_lane *l, int buf, const void *host, size_t bytes, void **dptr);
+int  dsvg_lane_copy_in(dsvg_lane *l, int buf, const void *dev, size_t bytes, void **dptr);
+int  dsvg_lane_download(dsvg_lane *l, void *host, const void *dptr, size_t bytes);
+int  dsvg_lane_order(dsvg_lane *l, dsvg_ctx *ctx);
+int  dsvg_lane_sync(dsvg_lane *l);
+void *dsvg_lane_stream(dsvg_lane *l);
+
+/* The passes: parameters, their own device state, per-source validity.  _run enqueues on `stream` and returns.  _destroy frees memory
+ * the pass's kernels may still read: the caller waits for the lane they ran on first (dsvg_lane_sync). */
+
+/* A converter of one (geometry, subsampling, format): nframes source frames -> tightly packed planar frames (device pointers). */
 typedef struct dsvg_pixconv dsvg_pixconv;
 int  dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pix_layout *L);
 void dsvg_pixconv_destroy(dsvg_pixconv *c);
-int  dsvg_pixconv_upload(dsvg_pixconv *c, int buf, const void *host, size_t bytes, void **dptr);
-int  dsvg_pixconv_alloc(dsvg_pixconv *c, void **dptr, size_t bytes);
-int  dsvg_pixconv_run(dsvg_pixconv *c, const void *src_dev, int nframes, void *dst_dev);
-int  dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev);
-int  dsvg_pixconv_order(dsvg_pixconv *c, dsvg_ctx *ctx);
-int  dsvg_pixconv_sync(dsvg_pixconv *c);
-int  dsvg_pixconv_download(dsvg_pixconv *c, void *host, const void *dptr, size_t bytes);
+int  dsvg_pixconv_run(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev);
 
 
 /* ---- RGB (include/dsv1_api.h, RGB; k_rgb.hip; host side: host/dsv1_rgb.c) ----
@@ -75,57 +88,36 @@ typedef struct {
 int dsv1_rgb_layout_of(const dsv1_rgb_format *rf, int w, int h, int subsamp, dsv1_rgb_layout *L);
 /* the output pass's view of it: frames decoded at `subsamp` -> RGB frames */
 int dsv1_rgbout_of(const dsv1_rgb_format *rf, int w, int h, int subsamp, dsvg_pixout *F);
-/* a dsvg_pixconv whose pass is the RGB import (k_rgb.hip) instead of a re-packing: everything else -- streams, upload buffers, _run,
- * _run_on, _order -- is the converter's */
+/* a dsvg_pixconv whose pass is the RGB import (k_rgb.hip) instead of a re-packing */
 int  dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv1_rgb_layout *L);
 /* the pass itself, on a stream of the caller's: nframes RGB frames of layout *L -> tightly packed planar frames (device pointers) */
 int  dsvg_rgb_import_run(void *stream, const dsv1_rgb_layout *L, const void *src_dev, int nframes, void *dst_dev);
 
 
 /* ---- deinterlacing (include/dsv1_api.h, Deinterlacing; k_deint.hip; host side: host/dsv1_deint.c) ----
- * A deinterlacer of one (geometry, subsampling, mode, field order) for nsrc sources: a stream, an event and two upload buffers of
- * its own (a session with a converter runs the converter's pass on this stream: dsvg_pixconv_run_on), the buffers it allocated, and
- * -- with_history -- each source's last input frame, which is the next call's prv.  _run deinterlaces a call's clip ([source][nin
- * frames] -> [source][nin or 2 nin pictures]) on its own stream and records the event; _run_on on a stream of the caller's (the
- * resolution ladder's scaler); _order makes a context's frame-load stream wait, on the device, for everything recorded so far;
+ * A deinterlacer of one (geometry, subsampling, mode, field order) for nsrc sources and -- with_history -- each source's last input
+ * frame, which is the next call's prv.  _run deinterlaces a call's clip ([source][nin frames] -> [source][nin or 2 nin pictures]);
  * _reset forgets one source's history (-1: all).  _clip is the standalone pass with an explicit prev and no history. */
 int  dsv1_deint_valid(const dsv1_deint *di);            /* 1: mode and tff are ones include/dsv1_api.h knows */
 typedef struct dsvg_deint dsvg_deint;
 int  dsvg_deint_create(dsvg_deint **out, int device, int w, int h, int subsamp, const dsv1_deint *di, int nsrc, int with_history);
 void dsvg_deint_destroy(dsvg_deint *d);
-int  dsvg_deint_alloc(dsvg_deint *d, void **dptr, size_t bytes);
-int  dsvg_deint_upload(dsvg_deint *d, int buf, const void *host, size_t bytes, void **dptr);
-void *dsvg_deint_stream(dsvg_deint *d);
-int  dsvg_deint_run(dsvg_deint *d, const void *src_dev, int nin, void *dst_dev);
-int  dsvg_deint_run_on(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev);
-int  dsvg_deint_clip(dsvg_deint *d, const void *src_dev, int n, const void *prev_dev, void *dst_dev);
+int  dsvg_deint_run(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev);
+int  dsvg_deint_clip(dsvg_deint *d, void *stream, const void *src_dev, int n, const void *prev_dev, void *dst_dev);
 int  dsvg_deint_reset(dsvg_deint *d, int source);
-int  dsvg_deint_order(dsvg_deint *d, dsvg_ctx *ctx);
-int  dsvg_deint_sync(dsvg_deint *d);
-int  dsvg_deint_download(dsvg_deint *d, void *host, const void *dptr, size_t bytes);
 
 /* ---- temporal noise reduction (include/dsv1_api.h, Temporal noise reduction; k_denoise.hip; host side: host/dsv1_denoise.c) ----
- * A noise filter of one (geometry, subsampling, strengths) for nsrc sources: a stream, an event and two upload buffers of its own (a
- * session runs the converter's and the deinterlacer's passes on this stream: dsvg_pixconv_run_on, dsvg_deint_run_on), the buffers it
- * allocated, and -- with_state -- each source's state in device memory: pin, the last input picture (two buffers, read from one and
- * written to the other), and S.  _run filters a call's clip ([source][n pictures] -> the same) on its own stream and records the
- * event; _run_on on a stream of the caller's (the resolution ladder's scaler); _order makes a context's frame-load stream wait, on the
- * device, for everything recorded so far; _reset forgets one source's state (-1: all).  _clip is the standalone pass with explicit
- * states (3 frames' bytes each, device memory, either may be NULL, they may be the same) and none kept. */
+ * A noise filter of one (geometry, subsampling, strengths) for nsrc sources and -- with_state -- each source's state in device memory:
+ * pin, the last input picture (two buffers, read from one and written to the other), and S.  _run filters a call's clip ([source][n
+ * pictures] -> the same); _reset forgets one source's state (-1: all).  _clip is the standalone pass with explicit states (3 frames'
+ * bytes each, device memory, either may be NULL, they may be the same) and none kept. */
 int  dsv1_denoise_valid(const dsv1_denoise *dn);        /* 1: both strengths in 0 .. 512 and not both 0 */
 typedef struct dsvg_denoise dsvg_denoise;
 int  dsvg_denoise_create(dsvg_denoise **out, int device, int w, int h, int subsamp, const dsv1_denoise *dn, int nsrc, int with_state);
 void dsvg_denoise_destroy(dsvg_denoise *d);
-int  dsvg_denoise_alloc(dsvg_denoise *d, void **dptr, size_t bytes);
-int  dsvg_denoise_upload(dsvg_denoise *d, int buf, const void *host, size_t bytes, void **dptr);
-void *dsvg_denoise_stream(dsvg_denoise *d);
-int  dsvg_denoise_run(dsvg_denoise *d, const void *src_dev, int n, void *dst_dev);
-int  dsvg_denoise_run_on(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev);
-int  dsvg_denoise_clip(dsvg_denoise *d, const void *src_dev, int n, const void *state_in_dev, void *state_out_dev, void *dst_dev);
+int  dsvg_denoise_run(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev);
+int  dsvg_denoise_clip(dsvg_denoise *d, void *stream, const void *src_dev, int n, const void *state_in_dev, void *state_out_dev, void *dst_dev);
 int  dsvg_denoise_reset(dsvg_denoise *d, int source);
-int  dsvg_denoise_order(dsvg_denoise *d, dsvg_ctx *ctx);
-int  dsvg_denoise_sync(dsvg_denoise *d);
-int  dsvg_denoise_download(dsvg_denoise *d, void *host, const void *dptr, size_t bytes);
 
 #ifdef __cplusplus
 }

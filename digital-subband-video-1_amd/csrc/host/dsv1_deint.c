@@ -18,24 +18,17 @@ int dsv1_deinterlace_clip(int device, const void *src, int w, int h, int subsamp
                           int on_device)
 {
     dsvg_deint *d = NULL;
-    void *dsrc = NULL, *dprev = NULL, *ddst = NULL;
     size_t fb;
-    int rc, nout, hs, vs;
+    int rc, nout;
     if (!src || !dst || n < 1 || device < 0 || w < 1 || h < 1) return DSVG_ERR_ARG;
     if (subsamp != DSV_SUBSAMP_444 && subsamp != DSV_SUBSAMP_422 && subsamp != DSV_SUBSAMP_420 && subsamp != DSV_SUBSAMP_411) return DSVG_ERR_ARG;
     if ((nout = dsv1_deint_out_frames(di, n)) < 0) return DSVG_ERR_ARG;
-    hs = (subsamp >> 2) & 3; vs = subsamp & 3;
-    fb = (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
+    fb = dsv1_frame_bytes(w, h, subsamp);
     if ((rc = dsvg_deint_create(&d, device, w, h, subsamp, di, 1, 0))) return rc;
-    if (on_device) rc = dsvg_deint_clip(d, src, n, prev, dst);
-    else {
-        rc = dsvg_deint_upload(d, 0, src, fb * (size_t)n, &dsrc);
-        if (!rc && prev) rc = dsvg_deint_upload(d, 1, prev, fb, &dprev);
-        if (!rc) rc = dsvg_deint_alloc(d, &ddst, fb * (size_t)nout);
-        if (!rc) rc = dsvg_deint_clip(d, dsrc, n, dprev, ddst);
-        if (!rc) rc = dsvg_deint_download(d, dst, ddst, fb * (size_t)nout);
+    {
+        const dsv1_clip_io io = {{src, prev}, {fb * (size_t)n, fb}, {dst, NULL}, {fb * (size_t)nout, 0}};
+        rc = dsv1_pass_clip(device, DSV1_SRC_DEINTERLACE, d, n, &io, on_device);
     }
-    if (!rc) rc = dsvg_deint_sync(d);
-    dsvg_deint_destroy(d);                              /* (frees ddst: the deinterlacer owns what it allocated) */
+    dsvg_deint_destroy(d);
     return rc;
 }

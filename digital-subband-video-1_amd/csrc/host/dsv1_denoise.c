@@ -13,39 +13,25 @@ static int subsamp_known(int subsamp)
     return subsamp == DSV_SUBSAMP_444 || subsamp == DSV_SUBSAMP_422 || subsamp == DSV_SUBSAMP_420 || subsamp == DSV_SUBSAMP_411;
 }
 
-static size_t frame_bytes(int w, int h, int subsamp)
-{
-    const int hs = (subsamp >> 2) & 3, vs = subsamp & 3;
-    return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
-}
-
 size_t dsv1_denoise_state_bytes(int w, int h, int subsamp)
 {
     if (w < 1 || h < 1 || !subsamp_known(subsamp)) return 0;
-    return 3 * frame_bytes(w, h, subsamp);
+    return 3 * dsv1_frame_bytes(w, h, subsamp);
 }
 
 int dsv1_denoise_clip(int device, const void *src, int w, int h, int subsamp, int n, const void *state_in, void *state_out, void *dst,
                       const dsv1_denoise *dn, int on_device)
 {
     dsvg_denoise *d = NULL;
-    void *dsrc = NULL, *dsin = NULL, *dsout = NULL, *ddst = NULL;
     size_t fb;
     int rc;
     if (!src || !dst || n < 1 || device < 0 || w < 1 || h < 1 || !subsamp_known(subsamp) || !dsv1_denoise_valid(dn)) return DSVG_ERR_ARG;
-    fb = frame_bytes(w, h, subsamp);
+    fb = dsv1_frame_bytes(w, h, subsamp);
     if ((rc = dsvg_denoise_create(&d, device, w, h, subsamp, dn, 1, 0))) return rc;
-    if (on_device) rc = dsvg_denoise_clip(d, src, n, state_in, state_out, dst);
-    else {
-        rc = dsvg_denoise_upload(d, 0, src, fb * (size_t)n, &dsrc);
-        if (!rc && state_in) rc = dsvg_denoise_upload(d, 1, state_in, 3 * fb, &dsin);
-        if (!rc) rc = dsvg_denoise_alloc(d, &ddst, fb * (size_t)n);
-        if (!rc && state_out) rc = dsvg_denoise_alloc(d, &dsout, 3 * fb);
-        if (!rc) rc = dsvg_denoise_clip(d, dsrc, n, dsin, dsout, ddst);
-        if (!rc) rc = dsvg_denoise_download(d, dst, ddst, fb * (size_t)n);
-        if (!rc && state_out) rc = dsvg_denoise_download(d, state_out, dsout, 3 * fb);
+    {
+        const dsv1_clip_io io = {{src, state_in}, {fb * (size_t)n, 3 * fb}, {dst, state_out}, {fb * (size_t)n, 3 * fb}};
+        rc = dsv1_pass_clip(device, DSV1_SRC_DENOISE, d, n, &io, on_device);
     }
-    if (!rc) rc = dsvg_denoise_sync(d);
-    dsvg_denoise_destroy(d);                            /* (frees what the filter allocated) */
+    dsvg_denoise_destroy(d);
     return rc;
 }

@@ -111,24 +111,9 @@ struct dsv1_batch {
     uint64_t *xsse;
     int64_t *xssim;
     size_t xsse_n, xssim_n;
-    /* source pixel format (dsv1_batch_set_source_format): the converter and the converted clips, one per call parity (a batch of that
-     * parity reads its clip, as a held clip, until its collect); pc == NULL: clips are packed planar 8-bit, nothing is converted */
-    int device;
-    dsvg_pixconv *pc;
-    size_t pc_raw_fb;
-    void *pc_clip[2];
-    /* deinterlacing (dsv1_batch_set_source_deinterlace): dd == NULL: off.  With it on, a call's upload, conversion (the converter's
-     * pass, where one is set, into pc_clip, which nothing else uses then) and deinterlacing run on the deinterlacer's stream; dd_clip is the deinterlaced clip of a
-     * call parity, read as a held clip until that batch's collect */
-    dsvg_deint *dd;
-    dsv1_deint dd_set;
-    void *dd_clip[2];
-    /* temporal noise reduction (dsv1_batch_set_source_denoise): dn == NULL: off.  With it on, a call's upload, the conversion and the
-     * deinterlacing (where set, into pc_clip / dd_clip, which nothing else reads then) and the filter run on the filter's stream;
-     * dn_clip is the filtered clip of a call parity, read as a held clip until that batch's collect */
-    dsvg_denoise *dn;
-    dsv1_denoise dn_set;
-    void *dn_clip[2];
+    /* the passes in front of the encoder (dsv1_batch_set_source_format / _rgb / _deinterlace / _denoise) and the lane they run on;
+     * none set: clips are packed planar 8-bit, there is no lane and nothing is converted */
+    dsv1_srcchain src;
 };
 
 /* source slot of frame number g (per-stream counter) of stream s */
@@ -204,9 +189,7 @@ void dsv1_batch_close(dsv1_batch *b)
     if (b->bg_on[0] || b->bg_on[1]) dsv1_par_bg_end();  /* a background prefix loop still reads this batch's pictures */
     if (b->holds_recycler) dsv1_recycle_hold(-1);       /* the last batch out gives the parked packet buffers back */
     if (b->ctx) dsvg_ctx_destroy(b->ctx);
-    dsvg_pixconv_destroy(b->pc);                        /* (after the context, whose kernels read the converted clips) */
-    dsvg_deint_destroy(b->dd);
-    dsvg_denoise_destroy(b->dn);
+    dsv1_srcchain_close(&b->src);                       /* (after the context, whose kernels read the chain's clips) */
     if (b->own_enc && b->enc) {
         int s;
         for (s = 0; s < b->nstreams; s++) {
@@ -234,7 +217,7 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     b = (dsv1_batch *)b_calloc(1, sizeof(*b));
     if (!b) return DSVG_ERR_NOMEM;
     b->nstreams = nstreams; b->nsrc = nsrc; b->R = R; b->F = F; b->enc = encs; b->own_enc = own;
-    b->device = device;
+    dsv1_srcchain_init(&b->src, device, m->width, m->height, m->subsamp, nsrc, F, 0);
     if (chains > F) chains = F;
     b->chains = chains; b->carry_pair = -1; b->carry_cur = -1;
     np = nstreams * F;
@@ -1266,7 +1249,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && (b->pc || b->dd || b->dn)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer or a noise filter is set"); return DSVG_ERR_ARG; }
+    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer or a noise filter is set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1274,7 +1257,6 @@ int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
 {
     dsv1_pix_layout L;
     const DSV_META *m;
-    int rc, k;
     if (!b) return DSVG_ERR_ARG;
     m = &b->enc[0].vidmeta;
     if (pf && dsv1_pix_layout_of(pf, m->width, m->height, m->subsamp, &L)) {
@@ -1282,23 +1264,15 @@ int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_format with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    /* nothing in flight: every batch that read a converted clip has been collected */
-    dsvg_pixconv_destroy(b->pc);
-    b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL;
-    if (dsv1_pix_is_default(pf, m->width, m->height, m->subsamp)) return DSVG_OK;
-    if ((rc = dsvg_pixconv_create(&b->pc, b->device, &L))) return rc;
-    for (k = 0; k < 2 && !rc; k++) rc = dsvg_pixconv_alloc(b->pc, &b->pc_clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
-    if (rc) { dsvg_pixconv_destroy(b->pc); b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL; return rc; }
-    b->pc_raw_fb = L.frame_bytes;
-    return DSVG_OK;
+    /* nothing in flight: every batch that read one of the chain's clips has been collected */
+    return dsv1_srcchain_set_format(&b->src, dsv1_pix_is_default(pf, m->width, m->height, m->subsamp) ? NULL : &L, NULL);
 }
 
-/* the RGB twin: the same converter object around the RGB import pass; the two setters replace each other */
+/* the RGB twin: the RGB import pass in the converter's place; the two setters replace each other */
 int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
 {
     dsv1_rgb_layout L;
     const DSV_META *m;
-    int rc, k;
     if (!b) return DSVG_ERR_ARG;
     if (!rf) return dsv1_batch_set_source_format(b, NULL);
     m = &b->enc[0].vidmeta;
@@ -1307,22 +1281,12 @@ int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_rgb with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    dsvg_pixconv_destroy(b->pc);
-    b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL;
-    if ((rc = dsvg_pixconv_create_rgb(&b->pc, b->device, &L))) return rc;
-    for (k = 0; k < 2 && !rc; k++) rc = dsvg_pixconv_alloc(b->pc, &b->pc_clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
-    if (rc) { dsvg_pixconv_destroy(b->pc); b->pc = NULL; b->pc_clip[0] = b->pc_clip[1] = NULL; return rc; }
-    b->pc_raw_fb = L.frame_bytes;
-    return DSVG_OK;
+    return dsv1_srcchain_set_format(&b->src, NULL, &L);
 }
 
 /* deinterlacing: the setter, and one source's discontinuity */
 int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
 {
-    const DSV_META *m;
-    dsvg_deint *dd = NULL;
-    void *clip[2] = {NULL, NULL};
-    int rc = DSVG_OK, k;
     if (!b) return DSVG_ERR_ARG;
     if (di && !dsv1_deint_valid(di)) { dsv1_log(1, "dsv1_batch_set_source_deinterlace: mode %d / tff %d is not a deinterlacer", di->mode, di->tff); return DSVG_ERR_ARG; }
     if (di && di->mode == DSV1_DEINT_FIELD && (b->F & 1)) {
@@ -1330,129 +1294,50 @@ int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_deinterlace with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (di) {
-        m = &b->enc[0].vidmeta;
-        if ((rc = dsvg_deint_create(&dd, b->device, m->width, m->height, m->subsamp, di, b->nsrc, 1))) return rc;
-        for (k = 0; k < 2 && !rc; k++) rc = dsvg_deint_alloc(dd, &clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
-        if (rc) { dsvg_deint_destroy(dd); return rc; }
-    }
-    /* nothing in flight: every batch that read a deinterlaced clip has been collected */
-    dsvg_deint_destroy(b->dd);
-    b->dd = dd;
-    memset(&b->dd_set, 0, sizeof(b->dd_set));
-    if (di) b->dd_set = *di;
-    for (k = 0; k < 2; k++) b->dd_clip[k] = clip[k];
-    if (b->dn) return dsvg_denoise_reset(b->dn, -1);    /* the pictures the noise filter sees change meaning */
-    return DSVG_OK;
+    return dsv1_srcchain_set_deinterlace(&b->src, di);
 }
 
 int dsv1_batch_deinterlace_reset(dsv1_batch *b, int source)
 {
-    if (!b || !b->dd || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
+    if (!b || !b->src.dd || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_deinterlace_reset with batches in flight"); return DSVG_ERR_ARG; }
-    return dsvg_deint_reset(b->dd, source);
+    return dsv1_srcchain_deinterlace_reset(&b->src, source);
 }
 
 /* temporal noise reduction: the setter, and one source's discontinuity */
 int dsv1_batch_set_source_denoise(dsv1_batch *b, const dsv1_denoise *dn)
 {
-    const DSV_META *m;
-    dsvg_denoise *nd = NULL;
-    void *clip[2] = {NULL, NULL};
-    int rc = DSVG_OK, k;
     if (!b) return DSVG_ERR_ARG;
     if (dn && !dsv1_denoise_valid(dn)) { dsv1_log(1, "dsv1_batch_set_source_denoise: luma %d / chroma %d is not a noise filter", dn->luma, dn->chroma); return DSVG_ERR_ARG; }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_denoise with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (dn) {
-        m = &b->enc[0].vidmeta;
-        if ((rc = dsvg_denoise_create(&nd, b->device, m->width, m->height, m->subsamp, dn, b->nsrc, 1))) return rc;
-        for (k = 0; k < 2 && !rc; k++) rc = dsvg_denoise_alloc(nd, &clip[k], b->g.frame_bytes * (size_t)b->nsrc * (size_t)b->F);
-        if (rc) { dsvg_denoise_destroy(nd); return rc; }
-    }
-    /* nothing in flight: every batch that read a filtered clip has been collected; the passes in front of the filter move to the
-     * new filter's stream (or back to their own), so theirs run dry first */
-    if (b->dd && (rc = dsvg_deint_sync(b->dd))) { dsvg_denoise_destroy(nd); return rc; }
-    if (b->pc && (rc = dsvg_pixconv_sync(b->pc))) { dsvg_denoise_destroy(nd); return rc; }
-    dsvg_denoise_destroy(b->dn);                        /* (waits for its stream) */
-    b->dn = nd;
-    memset(&b->dn_set, 0, sizeof(b->dn_set));
-    if (dn) b->dn_set = *dn;
-    for (k = 0; k < 2; k++) b->dn_clip[k] = clip[k];
-    return DSVG_OK;
+    return dsv1_srcchain_set_denoise(&b->src, dn);
 }
 
 int dsv1_batch_denoise_reset(dsv1_batch *b, int source)
 {
-    if (!b || !b->dn || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
+    if (!b || !b->src.dn || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_denoise_reset with batches in flight"); return DSVG_ERR_ARG; }
-    return dsvg_denoise_reset(b->dn, source);
+    return dsv1_srcchain_denoise_reset(&b->src, source);
 }
 
-/* a clip of the batch's source format -> the converted (and, with a deinterlacer set, deinterlaced) clip of the next submit's parity
- * (device memory the batch owns, read as a held clip until that batch's collect); the context's frame-load stream waits for the
- * passes on the device */
+/* a clip of the batch's source format -> the clip the chain's passes leave for the next submit's parity (device memory the chain owns,
+ * read as a held clip until that batch's collect); the context's frame-load stream waits for the passes on the device */
 static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 {
-    const int par = b->parity;
-    const int nfr = b->nsrc * (b->dd && b->dd_set.mode == DSV1_DEINT_FIELD ? b->F / 2 : b->F);
-    const void *raw = *yuv;
-    void *d;
     int rc;
-    if (!raw) return DSVG_ERR_ARG;
+    if (!*yuv) return DSVG_ERR_ARG;
     if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
-    if (b->pending[par]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
-    if (b->dn) {
-        /* everything on the noise filter's stream: upload, conversion, deinterlacing, the filter (the clips of this parity are free:
-         * their last readers ran on this stream, or were collected before the filter was set) */
-        void *st = dsvg_denoise_stream(b->dn);
-        if (!yuv_on_device) {
-            if ((rc = dsvg_denoise_upload(b->dn, par, raw, (b->pc ? b->pc_raw_fb : b->g.frame_bytes) * (size_t)nfr, &d))) return rc;
-            raw = d;
-        }
-        if (b->pc) {
-            if ((rc = dsvg_pixconv_run_on(b->pc, st, raw, nfr, b->pc_clip[par]))) return rc;
-            raw = b->pc_clip[par];
-        }
-        if (b->dd) {
-            if ((rc = dsvg_deint_run_on(b->dd, st, raw, nfr / b->nsrc, b->dd_clip[par]))) return rc;
-            raw = b->dd_clip[par];
-        }
-        if ((rc = dsvg_denoise_run(b->dn, raw, b->F, b->dn_clip[par]))) return rc;
-        if ((rc = dsvg_denoise_order(b->dn, b->ctx))) return rc;
-        if (yuv_on_device == 1 && (rc = dsvg_denoise_sync(b->dn))) return rc;
-        *yuv = b->dn_clip[par];
-        return DSVG_OK;
-    }
-    if (b->dd) {
-        if (!yuv_on_device) {
-            if ((rc = dsvg_deint_upload(b->dd, par, raw, (b->pc ? b->pc_raw_fb : b->g.frame_bytes) * (size_t)nfr, &d))) return rc;
-            raw = d;
-        }
-        if (b->pc) {                                     /* (the converted clip of this parity is free: its last reader was the deinterlacer, on this stream) */
-            if ((rc = dsvg_pixconv_run_on(b->pc, dsvg_deint_stream(b->dd), raw, nfr, b->pc_clip[par]))) return rc;
-            raw = b->pc_clip[par];
-        }
-        if ((rc = dsvg_deint_run(b->dd, raw, nfr / b->nsrc, b->dd_clip[par]))) return rc;
-        if ((rc = dsvg_deint_order(b->dd, b->ctx))) return rc;
-        if (yuv_on_device == 1 && (rc = dsvg_deint_sync(b->dd))) return rc;
-        *yuv = b->dd_clip[par];
-        return DSVG_OK;
-    }
-    if (!yuv_on_device) {
-        if ((rc = dsvg_pixconv_upload(b->pc, par, raw, b->pc_raw_fb * (size_t)nfr, &d))) return rc;
-        raw = d;
-    }
-    if ((rc = dsvg_pixconv_run(b->pc, raw, nfr, b->pc_clip[par]))) return rc;
-    if ((rc = dsvg_pixconv_order(b->pc, b->ctx))) return rc;
+    if (b->pending[b->parity]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
+    if ((rc = dsv1_srcchain_run(&b->src, b->parity, *yuv, yuv_on_device, yuv))) return rc;
+    if ((rc = dsvg_lane_order(b->src.lane, b->ctx))) return rc;
     /* a plain device clip is the caller's again when submit returns */
-    if (yuv_on_device == 1 && (rc = dsvg_pixconv_sync(b->pc))) return rc;
-    *yuv = b->pc_clip[par];
+    if (yuv_on_device == 1 && (rc = dsvg_lane_sync(b->src.lane))) return rc;
     return DSVG_OK;
 }
 
 int dsv1_batch_submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
-    if (b && (b->pc || b->dd || b->dn)) {
+    if (b && dsv1_srcchain_any(&b->src)) {
         int rc;
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
         return batch_submit_impl(b, yuv, 1, out, 0, 1);
@@ -1535,7 +1420,7 @@ int dsv1_batch_encode(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF
     int rc;
     if (!b || !out) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_encode with batches in flight"); return DSVG_ERR_ARG; }
-    if (b->pc || b->dd || b->dn) {
+    if (dsv1_srcchain_any(&b->src)) {
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
         yuv_on_device = 1;
     }

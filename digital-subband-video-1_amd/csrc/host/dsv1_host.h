@@ -9,7 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../../include/dsv1_api.h"
-#include "../dsvg_pixfmt.h"       /* source pixel formats: the layout of a format and the device converter (k_pixfmt.hip) */
+#include "../dsvg_pixfmt.h"       /* source pixel formats: the layout of a format; the lane and the passes in front of the encoder */
 
 /* `end` bounds the READER (bits): past it every bit reads as 1 -- which ends any exp-Golomb prefix -- and `over` is set,
  * so a truncated or hostile packet can neither run the reader off its buffer nor loop; the writer ignores it */
@@ -109,24 +109,56 @@ int dsv1_ladder_rungs_agree(const DSV_ENCODER *a, const DSV_ENCODER *b);
 /* dsvg_pipe.hip: what dsvg_ctx_create would answer for the geometry, without a device (DSVG_OK, DSVG_ERR_ARG, DSVG_ERR_UNSUPPORTED) */
 int dsvg_geom_check(int width, int height, int subsamp);
 /* k_scale.hip: the device side of the resampler.  A scaler holds the weight tables of ngeom destination geometries of one source
- * geometry (uploaded once), a stream of its own and two upload buffers; _order makes a context's frame-load stream wait, on the
- * device, for everything enqueued on the scaler so far. */
+ * geometry (uploaded once); _run scales a clip to geometry g on a stream of the caller's (a lane's, dsvg_pixfmt.h).  _destroy frees the
+ * tables its kernels read: the caller waits for that lane first. */
 typedef struct dsvg_scaler dsvg_scaler;
 int  dsvg_scaler_create(dsvg_scaler **out, int device, int sw, int sh, int subsamp, int ngeom, const int *dw, const int *dh, int filter);
 void dsvg_scaler_destroy(dsvg_scaler *s);
-int  dsvg_scaler_upload(dsvg_scaler *s, int buf, const void *host, size_t bytes, void **dptr);
-int  dsvg_scaler_run(dsvg_scaler *s, int g, const void *src_dev, int nframes, void *dst_dev);
-int  dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx);
-int  dsvg_scaler_sync(dsvg_scaler *s);
-int  dsvg_scaler_alloc(dsvg_scaler *s, void **dptr, size_t bytes);
-int  dsvg_scaler_download(dsvg_scaler *s, void *host, const void *dptr, size_t bytes);
-/* device clip -> upload buffer `buf` (0 / 1) on the scaler's stream, as dsvg_scaler_upload (a resolution ladder's plain device clip
- * that must outlive its submit) */
-int  dsvg_scaler_copy_in(dsvg_scaler *s, int buf, const void *dev, size_t bytes, void **dptr);
-/* a source of another pixel format: converted on the scaler's stream (in front of the scales that read dst_dev) */
-int  dsvg_scaler_convert(dsvg_scaler *s, dsvg_pixconv *pc, const void *src_dev, int nframes, void *dst_dev);
-int  dsvg_scaler_deint(dsvg_scaler *s, dsvg_deint *dd, const void *src_dev, int nin, void *dst_dev);     /* the same for the deinterlacer's pass */
-int  dsvg_scaler_denoise(dsvg_scaler *s, dsvg_denoise *dn, const void *src_dev, int n, void *dst_dev);            /* and for the noise filter's */
+int  dsvg_scaler_run(dsvg_scaler *s, void *stream, int g, const void *src_dev, int nframes, void *dst_dev);
+
+/* the tightly packed planar frame */
+static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
+{
+    const int hs = (subsamp >> 2) & 3, vs = subsamp & 3;
+    return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
+}
+
+/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, deinterlacer and noise filter with their
+ * settings, and each pass's output clip per call parity (a batch of that parity reads the last one as a held clip until its collect).
+ * A chain with no pass set holds no lane -- no stream, no device memory -- unless the session keeps it (keep_lane: a resolution
+ * ladder uploads and scales on it).  The setters replace or (NULL) clear one pass; on an error the chain is as it was.  The session
+ * checks that nothing is in flight, and its arguments, before it calls one. */
+enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_SCALE };
+typedef struct {
+    int device, w, h, subsamp, nsrc, F, keep_lane;
+    size_t fb, raw_fb;                  /* the packed planar frame; the converter's source frame */
+    dsvg_lane *lane;
+    dsvg_pixconv *pc;
+    dsvg_deint *dd;
+    dsv1_deint dd_set;
+    dsvg_denoise *dn;
+    dsv1_denoise dn_set;
+    void *clip[3][2];
+} dsv1_srcchain;
+void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp, int nsrc, int F, int keep_lane);
+void dsv1_srcchain_close(dsv1_srcchain *c);            /* waits for the lane; frees everything */
+int  dsv1_srcchain_lane(dsv1_srcchain *c);             /* creates the lane where there is none yet */
+int  dsv1_srcchain_set_format(dsv1_srcchain *c, const dsv1_pix_layout *L, const dsv1_rgb_layout *R);      /* one of them, or neither: no converter */
+int  dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di);         /* (resets the noise filter's state) */
+int  dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn);
+int  dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source);                 /* DSVG_ERR_ARG where the pass is not set */
+int  dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source);
+static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->dd || c->dn; }
+int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, or F / 2 at field rate */
+size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c); /* ... and the bytes of a call's clip */
+/* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> deinterlace -> denoise are
+ * set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where nothing ran) */
+int  dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out);
+/* the standalone clip calls: one pass (DSV1_SRC_*; SCALE: a scaler's geometry 0) over n frames on a lane of the call's own.  in[0] the
+ * clip, in[1] an optional second input (the deinterlacer's prev, the filter's state_in); out[0] the result, out[1] the filter's
+ * state_out.  Host memory is uploaded / allocated / downloaded, device memory used in place; the call waits for the pass. */
+typedef struct { const void *in[2]; size_t in_bytes[2]; void *out[2]; size_t out_bytes[2]; } dsv1_clip_io;
+int  dsv1_pass_clip(int device, int kind, void *pass, int n, const dsv1_clip_io *io, int on_device);
 /* dsv1_enc.c: source-resolution figures of a batch (dsvg_ctx_xres_enable; resolution ladders): stream k = s * R + r, frame t of a
  * call is measured against frame s * frames_per_call + t of the reference clip named for the next submit (device memory, kept until
  * that batch's collect); the figures of the batch collected last, [(k * F + t) * 3 + p].  Enable only between batches. */

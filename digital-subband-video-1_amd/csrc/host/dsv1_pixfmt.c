@@ -93,21 +93,16 @@ int dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, in
 {
     dsv1_pix_layout L;
     dsvg_pixconv *pc = NULL;
-    void *dsrc = NULL, *ddst = NULL;
     int rc;
     if (!src || !dst || !pf || n < 1 || device < 0) return DSVG_ERR_ARG;
     if ((rc = dsv1_pix_layout_of(pf, w, h, subsamp, &L))) return rc;
     if ((rc = dsvg_pixconv_create(&pc, device, &L))) return rc;
-    if (on_device) rc = dsvg_pixconv_run(pc, src, n, dst);
-    else {
+    {
         /* the last frame ends with its planes: a caller's buffer need not hold the stride's padding behind them */
-        rc = dsvg_pixconv_upload(pc, 0, src, L.frame_bytes * (size_t)(n - 1) + L.planes_bytes, &dsrc);
-        if (!rc) rc = dsvg_pixconv_alloc(pc, &ddst, L.out_frame_bytes * (size_t)n);
-        if (!rc) rc = dsvg_pixconv_run(pc, dsrc, n, ddst);
-        if (!rc) rc = dsvg_pixconv_download(pc, dst, ddst, L.out_frame_bytes * (size_t)n);
+        const dsv1_clip_io io = {{src, NULL}, {L.frame_bytes * (size_t)(n - 1) + L.planes_bytes, 0}, {dst, NULL}, {L.out_frame_bytes * (size_t)n, 0}};
+        rc = dsv1_pass_clip(device, DSV1_SRC_CONVERT, pc, n, &io, on_device);
     }
-    if (!rc) rc = dsvg_pixconv_sync(pc);
-    dsvg_pixconv_destroy(pc);                           /* (frees ddst: the converter owns what it allocated) */
+    dsvg_pixconv_destroy(pc);
     return rc;
 }
 

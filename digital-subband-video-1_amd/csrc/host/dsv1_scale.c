@@ -4,15 +4,15 @@
  * below, no contraction -- the Makefile compiles this file with -ffp-contract=off (gcc does not implement the STDC FP_CONTRACT
  * pragma), and tests/test_scale_host.py checks the object for fused multiply-adds and the tables against numpy.
  *
- * A resolution ladder is one quality ladder (dsv1_ladder_open) per geometry plus a scaler (k_scale.hip).  A call uploads the source
- * clip once on the scaler's stream, scales it there for every geometry whose size differs from the source's, and makes each
- * geometry's frame-load stream wait for that on the device (dsvg_scaler_order) before the geometry's submit; the scaled clips go to
- * the ladders as held device clips (DSV1_CLIP_HELD), one buffer per geometry and call parity, which the next submit of the same
- * parity -- after that geometry's collect -- overwrites.
+ * A resolution ladder is one quality ladder (dsv1_ladder_open) per geometry plus a source chain (dsv1_srcchain.c) and a scaler
+ * (k_scale.hip).  A call uploads the source clip once on the chain's lane, scales it there for every geometry whose size differs
+ * from the source's, and makes each geometry's frame-load stream wait for that on the device (dsvg_lane_order) before the geometry's
+ * submit; the scaled clips go to the ladders as held device clips (DSV1_CLIP_HELD), one buffer per geometry and call parity, which
+ * the next submit of the same parity -- after that geometry's collect -- overwrites.
  *
- * A source of another pixel format (dsv1_resladder_open_src): the raw clip is what crosses the link; it is converted on the scaler's
- * stream, in front of the scales, into a packed planar 8-bit clip the resladder holds per call parity, and that clip stands for the
- * source from there on (scales, a geometry of the source's size, the source-resolution figures). */
+ * A source of another pixel format (dsv1_resladder_open_src), a deinterlacer, a noise filter: the raw clip is what crosses the link;
+ * the chain's passes run on the lane in front of the scales, and the clip they leave, which the chain holds per call parity, stands
+ * for the source from there on (scales, a geometry of the source's size, the source-resolution figures). */
 #include <math.h>
 #include "dsv1_host.h"
 
@@ -95,31 +95,17 @@ static int dims_ok(int (*taps)(int, int, int), int sw, int sh, int fmt, int dw, 
 static int scale_dims_ok(int sw, int sh, int fmt, int dw, int dh, int filter) { return dims_ok(dsv1_scale_taps, sw, sh, fmt, dw, dh, filter); }
 static int resample_dims_ok(int sw, int sh, int fmt, int dw, int dh, int filter) { return dims_ok(dsv1_resample_taps, sw, sh, fmt, dw, dh, filter); }
 
-static size_t frame_bytes_of(int w, int h, int fmt)
-{
-    const int hs = (fmt >> 2) & 3, vs = fmt & 3;
-    return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
-}
-
 /* the standalone clip call of both directions (the scaler's tables are dsv1_resample_weights, which are dsv1_scale_weights where
  * S >= D); the caller has checked the dims against its own limits */
 static int resample_clip_impl(int device, const void *src, int sw, int sh, int subsamp, int n, void *dst, int dw, int dh, int filter,
                               int on_device)
 {
     dsvg_scaler *sc = NULL;
-    void *dsrc = NULL, *ddst = NULL;
-    const size_t sfb = frame_bytes_of(sw, sh, subsamp), dfb = frame_bytes_of(dw, dh, subsamp);
+    const dsv1_clip_io io = {{src, NULL}, {dsv1_frame_bytes(sw, sh, subsamp) * (size_t)n, 0}, {dst, NULL}, {dsv1_frame_bytes(dw, dh, subsamp) * (size_t)n, 0}};
     int rc;
     if ((rc = dsvg_scaler_create(&sc, device, sw, sh, subsamp, 1, &dw, &dh, filter))) return rc;
-    if (on_device) rc = dsvg_scaler_run(sc, 0, src, n, dst);
-    else {
-        rc = dsvg_scaler_upload(sc, 0, src, sfb * (size_t)n, &dsrc);
-        if (!rc) rc = dsvg_scaler_alloc(sc, &ddst, dfb * (size_t)n);
-        if (!rc) rc = dsvg_scaler_run(sc, 0, dsrc, n, ddst);
-        if (!rc) rc = dsvg_scaler_download(sc, dst, ddst, dfb * (size_t)n);
-    }
-    if (!rc) rc = dsvg_scaler_sync(sc);
-    dsvg_scaler_destroy(sc);                            /* (frees ddst: the scaler owns what it allocated) */
+    rc = dsv1_pass_clip(device, DSV1_SRC_SCALE, sc, n, &io, on_device);
+    dsvg_scaler_destroy(sc);
     return rc;
 }
 
@@ -141,10 +127,10 @@ int dsv1_resample_clip(int device, const void *src, int sw, int sh, int subsamp,
 
 /* ---- resolution ladders ------------------------------------------------------------------------------------------------- */
 struct dsv1_resladder {
-    int ngeom, nsrc, F, ntot, device, subsamp;
+    int ngeom, nsrc, F, ntot;
     int w[DSV1_MAX_GEOMS], h[DSV1_MAX_GEOMS], nr[DSV1_MAX_GEOMS], off[DSV1_MAX_GEOMS + 1];
     int same[DSV1_MAX_GEOMS];           /* geometry of the source's size: fed the source itself, no scale */
-    size_t sfb, gfb[DSV1_MAX_GEOMS];
+    size_t gfb[DSV1_MAX_GEOMS];
     dsv1_batch *lad[DSV1_MAX_GEOMS];
     dsvg_scaler *sc;
     int scale_idx[DSV1_MAX_GEOMS];      /* the scaler's table of geometry g (-1: same size) */
@@ -161,20 +147,9 @@ struct dsv1_resladder {
     uint64_t *xsse;
     int64_t *xssim;
     size_t xsse_n, xssim_n;
-    /* source pixel format (dsv1_resladder_open_src): the converter and the converted clips, per call parity; pc == NULL: the default */
-    dsvg_pixconv *pc;
-    size_t raw_fb;
-    void *conv[2];
-    /* deinterlacing (dsv1_resladder_set_deinterlace): its pass runs on the scaler's stream behind the conversion; dclip is the
-     * deinterlaced clip of a call parity, which stands for the source from there on; dd == NULL: off */
-    dsvg_deint *dd;
-    dsv1_deint dd_set;
-    void *dclip[2];
-    /* temporal noise reduction (dsv1_resladder_set_denoise): its pass runs on the scaler's stream behind the deinterlacer; nclip is the
-     * filtered clip of a call parity, which stands for the source from there on; dn == NULL: off */
-    dsvg_denoise *dn;
-    dsv1_denoise dn_set;
-    void *nclip[2];
+    /* the lane everything in front of the ladders runs on (kept while the resladder lives: uploads, scales), and the passes in front
+     * of the scales: the source pixel format (dsv1_resladder_open_src), dsv1_resladder_set_deinterlace, dsv1_resladder_set_denoise */
+    dsv1_srcchain src;
 };
 
 void dsv1_resladder_close(dsv1_resladder *r)
@@ -182,10 +157,9 @@ void dsv1_resladder_close(dsv1_resladder *r)
     int g;
     if (!r) return;
     for (g = 0; g < r->ngeom; g++) dsv1_batch_close(r->lad[g]);
-    dsvg_scaler_destroy(r->sc);                         /* (and the scaled clips and upload buffers it allocated; it waits for its stream) */
-    dsvg_pixconv_destroy(r->pc);
-    dsvg_deint_destroy(r->dd);
-    dsvg_denoise_destroy(r->dn);
+    if (r->src.lane) (void)dsvg_lane_sync(r->src.lane); /* (the scales read the tables) */
+    dsvg_scaler_destroy(r->sc);
+    dsv1_srcchain_close(&r->src);                       /* (and the scaled clips and upload buffers of its lane) */
     free(r->tmp); free(r->sse); free(r->ssim); free(r->xsse); free(r->xssim);
     free(r);
 }
@@ -269,8 +243,8 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     r = (dsv1_resladder *)calloc(1, sizeof(*r));
     if (!r) return DSVG_ERR_NOMEM;
     r->ngeom = ngeoms; r->nsrc = nsources; r->F = frames_per_call; r->ntot = ntot;
-    r->sw = src->width; r->sh = src->height; r->device = device; r->subsamp = src->subsamp;
-    r->sfb = frame_bytes_of(src->width, src->height, src->subsamp);
+    r->sw = src->width; r->sh = src->height;
+    dsv1_srcchain_init(&r->src, device, src->width, src->height, src->subsamp, nsources, frames_per_call, 1);
     r->tmp = (DSV_BUF *)calloc((size_t)nsources * maxr, sizeof(DSV_BUF));
     r->sse = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
     r->ssim = (int64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(int64_t));
@@ -278,24 +252,19 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     for (g = 0; g < ngeoms; g++) {
         r->w[g] = rungs[g].width; r->h[g] = rungs[g].height; r->nr[g] = rungs[g].nrates;
         r->off[g + 1] = r->off[g] + rungs[g].nrates;
-        r->gfb[g] = frame_bytes_of(r->w[g], r->h[g], src->subsamp);
+        r->gfb[g] = dsv1_frame_bytes(r->w[g], r->h[g], src->subsamp);
         r->same[g] = r->w[g] == src->width && r->h[g] == src->height;
         r->scale_idx[g] = -1;
         if (!r->same[g]) { r->scale_idx[g] = nscaled; dw[nscaled] = r->w[g]; dh[nscaled] = r->h[g]; nscaled++; }
     }
-    /* the scaler exists even when no geometry is scaled: host input is uploaded through it */
-    if ((rc = dsvg_scaler_create(&r->sc, device, src->width, src->height, src->subsamp, nscaled, dw, dh, filter))) { dsv1_resladder_close(r); return rc; }
-    if (pf || rf) {
-        r->raw_fb = rf ? rl.frame_bytes : pl.frame_bytes;
-        if ((rc = rf ? dsvg_pixconv_create_rgb(&r->pc, device, &rl) : dsvg_pixconv_create(&r->pc, device, &pl))) { dsv1_resladder_close(r); return rc; }
-        for (k = 0; k < 2; k++)
-            if ((rc = dsvg_scaler_alloc(r->sc, &r->conv[k], r->sfb * (size_t)nsources * frames_per_call))) { dsv1_resladder_close(r); return rc; }
-    }
+    /* the lane exists even when no geometry is scaled: host input is uploaded through it */
+    if ((rc = dsvg_scaler_create(&r->sc, device, src->width, src->height, src->subsamp, nscaled, dw, dh, filter)) ||
+        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_set_format(&r->src, pf ? &pl : NULL, rf ? &rl : NULL))) { dsv1_resladder_close(r); return rc; }
     for (g = 0; g < ngeoms; g++) {
         if ((rc = dsv1_ladder_open(&r->lad[g], rungs[g].rates, rungs[g].nrates, device, nsources, frames_per_call))) break;
         r->ngeom = g + 1;
         if (!r->same[g])
-            for (k = 0; k < 2 && !rc; k++) rc = dsvg_scaler_alloc(r->sc, &r->clip[g][k], r->gfb[g] * (size_t)nsources * frames_per_call);
+            for (k = 0; k < 2 && !rc; k++) rc = dsvg_lane_alloc(r->src.lane, &r->clip[g][k], r->gfb[g] * (size_t)nsources * frames_per_call);
         if (rc) break;
     }
     if (rc) { r->ngeom = g + (g < ngeoms && r->lad[g] ? 1 : 0); dsv1_resladder_close(r); return rc; }
@@ -346,73 +315,44 @@ static void view_out(dsv1_resladder *r, int g, DSV_BUF *out)
 
 int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
-    const uint8_t *dsrc = (const uint8_t *)yuv;
-    /* nfr: the frames that come in; with a field-rate deinterlacer half of the pictures coded */
-    const int nfr = r ? r->nsrc * (r->dd && r->dd_set.mode == DSV1_DEINT_FIELD ? r->F / 2 : r->F) : 0, plain_dev = yuv_on_device == 1;
+    const void *dsrc;
+    const int plain_dev = yuv_on_device == 1;
     int g, rc, par;
     if (!r || !yuv || !out || yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     par = r->parity;
     if (r->pending[par]) { dsv1_log(1, "resolution ladder submitted twice without collect"); return DSVG_ERR_ARG; }
-    if (r->pc) {
-        /* another pixel format: the RAW clip crosses the link (host input), and the conversion, on the scaler's stream, writes the
-         * clip of this call's parity, which the resladder holds until collect and which stands for the source from here on */
-        if (!yuv_on_device) {
-            void *d;
-            const size_t bytes = r->raw_fb * (size_t)nfr;
-            if ((rc = dsvg_scaler_upload(r->sc, par, yuv, bytes, &d))) return rc;
-            r->up_bytes += bytes;
-            r->up_calls++;
-            dsrc = (const uint8_t *)d;
-        }
-        if ((rc = dsvg_scaler_convert(r->sc, r->pc, dsrc, nfr, r->conv[par]))) return rc;
-        dsrc = (const uint8_t *)r->conv[par];
-        yuv_on_device = DSV1_CLIP_HELD;                 /* (a plain device clip: the sync below waits for the conversion that read it) */
-    } else if (!yuv_on_device) {
-        /* the source crosses the link once, on the scaler's stream; its buffer (per parity) is held until this call's collect: a
-         * geometry of the source's size reads it in place */
-        void *d;
-        const size_t bytes = r->sfb * (size_t)nfr;
-        if ((rc = dsvg_scaler_upload(r->sc, par, yuv, bytes, &d))) return rc;
-        r->up_bytes += bytes;
-        r->up_calls++;
-        dsrc = (const uint8_t *)d;
-    } else if (yuv_on_device == 1 && (r->xsse_on || r->xssim_on) && !r->dd && !r->dn) {
+    if (plain_dev && (r->xsse_on || r->xssim_on) && !dsv1_srcchain_any(&r->src)) {
         /* the source-resolution figures read the source until collect, and a plain device clip is the caller's again when submit
-         * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip (held) */
+         * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip */
         void *d;
-        if ((rc = dsvg_scaler_copy_in(r->sc, par, yuv, r->sfb * (size_t)nfr, &d))) return rc;
-        dsrc = (const uint8_t *)d;
-        yuv_on_device = DSV1_CLIP_HELD;
+        if ((rc = dsvg_lane_copy_in(r->src.lane, par, yuv, dsv1_srcchain_bytes_in(&r->src), &d))) return rc;
+        dsrc = d;
+    } else {
+        /* the RAW clip crosses the link once (host input), into the lane's buffer of this call's parity, which is held until this
+         * call's collect (a geometry of the source's size reads it in place); the chain's passes write clips of this call's parity,
+         * and what they leave stands for the source from here on */
+        if ((rc = dsv1_srcchain_run(&r->src, par, yuv, yuv_on_device, &dsrc))) return rc;
+        if (!yuv_on_device) { r->up_bytes += dsv1_srcchain_bytes_in(&r->src); r->up_calls++; }
     }
-    if (r->dd) {
-        /* the deinterlaced clip, in the resladder's memory until collect, is the source of everything below (a plain device clip:
-         * the sync at the end waits for the pass that read it) */
-        if ((rc = dsvg_scaler_deint(r->sc, r->dd, dsrc, nfr / r->nsrc, r->dclip[par]))) return rc;
-        dsrc = (const uint8_t *)r->dclip[par];
-        yuv_on_device = DSV1_CLIP_HELD;
-    }
-    if (r->dn) {                                        /* the same for the filtered clip */
-        if ((rc = dsvg_scaler_denoise(r->sc, r->dn, dsrc, r->F, r->nclip[par]))) return rc;
-        dsrc = (const uint8_t *)r->nclip[par];
-        yuv_on_device = DSV1_CLIP_HELD;
-    }
+    /* the resladder's own memory is held until collect (a plain device clip: the sync at the end waits for whatever read it) */
+    if (dsrc != yuv) yuv_on_device = DSV1_CLIP_HELD;
     for (g = 0; g < r->ngeom; g++) {
         const void *clip = dsrc;
-        int form = yuv_on_device ? yuv_on_device : DSV1_CLIP_HELD;
+        int form = yuv_on_device;
         if ((r->xsse_on || r->xssim_on) && (rc = dsv1_batch_xres_source(r->lad[g], dsrc))) return rc;
         if (!r->same[g]) {
-            if ((rc = dsvg_scaler_run(r->sc, r->scale_idx[g], dsrc, r->nsrc * r->F, r->clip[g][par]))) return rc;
+            if ((rc = dsvg_scaler_run(r->sc, dsvg_lane_stream(r->src.lane), r->scale_idx[g], dsrc, r->nsrc * r->F, r->clip[g][par]))) return rc;
             clip = r->clip[g][par];
             form = DSV1_CLIP_HELD;
         }
-        if ((rc = dsvg_scaler_order(r->sc, (dsvg_ctx *)dsv1_batch_ctx(r->lad[g])))) return rc;
+        if ((rc = dsvg_lane_order(r->src.lane, (dsvg_ctx *)dsv1_batch_ctx(r->lad[g])))) return rc;
         view_in(r, g, out);
         rc = dsv1_batch_submit(r->lad[g], clip, form, r->tmp);
         view_out(r, g, out);
         if (rc) return rc;
     }
-    /* a plain device clip is the caller's again when submit returns: the scales (or the copy) that read it must have run */
-    if (plain_dev && (rc = dsvg_scaler_sync(r->sc))) return rc;
+    /* a plain device clip is the caller's again when submit returns: the passes, scales or the copy that read it must have run */
+    if (plain_dev && (rc = dsvg_lane_sync(r->src.lane))) return rc;
     r->pending[par] = 1;
     r->parity ^= 1;
     return DSVG_OK;
@@ -420,9 +360,6 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
 
 int dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di)
 {
-    dsvg_deint *dd = NULL;
-    void *clip[2] = {NULL, NULL};
-    int rc = DSVG_OK, k;
     if (!r) return DSVG_ERR_ARG;
     if (di && !dsv1_deint_valid(di)) { dsv1_log(1, "dsv1_resladder_set_deinterlace: mode %d / tff %d is not a deinterlacer", di->mode, di->tff); return DSVG_ERR_ARG; }
     if (di && di->mode == DSV1_DEINT_FIELD && (r->F & 1)) {
@@ -430,55 +367,29 @@ int dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di)
         return DSVG_ERR_ARG;
     }
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_deinterlace with calls in flight"); return DSVG_ERR_ARG; }
-    if (di) {
-        if ((rc = dsvg_deint_create(&dd, r->device, r->sw, r->sh, r->subsamp, di, r->nsrc, 1))) return rc;
-        for (k = 0; k < 2 && !rc; k++) rc = dsvg_deint_alloc(dd, &clip[k], r->sfb * (size_t)r->nsrc * (size_t)r->F);
-        if (rc) { dsvg_deint_destroy(dd); return rc; }
-    }
-    if ((rc = dsvg_scaler_sync(r->sc))) { dsvg_deint_destroy(dd); return rc; }      /* (the old one's pass ran on the scaler's stream) */
-    dsvg_deint_destroy(r->dd);
-    r->dd = dd;
-    memset(&r->dd_set, 0, sizeof(r->dd_set));
-    if (di) r->dd_set = *di;
-    r->dclip[0] = clip[0]; r->dclip[1] = clip[1];
-    if (r->dn) return dsvg_denoise_reset(r->dn, -1);    /* the pictures the noise filter sees change meaning */
-    return DSVG_OK;
+    return dsv1_srcchain_set_deinterlace(&r->src, di);
 }
 
 int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)
 {
-    if (!r || !r->dd || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
+    if (!r || !r->src.dd || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_deinterlace_reset with calls in flight"); return DSVG_ERR_ARG; }
-    return dsvg_deint_reset(r->dd, source);
+    return dsv1_srcchain_deinterlace_reset(&r->src, source);
 }
 
 int dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn)
 {
-    dsvg_denoise *nd = NULL;
-    void *clip[2] = {NULL, NULL};
-    int rc = DSVG_OK, k;
     if (!r) return DSVG_ERR_ARG;
     if (dn && !dsv1_denoise_valid(dn)) { dsv1_log(1, "dsv1_resladder_set_denoise: luma %d / chroma %d is not a noise filter", dn->luma, dn->chroma); return DSVG_ERR_ARG; }
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_denoise with calls in flight"); return DSVG_ERR_ARG; }
-    if (dn) {
-        if ((rc = dsvg_denoise_create(&nd, r->device, r->sw, r->sh, r->subsamp, dn, r->nsrc, 1))) return rc;
-        for (k = 0; k < 2 && !rc; k++) rc = dsvg_denoise_alloc(nd, &clip[k], r->sfb * (size_t)r->nsrc * (size_t)r->F);
-        if (rc) { dsvg_denoise_destroy(nd); return rc; }
-    }
-    if ((rc = dsvg_scaler_sync(r->sc))) { dsvg_denoise_destroy(nd); return rc; }    /* (the old one's pass ran on the scaler's stream) */
-    dsvg_denoise_destroy(r->dn);
-    r->dn = nd;
-    memset(&r->dn_set, 0, sizeof(r->dn_set));
-    if (dn) r->dn_set = *dn;
-    r->nclip[0] = clip[0]; r->nclip[1] = clip[1];
-    return DSVG_OK;
+    return dsv1_srcchain_set_denoise(&r->src, dn);
 }
 
 int dsv1_resladder_denoise_reset(dsv1_resladder *r, int source)
 {
-    if (!r || !r->dn || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
+    if (!r || !r->src.dn || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_denoise_reset with calls in flight"); return DSVG_ERR_ARG; }
-    return dsvg_denoise_reset(r->dn, source);
+    return dsv1_srcchain_denoise_reset(&r->src, source);
 }
 
 int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)

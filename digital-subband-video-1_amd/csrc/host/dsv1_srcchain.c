@@ -1,0 +1,152 @@
+/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace -> denoise on one lane (dsvg_pixfmt.h), for
+ * batches (dsv1_enc.c) and resolution ladders (dsv1_scale.c), and the sequence the standalone clip calls share. */
+#include "dsv1_host.h"
+
+void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp, int nsrc, int F, int keep_lane)
+{
+    memset(c, 0, sizeof(*c));
+    c->device = device; c->w = w; c->h = h; c->subsamp = subsamp; c->nsrc = nsrc; c->F = F; c->keep_lane = keep_lane;
+    c->fb = dsv1_frame_bytes(w, h, subsamp);
+}
+
+int dsv1_srcchain_lane(dsv1_srcchain *c) { return c->lane ? DSVG_OK : dsvg_lane_create(&c->lane, c->device); }
+
+/* no pass left: no lane (a session that keeps it for its own uploads and scales says so at init) */
+static void chain_release(dsv1_srcchain *c)
+{
+    if (c->keep_lane || dsv1_srcchain_any(c)) return;
+    dsvg_lane_destroy(c->lane);
+    c->lane = NULL;
+}
+
+void dsv1_srcchain_close(dsv1_srcchain *c)
+{
+    if (c->lane) (void)dsvg_lane_sync(c->lane);        /* (the passes' kernels read the memory their destroy frees) */
+    dsvg_pixconv_destroy(c->pc);
+    dsvg_deint_destroy(c->dd);
+    dsvg_denoise_destroy(c->dn);
+    dsvg_lane_destroy(c->lane);                         /* (and the clips) */
+    memset(c, 0, sizeof(*c));
+}
+
+/* pass p (NULL: none) takes slot k (DSV1_SRC_*): its two clips first, and only then does the pass set before go, with its clips.
+ * On an error the chain is as it was and p is still the caller's. */
+static int chain_install(dsv1_srcchain *c, int k, void *p)
+{
+    void *clip[2] = {NULL, NULL};
+    int rc, j;
+    if (!p && !c->clip[k][0]) return DSVG_OK;
+    rc = dsv1_srcchain_lane(c);
+    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], c->fb * (size_t)c->nsrc * (size_t)c->F);
+    if (!rc) rc = dsvg_lane_sync(c->lane);
+    if (rc) {
+        if (c->lane) for (j = 0; j < 2; j++) (void)dsvg_lane_free(c->lane, clip[j]);
+        chain_release(c);
+        return rc;
+    }
+    switch (k) {
+    case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; break;
+    case DSV1_SRC_DEINTERLACE: dsvg_deint_destroy(c->dd); c->dd = (dsvg_deint *)p; break;
+    default:                   dsvg_denoise_destroy(c->dn); c->dn = (dsvg_denoise *)p; break;
+    }
+    for (j = 0; j < 2; j++) {
+        (void)dsvg_lane_free(c->lane, c->clip[k][j]);
+        c->clip[k][j] = clip[j];
+    }
+    chain_release(c);
+    return DSVG_OK;
+}
+
+int dsv1_srcchain_set_format(dsv1_srcchain *c, const dsv1_pix_layout *L, const dsv1_rgb_layout *R)
+{
+    dsvg_pixconv *pc = NULL;
+    int rc;
+    if (L && (rc = dsvg_pixconv_create(&pc, c->device, L))) return rc;
+    if (R && (rc = dsvg_pixconv_create_rgb(&pc, c->device, R))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_CONVERT, pc))) { dsvg_pixconv_destroy(pc); return rc; }
+    c->raw_fb = L ? L->frame_bytes : R ? R->frame_bytes : 0;
+    return DSVG_OK;
+}
+
+int dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di)
+{
+    dsvg_deint *dd = NULL;
+    int rc;
+    if (di && (rc = dsvg_deint_create(&dd, c->device, c->w, c->h, c->subsamp, di, c->nsrc, 1))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_DEINTERLACE, dd))) { dsvg_deint_destroy(dd); return rc; }
+    memset(&c->dd_set, 0, sizeof(c->dd_set));
+    if (di) c->dd_set = *di;
+    return c->dn ? dsvg_denoise_reset(c->dn, -1) : DSVG_OK;     /* the pictures the noise filter sees change meaning */
+}
+
+int dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn)
+{
+    dsvg_denoise *nd = NULL;
+    int rc;
+    if (dn && (rc = dsvg_denoise_create(&nd, c->device, c->w, c->h, c->subsamp, dn, c->nsrc, 1))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_DENOISE, nd))) { dsvg_denoise_destroy(nd); return rc; }
+    memset(&c->dn_set, 0, sizeof(c->dn_set));
+    if (dn) c->dn_set = *dn;
+    return DSVG_OK;
+}
+
+int dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source) { return c->dd ? dsvg_deint_reset(c->dd, source) : DSVG_ERR_ARG; }
+int dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source) { return c->dn ? dsvg_denoise_reset(c->dn, source) : DSVG_ERR_ARG; }
+
+int dsv1_srcchain_frames_in(const dsv1_srcchain *c) { return c->dd && c->dd_set.mode == DSV1_DEINT_FIELD ? c->F / 2 : c->F; }
+size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c)
+{
+    return (c->pc ? c->raw_fb : c->fb) * (size_t)c->nsrc * (size_t)dsv1_srcchain_frames_in(c);
+}
+
+int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out)
+{
+    const int nin = dsv1_srcchain_frames_in(c);
+    void *st = dsvg_lane_stream(c->lane), *d;
+    int rc;
+    if (!c->lane || !clip || !out) return DSVG_ERR_ARG;
+    if (!on_device) {
+        if ((rc = dsvg_lane_upload(c->lane, par, clip, dsv1_srcchain_bytes_in(c), &d))) return rc;
+        clip = d;
+    }
+    if (c->pc) {
+        if ((rc = dsvg_pixconv_run(c->pc, st, clip, c->nsrc * nin, c->clip[DSV1_SRC_CONVERT][par]))) return rc;
+        clip = c->clip[DSV1_SRC_CONVERT][par];
+    }
+    if (c->dd) {
+        if ((rc = dsvg_deint_run(c->dd, st, clip, nin, c->clip[DSV1_SRC_DEINTERLACE][par]))) return rc;
+        clip = c->clip[DSV1_SRC_DEINTERLACE][par];
+    }
+    if (c->dn) {
+        if ((rc = dsvg_denoise_run(c->dn, st, clip, c->F, c->clip[DSV1_SRC_DENOISE][par]))) return rc;
+        clip = c->clip[DSV1_SRC_DENOISE][par];
+    }
+    *out = clip;
+    return DSVG_OK;
+}
+
+int dsv1_pass_clip(int device, int kind, void *pass, int n, const dsv1_clip_io *io, int on_device)
+{
+    dsvg_lane *l = NULL;
+    const void *din[2] = {io->in[0], io->in[1]};
+    void *dout[2] = {io->out[0], io->out[1]}, *st, *d;
+    int rc, k;
+    if ((rc = dsvg_lane_create(&l, device))) return rc;
+    st = dsvg_lane_stream(l);
+    for (k = 0; !on_device && k < 2 && !rc; k++) {
+        if (io->in[k] && !(rc = dsvg_lane_upload(l, k, io->in[k], io->in_bytes[k], &d))) din[k] = d;
+        if (io->out[k] && !rc) rc = dsvg_lane_alloc(l, &dout[k], io->out_bytes[k]);
+    }
+    if (!rc)
+        switch (kind) {
+        case DSV1_SRC_CONVERT:     rc = dsvg_pixconv_run((dsvg_pixconv *)pass, st, din[0], n, dout[0]); break;
+        case DSV1_SRC_DEINTERLACE: rc = dsvg_deint_clip((dsvg_deint *)pass, st, din[0], n, din[1], dout[0]); break;
+        case DSV1_SRC_DENOISE:     rc = dsvg_denoise_clip((dsvg_denoise *)pass, st, din[0], n, din[1], dout[1], dout[0]); break;
+        default:                   rc = dsvg_scaler_run((dsvg_scaler *)pass, st, 0, din[0], n, dout[0]); break;
+        }
+    for (k = 0; !on_device && k < 2 && !rc; k++)
+        if (io->out[k]) rc = dsvg_lane_download(l, io->out[k], dout[k], io->out_bytes[k]);
+    if (!rc) rc = dsvg_lane_sync(l);
+    dsvg_lane_destroy(l);                               /* (waits for the stream; frees what the call allocated) */
+    return rc;
+}

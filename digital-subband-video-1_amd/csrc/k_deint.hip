@@ -202,20 +202,13 @@ __global__ __launch_bounds__(DI_THREADS) void k_deint(const DiParams P, const ui
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-extern "C" int dsvg_ctx_load_wait(dsvg_ctx *ctx, void *event);
-
 struct dsvg_deint {
     int device = 0, mode = 0, tff = 0, nsrc = 0;
     DiParams P;
     int nblocks = 0;
     size_t fb = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev = nullptr;
-    uint8_t *up[2] = {nullptr, nullptr};
-    size_t up_bytes[2] = {0, 0};
     uint8_t *hist = nullptr;             // [nsrc] frames: each source's last input frame
     std::vector<unsigned char> valid;    // per source: hist holds one
-    std::vector<void *> owned;
 };
 
 extern "C" int dsv1_deint_valid(const dsv1_deint *di);
@@ -223,24 +216,15 @@ extern "C" int dsv1_deint_valid(const dsv1_deint *di);
 extern "C" void dsvg_deint_destroy(dsvg_deint *d)
 {
     if (!d) return;
-    if (hipSetDevice(d->device) == hipSuccess) {
-        if (d->st) (void)hipStreamSynchronize(d->st);
-        for (void *p : d->owned) (void)hipFree(p);
-        for (int k = 0; k < 2; k++) if (d->up[k]) (void)hipFree(d->up[k]);
-        if (d->hist) (void)hipFree(d->hist);
-        if (d->ev) (void)hipEventDestroy(d->ev);
-        if (d->st) (void)hipStreamDestroy(d->st);
-    }
+    if (d->hist && hipSetDevice(d->device) == hipSuccess) (void)hipFree(d->hist);
     (void)hipGetLastError();
     delete d;
 }
 
-static int deint_device_side(dsvg_deint *d, bool with_history)
+static int deint_history(dsvg_deint *d)
 {
     HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
-    if (with_history) HIPCHK(hipMalloc((void **)&d->hist, d->fb * (size_t)d->nsrc + 256));
+    HIPCHK(hipMalloc((void **)&d->hist, d->fb * (size_t)d->nsrc + 256));
     return DSVG_OK;
 }
 
@@ -272,38 +256,11 @@ extern "C" int dsvg_deint_create(dsvg_deint **out, int device, int w, int h, int
     d->P.fb = off;
     d->P.field = di->mode == DSV1_DEINT_FIELD;
     d->P.p = di->tff ? 0 : 1;
-    const int rc = deint_device_side(d, with_history != 0);
+    const int rc = with_history ? deint_history(d) : DSVG_OK;
     if (rc) { dsvg_deint_destroy(d); return rc; }
     *out = d;
     return DSVG_OK;
 }
-
-extern "C" int dsvg_deint_alloc(dsvg_deint *d, void **dptr, size_t bytes)
-{
-    if (!d || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(d->device));
-    const hipError_t e = hipMalloc(dptr, bytes + 256);
-    if (e != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; dsvg_set_error("hipMalloc of %zu bytes failed", bytes); return DSVG_ERR_HIP; }
-    d->owned.push_back(*dptr);
-    return DSVG_OK;
-}
-
-// host bytes -> upload buffer `buf` (0 / 1) on the deinterlacer's stream: behind the pass that read the buffer last
-extern "C" int dsvg_deint_upload(dsvg_deint *d, int buf, const void *host, size_t bytes, void **dptr)
-{
-    if (!d || !host || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad deinterlacer upload arguments"); return DSVG_ERR_ARG; }
-    HIPCHK(hipSetDevice(d->device));
-    if (d->up_bytes[buf] < bytes) {
-        if (d->up[buf]) { HIPCHK(hipStreamSynchronize(d->st)); HIPCHK(hipFree(d->up[buf])); d->up[buf] = nullptr; d->up_bytes[buf] = 0; }
-        HIPCHK(hipMalloc((void **)&d->up[buf], bytes + 256));
-        d->up_bytes[buf] = bytes;
-    }
-    HIPCHK(hipMemcpyAsync(d->up[buf], host, bytes, hipMemcpyHostToDevice, d->st));
-    *dptr = d->up[buf];
-    return DSVG_OK;
-}
-
-extern "C" void *dsvg_deint_stream(dsvg_deint *d) { return d ? (void *)d->st : nullptr; }
 
 // nsrc sources x nin frames ([source][frame]) -> nsrc x (nin or 2 nin) pictures; prev: one frame per source, pstride apart, or nullptr
 static int di_launch(const dsvg_deint *d, hipStream_t st, const uint8_t *src, int nsrc, int nin, const uint8_t *prev, size_t pstride, uint8_t *dst)
@@ -338,7 +295,7 @@ static int di_launch(const dsvg_deint *d, hipStream_t st, const uint8_t *src, in
 
 // a session's call: nin frames of each of the nsrc sources; `prev` is what the deinterlacer kept of the call before, and the call's
 // last input frames are kept for the next
-extern "C" int dsvg_deint_run_on(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev)
+extern "C" int dsvg_deint_run(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev)
 {
     if (!d || !d->hist || !src_dev || !dst_dev || nin < 1) { dsvg_set_error("bad deinterlace arguments"); return DSVG_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
@@ -361,26 +318,12 @@ extern "C" int dsvg_deint_run_on(dsvg_deint *d, void *stream, const void *src_de
     return DSVG_OK;
 }
 
-static int deint_record(dsvg_deint *d, void *stream)
-{
-    if (!d) return DSVG_ERR_ARG;
-    HIPCHK(hipEventRecord(d->ev, (hipStream_t)stream));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_deint_run(dsvg_deint *d, const void *src_dev, int nin, void *dst_dev)
-{
-    if (!d) return DSVG_ERR_ARG;
-    const int rc = dsvg_deint_run_on(d, (void *)d->st, src_dev, nin, dst_dev);
-    return rc ? rc : deint_record(d, (void *)d->st);
-}
-
 // the standalone pass: n frames of one stream, `prev` (device, or nullptr) the frame before them; no history is read or kept
-extern "C" int dsvg_deint_clip(dsvg_deint *d, const void *src_dev, int n, const void *prev_dev, void *dst_dev)
+extern "C" int dsvg_deint_clip(dsvg_deint *d, void *stream, const void *src_dev, int n, const void *prev_dev, void *dst_dev)
 {
     if (!d || !src_dev || !dst_dev || n < 1) { dsvg_set_error("bad deinterlace arguments"); return DSVG_ERR_ARG; }
     HIPCHK(hipSetDevice(d->device));
-    return di_launch(d, d->st, (const uint8_t *)src_dev, 1, n, (const uint8_t *)prev_dev, 0, (uint8_t *)dst_dev);
+    return di_launch(d, (hipStream_t)stream, (const uint8_t *)src_dev, 1, n, (const uint8_t *)prev_dev, 0, (uint8_t *)dst_dev);
 }
 
 extern "C" int dsvg_deint_reset(dsvg_deint *d, int source)
@@ -388,28 +331,5 @@ extern "C" int dsvg_deint_reset(dsvg_deint *d, int source)
     if (!d || source < -1 || source >= d->nsrc) return DSVG_ERR_ARG;
     for (int s = 0; s < d->nsrc; s++)
         if (source < 0 || s == source) d->valid[(size_t)s] = 0;
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_deint_order(dsvg_deint *d, dsvg_ctx *ctx)
-{
-    if (!d || !ctx) return DSVG_ERR_ARG;
-    return dsvg_ctx_load_wait(ctx, (void *)d->ev);
-}
-
-extern "C" int dsvg_deint_sync(dsvg_deint *d)
-{
-    if (!d) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipStreamSynchronize(d->st));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_deint_download(dsvg_deint *d, void *host, const void *dptr, size_t bytes)
-{
-    if (!d || !host || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipMemcpyAsync(host, dptr, bytes, hipMemcpyDeviceToHost, d->st));
-    HIPCHK(hipStreamSynchronize(d->st));
     return DSVG_OK;
 }

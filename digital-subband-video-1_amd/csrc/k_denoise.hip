@@ -229,22 +229,16 @@ __global__ __launch_bounds__(DN_THREADS) void k_denoise(const DnParams P, const 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-extern "C" int dsvg_ctx_load_wait(dsvg_ctx *ctx, void *event);
-
 struct dsvg_denoise {
     int device = 0, nsrc = 0;
     DnParams P;
     int nblocks = 0;
     size_t fb = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev = nullptr;
-    uint8_t *up[2] = {nullptr, nullptr};
-    size_t up_bytes[2] = {0, 0};
     uint8_t *pin[2] = {nullptr, nullptr};// [nsrc] frames each: the state's pin, read from pin[flip] and written to pin[flip ^ 1]
     uint8_t *S = nullptr;                // [nsrc][2 * fb]: the state's S, updated in place (a sample's S is its own item's)
     int flip = 0;
     std::vector<unsigned char> valid;    // per source: the state holds a picture
-    std::vector<void *> owned;
+    uint8_t *tmp = nullptr;              // _clip: the state a clip leaves (3 frames), allocated by the first call
 };
 
 extern "C" int dsv1_denoise_valid(const dsv1_denoise *dn);
@@ -253,27 +247,19 @@ extern "C" void dsvg_denoise_destroy(dsvg_denoise *d)
 {
     if (!d) return;
     if (hipSetDevice(d->device) == hipSuccess) {
-        if (d->st) (void)hipStreamSynchronize(d->st);
-        for (void *p : d->owned) (void)hipFree(p);
-        for (int k = 0; k < 2; k++) if (d->up[k]) (void)hipFree(d->up[k]);
         for (int k = 0; k < 2; k++) if (d->pin[k]) (void)hipFree(d->pin[k]);
         if (d->S) (void)hipFree(d->S);
-        if (d->ev) (void)hipEventDestroy(d->ev);
-        if (d->st) (void)hipStreamDestroy(d->st);
+        if (d->tmp) (void)hipFree(d->tmp);
     }
     (void)hipGetLastError();
     delete d;
 }
 
-static int denoise_device_side(dsvg_denoise *d, bool with_state)
+static int denoise_state(dsvg_denoise *d)
 {
     HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&d->ev, hipEventDisableTiming));
-    if (with_state) {
-        for (int k = 0; k < 2; k++) HIPCHK(hipMalloc((void **)&d->pin[k], d->fb * (size_t)d->nsrc + 256));
-        HIPCHK(hipMalloc((void **)&d->S, 2 * d->fb * (size_t)d->nsrc + 256));
-    }
+    for (int k = 0; k < 2; k++) HIPCHK(hipMalloc((void **)&d->pin[k], d->fb * (size_t)d->nsrc + 256));
+    HIPCHK(hipMalloc((void **)&d->S, 2 * d->fb * (size_t)d->nsrc + 256));
     return DSVG_OK;
 }
 
@@ -308,38 +294,11 @@ extern "C" int dsvg_denoise_create(dsvg_denoise **out, int device, int w, int h,
     d->nblocks = (int)blocks;
     d->fb = (size_t)off;
     d->P.fb = off;
-    const int rc = denoise_device_side(d, with_state != 0);
+    const int rc = with_state ? denoise_state(d) : DSVG_OK;
     if (rc) { dsvg_denoise_destroy(d); return rc; }
     *out = d;
     return DSVG_OK;
 }
-
-extern "C" int dsvg_denoise_alloc(dsvg_denoise *d, void **dptr, size_t bytes)
-{
-    if (!d || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(d->device));
-    const hipError_t e = hipMalloc(dptr, bytes + 256);
-    if (e != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; dsvg_set_error("hipMalloc of %zu bytes failed", bytes); return DSVG_ERR_HIP; }
-    d->owned.push_back(*dptr);
-    return DSVG_OK;
-}
-
-// host bytes -> upload buffer `buf` (0 / 1) on the filter's stream: behind the pass that read the buffer last
-extern "C" int dsvg_denoise_upload(dsvg_denoise *d, int buf, const void *host, size_t bytes, void **dptr)
-{
-    if (!d || !host || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad noise filter upload arguments"); return DSVG_ERR_ARG; }
-    HIPCHK(hipSetDevice(d->device));
-    if (d->up_bytes[buf] < bytes) {
-        if (d->up[buf]) { HIPCHK(hipStreamSynchronize(d->st)); HIPCHK(hipFree(d->up[buf])); d->up[buf] = nullptr; d->up_bytes[buf] = 0; }
-        HIPCHK(hipMalloc((void **)&d->up[buf], bytes + 256));
-        d->up_bytes[buf] = bytes;
-    }
-    HIPCHK(hipMemcpyAsync(d->up[buf], host, bytes, hipMemcpyHostToDevice, d->st));
-    *dptr = d->up[buf];
-    return DSVG_OK;
-}
-
-extern "C" void *dsvg_denoise_stream(dsvg_denoise *d) { return d ? (void *)d->st : nullptr; }
 
 // nsrc sources x n pictures ([source][picture]) -> the same; the state each source starts from (pin_in / s_in, null: none) and the
 // one it leaves, each with its source-to-source distance
@@ -372,7 +331,7 @@ static int dn_launch(const dsvg_denoise *d, hipStream_t st, const uint8_t *src, 
 }
 
 // a session's call: n pictures of each of the nsrc sources; every source goes on from the state the call before left, and leaves its own
-extern "C" int dsvg_denoise_run_on(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev)
+extern "C" int dsvg_denoise_run(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev)
 {
     if (!d || !d->S || !src_dev || !dst_dev || n < 1) { dsvg_set_error("bad noise filter arguments"); return DSVG_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
@@ -396,28 +355,18 @@ extern "C" int dsvg_denoise_run_on(dsvg_denoise *d, void *stream, const void *sr
     return DSVG_OK;
 }
 
-extern "C" int dsvg_denoise_run(dsvg_denoise *d, const void *src_dev, int n, void *dst_dev)
-{
-    if (!d) return DSVG_ERR_ARG;
-    const int rc = dsvg_denoise_run_on(d, (void *)d->st, src_dev, n, dst_dev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(d->ev, d->st));
-    return DSVG_OK;
-}
-
 // the standalone pass: n pictures of one stream from the state state_in (device, 3 frames' bytes, or nullptr: the stream starts here);
 // state_out (device or nullptr) receives the state the clip leaves -- through a buffer of the filter's own, so it may be state_in
-extern "C" int dsvg_denoise_clip(dsvg_denoise *d, const void *src_dev, int n, const void *state_in_dev, void *state_out_dev, void *dst_dev)
+extern "C" int dsvg_denoise_clip(dsvg_denoise *d, void *stream, const void *src_dev, int n, const void *state_in_dev, void *state_out_dev, void *dst_dev)
 {
     if (!d || !src_dev || !dst_dev || n < 1) { dsvg_set_error("bad noise filter arguments"); return DSVG_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(d->device));
-    void *tmp = nullptr;
-    int rc = dsvg_denoise_alloc(d, &tmp, 3 * d->fb);
-    if (rc) return rc;
+    if (!d->tmp) HIPCHK(hipMalloc((void **)&d->tmp, 3 * d->fb + 256));
     const uint8_t *si = (const uint8_t *)state_in_dev;
-    rc = dn_launch(d, d->st, (const uint8_t *)src_dev, 1, n, si, si ? si + d->fb : nullptr, 0, 0, (uint8_t *)tmp, (uint8_t *)tmp + d->fb, 0, 0, (uint8_t *)dst_dev);
+    const int rc = dn_launch(d, st, (const uint8_t *)src_dev, 1, n, si, si ? si + d->fb : nullptr, 0, 0, d->tmp, d->tmp + d->fb, 0, 0, (uint8_t *)dst_dev);
     if (rc) return rc;
-    if (state_out_dev) HIPCHK(hipMemcpyAsync(state_out_dev, tmp, 3 * d->fb, hipMemcpyDeviceToDevice, d->st));
+    if (state_out_dev) HIPCHK(hipMemcpyAsync(state_out_dev, d->tmp, 3 * d->fb, hipMemcpyDeviceToDevice, st));
     return DSVG_OK;
 }
 
@@ -426,28 +375,5 @@ extern "C" int dsvg_denoise_reset(dsvg_denoise *d, int source)
     if (!d || source < -1 || source >= d->nsrc) return DSVG_ERR_ARG;
     for (int s = 0; s < d->nsrc; s++)
         if (source < 0 || s == source) d->valid[(size_t)s] = 0;
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_denoise_order(dsvg_denoise *d, dsvg_ctx *ctx)
-{
-    if (!d || !ctx) return DSVG_ERR_ARG;
-    return dsvg_ctx_load_wait(ctx, (void *)d->ev);
-}
-
-extern "C" int dsvg_denoise_sync(dsvg_denoise *d)
-{
-    if (!d) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipStreamSynchronize(d->st));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_denoise_download(dsvg_denoise *d, void *host, const void *dptr, size_t bytes)
-{
-    if (!d || !host || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(d->device));
-    HIPCHK(hipMemcpyAsync(host, dptr, bytes, hipMemcpyDeviceToHost, d->st));
-    HIPCHK(hipStreamSynchronize(d->st));
     return DSVG_OK;
 }

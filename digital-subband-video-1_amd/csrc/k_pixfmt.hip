@@ -163,8 +163,6 @@ __global__ __launch_bounds__(PX_THREADS) void k_pixfmt(const PixParams P, const 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-extern "C" int dsvg_ctx_load_wait(dsvg_ctx *ctx, void *event);
-
 struct dsvg_pixconv {
     int device = 0;
     int layout = 0;                      // PXL_*
@@ -173,34 +171,9 @@ struct dsvg_pixconv {
     int nblocks = 0;
     bool rgb = false;                    // the pass is the RGB import (k_rgb.hip) of layout R; L, P and nblocks are not used
     dsv1_rgb_layout R;
-    hipStream_t st = nullptr;
-    hipEvent_t ev = nullptr;
-    uint8_t *up[2] = {nullptr, nullptr};
-    size_t up_bytes[2] = {0, 0};
-    std::vector<void *> owned;
 };
 
-extern "C" void dsvg_pixconv_destroy(dsvg_pixconv *c)
-{
-    if (!c) return;
-    if (hipSetDevice(c->device) == hipSuccess) {
-        if (c->st) (void)hipStreamSynchronize(c->st);
-        for (void *p : c->owned) (void)hipFree(p);
-        for (int k = 0; k < 2; k++) if (c->up[k]) (void)hipFree(c->up[k]);
-        if (c->ev) (void)hipEventDestroy(c->ev);
-        if (c->st) (void)hipStreamDestroy(c->st);
-    }
-    (void)hipGetLastError();
-    delete c;
-}
-
-static int pixconv_streams(dsvg_pixconv *c)
-{
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
-    return DSVG_OK;
-}
+extern "C" void dsvg_pixconv_destroy(dsvg_pixconv *c) { delete c; }
 
 extern "C" int dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pix_layout *L)
 {
@@ -228,13 +201,11 @@ extern "C" int dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pi
     c->nblocks = (int)blocks;
     c->P.nseg = L->nseg; c->P.shift = L->shift;
     c->P.sfb = (long long)L->frame_bytes; c->P.dfb = (long long)L->out_frame_bytes;
-    const int rc = pixconv_streams(c);
-    if (rc) { dsvg_pixconv_destroy(c); return rc; }
     *out = c;
     return DSVG_OK;
 }
 
-// the converter of an RGB source: the same streams, buffers and ordering around another pass
+// the converter of an RGB source: another pass behind the same entry points
 extern "C" int dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv1_rgb_layout *R)
 {
     if (!out || !R || R->w < 1 || R->h < 1 || (R->nplanes != 1 && R->nplanes != 3)) { dsvg_set_error("bad converter arguments"); return DSVG_ERR_ARG; }
@@ -244,34 +215,7 @@ extern "C" int dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv
     c->device = device; c->rgb = true; c->R = *R;
     memset(&c->L, 0, sizeof c->L);
     memset(&c->P, 0, sizeof c->P);
-    const int rc = pixconv_streams(c);
-    if (rc) { dsvg_pixconv_destroy(c); return rc; }
     *out = c;
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_pixconv_alloc(dsvg_pixconv *c, void **dptr, size_t bytes)
-{
-    if (!c || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    const hipError_t e = hipMalloc(dptr, bytes + 256);
-    if (e != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; dsvg_set_error("hipMalloc of %zu bytes failed", bytes); return DSVG_ERR_HIP; }
-    c->owned.push_back(*dptr);
-    return DSVG_OK;
-}
-
-// raw host clip -> upload buffer `buf` (0 / 1) on the converter's stream: behind the conversion that read the buffer last
-extern "C" int dsvg_pixconv_upload(dsvg_pixconv *c, int buf, const void *host, size_t bytes, void **dptr)
-{
-    if (!c || !host || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad converter upload arguments"); return DSVG_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    if (c->up_bytes[buf] < bytes) {
-        if (c->up[buf]) { HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipFree(c->up[buf])); c->up[buf] = nullptr; c->up_bytes[buf] = 0; }
-        HIPCHK(hipMalloc((void **)&c->up[buf], bytes + 256));
-        c->up_bytes[buf] = bytes;
-    }
-    HIPCHK(hipMemcpyAsync(c->up[buf], host, bytes, hipMemcpyHostToDevice, c->st));
-    *dptr = c->up[buf];
     return DSVG_OK;
 }
 
@@ -292,7 +236,7 @@ static int seg_fast(const PixParams &P, const PixSeg &S, const void *src, const 
     return 1;
 }
 
-extern "C" int dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev)
+extern "C" int dsvg_pixconv_run(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev)
 {
     if (!c || !src_dev || !dst_dev || nframes < 1) { dsvg_set_error("bad convert arguments"); return DSVG_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
@@ -317,37 +261,5 @@ extern "C" int dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *sr
         }
     }
     HIPCHK(hipGetLastError());
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_pixconv_run(dsvg_pixconv *c, const void *src_dev, int nframes, void *dst_dev)
-{
-    if (!c) return DSVG_ERR_ARG;
-    const int rc = dsvg_pixconv_run_on(c, (void *)c->st, src_dev, nframes, dst_dev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(c->ev, c->st));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_pixconv_order(dsvg_pixconv *c, dsvg_ctx *ctx)
-{
-    if (!c || !ctx) return DSVG_ERR_ARG;
-    return dsvg_ctx_load_wait(ctx, (void *)c->ev);
-}
-
-extern "C" int dsvg_pixconv_sync(dsvg_pixconv *c)
-{
-    if (!c) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->st));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_pixconv_download(dsvg_pixconv *c, void *host, const void *dptr, size_t bytes)
-{
-    if (!c || !host || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(host, dptr, bytes, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
     return DSVG_OK;
 }

@@ -130,7 +130,6 @@ __global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restri
 // ------------------------------------------------------------------------------------------------ host side
 extern "C" int dsv1_resample_taps(int S, int D, int filter);
 extern "C" int dsv1_resample_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T);
-extern "C" int dsvg_ctx_load_wait(dsvg_ctx *ctx, void *event);
 
 struct ScaleGeo {
     ScalePlane *planes_d = nullptr;      // [3] + tables, one allocation
@@ -143,12 +142,7 @@ struct ScaleGeo {
 struct dsvg_scaler {
     int device = 0, sw = 0, sh = 0, fmt = 0, filter = 0;
     size_t sfb = 0;
-    hipStream_t st = nullptr;
-    hipEvent_t ev = nullptr;
     std::vector<ScaleGeo> geo;
-    uint8_t *up[2] = {nullptr, nullptr};
-    size_t up_bytes[2] = {0, 0};
-    std::vector<void *> owned;           // scaled clips (dsvg_scaler_alloc)
 };
 
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -241,14 +235,8 @@ static int scaler_geo(dsvg_scaler *s, int dw, int dh, ScaleGeo &G)
 extern "C" void dsvg_scaler_destroy(dsvg_scaler *s)
 {
     if (!s) return;
-    if (hipSetDevice(s->device) == hipSuccess) {
-        if (s->st) (void)hipStreamSynchronize(s->st);
+    if (hipSetDevice(s->device) == hipSuccess)
         for (auto &G : s->geo) if (G.planes_d) (void)hipFree(G.planes_d);
-        for (void *p : s->owned) (void)hipFree(p);
-        for (int k = 0; k < 2; k++) if (s->up[k]) (void)hipFree(s->up[k]);
-        if (s->ev) (void)hipEventDestroy(s->ev);
-        if (s->st) (void)hipStreamDestroy(s->st);
-    }
     (void)hipGetLastError();
     delete s;
 }
@@ -256,8 +244,6 @@ extern "C" void dsvg_scaler_destroy(dsvg_scaler *s)
 static int scaler_create_impl(dsvg_scaler *s, int ngeom, const int *dw, const int *dh)
 {
     HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&s->ev, hipEventDisableTiming));
     s->geo.resize((size_t)ngeom);
     for (int g = 0; g < ngeom; g++) {
         const int rc = scaler_geo(s, dw[g], dh[g], s->geo[(size_t)g]);
@@ -280,112 +266,17 @@ extern "C" int dsvg_scaler_create(dsvg_scaler **out, int device, int sw, int sh,
     return DSVG_OK;
 }
 
-extern "C" int dsvg_scaler_alloc(dsvg_scaler *s, void **dptr, size_t bytes)
-{
-    if (!s || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(s->device));
-    const hipError_t e = hipMalloc(dptr, bytes + 256);
-    if (e != hipSuccess) { (void)hipGetLastError(); *dptr = nullptr; dsvg_set_error("hipMalloc of %zu bytes failed", bytes); return DSVG_ERR_HIP; }
-    s->owned.push_back(*dptr);
-    return DSVG_OK;
-}
-
-// host clip -> upload buffer `buf` (0 / 1) on the scaler's stream: behind the scales that read the buffer last, in stream order
-static int scaler_copy(dsvg_scaler *s, int buf, const void *from, size_t bytes, void **dptr, hipMemcpyKind kind)
-{
-    if (!s || !from || !dptr || !bytes || buf < 0 || buf > 1) { dsvg_set_error("bad scaler upload arguments"); return DSVG_ERR_ARG; }
-    HIPCHK(hipSetDevice(s->device));
-    if (s->up_bytes[buf] < bytes) {
-        if (s->up[buf]) { HIPCHK(hipStreamSynchronize(s->st)); HIPCHK(hipFree(s->up[buf])); s->up[buf] = nullptr; s->up_bytes[buf] = 0; }
-        HIPCHK(hipMalloc((void **)&s->up[buf], bytes + 256));
-        s->up_bytes[buf] = bytes;
-    }
-    HIPCHK(hipMemcpyAsync(s->up[buf], from, bytes, kind, s->st));
-    HIPCHK(hipEventRecord(s->ev, s->st));
-    *dptr = s->up[buf];
-    return DSVG_OK;
-}
-extern "C" int dsvg_scaler_upload(dsvg_scaler *s, int buf, const void *host, size_t bytes, void **dptr)
-{
-    return scaler_copy(s, buf, host, bytes, dptr, hipMemcpyHostToDevice);
-}
-// the same from device memory (a copy the caller's clip need not outlive)
-extern "C" int dsvg_scaler_copy_in(dsvg_scaler *s, int buf, const void *dev, size_t bytes, void **dptr)
-{
-    return scaler_copy(s, buf, dev, bytes, dptr, hipMemcpyDeviceToDevice);
-}
-
-extern "C" int dsvg_scaler_run(dsvg_scaler *s, int g, const void *src_dev, int nframes, void *dst_dev)
+extern "C" int dsvg_scaler_run(dsvg_scaler *s, void *stream, int g, const void *src_dev, int nframes, void *dst_dev)
 {
     if (!s || g < 0 || g >= (int)s->geo.size() || !src_dev || !dst_dev || nframes < 1) { dsvg_set_error("bad scale arguments"); return DSVG_ERR_ARG; }
     const ScaleGeo &G = s->geo[(size_t)g];
     HIPCHK(hipSetDevice(s->device));
     for (int f0 = 0; f0 < nframes; f0 += 65535) {        // (gridDim.y; one launch for any call the ladders make)
         const int n = std::min(65535, nframes - f0);
-        hipLaunchKernelGGL(k_scale, dim3(G.ntiles, n), dim3(SC_THREADS), G.lds, s->st, G.planes_d,
+        hipLaunchKernelGGL(k_scale, dim3(G.ntiles, n), dim3(SC_THREADS), G.lds, (hipStream_t)stream, G.planes_d,
                            (const uint8_t *)src_dev + (size_t)f0 * s->sfb, (uint8_t *)dst_dev + (size_t)f0 * G.dfb,
                            (long long)s->sfb, (long long)G.dfb, G.th_tile, G.rows_cap, G.th_cap, G.tv_cap, G.span_cap);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(s->ev, s->st));
-    return DSVG_OK;
-}
-
-// a source of another pixel format (k_pixfmt.hip): converted on this stream, so that the scales enqueued next read the result
-struct dsvg_pixconv;
-extern "C" int dsvg_pixconv_run_on(dsvg_pixconv *c, void *stream, const void *src_dev, int nframes, void *dst_dev);
-extern "C" int dsvg_scaler_convert(dsvg_scaler *s, dsvg_pixconv *pc, const void *src_dev, int nframes, void *dst_dev)
-{
-    if (!s || !pc) { dsvg_set_error("bad scaler convert arguments"); return DSVG_ERR_ARG; }
-    const int rc = dsvg_pixconv_run_on(pc, (void *)s->st, src_dev, nframes, dst_dev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(s->ev, s->st));
-    return DSVG_OK;
-}
-
-// the deinterlacer's pass (k_deint.hip) on the scaler's stream, behind the conversion and in front of the scales
-struct dsvg_deint;
-extern "C" int dsvg_deint_run_on(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev);
-extern "C" int dsvg_scaler_deint(dsvg_scaler *s, dsvg_deint *dd, const void *src_dev, int nin, void *dst_dev)
-{
-    if (!s || !dd) { dsvg_set_error("bad scaler deinterlace arguments"); return DSVG_ERR_ARG; }
-    const int rc = dsvg_deint_run_on(dd, (void *)s->st, src_dev, nin, dst_dev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(s->ev, s->st));
-    return DSVG_OK;
-}
-
-// the noise filter's pass (k_denoise.hip) on the scaler's stream, behind the deinterlacer and in front of the scales
-struct dsvg_denoise;
-extern "C" int dsvg_denoise_run_on(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev);
-extern "C" int dsvg_scaler_denoise(dsvg_scaler *s, dsvg_denoise *dn, const void *src_dev, int n, void *dst_dev)
-{
-    if (!s || !dn) { dsvg_set_error("bad scaler noise filter arguments"); return DSVG_ERR_ARG; }
-    const int rc = dsvg_denoise_run_on(dn, (void *)s->st, src_dev, n, dst_dev);
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(s->ev, s->st));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_scaler_order(dsvg_scaler *s, dsvg_ctx *ctx)
-{
-    if (!s || !ctx) return DSVG_ERR_ARG;
-    return dsvg_ctx_load_wait(ctx, (void *)s->ev);
-}
-
-extern "C" int dsvg_scaler_sync(dsvg_scaler *s)
-{
-    if (!s) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipStreamSynchronize(s->st));
-    return DSVG_OK;
-}
-
-extern "C" int dsvg_scaler_download(dsvg_scaler *s, void *host, const void *dptr, size_t bytes)
-{
-    if (!s || !host || !dptr) return DSVG_ERR_ARG;
-    HIPCHK(hipSetDevice(s->device));
-    HIPCHK(hipMemcpyAsync(host, dptr, bytes, hipMemcpyDeviceToHost, s->st));
-    HIPCHK(hipStreamSynchronize(s->st));
     return DSVG_OK;
 }

@@ -348,6 +348,112 @@ def test_behind_the_deinterlacer(pkg, orc, mode):
     assert [x + y for x, y in zip(first, second)] == want
 
 
+def _uyvy(clips, fmt):
+    """the clips as UYVY, [n, raw frame bytes] each, and the format"""
+    f = PF.pf(PF.UYVY)
+    raws = [PF.pack(c.astype(np.uint32), f, W, H, fmt, np.random.default_rng(s)).reshape(c.shape[0], -1) for s, c in enumerate(clips)]
+    for r, c in zip(raws, clips):
+        assert np.array_equal(PF.convert(r.reshape(-1), f, W, H, fmt, c.shape[0]), c)
+    return raws, f
+
+
+def test_all_three_passes(pkg, orc):
+    """a UYVY source -> frame-rate deinterlacer -> noise filter: a batch with host input, and a resolution ladder with one scaled and
+    one same-size geometry and a plain device clip, code the oracle's streams of the clip after tests/_pixfmt.py, tests/_deint.py and
+    tests/_denoise.py in that order (and tests/_scale.py for the scaled geometry)"""
+    fmt = A.SUBSAMP_422
+    clips = interlaced(fmt, DI.FRAME)
+    raws, f = _uyvy(clips, fmt)
+    den = [D.denoise_clip(DI.deint_clip(c, W, H, fmt, DI.FRAME, 1), W, H, fmt, *DN)[0] for c in clips]
+    calls = calls_of(raws, F)
+    assert len(calls) == 2
+    pf = pkg.PixFormat(f["layout"], f["depth"], f["msb"], f["pitch"], f["frame_bytes"])
+    want = [oracle(("3b", s), den[s], W, H, fmt, qp=80)[0] for s in range(S)]
+    b = pkg.Batch(pkg.make_encoder_cfg(W, H, fmt, **dict(CRF, qp=80)), S, F)
+    try:
+        b.set_source_format(pf)
+        b.set_source_deinterlace(pkg.Deint(DI.FRAME, 1))
+        b.set_source_denoise(pkg.Denoise(*DN))
+        got, _ = run(b, calls, "host")
+    finally:
+        b.close()
+    assert got == want, "batch"
+    geoms = [(W, H, 80), (176, 144, 70)]
+    want = [oracle(("3b", s), den[s], W, H, fmt, qp=80)[0] if gw == W else
+            oracle(("3r", s), Z.scale_clip(den[s], W, H, fmt, gw, gh, Z.CUBIC), gw, gh, fmt, qp=qp)[0] for s in range(S) for gw, gh, qp in geoms]
+    r = pkg.ResLadder(W, H, fmt, [(gw, gh, [pkg.make_encoder_cfg(gw, gh, fmt, **dict(CRF, qp=qp))]) for gw, gh, qp in geoms], S, F, Z.CUBIC,
+                      src_format=pf)
+    try:
+        r.set_deinterlace(pkg.Deint(DI.FRAME, 1))
+        r.set_denoise(pkg.Denoise(*DN))
+        junk = np.full(calls[0].size, 0x5A, dtype=np.uint8)
+        ins = [r.upload(c) for c in calls]
+        got = [b""] * r.nstreams
+        for c in ins:
+            r.submit(c, on_device=True)
+            assert r.L.dsvg_dev_upload(r.ctx, c, junk.ctypes.data, junk.nbytes) == 0    # a plain device clip is the caller's again
+        for _ in ins:
+            got[:] = [x + bytes(p) for x, p in zip(got, r.collect())]
+    finally:
+        r.close()
+    for k in range(len(want)):
+        assert got[k] == want[k], "resolution ladder: output stream %d" % k
+
+
+def test_setters_between_batches_on_one_lane(pkg, orc):
+    """One batch, every call collected before the next change; the pass sets, in turn: none, denoise, deinterlace + denoise, UYVY +
+    deinterlace + denoise (two calls, deinterlace_reset(-1) / denoise_reset(-1) between them), UYVY only; then every pass cleared and
+    one more call, which codes the clip's frames themselves.  The streams are the oracle's of the concatenated numpy-modelled calls.  The documented state rules make the model:
+    setting the deinterlacer resets the filter's state, a newly set filter starts fresh, changing the converter resets nothing (so
+    the first call behind the converter goes on from the call before, history and state: the resets come after it, at the one kind
+    of call boundary where both passes are set on either side without a setter in between)."""
+    fmt = A.SUBSAMP_422
+    n = 7
+    clips = [DI.gen_interlaced(W, H, fmt, n * F, 0x4E0 + s, 1) for s in range(S)]
+    raws, f = _uyvy(clips, fmt)
+    dn = lambda c, state=None: D.denoise_clip(c, W, H, fmt, *DN, state=state)
+    di = lambda c, prev=None: DI.deint_clip(c, W, H, fmt, DI.FRAME, 1, prev=prev)
+    model, cont = [], []
+    for c in clips:
+        k = [c[i * F:(i + 1) * F] for i in range(n)]
+        c3, st3 = dn(di(k[2]))                           # the deinterlacer set: the filter set by the call before starts again
+        c4, _ = dn(di(k[3], prev=k[2][-1]), state=st3)   # the converter set: history and state go on
+        model.append(np.concatenate([k[0], dn(k[1])[0], c3, c4, dn(di(k[4]))[0], k[5], k[6]]))
+        cont.append(np.concatenate([dn(k[2])[0], dn(di(k[3]))[0]]))
+    # (what a filter that kept its state over the deinterlacer's setter, or passes that started again behind the converter's, would code)
+    assert not np.array_equal(model[0][2 * F:3 * F], dn(di(clips[0][2 * F:3 * F]), state=dn(clips[0][F:2 * F])[1])[0])
+    assert not np.array_equal(model[0][3 * F:4 * F], cont[0][F:])
+    want = [oracle(("lane", s), model[s], W, H, fmt, qp=80)[0] for s in range(S)]
+    pf = pkg.PixFormat(f["layout"], f["depth"], f["msb"], f["pitch"], f["frame_bytes"])
+    call = lambda src, i: np.ascontiguousarray(np.stack([c[i * F:(i + 1) * F] for c in src]))
+    got = [b""] * S
+    b = pkg.Batch(pkg.make_encoder_cfg(W, H, fmt, **dict(CRF, qp=80)), S, F)
+
+    def encode(src, i):
+        got[:] = [x + bytes(p) for x, p in zip(got, b.encode(call(src, i)))]
+
+    try:
+        encode(clips, 0)
+        b.set_source_denoise(pkg.Denoise(*DN))
+        encode(clips, 1)
+        b.set_source_deinterlace(pkg.Deint(DI.FRAME, 1))
+        encode(clips, 2)
+        b.set_source_format(pf)
+        encode(raws, 3)
+        b.deinterlace_reset(-1)
+        b.denoise_reset(-1)
+        encode(raws, 4)
+        b.set_source_deinterlace(None)
+        b.set_source_denoise(None)
+        encode(raws, 5)
+        b.set_source_format(None)
+        encode(clips, 6)
+    finally:
+        b.close()
+    for s in range(S):                                   # (the last call, every pass cleared, included: the clip's frames themselves)
+        assert got[s] == want[s], "source %d" % s
+
+
 @pytest.mark.parametrize("form", ["host", "device", "held"])
 def test_resolution_ladder(pkg, orc, form):
     fmt = A.SUBSAMP_420

@@ -94,15 +94,21 @@ def host_section(n, rounds):
         # 8 streams of n / 8: the standalone call takes one stream, so this figure comes from a session's filter object (section "batch"
         # has a whole call)
         try:
-            d8 = C.c_void_p(None)
+            d8, lane = C.c_void_p(None), C.c_void_p(None)
+            L.dsvg_lane_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
+            L.dsvg_lane_stream.argtypes = [C.c_void_p]
+            L.dsvg_lane_stream.restype = C.c_void_p
+            L.dsvg_lane_sync.argtypes = [C.c_void_p]
+            L.dsvg_lane_destroy.argtypes = [C.c_void_p]
             L.dsvg_denoise_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(pkg.Denoise), C.c_int, C.c_int]
-            L.dsvg_denoise_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-            L.dsvg_denoise_sync.argtypes = [C.c_void_p]
+            L.dsvg_denoise_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
             L.dsvg_denoise_destroy.argtypes = [C.c_void_p]
+            assert L.dsvg_lane_create(C.byref(lane), 0) == 0
             assert L.dsvg_denoise_create(C.byref(d8), 0, W, H, fmt, C.byref(dn), 8, 1) == 0
+            st = L.dsvg_lane_stream(lane)
 
             def eight():
-                assert L.dsvg_denoise_run(d8, src, n // 8, out) == 0 and L.dsvg_denoise_sync(d8) == 0
+                assert L.dsvg_denoise_run(d8, st, src, n // 8, out) == 0 and L.dsvg_lane_sync(lane) == 0
 
             fns = [lambda: pkg.convert_clip(raw, padded, W, H, fmt, n=n, out=out),
                    lambda: pkg.denoise_clip(src, W, H, fmt, dn, state=state, n=n, out=out, state_out=state), eight]
@@ -114,8 +120,12 @@ def host_section(n, rounds):
                     if r:                                # (round 0 warms up)
                         times[name].append(time.perf_counter() - t0)
         finally:
+            if lane:
+                L.dsvg_lane_sync(lane)                   # (the filter's kernels read what its destroy frees)
             if d8:
                 L.dsvg_denoise_destroy(d8)
+            if lane:
+                L.dsvg_lane_destroy(lane)
     finally:
         mem.close()
     return ["%dx%d 4:2:0, %d pictures resident in HBM, luma = chroma = 24, %d timed rounds, the settings alternating.  The standalone calls" % (W, H, n, rounds),
