@@ -656,6 +656,22 @@ def pix_frame_bytes(pf, w, h, fmt):
     return int(n)
 
 
+def _host_clip(clip, fb, what="a clip", raw=False):
+    """a host clip of fb-byte frames as (flat uint8 array, frames); raw: the clip's bytes as they lie, whatever its dtype"""
+    a = (_np.ascontiguousarray(clip).view(_np.uint8) if raw else _np.ascontiguousarray(clip, dtype=_np.uint8)).reshape(-1)
+    if a.size % fb or not a.size:
+        raise ValueError("%s is a whole number of %d-byte frames, got %d bytes" % (what, fb, a.size))
+    return a, a.size // fb
+
+
+def _host_out(out, frames, dfb):
+    """the exporters' result: `out` if it can hold frames x dfb bytes, or a zeroed array of that shape"""
+    res = _np.zeros((frames, dfb), dtype=_np.uint8) if out is None else out
+    if res.dtype != _np.uint8 or not res.flags.c_contiguous or res.size < frames * dfb:
+        raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % (frames * dfb))
+    return res
+
+
 def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None):
     """convert frames of PixFormat pf to packed planar 8-bit on the GPU (dsv1_convert_clip): clip numpy uint8 [frames][frame bytes]
     (host), or a device pointer with n frames and `out` a device pointer for the result.  Host input returns numpy uint8
@@ -666,10 +682,7 @@ def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None):
     if n is not None:
         _chk(L.dsv1_convert_clip(device, clip, _C.byref(pf), w, h, fmt, n, out, 1), "dsv1_convert_clip")
         return out
-    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
-    if a.size % sfb or not a.size:
-        raise ValueError("a clip of this format is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
-    frames = a.size // sfb
+    a, frames = _host_clip(clip, sfb, "a clip of this format", raw=True)
     res = _np.zeros((frames, dfb), dtype=_np.uint8)
     _chk(L.dsv1_convert_clip(device, a.ctypes.data, _C.byref(pf), w, h, fmt, frames, res.ctypes.data, 0), "dsv1_convert_clip")
     return res
@@ -684,10 +697,7 @@ def deinterlace_clip(clip, w, h, fmt, di, prev=None, device=0, n=None, out=None)
     if n is not None:
         _chk(L.dsv1_deinterlace_clip(device, clip, w, h, fmt, n, prev, out, _C.byref(di), 1), "dsv1_deinterlace_clip")
         return out
-    a = _np.ascontiguousarray(clip, dtype=_np.uint8).reshape(-1)
-    if a.size % fb or not a.size:
-        raise ValueError("a clip is a whole number of %d-byte frames, got %d bytes" % (fb, a.size))
-    frames = a.size // fb
+    a, frames = _host_clip(clip, fb)
     nout = L.dsv1_deint_out_frames(_C.byref(di), frames)
     if nout < 0:
         raise ValueError("not a deinterlacer: mode %d, tff %d" % (di.mode, di.tff))
@@ -712,17 +722,15 @@ def denoise_clip(clip, w, h, fmt, dn, state=None, device=0, n=None, out=None, st
     if n is not None:
         _chk(L.dsv1_denoise_clip(device, clip, w, h, fmt, n, state, state_out, out, _C.byref(dn), 1), "dsv1_denoise_clip")
         return out
-    a = _np.ascontiguousarray(clip, dtype=_np.uint8).reshape(-1)
-    if a.size % fb or not a.size:
-        raise ValueError("a clip is a whole number of %d-byte frames, got %d bytes" % (fb, a.size))
+    a, frames = _host_clip(clip, fb)
     p = None
     if state is not None:
         p = _np.ascontiguousarray(state, dtype=_np.uint8).reshape(-1)
         if p.size != 3 * fb:
             raise ValueError("a state is %d bytes, got %d" % (3 * fb, p.size))
-    res = _np.zeros((a.size // fb, fb), dtype=_np.uint8)
+    res = _np.zeros((frames, fb), dtype=_np.uint8)
     new = _np.zeros(3 * fb, dtype=_np.uint8)
-    _chk(L.dsv1_denoise_clip(device, a.ctypes.data, w, h, fmt, a.size // fb, p.ctypes.data if p is not None else None, new.ctypes.data,
+    _chk(L.dsv1_denoise_clip(device, a.ctypes.data, w, h, fmt, frames, p.ctypes.data if p is not None else None, new.ctypes.data,
                              res.ctypes.data, _C.byref(dn), 0), "dsv1_denoise_clip")
     return res, new
 
@@ -738,14 +746,8 @@ def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=Non
     if n is not None:
         _chk(L.dsv1_export_clip(device, clip, w, h, fmt, n, out, _C.byref(pf), osub, 1), "dsv1_export_clip")
         return out
-    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
-    if a.size % sfb or not a.size:
-        raise ValueError("a planar clip is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
-    frames = a.size // sfb
-    dfb = pix_frame_bytes(pf, w, h, osub)
-    res = _np.zeros((frames, dfb), dtype=_np.uint8) if out is None else out
-    if res.dtype != _np.uint8 or not res.flags.c_contiguous or res.size < frames * dfb:
-        raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % (frames * dfb))
+    a, frames = _host_clip(clip, sfb, "a planar clip", raw=True)
+    res = _host_out(out, frames, pix_frame_bytes(pf, w, h, osub))
     _chk(L.dsv1_export_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(pf), osub, 0), "dsv1_export_clip")
     return res
 
@@ -777,10 +779,7 @@ def rgb_import_clip(clip, rf, w, h, fmt, device=0, n=None, out=None):
     if n is not None:
         _chk(L.dsv1_rgb_import_clip(device, clip, _C.byref(rf), w, h, fmt, n, out, 1), "dsv1_rgb_import_clip")
         return out
-    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
-    if a.size % sfb or not a.size:
-        raise ValueError("a clip of this format is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
-    frames = a.size // sfb
+    a, frames = _host_clip(clip, sfb, "a clip of this format", raw=True)
     res = _np.zeros((frames, dfb), dtype=_np.uint8)
     _chk(L.dsv1_rgb_import_clip(device, a.ctypes.data, _C.byref(rf), w, h, fmt, frames, res.ctypes.data, 0), "dsv1_rgb_import_clip")
     return res
@@ -796,14 +795,8 @@ def rgb_export_clip(clip, w, h, fmt, rf, device=0, n=None, out=None):
     if n is not None:
         _chk(L.dsv1_rgb_export_clip(device, clip, w, h, fmt, n, out, _C.byref(rf), 1), "dsv1_rgb_export_clip")
         return out
-    a = _np.ascontiguousarray(clip).view(_np.uint8).reshape(-1)
-    if a.size % sfb or not a.size:
-        raise ValueError("a planar clip is a whole number of %d-byte frames, got %d bytes" % (sfb, a.size))
-    frames = a.size // sfb
-    dfb = rgb_frame_bytes(rf, w, h)
-    res = _np.zeros((frames, dfb), dtype=_np.uint8) if out is None else out
-    if res.dtype != _np.uint8 or not res.flags.c_contiguous or res.size < frames * dfb:
-        raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % (frames * dfb))
+    a, frames = _host_clip(clip, sfb, "a planar clip", raw=True)
+    res = _host_out(out, frames, rgb_frame_bytes(rf, w, h))
     _chk(L.dsv1_rgb_export_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(rf), 0), "dsv1_rgb_export_clip")
     return res
 
@@ -834,10 +827,7 @@ def scale_clip(clip, sw, sh, fmt, dw, dh, filt=SCALE_CUBIC, device=0, n=None, ou
     if n is not None:
         _chk(L.dsv1_scale_clip(device, clip, sw, sh, fmt, n, out, dw, dh, filt, 1), "dsv1_scale_clip")
         return out
-    a = _np.ascontiguousarray(clip, dtype=_np.uint8)
-    if a.size % sfb or not a.size:
-        raise ValueError("a clip of %dx%d frames is a whole number of %d-byte frames, got %d bytes" % (sw, sh, sfb, a.size))
-    frames = a.size // sfb
+    a, frames = _host_clip(clip, sfb, "a clip of %dx%d frames" % (sw, sh))
     res = _np.zeros((frames, dfb), dtype=_np.uint8)
     _chk(L.dsv1_scale_clip(device, a.ctypes.data, sw, sh, fmt, frames, res.ctypes.data, dw, dh, filt, 0), "dsv1_scale_clip")
     return res
@@ -868,10 +858,7 @@ def resample_clip(clip, sw, sh, fmt, dw, dh, filt=SCALE_CUBIC, device=0, n=None,
     if n is not None:
         _chk(L.dsv1_resample_clip(device, clip, sw, sh, fmt, n, out, dw, dh, filt, 1), "dsv1_resample_clip")
         return out
-    a = _np.ascontiguousarray(clip, dtype=_np.uint8)
-    if a.size % sfb or not a.size:
-        raise ValueError("a clip of %dx%d frames is a whole number of %d-byte frames, got %d bytes" % (sw, sh, sfb, a.size))
-    frames = a.size // sfb
+    a, frames = _host_clip(clip, sfb, "a clip of %dx%d frames" % (sw, sh))
     res = _np.zeros((frames, dfb), dtype=_np.uint8)
     _chk(L.dsv1_resample_clip(device, a.ctypes.data, sw, sh, fmt, frames, res.ctypes.data, dw, dh, filt, 0), "dsv1_resample_clip")
     return res
@@ -1105,6 +1092,13 @@ class DecBatch:
         """the device context (not cached: the batch builds a new one when its streams announce another block size)"""
         return self.L.dsv1_decbatch_ctx(self.h)
 
+    def _output_changed(self):
+        self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))
+        if self._dev is not None:                      # (sized for the frames of the setting before)
+            self.sync()
+            self.L.dsvg_dev_free(self.ctx, self._dev)
+            self._dev = None
+
     def set_output_format(self, pixformat, out_subsamp=None):
         """from the next decode() on, frames are written as PixFormat pixformat at subsampling out_subsamp (None: the streams' own;
         dsv1_decbatch_set_output_format); None switches back to packed planar.  frame_bytes follows; ValueError (and the setting as
@@ -1112,11 +1106,7 @@ class DecBatch:
         osub = self.fmt if out_subsamp is None else out_subsamp
         if self.L.dsv1_decbatch_set_output_format(self.h, None if pixformat is None else _C.byref(pixformat), osub) != 0:
             raise ValueError("not a valid output format for these streams (subsampling 0x%x -> 0x%x)" % (self.fmt, osub))
-        self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))
-        if self._dev is not None:                      # (sized for the frames of the setting before)
-            self.sync()
-            self.L.dsvg_dev_free(self.ctx, self._dev)
-            self._dev = None
+        self._output_changed()
 
     def set_output_rgb(self, rf):
         """from the next decode() on, frames are written as RGB of RgbFormat rf (dsv1_decbatch_set_output_rgb); None switches back to
@@ -1124,11 +1114,7 @@ class DecBatch:
         invalid format."""
         if self.L.dsv1_decbatch_set_output_rgb(self.h, None if rf is None else _C.byref(rf)) != 0:
             raise ValueError("not a valid RGB output format for these streams (subsampling 0x%x)" % self.fmt)
-        self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))
-        if self._dev is not None:                      # (sized for the frames of the setting before)
-            self.sync()
-            self.L.dsvg_dev_free(self.ctx, self._dev)
-            self._dev = None
+        self._output_changed()
 
     def decode(self, packets, out=None, on_device=False):
         """packets: one bytes object per stream.  Host output: returns (frames [nstreams][frame_bytes] uint8, status,

@@ -1,5 +1,6 @@
 // dsvg_lane.hip -- where a session's source-side work is enqueued (dsvg_pixfmt.h): one stream, one event, two upload buffers and the
-// device memory handed out.  The passes (k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_denoise.hip, k_scale.hip) run on the lane's stream.
+// device memory handed out.  The passes (k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_denoise.hip, k_scale.hip; the standalone export of
+// k_pixout.hip) run on the lane's stream.
 #include <algorithm>
 #include <vector>
 #include "dsvg_host.hpp"

@@ -253,10 +253,9 @@ struct dsvg_ctx {
         bool active = false, in_redo = false;
         int parity = 0, njobs = 0;
         std::vector<dsvg_dec_job> jobs;                  // the call's jobs in device order, pointing into the parity's pinned staging
-        bool have_pack = false;
-        std::vector<int> pack_slots; void *pack_out = nullptr; size_t pack_pitch = 0;
-        bool pack_export = false;                        // the pack was dsvg_export_recons: its frame indices and format
-        std::vector<int> pack_index; dsvg_pixout pack_fmt;
+        // the one output pass recorded (output_pass; none: no slots): slots, frame indices (empty: identity), destination, format
+        std::vector<int> slots, index; void *out = nullptr; size_t pitch = 0;
+        bool has_fmt = false; dsvg_pixout fmt;
     } dec_pending;
     bool dec_ov[2] = {false, false};    // luma / chroma planes have cells shared between scan regions (k_hz_dec_resolve)
     long dec_redone = 0;                // calls decoded again on the int32 path (tests)
@@ -265,8 +264,7 @@ struct dsvg_ctx {
     uint8_t *yuv_stage = nullptr;    // device staging for host-resident input frames
     size_t yuv_stage_bytes = 0;
     int *ltab_d = nullptr;           // slot table of dsvg_load_frames_map
-    int *ptab_d = nullptr;           // slot table of dsvg_pack_recons
-    int *xtab_d = nullptr;           // (slot, output frame) table of dsvg_export_recons
+    int *otab_d = nullptr;           // table of the output pass: slots (k_pack_n) or (slot, output frame) pairs (k_pixout)
     int *ilist_h = nullptr, *ilist_d = nullptr;   // intra blocks of the P pictures of a batch (pinned / device), indexed like jobs_h
     // host-resident input: two device ingest buffers filled on a copy stream of their own, so the upload of the
     // next batch runs under the analysis and coding of the current one
@@ -428,7 +426,7 @@ static void ctx_free(dsvg_ctx *c)
     c->recon.release(); c->xf.release(); c->pred.release();
     xres_geo_free(c->xg);
     void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->ptab_d, c->xtab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d, c->ssim_d, c->xsse_d, c->xssim_d, (void *)c->xref_d};
+                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d, c->ssim_d, c->xsse_d, c->xssim_d, (void *)c->xref_d};
     for (void *p : d) if (p) (void)hipFree(p);
     void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, c->sse_h, c->ssim_h, c->xsse_h, c->xssim_h, (void *)c->xref_h};
     for (void *p : hh) if (p) (void)hipHostFree(p);
@@ -2119,129 +2117,106 @@ extern "C" int dsvg_download_recon_raw(dsvg_ctx *c, int recon_slot, uint8_t *raw
     return DSVG_OK;
 }
 
-extern "C" int dsvg_pack_recons(dsvg_ctx *c, int n, const int *recon_slots, void *yuv_out, size_t out_pitch, int out_on_device)
+// The output pass of decoded pictures: n reconstruction slots to frames of `out`, in the context's packed planar frames (fmt == nullptr,
+// k_pack_n: frame i at position i) or in an output format (k_pixout: frame i at position index[i]; index == nullptr: i).  Device
+// output is written optimistically and recorded while the decoder call's escape flags are not back (dsvg_ctx::DecPending); host
+// output settles the call first, since it synchronises anyway.
+static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, void *out, size_t pitch, int on_device, const dsvg_pixout *fmt)
 {
-    if (!c || !recon_slots || !yuv_out || n < 1 || n > c->n_recon) { dsvg_set_error("bad pack_recons arguments"); return DSVG_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
-    const size_t fb = (size_t)c->L[0].w[0] * c->L[0].h[0] + 2 * (size_t)c->L[0].w[1] * c->L[0].h[1];
-    if (out_pitch < fb) { dsvg_set_error("output pitch smaller than a frame"); return DSVG_ERR_ARG; }
-    for (int i = 0; i < n; i++)
-        if (recon_slots[i] < 0 || recon_slots[i] >= c->n_recon) { dsvg_set_error("slot out of range"); return DSVG_ERR_ARG; }
-    if (!out_on_device) OPCHK(dec_resolve(c));          // (the call synchronises anyway: a flagged decoder call is repeated first)
-    else if (c->dec_pending.active && !c->dec_pending.in_redo && !c->dec_pending.have_pack) {
-        // device output of a decoder call whose flags are not back yet: packed optimistically, repeated by dec_resolve if need be
-        c->dec_pending.have_pack = true;
-        c->dec_pending.pack_slots.assign(recon_slots, recon_slots + n);
-        c->dec_pending.pack_out = yuv_out; c->dec_pending.pack_pitch = out_pitch;
-    } else if (c->dec_pending.active && !c->dec_pending.in_redo) OPCHK(dec_resolve(c));   // a second pack of the same call: settle it now
-    if (!c->ptab_d) HIPCHK(hipMalloc((void **)&c->ptab_d, sizeof(int) * (size_t)c->n_recon + 64));
-    if (out_on_device) {
-        // Round 5: device output is packed on the second coding stream -- beside the next call's entropy decoding, which touches neither the
-        // reconstructions nor the caller's frames (70 us of a 620 us step of 64 pictures).  Whatever rewrites a reconstruction slot next waits
-        // for the pass (dsvg_decode_pictures, in front of its inverse transform); dsvg_ctx_sync waits for every stream.
-        static const bool one_stream = getenv("DSV1_DEC_ONE_STREAM") != nullptr;      // (A/B)
-        hipStream_t sp_ = c->st;
-        if (!one_stream && n >= 4 && !c->dec_pending.in_redo && !c->prof.mask && c->stx[1]) {
-            for (int i = 0; i < 2; i++) if (!c->ev_pack[i]) HIPCHK(hipEventCreateWithFlags(&c->ev_pack[i], hipEventDisableTiming));
-            if (c->pack_pending) HIPCHK(hipStreamWaitEvent(c->st, c->ev_pack[1], 0));      // (a second pass before the next decode call: keep the passes in order)
-            sp_ = c->stx[1];
-            HIPCHK(hipEventRecord(c->ev_pack[0], c->st));
-            HIPCHK(hipStreamWaitEvent(sp_, c->ev_pack[0], 0));
-        }
-        HIPCHK(hipMemcpyAsync(c->ptab_d, recon_slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, sp_));   // pageable: staged by the runtime
-        launch_pack_n(sp_, (uint8_t *)yuv_out, out_pitch, c->recon.p, c->L[0], c->ptab_d, n, &c->prof);
-        if (sp_ != c->st) { HIPCHK(hipEventRecord(c->ev_pack[1], sp_)); c->pack_pending = true; }
-        HIPCHK(hipGetLastError());
-        return DSVG_OK;
-    }
-    if (c->pack_pending) { HIPCHK(hipStreamWaitEvent(c->st, c->ev_pack[1], 0)); c->pack_pending = false; }
-    HIPCHK(hipMemcpyAsync(c->ptab_d, recon_slots, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->st));   // pageable: staged by the runtime
-    const size_t sp = (fb + 255) & ~(size_t)255;
-    if (c->yuv_stage_bytes < sp * n) {
-        if (c->yuv_stage) { HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipStreamSynchronize(c->st_a)); HIPCHK(hipStreamSynchronize(c->st_l)); (void)hipFree(c->yuv_stage); c->yuv_stage = nullptr; }
-        HIPCHK(hipMalloc((void **)&c->yuv_stage, sp * n + 256));
-        c->yuv_stage_bytes = sp * n;
-    }
-    launch_pack_n(c->st, c->yuv_stage, sp, c->recon.p, c->L[0], c->ptab_d, n, &c->prof);
-    if (out_pitch == sp) HIPCHK(hipMemcpyAsync(yuv_out, c->yuv_stage, sp * (size_t)(n - 1) + fb, hipMemcpyDeviceToHost, c->st));
-    else HIPCHK(hipMemcpy2DAsync(yuv_out, out_pitch, c->yuv_stage, sp, fb, (size_t)n, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    HIPCHK(hipGetLastError());
-    return DSVG_OK;
-}
-
-// dsvg_pack_recons for an output format (include/dsvg.h): the same stream placement and ordering, k_pixout in the place of k_pack_n
-extern "C" int dsvg_export_recons(dsvg_ctx *c, int n, const int *recon_slots, const int *out_index, void *out, size_t out_pitch, int out_on_device,
-                                  const dsvg_pixout *fmt)
-{
-    if (!c || !recon_slots || !out || !fmt || n < 1 || n > c->n_recon) { dsvg_set_error("bad export_recons arguments"); return DSVG_ERR_ARG; }
+    if (!c || !slots || !out || n < 1 || n > c->n_recon) { dsvg_set_error("bad %s arguments", fmt ? "export_recons" : "pack_recons"); return DSVG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const FrameLayout &L = c->L[0];
     PoSource S;
     for (int p = 0; p < 3; p++) { S.w[p] = L.w[p]; S.h[p] = L.h[p]; S.pitch[p] = L.stride[p]; S.off[p] = (long long)L.off[p]; }
     S.fb = (long long)L.pitch;
-    if (out_pitch < fmt->frame_bytes) { dsvg_set_error("output pitch smaller than a frame"); return DSVG_ERR_ARG; }
-    if (pixout_check(fmt, S, out_pitch)) { dsvg_set_error("the output format does not fit the context's frames"); return DSVG_ERR_ARG; }
+    const size_t fb = fmt ? fmt->frame_bytes : (size_t)L.w[0] * L.h[0] + 2 * (size_t)L.w[1] * L.h[1];
+    if (pitch < fb) { dsvg_set_error("output pitch smaller than a frame"); return DSVG_ERR_ARG; }
+    if (fmt && pixout_check(fmt, S, pitch)) { dsvg_set_error("the output format does not fit the context's frames"); return DSVG_ERR_ARG; }
+    // the table the kernel reads: the slots (k_pack_n), or (slot, output frame) pairs (k_pixout)
+    std::vector<int> pairs;
     int last = 0;
-    std::vector<int> tab(2 * (size_t)n);
     for (int i = 0; i < n; i++) {
-        if (recon_slots[i] < 0 || recon_slots[i] >= c->n_recon) { dsvg_set_error("slot out of range"); return DSVG_ERR_ARG; }
-        const int o = out_index ? out_index[i] : i;
+        if (slots[i] < 0 || slots[i] >= c->n_recon) { dsvg_set_error("slot out of range"); return DSVG_ERR_ARG; }
+        if (!fmt) continue;
+        const int o = index ? index[i] : i;
         if (o < 0) { dsvg_set_error("negative output frame index"); return DSVG_ERR_ARG; }
-        tab[2 * i] = recon_slots[i]; tab[2 * i + 1] = o;
+        pairs.push_back(slots[i]); pairs.push_back(o);
         last = std::max(last, o);
     }
-    if (!out_on_device) OPCHK(dec_resolve(c));          // (the call synchronises anyway: a flagged decoder call is repeated first)
-    else if (c->dec_pending.active && !c->dec_pending.in_redo && !c->dec_pending.have_pack) {
-        // device output of a decoder call whose flags are not back yet: written optimistically, repeated by dec_resolve -- in this
-        // format -- if need be
-        dsvg_ctx::DecPending &P = c->dec_pending;
-        P.have_pack = true; P.pack_export = true;
-        P.pack_slots.assign(recon_slots, recon_slots + n);
-        P.pack_index.resize((size_t)n);
-        for (int i = 0; i < n; i++) P.pack_index[i] = tab[2 * i + 1];
-        P.pack_out = out; P.pack_pitch = out_pitch; P.pack_fmt = *fmt;
-    } else if (c->dec_pending.active && !c->dec_pending.in_redo) OPCHK(dec_resolve(c));   // a second pass over the same call: settle it now
-    if (!c->xtab_d) HIPCHK(hipMalloc((void **)&c->xtab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
-    if (out_on_device) {
-        static const bool one_stream = getenv("DSV1_DEC_ONE_STREAM") != nullptr;      // (A/B, as dsvg_pack_recons)
-        hipStream_t sp_ = c->st;
-        if (!one_stream && n >= 4 && !c->dec_pending.in_redo && !c->prof.mask && c->stx[1]) {
-            for (int i = 0; i < 2; i++) if (!c->ev_pack[i]) HIPCHK(hipEventCreateWithFlags(&c->ev_pack[i], hipEventDisableTiming));
-            if (c->pack_pending) HIPCHK(hipStreamWaitEvent(c->st, c->ev_pack[1], 0));      // (a second pass before the next decode call: keep the passes in order)
-            sp_ = c->stx[1];
-            HIPCHK(hipEventRecord(c->ev_pack[0], c->st));
-            HIPCHK(hipStreamWaitEvent(sp_, c->ev_pack[0], 0));
+    const int *tab = fmt ? pairs.data() : slots;
+    const size_t tab_bytes = sizeof(int) * (size_t)n * (fmt ? 2 : 1);
+    dsvg_ctx::DecPending &P = c->dec_pending;
+    if (!on_device) OPCHK(dec_resolve(c));              // (a flagged decoder call is repeated first)
+    else if (P.active && !P.in_redo && P.slots.empty()) {
+        // the first pass over a decoder call whose flags are not back yet: repeated by dec_resolve, as it was asked for, if need be
+        P.slots.assign(slots, slots + n);
+        P.index.assign(index, index + (fmt && index ? n : 0));
+        P.out = out; P.pitch = pitch;
+        P.has_fmt = fmt != nullptr;
+        if (fmt) P.fmt = *fmt;
+    } else if (P.active && !P.in_redo) OPCHK(dec_resolve(c));   // a second pass over the same call: settle it now
+    if (!c->otab_d) HIPCHK(hipMalloc((void **)&c->otab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
+    // One pass at a time: the first coding stream waits for the pass before, which keeps the passes in order and the table whole.
+    // Round 5: device output of four pictures or more goes to the second coding stream -- beside the next call's entropy decoding, which
+    // touches neither the reconstructions nor the caller's frames (70 us of a 620 us step of 64 pictures).  Whatever rewrites a
+    // reconstruction slot next waits for the pass (dsvg_decode_pictures, in front of its inverse transform); dsvg_ctx_sync waits for
+    // every stream.
+    OPCHK(join_pack(c));
+    static const bool one_stream = getenv("DSV1_DEC_ONE_STREAM") != nullptr;      // (A/B)
+    hipStream_t st = c->st;
+    if (on_device && !one_stream && n >= 4 && !P.in_redo && !c->prof.mask && c->stx[1]) {
+        for (int i = 0; i < 2; i++) if (!c->ev_pack[i]) HIPCHK(hipEventCreateWithFlags(&c->ev_pack[i], hipEventDisableTiming));
+        st = c->stx[1];
+        HIPCHK(hipEventRecord(c->ev_pack[0], c->st));
+        HIPCHK(hipStreamWaitEvent(st, c->ev_pack[0], 0));
+    }
+    HIPCHK(hipMemcpyAsync(c->otab_d, tab, tab_bytes, hipMemcpyHostToDevice, st));   // pageable: staged by the runtime
+    uint8_t *dst = (uint8_t *)out;
+    size_t dpitch = pitch, span = 0;
+    if (!on_device) {
+        // Host output goes through the stage.  Packed planar: frames at a 256-aligned pitch.  A format: the stage mirrors the caller's
+        // buffer, frame for frame at `pitch`; dense frames (no padding in or between them, every one written) come back with one copy,
+        // else the buffer goes up first, so that the copy back returns what the pass left alone
+        if (!fmt) dpitch = (fb + 255) & ~(size_t)255;
+        span = fmt ? pitch * (size_t)last + fmt->planes_bytes : dpitch * (size_t)n;
+        if (c->yuv_stage_bytes < span) {
+            if (c->yuv_stage) { HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipStreamSynchronize(c->st_a)); HIPCHK(hipStreamSynchronize(c->st_l)); (void)hipFree(c->yuv_stage); c->yuv_stage = nullptr; }
+            HIPCHK(hipMalloc((void **)&c->yuv_stage, span + 256));
+            c->yuv_stage_bytes = span;
         }
-        HIPCHK(hipMemcpyAsync(c->xtab_d, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, sp_));   // pageable: staged by the runtime
-        OPCHK(launch_pixout(sp_, fmt, S, c->recon.p, c->xtab_d, n, (uint8_t *)out, out_pitch, &c->prof));
-        if (sp_ != c->st) { HIPCHK(hipEventRecord(c->ev_pack[1], sp_)); c->pack_pending = true; }
-        HIPCHK(hipGetLastError());
-        return DSVG_OK;
+        dst = c->yuv_stage;
+        bool dense = fmt && !index && fmt->planes_bytes == pitch;
+        for (int s = 0; dense && s < fmt->nseg; s++) {
+            const dsvg_pixout_seg &G = fmt->seg[s];
+            const size_t end = s + 1 < fmt->nseg ? fmt->seg[s + 1].off : fmt->planes_bytes;
+            dense = G.off + G.pitch * (size_t)G.rows == end && (s ? true : G.off == 0) && (G.kind == DSVG_PIXOUT_PLAIN || G.kind == DSVG_PIXOUT_PAIR) &&
+                    G.pitch == (size_t)G.width * (fmt->wide ? 2 : 1) * (size_t)G.nin;
+        }
+        if (fmt && !dense) HIPCHK(hipMemcpyAsync(dst, out, span, hipMemcpyHostToDevice, st));
     }
-    if (c->pack_pending) { HIPCHK(hipStreamWaitEvent(c->st, c->ev_pack[1], 0)); c->pack_pending = false; }
-    HIPCHK(hipMemcpyAsync(c->xtab_d, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->st));
-    // the stage mirrors the caller's buffer, frame for frame at out_pitch.  Dense frames (no padding in or between them, every one
-    // written) come back with one copy; else the buffer goes up first, so that the copy back returns what the pass left alone
-    const size_t span = out_pitch * (size_t)last + fmt->planes_bytes;
-    bool dense = !out_index && fmt->planes_bytes == out_pitch;
-    for (int s = 0; s < fmt->nseg && dense; s++) {
-        const dsvg_pixout_seg &G = fmt->seg[s];
-        const size_t end = s + 1 < fmt->nseg ? fmt->seg[s + 1].off : fmt->planes_bytes;
-        dense = G.off + G.pitch * (size_t)G.rows == end && (s ? true : G.off == 0) && (G.kind == DSVG_PIXOUT_PLAIN || G.kind == DSVG_PIXOUT_PAIR) &&
-                G.pitch == (size_t)G.width * (fmt->wide ? 2 : 1) * (size_t)G.nin;
+    if (fmt) OPCHK(launch_pixout(st, fmt, S, c->recon.p, c->otab_d, n, dst, dpitch, &c->prof));
+    else launch_pack_n(st, dst, dpitch, c->recon.p, L, c->otab_d, n, &c->prof);
+    if (st != c->st) { HIPCHK(hipEventRecord(c->ev_pack[1], st)); c->pack_pending = true; }
+    if (!on_device) {
+        if (fmt) HIPCHK(hipMemcpyAsync(out, dst, span, hipMemcpyDeviceToHost, st));
+        else if (pitch == dpitch) HIPCHK(hipMemcpyAsync(out, dst, dpitch * (size_t)(n - 1) + fb, hipMemcpyDeviceToHost, st));
+        else HIPCHK(hipMemcpy2DAsync(out, pitch, dst, dpitch, fb, (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
-    if (c->yuv_stage_bytes < span) {
-        if (c->yuv_stage) { HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipStreamSynchronize(c->st_a)); HIPCHK(hipStreamSynchronize(c->st_l)); (void)hipFree(c->yuv_stage); c->yuv_stage = nullptr; }
-        HIPCHK(hipMalloc((void **)&c->yuv_stage, span + 256));
-        c->yuv_stage_bytes = span;
-    }
-    if (!dense) HIPCHK(hipMemcpyAsync(c->yuv_stage, out, span, hipMemcpyHostToDevice, c->st));
-    OPCHK(launch_pixout(c->st, fmt, S, c->recon.p, c->xtab_d, n, c->yuv_stage, out_pitch, &c->prof));
-    HIPCHK(hipMemcpyAsync(out, c->yuv_stage, span, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
     HIPCHK(hipGetLastError());
     return DSVG_OK;
+}
+
+extern "C" int dsvg_pack_recons(dsvg_ctx *c, int n, const int *recon_slots, void *yuv_out, size_t out_pitch, int out_on_device)
+{
+    return output_pass(c, n, recon_slots, nullptr, yuv_out, out_pitch, out_on_device, nullptr);
+}
+
+extern "C" int dsvg_export_recons(dsvg_ctx *c, int n, const int *recon_slots, const int *out_index, void *out, size_t out_pitch, int out_on_device,
+                                  const dsvg_pixout *fmt)
+{
+    if (!fmt) { dsvg_set_error("bad export_recons arguments"); return DSVG_ERR_ARG; }
+    return output_pass(c, n, recon_slots, out_index, out, out_pitch, out_on_device, fmt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2275,13 +2250,11 @@ static int dec_resolve(dsvg_ctx *c)
     P.in_redo = true;
     c->dec_redone++;
     std::vector<dsvg_dec_job> jobs = P.jobs;             // (decode_impl overwrites the pending record)
-    const bool pack = P.have_pack;
-    std::vector<int> slots = P.pack_slots; void *out = P.pack_out; const size_t pitch = P.pack_pitch;
-    const bool exported = P.pack_export;
-    std::vector<int> index = P.pack_index; const dsvg_pixout fmt = P.pack_fmt;
+    const std::vector<int> slots = P.slots, index = P.index;
+    void *out = P.out; const size_t pitch = P.pitch;
+    const bool has_fmt = P.has_fmt; const dsvg_pixout fmt = P.fmt;
     int rc = decode_impl(c, (int)jobs.size(), jobs.data(), true);
-    if (!rc && pack && exported) rc = dsvg_export_recons(c, (int)slots.size(), slots.data(), index.data(), out, pitch, 1, &fmt);
-    else if (!rc && pack) rc = dsvg_pack_recons(c, (int)slots.size(), slots.data(), out, pitch, 1);
+    if (!rc && !slots.empty()) rc = output_pass(c, (int)slots.size(), slots.data(), index.empty() ? nullptr : index.data(), out, pitch, 1, has_fmt ? &fmt : nullptr);
     P.in_redo = false;
     P.active = false;
     return rc;
@@ -2345,7 +2318,7 @@ static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool fo
     }
     dsvg_ctx::DecPending &P = c->dec_pending;
     const bool was_redo = P.in_redo;
-    if (!was_redo) { P.jobs.resize((size_t)njobs); P.have_pack = false; P.pack_export = false; }
+    if (!was_redo) { P.jobs.resize((size_t)njobs); P.slots.clear(); }
     int max_entries = 0, max_chunks = 0;
     size_t moff = 0;
     const CoefLayout &CL = c->CL;

@@ -363,28 +363,30 @@ int dsv1_decbatch_open(dsv1_decbatch **out, int device, const DSV_META *meta, in
     return DSVG_OK;
 }
 
+/* the output setters' tail: a format that was refused leaves the setting in force */
+static int set_output(dsv1_decbatch *d, int rc, const dsvg_pixout *F, int on)
+{
+    if (rc) return rc;
+    d->out_set = on;
+    d->out = *F;
+    return DSVG_OK;
+}
+
 int dsv1_decbatch_set_output_format(dsv1_decbatch *d, const dsv1_pix_format *pf, int out_subsamp)
 {
     dsvg_pixout F;
-    int rc;
     if (!d) return DSVG_ERR_ARG;
     if (!pf) { d->out_set = 0; return DSVG_OK; }
-    if ((rc = dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, &F))) return rc;     /* (the setting in force stays) */
-    d->out_set = !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp));
-    d->out = F;
-    return DSVG_OK;
+    return set_output(d, dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, &F), &F,
+                      !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp)));
 }
 
 int dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf)
 {
     dsvg_pixout F;
-    int rc;
     if (!d) return DSVG_ERR_ARG;
     if (!rf) { d->out_set = 0; return DSVG_OK; }
-    if ((rc = dsv1_rgbout_of(rf, d->meta.width, d->meta.height, d->meta.subsamp, &F))) return rc;     /* (the setting in force stays) */
-    d->out_set = 1;
-    d->out = F;
-    return DSVG_OK;
+    return set_output(d, dsv1_rgbout_of(rf, d->meta.width, d->meta.height, d->meta.subsamp, &F), &F, 1);
 }
 
 size_t dsv1_decbatch_out_frame_bytes(const dsv1_decbatch *d)
@@ -484,18 +486,14 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
         for (s = 0; s < n; s++) status[d->slots[s]] = DSV_DEC_ERROR;
         return rc;
     }
-    if (d->out_set) {                    /* one pass, straight into the caller's format: picture i to its stream's frame */
-        for (s = 0; s < n; s++) d->recs[s] = d->jobs[s].recon_slot;
+    for (s = 0; s < n; s++) d->recs[s] = d->jobs[s].recon_slot;
+    if (d->out_set)                      /* one pass, straight into the caller's format: picture i to its stream's frame */
         rc = dsvg_export_recons(d->ctx, n, d->recs, n == d->nstreams ? NULL : d->slots, yuv_out, out_pitch, out_on_device, &d->out);
-    } else if (n == d->nstreams) {
-        for (s = 0; s < n; s++) d->slots[s] = d->jobs[s].recon_slot;
-        rc = dsvg_pack_recons(d->ctx, n, d->slots, yuv_out, out_pitch, out_on_device);
-    } else {                             /* some streams had no picture this call: their output frames stay untouched */
-        rc = DSVG_OK;
-        for (s = 0; s < n && !rc; s++) {
-            const int st = d->slots[s], slot = d->jobs[s].recon_slot;
-            rc = dsvg_pack_recons(d->ctx, 1, &slot, (uint8_t *)yuv_out + (size_t)st * out_pitch, out_pitch, out_on_device);
-        }
+    else {                               /* packed planar writes picture i to frame i: one pass, or -- some streams had no picture this
+                                          * call, their output frames stay untouched -- one per picture, to its stream's frame */
+        const int per = n == d->nstreams ? n : 1;
+        for (s = 0, rc = DSVG_OK; s < n && !rc; s += per)
+            rc = dsvg_pack_recons(d->ctx, per, d->recs + s, (uint8_t *)yuv_out + (size_t)d->slots[s] * out_pitch, out_pitch, out_on_device);
     }
     if (rc) dsv1_log(1, "GPU pack failed: %s", dsvg_last_error());
     return rc;

@@ -27,6 +27,7 @@
 // odd-width packed row repeats the row's last luma sample.
 #include <algorithm>
 #include "dsvg_host.hpp"
+#include "dsvg_pixfmt.h"
 
 #define PO_THREADS 256
 
@@ -341,20 +342,6 @@ int launch_pixout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const
     return DSVG_OK;
 }
 
-namespace {
-struct PoScratch {                       // the standalone call's stream and staging: gone when it returns
-    hipStream_t st = nullptr;
-    void *s = nullptr, *d = nullptr;
-    ~PoScratch()
-    {
-        if (s) (void)hipFree(s);
-        if (d) (void)hipFree(d);
-        if (st) (void)hipStreamDestroy(st);
-        (void)hipGetLastError();
-    }
-};
-}
-
 extern "C" int dsvg_export_planar(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsvg_pixout *F, int on_device)
 {
     if (!src || !dst || !F || w < 1 || h < 1 || n < 1 || device < 0) { dsvg_set_error("bad export arguments"); return DSVG_ERR_ARG; }
@@ -365,24 +352,19 @@ extern "C" int dsvg_export_planar(int device, const void *src, int w, int h, int
     S.off[0] = 0; S.off[1] = (long long)w * h; S.off[2] = S.off[1] + (long long)cw * ch;
     S.fb = S.off[2] + (long long)cw * ch;
     if (pixout_check(F, S, F->frame_bytes)) { dsvg_set_error("the output format does not fit the frames"); return DSVG_ERR_ARG; }
-    if (dsvg_device_count() <= device) { dsvg_set_error("HIP device %d not present", device); (void)hipGetLastError(); return DSVG_ERR_NODEVICE; }
-    HIPCHK(hipSetDevice(device));
-    PoScratch X;
-    HIPCHK(hipStreamCreateWithFlags(&X.st, hipStreamNonBlocking));
+    // on a lane of the call's own (dsvg_pixfmt.h).  Host frames: the destination goes up as well, so that what the pass does not
+    // write comes back as it was
     const size_t sbytes = (size_t)S.fb * n, dbytes = F->frame_bytes * (size_t)(n - 1) + F->planes_bytes;   // (the last frame ends with its planes)
-    const uint8_t *s = (const uint8_t *)src;
-    uint8_t *d = (uint8_t *)dst;
-    if (!on_device) {
-        HIPCHK(hipMalloc(&X.s, sbytes + 256));
-        HIPCHK(hipMalloc(&X.d, dbytes + 256));
-        HIPCHK(hipMemcpy(X.s, src, sbytes, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(X.d, dst, dbytes, hipMemcpyHostToDevice));   // what the pass does not write comes back as it was
-        s = (const uint8_t *)X.s; d = (uint8_t *)X.d;
-    }
-    const int rc = launch_pixout(X.st, F, S, s, nullptr, n, d, F->frame_bytes, nullptr);
+    dsvg_lane *l = nullptr;
+    int rc = dsvg_lane_create(&l, device);
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(X.st));
-    if (!on_device) HIPCHK(hipMemcpy(dst, X.d, dbytes, hipMemcpyDeviceToHost));
-    return DSVG_OK;
+    void *s = const_cast<void *>(src), *d = dst;
+    if (!on_device && !(rc = dsvg_lane_upload(l, 0, src, sbytes, &s))) rc = dsvg_lane_upload(l, 1, dst, dbytes, &d);
+    if (!rc) rc = launch_pixout((hipStream_t)dsvg_lane_stream(l), F, S, (const uint8_t *)s, nullptr, n, (uint8_t *)d, F->frame_bytes, nullptr);
+    const hipError_t e = rc ? hipSuccess : hipGetLastError();
+    if (e != hipSuccess) { dsvg_set_error("the output pass could not be launched: %s", hipGetErrorString(e)); rc = DSVG_ERR_HIP; }
+    if (!rc && !on_device) rc = dsvg_lane_download(l, dst, d, dbytes);
+    if (!rc) rc = dsvg_lane_sync(l);
+    dsvg_lane_destroy(l);                               // (waits for the stream; frees the uploads)
+    return rc;
 }

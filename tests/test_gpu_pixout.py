@@ -296,6 +296,67 @@ def test_escape_redo_keeps_the_format(pkg, orc):
         d.close()
 
 
+@pytest.mark.parametrize("setting", ["nv12-420", None])
+def test_escape_redo_of_a_call_in_which_some_streams_have_no_picture(pkg, orc, setting):
+    """the pass recorded with a call that is decoded again is replayed as it was asked for, also where only streams 0 and 2 of four
+    had a picture: NV12 at 4:2:0 is one export with the frame indices {0, 2}; packed planar is one pass per picture, of which the
+    second settles the call (the first is replayed behind the redo, the second still has to be written).  The frames of streams 1
+    and 3 keep the sentinel, byte for byte"""
+    w, h, fmt, S = 352, 288, A.SUBSAMP_444, 4
+    pk, ip = _two_picture_stream(w, h, fmt, 0xE5CA9E)
+    b2, sw2 = region_base(w, h, 2, 1)
+    b1, sw1 = region_base(w, h, 1, 2)
+    entries = sorted([(5, 3), (b1 + 4 * sw1 + 9, -2), (b2 + 10 * sw2 + 10, 40000), (b2 + 30 * sw2 + 77, 1)])
+    pk[ip] = splice(pk[ip], {0: plane_payload(7, entries)})
+    want = A.orc_decode(b"".join(pk), w, h, fmt)
+    assert len(want) == 2
+    eos = bytes(pk[-1])
+    assert len(eos) == 14 and not (eos[5] & 4)
+    ii = [i for i, p in enumerate(pk) if p[5] & 4][0]
+    assert ii < ip
+    L = pkg.lib()
+    L.dsvg_ctx_decoder_redone.restype = C.c_long
+    L.dsvg_ctx_decoder_redone.argtypes = [C.c_void_p]
+    nv12 = PF.pf(PF.SEMI_UV)
+
+    def expected(t):
+        if setting is None:
+            return want[t].reshape(-1)
+        return PO.export(want[t][None], nv12, w, h, fmt, A.SUBSAMP_420, 1).reshape(-1)
+
+    d = pkg.DecBatch(w, h, fmt, S)
+    try:
+        if setting is not None:
+            d.set_output_format(cpf(pkg, nv12), A.SUBSAMP_420)
+        dev = d.dev_alloc()
+        # first call: the I picture to all four streams
+        before = L.dsvg_ctx_decoder_redone(d.ctx)
+        _, status, fnum = d.decode([pk[ii]] * S, out=dev, on_device=True)
+        assert status == [0] * S
+        first = d.download(dev)
+        for s in range(S):
+            assert np.array_equal(first[s], expected(0)), "I picture, stream %d" % s
+        assert L.dsvg_ctx_decoder_redone(d.ctx) - before == 0
+        # between the calls: everything settled, a sentinel over the whole buffer
+        d.sync()
+        sentinel = np.random.default_rng(0x5E71).integers(0, 256, (S, d.frame_bytes), dtype=np.uint8)
+        assert L.dsvg_dev_upload(d.ctx, dev, sentinel.ctypes.data, sentinel.nbytes) == 0
+        d.sync()
+        # second call: the P picture with its symbol beyond int16 to streams 0 and 2, end of stream to 1 and 3
+        before = L.dsvg_ctx_decoder_redone(d.ctx)
+        _, status, fnum = d.decode([pk[ip], eos, pk[ip], eos], out=dev, on_device=True)
+        assert status[0] == 0 and status[2] == 0 and status[1] in (2, 3) and status[3] in (2, 3)
+        frames = d.download(dev)
+        exp = expected(1)
+        for s in (0, 2):
+            assert np.array_equal(frames[s], exp), "stream %d: first difference at %s" % (s, np.argwhere(frames[s] != exp)[:3].ravel())
+        for s in (1, 3):
+            assert np.array_equal(frames[s], sentinel[s]), "stream %d: its frame was written at %s" % (s, np.argwhere(frames[s] != sentinel[s])[:3].ravel())
+        assert L.dsvg_ctx_decoder_redone(d.ctx) - before == 1
+    finally:
+        d.close()
+
+
 def test_refusals(pkg, orc):
     w, h, fmt = 352, 288, A.SUBSAMP_420
     L = pkg.lib()
