@@ -120,10 +120,12 @@ def lib():
         L.dsv1_batch_set_fnum.argtypes = [_C.c_void_p, _C.c_int, _C.c_uint32]
         L.dsv1_batch_dropped_recons.restype = _C.c_long
         L.dsv1_batch_recon_all.argtypes = [_C.c_void_p, _C.c_int]
-        L.dsv1_batch_sse_enable.argtypes = [_C.c_void_p, _C.c_int]
-        L.dsv1_batch_get_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
-        L.dsv1_batch_ssim_enable.argtypes = [_C.c_void_p, _C.c_int]
-        L.dsv1_batch_get_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
+        for f in ("batch_sse", "batch_ssim", "resladder_sse", "resladder_ssim"):
+            getattr(L, "dsv1_%s_enable" % f).argtypes = [_C.c_void_p, _C.c_int]
+        for f in ("batch_get_sse", "resladder_get_sse", "resladder_get_src_sse"):        # the quality figures (_figures): SSE uint64,
+            getattr(L, "dsv1_" + f).argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
+        for f in ("batch_get_ssim", "resladder_get_ssim", "resladder_get_src_ssim"):     # SSIM_FX int64
+            getattr(L, "dsv1_" + f).argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
         L.dsv1_batch_dropped_recons.argtypes = [_C.c_void_p, _C.POINTER(_C.c_long)]
         L.dsv1_batch_encode.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
         L.dsv1_batch_submit.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
@@ -192,17 +194,11 @@ def lib():
             getattr(L, "dsv1_resladder_" + f).argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.POINTER(Buf)]
         L.dsv1_resladder_collect.argtypes = [_C.c_void_p, _C.POINTER(Buf)]
         L.dsv1_resladder_eos.argtypes = [_C.c_void_p, _C.c_int, _C.POINTER(Buf)]
-        L.dsv1_resladder_sse_enable.argtypes = [_C.c_void_p, _C.c_int]
-        L.dsv1_resladder_ssim_enable.argtypes = [_C.c_void_p, _C.c_int]
-        L.dsv1_resladder_get_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
-        L.dsv1_resladder_get_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
         L.dsv1_resladder_uploads.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.POINTER(_C.c_long)]
         L.dsv1_resample_taps.argtypes = [_C.c_int, _C.c_int, _C.c_int]
         L.dsv1_resample_weights.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_int]
         L.dsv1_resample_clip.argtypes = L.dsv1_scale_clip.argtypes
         L.dsv1_resladder_src_quality_enable.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int]
-        L.dsv1_resladder_get_src_sse.argtypes = [_C.c_void_p, _C.POINTER(_C.c_uint64), _C.c_size_t]
-        L.dsv1_resladder_get_src_ssim.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int64), _C.c_size_t]
         L.dsv1_pix_frame_bytes.restype = _C.c_size_t
         L.dsv1_pix_frame_bytes.argtypes = [_C.POINTER(PixFormat), _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_convert_clip.argtypes = [_C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int]
@@ -418,14 +414,11 @@ class Batch:
         """measure the pictures of the batches submitted from now on (on) / stop measuring (off); between batches only.
         The packets are the same either way (include/dsv1_api.h, dsv1_batch_sse_enable)"""
         _chk(self.L.dsv1_batch_sse_enable(self.h, 1 if on else 0), "dsv1_batch_sse_enable")
-        self._sse_on = bool(on)
 
     def sse(self):
         """the batch collected last: per stream, frame (submitted order) and plane Y, U, V the exact sum of squared errors
         source vs reconstruction over the picture area -> numpy.uint64 [nstreams, F, 3].  Raises if it was not measured."""
-        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.uint64)
-        _chk(self.L.dsv1_batch_get_sse(self.h, out.ctypes.data_as(_C.POINTER(_C.c_uint64)), out.size), "dsv1_batch_get_sse")
-        return out
+        return _figures(self.L.dsv1_batch_get_sse, self.h, (self.nstreams, self.F, 3), _np.uint64)
 
     def psnr(self):
         """the same as PSNR in dB, float64 [nstreams, F, 4]: planes Y, U, V, then the whole picture (inf where SSE is 0)"""
@@ -439,9 +432,7 @@ class Batch:
     def ssim_fx(self):
         """the batch collected last: per stream, frame (submitted order) and plane Y, U, V the exact fixed-point SSIM -- the sum over
         the plane's 8x8 windows at stride 4 of rint(2^32 SSIM) -> numpy.int64 [nstreams, F, 3].  Raises if it was not measured."""
-        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.int64)
-        _chk(self.L.dsv1_batch_get_ssim(self.h, out.ctypes.data_as(_C.POINTER(_C.c_int64)), out.size), "dsv1_batch_get_ssim")
-        return out
+        return _figures(self.L.dsv1_batch_get_ssim, self.h, (self.nstreams, self.F, 3), _np.int64)
 
     def ssim(self):
         """the same as mean SSIM, float64 [nstreams, F, 4]: planes Y, U, V, then the whole picture (weighted by window count)"""
@@ -992,14 +983,11 @@ class ResLadder:
 
     def sse(self):
         """numpy.uint64 [nstreams, F, 3] of the call collected last (against each stream's scaled source)"""
-        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.uint64)
-        _chk(self.L.dsv1_resladder_get_sse(self.h, out.ctypes.data_as(_C.POINTER(_C.c_uint64)), out.size), "dsv1_resladder_get_sse")
-        return out
+        return _figures(self.L.dsv1_resladder_get_sse, self.h, (self.nstreams, self.F, 3), _np.uint64)
 
     def ssim_fx(self):
-        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.int64)
-        _chk(self.L.dsv1_resladder_get_ssim(self.h, out.ctypes.data_as(_C.POINTER(_C.c_int64)), out.size), "dsv1_resladder_get_ssim")
-        return out
+        """numpy.int64 [nstreams, F, 3] of the call collected last (against each stream's scaled source)"""
+        return _figures(self.L.dsv1_resladder_get_ssim, self.h, (self.nstreams, self.F, 3), _np.int64)
 
     def psnr(self):
         """float64 [nstreams, F, 4] in dB, each stream at its own geometry"""
@@ -1018,15 +1006,11 @@ class ResLadder:
 
     def src_sse(self):
         """numpy.uint64 [nstreams, F, 3] of the call collected last, over the source's plane areas"""
-        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.uint64)
-        _chk(self.L.dsv1_resladder_get_src_sse(self.h, out.ctypes.data_as(_C.POINTER(_C.c_uint64)), out.size), "dsv1_resladder_get_src_sse")
-        return out
+        return _figures(self.L.dsv1_resladder_get_src_sse, self.h, (self.nstreams, self.F, 3), _np.uint64)
 
     def src_ssim_fx(self):
         """numpy.int64 [nstreams, F, 3]: SSIM_FX over the windows of the source's plane dims"""
-        out = _np.zeros((self.nstreams, self.F, 3), dtype=_np.int64)
-        _chk(self.L.dsv1_resladder_get_src_ssim(self.h, out.ctypes.data_as(_C.POINTER(_C.c_int64)), out.size), "dsv1_resladder_get_src_ssim")
-        return out
+        return _figures(self.L.dsv1_resladder_get_src_ssim, self.h, (self.nstreams, self.F, 3), _np.int64)
 
     def src_psnr(self):
         """float64 [nstreams, F, 4] in dB, every stream at the source geometry"""
@@ -1184,6 +1168,14 @@ def plane_samples(w, h, fmt):
     """samples of the planes Y, U, V of a w x h picture in DSV_SUBSAMP_* format fmt (chroma rounded up, as the codec sizes it)"""
     c = _chroma_size(w, h, fmt)
     return w * h, c, c
+
+
+def _figures(getter, handle, shape, dtype):
+    """one kind of quality figure of the batch or call collected last (handle: a Batch's, a ResLadder's) through the library's getter
+    for it -> numpy array of that shape and dtype (SSE uint64, SSIM_FX int64).  Raises if it was not measured."""
+    out = _np.zeros(shape, dtype=dtype)
+    _chk(getter(handle, out.ctypes.data_as(_C.POINTER(_np.ctypeslib.as_ctypes_type(dtype))), out.size), getter.__name__)
+    return out
 
 
 def psnr_db(sse, w, h, fmt):

@@ -179,24 +179,21 @@ struct dsvg_ctx {
     uint8_t *stable = nullptr;
     JobDev *jobs_d = nullptr, *jobs_h = nullptr;
     std::vector<char> slot_isP;      // per out slot: the picture coded into it last was a P picture (dsvg_fetch_pictures' fast path)
-    // quality measurement (dsvg_ctx_sse_enable, k_quality.hip): per out slot the three planes' sums of squared errors source vs
-    // reconstruction, and whether the picture coded into the slot last was measured.  Allocated when first switched on.
-    bool sse_on = false;
-    unsigned long long *sse_d = nullptr, *sse_h = nullptr;   // [out_slots][3] device / pinned host
-    std::vector<char> slot_sse;
-    // the same for SSIM (dsvg_ctx_ssim_enable): per out slot the three planes' fixed-point window sums (int64 as two's complement)
-    bool ssim_on = false;
-    unsigned long long *ssim_d = nullptr, *ssim_h = nullptr; // [out_slots][3] device / pinned host
-    std::vector<char> slot_ssim;
-    // source-resolution quality (dsvg_ctx_xres_enable, k_xres_quality): the reference geometry's upscale tables, per out slot the
-    // reference frame the next call measures against (xref_next, set by dsvg_ctx_xres_refs and consumed by the call that codes the
-    // slot; its pinned staging and device copy xref_h / xref_d), the sums, and whether the picture coded into the slot last was measured
-    bool xsse_on = false, xssim_on = false;
+    // quality measurements (k_quality.hip), one record per kind: DSVG_Q_SSE / DSVG_Q_SSIM of the pictures as coded (dsvg_ctx_sse_enable,
+    // dsvg_ctx_ssim_enable), DSVG_Q_XSSE / DSVG_Q_XSSIM of the reconstruction upscaled to the reference geometry (dsvg_ctx_xres_enable).
+    // Per out slot the three planes' sums -- squared errors, or SSIM's fixed-point window sums (int64 as two's complement) -- and
+    // whether the picture coded into the slot last was measured.  Allocated when the kind is first switched on.
+    struct Quality {
+        bool on = false;
+        unsigned long long *dev = nullptr, *host = nullptr;  // [out_slots][3] device / pinned host
+        std::vector<char> measured;                          // [out_slots], sized with the tables
+    } q[DSVG_Q_KINDS];
+    // source-resolution quality: the reference geometry's upscale tables, per out slot the reference frame the next call measures
+    // against (xref_next, set by dsvg_ctx_xres_refs and consumed by the call that codes the slot; its pinned staging and device
+    // copy xref_h / xref_d)
     XresGeo xg;
-    unsigned long long *xsse_d = nullptr, *xsse_h = nullptr, *xssim_d = nullptr, *xssim_h = nullptr;
     const uint8_t **xref_d = nullptr, **xref_h = nullptr;
     std::vector<const uint8_t *> xref_next;
-    std::vector<char> slot_xsse, slot_xssim;
     // device-resident rate control (dsvg_code_batch_rc): per-stream state, per-job tables (indexed like jobs_h / jobs_d)
     dsvg_rc_state *rc_state_d = nullptr;
     RcJobDev *rcj_d = nullptr, *rcj_h = nullptr;
@@ -426,10 +423,11 @@ static void ctx_free(dsvg_ctx *c)
     c->recon.release(); c->xf.release(); c->pred.release();
     xres_geo_free(c->xg);
     void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, c->sse_d, c->ssim_d, c->xsse_d, c->xssim_d, (void *)c->xref_d};
+                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, (void *)c->xref_d};
     for (void *p : d) if (p) (void)hipFree(p);
-    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, c->sse_h, c->ssim_h, c->xsse_h, c->xssim_h, (void *)c->xref_h};
+    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, (void *)c->xref_h};
     for (void *p : hh) if (p) (void)hipHostFree(p);
+    for (auto &q : c->q) { if (q.dev) (void)hipFree(q.dev); if (q.host) (void)hipHostFree(q.host); }
     if (c->st) (void)hipStreamDestroy(c->st);
     for (int i = 0; i < 2; i++) if (c->ev_mark[i]) (void)hipEventDestroy(c->ev_mark[i]);
     if (c->st_l && c->st_l != c->st_a) (void)hipStreamDestroy(c->st_l);
@@ -1353,9 +1351,9 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
                 if (rcj[k].rc_slot == rcj[i].rc_slot) { dsvg_set_error("two pictures of one rate-controlled stream in one frame step (jobs %d, %d)", k, i); return DSVG_ERR_ARG; }
         }
     HIPCHK(hipSetDevice(c->device));
-    const bool sse = c->sse_on;                              // quality measurement of this call's pictures (dsvg_ctx_sse_enable)
-    const bool ssim = c->ssim_on;                            // (dsvg_ctx_ssim_enable)
-    const bool xres = c->xsse_on || c->xssim_on;             // (dsvg_ctx_xres_enable)
+    const bool sse = c->q[DSVG_Q_SSE].on;                         // quality measurement of this call's pictures (dsvg_ctx_sse_enable)
+    const bool ssim = c->q[DSVG_Q_SSIM].on;                       // (dsvg_ctx_ssim_enable)
+    const bool xres = c->q[DSVG_Q_XSSE].on || c->q[DSVG_Q_XSSIM].on;   // (dsvg_ctx_xres_enable)
     static const bool cprof = getenv("DSV1_HOST_PROF") != nullptr;
     const auto cnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = cprof ? cnow() : 0.0;
@@ -1451,19 +1449,16 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             dj[(size_t)t * njobs + k] = &j;
             if (c->slot_isP.size() != (size_t)c->out_slots) c->slot_isP.assign((size_t)c->out_slots, 0);
             c->slot_isP[(size_t)j.out_slot] = (char)isP;
-            if (c->slot_sse.size() != (size_t)c->out_slots) c->slot_sse.assign((size_t)c->out_slots, 0);
-            c->slot_sse[(size_t)j.out_slot] = (char)sse;
-            if (c->slot_ssim.size() != (size_t)c->out_slots) c->slot_ssim.assign((size_t)c->out_slots, 0);
-            c->slot_ssim[(size_t)j.out_slot] = (char)ssim;
+            const uint8_t *xr = nullptr;
             if (xres) {
                 // the reference frame dsvg_ctx_xres_refs set for the slot, taken by this call (none: the picture is not measured)
-                const uint8_t *r = c->xref_next[(size_t)j.out_slot];
+                xr = c->xref_next[(size_t)j.out_slot];
                 c->xref_next[(size_t)j.out_slot] = nullptr;
-                c->xref_h[j.out_slot] = r;
-                c->slot_xsse[(size_t)j.out_slot] = (char)(c->xsse_on && r);
-                c->slot_xssim[(size_t)j.out_slot] = (char)(c->xssim_on && r);
-            } else if (!c->slot_xsse.empty()) {
-                c->slot_xsse[(size_t)j.out_slot] = c->slot_xssim[(size_t)j.out_slot] = 0;
+                c->xref_h[j.out_slot] = xr;
+            }
+            for (int kind = 0; kind < DSVG_Q_KINDS; kind++) {
+                dsvg_ctx::Quality &q = c->q[kind];
+                if (!q.measured.empty()) q.measured[(size_t)j.out_slot] = (char)(q.on && (kind < DSVG_Q_XSSE || xr));
             }
             if (rcj) dpos[(size_t)t * njobs + order[k]] = k;
             if (isP && !c->mc_fused) noint[NG * t + g] = 0;
@@ -1600,12 +1595,10 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
     }
     HIPCHK(hipMemcpyAsync(c->slots_d + 2 * c->out_slots + base, c->slots_h + base, sizeof(int) * total, hipMemcpyHostToDevice, c->st));
     // the measurements' sums of the call's out slots start at zero (k_sse / k_ssim add into them); before the fork: every coding stream is behind it
-    if (sse) HIPCHK(hipMemsetAsync(c->sse_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
-    if (ssim) HIPCHK(hipMemsetAsync(c->ssim_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
-    if (xres) {
-        HIPCHK(hipMemcpyAsync(c->xref_d + base, c->xref_h + base, sizeof(const uint8_t *) * total, hipMemcpyHostToDevice, c->st));
-        if (c->xsse_on) HIPCHK(hipMemsetAsync(c->xsse_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
-        if (c->xssim_on) HIPCHK(hipMemsetAsync(c->xssim_d + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
+    for (int kind = 0; kind < DSVG_Q_KINDS; kind++) {
+        // (the reference frames of the call's out slots go up between the two pairs of kinds, where they always did)
+        if (kind == DSVG_Q_XSSE && xres) HIPCHK(hipMemcpyAsync(c->xref_d + base, c->xref_h + base, sizeof(const uint8_t *) * total, hipMemcpyHostToDevice, c->st));
+        if (c->q[kind].on) HIPCHK(hipMemsetAsync(c->q[kind].dev + (size_t)3 * base, 0, sizeof(unsigned long long) * 3 * (size_t)total, c->st));
     }
     tl_mark(c, c->st, "code0");
     if (NG > 1) {
@@ -1668,10 +1661,10 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             bool keeps = sse || ssim || xres;
             for (int k = k0; k < k0 + n && !keeps; k++) keeps = dj[(size_t)t * njobs + k]->recon_slot >= 0;
             if (keeps) OPCHK(enqueue_recon(c, nI, n, d0, 7, st, true, c->llq));
-            if (ssim) launch_ssim(st, jd, n, c->L[0], c->psum, c->ssim_d, sse ? c->sse_d : nullptr);
-            else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->sse_d);
+            if (ssim) launch_ssim(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSIM].dev, sse ? c->q[DSVG_Q_SSE].dev : nullptr);
+            else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSE].dev);
             // (the same place and ordering argument: the reconstruction upscaled to the reference geometry, k_xres_quality)
-            if (xres) launch_xres(st, jd, n, c->L[0], c->xg, c->xref_d, c->psum, c->xsse_on ? c->xsse_d : nullptr, c->xssim_on ? c->xssim_d : nullptr);
+            if (xres) launch_xres(st, jd, n, c->L[0], c->xg, c->xref_d, c->psum, c->q[DSVG_Q_XSSE].on ? c->q[DSVG_Q_XSSE].dev : nullptr, c->q[DSVG_Q_XSSIM].on ? c->q[DSVG_Q_XSSIM].dev : nullptr);
             launch_hz_pack(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
             // rate control: the sizes of these packets -> the quantiser tables of the same streams' pictures of the next step
             if (rcj) launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, d0, n, 1);
@@ -1917,27 +1910,31 @@ extern "C" int dsvg_fetch_pictures_cb(dsvg_ctx *c, int n, const int *out_slots, 
     return DSVG_OK;
 }
 
-// the two measurements' switches and fetches (dsvg_ctx_sse_enable / dsvg_fetch_sse, dsvg_ctx_ssim_enable / dsvg_fetch_ssim): per out
-// slot three 64-bit sums on the device (dev), a pinned copy (host) and whether the picture coded into the slot last was measured
-static int quality_enable(dsvg_ctx *c, bool &flag, unsigned long long *&dev, unsigned long long *&host, int on)
+// the measurements' switches and fetches, by kind: per out slot three 64-bit sums on the device, a pinned copy and whether the
+// picture coded into the slot last was measured (dsvg_ctx::Quality)
+static int quality_enable(dsvg_ctx *c, int kind, int on)
 {
-    if (on && !dev) {                           // (every call zeroes the sums of its out slots itself)
+    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
+    dsvg_ctx::Quality &q = c->q[kind];
+    if (on && !q.dev) {                         // (every call zeroes the sums of its out slots itself)
         HIPCHK(hipSetDevice(c->device));
-        OPCHK(dmalloc(&dev, (size_t)3 * c->out_slots, false));
-        OPCHK(hmalloc(&host, (size_t)3 * c->out_slots));
+        q.measured.assign((size_t)c->out_slots, 0);             // (first: sized wherever a table exists)
+        OPCHK(dmalloc(&q.dev, (size_t)3 * c->out_slots, false));
+        OPCHK(hmalloc(&q.host, (size_t)3 * c->out_slots));
     }
-    flag = on != 0;
+    q.on = on != 0;
     return DSVG_OK;
 }
 
-static int quality_fetch(dsvg_ctx *c, const char *what, const unsigned long long *dev, unsigned long long *host,
-                         const std::vector<char> &measured, int n, const int *out_slots, void *out)
+static int quality_fetch(dsvg_ctx *c, int kind, const char *what, int n, const int *out_slots, void *out)
 {
+    if (!c || n < 0 || (n > 0 && (!out_slots || !out))) { dsvg_set_error("bad %s arguments", what); return DSVG_ERR_ARG; }
+    dsvg_ctx::Quality &q = c->q[kind];
     int lo = c->out_slots, hi = -1;
     for (int i = 0; i < n; i++) {
         const int s = out_slots[i];
         if (s < 0 || s >= c->out_slots) { dsvg_set_error("%s: out slot %d out of range", what, s); return DSVG_ERR_ARG; }
-        if (!dev || (size_t)s >= measured.size() || !measured[(size_t)s]) {
+        if (!q.dev || !q.host || !q.measured[(size_t)s]) {
             dsvg_set_error("%s: the picture in out slot %d was coded with the measurement off", what, s); return DSVG_ERR_ARG;
         }
         lo = std::min(lo, s); hi = std::max(hi, s);
@@ -1950,40 +1947,29 @@ static int quality_fetch(dsvg_ctx *c, const char *what, const unsigned long long
         const int e = c->slot_ev[(size_t)out_slots[i]];
         if (e >= 0 && !seen[(size_t)e]) { seen[(size_t)e] = 1; HIPCHK(hipStreamWaitEvent(c->st_c, c->ev_coded[(size_t)e], 0)); }
     }
-    HIPCHK(hipMemcpyAsync(host + (size_t)3 * lo, dev + (size_t)3 * lo, sizeof(unsigned long long) * 3 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, c->st_c));
+    HIPCHK(hipMemcpyAsync(q.host + (size_t)3 * lo, q.dev + (size_t)3 * lo, sizeof(unsigned long long) * 3 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, c->st_c));
     HIPCHK(hipStreamSynchronize(c->st_c));
-    for (int i = 0; i < n; i++) memcpy((unsigned long long *)out + (size_t)3 * i, host + (size_t)3 * out_slots[i], 3 * sizeof(unsigned long long));
+    for (int i = 0; i < n; i++) memcpy((unsigned long long *)out + (size_t)3 * i, q.host + (size_t)3 * out_slots[i], 3 * sizeof(unsigned long long));
     return DSVG_OK;
 }
 
-extern "C" int dsvg_ctx_sse_enable(dsvg_ctx *c, int on)
-{
-    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
-    return quality_enable(c, c->sse_on, c->sse_d, c->sse_h, on);
-}
+extern "C" int dsvg_ctx_sse_enable(dsvg_ctx *c, int on) { return quality_enable(c, DSVG_Q_SSE, on); }
+extern "C" int dsvg_ctx_ssim_enable(dsvg_ctx *c, int on) { return quality_enable(c, DSVG_Q_SSIM, on); }
+extern "C" int dsvg_fetch_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out) { return quality_fetch(c, DSVG_Q_SSE, "dsvg_fetch_sse", n, out_slots, sse_out); }
+extern "C" int dsvg_fetch_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t *ssim_out) { return quality_fetch(c, DSVG_Q_SSIM, "dsvg_fetch_ssim", n, out_slots, ssim_out); }
+extern "C" int dsvg_fetch_xres_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out) { return quality_fetch(c, DSVG_Q_XSSE, "dsvg_fetch_xres_sse", n, out_slots, sse_out); }
+extern "C" int dsvg_fetch_xres_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t *ssim_out) { return quality_fetch(c, DSVG_Q_XSSIM, "dsvg_fetch_xres_ssim", n, out_slots, ssim_out); }
 
-extern "C" int dsvg_fetch_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out)
+extern "C" int dsvg_fetch_quality(dsvg_ctx *c, int kind, int n, const int *out_slots, uint64_t *out)
 {
-    if (!c || n < 0 || (n > 0 && (!out_slots || !sse_out))) { dsvg_set_error("bad dsvg_fetch_sse arguments"); return DSVG_ERR_ARG; }
-    return quality_fetch(c, "dsvg_fetch_sse", c->sse_d, c->sse_h, c->slot_sse, n, out_slots, sse_out);
-}
-
-extern "C" int dsvg_ctx_ssim_enable(dsvg_ctx *c, int on)
-{
-    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
-    return quality_enable(c, c->ssim_on, c->ssim_d, c->ssim_h, on);
-}
-
-extern "C" int dsvg_fetch_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t *ssim_out)
-{
-    if (!c || n < 0 || (n > 0 && (!out_slots || !ssim_out))) { dsvg_set_error("bad dsvg_fetch_ssim arguments"); return DSVG_ERR_ARG; }
-    return quality_fetch(c, "dsvg_fetch_ssim", c->ssim_d, c->ssim_h, c->slot_ssim, n, out_slots, ssim_out);
+    if (kind < 0 || kind >= DSVG_Q_KINDS) { dsvg_set_error("dsvg_fetch_quality: bad kind %d", kind); return DSVG_ERR_ARG; }
+    return quality_fetch(c, kind, "dsvg_fetch_quality", n, out_slots, out);
 }
 
 extern "C" int dsvg_ctx_xres_enable(dsvg_ctx *c, int sse_on, int ssim_on, int ref_w, int ref_h, int filter)
 {
     if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
-    if (!sse_on && !ssim_on) { c->xsse_on = c->xssim_on = false; return DSVG_OK; }     // (the tables stay for the next switch-on)
+    if (!sse_on && !ssim_on) { c->q[DSVG_Q_XSSE].on = c->q[DSVG_Q_XSSIM].on = false; return DSVG_OK; }     // (the tables stay for the next switch-on)
     if (filter != 0 && filter != 1) { dsvg_set_error("dsvg_ctx_xres_enable: bad filter %d", filter); return DSVG_ERR_ARG; }
     if (ref_w < 1 || ref_h < 1) { dsvg_set_error("dsvg_ctx_xres_enable: bad reference geometry"); return DSVG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
@@ -1996,15 +1982,9 @@ extern "C" int dsvg_ctx_xres_enable(dsvg_ctx *c, int sse_on, int ssim_on, int re
         OPCHK(dmalloc(&c->xref_d, (size_t)c->out_slots, true));
         OPCHK(hmalloc(&c->xref_h, (size_t)c->out_slots));
         c->xref_next.assign((size_t)c->out_slots, nullptr);
-        c->slot_xsse.assign((size_t)c->out_slots, 0);
-        c->slot_xssim.assign((size_t)c->out_slots, 0);
     }
-    bool on = false;
-    OPCHK(quality_enable(c, on, c->xsse_d, c->xsse_h, sse_on));
-    OPCHK(quality_enable(c, on, c->xssim_d, c->xssim_h, ssim_on));
-    c->xsse_on = sse_on != 0;
-    c->xssim_on = ssim_on != 0;
-    return DSVG_OK;
+    OPCHK(quality_enable(c, DSVG_Q_XSSE, sse_on));
+    return quality_enable(c, DSVG_Q_XSSIM, ssim_on);
 }
 
 extern "C" int dsvg_ctx_xres_refs(dsvg_ctx *c, const void *ref_clip, int n, const int *out_slots, const int *frames)
@@ -2016,18 +1996,6 @@ extern "C" int dsvg_ctx_xres_refs(dsvg_ctx *c, const void *ref_clip, int n, cons
     for (int i = 0; i < n; i++)
         c->xref_next[(size_t)out_slots[i]] = ref_clip ? (const uint8_t *)ref_clip + (size_t)frames[i] * c->xg.rfb : nullptr;
     return DSVG_OK;
-}
-
-extern "C" int dsvg_fetch_xres_sse(dsvg_ctx *c, int n, const int *out_slots, uint64_t *sse_out)
-{
-    if (!c || n < 0 || (n > 0 && (!out_slots || !sse_out))) { dsvg_set_error("bad dsvg_fetch_xres_sse arguments"); return DSVG_ERR_ARG; }
-    return quality_fetch(c, "dsvg_fetch_xres_sse", c->xsse_d, c->xsse_h, c->slot_xsse, n, out_slots, sse_out);
-}
-
-extern "C" int dsvg_fetch_xres_ssim(dsvg_ctx *c, int n, const int *out_slots, int64_t *ssim_out)
-{
-    if (!c || n < 0 || (n > 0 && (!out_slots || !ssim_out))) { dsvg_set_error("bad dsvg_fetch_xres_ssim arguments"); return DSVG_ERR_ARG; }
-    return quality_fetch(c, "dsvg_fetch_xres_ssim", c->xssim_d, c->xssim_h, c->slot_xssim, n, out_slots, ssim_out);
 }
 
 extern "C" int dsvg_fetch_pictures(dsvg_ctx *c, int n, const int *out_slots, dsvg_pic_out *outs)

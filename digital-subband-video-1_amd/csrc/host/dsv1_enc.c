@@ -94,23 +94,11 @@ struct dsv1_batch {
     /* Quality measurement (dsv1_batch_sse_enable): the device sums the squared errors of every picture per plane into its out slot
      * (dsvg_ctx_sse_enable).  The two batches in flight use the two halves of the out slots, so batch i's sums stay on the device
      * until its collect copies them here, whatever batch i+1 does meanwhile; a remedied picture (remedy_dropped) is coded into the
-     * half of the batch being submitted, whose own call zeroes those sums again before it codes its pictures. */
-    int sse_on;
-    int sse_sub[2];                  /* per pending slot: its batch was submitted with the measurement on */
-    uint64_t *sse;                   /* [nstreams][frames][3] of the batch collected last */
-    size_t sse_n;                    /* values in sse; 0 = that batch was not measured (or nothing has been collected) */
-    /* SSIM (dsv1_batch_ssim_enable): the same bookkeeping, its own switch (dsvg_ctx_ssim_enable) */
-    int ssim_on;
-    int ssim_sub[2];
-    int64_t *ssim;                   /* [nstreams][frames][3] fixed-point SSIM of the batch collected last */
-    size_t ssim_n;
-    /* source-resolution figures (dsv1_batch_xres_enable): the same bookkeeping per measure, and the reference clip of the next submit */
-    int xsse_on, xssim_on;
-    int xsse_sub[2], xssim_sub[2];
-    const void *xres_clip;
-    uint64_t *xsse;
-    int64_t *xssim;
-    size_t xsse_n, xssim_n;
+     * half of the batch being submitted, whose own call zeroes those sums again before it codes its pictures.
+     * SSIM (dsv1_batch_ssim_enable) and the two source-resolution figures (dsv1_batch_xres_enable) keep the same record, one per
+     * kind (DSVG_Q_*).  A switch is refused with batches in flight, so `on` at a batch's collect is what its submit saw. */
+    dsv1_quality q[DSVG_Q_KINDS];
+    const void *xres_clip;           /* source-resolution figures: the reference clip of the next submit */
     /* the passes in front of the encoder (dsv1_batch_set_source_format / _rgb / _deinterlace / _denoise) and the lane they run on;
      * none set: clips are packed planar 8-bit, there is no lane and nothing is converted */
     dsv1_srcchain src;
@@ -184,6 +172,7 @@ static void *b_calloc(size_t n, size_t sz)
 
 void dsv1_batch_close(dsv1_batch *b)
 {
+    int i;
     hp_report();
     if (!b) return;
     if (b->bg_on[0] || b->bg_on[1]) dsv1_par_bg_end();  /* a background prefix loop still reads this batch's pictures */
@@ -202,7 +191,8 @@ void dsv1_batch_close(dsv1_batch *b)
     free(b->slots_cur); free(b->slots_ref); free(b->pair_pic); free(b->out_slots);
     free(b->luma); free(b->mv_tmp); free(b->jobs); free(b->outs); free(b->rcjobs); free(b->sc0.pkt); free(b->rpar); free(b->has_recon); free(b->border_skipped); free(b->recon_dropped);
     free(b->ch_start); free(b->ch_len); free(b->ch_pair); free(b->ch_cur);
-    free(b->rc_dev); free(b->rc_par); free(b->sse); free(b->ssim); free(b->xsse); free(b->xssim);
+    free(b->rc_dev); free(b->rc_par);
+    for (i = 0; i < DSVG_Q_KINDS; i++) free(b->q[i].v);
     free(b);
 }
 
@@ -891,45 +881,35 @@ int dsv1_batch_recon_all(dsv1_batch *b, int on)
     b->keep_all = on != 0;
     return DSVG_OK;
 }
+/* what every switch of a kind does before it switches the context: refused with batches in flight; the values' room, once */
+static int quality_prepare(dsv1_batch *b, const char *fn, int kind, int on)
+{
+    if (!b) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "%s with batches in flight", fn); return DSVG_ERR_ARG; }
+    if (on && !b->q[kind].v && !(b->q[kind].v = (uint64_t *)malloc(sizeof(uint64_t) * 3 * (size_t)b->nstreams * (size_t)b->F))) return DSVG_ERR_NOMEM;
+    return DSVG_OK;
+}
 int dsv1_batch_sse_enable(dsv1_batch *b, int on)
 {
     int rc;
-    if (!b) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_sse_enable with batches in flight"); return DSVG_ERR_ARG; }
-    if (on && !b->sse && !(b->sse = (uint64_t *)malloc(sizeof(uint64_t) * 3 * (size_t)b->nstreams * (size_t)b->F))) return DSVG_ERR_NOMEM;
-    if ((rc = dsvg_ctx_sse_enable(b->ctx, on))) return rc;
-    b->sse_on = on != 0;
-    return DSVG_OK;
-}
-int dsv1_batch_get_sse(const dsv1_batch *b, uint64_t *sse, size_t n)
-{
-    if (!b || !sse) return DSVG_ERR_ARG;
-    if (!b->sse_n) { dsv1_log(1, "dsv1_batch_get_sse: the batch collected last was not measured (or none was collected)"); return DSVG_ERR_ARG; }
-    if (n < b->sse_n) { dsv1_log(1, "dsv1_batch_get_sse: %zu values needed, room for %zu", b->sse_n, n); return DSVG_ERR_ARG; }
-    memcpy(sse, b->sse, sizeof(uint64_t) * b->sse_n);
+    if ((rc = quality_prepare(b, "dsv1_batch_sse_enable", DSVG_Q_SSE, on)) || (rc = dsvg_ctx_sse_enable(b->ctx, on))) return rc;
+    b->q[DSVG_Q_SSE].on = on != 0;
     return DSVG_OK;
 }
 int dsv1_batch_ssim_enable(dsv1_batch *b, int on)
 {
     int rc;
-    if (!b) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_ssim_enable with batches in flight"); return DSVG_ERR_ARG; }
-    if (on && !b->ssim && !(b->ssim = (int64_t *)malloc(sizeof(int64_t) * 3 * (size_t)b->nstreams * (size_t)b->F))) return DSVG_ERR_NOMEM;
-    if ((rc = dsvg_ctx_ssim_enable(b->ctx, on))) return rc;
-    b->ssim_on = on != 0;
+    if ((rc = quality_prepare(b, "dsv1_batch_ssim_enable", DSVG_Q_SSIM, on)) || (rc = dsvg_ctx_ssim_enable(b->ctx, on))) return rc;
+    b->q[DSVG_Q_SSIM].on = on != 0;
     return DSVG_OK;
 }
 int dsv1_batch_xres_enable(dsv1_batch *b, int sse_on, int ssim_on, int ref_w, int ref_h, int filter)
 {
     int rc;
-    const size_t n = b ? (size_t)3 * b->nstreams * b->F : 0;
-    if (!b) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_xres_enable with batches in flight"); return DSVG_ERR_ARG; }
-    if (sse_on && !b->xsse && !(b->xsse = (uint64_t *)malloc(sizeof(uint64_t) * n))) return DSVG_ERR_NOMEM;
-    if (ssim_on && !b->xssim && !(b->xssim = (int64_t *)malloc(sizeof(int64_t) * n))) return DSVG_ERR_NOMEM;
-    if ((rc = dsvg_ctx_xres_enable(b->ctx, sse_on, ssim_on, ref_w, ref_h, filter))) return rc;
-    b->xsse_on = sse_on != 0;
-    b->xssim_on = ssim_on != 0;
+    if ((rc = quality_prepare(b, "dsv1_batch_xres_enable", DSVG_Q_XSSE, sse_on)) || (rc = quality_prepare(b, "dsv1_batch_xres_enable", DSVG_Q_XSSIM, ssim_on)) ||
+        (rc = dsvg_ctx_xres_enable(b->ctx, sse_on, ssim_on, ref_w, ref_h, filter))) return rc;
+    b->q[DSVG_Q_XSSE].on = sse_on != 0;
+    b->q[DSVG_Q_XSSIM].on = ssim_on != 0;
     return DSVG_OK;
 }
 int dsv1_batch_xres_source(dsv1_batch *b, const void *ref_clip_dev)
@@ -938,27 +918,22 @@ int dsv1_batch_xres_source(dsv1_batch *b, const void *ref_clip_dev)
     b->xres_clip = ref_clip_dev;
     return DSVG_OK;
 }
-int dsv1_batch_get_xres_sse(const dsv1_batch *b, uint64_t *sse, size_t n)
+const dsv1_quality *dsv1_batch_quality(const dsv1_batch *b, int kind) { return b && kind >= 0 && kind < DSVG_Q_KINDS ? &b->q[kind] : NULL; }
+/* the values of one kind of the batch collected last (SSIM_FX sums: int64 kept as their two's complement) */
+static int quality_get(const dsv1_batch *b, int kind, const char *fn, void *out, size_t n)
 {
-    if (!b || !sse || !b->xsse_n || n < b->xsse_n) return DSVG_ERR_ARG;
-    memcpy(sse, b->xsse, sizeof(uint64_t) * b->xsse_n);
+    const dsv1_quality *q;
+    if (!b || !out) return DSVG_ERR_ARG;
+    q = &b->q[kind];
+    if (!q->n) { dsv1_log(1, "%s: the batch collected last was not measured (or none was collected)", fn); return DSVG_ERR_ARG; }
+    if (n < q->n) { dsv1_log(1, "%s: %zu values needed, room for %zu", fn, q->n, n); return DSVG_ERR_ARG; }
+    memcpy(out, q->v, sizeof(uint64_t) * q->n);
     return DSVG_OK;
 }
-int dsv1_batch_get_xres_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n)
-{
-    if (!b || !ssim_fx || !b->xssim_n || n < b->xssim_n) return DSVG_ERR_ARG;
-    memcpy(ssim_fx, b->xssim, sizeof(int64_t) * b->xssim_n);
-    return DSVG_OK;
-}
-
-int dsv1_batch_get_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n)
-{
-    if (!b || !ssim_fx) return DSVG_ERR_ARG;
-    if (!b->ssim_n) { dsv1_log(1, "dsv1_batch_get_ssim: the batch collected last was not measured (or none was collected)"); return DSVG_ERR_ARG; }
-    if (n < b->ssim_n) { dsv1_log(1, "dsv1_batch_get_ssim: %zu values needed, room for %zu", b->ssim_n, n); return DSVG_ERR_ARG; }
-    memcpy(ssim_fx, b->ssim, sizeof(int64_t) * b->ssim_n);
-    return DSVG_OK;
-}
+int dsv1_batch_get_sse(const dsv1_batch *b, uint64_t *sse, size_t n) { return quality_get(b, DSVG_Q_SSE, "dsv1_batch_get_sse", sse, n); }
+int dsv1_batch_get_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n) { return quality_get(b, DSVG_Q_SSIM, "dsv1_batch_get_ssim", ssim_fx, n); }
+int dsv1_batch_get_xres_sse(const dsv1_batch *b, uint64_t *sse, size_t n) { return quality_get(b, DSVG_Q_XSSE, "dsv1_batch_get_xres_sse", sse, n); }
+int dsv1_batch_get_xres_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n) { return quality_get(b, DSVG_Q_XSSIM, "dsv1_batch_get_xres_ssim", ssim_fx, n); }
 long dsv1_batch_dropped_recons(const dsv1_batch *b, long *remedied)
 {
     if (!b) return 0;
@@ -1121,7 +1096,7 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
                     *pc = pics[s * R * F + t];
                     pc->out_slot += r;
                 }
-        if ((b->xsse_on || b->xssim_on) && !b->chains) {
+        if ((b->q[DSVG_Q_XSSE].on || b->q[DSVG_Q_XSSIM].on) && !b->chains) {
             /* the reference frame of every picture of the call: stream s (source s / R), frame t -> frame (s / R) * F + t */
             int *fr = (int *)malloc(sizeof(int) * (size_t)N * nf), *os = (int *)malloc(sizeof(int) * (size_t)N * nf);
             if (!fr || !os) { free(fr); free(os); return DSVG_ERR_NOMEM; }
@@ -1224,10 +1199,6 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
         }
         if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
         b->pending[par] = serial ? 2 : 1;               /* 2 = already assembled */
-        b->sse_sub[par] = b->sse_on;
-        b->ssim_sub[par] = b->ssim_on;
-        b->xsse_sub[par] = b->xsse_on && !b->chains;
-        b->xssim_sub[par] = b->xssim_on && !b->chains;
         b->nf_pending[par] = nf;
     }
     HP_MARK(HP_PREFIX);
@@ -1358,8 +1329,7 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
     S = b->nstreams; F = b->F;
     par = b->pending[b->parity] ? b->parity : (b->parity ^ 1);   /* oldest first */
     if (!b->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
-    b->sse_n = b->ssim_n = 0;                           /* (dsv1_batch_get_sse / _ssim: from here on about this batch) */
-    b->xsse_n = b->xssim_n = 0;
+    for (k = 0; k < DSVG_Q_KINDS; k++) b->q[k].n = 0;   /* (dsv1_batch_get_sse and its kin: from here on about this batch) */
     pics = b->pics + (size_t)par * S * F;
     nf = b->nf_pending[par];
     if (b->bg_on[par]) {
@@ -1376,10 +1346,10 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
         b->pending[par] = 0;
         return rc_;
     }
+    /* in submitted frame order ([stream][frame]: pics[s * F + t]); a short batch (nf < F) has a single stream: its pictures are the first nf entries */
+    for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
     if (b->pending[par] == 1) {
         HP_BEGIN();
-        /* a short batch (nf < F) has a single stream: its pictures are the first nf entries */
-        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
         {
             /* the copy comes in pieces of whole streams; the packets of a piece are assembled while the next is on the link */
             asm_ctx ac;
@@ -1390,26 +1360,12 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
         }
         HP_MARK(HP_FETCH);
     }
-    if (b->sse_sub[par]) {
-        /* the batch's measurement, in submitted frame order ([stream][frame]: pics[s * F + t], a short batch has a single stream) */
-        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
-        if ((rc = dsvg_fetch_sse(b->ctx, S * nf, b->out_slots, b->sse))) return rc;
-        b->sse_n = (size_t)3 * S * nf;
-    }
-    if (b->ssim_sub[par]) {
-        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
-        if ((rc = dsvg_fetch_ssim(b->ctx, S * nf, b->out_slots, b->ssim))) return rc;
-        b->ssim_n = (size_t)3 * S * nf;
-    }
-    if (b->xsse_sub[par]) {
-        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
-        if ((rc = dsvg_fetch_xres_sse(b->ctx, S * nf, b->out_slots, b->xsse))) return rc;
-        b->xsse_n = (size_t)3 * S * nf;
-    }
-    if (b->xssim_sub[par]) {
-        for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
-        if ((rc = dsvg_fetch_xres_ssim(b->ctx, S * nf, b->out_slots, b->xssim))) return rc;
-        b->xssim_n = (size_t)3 * S * nf;
+    /* the batch's measurements, in that order; the source-resolution kinds do not run in chain mode (batch_submit_impl names no
+     * reference frames there) */
+    for (k = 0; k < DSVG_Q_KINDS; k++) {
+        if (!b->q[k].on || (k >= DSVG_Q_XSSE && b->chains)) continue;
+        if ((rc = dsvg_fetch_quality(b->ctx, k, S * nf, b->out_slots, b->q[k].v))) return rc;
+        b->q[k].n = (size_t)3 * S * nf;
     }
     b->pending[par] = 0;
     return DSVG_OK;

@@ -166,6 +166,12 @@ int  dsv1_batch_xres_enable(dsv1_batch *b, int sse_on, int ssim_on, int ref_w, i
 int  dsv1_batch_xres_source(dsv1_batch *b, const void *ref_clip_dev);
 int  dsv1_batch_get_xres_sse(const dsv1_batch *b, uint64_t *sse, size_t n);
 int  dsv1_batch_get_xres_ssim(const dsv1_batch *b, int64_t *ssim_fx, size_t n);
+/* the record of one kind of figure (DSVG_Q_*) that a batch, and a resolution ladder over its batches, keeps: the switch, and the
+ * batch collected last: [streams][frames][3], the SSIM_FX sums as their two's complement; n values, 0 = not measured (or nothing
+ * collected).  dsv1_batch_quality: the batch's own (NULL for no batch or no such kind), for the resolution ladder to gather from;
+ * what it points to holds until the batch's next collect or close. */
+typedef struct { int on; uint64_t *v; size_t n; } dsv1_quality;
+const dsv1_quality *dsv1_batch_quality(const dsv1_batch *b, int kind);
 
 #define CLAMPI(v, lo, hi) ((v) < (lo) ? (lo) : ((v) > (hi) ? (hi) : (v)))
 

@@ -139,14 +139,11 @@ struct dsv1_resladder {
     DSV_BUF *tmp;                       /* [max nsrc * nrates]: a geometry's view of the caller's output buffers */
     uint64_t up_bytes;
     long up_calls;
-    uint64_t *sse;
-    int64_t *ssim;
-    size_t sse_n, ssim_n;
-    /* source-resolution figures (dsv1_resladder_src_quality_enable): every geometry's ladder measures against the source clip */
-    int sw, sh, xsse_on, xssim_on;
-    uint64_t *xsse;
-    int64_t *xssim;
-    size_t xsse_n, xssim_n;
+    /* the figures of the call collected last, per kind (DSVG_Q_*), gathered from the geometries' ladders.  `on` is kept for the two
+     * source-resolution kinds only (dsv1_resladder_src_quality_enable: every geometry's ladder measures against the source clip, which
+     * submit must hold for them); the switches of the rungs' own two live in the ladders alone, and their `on` here stays 0 */
+    dsv1_quality q[DSVG_Q_KINDS];
+    int sw, sh;
     /* the lane everything in front of the ladders runs on (kept while the resladder lives: uploads, scales), and the passes in front
      * of the scales: the source pixel format (dsv1_resladder_open_src), dsv1_resladder_set_deinterlace, dsv1_resladder_set_denoise */
     dsv1_srcchain src;
@@ -160,7 +157,8 @@ void dsv1_resladder_close(dsv1_resladder *r)
     if (r->src.lane) (void)dsvg_lane_sync(r->src.lane); /* (the scales read the tables) */
     dsvg_scaler_destroy(r->sc);
     dsv1_srcchain_close(&r->src);                       /* (and the scaled clips and upload buffers of its lane) */
-    free(r->tmp); free(r->sse); free(r->ssim); free(r->xsse); free(r->xssim);
+    free(r->tmp);
+    for (g = 0; g < DSVG_Q_KINDS; g++) free(r->q[g].v);
     free(r);
 }
 
@@ -246,9 +244,9 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     r->sw = src->width; r->sh = src->height;
     dsv1_srcchain_init(&r->src, device, src->width, src->height, src->subsamp, nsources, frames_per_call, 1);
     r->tmp = (DSV_BUF *)calloc((size_t)nsources * maxr, sizeof(DSV_BUF));
-    r->sse = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
-    r->ssim = (int64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(int64_t));
-    if (!r->tmp || !r->sse || !r->ssim) { dsv1_resladder_close(r); return DSVG_ERR_NOMEM; }
+    r->q[DSVG_Q_SSE].v = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
+    r->q[DSVG_Q_SSIM].v = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
+    if (!r->tmp || !r->q[DSVG_Q_SSE].v || !r->q[DSVG_Q_SSIM].v) { dsv1_resladder_close(r); return DSVG_ERR_NOMEM; }
     for (g = 0; g < ngeoms; g++) {
         r->w[g] = rungs[g].width; r->h[g] = rungs[g].height; r->nr[g] = rungs[g].nrates;
         r->off[g + 1] = r->off[g] + rungs[g].nrates;
@@ -321,7 +319,7 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
     if (!r || !yuv || !out || yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     par = r->parity;
     if (r->pending[par]) { dsv1_log(1, "resolution ladder submitted twice without collect"); return DSVG_ERR_ARG; }
-    if (plain_dev && (r->xsse_on || r->xssim_on) && !dsv1_srcchain_any(&r->src)) {
+    if (plain_dev && (r->q[DSVG_Q_XSSE].on || r->q[DSVG_Q_XSSIM].on) && !dsv1_srcchain_any(&r->src)) {
         /* the source-resolution figures read the source until collect, and a plain device clip is the caller's again when submit
          * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip */
         void *d;
@@ -339,7 +337,7 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
     for (g = 0; g < r->ngeom; g++) {
         const void *clip = dsrc;
         int form = yuv_on_device;
-        if ((r->xsse_on || r->xssim_on) && (rc = dsv1_batch_xres_source(r->lad[g], dsrc))) return rc;
+        if ((r->q[DSVG_Q_XSSE].on || r->q[DSVG_Q_XSSIM].on) && (rc = dsv1_batch_xres_source(r->lad[g], dsrc))) return rc;
         if (!r->same[g]) {
             if ((rc = dsvg_scaler_run(r->sc, dsvg_lane_stream(r->src.lane), r->scale_idx[g], dsrc, r->nsrc * r->F, r->clip[g][par]))) return rc;
             clip = r->clip[g][par];
@@ -394,49 +392,30 @@ int dsv1_resladder_denoise_reset(dsv1_resladder *r, int source)
 
 int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)
 {
-    int g, par, s, q, t, rc;
-    size_t n;
+    int g, par, s, q, k, rc, have[DSVG_Q_KINDS];
     if (!r || !out) return DSVG_ERR_ARG;
     par = r->pending[r->parity] ? r->parity : (r->parity ^ 1);      /* oldest first */
     if (!r->pending[par]) { dsv1_log(1, "nothing to collect"); return DSVG_ERR_ARG; }
     r->pending[par] = 0;
-    r->sse_n = r->ssim_n = 0;
-    r->xsse_n = r->xssim_n = 0;
+    for (k = 0; k < DSVG_Q_KINDS; k++) { r->q[k].n = 0; have[k] = r->q[k].v != NULL; }
     for (g = 0; g < r->ngeom; g++) {
         const size_t per = (size_t)3 * r->F;
         view_in(r, g, out);
         rc = dsv1_batch_collect(r->lad[g], r->tmp);
         view_out(r, g, out);
         if (rc) return rc;
-        n = (size_t)r->nsrc * r->nr[g] * per;
-        /* the geometry's figures [s * nr + q][t][p] go to [s * Ntot + off + q][t][p] (a ladder measured ... or not) */
-        {
-            uint64_t *tmp = (uint64_t *)malloc(sizeof(uint64_t) * n), *tmp3 = (uint64_t *)malloc(sizeof(uint64_t) * n);
-            int64_t *tmp2 = (int64_t *)malloc(sizeof(int64_t) * n), *tmp4 = (int64_t *)malloc(sizeof(int64_t) * n);
-            int have_sse, have_ssim, have_xsse, have_xssim;
-            if (!tmp || !tmp2 || !tmp3 || !tmp4) { free(tmp); free(tmp2); free(tmp3); free(tmp4); return DSVG_ERR_NOMEM; }
-            have_sse = dsv1_batch_get_sse(r->lad[g], tmp, n) == DSVG_OK;
-            have_ssim = dsv1_batch_get_ssim(r->lad[g], tmp2, n) == DSVG_OK;
-            have_xsse = r->xsse && dsv1_batch_get_xres_sse(r->lad[g], tmp3, n) == DSVG_OK;
-            have_xssim = r->xssim && dsv1_batch_get_xres_ssim(r->lad[g], tmp4, n) == DSVG_OK;
+        /* the geometry's figures [s * nr + q][t][p] go to [s * Ntot + off + q][t][p], straight from its ladder's record; a kind is
+         * present only if every geometry delivered it (a ladder measured ... or not) */
+        for (k = 0; k < DSVG_Q_KINDS; k++) {
+            const dsv1_quality *from = dsv1_batch_quality(r->lad[g], k);
+            if (!from || !from->n || from->n > (size_t)r->nsrc * r->nr[g] * per) have[k] = 0;
+            if (!have[k]) continue;
             for (s = 0; s < r->nsrc; s++)
                 for (q = 0; q < r->nr[g]; q++)
-                    for (t = 0; t < (int)per; t++) {
-                        const size_t from = (size_t)(s * r->nr[g] + q) * per + t, to = (size_t)(s * r->ntot + r->off[g] + q) * per + t;
-                        if (have_sse) r->sse[to] = tmp[from];
-                        if (have_ssim) r->ssim[to] = tmp2[from];
-                        if (have_xsse) r->xsse[to] = tmp3[from];
-                        if (have_xssim) r->xssim[to] = tmp4[from];
-                    }
-            free(tmp); free(tmp2); free(tmp3); free(tmp4);
-            if (g == 0) { r->sse_n = have_sse; r->ssim_n = have_ssim; r->xsse_n = have_xsse; r->xssim_n = have_xssim; }
-            else { r->sse_n &= (size_t)have_sse; r->ssim_n &= (size_t)have_ssim; r->xsse_n &= (size_t)have_xsse; r->xssim_n &= (size_t)have_xssim; }
+                    memcpy(r->q[k].v + (size_t)(s * r->ntot + r->off[g] + q) * per, from->v + (size_t)(s * r->nr[g] + q) * per, sizeof(uint64_t) * per);
         }
     }
-    if (r->sse_n) r->sse_n = (size_t)3 * r->nsrc * r->ntot * r->F;
-    if (r->ssim_n) r->ssim_n = (size_t)3 * r->nsrc * r->ntot * r->F;
-    if (r->xsse_n) r->xsse_n = (size_t)3 * r->nsrc * r->ntot * r->F;
-    if (r->xssim_n) r->xssim_n = (size_t)3 * r->nsrc * r->ntot * r->F;
+    for (k = 0; k < DSVG_Q_KINDS; k++) if (have[k]) r->q[k].n = (size_t)3 * r->nsrc * r->ntot * r->F;
     return DSVG_OK;
 }
 
@@ -465,18 +444,16 @@ int dsv1_resladder_ssim_enable(dsv1_resladder *r, int on)
         if ((rc = dsv1_batch_ssim_enable(r->lad[g], on))) return rc;
     return DSVG_OK;
 }
-int dsv1_resladder_get_sse(const dsv1_resladder *r, uint64_t *sse, size_t n)
+static int resladder_get(const dsv1_resladder *r, int kind, const char *fn, void *out, size_t n)
 {
-    if (!r || !sse || !r->sse_n || n < r->sse_n) { dsv1_log(1, "dsv1_resladder_get_sse: nothing measured, or no room"); return DSVG_ERR_ARG; }
-    memcpy(sse, r->sse, sizeof(uint64_t) * r->sse_n);
+    if (!r || !out || !r->q[kind].n || n < r->q[kind].n) { dsv1_log(1, "%s: nothing measured, or no room", fn); return DSVG_ERR_ARG; }
+    memcpy(out, r->q[kind].v, sizeof(uint64_t) * r->q[kind].n);
     return DSVG_OK;
 }
-int dsv1_resladder_get_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n)
-{
-    if (!r || !ssim_fx || !r->ssim_n || n < r->ssim_n) { dsv1_log(1, "dsv1_resladder_get_ssim: nothing measured, or no room"); return DSVG_ERR_ARG; }
-    memcpy(ssim_fx, r->ssim, sizeof(int64_t) * r->ssim_n);
-    return DSVG_OK;
-}
+int dsv1_resladder_get_sse(const dsv1_resladder *r, uint64_t *sse, size_t n) { return resladder_get(r, DSVG_Q_SSE, "dsv1_resladder_get_sse", sse, n); }
+int dsv1_resladder_get_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n) { return resladder_get(r, DSVG_Q_SSIM, "dsv1_resladder_get_ssim", ssim_fx, n); }
+int dsv1_resladder_get_src_sse(const dsv1_resladder *r, uint64_t *sse, size_t n) { return resladder_get(r, DSVG_Q_XSSE, "dsv1_resladder_get_src_sse", sse, n); }
+int dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n) { return resladder_get(r, DSVG_Q_XSSIM, "dsv1_resladder_get_src_ssim", ssim_fx, n); }
 /* every geometry's ladder measures its pictures upscaled to the source's dims against the source clip (dsv1_batch_xres_*) */
 int dsv1_resladder_src_quality_enable(dsv1_resladder *r, int sse_on, int ssim_on, int filter)
 {
@@ -485,24 +462,12 @@ int dsv1_resladder_src_quality_enable(dsv1_resladder *r, int sse_on, int ssim_on
     if (!r) return DSVG_ERR_ARG;
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_src_quality_enable with calls in flight"); return DSVG_ERR_ARG; }
     if (filter != DSV1_SCALE_TENT && filter != DSV1_SCALE_CUBIC) { dsv1_log(1, "dsv1_resladder_src_quality_enable: bad filter %d", filter); return DSVG_ERR_ARG; }
-    if (sse_on && !r->xsse && !(r->xsse = (uint64_t *)calloc(n, sizeof(uint64_t)))) return DSVG_ERR_NOMEM;
-    if (ssim_on && !r->xssim && !(r->xssim = (int64_t *)calloc(n, sizeof(int64_t)))) return DSVG_ERR_NOMEM;
+    if (sse_on && !r->q[DSVG_Q_XSSE].v && !(r->q[DSVG_Q_XSSE].v = (uint64_t *)calloc(n, sizeof(uint64_t)))) return DSVG_ERR_NOMEM;
+    if (ssim_on && !r->q[DSVG_Q_XSSIM].v && !(r->q[DSVG_Q_XSSIM].v = (uint64_t *)calloc(n, sizeof(uint64_t)))) return DSVG_ERR_NOMEM;
     for (g = 0; g < r->ngeom; g++)
         if ((rc = dsv1_batch_xres_enable(r->lad[g], sse_on, ssim_on, r->sw, r->sh, filter))) return rc;
-    r->xsse_on = sse_on != 0;
-    r->xssim_on = ssim_on != 0;
-    return DSVG_OK;
-}
-int dsv1_resladder_get_src_sse(const dsv1_resladder *r, uint64_t *sse, size_t n)
-{
-    if (!r || !sse || !r->xsse_n || n < r->xsse_n) { dsv1_log(1, "dsv1_resladder_get_src_sse: nothing measured, or no room"); return DSVG_ERR_ARG; }
-    memcpy(sse, r->xsse, sizeof(uint64_t) * r->xsse_n);
-    return DSVG_OK;
-}
-int dsv1_resladder_get_src_ssim(const dsv1_resladder *r, int64_t *ssim_fx, size_t n)
-{
-    if (!r || !ssim_fx || !r->xssim_n || n < r->xssim_n) { dsv1_log(1, "dsv1_resladder_get_src_ssim: nothing measured, or no room"); return DSVG_ERR_ARG; }
-    memcpy(ssim_fx, r->xssim, sizeof(int64_t) * r->xssim_n);
+    r->q[DSVG_Q_XSSE].on = sse_on != 0;
+    r->q[DSVG_Q_XSSIM].on = ssim_on != 0;
     return DSVG_OK;
 }
 int dsv1_resladder_uploads(const dsv1_resladder *r, uint64_t *bytes, long *calls)

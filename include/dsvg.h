@@ -310,6 +310,9 @@ int dsvg_ctx_xres_enable(dsvg_ctx *ctx, int sse_on, int ssim_on, int ref_w, int 
 int dsvg_ctx_xres_refs(dsvg_ctx *ctx, const void *ref_clip, int n, const int *out_slots, const int *frames);
 int dsvg_fetch_xres_sse(dsvg_ctx *ctx, int n, const int *out_slots, uint64_t *sse_out);
 int dsvg_fetch_xres_ssim(dsvg_ctx *ctx, int n, const int *out_slots, int64_t *ssim_out);
+/* The four figures by kind: dsvg_fetch_quality(kind) is the fetch above of that kind, the SSIM_FX sums as their two's complement. */
+enum { DSVG_Q_SSE, DSVG_Q_SSIM, DSVG_Q_XSSE, DSVG_Q_XSSIM, DSVG_Q_KINDS };
+int dsvg_fetch_quality(dsvg_ctx *ctx, int kind, int n, const int *out_slots, uint64_t *out);
 int dsvg_download_recon(dsvg_ctx *ctx, int recon_slot, uint8_t *yuv_out);            /* syncs */
 /* the first `bytes` bytes of the slot's whole frame allocation in the reference layout (dsv_mk_frame frame.c:63-120:
  * Y,U,V back to back, 64-px replicated borders): what the next picture's motion compensation reads.  Syncs. */

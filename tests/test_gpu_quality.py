@@ -274,6 +274,36 @@ def test_error_contract(pkg):
         b.close()
 
 
+def test_operator_level_fetch_per_kind(pkg):
+    """dsvg_fetch_sse / dsvg_fetch_ssim on a call's first out slot: the kind that was on gives Batch's figures, the other is
+    refused; a context that never measured at the source resolution refuses dsvg_fetch_xres_sse.  The out slots are the batch's
+    layout (csrc/host/dsv1_enc.c, batch_submit_impl: pc->out_slot = par * N * F + t * N + s * R, par alternating from 0 with every
+    submit): one stream, so the first picture of call 1 is in slot 0 and of call 2 in slot F.  Each fetch is compared with the
+    Batch's own figure of that picture, so another layout fails here rather than passes."""
+    w, h, fmt, F = 176, 144, A.SUBSAMP_420, 4
+    b = pkg.Batch(pkg.make_encoder_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1), 1, F)
+    L, ctx = b.L, C.c_void_p(b.ctx)
+    u, i = (C.c_uint64 * 3)(), (C.c_int64 * 3)()
+    clip = A.gen_clip(w, h, fmt, 0xE772, 2 * F).reshape(1, 2 * F, -1)
+    try:
+        b.sse_enable()
+        b.encode(np.ascontiguousarray(clip[:, :F]))
+        slot = (C.c_int * 1)(0)                         # batches alternate between two halves of the out slots: call 1 used [0, F)
+        assert L.dsvg_fetch_sse(ctx, 1, slot, u) == 0
+        assert list(u) == list(b.sse()[0, 0]) and all(v > 0 for v in u)
+        assert L.dsvg_fetch_ssim(ctx, 1, slot, i) == DSVG_ERR_ARG
+        b.sse_enable(False)
+        b.ssim_enable()
+        b.encode(np.ascontiguousarray(clip[:, F:]))
+        slot = (C.c_int * 1)(F)                         # call 2: [F, 2F)
+        assert L.dsvg_fetch_ssim(ctx, 1, slot, i) == 0
+        assert list(i) == list(b.ssim_fx()[0, 0]) and any(v != 0 for v in i)
+        assert L.dsvg_fetch_sse(ctx, 1, slot, u) == DSVG_ERR_ARG
+        assert L.dsvg_fetch_xres_sse(ctx, 1, slot, u) == DSVG_ERR_ARG
+    finally:
+        b.close()
+
+
 def test_psnr_of_a_batch(pkg):
     """Batch.psnr(): the per-plane and whole-picture dB of Batch.sse() by the module's psnr_db"""
     w, h, fmt, F = 176, 144, A.SUBSAMP_422, 4

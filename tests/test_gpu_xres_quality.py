@@ -216,3 +216,82 @@ def test_error_contract(pkg):
         assert L.dsv1_resladder_get_src_sse(b.h, buf, n) == DSVG_ERR_ARG              # switched off again
     finally:
         b.close()
+
+
+def test_all_four_kinds_switched_from_call_to_call(pkg, orc):
+    """rung SSE / SSIM and source-resolution SSE / SSIM on one resolution ladder, another setting every two calls (all on; rung SSIM
+    and source SSE; all off; rung SSE and source SSIM), the two calls of a setting in flight together so that both halves of the
+    out slots carry it: after every collect a kind that is on gives the oracle's figures of those frames, one that is off is refused
+    by its getter, and the packets are the oracle's"""
+    from test_gpu_quality import expected_sse
+    from test_gpu_ssim import expected as expected_ssim
+    w, h, fmt, F, n = 176, 144, A.SUBSAMP_420, 4, 32
+    geoms = [(w, h, [dict(qp=80)]), (96, 72, [dict(qp=60), dict(qp=90)])]
+    clips = [A.gen_clip(w, h, fmt, 0x4C1 + s, n, style=(0, 3)[s]) for s in range(2)]
+    want = [[], [], [], [], []]                      # streams, then the kinds in the getters' order below: [N][n, 3]
+    for clip in clips:
+        for gw, gh, rates in geoms:
+            sc = clip if (gw, gh) == (w, h) else Z.scale_clip(clip, w, h, fmt, gw, gh, Z.CUBIC)
+            for rate in rates:
+                data, recs = A.orc_encode(sc, A.orc_cfg(gw, gh, fmt, **dict(CRF, **rate)), want_recon=True, eos=False)
+                q = [RS.src_quality(clip[t], r, w, h, gw, gh, fmt, Z.CUBIC) for t, r in enumerate(recs)]
+                for i, v in enumerate([data, expected_sse(sc, recs, gw, gh, fmt), expected_ssim(sc, recs, gw, gh, fmt)[0],
+                                       np.stack([a for a, _ in q]), np.stack([x for _, x in q])]):
+                    want[i].append(v)
+    b = make(pkg, w, h, fmt, CRF, geoms, 2, F, Z.CUBIC)
+    try:
+        L, N = b.L, b.nstreams
+        kinds = [(L.dsv1_resladder_get_sse, C.c_uint64), (L.dsv1_resladder_get_ssim, C.c_int64),
+                 (L.dsv1_resladder_get_src_sse, C.c_uint64), (L.dsv1_resladder_get_src_ssim, C.c_int64)]
+        got, call = [b""] * N, 0
+        calls = [np.ascontiguousarray(np.stack([c[k * F:(k + 1) * F] for c in clips])) for k in range(n // F)]
+
+        def take(on):
+            nonlocal call
+            got[:] = [g + bytes(p) for g, p in zip(got, b.collect())]
+            for i, (get, ty) in enumerate(kinds):
+                buf = np.zeros((N, F, 3), dtype=ty)
+                rc = get(b.h, buf.ctypes.data_as(C.POINTER(ty)), buf.size)
+                if not on[i]:
+                    assert rc == DSVG_ERR_ARG, "call %d: kind %d is off and was delivered (rc %d)" % (call, i, rc)
+                    continue
+                assert rc == 0, "call %d: kind %d is on, rc %d" % (call, i, rc)
+                exp = np.stack([v[call * F:(call + 1) * F] for v in want[1 + i]])
+                assert np.array_equal(buf, exp), "call %d: kind %d differs from the oracle's in streams %s" % (
+                    call, i, sorted(set(np.nonzero(buf != exp)[0])))
+            call += 1
+
+        for on in [(1, 1, 1, 1), (0, 1, 1, 0), (0, 0, 0, 0), (1, 0, 0, 1)]:
+            b.sse_enable(on[0])
+            b.ssim_enable(on[1])
+            b.src_quality_enable(sse=on[2], ssim=on[3], filt=Z.CUBIC)
+            b.submit(calls[call])
+            b.submit(calls[call + 1])
+            take(on)
+            take(on)
+    finally:
+        b.close()
+    assert call == n // F
+    for k in range(N):
+        assert got[k] == want[0][k], "output stream %d: packets differ from the oracle's" % k
+
+
+def test_nothing_measured_logs_nothing(pkg, capfd):
+    """a resolution ladder with no measurement on gathers no figures and asks for none: a call logs no "not measured" line (the
+    library logs to stdout; the refused getter after the call shows that the capture sees its lines)"""
+    w, h, fmt, F = 176, 144, A.SUBSAMP_420, 4
+    libc = C.CDLL(None)
+    b = make(pkg, w, h, fmt, CRF, [(w, h, [dict(qp=80)]), (96, 72, [dict(qp=60), dict(qp=90)])], 1, F, Z.CUBIC)
+    try:
+        libc.fflush(None)
+        capfd.readouterr()
+        b.encode(A.gen_clip(w, h, fmt, 0x109, F).reshape(1, F, -1))
+        libc.fflush(None)
+        out = capfd.readouterr().out
+        assert "not measured" not in out and "nothing measured" not in out, out
+        buf = (C.c_uint64 * (3 * F * 3))()
+        assert b.L.dsv1_resladder_get_sse(b.h, buf, len(buf)) == DSVG_ERR_ARG
+        libc.fflush(None)
+        assert "dsv1_resladder_get_sse: nothing measured" in capfd.readouterr().out
+    finally:
+        b.close()
