@@ -411,6 +411,9 @@ static __device__ __forceinline__ void collect_chunk_ll(const JobDev &jb, int c,
                 if (p < ll_end) v[k][j] = ls[p];
                 else if (p < nscan && (!nzf || nzf[p >> 2])) {
                     v[k][j] = sym[p];
+#ifdef AB_HZ_BREAK_STRADDLE                // (test of the tests, DESIGN.md section 3: a detail symbol of the straddling chunk, one larger; tests/test_gpu_hz_paths.py::test_pipeline_case[tiny-noise] must fail with this)
+                    if (v[k][j] > 0) v[k][j]++;
+#endif
                     if (nzf) sym[p] = 0;
                 }
             }
@@ -682,7 +685,11 @@ __global__ __launch_bounds__(NT) void k_hz_scan(const JobDev *__restrict__ jobs)
         const int per = (limit - t0 + NT - 1) / NT;     // <= SCAN_ITEMS
         const int first = t0 + threadIdx.x * per;
         const int c_ne = s_c_ne, c_nnz = s_c_nnz;
+#ifdef AB_HZ_BREAK_TILE_CARRY              // (test of the tests: the bit count carried into a second tile, one more; tests/test_gpu_hz_paths.py::test_scan_second_tile must fail with this)
+        const unsigned long long c_bits = s_c_bits + (t0 ? 1ull : 0ull);
+#else
         const unsigned long long c_bits = s_c_bits;
+#endif
 
         // pass 1: index of the last non-empty chunk at or before each chunk (max-scan), nnz prefix
         int z[SCAN_ITEMS];
@@ -893,6 +900,9 @@ static __device__ __forceinline__ void emit_round64(EmitState &S, bool prev_in, 
             pat = (pat << (2 * k2 + 2)) | ((((x & 0xffffu) << 1) | 1u) << 1) | (pval < 0 ? 1u : 0u);
             len += 2u * k2 + 2u;
         }
+#ifdef AB_HZ_BREAK_TIER8                   // (test of the tests, DESIGN.md section 3: the last bit of the round's first code flipped; tests/test_gpu_hz_paths.py::test_operator_case[short-codes] must fail with this)
+        if (lane == 0 && valid) pat ^= 1u;
+#endif
         const unsigned incl = wave_scan_incl(len);
         tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
         stg[lane] = lane ? 0u : carry;
@@ -932,6 +942,9 @@ static __device__ __forceinline__ void emit_round64(EmitState &S, bool prev_in, 
             pat = (pat << (2 * k2 + 2)) | ((((unsigned long long)x2 << 1) | 1ull) << 1) | (pval < 0 ? 1ull : 0ull);
             len += 2u * k2 + 2u;
         }
+#ifdef AB_HZ_BREAK_TIER15                  // (as above; tests/test_gpu_hz_paths.py::test_operator_case[tier15] must fail with this)
+        if (lane == 0 && valid) pat ^= 1ull;
+#endif
         const unsigned incl = wave_scan_incl(len);
         tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
         stg[lane] = lane ? 0u : carry;
@@ -957,6 +970,9 @@ static __device__ __forceinline__ void emit_round64(EmitState &S, bool prev_in, 
             p1 = pat_ueg(m - 1u, l1);
             if (hasn) p2 = pat_neg(pval, l2);
         }
+#ifdef AB_HZ_BREAK_TIER31                  // (as above; tests/test_gpu_hz_paths.py::test_operator_case[tier31] must fail with this)
+        if (lane == 0 && valid) p1 ^= 1ull;
+#endif
         const unsigned len = (unsigned)(l1 + l2);
         const unsigned incl = wave_scan_incl(len);
         tot = (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
@@ -1109,6 +1125,9 @@ static __device__ __forceinline__ void emit_chunk_t(const JobDev &jb, int c, int
                     }
                     if (!valid[t]) pat[t] = 0u;
                 }
+#ifdef AB_HZ_BREAK_R256                    // (test of the tests: the last bit of the round's first code flipped; tests/test_gpu_hz_paths.py::test_pipeline_case[odd-ll-soft] must fail with this)
+                if (lane == 0) pat[0] ^= 1u;
+#endif
                 const unsigned long long sa = ((unsigned long long)pat[0] << len[1]) | pat[1], sb = ((unsigned long long)pat[2] << len[3]) | pat[3];
                 const unsigned la = len[0] + len[1], lb = len[2] + len[3];
                 const unsigned incl = wave_scan_incl(la + lb);
@@ -1151,6 +1170,14 @@ static __device__ __forceinline__ void emit_chunk_t(const JobDev &jb, int c, int
         if (lane == 0) {
             // the first and the last word of the chunk, possibly shared with the neighbouring chunks (or with each other)
             unsigned *og = reinterpret_cast<unsigned *>(jb.bits + jb.bits_off[c]);
+#ifdef AB_HZ_BREAK_SINGLE                  // (test of the tests: the single-word close, the word's last bit set; tests/test_gpu_hz_paths.py::test_operator_case[phase-single-both] must fail with this)
+            if (S.first_pending) S.carry |= 1u;
+#endif
+#ifdef AB_HZ_BREAK_ENDWORD                 // (test of the tests: the word-boundary close, final carry 0: the last bit of the word after it set;
+                                           // tests/test_gpu_hz_paths.py::test_operator_case[phase-endword-single] must fail with this.  That word is the payload's:
+                                           // the next chunk's first code or the plane's trailing value starts in it, and k_hz_scan cleared four words past the last)
+            if (!S.first_pending && (S.at0 & 31u) == 0u) S.carry |= 1u;
+#endif
             if (S.first_pending) { if (S.carry) atomicOr(og + S.wbase, __builtin_bswap32(S.carry)); }
             else {
                 if (S.firstv) atomicOr(og + S.wbase, __builtin_bswap32(S.firstv));

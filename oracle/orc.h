@@ -111,6 +111,9 @@ void orc_inv_sbt(orc_plane *dst, orc_coefs *src, int q, int isP, int c);
 int  orc_get_quant(int q, int isP, int level);
 int  orc_lb2(unsigned n);
 void orc_encode_plane(orc_bs *bs, orc_coefs *src, int q, const orc_stability *stab);
+/* entry recorder of the plane coder (orc_hzcc.c): arm(1) clears and starts, arm(0) stops and frees; read copies min(cap, n) words, returns n */
+void   orc_hz_rec_arm(int on);
+size_t orc_hz_rec_read(int32_t *out, size_t cap);
 void orc_decode_plane(uint8_t *in, unsigned len, orc_coefs *dst, int q, const orc_stability *stab);
 
 /* ---- frames (frame.c) ---------------------------------------------------------------- */

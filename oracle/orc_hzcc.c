@@ -14,6 +14,7 @@
  *   plane framing         dsv_encode_plane hzcc.c:449-476, dsv_decode_plane hzcc.c:479-496
  */
 #include <limits.h>
+#include <stdlib.h>
 #include "orc.h"
 
 #define MINQ 16            /* MINQUANT hzcc.c:27 */
@@ -109,17 +110,48 @@ static inline int cell_quant(const region *r, const orc_stability *st, int x, in
     return t < MINQ ? MINQ : t;
 }
 
+/* Entry recorder (tests/hz_plan.py): while armed, every packed plane leaves one record of int32 words --
+ * w, h, isP, cur_plane, entries n, byte offset of the payload in its bit stream, payload bits, then n x (scan position, value).
+ * Not thread safe: the tests arm it around one encode at a time. */
+static struct { int on; int32_t *w; size_t n, cap; } hz_rec;
+static void rec_put(int32_t v)
+{
+    if (hz_rec.n == hz_rec.cap) {
+        hz_rec.cap = hz_rec.cap ? 2 * hz_rec.cap : 1 << 16;
+        hz_rec.w = (int32_t *)realloc(hz_rec.w, hz_rec.cap * sizeof(int32_t));
+        if (!hz_rec.w) abort();
+    }
+    hz_rec.w[hz_rec.n++] = v;
+}
+void orc_hz_rec_arm(int on)
+{
+    free(hz_rec.w);
+    hz_rec.w = NULL; hz_rec.n = hz_rec.cap = 0;
+    hz_rec.on = on;
+}
+size_t orc_hz_rec_read(int32_t *out, size_t cap)
+{
+    for (size_t i = 0; i < hz_rec.n && i < cap; i++) out[i] = hz_rec.w[i];
+    return hz_rec.n;
+}
+
 static void hzcc_write(orc_bs *bs, int32_t *src, int w, int h, int q, const orc_stability *st)
 {
     region reg[10];
-    int nreg, run = 0, nruns = 0, held = 0;
+    int nreg, run = 0, nruns = 0, held = 0, cell = 0;
     unsigned count_at;
+    size_t rec_at = 0;
 
     orc_bs_align(bs);
     count_at = bs->pos;
     orc_bs_put_bits(bs, 32, 0);
     orc_bs_align(bs);
 
+    if (hz_rec.on) {
+        const int32_t head[7] = {w, h, st->isP, st->cur_plane, 0, (int32_t)(bs->pos >> 3), (int32_t)bs->pos};
+        rec_at = hz_rec.n;
+        for (int i = 0; i < 7; i++) rec_put(head[i]);
+    }
     nreg = build_regions(reg, w, h, q, st);
     src[0] = 0;                                   /* DC travels separately */
 
@@ -128,10 +160,11 @@ static void hzcc_write(orc_bs *bs, int32_t *src, int w, int h, int q, const orc_
         const int hi = (r->level == ORC_MAXLVL - 1);
         for (int y = 0; y < r->sh; y++) {
             int32_t *row = src + (size_t)(r->y0 + y) * w + r->x0;
-            for (int x = 0; x < r->sw; x++) {
+            for (int x = 0; x < r->sw; x++, cell++) {
                 int tq = cell_quant(r, st, x, y);
                 int v = hi ? q_hi(row[x], tq) : q_lo(row[x], tq);
                 if (v) {
+                    if (hz_rec.on) { rec_put(cell); rec_put(v); }
                     row[x] = hi ? dq_hi(v, tq) : dq_lo(v, tq);
                     orc_bs_put_ueg(bs, (unsigned)run);
                     if (held) orc_bs_put_neg(bs, held);   /* value k-1 follows run k */
@@ -146,6 +179,10 @@ static void hzcc_write(orc_bs *bs, int32_t *src, int w, int h, int q, const orc_
         }
     }
     if (held) orc_bs_put_neg(bs, held);
+    if (hz_rec.on) {
+        hz_rec.w[rec_at + 4] = nruns;
+        hz_rec.w[rec_at + 6] = (int32_t)bs->pos - hz_rec.w[rec_at + 6];
+    }
     orc_bs_align(bs);
 
     unsigned end = bs->pos;
