@@ -209,6 +209,14 @@ def lib():
         L.dsv1_decbatch_out_frame_bytes.restype = _C.c_size_t
         L.dsv1_decbatch_out_frame_bytes.argtypes = [_C.c_void_p]
         L.dsv1_export_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int]
+        L.dsv1_convert_clip_sub.argtypes = [_C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,
+                                            _C.c_int]
+        L.dsv1_batch_set_source_format_sub.argtypes = [_C.c_void_p, _C.POINTER(PixFormat), _C.c_int]
+        L.dsv1_resladder_open_src_sub.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(PixFormat), _C.c_int, _C.POINTER(ResRung),
+                                                  _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_export_clip_up.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int,
+                                          _C.c_int, _C.c_int]
+        L.dsv1_decbatch_set_output_format_up.argtypes = [_C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int]
         L.dsv1_rgb_frame_bytes.restype = _C.c_size_t
         L.dsv1_rgb_frame_bytes.argtypes = [_C.POINTER(RgbFormat), _C.c_int, _C.c_int]
         L.dsv1_rgb_tables.argtypes = [_C.c_int, _C.c_int, _C.POINTER(_C.c_int32), _C.POINTER(_C.c_int32)]
@@ -384,12 +392,19 @@ class Batch:
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
 
-    def set_source_format(self, pf):
+    def set_source_format(self, pf, src_subsamp=None):
         """from the next submit on, encode() / submit() take clips of PixFormat pf (dsv1_batch_set_source_format), converted on the
-        GPU; None switches back to packed planar 8-bit.  Between batches only.  The input-length check follows the format."""
-        _chk(self.L.dsv1_batch_set_source_format(self.h, _C.byref(pf) if pf is not None else None), "dsv1_batch_set_source_format")
-        planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, self.fmt)
-        self.frame_bytes = pix_frame_bytes(pf, self.width, self.height, self.fmt) if pf is not None else planar
+        GPU; None switches back to packed planar 8-bit.  Between batches only.  The input-length check follows the format.
+        src_subsamp: the clips' subsampling where it is not the batch's (dsv1_batch_set_source_format_sub) -- 4:4:4 or 4:2:2, chroma
+        halved on the way; pf None then means packed planar 8-bit at src_subsamp."""
+        if src_subsamp is None:
+            _chk(self.L.dsv1_batch_set_source_format(self.h, _C.byref(pf) if pf is not None else None), "dsv1_batch_set_source_format")
+            src_subsamp = self.fmt
+        else:
+            _chk(self.L.dsv1_batch_set_source_format_sub(self.h, _C.byref(pf) if pf is not None else None, src_subsamp),
+                 "dsv1_batch_set_source_format_sub")
+        planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, src_subsamp)
+        self.frame_bytes = pix_frame_bytes(pf, self.width, self.height, src_subsamp) if pf is not None else planar
 
     def set_source_rgb(self, rf):
         """from the next submit on, encode() / submit() take RGB clips of RgbFormat rf (dsv1_batch_set_source_rgb), converted on the
@@ -663,19 +678,24 @@ def _host_out(out, frames, dfb):
     return res
 
 
-def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None):
+def convert_clip(clip, pf, w, h, fmt, device=0, n=None, out=None, src_fmt=None):
     """convert frames of PixFormat pf to packed planar 8-bit on the GPU (dsv1_convert_clip): clip numpy uint8 [frames][frame bytes]
     (host), or a device pointer with n frames and `out` a device pointer for the result.  Host input returns numpy uint8
-    [frames][planar frame_bytes]."""
+    [frames][planar frame_bytes].  src_fmt: the subsampling of the clip where it is not fmt (dsv1_convert_clip_sub) -- 4:4:4 or 4:2:2,
+    chroma halved to fmt in the same pass."""
     L = lib()
-    sfb = pix_frame_bytes(pf, w, h, fmt)
+    if src_fmt is None:
+        call, what, sub = L.dsv1_convert_clip, "dsv1_convert_clip", (fmt,)
+    else:
+        call, what, sub = L.dsv1_convert_clip_sub, "dsv1_convert_clip_sub", (src_fmt, fmt)
+    sfb = pix_frame_bytes(pf, w, h, sub[0])
     dfb = w * h + 2 * _chroma_size(w, h, fmt)
     if n is not None:
-        _chk(L.dsv1_convert_clip(device, clip, _C.byref(pf), w, h, fmt, n, out, 1), "dsv1_convert_clip")
+        _chk(call(device, clip, _C.byref(pf), w, h, *sub, n, out, 1), what)
         return out
     a, frames = _host_clip(clip, sfb, "a clip of this format", raw=True)
     res = _np.zeros((frames, dfb), dtype=_np.uint8)
-    _chk(L.dsv1_convert_clip(device, a.ctypes.data, _C.byref(pf), w, h, fmt, frames, res.ctypes.data, 0), "dsv1_convert_clip")
+    _chk(call(device, a.ctypes.data, _C.byref(pf), w, h, *sub, frames, res.ctypes.data, 0), what)
     return res
 
 
@@ -726,20 +746,25 @@ def denoise_clip(clip, w, h, fmt, dn, state=None, device=0, n=None, out=None, st
     return res, new
 
 
-def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=None):
+def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=None, upsample=None):
     """packed planar 8-bit frames (w x h at subsampling fmt) to frames of PixFormat pf at subsampling out_subsamp (None: fmt) on the
     GPU (dsv1_export_clip), chroma halved on the way where out_subsamp asks for it: clip numpy uint8 [frames][frame_bytes] (host), or
     a device pointer with n frames and `out` a device pointer for the result.  Host input returns numpy uint8 [frames][frame bytes
-    of pf]; `out` (a numpy uint8 array of that size) is written in place -- what the format pads stays as it was."""
+    of pf]; `out` (a numpy uint8 array of that size) is written in place -- what the format pads stays as it was.  upsample
+    (CHROMA_REPLICATE / CHROMA_LINEAR; dsv1_export_clip_up): out_subsamp may also be a finer one than fmt, chroma doubled that way."""
     L = lib()
     osub = fmt if out_subsamp is None else out_subsamp
     sfb = w * h + 2 * _chroma_size(w, h, fmt)
+    if upsample is None:
+        call, what, tail = L.dsv1_export_clip, "dsv1_export_clip", (osub,)
+    else:
+        call, what, tail = L.dsv1_export_clip_up, "dsv1_export_clip_up", (osub, upsample)
     if n is not None:
-        _chk(L.dsv1_export_clip(device, clip, w, h, fmt, n, out, _C.byref(pf), osub, 1), "dsv1_export_clip")
+        _chk(call(device, clip, w, h, fmt, n, out, _C.byref(pf), *tail, 1), what)
         return out
     a, frames = _host_clip(clip, sfb, "a planar clip", raw=True)
     res = _host_out(out, frames, pix_frame_bytes(pf, w, h, osub))
-    _chk(L.dsv1_export_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(pf), osub, 0), "dsv1_export_clip")
+    _chk(call(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(pf), *tail, 0), what)
     return res
 
 
@@ -861,11 +886,15 @@ class ResLadder:
     SOURCE clip [source][frame] (nsources x F frames of w x h: one upload per call); results are per output stream
     k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
 
-    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None, src_rgb=None):
+    def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None, src_rgb=None,
+                 src_subsamp=None):
         """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit); src_rgb: their RgbFormat
-        instead (dsv1_resladder_open_rgb)"""
+        instead (dsv1_resladder_open_rgb); src_subsamp: the subsampling of the source clips where it is not fmt
+        (dsv1_resladder_open_src_sub) -- 4:4:4 or 4:2:2, chroma halved to fmt by the converter"""
         if src_format is not None and src_rgb is not None:
             raise ValueError("src_format and src_rgb exclude each other")
+        if src_subsamp is not None and src_rgb is not None:
+            raise ValueError("src_subsamp and src_rgb exclude each other")
         geoms = [(gw, gh, list(rates)) for gw, gh, rates in geoms]
         self.L = lib()
         self.h = _C.c_void_p(None)
@@ -879,6 +908,10 @@ class ResLadder:
         if src_rgb is not None:
             _chk(self.L.dsv1_resladder_open_rgb(_C.byref(self.h), _C.byref(meta), _C.byref(src_rgb), rr, len(geoms), device, nsources,
                                                 frames_per_call, filt), "dsv1_resladder_open_rgb")
+        elif src_subsamp is not None:
+            _chk(self.L.dsv1_resladder_open_src_sub(_C.byref(self.h), _C.byref(meta), None if src_format is None else _C.byref(src_format),
+                                                    src_subsamp, rr, len(geoms), device, nsources, frames_per_call, filt),
+                 "dsv1_resladder_open_src_sub")
         elif src_format is None:
             _chk(self.L.dsv1_resladder_open(_C.byref(self.h), _C.byref(meta), rr, len(geoms), device, nsources, frames_per_call, filt),
                  "dsv1_resladder_open")
@@ -887,7 +920,8 @@ class ResLadder:
                                                 frames_per_call, filt), "dsv1_resladder_open_src")
         self.ntot = sum(n for _, _, n in self.geoms)
         self.nstreams = self.L.dsv1_resladder_nstreams(self.h)
-        self.frame_bytes = w * h + 2 * _chroma_size(w, h, fmt) if src_format is None else pix_frame_bytes(src_format, w, h, fmt)
+        sfmt = fmt if src_subsamp is None else src_subsamp
+        self.frame_bytes = w * h + 2 * _chroma_size(w, h, sfmt) if src_format is None else pix_frame_bytes(src_format, w, h, sfmt)
         if src_rgb is not None:
             self.frame_bytes = rgb_frame_bytes(src_rgb, w, h)
         self.ctx = self.L.dsv1_batch_ctx(self.L.dsv1_resladder_batch(self.h, 0))
@@ -1083,12 +1117,18 @@ class DecBatch:
             self.L.dsvg_dev_free(self.ctx, self._dev)
             self._dev = None
 
-    def set_output_format(self, pixformat, out_subsamp=None):
+    def set_output_format(self, pixformat, out_subsamp=None, upsample=None):
         """from the next decode() on, frames are written as PixFormat pixformat at subsampling out_subsamp (None: the streams' own;
         dsv1_decbatch_set_output_format); None switches back to packed planar.  frame_bytes follows; ValueError (and the setting as
-        it was) for an invalid combination."""
+        it was) for an invalid combination.  upsample (CHROMA_REPLICATE / CHROMA_LINEAR; dsv1_decbatch_set_output_format_up):
+        out_subsamp may also be a finer one than the streams', chroma doubled that way."""
         osub = self.fmt if out_subsamp is None else out_subsamp
-        if self.L.dsv1_decbatch_set_output_format(self.h, None if pixformat is None else _C.byref(pixformat), osub) != 0:
+        pfp = None if pixformat is None else _C.byref(pixformat)
+        if upsample is None:
+            rc = self.L.dsv1_decbatch_set_output_format(self.h, pfp, osub)
+        else:
+            rc = self.L.dsv1_decbatch_set_output_format_up(self.h, pfp, osub, upsample)
+        if rc != 0:
             raise ValueError("not a valid output format for these streams (subsampling 0x%x -> 0x%x)" % (self.fmt, osub))
         self._output_changed()
 

@@ -30,14 +30,20 @@ typedef struct {
     size_t planes_bytes;        /* what a source frame holds: the last frame need not be longer */
     size_t out_frame_bytes;
     dsv1_pix_seg seg[3];
+    /* chroma halved on the way (include/dsv1_api.h, chroma resampling): horizontally / vertically, o = (a + b + 1) >> 1 on the 8-bit
+     * samples, the last column / row repeated, horizontally first; scw x sch are the chroma dims of the source.  The chroma outputs of
+     * a segment then have the halved dims (PLAIN / PAIR: rows and width; packed: cwidth, and a chroma row for every two of `rows`). */
+    int hd, vd, scw, sch;
 } dsv1_pix_layout;
-/* DSVG_OK, or DSVG_ERR_ARG for every combination include/dsv1_api.h calls invalid; no device is looked at */
-int dsv1_pix_layout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, dsv1_pix_layout *L);
+/* the layout of *pf at src_subsamp for frames at `subsamp` (the same, or one that halves: 4:4:4 -> 4:2:2 / 4:2:0, 4:2:2 -> 4:2:0).
+ * DSVG_OK, or DSVG_ERR_ARG for every combination include/dsv1_api.h calls invalid; no device is looked at */
+int dsv1_pix_layout_of(const dsv1_pix_format *pf, int w, int h, int src_subsamp, int subsamp, dsv1_pix_layout *L);
 int dsv1_pix_is_default(const dsv1_pix_format *pf, int w, int h, int subsamp);      /* NULL, or planar / 8 bits / tight */
 /* The other direction (decoder output formats, k_pixout.hip): format *pf at subsampling out_subsamp for frames decoded at `subsamp`,
  * resolved for the output pass.  DSVG_ERR_ARG for an invalid format and for every pair but: the same subsampling, 4:4:4 -> 4:2:2,
- * 4:4:4 or 4:2:2 -> 4:2:0. */
-int dsv1_pixout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, int out_subsamp, dsvg_pixout *F);
+ * 4:4:4 or 4:2:2 -> 4:2:0, and -- upsample a DSV1_CHROMA_* mode, not DSV1_CHROMA_NONE -- 4:2:0 -> 4:2:2 / 4:4:4, 4:2:2 -> 4:4:4. */
+#define DSV1_CHROMA_NONE (-1)
+int dsv1_pixout_of(const dsv1_pix_format *pf, int w, int h, int subsamp, int out_subsamp, int upsample, dsvg_pixout *F);
 
 /* ---- the lane: where a session's source-side work is enqueued (dsvg_lane.hip) ----
  * One non-blocking stream, one event, two raw upload buffers (per call parity, grown on demand) and the device memory handed out.

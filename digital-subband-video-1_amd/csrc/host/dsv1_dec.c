@@ -377,7 +377,17 @@ int dsv1_decbatch_set_output_format(dsv1_decbatch *d, const dsv1_pix_format *pf,
     dsvg_pixout F;
     if (!d) return DSVG_ERR_ARG;
     if (!pf) { d->out_set = 0; return DSVG_OK; }
-    return set_output(d, dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, &F), &F,
+    return set_output(d, dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, DSV1_CHROMA_NONE, &F), &F,
+                      !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp)));
+}
+
+/* every pair, the ones that double chroma included; `upsample` is validated always and read only where something goes up */
+int dsv1_decbatch_set_output_format_up(dsv1_decbatch *d, const dsv1_pix_format *pf, int out_subsamp, int upsample)
+{
+    dsvg_pixout F;
+    if (!d || (upsample != DSV1_CHROMA_REPLICATE && upsample != DSV1_CHROMA_LINEAR)) return DSVG_ERR_ARG;
+    if (!pf) { d->out_set = 0; return DSVG_OK; }
+    return set_output(d, dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, upsample, &F), &F,
                       !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp)));
 }
 

@@ -1224,19 +1224,32 @@ int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
-int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
+/* the two source-format setters: clips of *pf at src_subsamp (NULL: tight planar 8-bit) into the batch's subsampling */
+static int set_source_format(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp, const char *who)
 {
+    static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
     dsv1_pix_layout L;
-    const DSV_META *m;
-    if (!b) return DSVG_ERR_ARG;
-    m = &b->enc[0].vidmeta;
-    if (pf && dsv1_pix_layout_of(pf, m->width, m->height, m->subsamp, &L)) {
-        dsv1_log(1, "dsv1_batch_set_source_format: not a valid pixel format for %dx%d, subsampling 0x%x", m->width, m->height, m->subsamp);
+    const DSV_META *m = &b->enc[0].vidmeta;
+    if (!pf && src_subsamp != m->subsamp) pf = &planar8;
+    if (pf && dsv1_pix_layout_of(pf, m->width, m->height, src_subsamp, m->subsamp, &L)) {
+        dsv1_log(1, "%s: not a valid pixel format for %dx%d, subsampling 0x%x into 0x%x", who, m->width, m->height, src_subsamp, m->subsamp);
         return DSVG_ERR_ARG;
     }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_format with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "%s with batches in flight or clips staged", who); return DSVG_ERR_ARG; }
     /* nothing in flight: every batch that read one of the chain's clips has been collected */
-    return dsv1_srcchain_set_format(&b->src, dsv1_pix_is_default(pf, m->width, m->height, m->subsamp) ? NULL : &L, NULL);
+    return dsv1_srcchain_set_format(&b->src, src_subsamp == m->subsamp && dsv1_pix_is_default(pf, m->width, m->height, m->subsamp) ? NULL : &L, NULL);
+}
+
+int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
+{
+    if (!b) return DSVG_ERR_ARG;
+    return set_source_format(b, pf, b->enc[0].vidmeta.subsamp, "dsv1_batch_set_source_format");
+}
+
+int dsv1_batch_set_source_format_sub(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp)
+{
+    if (!b) return DSVG_ERR_ARG;
+    return set_source_format(b, pf, src_subsamp, "dsv1_batch_set_source_format_sub");
 }
 
 /* the RGB twin: the RGB import pass in the converter's place; the two setters replace each other */

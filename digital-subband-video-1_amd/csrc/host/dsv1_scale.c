@@ -168,13 +168,22 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
     return dsv1_resladder_open_src(out, src, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
-static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_rgb_format *rf,
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp, const dsv1_rgb_format *rf,
                               const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter);
 
 int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs, int ngeoms,
                             int device, int nsources, int frames_per_call, int filter)
 {
-    return resladder_open_fmt(out, src, pf, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, pf, src ? src->subsamp : 0, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+/* sources at src_subsamp: the converter halves their chroma to src->subsamp on the way */
+int dsv1_resladder_open_src_sub(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp, const dsv1_res_rung *rungs,
+                                int ngeoms, int device, int nsources, int frames_per_call, int filter)
+{
+    static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
+    if (!pf && src && src_subsamp != src->subsamp) pf = &planar8;
+    return resladder_open_fmt(out, src, pf, src_subsamp, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* RGB sources: the RGB import pass (k_rgb.hip) in the converter's place, everything else as dsv1_resladder_open_src */
@@ -183,10 +192,10 @@ int dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const dsv
 {
     if (out) *out = NULL;
     if (!rf) return DSVG_ERR_ARG;
-    return resladder_open_fmt(out, src, NULL, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, NULL, src ? src->subsamp : 0, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
-static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_rgb_format *rf,
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp, const dsv1_rgb_format *rf,
                               const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter)
 {
     dsv1_resladder *r;
@@ -198,11 +207,12 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     if (!out || !src || !rungs || ngeoms < 1 || ngeoms > DSV1_MAX_GEOMS || nsources < 1 || frames_per_call < 1) return DSVG_ERR_ARG;
     if (filter != DSV1_SCALE_TENT && filter != DSV1_SCALE_CUBIC) return DSVG_ERR_ARG;
     if (src->width < 1 || src->height < 1) return DSVG_ERR_ARG;
-    if (pf && dsv1_pix_layout_of(pf, src->width, src->height, src->subsamp, &pl)) {
-        dsv1_log(1, "dsv1_resladder_open_src: not a valid pixel format for %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
+    if (pf && dsv1_pix_layout_of(pf, src->width, src->height, src_subsamp, src->subsamp, &pl)) {
+        dsv1_log(1, "dsv1_resladder_open_src: not a valid pixel format for %dx%d sources of subsampling 0x%x into 0x%x", src->width, src->height,
+                 src_subsamp, src->subsamp);
         return DSVG_ERR_ARG;
     }
-    if (pf && dsv1_pix_is_default(pf, src->width, src->height, src->subsamp)) pf = NULL;
+    if (pf && src_subsamp == src->subsamp && dsv1_pix_is_default(pf, src->width, src->height, src->subsamp)) pf = NULL;
     if (rf && dsv1_rgb_layout_of(rf, src->width, src->height, src->subsamp, &rl)) {
         dsv1_log(1, "dsv1_resladder_open_rgb: not a valid RGB format for %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
         return DSVG_ERR_ARG;

@@ -20,6 +20,14 @@
 // decided on the host per segment and launch from the pointers, offsets, pitches and frame strides -- uniform, no per-lane test.
 // It takes the whole steps of a row; the row's tail, and every step of a segment that is not aligned, takes the byte path, which
 // loads exactly the bytes of the samples it converts: nothing outside the frame is ever read, whatever the pitch or the width.
+//
+// Chroma halving (include/dsv1_api.h, chroma resampling; k_pixfmt_sub): a source at 4:4:4 or 4:2:2 into frames at 4:2:2 or 4:2:0 in the
+// same launch.  The samples are reduced to 8 bits first and averaged second, with the carry-free byte arithmetic of k_pixout.hip:
+// horizontally the even and the odd bytes of a dword are added in 16-bit halves, vertically ceil((a + b) / 2) = (a | b) - ((a ^ b) >>
+// 1) byte for byte; horizontally first, rounded to 8 bits.  A step is still 16 bytes of each output plane: a planar chroma step reads
+// 32 source samples of one or two rows, a semi-planar one 16 pairs of two rows; a packed item is a step of TWO source rows, which
+// gives both luma rows and the one chroma row -- every source byte is loaded once.  The repeated last row is an edge select of the
+// row pointer; the repeated last column takes the byte path, which clamps the index: no load past the last sample of a row.
 #include <algorithm>
 #include "dsvg_host.hpp"
 #include "dsvg_pixfmt.h"
@@ -35,6 +43,8 @@ struct PixSeg {
     int dpitch[3], pad;
     long long doff[3];
     long long soff, spitch;
+    int hd, vd, iw, ih;                  // k_pixfmt_sub: the segment's chroma is halved horizontally / vertically; source samples per row, rows
+    int irows, pad2;                     // rows of items (packed, halved vertically: row pairs)
 };
 struct PixParams {
     PixSeg seg[3];
@@ -162,6 +172,147 @@ __global__ __launch_bounds__(PX_THREADS) void k_pixfmt(const PixParams P, const 
     }
 }
 
+// ---- chroma halving on the way ----
+// (a + b + 1) >> 1 of four byte pairs
+static __device__ __forceinline__ unsigned px_avg4(unsigned a, unsigned b) { return (a | b) - (((a ^ b) >> 1) & 0x7f7f7f7fu); }
+static __device__ __forceinline__ u32x4 px_avg16(u32x4 a, u32x4 b)
+{
+    u32x4 o;
+    o.x = px_avg4(a.x, b.x); o.y = px_avg4(a.y, b.y); o.z = px_avg4(a.z, b.z); o.w = px_avg4(a.w, b.w);
+    return o;
+}
+// (b0 + b1 + 1) >> 1 and (b2 + b3 + 1) >> 1 of a dword, in bytes 0 and 2
+static __device__ __forceinline__ unsigned px_havg2(unsigned d) { return (((d & 0x00ff00ffu) + ((d >> 8) & 0x00ff00ffu) + 0x00010001u) >> 1) & 0x00ff00ffu; }
+// 32 bytes -> the 16 averages of their pairs
+static __device__ __forceinline__ u32x4 px_hhalf16(u32x4 a, u32x4 b)
+{
+    u32x4 o;
+    o.x = px_perm(px_havg2(a.y), px_havg2(a.x), PX_EVEN); o.y = px_perm(px_havg2(a.w), px_havg2(a.z), PX_EVEN);
+    o.z = px_perm(px_havg2(b.y), px_havg2(b.x), PX_EVEN); o.w = px_perm(px_havg2(b.w), px_havg2(b.z), PX_EVEN);
+    return o;
+}
+// samples s0 .. s0 + 15 of a row as 8-bit values (s0 a multiple of 16, the row aligned)
+template <bool WIDE> static __device__ __forceinline__ u32x4 px_get16(const uint8_t *row, long long s0, int shift)
+{
+    if (!WIDE) return px_load(row + s0);
+    const u32x4 a = px_load(row + 2 * s0), b = px_load(row + 2 * s0 + 16);
+    u32x4 o;
+    o.x = px_perm(px_reduce2(a.y, shift), px_reduce2(a.x, shift), PX_EVEN);
+    o.y = px_perm(px_reduce2(a.w, shift), px_reduce2(a.z, shift), PX_EVEN);
+    o.z = px_perm(px_reduce2(b.y, shift), px_reduce2(b.x, shift), PX_EVEN);
+    o.w = px_perm(px_reduce2(b.w, shift), px_reduce2(b.z, shift), PX_EVEN);
+    return o;
+}
+// pairs p0 .. p0 + 15 of an interleaved row -> the 16 first and the 16 second samples
+template <bool WIDE> static __device__ __forceinline__ void px_pair16(const uint8_t *row, long long p0, int shift, u32x4 &u, u32x4 &v)
+{
+    const u32x4 a = px_get16<WIDE>(row, 2 * p0, shift), b = px_get16<WIDE>(row, 2 * p0 + 16, shift);
+    u.x = px_perm(a.y, a.x, PX_EVEN); u.y = px_perm(a.w, a.z, PX_EVEN); u.z = px_perm(b.y, b.x, PX_EVEN); u.w = px_perm(b.w, b.z, PX_EVEN);
+    v.x = px_perm(a.y, a.x, PX_ODD);  v.y = px_perm(a.w, a.z, PX_ODD);  v.z = px_perm(b.y, b.x, PX_ODD);  v.w = px_perm(b.w, b.z, PX_ODD);
+}
+// byte path: output sample x of a plane whose rows r0 and r1 (the same at the last odd row) feed one output row; `step` source
+// samples from one of the plane's to the next and `first` the plane's first (interleaved planes), iw samples of the plane per row
+template <bool WIDE>
+static __device__ __forceinline__ unsigned px_hsample(const uint8_t *r0, const uint8_t *r1, int x, int hd, int vd, int iw, int step, int first, int shift)
+{
+    const int x0 = hd ? 2 * x : x, x1 = hd ? min(x0 + 1, iw - 1) : x0;
+    const long long i0 = (long long)x0 * step + first, i1 = (long long)x1 * step + first;
+    unsigned v = hd ? (px_sample<WIDE>(r0, i0, shift) + px_sample<WIDE>(r0, i1, shift) + 1u) >> 1 : px_sample<WIDE>(r0, i0, shift);
+    if (vd) {
+        const unsigned u = hd ? (px_sample<WIDE>(r1, i0, shift) + px_sample<WIDE>(r1, i1, shift) + 1u) >> 1 : px_sample<WIDE>(r1, i0, shift);
+        v = (v + u + 1u) >> 1;
+    }
+    return v;
+}
+
+template <int LAYOUT, bool WIDE>
+__global__ __launch_bounds__(PX_THREADS) void k_pixfmt_sub(const PixParams P, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst)
+{
+    const int bx = blockIdx.x;
+    const int si = (LAYOUT == PXL_PLANAR) ? (bx >= P.seg[2].block0 ? 2 : (bx >= P.seg[1].block0 ? 1 : 0))
+                 : (LAYOUT == PXL_SEMI)   ? (bx >= P.seg[1].block0 ? 1 : 0) : 0;
+    const PixSeg &S = P.seg[si];
+    const int item = (bx - S.block0) * PX_THREADS + (int)threadIdx.x;
+    const int cpr = S.cpr;
+    const int y = item / cpr, c = item - y * cpr;
+    if (y >= S.irows) return;
+    const int shift = P.shift, hd = S.hd, vd = S.vd;
+    const uint8_t *plane = src + (long long)blockIdx.y * P.sfb + S.soff;
+    uint8_t *frame = dst + (long long)blockIdx.y * P.dfb;
+    // the source rows of output (chroma) row y: the last one once more where there is no second
+    const int y0 = vd ? 2 * y : y, y1 = min(y0 + 1, S.ih - 1);
+    const uint8_t *r0 = plane + (long long)y0 * S.spitch, *r1 = plane + (long long)y1 * S.spitch;
+    if (LAYOUT == PXL_PLANAR || (LAYOUT == PXL_SEMI && si == 0)) {
+        uint8_t *o0 = frame + S.doff[0] + (long long)y * S.dpitch[0];
+        if (S.fast && ((16 * c + 16) << hd) <= S.iw) {
+            const long long s0 = (long long)(16 * c) << hd;
+            u32x4 v = hd ? px_hhalf16(px_get16<WIDE>(r0, s0, shift), px_get16<WIDE>(r0, s0 + 16, shift)) : px_get16<WIDE>(r0, s0, shift);
+            if (vd) v = px_avg16(v, hd ? px_hhalf16(px_get16<WIDE>(r1, s0, shift), px_get16<WIDE>(r1, s0 + 16, shift)) : px_get16<WIDE>(r1, s0, shift));
+            px_store(o0 + 16 * c, v);
+        } else {
+            const int n = min(16, S.width - 16 * c);
+            for (int i = 0; i < n; i++) o0[16 * c + i] = (uint8_t)px_hsample<WIDE>(r0, r1, 16 * c + i, hd, vd, S.iw, 1, 0, shift);
+        }
+    } else if (LAYOUT == PXL_SEMI) {
+        // the interleaved plane of a 4:2:2 source: halved vertically only
+        uint8_t *o0 = frame + S.doff[0] + (long long)y * S.dpitch[0], *o1 = frame + S.doff[1] + (long long)y * S.dpitch[1];
+        if (S.fast && 16 * c + 16 <= S.width) {
+            u32x4 u, v;
+            px_pair16<WIDE>(r0, 16 * c, shift, u, v);
+            if (vd) {
+                u32x4 u1, v1;
+                px_pair16<WIDE>(r1, 16 * c, shift, u1, v1);
+                u = px_avg16(u, u1); v = px_avg16(v, v1);
+            }
+            px_store(o0 + 16 * c, u);
+            px_store(o1 + 16 * c, v);
+        } else {
+            const int n = min(16, S.width - 16 * c);
+            for (int i = 0; i < n; i++) {
+                o0[16 * c + i] = (uint8_t)px_hsample<WIDE>(r0, r1, 16 * c + i, 0, vd, S.iw, 2, 0, shift);
+                o1[16 * c + i] = (uint8_t)px_hsample<WIDE>(r0, r1, 16 * c + i, 0, vd, S.iw, 2, 1, shift);
+            }
+        }
+    } else {
+        // packed 4:2:2, 8 bits, halved vertically: item row y is source rows 2y and 2y + 1 -> two luma rows, one chroma row
+        const bool two = y0 + 1 < S.rows;
+        uint8_t *l0 = frame + S.doff[0] + (long long)y0 * S.dpitch[0], *l1 = l0 + S.dpitch[0];
+        uint8_t *o1 = frame + S.doff[1] + (long long)y * S.dpitch[1], *o2 = frame + S.doff[2] + (long long)y * S.dpitch[2];
+        const unsigned ysel = LAYOUT == PXL_YUYV ? PX_EVEN : PX_ODD, csel = LAYOUT == PXL_YUYV ? PX_ODD : PX_EVEN;
+        if (S.fast && 16 * c + 16 <= S.width) {
+            const u32x4 a = px_load(r0 + 32 * c), b = px_load(r0 + 32 * c + 16);
+            u32x4 yy;
+            yy.x = px_perm(a.y, a.x, ysel); yy.y = px_perm(a.w, a.z, ysel); yy.z = px_perm(b.y, b.x, ysel); yy.w = px_perm(b.w, b.z, ysel);
+            px_store(l0 + 16 * c, yy);
+            unsigned c0 = px_perm(a.y, a.x, csel), c1 = px_perm(a.w, a.z, csel), c2 = px_perm(b.y, b.x, csel), c3 = px_perm(b.w, b.z, csel);   // U V U V
+            if (two) {
+                const u32x4 d = px_load(r1 + 32 * c), e = px_load(r1 + 32 * c + 16);
+                yy.x = px_perm(d.y, d.x, ysel); yy.y = px_perm(d.w, d.z, ysel); yy.z = px_perm(e.y, e.x, ysel); yy.w = px_perm(e.w, e.z, ysel);
+                px_store(l1 + 16 * c, yy);
+                c0 = px_avg4(c0, px_perm(d.y, d.x, csel)); c1 = px_avg4(c1, px_perm(d.w, d.z, csel));
+                c2 = px_avg4(c2, px_perm(e.y, e.x, csel)); c3 = px_avg4(c3, px_perm(e.w, e.z, csel));
+            }
+            u32x2 u, v;
+            u.x = px_perm(c1, c0, PX_EVEN); u.y = px_perm(c3, c2, PX_EVEN);
+            v.x = px_perm(c1, c0, PX_ODD);  v.y = px_perm(c3, c2, PX_ODD);
+            *reinterpret_cast<u32x2 *>(o1 + 8 * c) = u;
+            *reinterpret_cast<u32x2 *>(o2 + 8 * c) = v;
+        } else {
+            const int yo = LAYOUT == PXL_YUYV ? 0 : 1, uo = 1 - yo;
+            const int n = min(16, S.width - 16 * c), m = min(8, S.cwidth - 8 * c);
+            for (int i = 0; i < n; i++) {
+                l0[16 * c + i] = r0[2 * (long long)(16 * c + i) + yo];
+                if (two) l1[16 * c + i] = r1[2 * (long long)(16 * c + i) + yo];
+            }
+            for (int i = 0; i < m; i++) {
+                const long long k = 4 * (long long)(8 * c + i) + uo;
+                o1[8 * c + i] = (uint8_t)(((unsigned)r0[k] + r1[k] + 1u) >> 1);
+                o2[8 * c + i] = (uint8_t)(((unsigned)r0[k + 2] + r1[k + 2] + 1u) >> 1);
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct dsvg_pixconv {
     int device = 0;
@@ -195,7 +346,13 @@ extern "C" int dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pi
         S.block0 = (int)blocks;
         for (int o = 0; o < 3; o++) { S.dpitch[o] = G.dpitch[o]; S.doff[o] = (long long)G.doff[o]; }
         S.soff = (long long)G.soff; S.spitch = (long long)G.spitch;
-        blocks += ((long long)S.cpr * S.rows + PX_THREADS - 1) / PX_THREADS;
+        // chroma halving: the packed segment's rows are luma rows (an item is two of them), every other chroma segment's are halved
+        const bool packed = c->layout == PXL_YUYV || c->layout == PXL_UYVY, chroma = packed || s > 0;
+        S.hd = chroma ? L->hd : 0; S.vd = chroma ? L->vd : 0;
+        if (packed && S.hd) { delete c; dsvg_set_error("bad converter arguments"); return DSVG_ERR_ARG; }
+        S.iw = chroma && !packed ? L->scw : G.width; S.ih = chroma && !packed ? L->sch : G.rows;
+        S.irows = packed && S.vd ? (G.rows + 1) / 2 : G.rows;
+        blocks += ((long long)S.cpr * S.irows + PX_THREADS - 1) / PX_THREADS;
         if (blocks > INT_MAX / 2) { delete c; dsvg_set_error("frame too large for the converter's grid"); return DSVG_ERR_UNSUPPORTED; }
     }
     c->nblocks = (int)blocks;
@@ -219,9 +376,10 @@ extern "C" int dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv
     return DSVG_OK;
 }
 
-template <int LAYOUT, bool WIDE> static void pix_launch(const PixParams &P, dim3 grid, hipStream_t st, const uint8_t *src, uint8_t *dst)
+template <int LAYOUT, bool WIDE> static void pix_launch(const PixParams &P, dim3 grid, hipStream_t st, const uint8_t *src, uint8_t *dst, bool sub)
 {
-    hipLaunchKernelGGL((k_pixfmt<LAYOUT, WIDE>), grid, dim3(PX_THREADS), 0, st, P, src, dst);
+    if (sub) hipLaunchKernelGGL((k_pixfmt_sub<LAYOUT, WIDE>), grid, dim3(PX_THREADS), 0, st, P, src, dst);
+    else hipLaunchKernelGGL((k_pixfmt<LAYOUT, WIDE>), grid, dim3(PX_THREADS), 0, st, P, src, dst);
 }
 
 // the 16-byte path of a segment: every row of every frame aligned, source and destination
@@ -244,19 +402,19 @@ extern "C" int dsvg_pixconv_run(dsvg_pixconv *c, void *stream, const void *src_d
     if (c->rgb) return dsvg_rgb_import_run(stream, &c->R, src_dev, nframes, dst_dev);
     PixParams P = c->P;
     for (int s = 0; s < P.nseg; s++) P.seg[s].fast = seg_fast(P, P.seg[s], src_dev, dst_dev);
-    const bool wide = c->L.wide != 0;
+    const bool wide = c->L.wide != 0, sub = c->L.hd || c->L.vd;
     for (int f0 = 0; f0 < nframes; f0 += 65535) {        // (gridDim.y; one launch for any call the batches make)
         const int n = std::min(65535, nframes - f0);
         const uint8_t *s = (const uint8_t *)src_dev + (size_t)f0 * c->L.frame_bytes;
         uint8_t *d = (uint8_t *)dst_dev + (size_t)f0 * c->L.out_frame_bytes;
         const dim3 grid(c->nblocks, n);
         switch (c->layout * 2 + (wide ? 1 : 0)) {
-        case PXL_PLANAR * 2:     pix_launch<PXL_PLANAR, false>(P, grid, st, s, d); break;
-        case PXL_PLANAR * 2 + 1: pix_launch<PXL_PLANAR, true>(P, grid, st, s, d); break;
-        case PXL_SEMI * 2:       pix_launch<PXL_SEMI, false>(P, grid, st, s, d); break;
-        case PXL_SEMI * 2 + 1:   pix_launch<PXL_SEMI, true>(P, grid, st, s, d); break;
-        case PXL_YUYV * 2:       pix_launch<PXL_YUYV, false>(P, grid, st, s, d); break;
-        case PXL_UYVY * 2:       pix_launch<PXL_UYVY, false>(P, grid, st, s, d); break;
+        case PXL_PLANAR * 2:     pix_launch<PXL_PLANAR, false>(P, grid, st, s, d, sub); break;
+        case PXL_PLANAR * 2 + 1: pix_launch<PXL_PLANAR, true>(P, grid, st, s, d, sub); break;
+        case PXL_SEMI * 2:       pix_launch<PXL_SEMI, false>(P, grid, st, s, d, sub); break;
+        case PXL_SEMI * 2 + 1:   pix_launch<PXL_SEMI, true>(P, grid, st, s, d, sub); break;
+        case PXL_YUYV * 2:       pix_launch<PXL_YUYV, false>(P, grid, st, s, d, sub); break;
+        case PXL_UYVY * 2:       pix_launch<PXL_UYVY, false>(P, grid, st, s, d, sub); break;
         default: dsvg_set_error("no converter kernel for this format"); return DSVG_ERR_UNSUPPORTED;
         }
     }

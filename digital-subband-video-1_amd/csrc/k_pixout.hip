@@ -25,6 +25,13 @@
 // byte path, which stores exactly the bytes of the samples it owns: nothing between a row's end and its pitch, behind the planes or
 // between frames is ever written.  The one exception lies inside the frame: the second luma byte of the last macro-pixel of an
 // odd-width packed row repeats the row's last luma sample.
+//
+// Chroma doubling (include/dsv1_api.h, chroma resampling; the UP instances of the kernel): a 4:2:0 or 4:2:2 stream written at 4:2:2 or
+// 4:4:4, as k_rgb.hip brings chroma to the luma grid -- vertically first, o = (3 c + n + 2) >> 2 with n the row above (even output
+// rows) or below (odd ones), clamped; then the same over columns on that 8-bit result; replication is the same arithmetic with n = c.
+// A step's 16 samples come from 16 (vertical only) or 8 (horizontal) input samples of one or two rows plus, horizontally, the one
+// neighbour on each side -- two clamped byte loads.  3 a + b + 2 <= 1022 is formed on the even and the odd bytes of a dword in 16-bit
+// halves, so nothing carries.  The 16-byte path takes the steps whose 16 output samples exist (their inputs then exist too).
 #include <algorithm>
 #include "dsvg_host.hpp"
 #include "dsvg_pixfmt.h"
@@ -38,6 +45,7 @@ struct PoSeg {
     int kind, rows, width, cwidth;
     int cpr, block0, fast, nin;          // steps per row, first block of the segment in blockIdx.x, every row on the 16-byte path
     int hd, vd, iw, ih;                  // the chroma inputs: halved horizontally / vertically, their dims (the clamps)
+    int hu, vu, lin, pad2;               // ... or doubled; centre-sited linear, else replicated
     int ipitch[3], pad;
     long long ioff[3];                   // input planes inside a source frame
     long long ooff, opitch;              // the output plane inside an output frame
@@ -125,6 +133,82 @@ static __device__ __forceinline__ unsigned po_sample(const uint8_t *plane, long 
     }
     return v;
 }
+// ---- chroma doubling ----
+// (3 a + b + 2) >> 2 of four byte pairs
+static __device__ __forceinline__ unsigned po_lerp4(unsigned a, unsigned b)
+{
+    const unsigned e = ((3u * (a & 0x00ff00ffu) + (b & 0x00ff00ffu) + 0x00020002u) >> 2) & 0x00ff00ffu;
+    const unsigned o = ((3u * ((a >> 8) & 0x00ff00ffu) + ((b >> 8) & 0x00ff00ffu) + 0x00020002u) >> 2) & 0x00ff00ffu;
+    return e | (o << 8);
+}
+// the two input rows of output row y: the one it lies in and its vertical neighbour (the same row: none, or replication)
+static __device__ __forceinline__ void po_up_rows(const uint8_t *plane, long long pitch, int y, int vu, int lin, int ih, const uint8_t *&r0, const uint8_t *&r1)
+{
+    const int j = vu ? y >> 1 : y;
+    const int n = vu && lin ? ((y & 1) ? min(j + 1, ih - 1) : max(j - 1, 0)) : j;
+    r0 = plane + (long long)j * pitch;
+    r1 = plane + (long long)n * pitch;
+}
+// 16 arriving samples of a plane, doubled: output row y, output columns x0 .. x0 + 15 (all of them exist, every load is aligned)
+static __device__ __forceinline__ u32x4 po_up16(const uint8_t *plane, long long pitch, int y, int x0, int hu, int vu, int lin, int iw, int ih)
+{
+    const uint8_t *r0, *r1;
+    po_up_rows(plane, pitch, y, vu, lin, ih, r0, r1);
+    if (!hu) {
+        const u32x4 a = po_load(r0 + x0);
+        if (!(vu && lin)) return a;                     // (luma, replicated rows)
+        const u32x4 b = po_load(r1 + x0);
+        u32x4 o;
+        o.x = po_lerp4(a.x, b.x); o.y = po_lerp4(a.y, b.y); o.z = po_lerp4(a.z, b.z); o.w = po_lerp4(a.w, b.w);
+        return o;
+    }
+    // input columns i0 .. i0 + 7 and their neighbours on both sides, vertically interpolated first
+    const int i0 = x0 >> 1, il = max(i0 - 1, 0), ir = min(i0 + 8, iw - 1);
+    const u32x2 a = *reinterpret_cast<const u32x2 *>(r0 + i0), b = *reinterpret_cast<const u32x2 *>(r1 + i0);
+    const unsigned lo = po_lerp4(a.x, b.x), hi = po_lerp4(a.y, b.y);
+    const unsigned l = (3u * r0[il] + r1[il] + 2u) >> 2, r = (3u * r0[ir] + r1[ir] + 2u) >> 2;
+    const unsigned plo = lin ? (lo << 8) | l : lo, phi = lin ? (hi << 8) | (lo >> 24) : hi;           // the sample before each
+    const unsigned nlo = lin ? (lo >> 8) | (hi << 24) : lo, nhi = lin ? (hi >> 8) | (r << 24) : hi;    // the sample after each
+    const unsigned elo = po_lerp4(lo, plo), ehi = po_lerp4(hi, phi), olo = po_lerp4(lo, nlo), ohi = po_lerp4(hi, nhi);
+    u32x4 o;
+    o.x = po_perm(olo, elo, PO_ZIP01); o.y = po_perm(olo, elo, PO_ZIP23); o.z = po_perm(ohi, ehi, PO_ZIP01); o.w = po_perm(ohi, ehi, PO_ZIP23);
+    return o;
+}
+// 8 of them (the packed layouts' U and V: 4:2:2 out, so only rows are doubled)
+static __device__ __forceinline__ u32x2 po_up8(const uint8_t *plane, long long pitch, int y, int x0, int vu, int lin, int ih)
+{
+    const uint8_t *r0, *r1;
+    po_up_rows(plane, pitch, y, vu, lin, ih, r0, r1);
+    const u32x2 a = *reinterpret_cast<const u32x2 *>(r0 + x0);
+    if (!(vu && lin)) return a;
+    const u32x2 b = *reinterpret_cast<const u32x2 *>(r1 + x0);
+    u32x2 o;
+    o.x = po_lerp4(a.x, b.x); o.y = po_lerp4(a.y, b.y);
+    return o;
+}
+// byte path: arriving sample x of output row y
+static __device__ __forceinline__ unsigned po_upsample(const uint8_t *plane, long long pitch, int y, int x, int hu, int vu, int lin, int iw, int ih)
+{
+    const uint8_t *r0, *r1;
+    po_up_rows(plane, pitch, y, vu, lin, ih, r0, r1);
+    const int i = hu ? x >> 1 : x;
+    const int n = hu && lin ? ((x & 1) ? min(i + 1, iw - 1) : max(i - 1, 0)) : i;
+    const unsigned a = (3u * r0[i] + r1[i] + 2u) >> 2, b = (3u * r0[n] + r1[n] + 2u) >> 2;
+    return (3u * a + b + 2u) >> 2;
+}
+// the kernel's three fetches, halving or (UP) doubling
+template <bool UP> static __device__ __forceinline__ u32x4 po_in16(const PoSeg &S, const uint8_t *plane, long long pitch, int y, int x0)
+{
+    return UP ? po_up16(plane, pitch, y, x0, S.hu, S.vu, S.lin, S.iw, S.ih) : po_fetch16(plane, pitch, y, x0, S.hd, S.vd, S.ih);
+}
+template <bool UP> static __device__ __forceinline__ u32x2 po_in8(const PoSeg &S, const uint8_t *plane, long long pitch, int y, int x0)
+{
+    return UP ? po_up8(plane, pitch, y, x0, S.vu, S.lin, S.ih) : po_fetch8(plane, pitch, y, x0, S.hd, S.vd, S.ih);
+}
+template <bool UP> static __device__ __forceinline__ unsigned po_in1(const PoSeg &S, const uint8_t *plane, long long pitch, int y, int x)
+{
+    return UP ? po_upsample(plane, pitch, y, x, S.hu, S.vu, S.lin, S.iw, S.ih) : po_sample(plane, pitch, y, x, S.hd, S.vd, S.iw, S.ih);
+}
 template <bool WIDE> static __device__ __forceinline__ void po_put(uint8_t *row, long long i, unsigned v, int shift)
 {
     if (!WIDE) row[i] = (uint8_t)v;
@@ -132,7 +216,7 @@ template <bool WIDE> static __device__ __forceinline__ void po_put(uint8_t *row,
 }
 
 // tab: (source frame, output frame) per blockIdx.y -- the reconstruction slot and the caller's frame index -- or null: both blockIdx.y
-template <int LAYOUT, bool WIDE>
+template <int LAYOUT, bool WIDE, bool UP>
 __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const int *__restrict__ tab)
 {
     const int bx = blockIdx.x;
@@ -150,9 +234,9 @@ __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const u
     uint8_t *orow = dst + df * P.dfb + S.ooff + (long long)y * S.opitch;
     const int hd = S.hd, vd = S.vd;
     if (LAYOUT == POL_PLANAR || (LAYOUT == POL_SEMI && si == 0)) {
-        const bool whole = S.fast && ((16 * c + 16) << hd) <= S.iw;
+        const bool whole = S.fast && (UP ? 16 * c + 16 <= S.width : ((16 * c + 16) << hd) <= S.iw);
         if (whole) {
-            const u32x4 v = po_fetch16(i0, S.ipitch[0], y, 16 * c, hd, vd, S.ih);
+            const u32x4 v = po_in16<UP>(S, i0, S.ipitch[0], y, 16 * c);
             if (!WIDE) po_store(orow + 16 * c, v);
             else {
                 u32x4 a, b;
@@ -165,13 +249,13 @@ __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const u
             }
         } else {
             const int n = min(16, S.width - 16 * c);
-            for (int i = 0; i < n; i++) po_put<WIDE>(orow, 16 * c + i, po_sample(i0, S.ipitch[0], y, 16 * c + i, hd, vd, S.iw, S.ih), shift);
+            for (int i = 0; i < n; i++) po_put<WIDE>(orow, 16 * c + i, po_in1<UP>(S, i0, S.ipitch[0], y, 16 * c + i), shift);
         }
     } else if (LAYOUT == POL_SEMI) {
         const uint8_t *i1 = frame + S.ioff[1];
-        const bool whole = S.fast && ((16 * c + 16) << hd) <= S.iw;
+        const bool whole = S.fast && (UP ? 16 * c + 16 <= S.width : ((16 * c + 16) << hd) <= S.iw);
         if (whole) {
-            const u32x4 a = po_fetch16(i0, S.ipitch[0], y, 16 * c, hd, vd, S.ih), b = po_fetch16(i1, S.ipitch[1], y, 16 * c, hd, vd, S.ih);
+            const u32x4 a = po_in16<UP>(S, i0, S.ipitch[0], y, 16 * c), b = po_in16<UP>(S, i1, S.ipitch[1], y, 16 * c);
             const unsigned av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
             if (!WIDE) {
                 u32x4 o, p;
@@ -194,8 +278,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const u
             const int n = min(16, S.width - 16 * c);
             for (int i = 0; i < n; i++) {
                 const long long x = 16 * c + i;
-                po_put<WIDE>(orow, 2 * x, po_sample(i0, S.ipitch[0], y, (int)x, hd, vd, S.iw, S.ih), shift);
-                po_put<WIDE>(orow, 2 * x + 1, po_sample(i1, S.ipitch[1], y, (int)x, hd, vd, S.iw, S.ih), shift);
+                po_put<WIDE>(orow, 2 * x, po_in1<UP>(S, i0, S.ipitch[0], y, (int)x), shift);
+                po_put<WIDE>(orow, 2 * x + 1, po_in1<UP>(S, i1, S.ipitch[1], y, (int)x), shift);
             }
         }
     } else {
@@ -205,7 +289,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const u
         const bool whole = S.fast && 16 * c + 16 <= S.width;           // (then the chroma inputs of the step exist too)
         if (whole) {
             const u32x4 yv = po_load(yrow + 16 * c);
-            const u32x2 u = po_fetch8(i1, S.ipitch[1], y, 8 * c, hd, vd, S.ih), v = po_fetch8(i2, S.ipitch[2], y, 8 * c, hd, vd, S.ih);
+            const u32x2 u = po_in8<UP>(S, i1, S.ipitch[1], y, 8 * c), v = po_in8<UP>(S, i2, S.ipitch[2], y, 8 * c);
             const unsigned yy[4] = {yv.x, yv.y, yv.z, yv.w};
             const unsigned uv[4] = {po_perm(v.x, u.x, PO_ZIP01), po_perm(v.x, u.x, PO_ZIP23), po_perm(v.y, u.y, PO_ZIP01), po_perm(v.y, u.y, PO_ZIP23)};   // U V U V
             unsigned o[8];
@@ -226,8 +310,8 @@ __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const u
                 uint8_t *mp = orow + 4 * (long long)m;
                 mp[yo] = yrow[2 * m];
                 mp[yo + 2] = yrow[min(2 * m + 1, S.width - 1)];        // (odd width: the row's last luma sample once more)
-                mp[uo] = (uint8_t)po_sample(i1, S.ipitch[1], y, m, hd, vd, S.iw, S.ih);
-                mp[uo + 2] = (uint8_t)po_sample(i2, S.ipitch[2], y, m, hd, vd, S.iw, S.ih);
+                mp[uo] = (uint8_t)po_in1<UP>(S, i1, S.ipitch[1], y, m);
+                mp[uo + 2] = (uint8_t)po_in1<UP>(S, i2, S.ipitch[2], y, m);
             }
         }
     }
@@ -239,6 +323,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pixout(const PoParams P, const u
 static int po_params(PoParams &P, int &layout, int &nblocks, const dsvg_pixout *F, const PoSource &S, long long dfb)
 {
     if (!F || F->nseg < 1 || F->nseg > 3 || (F->hd & ~1) || (F->vd & ~1) || (F->wide & ~1) || F->shift < 0 || F->shift > 8 || (!F->wide && F->shift)) return DSVG_ERR_ARG;
+    if ((F->hu & ~1) || (F->vu & ~1) || ((F->hu || F->vu) && (F->hd || F->vd))) return DSVG_ERR_ARG;
     if (F->planes_bytes > F->frame_bytes || dfb < (long long)F->frame_bytes) return DSVG_ERR_ARG;
     const int k0 = F->seg[0].kind;
     const bool packed = k0 == DSVG_PIXOUT_YUYV || k0 == DSVG_PIXOUT_UYVY;
@@ -259,8 +344,10 @@ static int po_params(PoParams &P, int &layout, int &nblocks, const dsvg_pixout *
         // the chroma inputs of a segment share their dims; luma is never halved
         const int pc = G.in_plane[nin - 1];
         const bool chroma = pc != 0;
-        const int hd = chroma ? F->hd : 0, vd = chroma ? F->vd : 0;
-        const int ow = (S.w[pc] + hd) >> hd, oh = (S.h[pc] + vd) >> vd;
+        const int hd = chroma ? F->hd : 0, vd = chroma ? F->vd : 0, hu = chroma ? F->hu : 0, vu = chroma ? F->vu : 0;
+        // doubled chroma reaches the luma dims on that axis, so the plane must be their rshift_up by one
+        if ((hu && S.w[pc] != (S.w[0] + 1) / 2) || (vu && S.h[pc] != (S.h[0] + 1) / 2) || (packed && hu)) return DSVG_ERR_ARG;
+        const int ow = hu ? S.w[0] : (S.w[pc] + hd) >> hd, oh = vu ? S.h[0] : (S.h[pc] + vd) >> vd;
         if (packed) {
             if (G.width != S.w[0] || G.rows != S.h[0] || oh != S.h[0] || G.cwidth != ow || ow != (S.w[0] + 1) / 2) return DSVG_ERR_ARG;
         } else if (G.width != ow || G.rows != oh) return DSVG_ERR_ARG;
@@ -268,6 +355,7 @@ static int po_params(PoParams &P, int &layout, int &nblocks, const dsvg_pixout *
         if (G.pitch < rowb || G.off + G.pitch * (size_t)(G.rows - 1) + rowb > F->planes_bytes) return DSVG_ERR_ARG;
         D.kind = G.kind; D.rows = G.rows; D.width = G.width; D.cwidth = G.cwidth; D.nin = nin;
         D.hd = hd; D.vd = vd; D.iw = S.w[pc]; D.ih = S.h[pc];
+        D.hu = hu; D.vu = vu; D.lin = F->linear != 0;
         for (int k = 0; k < nin; k++) { D.ipitch[k] = (int)S.pitch[G.in_plane[k]]; D.ioff[k] = S.off[G.in_plane[k]]; }
         D.ooff = (long long)G.off; D.opitch = (long long)G.pitch;
         D.cpr = (G.width + 15) / 16;
@@ -286,15 +374,16 @@ static int po_seg_fast(const PoParams &P, const PoSeg &S, const void *src, const
 {
     const bool packed = S.kind == DSVG_PIXOUT_YUYV || S.kind == DSVG_PIXOUT_UYVY;
     for (int k = 0; k < S.nin; k++) {
-        const uintptr_t m = packed && k > 0 && !S.hd ? 7 : 15;
+        const uintptr_t m = (packed && k > 0 && !S.hd) || S.hu ? 7 : 15;    // (8-byte loads)
         if ((((uintptr_t)src) | (uintptr_t)P.sfb | (uintptr_t)S.ioff[k] | (uintptr_t)S.ipitch[k]) & m) return 0;
     }
     return !((((uintptr_t)dst) | (uintptr_t)P.dfb | (uintptr_t)S.ooff | (uintptr_t)S.opitch) & 15);
 }
 
-template <int LAYOUT, bool WIDE> static void po_launch(const PoParams &P, dim3 grid, hipStream_t st, const uint8_t *src, uint8_t *dst, const int *tab)
+template <int LAYOUT, bool WIDE> static void po_launch(const PoParams &P, dim3 grid, hipStream_t st, const uint8_t *src, uint8_t *dst, const int *tab, bool up)
 {
-    hipLaunchKernelGGL((k_pixout<LAYOUT, WIDE>), grid, dim3(PO_THREADS), 0, st, P, src, dst, tab);
+    if (up) hipLaunchKernelGGL((k_pixout<LAYOUT, WIDE, true>), grid, dim3(PO_THREADS), 0, st, P, src, dst, tab);
+    else hipLaunchKernelGGL((k_pixout<LAYOUT, WIDE, false>), grid, dim3(PO_THREADS), 0, st, P, src, dst, tab);
 }
 
 int pixout_check(const dsvg_pixout *F, const PoSource &S, size_t dfb)
@@ -320,6 +409,7 @@ int launch_pixout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const
         const double in_c = (double)D.iw * D.ih, out_row = packed ? 4.0 * D.cwidth : (double)D.width * D.nin * (F->wide ? 2 : 1);
         bytes += (packed ? (double)D.width * D.rows + 2 * in_c : in_c * D.nin) + out_row * D.rows;
     }
+    const bool up = F->hu || F->vu;
     const int kid = layout == POL_PLANAR ? (F->wide ? KID_PIXOUT_PLANAR16 : KID_PIXOUT_PLANAR) : layout == POL_SEMI ? (F->wide ? KID_PIXOUT_SEMI16 : KID_PIXOUT_SEMI)
                   : layout == POL_YUYV ? KID_PIXOUT_YUYV : KID_PIXOUT_UYVY;
     if (pf) pf->begin(st, kid, bytes * n);
@@ -330,12 +420,12 @@ int launch_pixout(hipStream_t st, const dsvg_pixout *F, const PoSource &S, const
         const int *t = tab_d ? tab_d + 2 * (size_t)f0 : nullptr;
         const dim3 grid(nblocks, m);
         switch (layout * 2 + (F->wide ? 1 : 0)) {
-        case POL_PLANAR * 2:     po_launch<POL_PLANAR, false>(P, grid, st, s, d, t); break;
-        case POL_PLANAR * 2 + 1: po_launch<POL_PLANAR, true>(P, grid, st, s, d, t); break;
-        case POL_SEMI * 2:       po_launch<POL_SEMI, false>(P, grid, st, s, d, t); break;
-        case POL_SEMI * 2 + 1:   po_launch<POL_SEMI, true>(P, grid, st, s, d, t); break;
-        case POL_YUYV * 2:       po_launch<POL_YUYV, false>(P, grid, st, s, d, t); break;
-        default:                 po_launch<POL_UYVY, false>(P, grid, st, s, d, t); break;
+        case POL_PLANAR * 2:     po_launch<POL_PLANAR, false>(P, grid, st, s, d, t, up); break;
+        case POL_PLANAR * 2 + 1: po_launch<POL_PLANAR, true>(P, grid, st, s, d, t, up); break;
+        case POL_SEMI * 2:       po_launch<POL_SEMI, false>(P, grid, st, s, d, t, up); break;
+        case POL_SEMI * 2 + 1:   po_launch<POL_SEMI, true>(P, grid, st, s, d, t, up); break;
+        case POL_YUYV * 2:       po_launch<POL_YUYV, false>(P, grid, st, s, d, t, up); break;
+        default:                 po_launch<POL_UYVY, false>(P, grid, st, s, d, t, up); break;
         }
     }
     if (pf) pf->end(st);

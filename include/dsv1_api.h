@@ -402,7 +402,8 @@ int  dsv1_convert_clip(int device, const void *src, const dsv1_pix_format *pf, i
  * DSV1_CLIP_HELD clip stays unchanged until that batch's collect and submit does not wait.  The converted clip lives in buffers
  * the batch owns (one per call parity) and goes on as a held clip.  Plain batches, quality ladders (per source) and chain mode.
  * dsv1_batch_stage returns DSVG_ERR_ARG while a format is set.  Not offered: the drop-in dsv_enc and dsv_dec (it returns a host
- * DSV_FRAME), upsampling between YCbCr subsamplings.  RGB, in and out: the extension at the end of this file. */
+ * DSV_FRAME).  Another subsampling than the stream's, in and out: chroma resampling, below.  RGB, in and out: the extension at the
+ * end of this file. */
 int  dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf);
 /* dsv1_resladder_open for sources of format *pf (NULL or the default: dsv1_resladder_open itself).  The conversion runs on the
  * scaler's stream in front of the scales; a geometry of the source's size and dsv1_resladder_src_quality_enable read the CONVERTED
@@ -450,6 +451,48 @@ int  dsv1_export_clip(int device, const void *src, int w, int h, int subsamp, in
                       int on_device);
 void *dsv1_decbatch_ctx(dsv1_decbatch *d);      /* (ask again after every decode call: the batch builds a new context when its streams
                                                   * announce another block size while none of them holds a reference picture) */
+
+/* ---- extension: chroma resampling in the source and output passes (csrc/k_pixfmt.hip, csrc/k_pixout.hip; stated in numpy in
+ * tests/_chroma.py) ----
+ * The entry points above keep the subsampling (sources) or halve it (output) and refuse everything else; these take the other
+ * subsampling beside the format.  In both directions a pair with 4:1:1 on one side only is DSVG_ERR_ARG.
+ * IN, halving: a source of format *pf at src_subsamp into frames at `subsamp`.  Pairs: 4:4:4 -> 4:2:2 or 4:2:0, 4:2:2 -> 4:2:0; equal
+ * subsamplings are the pass above; upsampling on the way in is DSVG_ERR_ARG.  Every layout that is valid at src_subsamp
+ * (dsv1_pix_frame_bytes(pf, w, h, src_subsamp) != 0) is taken: planar for all three pairs, NV16 / NV61 / P210 and YUYV / UYVY for 4:2:2
+ * -> 4:2:0.  Every sample is reduced to 8 bits first (the depth rule above); the 8-bit chroma planes are then halved as the decoder
+ * output pass halves them -- the horizontal step, rounded to 8 bits, then the vertical one, the last column and the last row
+ * repeated -- in the same launch, with no intermediate plane:
+ *   dsv1_convert_clip_sub(buf, pf, src_subsamp -> subsamp) == dsv1_export_clip(dsv1_convert_clip(buf, pf, src_subsamp), planar 8-bit
+ *   tight, src_subsamp -> subsamp),
+ * the composition the RGB import follows.  Not offered: halving at the source depth before the reduction, dither.
+ * dsv1_batch_set_source_format_sub: dsv1_batch_set_source_format with its contract (ownership, staging, in flight, plain batches,
+ * quality ladders, chain mode) for clips at src_subsamp; the target is the batch's vidmeta.subsamp.  pf == NULL: tight planar 8-bit
+ * at src_subsamp.  The source setters replace each other.  The deinterlacer and the noise filter run behind the converter, at the
+ * batch's subsampling.  dsv1_resladder_open_src_sub: dsv1_resladder_open_src for such sources; the converted clip at src->subsamp
+ * stands for the source (scales, a geometry of the source's size, get_src_sse / get_src_ssim); dsv1_resladder_uploads counts the raw
+ * bytes.
+ * OUT, upsampling: frames decoded at `subsamp` written at out_subsamp.  dsv1_export_clip_up and dsv1_decbatch_set_output_format_up
+ * take every pair the calls above take and 4:2:0 -> 4:2:2, 4:2:0 -> 4:4:4, 4:2:2 -> 4:4:4; the layout must be valid at out_subsamp (4:2:2:
+ * planar, NV16 / NV61, P210, YUYV / UYVY; 4:4:4: planar).  `upsample` is DSV1_CHROMA_REPLICATE or DSV1_CHROMA_LINEAR (RGB, below),
+ * validated always and read only where something goes up.  The chroma planes are brought to the output's chroma dims ocw x och
+ * (rshift_up of w x h at out_subsamp) as the RGB output pass brings them to the luma grid.  REPLICATE: c[y >> dv][x >> dh], dv / dh 1
+ * where the vertical / horizontal shift drops.  LINEAR, centre-sited: vertically first where the vertical shift drops, o[2j] =
+ * (3 c[j] + c[max(j - 1, 0)] + 2) >> 2, o[2j+1] = (3 c[j] + c[min(j + 1, ch - 1)] + 2) >> 2, rows at or beyond och dropped; then the same
+ * over columns, on that 8-bit result, where the horizontal shift drops, columns at or beyond ocw dropped.  Each sample is then
+ * written by the output rule above (depth, msb_aligned, padding never written, the odd-width packed row).  So
+ * dsv1_rgb_export_clip(x at 4:2:0, rf) == dsv1_rgb_export_clip(dsv1_export_clip_up(x, planar 8-bit tight, 4:4:4, rf->upsample), rf).
+ * dsv1_decbatch_set_output_format_up: the contract of dsv1_decbatch_set_output_format (one pass in the place of the packing pass;
+ * dsv1_decbatch_out_frame_bytes follows; the int32 second pass writes its frames again; the setting outlives a rebuilt context; an
+ * invalid call leaves the setting in force as it was).  The three output setters replace each other.
+ * Not offered: chroma siting other than centre, the drop-in dsv_enc / dsv_dec. */
+int  dsv1_convert_clip_sub(int device, const void *src, const dsv1_pix_format *pf, int w, int h, int src_subsamp, int subsamp, int n,
+                           void *dst, int on_device);
+int  dsv1_batch_set_source_format_sub(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp);
+int  dsv1_resladder_open_src_sub(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp,
+                                 const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter);
+int  dsv1_export_clip_up(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsv1_pix_format *pf,
+                         int out_subsamp, int upsample, int on_device);
+int  dsv1_decbatch_set_output_format_up(dsv1_decbatch *d, const dsv1_pix_format *pf, int out_subsamp, int upsample);
 
 /* ---- extension: RGB, in and out (csrc/k_rgb.hip; stated in numpy in tests/_rgb.py) ----
  * What renderers, capture and displays hold: 8-bit RGB, packed or planar.  Unlike the pixel formats above this is no re-packing: a

@@ -337,7 +337,8 @@ int dsvg_pack_recons(dsvg_ctx *ctx, int n, const int *recon_slots, void *yuv_out
  * SEGMENT is one output plane and the planes of the decoded frame (0 Y, 1 U, 2 V) that feed it, in the order their samples appear:
  * PLAIN one plane, sample for sample; PAIR two planes interleaved; YUYV / UYVY all three as 4:2:2 macro-pixels.  hd / vd: the chroma
  * planes are halved horizontally / vertically on the way, o = (a + b + 1) >> 1 with the last column / row repeated, horizontally
- * first.  wide: a sample v is written as the little-endian 16-bit word v << shift. */
+ * first.  wide: a sample v is written as the little-endian 16-bit word v << shift.  A segment's width and rows are those of the
+ * output, after the halving or the doubling (hu / vu below). */
 enum { DSVG_PIXOUT_PLAIN, DSVG_PIXOUT_PAIR, DSVG_PIXOUT_YUYV, DSVG_PIXOUT_UYVY, DSVG_PIXOUT_RGB };
 typedef struct {
     int kind, nin, in_plane[3];
@@ -357,6 +358,8 @@ typedef struct {
     size_t planes_bytes;     /* where its last plane ends */
     dsvg_pixout_seg seg[3];
     dsvg_rgbout rgb;
+    int hu, vu, linear;      /* the chroma planes are doubled horizontally / vertically on the way, vertically first: centre-sited linear
+                                (linear != 0; include/dsv1_api.h, chroma resampling) or by replication */
 } dsvg_pixout;
 /* dsvg_pack_recons for an output format: slot recon_slots[i] -> frame out_index[i] (NULL: i) at out + out_index[i] * out_pitch, in
  * ONE pass over the bordered reconstructions (csrc/k_pixout.hip) that writes only the bytes of samples -- never the padding behind a
