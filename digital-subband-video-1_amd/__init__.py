@@ -52,6 +52,20 @@ class Dispatch(_C.Structure):
                 "hme": tuple(tuple(self.hme[l]) for l in range(max(n, 0)))}
 
 
+INV_NO_PATCH_PART, INV_NO_EDGE_TILES, INV_NO_FUSED_BORDER, INV_NO_XCD_ORDER = 1, 2, 4, 8      # DSVG_INV_NO_*
+INV_COVER_NONE, INV_COVER_WHOLE, INV_COVER_RECT, INV_COVER_FROM = 0, 1, 2, 3                 # DSVG_INV_COVER_*
+
+
+class InvStep(_C.Structure):
+    """dsvg_inv_step (include/dsvg.h): one launch of the inverse transform's plan"""
+    _fields_ = [("kernel", _C.c_int), ("grid", _C.c_int * 3), ("xcd", _C.c_int), ("args", _C.c_int * 4), ("bytes", _C.c_double),
+                ("cover", _C.c_int), ("cx", _C.c_int), ("cy", _C.c_int)]
+
+    def as_dict(self):
+        return {"kernel": lib().dsvg_prof_kernel_name(self.kernel).decode(), "grid": tuple(self.grid), "xcd": self.xcd, "args": tuple(self.args),
+                "bytes": self.bytes, "cover": (self.cover, self.cx, self.cy)}
+
+
 class ResRung(_C.Structure):
     """dsv1_res_rung: one geometry of a resolution ladder and its rate rungs"""
     _fields_ = [("width", _C.c_int), ("height", _C.c_int), ("nrates", _C.c_int), ("rates", _C.POINTER(Encoder))]
@@ -243,6 +257,7 @@ def lib():
         L.dsv1_resladder_denoise_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
+        L.dsvg_inv_plan.argtypes = [_C.c_int] * 9 + [_C.c_uint, _C.c_int, _C.POINTER(InvStep), _C.c_int, _C.POINTER(_C.c_int)]
         _lib = L
     return _lib
 
@@ -264,6 +279,16 @@ def dispatch_plan(w, h, fmt):
     d = Dispatch()
     _chk(lib().dsvg_dispatch_plan(w, h, fmt, _C.byref(d)), "dsvg_dispatch_plan")
     return d.as_dict()
+
+
+def inv_plan(w, h, fmt, group, isP, with_tail=1, insym=0, patch_kernel=0, fuse_border=0, switches=0, njobs=1):
+    """the launches of launch_inv_sbt for plane group `group` (0 luma, 1 the chroma pair) of njobs pictures of an encoder of this
+    geometry, with the A/B switches of the mask `switches` (INV_NO_*): ([step dicts in launch order], fb); needs no device"""
+    steps, fb = (InvStep * 5)(), _C.c_int(0)
+    n = lib().dsvg_inv_plan(w, h, fmt, group, isP, with_tail, insym, patch_kernel, fuse_border, switches, njobs, steps, 5, _C.byref(fb))
+    if n < 0:
+        _chk(n, "dsvg_inv_plan")
+    return [steps[i].as_dict() for i in range(n)], fb.value
 
 
 def make_encoder_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1, kbps=0, scd=1, ipct=50, pyrlevels=0, stabref=0,

@@ -53,10 +53,31 @@ void dispatch_note_fwd(int group, int mask);
 void dispatch_note_hme(const struct HmeArgs &A, int level, const HmeLevelPlan &P);
 void dispatch_note_csum(int csum);
 void dispatch_note_threads(int tail, int scan);      // the workgroup sizes launch_tail_q / the k_hz_scan launch took (0: not this one)
+// The inverse transform of planes [c0, c0+npl) of njobs pictures (all P or all I) as a pure function of the geometry, the caller's
+// flags and the A/B switches: every launch in order, decided once.  launch_inv_plan runs a plan and decides nothing; the border
+// question of enqueue_recon (InvPlan.fb) and the device-free query dsvg_inv_plan read the same plan.
+struct InvSwitches { bool no_patch_part, no_edge_tiles, no_fused_border, no_xcd_order; };   // DSV1_NO_PATCH_PART / _EDGE_TILES / _FUSED_BORDER / _XCD_ORDER
+const InvSwitches &inv_switches();                          // the process's own, read from the environment once
+struct InvStep {
+    int kid;                 // KID_INV_*: names the template instance
+    int gx, gy, gz;          // the grid; xcd: launched as tile_grid(gx, gy, gz) and decoded with mk_xcd_grid(gx, gy, gz), plain = DSV1_NO_XCD_ORDER
+    bool xcd, plain;
+    int bx, by;              // the block
+    size_t lds;              // dynamic LDS bytes
+    int a[4];                // the kernel's trailing integer arguments: tcx, -tcy-1 | er, eb | imax, jmax, jpart, fb
+    double bytes;            // the algorithmic bytes of Prof::begin
+    int cover, cx, cy;       // the level-3 cells of every plane whose pixels the step writes: DSVG_INV_COVER_*
+};
+struct InvPlan {
+    int n;
+    InvStep s[5];
+    int fb;                  // the chroma patch kernel writes the reconstruction's borders, of its own planes and of the luma plane (JobDev.ext)
+};
+InvPlan inv_sbt_plan(const SbtGeo3 &G, int njobs, int c0, int npl, int isP, int with_tail, int insym, int patch_kernel, int fuse_border, const InvSwitches &sw);
+void launch_inv_plan(hipStream_t st, const JobDev *jobs, const SbtGeo3 &G, int c0, int npl, const InvPlan &P, Prof *pf);
 void launch_inv_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, Prof *pf = nullptr, int with_tail = 1,
                     int insym = 0, int patch_kernel = 0,    // patch_kernel: sparse P pictures (flags valid, prediction given): unfiltered planes take k_inv_patch_c
-                    int fuse_border = 0);                   // the kernels also write the reconstruction's border (JobDev.ext) where inv_sbt_fuses_border says they can
-bool inv_sbt_fuses_border(const SbtGeo3 &G, int insym_c, int patch_kernel_c);   // the chroma patch kernel writes the borders of all three planes
+                    int fuse_border = 0);                   // the kernels also write the reconstruction's border (JobDev.ext) where the plan says they can (InvPlan.fb)
 void launch_inv54_all(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, Prof *pf = nullptr);   // levels 5..4 of all planes: then launch_inv_sbt(.., with_tail | 2)
 void launch_sbt_tail(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int inverse, Prof *pf = nullptr);
 void launch_fwd_mid4(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, bool llq, Prof *pf = nullptr);   // levels 4..5: launch_fwd_sbt does it itself unless fused >= 3

@@ -467,60 +467,81 @@ template <typename T> static int hmalloc(T **p, size_t n)
     return DSVG_OK;
 }
 
-extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int height, int subsamp,
-                                   int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots, int blk_w, int blk_h);
+// The geometry tables of a context as functions of the picture alone: block geometry (blk_w = 0: the encoder's own block size), frame and
+// coefficient layout, the transform's plane geometry with l1a, the motion compensation's.  dsvg_ctx_create_blk builds them here, and so
+// do the device-free queries below (dsvg_geom_check, dsvg_dispatch_plan, dsvg_inv_plan): what they say is said of a context's tables.
+struct CtxGeo {
+    int bw, bh, nbh, nbv;
+    FrameLayout L;
+    CoefLayout CL;
+    SbtGeo3 G;
+    McGeo MG;
+};
+static void make_ctx_geo(CtxGeo &o, int width, int height, int subsamp, int blk_w = 0, int blk_h = 0)
+{
+    block_geometry(width, height, &o.bw, &o.bh, &o.nbh, &o.nbv);
+    if (blk_w) {                                            // a decoder: the block size its stream announces
+        o.bw = blk_w; o.bh = blk_h;
+        o.nbh = (width + blk_w - 1) / blk_w; o.nbv = (height + blk_h - 1) / blk_h;
+    }
+    make_frame_layout(o.L, subsamp, width, height);
+    make_coef_layout(o.CL, subsamp, width, height);
+    const FrameLayout &L = o.L;
+    const CoefLayout &CL = o.CL;
+    McGeo &MG = o.MG;
+    memset(&MG, 0, sizeof(MG));
+    MG.blk_w = o.bw; MG.blk_h = o.bh; MG.nbh = o.nbh; MG.nbv = o.nbv; MG.hs = L.hs; MG.vs = L.vs;
+    for (int p = 0; p < 3; p++) {
+        make_sbt_geo(o.G.g[p], CL.w[p], CL.h[p], L.w[p], L.h[p], L.stride[p], L.off[p], CL.off[p], CL.s3off[p], CL.s1off[p], CL.s5off[p]);
+        HzPlane hp0;
+        make_hz_plane(hp0, CL.w[p], CL.h[p], 100, 1, p, o.nbh, o.nbv);
+        o.G.g[p].l1a = ((hp0.r[7].sw | hp0.r[7].base | hp0.r[8].base | hp0.r[9].base) & 3) == 0;
+        MG.w[p] = L.w[p]; MG.h[p] = L.h[p]; MG.stride[p] = L.stride[p]; MG.off[p] = L.off[p];
+        MG.cw_extra[p] = CL.w[p] > L.w[p];
+    }
+}
+
 // What dsvg_ctx_create (encoder block size) answers for a geometry, without a device: the resolution ladder refuses a geometry before
 // it allocates anything (dsv1_resladder_open).  The same checks, in the same order, as the context creation below.
-extern "C" int dsvg_geom_check(int width, int height, int subsamp)
+static int geom_check(int width, int height, int subsamp, CtxGeo &geo)
 {
     if (width < 32 || height < 32) { dsvg_set_error("bad ctx_create arguments"); return DSVG_ERR_ARG; }
     if (subsamp != 0x0 && subsamp != 0x4 && subsamp != 0x5 && subsamp != 0x8) { dsvg_set_error("bad subsampling"); return DSVG_ERR_ARG; }
-    int bw, bh, nbh, nbv;
-    block_geometry(width, height, &bw, &bh, &nbh, &nbv);
-    FrameLayout L;
-    CoefLayout CL;
-    make_frame_layout(L, subsamp, width, height);
-    make_coef_layout(CL, subsamp, width, height);
-    for (int p = 0; p < 3; p++) {
-        SbtGeo g;
-        make_sbt_geo(g, CL.w[p], CL.h[p], L.w[p], L.h[p], L.stride[p], L.off[p], CL.off[p], CL.s3off[p], CL.s1off[p], CL.s5off[p]);
-        if (!sbt_tail_supported(g)) { dsvg_set_error("plane %dx%d: LL5 band does not fit the LDS tail kernel", CL.w[p], CL.h[p]); return DSVG_ERR_UNSUPPORTED; }
-    }
+    make_ctx_geo(geo, width, height, subsamp);
+    const CoefLayout &CL = geo.CL;
+    for (int p = 0; p < 3; p++)
+        if (!sbt_tail_supported(geo.G.g[p])) { dsvg_set_error("plane %dx%d: LL5 band does not fit the LDS tail kernel", CL.w[p], CL.h[p]); return DSVG_ERR_UNSUPPORTED; }
     if ((width | height) & 1) { dsvg_set_error("odd luma dimensions are not supported (intra B4T needs even planes)"); return DSVG_ERR_UNSUPPORTED; }
     for (int p = 0; p < 3; p++) {
-        HzPlane hp; make_hz_plane(hp, CL.w[p], CL.h[p], 100, 0, p, nbh, nbv);
+        HzPlane hp; make_hz_plane(hp, CL.w[p], CL.h[p], 100, 0, p, geo.nbh, geo.nbv);
         if (hp.nchunks > hz_scan_items_max()) { dsvg_set_error("plane too large for the scan kernel"); return DSVG_ERR_UNSUPPORTED; }
     }
     return DSVG_OK;
 }
+extern "C" int dsvg_geom_check(int width, int height, int subsamp)
+{
+    CtxGeo geo;
+    return geom_check(width, height, subsamp, geo);
+}
 
 // What the forward launchers decide for an encoder context of this geometry (default block size and pyramid depth, the chroma
-// table of the motion search on): the geometry tables of dsvg_ctx_create_blk below, handed to the launchers' own decision functions
+// table of the motion search on): the context's geometry tables, handed to the launchers' own decision functions
 extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out)
 {
     if (!out) { dsvg_set_error("null argument"); return DSVG_ERR_ARG; }
-    const int rc = dsvg_geom_check(width, height, subsamp);
+    CtxGeo geo;
+    const int rc = geom_check(width, height, subsamp, geo);
     if (rc) return rc;
     memset(out, 0, sizeof(*out));
-    int nbh, nbv;
-    block_geometry(width, height, &out->blk_w, &out->blk_h, &nbh, &nbv);
+    out->blk_w = geo.bw; out->blk_h = geo.bh;
     HmeArgs A; memset(&A, 0, sizeof(A));
-    A.levels = auto_pyramid_levels(width, height, nbh, nbv);
-    make_frame_layout(A.L[0], subsamp, width, height);
+    A.levels = auto_pyramid_levels(width, height, geo.nbh, geo.nbv);
+    A.L[0] = geo.L;
     for (int l = 1; l <= A.levels; l++) make_frame_layout(A.L[l], subsamp, rsu(width, l), rsu(height, l));
-    A.nxb = nbh; A.nyb = nbv; A.nblk = nbh * nbv; A.blk_w = out->blk_w; A.blk_h = out->blk_h;
-    CoefLayout CL;
-    make_coef_layout(CL, subsamp, width, height);
-    SbtGeo3 G;
-    McGeo MG; memset(&MG, 0, sizeof(MG));
-    MG.blk_w = out->blk_w; MG.blk_h = out->blk_h; MG.nbh = nbh; MG.nbv = nbv; MG.hs = A.L[0].hs; MG.vs = A.L[0].vs;
-    for (int p = 0; p < 3; p++) {
-        make_sbt_geo(G.g[p], CL.w[p], CL.h[p], A.L[0].w[p], A.L[0].h[p], A.L[0].stride[p], A.L[0].off[p], CL.off[p], CL.s3off[p], CL.s1off[p], CL.s5off[p]);
-        MG.w[p] = A.L[0].w[p]; MG.h[p] = A.L[0].h[p]; MG.stride[p] = A.L[0].stride[p];
-    }
-    out->fusable = mc_fusable(MG) ? 1 : 0;
+    A.nxb = geo.nbh; A.nyb = geo.nbv; A.nblk = geo.nbh * geo.nbv; A.blk_w = geo.bw; A.blk_h = geo.bh;
+    out->fusable = mc_fusable(geo.MG) ? 1 : 0;
     // (code_batch_impl passes general_whole from the pictures' intra blocks; with FWD_FAST_INTRA it does not enter the decision)
-    for (int g = 0; g < 2; g++) out->fwd[g] = out->fusable ? fwd_general_mask(G, MG, g ? 1 : 0, g ? 2 : 1, 0) : -1;
+    for (int g = 0; g < 2; g++) out->fwd[g] = out->fusable ? fwd_general_mask(geo.G, geo.MG, g ? 1 : 0, g ? 2 : 1, 0) : -1;
     out->hme_levels = A.levels;
     for (int l = 0; l <= A.levels; l++) {
         const HmeLevelPlan P = hme_level_plan(A, l);
@@ -530,6 +551,31 @@ extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispa
     out->csum = hme_csum_plan(A, &fullx, &fully);
     out->tail_threads = out->scan_threads = -1;      // (a function of the jobs per launch, not of the geometry)
     return DSVG_OK;
+}
+
+// The inverse launcher's plan for one plane group of njobs pictures of an encoder context of this geometry (include/dsvg.h): inv_sbt_plan on
+// the context's geometry tables, with the switches the caller names instead of the environment's
+extern "C" int dsvg_inv_plan(int width, int height, int subsamp, int group, int isP, int with_tail, int insym, int patch_kernel, int fuse_border,
+                             unsigned switches, int njobs, dsvg_inv_step *steps, int cap, int *fb)
+{
+    if (group < 0 || group > 1 || njobs < 1 || cap < 0 || (cap > 0 && !steps)) { dsvg_set_error("bad inv_plan arguments"); return DSVG_ERR_ARG; }
+    CtxGeo geo;
+    const int rc = geom_check(width, height, subsamp, geo);
+    if (rc) return rc;
+    const InvSwitches sw = { (switches & DSVG_INV_NO_PATCH_PART) != 0, (switches & DSVG_INV_NO_EDGE_TILES) != 0,
+                             (switches & DSVG_INV_NO_FUSED_BORDER) != 0, (switches & DSVG_INV_NO_XCD_ORDER) != 0 };
+    const InvPlan P = inv_sbt_plan(geo.G, njobs, group ? 1 : 0, group ? 2 : 1, isP, with_tail, insym, patch_kernel, fuse_border, sw);
+    for (int i = 0; i < P.n && i < cap; i++) {
+        const InvStep &s = P.s[i];
+        dsvg_inv_step &o = steps[i];
+        o.kernel = s.kid;
+        o.grid[0] = s.gx; o.grid[1] = s.gy; o.grid[2] = s.gz; o.xcd = s.xcd ? (s.plain ? 2 : 1) : 0;
+        for (int k = 0; k < 4; k++) o.args[k] = s.a[k];
+        o.bytes = s.bytes;
+        o.cover = s.cover; o.cx = s.cx; o.cy = s.cy;
+    }
+    if (fb) *fb = P.fb;
+    return P.n;
 }
 
 extern "C" int dsvg_ctx_create(dsvg_ctx **out, int device, int width, int height, int subsamp,
@@ -558,39 +604,23 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
     c->w = width; c->h = height; c->fmt = subsamp;
     c->n_src = n_src_slots; c->n_recon = n_recon_slots; c->max_jobs = max_jobs; c->out_slots = out_slots;
     c->nwin = (out_slots + max_jobs - 1) / max_jobs + 1;
-    block_geometry(width, height, &c->bw, &c->bh, &c->nbh, &c->nbv);
-    if (blk_w) {                                            // a decoder: the block size its stream announces
-        c->bw = blk_w; c->bh = blk_h;
-        c->nbh = (width + blk_w - 1) / blk_w; c->nbv = (height + blk_h - 1) / blk_h;
+    {
+        CtxGeo geo;
+        make_ctx_geo(geo, width, height, subsamp, blk_w, blk_h);
+        c->bw = geo.bw; c->bh = geo.bh; c->nbh = geo.nbh; c->nbv = geo.nbv;
+        c->L[0] = geo.L; c->CL = geo.CL; c->G = geo.G; c->MG = geo.MG;
     }
     c->nblk = c->nbh * c->nbv;
     c->levels = pyramid_levels > 0 ? std::min(pyramid_levels, DSVG_MAX_PYRAMID) : auto_pyramid_levels(width, height, c->nbh, c->nbv);
-    make_frame_layout(c->L[0], subsamp, width, height);
     for (int l = 1; l <= c->levels; l++) make_frame_layout(c->L[l], subsamp, rsu(width, l), rsu(height, l));
-    make_coef_layout(c->CL, subsamp, width, height);
     const CoefLayout &CL = c->CL;
-    for (int p = 0; p < 3; p++) {
-        make_sbt_geo(c->G.g[p], CL.w[p], CL.h[p], c->L[0].w[p], c->L[0].h[p], c->L[0].stride[p], c->L[0].off[p],
-                     CL.off[p], CL.s3off[p], CL.s1off[p], CL.s5off[p]);
-        {
-            HzPlane hp0;
-            make_hz_plane(hp0, CL.w[p], CL.h[p], 100, 1, p, c->nbh, c->nbv);
-            c->G.g[p].l1a = ((hp0.r[7].sw | hp0.r[7].base | hp0.r[8].base | hp0.r[9].base) & 3) == 0;
-        }
+    for (int p = 0; p < 3; p++)
         if (!sbt_tail_supported(c->G.g[p])) {
             dsvg_set_error("plane %dx%d: LL5 band does not fit the LDS tail kernel", CL.w[p], CL.h[p]);
             delete c; return DSVG_ERR_UNSUPPORTED;
         }
-    }
     if ((width | height) & 1) { dsvg_set_error("odd luma dimensions are not supported (intra B4T needs even planes)"); delete c; return DSVG_ERR_UNSUPPORTED; }
-    McGeo &MG = c->MG;
-    memset(&MG, 0, sizeof(MG));
-    MG.blk_w = c->bw; MG.blk_h = c->bh; MG.nbh = c->nbh; MG.nbv = c->nbv; MG.hs = c->L[0].hs; MG.vs = c->L[0].vs;
-    for (int p = 0; p < 3; p++) {
-        MG.w[p] = c->L[0].w[p]; MG.h[p] = c->L[0].h[p]; MG.stride[p] = c->L[0].stride[p]; MG.off[p] = c->L[0].off[p];
-        MG.cw_extra[p] = CL.w[p] > c->L[0].w[p];
-    }
-    c->mc_fused = mc_fusable(MG) && !getenv("DSV1_NO_MC_FUSION");
+    c->mc_fused = mc_fusable(c->MG) && !getenv("DSV1_NO_MC_FUSION");
     c->no_inplace_pred = getenv("DSV1_NO_INPLACE_PRED") != nullptr;
     c->no_dec_sym = getenv("DSV1_NO_DEC_SYM") != nullptr;
     c->no_dec_sym_I = getenv("DSV1_NO_DEC_SYM_I") != nullptr;
@@ -1310,10 +1340,12 @@ static int enqueue_recon(dsvg_ctx *c, int nI, int n, int d0 = 0, int insym = 0, 
     if (n > nI) {
         const int symY = (insym >> 1) & 1, symC = (insym >> 2) & 1, pkY = symY && !c->no_patch_kernel, pkC = symC && !c->no_patch_kernel;
         // round 5: where the chroma patch kernel covers its planes completely (1080p, 4K, 720p, CIF ...) its edge patches write the borders
-        // of all three planes -- k_extend16 then only serves the I pictures of the step: one launch less in the chain of every P frame step
-        fused = lazy_border && inv_sbt_fuses_border(c->G, symC, pkC);
+        // of all three planes -- k_extend16 then only serves the I pictures of the step: one launch less in the chain of every P frame step.
+        // The chroma plan says so (fb), and is the one that is launched: the question is asked once
+        const InvPlan pc = inv_sbt_plan(c->G, n - nI, 1, 2, 1, wt, symC, pkC, lazy_border, inv_switches());
+        fused = pc.fb != 0;
         launch_inv_sbt(st, jd + nI, n - nI, c->G, 0, 1, 1, &c->prof, wt, symY, pkY);
-        launch_inv_sbt(st, jd + nI, n - nI, c->G, 1, 2, 1, &c->prof, wt, symC, pkC, fused);
+        launch_inv_plan(st, jd + nI, c->G, 1, 2, pc, &c->prof);
     }
     if (fused && c->stats_on) {
         // what the fused border writes (counted beside the tiles: bench.py prices k_inv_patch_c with it): per plane the rows above / below over the

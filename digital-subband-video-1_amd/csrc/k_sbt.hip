@@ -3248,7 +3248,7 @@ static inline dim3 grid3(int w3, int h3, int nz) { return dim3((w3 + 63) / 64, (
 // a logical gx x gy x gz grid for a kernel that decodes it with d_xcd_blk3 (DSV1_NO_XCD_ORDER: the A/B switch -- the
 // same kernels with the hardware's round-robin order, i.e. neighbouring tiles on different XCDs)
 static inline dim3 tile_grid(int gx, int gy, int gz) { return dim3(xcd_grid(gx * gy * gz)); }
-static inline int xcd_plain() { static const int v = getenv("DSV1_NO_XCD_ORDER") != nullptr; return v; }
+static inline int xcd_plain() { return inv_switches().no_xcd_order; }
 
 int sbt_tail_supported(const SbtGeo &g)
 {
@@ -3439,129 +3439,160 @@ void launch_inv54_all(hipStream_t st, const JobDev *jobs, int njobs, const SbtGe
     PE();
 }
 
-// Can the patch kernel of these pictures' chroma planes write the reconstruction's border (k_inv_patch_c, fb) -- its own planes' and the luma
-// plane's?  Every patch of the chroma planes must be the patch kernel's (no ragged strips for the tile kernel), both chroma planes alike, the
-// luma plane an exact multiple of them, and the widths / strides what the 16-byte border stores need.
-bool inv_sbt_fuses_border(const SbtGeo3 &G, int insym_c, int patch_kernel_c)
+// The A/B switches that enter the inverse plan (and the XCD order of the forward kernels): the process's own, read once -- this
+// sits on the enqueue path.  inv_sbt_plan itself takes them as an argument, so a caller can ask it about any setting.
+const InvSwitches &inv_switches()
 {
-    static const bool off = getenv("DSV1_NO_FUSED_BORDER") != nullptr || getenv("DSV1_NO_PATCH_PART") != nullptr;   // (A/B; read once: this sits on the enqueue path)
-    if (off || !insym_c || !patch_kernel_c) return false;
+    static const InvSwitches sw = { getenv("DSV1_NO_PATCH_PART") != nullptr, getenv("DSV1_NO_EDGE_TILES") != nullptr,
+                                    getenv("DSV1_NO_FUSED_BORDER") != nullptr, getenv("DSV1_NO_XCD_ORDER") != nullptr };
+    return sw;
+}
+
+// Can the patch kernel of these pictures' chroma planes write the reconstruction's border (k_inv_patch_c, fb) -- its own planes' and the luma
+// plane's?  Every patch of the chroma planes must be the patch kernel's (the plan so far: a patch step over the whole planes, no strips for the
+// tile kernel), both chroma planes alike, the luma plane an exact multiple of them, and the widths / strides what the 16-byte border stores need.
+static bool inv_sbt_fuses_border(const SbtGeo3 &G, const InvPlan &P)
+{
     const SbtGeo &g = G.g[1], &gy = G.g[0];
+    bool whole = false;
+    for (int i = 0; i < P.n; i++) {
+        if (P.s[i].cover == DSVG_INV_COVER_FROM) return false;
+        if (P.s[i].kid == KID_INV_PATCH_C) whole = P.s[i].a[0] == g.w3 && P.s[i].a[1] == g.h3;
+    }
+    if (!whole) return false;
     for (int c = 1; c <= 2; c++) {
         const SbtGeo &q = G.g[c];
         if (q.pw != g.pw || q.ph != g.ph || q.w3 != g.w3 || q.h3 != g.h3 || (q.pw & 15) != 0 || (q.pstride & 15) != 0) return false;
-        const int fullc = q.pw / 8, fullr = q.ph / 8;
-        const bool part4 = fullr == q.h3 - 1 && fullr >= 1 && (q.ph & 7) == 4 && (q.H & 7) == 4;
-        if (fullc < q.w3 || !(fullr >= q.h3 || part4)) return false;
     }
     if (g.pw < 16 || g.ph < 8 || gy.pw % g.pw || gy.ph % g.ph || (gy.pstride & 15) != 0 || (gy.pw & 15) != 0) return false;
     const int hr = gy.pw / g.pw, vr = gy.ph / g.ph;
     return (hr == 1 || hr == 2 || hr == 4) && (vr == 1 || vr == 2);
 }
 
-void launch_inv_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, Prof *pf, int with_tail,
-                    int insym, int patch_kernel, int fuse_border)
+InvPlan inv_sbt_plan(const SbtGeo3 &G, int njobs, int c0, int npl, int isP, int with_tail, int insym, int patch_kernel, int fuse_border, const InvSwitches &sw)
 {
-    const int fb = (fuse_border && isP && c0 == 1 && npl == 2 && inv_sbt_fuses_border(G, insym, patch_kernel)) ? 1 : 0;
+    InvPlan P;
+    memset(&P, 0, sizeof(P));
     const SbtGeo &g = G.g[c0];
     const int nz = njobs * npl;
     const double smp = (double)g.W * g.H * nz, s3 = (double)g.w3 * g.h3 * nz;
     const bool filt = (c0 == 0);
+    const int tgx = (g.w3 + IT_TX - 1) / IT_TX, tgy = (g.h3 + IT_TY - 1) / IT_TY;       // the tile grid of the planes
+    // a gx x gy x nz grid of 256 threads; xcd: in XCD order
+    const auto step = [&](int kid, int gx, int gy, double bytes, bool xcd = false) -> InvStep & {
+        InvStep &s = P.s[P.n++];
+        s.kid = kid; s.gx = gx; s.gy = gy; s.gz = nz; s.bx = 256; s.by = 1; s.bytes = bytes;
+        s.xcd = xcd; s.plain = xcd && sw.no_xcd_order;
+        return s;
+    };
+    const auto whole = [&](int kid, double bytes) { step(kid, tgx, tgy, bytes).cover = DSVG_INV_COVER_WHOLE; };
+    // every tile from tile column tx / tile row ty on: right strip and bottom strip in one L-shaped launch
+    const auto strips = [&](int kid, int tx, int ty, double bytes) {
+        InvStep &s = step(kid, (tgx - tx) * tgy + tx * (tgy - ty), 1, bytes);
+        s.a[0] = tx; s.a[1] = -ty - 1;
+        s.cover = DSVG_INV_COVER_FROM; s.cx = tx; s.cy = ty;
+    };
     if (with_tail & 1) {
-        PB(KID_INV_TAIL, (double)g.w5 * g.h5 * nz * 8.0);
-        hipLaunchKernelGGL(k_inv_tail, dim3(nz), dim3(TAIL_THREADS), (size_t)g.w5 * g.h5 * 4, st, jobs, G, c0, npl);
-        PE();
+        InvStep &s = step(KID_INV_TAIL, nz, 1, (double)g.w5 * g.h5 * nz * 8.0);
+        s.gz = 1; s.bx = TAIL_THREADS; s.lds = (size_t)g.w5 * g.h5 * 4;
     }
-    if (!(with_tail & 2)) {   // levels 5..4 (LL5 -> LL3) for every picture type (with_tail & 2: launch_inv54_all did them for all planes)
-        const dim3 mg((g.w5 + IT_TX - 1) / IT_TX, (g.h5 + IT_TY - 1) / IT_TY, nz);
-        PB(filt ? KID_INV_TILE_54_F : KID_INV_TILE_54, s3 * 8.0);
-        if (filt) hipLaunchKernelGGL((k_inv_haar_tile<true, 2, false>), mg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-        else      hipLaunchKernelGGL((k_inv_haar_tile<false, 2, false>), mg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-        PE();
+    if (!(with_tail & 2))     // levels 5..4 (LL5 -> LL3) for every picture type (with_tail & 2: launch_inv54_all did them for all planes)
+        step(filt ? KID_INV_TILE_54_F : KID_INV_TILE_54, (g.w5 + IT_TX - 1) / IT_TX, (g.h5 + IT_TY - 1) / IT_TY, s3 * 8.0);
+    if (!isP) {
+        step(insym ? (filt ? KID_INV_TILE_S1_SYM_F : KID_INV_TILE_S1_SYM) : (filt ? KID_INV_TILE_S1_F : KID_INV_TILE_S1), tgx, tgy, smp * (insym ? 1.4 : 2.0));
+        step(insym ? KID_INV_B4T_SYM : KID_INV_B4T, ((g.W >> 1) + BT_CX - 1) / BT_CX, ((g.H >> 1) + BT_CY - 1) / BT_CY,
+             smp * (insym ? 3.5 : 5.0), true).cover = DSVG_INV_COVER_WHOLE;            // LL1 1 + details 3 (symbols: 1.5) in, 1 out
+        return P;
     }
-    const dim3 tg((g.w3 + IT_TX - 1) / IT_TX, (g.h3 + IT_TY - 1) / IT_TY, nz);
-    if (isP) {
-        // 4 B/sample coefficients + 1 B prediction in, 1 B out; from the symbol planes (insym): prediction 1 + reconstruction 1 +
-        // the level-2/3 symbols 0.47 + flags -- the level-1 symbols (1.5 B/sample) are only fetched for flagged patches
-        if (insym && !filt && patch_kernel) {
-            // no smoothing filter: patches are closed computations -- the lean kernel takes every whole patch that does not lie
-            // in a tile of the last tile row / column with a ragged edge, the tile kernel those strips
-            const int fullc = G.g[c0].pw / 8, fullr = G.g[c0].ph / 8;
-            // a last patch row of exactly four pixel rows (plane height 8k + 4 -- 1080 lines of 4:2:0 / 4:2:2 chroma: 540) stays with the lean
-            // kernel (k_inv_patch_c, jpart); every plane of the launch must have it (they share one grid): 4:2:0 and 4:4:4 do
-            static const bool no_part = getenv("DSV1_NO_PATCH_PART") != nullptr;       // (A/B)
-            bool part4 = !no_part && fullr == g.h3 - 1 && fullr >= 1;
-            for (int c = c0; c < c0 + npl; c++) part4 = part4 && G.g[c].ph == G.g[c0].ph && (G.g[c].ph & 7) == 4 && (G.g[c].H & 7) == 4 && G.g[c].h3 == g.h3;
-            const int tcx = fullc >= g.w3 ? (int)tg.x : fullc / IT_TX, tcy = (fullr >= g.h3 || part4) ? (int)tg.y : fullr / IT_TY;   // first tile column / row of the strips
-            const int imax = tcx >= (int)tg.x ? g.w3 : tcx * IT_TX, jmax = tcy >= (int)tg.y ? g.h3 : tcy * IT_TY;
-            if (imax > 0 && jmax > 0) {
-                PB(KID_INV_PATCH_C, 64.0 * imax * jmax * nz * 2.0);          // prediction in, reconstruction out (+ 5 B per patch: LL3, flag)
-                const int cgx = (imax + 63) / 64, cgy = (jmax + 3) / 4;
-                hipLaunchKernelGGL(k_inv_patch_c, tile_grid(cgx, cgy, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, imax, jmax, mk_xcd_grid(cgx, cgy, nz), xcd_plain(),
-                                   part4 ? g.h3 - 1 : -1, fb);
-                PE();
-            }
-            if (tcx < (int)tg.x || tcy < (int)tg.y) {
-                PB(KID_INV_TILE_PIX_SYM, (smp - 64.0 * imax * jmax * nz) * 2.5);
-                // (right strip and bottom strip in one L-shaped launch)
-                const int nrest = ((int)tg.x - tcx) * (int)tg.y + tcx * ((int)tg.y - tcy);
-                hipLaunchKernelGGL((k_inv_haar_tile<false, 0, true>), dim3(nrest, 1, nz), dim3(256), 0, st, jobs, G, c0, npl, tcx, -tcy - 1);
-                PE();
-            }
-        } else if (insym) {
-            // sparse pictures (patch_kernel: every job has flags and a reference) on a geometry with aligned level-1 rows: the
-            // tiles whose cells and halo are complete (not in the last tile column / row, nor within a cell of the band's end)
-            // take the fast body as a kernel of its own, the general kernel the right and bottom strips
-            const int fx = (patch_kernel && g.l1a && g.w3 >= IT_TX + 2) ? (g.w3 - IT_TX - 2) / IT_TX + 1 : 0;
-            const int fy = (patch_kernel && g.l1a && g.h3 >= IT_TY + 2) ? (g.h3 - IT_TY - 2) / IT_TY + 1 : 0;
-            static const bool no_er = getenv("DSV1_NO_EDGE_TILES") != nullptr;
-            if (fx > 0 && fy > 0) {
-                // the last tile column too, when it ends exactly where the band ends and every cell of every level is complete
-                const bool er = !no_er && fx == (int)tg.x - 1 && g.w3 == (int)tg.x * IT_TX && (g.W & 7) == 0;
-                // ... and the last tile row, when it is the only one left and every cell row is complete
-                const bool eb = !no_er && fy == (int)tg.y - 1 && (g.H & 7) == 0;
-                const int fxg = er ? fx + 1 : fx, fyg = eb ? fy + 1 : fy;      // tile columns / rows the fast kernel takes
-                const double fsmp = 64.0 * std::min(fxg * IT_TX, g.w3) * std::min(fyg * IT_TY, g.h3) * nz;   // samples of the fast tiles
-                PB(filt ? KID_INV_P_TILE_F : KID_INV_P_TILE, fsmp * 2.5);
-                const dim3 pg = tile_grid(fxg, fyg, nz);
-                if (filt) hipLaunchKernelGGL((k_inv_p_tile<true>), pg, dim3(256), 0, st, jobs, G, c0, npl, er ? fx : -1, eb ? fy : -1, mk_xcd_grid(fxg, fyg, nz), xcd_plain());
-                else      hipLaunchKernelGGL((k_inv_p_tile<false>), pg, dim3(256), 0, st, jobs, G, c0, npl, er ? fx : -1, eb ? fy : -1, mk_xcd_grid(fxg, fyg, nz), xcd_plain());
-                PE();
-                const int nrest = ((int)tg.x - fxg) * (int)tg.y + fxg * ((int)tg.y - fyg);      // right strip + bottom strip, one launch
-                if (nrest > 0) {
-                    PB(filt ? KID_INV_TILE_PIX_SYM_F : KID_INV_TILE_PIX_SYM, (smp - fsmp) * 2.5);
-                    if (filt) hipLaunchKernelGGL((k_inv_haar_tile<true, 0, true>), dim3(nrest, 1, nz), dim3(256), 0, st, jobs, G, c0, npl, fxg, -fyg - 1);
-                    else      hipLaunchKernelGGL((k_inv_haar_tile<false, 0, true>), dim3(nrest, 1, nz), dim3(256), 0, st, jobs, G, c0, npl, fxg, -fyg - 1);
-                    PE();
-                }
-                return;
-            }
-            PB(filt ? KID_INV_TILE_PIX_SYM_F : KID_INV_TILE_PIX_SYM, smp * 2.5);
-            if (filt) hipLaunchKernelGGL((k_inv_haar_tile<true, 0, true>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-            else      hipLaunchKernelGGL((k_inv_haar_tile<false, 0, true>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-            PE();
-        } else {
-            PB(filt ? KID_INV_TILE_PIX_F : KID_INV_TILE_PIX, smp * 6.0);
-            if (filt) hipLaunchKernelGGL((k_inv_haar_tile<true, 0, false>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-            else      hipLaunchKernelGGL((k_inv_haar_tile<false, 0, false>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-            PE();
+    // 4 B/sample coefficients + 1 B prediction in, 1 B out; from the symbol planes (insym): prediction 1 + reconstruction 1 +
+    // the level-2/3 symbols 0.47 + flags -- the level-1 symbols (1.5 B/sample) are only fetched for flagged patches
+    if (insym && !filt && patch_kernel) {
+        // no smoothing filter: patches are closed computations -- the lean kernel takes every whole patch that does not lie
+        // in a tile of the last tile row / column with a ragged edge, the tile kernel those strips
+        const int fullc = g.pw / 8, fullr = g.ph / 8;
+        // a last patch row of exactly four pixel rows (plane height 8k + 4 -- 1080 lines of 4:2:0 / 4:2:2 chroma: 540) stays with the lean
+        // kernel (k_inv_patch_c, jpart); every plane of the launch must have it (they share one grid): 4:2:0 and 4:4:4 do
+        bool part4 = !sw.no_patch_part && fullr == g.h3 - 1 && fullr >= 1;
+        for (int c = c0; c < c0 + npl; c++) part4 = part4 && G.g[c].ph == g.ph && (G.g[c].ph & 7) == 4 && (G.g[c].H & 7) == 4 && G.g[c].h3 == g.h3;
+        const int tcx = fullc >= g.w3 ? tgx : fullc / IT_TX, tcy = (fullr >= g.h3 || part4) ? tgy : fullr / IT_TY;   // first tile column / row of the strips
+        const int imax = tcx >= tgx ? g.w3 : tcx * IT_TX, jmax = tcy >= tgy ? g.h3 : tcy * IT_TY;
+        InvStep *patch = nullptr;
+        if (imax > 0 && jmax > 0) {
+            // prediction in, reconstruction out (+ 5 B per patch: LL3, flag)
+            patch = &step(KID_INV_PATCH_C, (imax + 63) / 64, (jmax + 3) / 4, 64.0 * imax * jmax * nz * 2.0, true);
+            patch->bx = 64; patch->by = 4;
+            patch->a[0] = imax; patch->a[1] = jmax; patch->a[2] = part4 ? g.h3 - 1 : -1;
+            patch->cover = DSVG_INV_COVER_RECT; patch->cx = imax; patch->cy = jmax;
         }
-    } else {
-        PB(insym ? (filt ? KID_INV_TILE_S1_SYM_F : KID_INV_TILE_S1_SYM) : (filt ? KID_INV_TILE_S1_F : KID_INV_TILE_S1), smp * (insym ? 1.4 : 2.0));
-        if (insym) {
-            if (filt) hipLaunchKernelGGL((k_inv_haar_tile<true, 1, true>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-            else      hipLaunchKernelGGL((k_inv_haar_tile<false, 1, true>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-        } else {
-            if (filt) hipLaunchKernelGGL((k_inv_haar_tile<true, 1, false>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
-            else      hipLaunchKernelGGL((k_inv_haar_tile<false, 1, false>), tg, dim3(256), 0, st, jobs, G, c0, npl, 0, 0);
+        if (tcx < tgx || tcy < tgy) strips(KID_INV_TILE_PIX_SYM, tcx, tcy, (smp - 64.0 * imax * jmax * nz) * 2.5);
+        // (DSV1_NO_PATCH_PART switches the fused border off with the part row, whatever the planes' heights)
+        if (patch && fuse_border && c0 == 1 && npl == 2 && !sw.no_fused_border && !sw.no_patch_part && inv_sbt_fuses_border(G, P)) P.fb = patch->a[3] = 1;
+    } else if (insym) {
+        // sparse pictures (patch_kernel: every job has flags and a reference) on a geometry with aligned level-1 rows: the
+        // tiles whose cells and halo are complete (not in the last tile column / row, nor within a cell of the band's end)
+        // take the fast body as a kernel of its own, the general kernel the right and bottom strips
+        const int fx = (patch_kernel && g.l1a && g.w3 >= IT_TX + 2) ? (g.w3 - IT_TX - 2) / IT_TX + 1 : 0;
+        const int fy = (patch_kernel && g.l1a && g.h3 >= IT_TY + 2) ? (g.h3 - IT_TY - 2) / IT_TY + 1 : 0;
+        if (fx > 0 && fy > 0) {
+            // the last tile column too, when it ends exactly where the band ends and every cell of every level is complete
+            const bool er = !sw.no_edge_tiles && fx == tgx - 1 && g.w3 == tgx * IT_TX && (g.W & 7) == 0;
+            // ... and the last tile row, when it is the only one left and every cell row is complete
+            const bool eb = !sw.no_edge_tiles && fy == tgy - 1 && (g.H & 7) == 0;
+            const int fxg = er ? fx + 1 : fx, fyg = eb ? fy + 1 : fy;      // tile columns / rows the fast kernel takes
+            const int fcx = std::min(fxg * IT_TX, g.w3), fcy = std::min(fyg * IT_TY, g.h3);
+            const double fsmp = 64.0 * fcx * fcy * nz;                     // samples of the fast tiles
+            InvStep &s = step(filt ? KID_INV_P_TILE_F : KID_INV_P_TILE, fxg, fyg, fsmp * 2.5, true);
+            s.a[0] = er ? fx : -1; s.a[1] = eb ? fy : -1;
+            s.cover = DSVG_INV_COVER_RECT; s.cx = fcx; s.cy = fcy;
+            if (fxg < tgx || fyg < tgy) strips(filt ? KID_INV_TILE_PIX_SYM_F : KID_INV_TILE_PIX_SYM, fxg, fyg, (smp - fsmp) * 2.5);
+        } else
+            whole(filt ? KID_INV_TILE_PIX_SYM_F : KID_INV_TILE_PIX_SYM, smp * 2.5);
+    } else
+        whole(filt ? KID_INV_TILE_PIX_F : KID_INV_TILE_PIX, smp * 6.0);
+    return P;
+}
+
+// run a plan: one launch per step, each template instance of an inverse kernel named here and nowhere else
+void launch_inv_plan(hipStream_t st, const JobDev *jobs, const SbtGeo3 &G, int c0, int npl, const InvPlan &P, Prof *pf)
+{
+#define INV_TILE(kid, ...) case kid: hipLaunchKernelGGL((k_inv_haar_tile<__VA_ARGS__>), grid, block, 0, st, jobs, G, c0, npl, s.a[0], s.a[1]); break
+#define INV_P_TILE(kid, F) case kid: hipLaunchKernelGGL((k_inv_p_tile<F>), grid, block, 0, st, jobs, G, c0, npl, s.a[0], s.a[1], mk_xcd_grid(s.gx, s.gy, s.gz), (int)s.plain); break
+#define INV_B4T(kid, S)    case kid: hipLaunchKernelGGL((k_inv_b4t<S>), grid, block, 0, st, jobs, G, c0, npl, mk_xcd_grid(s.gx, s.gy, s.gz), (int)s.plain); break
+    for (int i = 0; i < P.n; i++) {
+        const InvStep &s = P.s[i];
+        const dim3 grid = s.xcd ? tile_grid(s.gx, s.gy, s.gz) : dim3(s.gx, s.gy, s.gz), block(s.bx, s.by);
+        PB(s.kid, s.bytes);
+        switch (s.kid) {
+        case KID_INV_TAIL: hipLaunchKernelGGL(k_inv_tail, grid, block, s.lds, st, jobs, G, c0, npl); break;
+        INV_TILE(KID_INV_TILE_54_F, true, 2, false);
+        INV_TILE(KID_INV_TILE_54, false, 2, false);
+        case KID_INV_PATCH_C:
+            hipLaunchKernelGGL(k_inv_patch_c, grid, block, 0, st, jobs, G, c0, npl, s.a[0], s.a[1], mk_xcd_grid(s.gx, s.gy, s.gz), (int)s.plain, s.a[2], s.a[3]);
+            break;
+        INV_TILE(KID_INV_TILE_PIX_SYM, false, 0, true);
+        INV_P_TILE(KID_INV_P_TILE_F, true);
+        INV_P_TILE(KID_INV_P_TILE, false);
+        INV_TILE(KID_INV_TILE_PIX_SYM_F, true, 0, true);
+        INV_TILE(KID_INV_TILE_PIX_F, true, 0, false);
+        INV_TILE(KID_INV_TILE_PIX, false, 0, false);
+        INV_TILE(KID_INV_TILE_S1_SYM_F, true, 1, true);
+        INV_TILE(KID_INV_TILE_S1_SYM, false, 1, true);
+        INV_TILE(KID_INV_TILE_S1_F, true, 1, false);
+        INV_TILE(KID_INV_TILE_S1, false, 1, false);
+        INV_B4T(KID_INV_B4T_SYM, true);
+        INV_B4T(KID_INV_B4T, false);
         }
         PE();
-        const dim3 bg(((g.W >> 1) + BT_CX - 1) / BT_CX, ((g.H >> 1) + BT_CY - 1) / BT_CY, nz);
-        PB(insym ? KID_INV_B4T_SYM : KID_INV_B4T, smp * (insym ? 3.5 : 5.0));           // LL1 1 + details 3 (symbols: 1.5) in, 1 out
-        if (insym) hipLaunchKernelGGL((k_inv_b4t<true>), tile_grid(bg.x, bg.y, bg.z), dim3(256), 0, st, jobs, G, c0, npl, mk_xcd_grid((int)bg.x, (int)bg.y, (int)bg.z), xcd_plain());
-        else       hipLaunchKernelGGL((k_inv_b4t<false>), tile_grid(bg.x, bg.y, bg.z), dim3(256), 0, st, jobs, G, c0, npl, mk_xcd_grid((int)bg.x, (int)bg.y, (int)bg.z), xcd_plain());
-        PE();
     }
+#undef INV_TILE
+#undef INV_P_TILE
+#undef INV_B4T
+}
+
+void launch_inv_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, Prof *pf, int with_tail,
+                    int insym, int patch_kernel, int fuse_border)
+{
+    launch_inv_plan(st, jobs, G, c0, npl, inv_sbt_plan(G, njobs, c0, npl, isP, with_tail, insym, patch_kernel, fuse_border, inv_switches()), pf);
 }
 
 void sbt_set_func_attributes()

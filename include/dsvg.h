@@ -429,8 +429,8 @@ int dsvg_prof_get(dsvg_ctx *ctx, int kid, double *ms, long *launches, double *al
  * dsvg_dispatch_last: what launch_fwd_sbt / launch_hme / launch_tail_q / the scan launch last decided in this process (the
  * launchers fill it in; fusable: whether the last P plane group took the fused kernels).
  * dsvg_dispatch_plan: what they decide for an encoder context of this geometry, without a device -- the launchers' own decision
- * functions on geometry tables built as dsvg_ctx_create builds them (a second set-up of the same tables: what ties it to a live
- * context is the comparison of both queries on the GPU); tail_threads / scan_threads = -1 (they depend on the jobs per launch). */
+ * functions on the geometry tables of dsvg_ctx_create (one set-up, shared with the context; the GPU tests still compare both
+ * queries on a live context); tail_threads / scan_threads = -1 (they depend on the jobs per launch). */
 #define DSVG_FWD_WHOLE  1
 #define DSVG_FWD_TOP    2
 #define DSVG_FWD_BOTTOM 4
@@ -449,6 +449,39 @@ typedef struct dsvg_dispatch {
 } dsvg_dispatch;
 int dsvg_dispatch_last(dsvg_dispatch *out);
 int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out);
+
+/* The launches of the inverse transform (tests): what the launcher of the inverse kernels (launch_inv_sbt) does for one plane group of
+ * njobs pictures of an encoder context of this geometry, without a device -- the launcher's own plan (inv_sbt_plan: the launcher runs
+ * its steps and decides nothing), on the geometry tables of dsvg_ctx_create.  group: 0 luma, 1 the chroma pair; isP, with_tail
+ * (bit 0: the LDS tail first, bit 1: levels 5..4 were done for all planes in one launch), insym (details from the symbol planes),
+ * patch_kernel (sparse P pictures: flags and prediction given) and fuse_border (the caller lets the chroma patch kernel write the
+ * reconstruction's borders where it can) as the callers pass them; switches: a mask of DSVG_INV_NO_* for the A/B switches of the
+ * same names (DSV1_NO_*), whatever the environment says.  Writes the first min(steps, cap) steps in launch order and *fb (1: the
+ * chroma patch kernel writes the borders of all three planes; fb may be null) and returns the number of steps, or a negative
+ * DSVG_ERR_* for a geometry dsvg_ctx_create refuses.
+ * A step: kernel = the index of dsvg_prof_kernel_name; the grid (xcd != 0: launched in one dimension, 8 * ceil(x * y * z / 8) workgroups
+ * that decode the logical grid, 1: in XCD order, 2: in the hardware's order, DSVG_INV_NO_XCD_ORDER); args = the kernel's trailing integer arguments (k_inv_haar_tile: first tile column of the
+ * strips, -(first tile row) - 1, or 0, 0 for its whole grid; k_inv_p_tile: the edge tile column / row it also takes or -1;
+ * k_inv_patch_c: imax, jmax, jpart, fb); bytes = the algorithmic bytes the profiler books; cover = the level-3 cells of every plane
+ * of the group whose pixels the step writes: NONE, the WHOLE plane, the RECTangle of cells [0, cx) x [0, cy), or every tile FROM
+ * tile column cx or tile row cy on (tiles of 16 x 8 cells). */
+#define DSVG_INV_NO_PATCH_PART   1
+#define DSVG_INV_NO_EDGE_TILES   2
+#define DSVG_INV_NO_FUSED_BORDER 4
+#define DSVG_INV_NO_XCD_ORDER    8
+#define DSVG_INV_COVER_NONE  0
+#define DSVG_INV_COVER_WHOLE 1
+#define DSVG_INV_COVER_RECT  2
+#define DSVG_INV_COVER_FROM  3
+typedef struct dsvg_inv_step {
+    int kernel;
+    int grid[3], xcd;
+    int args[4];
+    double bytes;
+    int cover, cx, cy;
+} dsvg_inv_step;
+int dsvg_inv_plan(int width, int height, int subsamp, int group, int isP, int with_tail, int insym, int patch_kernel, int fuse_border,
+                  unsigned switches, int njobs, dsvg_inv_step *steps, int cap, int *fb);
 
 #ifdef __cplusplus
 }
