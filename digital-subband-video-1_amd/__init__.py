@@ -120,6 +120,15 @@ class Denoise(_C.Structure):
         super().__init__(luma, chroma)
 
 
+class BlockInfo(_C.Structure):
+    """dsv1_blockinfo: one block's side information (packet_blockinfo, draw_info_clip)"""
+    _fields_ = [("mvx", _C.c_int16), ("mvy", _C.c_int16), ("mode", _C.c_uint8), ("submask", _C.c_uint8), ("stable", _C.c_uint8),
+                ("reserved", _C.c_uint8)]
+
+
+BLOCKINFO_DTYPE = _np.dtype([("mvx", "<i2"), ("mvy", "<i2"), ("mode", "u1"), ("submask", "u1"), ("stable", "u1"), ("reserved", "u1")])
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -258,6 +267,11 @@ def lib():
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         L.dsvg_inv_plan.argtypes = [_C.c_int] * 9 + [_C.c_uint, _C.c_int, _C.POINTER(InvStep), _C.c_int, _C.POINTER(_C.c_int)]
+        L.dsv1_decbatch_set_draw_info.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_packet_blockinfo.argtypes = [_C.c_void_p, _C.c_size_t, _C.c_int, _C.c_int, _C.POINTER(_C.c_int), _C.POINTER(_C.c_int),
+                                            _C.POINTER(_C.c_int), _C.c_void_p, _C.c_size_t]
+        L.dsv1_draw_info_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int,
+                                          _C.c_int]
         _lib = L
     return _lib
 
@@ -793,6 +807,45 @@ def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=Non
     return res
 
 
+def packet_blockinfo(packet, w, h, n=None):
+    """the side information of one picture packet of a w x h stream (dsv1_packet_blockinfo; host only): (blk_w, blk_h, has_ref, table),
+    table a numpy array of BLOCKINFO_DTYPE, one entry per block in raster order (mode 0 inter / 1 intra; without a reference only
+    `stable` is filled).  n: the room offered (None: enough for 16 x 16 blocks).  ValueError for anything but a well-formed picture
+    packet, or too small an n."""
+    data = _np.frombuffer(bytes(packet), dtype=_np.uint8)
+    room = ((w + 15) // 16) * ((h + 15) // 16) if n is None else n
+    tab = _np.zeros(max(room, 1), dtype=BLOCKINFO_DTYPE)
+    bw, bh, ref = _C.c_int(0), _C.c_int(0), _C.c_int(0)
+    rc = lib().dsv1_packet_blockinfo(data.ctypes.data, data.size, w, h, _C.byref(bw), _C.byref(bh), _C.byref(ref), tab.ctypes.data, room)
+    if rc != 0:
+        raise ValueError("not a picture packet of a %dx%d stream that %d entries can describe (rc=%d)" % (w, h, room, rc))
+    nblk = ((w + bw.value - 1) // bw.value) * ((h + bh.value - 1) // bh.value)
+    return bw.value, bh.value, ref.value, tab[:nblk]
+
+
+def draw_info_clip(clip, w, h, fmt, blk_w, blk_h, info, mode, device=0, n=None):
+    """the decoders' debug overlay (dsv1_draw_info_clip) on packed planar 8-bit frames: clip numpy uint8 [frames][frame_bytes] (host;
+    returns the drawn copy), or a device pointer with n frames, drawn in place.  info: BLOCKINFO_DTYPE entries, ceil(w / blk_w) *
+    ceil(h / blk_h) per frame.  ValueError for arguments the library refuses."""
+    L = lib()
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    tab = _np.ascontiguousarray(info, dtype=BLOCKINFO_DTYPE).reshape(-1)
+    if n is not None:
+        frames, ptr, res = n, clip, clip
+    else:
+        a, frames = _host_clip(clip, fb)
+        res = a.copy().reshape(frames, fb)
+        ptr = res.ctypes.data
+    nblk = ((w + max(blk_w, 1) - 1) // max(blk_w, 1)) * ((h + max(blk_h, 1) - 1) // max(blk_h, 1))
+    if tab.size < nblk * frames:
+        raise ValueError("info holds %d entries, %d frames of %d blocks need %d" % (tab.size, frames, nblk, nblk * frames))
+    rc = L.dsv1_draw_info_clip(device, ptr, w, h, fmt, frames, blk_w, blk_h, tab.ctypes.data, mode, 0 if n is None else 1)
+    if rc == -2:
+        raise ValueError("dsv1_draw_info_clip refuses these arguments (block %dx%d, mode %d, subsampling 0x%x)" % (blk_w, blk_h, mode, fmt))
+    _chk(rc, "dsv1_draw_info_clip")
+    return res
+
+
 def rgb_frame_bytes(rf, w, h):
     """bytes from frame to frame of an RGB clip of RgbFormat rf (dsv1_rgb_frame_bytes); ValueError for an invalid format"""
     n = lib().dsv1_rgb_frame_bytes(_C.byref(rf), w, h)
@@ -1164,6 +1217,12 @@ class DecBatch:
         if self.L.dsv1_decbatch_set_output_rgb(self.h, None if rf is None else _C.byref(rf)) != 0:
             raise ValueError("not a valid RGB output format for these streams (subsampling 0x%x)" % self.fmt)
         self._output_changed()
+
+    def set_draw_info(self, mode):
+        """from the next decode() on, the debug overlay of mode 0 .. 7 (DSV_DRAW_* bits; 0: off) is drawn onto the luma of every picture
+        that has a reference, ahead of the output pass (dsv1_decbatch_set_draw_info); ValueError for another mode."""
+        if self.L.dsv1_decbatch_set_draw_info(self.h, mode) != 0:
+            raise ValueError("not a draw_info mode: %r" % (mode,))
 
     def decode(self, packets, out=None, on_device=False):
         """packets: one bytes object per stream.  Host output: returns (frames [nstreams][frame_bytes] uint8, status,

@@ -145,5 +145,10 @@ int xres_geo_build(XresGeo &G, const FrameLayout &L, int rw, int rh, int filter)
 void xres_geo_free(XresGeo &G);
 void launch_xres(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const XresGeo &G, const uint8_t *const *xref,
                  const HzPlaneSum *psum0, unsigned long long *xsse, unsigned long long *xssim);
+// k_drawinfo.hip: the decoders' debug overlay (mode: DSV_DRAW_* bits, non-zero) onto the luma planes of n pictures -- picture i at
+// luma0 + i * pic_pitch, w x h at row stride `stride` -- from their block tables, picture i at mvs + i * nblk and stable + i * nblk
+// (nblk = ceil(w / bw) * ceil(h / bh)); two launches in stream order, every store inside the plane
+void launch_drawinfo(hipStream_t st, uint8_t *luma0, size_t pic_pitch, int w, int h, int stride, int bw, int bh, int mode,
+                     const DMV *mvs, const uint8_t *stable, int n);
 // k_hme.hip
 void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf = nullptr);

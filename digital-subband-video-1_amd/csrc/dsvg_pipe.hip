@@ -262,6 +262,14 @@ struct dsvg_ctx {
     size_t yuv_stage_bytes = 0;
     int *ltab_d = nullptr;           // slot table of dsvg_load_frames_map
     int *otab_d = nullptr;           // table of the output pass: slots (k_pack_n) or (slot, output frame) pairs (k_pixout)
+    // Decoder, debug overlay (dsvg_ctx_draw_info, k_drawinfo.hip): with a mode set, every P picture of a decoder call is copied behind its
+    // reconstruction into a scratch frame -- one per job of a call, allocated when the first such picture arrives -- and drawn on there;
+    // the reconstruction slots, which later pictures predict from, stay clean.  draw_at[slot]: the scratch frame that stands in for the
+    // slot in the output pass and the downloads until the next decoder call, or -1.  Mode 0: nothing of this exists or runs.
+    int draw_mode = 0;
+    uint8_t *draw_scratch = nullptr;
+    std::vector<int> draw_at;
+    bool draw_any = false;
     int *ilist_h = nullptr, *ilist_d = nullptr;   // intra blocks of the P pictures of a batch (pinned / device), indexed like jobs_h
     // host-resident input: two device ingest buffers filled on a copy stream of their own, so the upload of the
     // next batch runs under the analysis and coding of the current one
@@ -423,7 +431,7 @@ static void ctx_free(dsvg_ctx *c)
     c->recon.release(); c->xf.release(); c->pred.release();
     xres_geo_free(c->xg);
     void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, (void *)c->xref_d};
+                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->draw_scratch, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, (void *)c->xref_d};
     for (void *p : d) if (p) (void)hipFree(p);
     void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, (void *)c->xref_h};
     for (void *p : hh) if (p) (void)hipHostFree(p);
@@ -2037,6 +2045,19 @@ extern "C" int dsvg_fetch_pictures(dsvg_ctx *c, int n, const int *out_slots, dsv
 
 
 
+// the frame a reader of decoded pictures takes for a slot: the slot's reconstruction, or the overlay's scratch copy of it (ask after dec_resolve)
+static uint8_t *shown_frame(const dsvg_ctx *c, int slot)
+{
+    return c->draw_any && c->draw_at[(size_t)slot] >= 0 ? c->draw_scratch + (size_t)c->draw_at[(size_t)slot] * c->L[0].pitch : c->recon.p + (size_t)slot * c->L[0].pitch;
+}
+
+extern "C" int dsvg_ctx_draw_info(dsvg_ctx *c, int mode)
+{
+    if (!c || mode < 0) { dsvg_set_error("bad draw_info mode"); return DSVG_ERR_ARG; }
+    c->draw_mode = mode;
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_download_recon(dsvg_ctx *c, int recon_slot, uint8_t *yuv_out)
 {
     if (!c || !yuv_out || recon_slot < 0 || recon_slot >= c->n_recon) return DSVG_ERR_ARG;
@@ -2048,7 +2069,7 @@ extern "C" int dsvg_download_recon(dsvg_ctx *c, int recon_slot, uint8_t *yuv_out
         HIPCHK(hipMalloc((void **)&c->yuv_stage, fb + 256));
         c->yuv_stage_bytes = fb;
     }
-    launch_pack(c->st, c->yuv_stage, c->recon.p + (size_t)recon_slot * c->L[0].pitch, c->L[0]);
+    launch_pack(c->st, c->yuv_stage, shown_frame(c, recon_slot), c->L[0]);
     HIPCHK(hipMemcpyAsync(yuv_out, c->yuv_stage, fb, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return DSVG_OK;
@@ -2082,7 +2103,7 @@ extern "C" int dsvg_download_recon_frame(dsvg_ctx *c, int recon_slot, void *raw_
     if (!c || !raw_out || recon_slot < 0 || recon_slot >= c->n_recon || bytes > c->L[0].bytes) return DSVG_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
     OPCHK(dec_resolve(c));                               // (a flagged call is decoded again from int32 coefficients first)
-    HIPCHK(hipMemcpyAsync(raw_out, c->recon.p + (size_t)recon_slot * c->L[0].pitch, bytes, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(raw_out, shown_frame(c, recon_slot), bytes, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return DSVG_OK;
 }
@@ -2155,6 +2176,18 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
         P.has_fmt = fmt != nullptr;
         if (fmt) P.fmt = *fmt;
     } else if (P.active && !P.in_redo) OPCHK(dec_resolve(c));   // a second pass over the same call: settle it now
+    // debug overlay: pictures drawn on are read from their scratch frames -- the table names the scratch frame, and the pass is launched
+    // once per run of entries that read the same slab (with the overlay off: one run, the table as it is)
+    std::vector<int> shown;
+    std::vector<char> alt((size_t)n, 0);
+    if (c->draw_any) {
+        shown.assign(tab, tab + (size_t)n * (fmt ? 2 : 1));
+        for (int i = 0; i < n; i++) {
+            int &e = shown[(size_t)i * (fmt ? 2 : 1)];
+            if (c->draw_at[(size_t)e] >= 0) { e = c->draw_at[(size_t)e]; alt[(size_t)i] = 1; }
+        }
+        tab = shown.data();
+    }
     if (!c->otab_d) HIPCHK(hipMalloc((void **)&c->otab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
     // One pass at a time: the first coding stream waits for the pass before, which keeps the passes in order and the table whole.
     // Round 5: device output of four pictures or more goes to the second coding stream -- beside the next call's entropy decoding, which
@@ -2194,8 +2227,12 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
         }
         if (fmt && !dense) HIPCHK(hipMemcpyAsync(dst, out, span, hipMemcpyHostToDevice, st));
     }
-    if (fmt) OPCHK(launch_pixout(st, fmt, S, c->recon.p, c->otab_d, n, dst, dpitch, &c->prof));
-    else launch_pack_n(st, dst, dpitch, c->recon.p, L, c->otab_d, n, &c->prof);
+    for (int i0 = 0, i1; i0 < n; i0 = i1) {
+        for (i1 = i0 + 1; i1 < n && alt[(size_t)i1] == alt[(size_t)i0]; i1++) ;
+        const uint8_t *slab = alt[(size_t)i0] ? c->draw_scratch : c->recon.p;
+        if (fmt) OPCHK(launch_pixout(st, fmt, S, slab, c->otab_d + 2 * (size_t)i0, i1 - i0, dst, dpitch, &c->prof));
+        else launch_pack_n(st, dst + (size_t)i0 * dpitch, dpitch, slab, L, c->otab_d + i0, i1 - i0, &c->prof);
+    }
     if (st != c->st) { HIPCHK(hipEventRecord(c->ev_pack[1], st)); c->pack_pending = true; }
     if (!on_device) {
         if (fmt) HIPCHK(hipMemcpyAsync(out, dst, span, hipMemcpyDeviceToHost, st));
@@ -2272,6 +2309,7 @@ extern "C" int dsvg_decode_pictures(dsvg_ctx *c, int njobs, const dsvg_dec_job *
 static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool force32)
 {
     HIPCHK(hipSetDevice(c->device));
+    if (c->draw_any) { std::fill(c->draw_at.begin(), c->draw_at.end(), -1); c->draw_any = false; }
     std::vector<int> ord;
     for (int i = 0; i < njobs; i++) if (jobs[i].ref_recon_slot < 0) ord.push_back(i);
     const int nI = (int)ord.size();
@@ -2469,6 +2507,21 @@ static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool fo
     }
     OPCHK(enqueue_recon(c, nI, njobs, 0, insym));
     if (anysym) launch_hz_unscatter(c->st, c->jobs_d + f0, njobs - f0, max_entries);
+    if (c->draw_mode && njobs > nI) {
+        // debug overlay on the call's P pictures (jobs nI .. njobs - 1, whose tables lie in c->mvs / c->stable in that order): each is
+        // copied to the scratch frame of its job and drawn on there, in stream order behind its reconstruction
+        const FrameLayout &L = c->L[0];
+        if (!c->draw_scratch) HIPCHK(hipMalloc((void **)&c->draw_scratch, L.pitch * (size_t)c->max_jobs + 256));
+        if (c->draw_at.empty()) c->draw_at.assign((size_t)c->n_recon, -1);
+        for (int t = nI; t < njobs; t++) {
+            const int slot = jobs[ord[t]].recon_slot;
+            HIPCHK(hipMemcpyAsync(c->draw_scratch + (size_t)t * L.pitch, c->recon.p + (size_t)slot * L.pitch, L.bytes, hipMemcpyDeviceToDevice, c->st));
+            c->draw_at[(size_t)slot] = t;
+        }
+        c->draw_any = true;
+        launch_drawinfo(c->st, c->draw_scratch + (size_t)nI * L.pitch + L.off[0], L.pitch, L.w[0], L.h[0], L.stride[0], c->bw, c->bh, c->draw_mode,
+                        c->mvs + (size_t)nI * c->nblk, c->stable + (size_t)nI * c->nblk, njobs - nI);
+    }
     HIPCHK(hipGetLastError());
     return DSVG_OK;
 }

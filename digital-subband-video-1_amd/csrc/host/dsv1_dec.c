@@ -3,7 +3,8 @@
  * payloads to the device: entropy parse, scatter + dequantise, inverse transform and motion compensation
  * run on the GPU.  dsv_dec() is the reference's one-picture-per-call entry (the frame is copied back into
  * a host DSV_FRAME); dsv1_decbatch_* decodes one picture of each of many independent streams per call.
- * Debug overlays (draw_info) are accepted and ignored. */
+ * Debug overlays (draw_info): drawn on the device onto a copy of every picture that has a reference, ahead of the download or the
+ * output pass (dsvg_ctx_draw_info; include/dsv1_api.h, debug overlays). */
 #include <stdio.h>
 #include <time.h>
 #include "dsv1_host.h"
@@ -258,6 +259,8 @@ int dsv_dec(DSV_DECODER *d, DSV_BUF *buffer, DSV_FRAME **out, DSV_FNUM *fn)
      * slot its reconstruction will live in, dsvg_decode_pictures); other pictures go to slot 2 */
     job.ref_recon_slot = has_ref ? ss->rpar : -1;
     job.recon_slot = is_ref ? (ss->rpar ^ 1) : 2;
+    /* any non-zero draw_info draws the grid, bits 1 / 2 / 4 the rest (dsv_decoder.c:443, 184-243); the downloads below then read the drawn copy */
+    if (dsvg_ctx_draw_info(ss->ctx, d->draw_info ? (d->draw_info & 7) | 8 : 0)) goto done;
     DEC_NOW(t1);
     if ((rc = dsvg_decode_pictures(ss->ctx, 1, &job))) {
         dsv1_log(1, "GPU decode failed: %s", dsvg_last_error());
@@ -322,6 +325,7 @@ struct dsv1_decbatch {
     int *recs;                       /* [nstreams] reconstruction slots of this call's pictures (the output pass) */
     int out_set;                     /* an output format is in force (dsv1_decbatch_set_output_format); else the packed planar pass */
     dsvg_pixout out;                 /* ... resolved for the streams' geometry: it does not depend on the block size */
+    int draw_mode;                   /* debug overlay (dsv1_decbatch_set_draw_info): handed to every context the batch builds */
 };
 
 void dsv1_decbatch_close(dsv1_decbatch *d)
@@ -399,6 +403,15 @@ int dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf)
     return set_output(d, dsv1_rgbout_of(rf, d->meta.width, d->meta.height, d->meta.subsamp, &F), &F, 1);
 }
 
+int dsv1_decbatch_set_draw_info(dsv1_decbatch *d, int mode)
+{
+    int rc;
+    if (!d || mode < 0 || mode > 7) return DSVG_ERR_ARG;
+    if ((rc = dsvg_ctx_draw_info(d->ctx, mode))) return rc;
+    d->draw_mode = mode;
+    return DSVG_OK;
+}
+
 size_t dsv1_decbatch_out_frame_bytes(const dsv1_decbatch *d)
 {
     if (!d) return 0;
@@ -472,6 +485,7 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
                                               d->nstreams, bw_, bh_))) return rc;
                 dsvg_ctx_destroy(d->ctx);
                 d->ctx = nc;
+                dsvg_ctx_draw_info(d->ctx, d->draw_mode);
                 dsvg_ctx_geom(d->ctx, &d->g);
                 d->nblk = d->g.nblocks_h * d->g.nblocks_v;
                 free(d->stable); free(d->mvs);
@@ -510,3 +524,68 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
 }
 
 void *dsv1_decbatch_ctx(dsv1_decbatch *d) { return d ? (void *)d->ctx : NULL; }
+
+/* ---- debug overlays: a packet's side information, and the overlay on a clip (include/dsv1_api.h) ---- */
+int dsv1_packet_blockinfo(const uint8_t *data, size_t len, int w, int h, int *blk_w, int *blk_h, int *has_ref, dsv1_blockinfo *out, size_t n)
+{
+    bitw r;
+    dsvg_geom g;
+    dsvg_dec_job job;
+    DSV_FNUM fn;
+    DSV_MV *mvs;
+    unsigned char *stable;
+    int type, bw_, bh_, ref, rc;
+    size_t nblk, i;
+    if (!data || !blk_w || !blk_h || !has_ref || !out || w < 1 || h < 1 || len > 0x7fffffffu) return DSVG_ERR_ARG;
+    if (parse_packet_header(&r, (uint8_t *)data, (unsigned)len, &type) || !(type & DSV_PT_PIC)) return DSVG_ERR_ARG;
+    if (parse_picture_head(&r, &fn, &bw_, &bh_)) return DSVG_ERR_ARG;
+    memset(&g, 0, sizeof(g));
+    g.width = w; g.height = h;
+    g.subsamp = DSV_SUBSAMP_444;                         /* (only bounds the plane lengths the packet may announce: the widest) */
+    g.blk_w = bw_; g.blk_h = bh_;
+    g.nblocks_h = (w + bw_ - 1) / bw_; g.nblocks_v = (h + bh_ - 1) / bh_;
+    nblk = (size_t)g.nblocks_h * g.nblocks_v;
+    if (n < nblk) return DSVG_ERR_ARG;
+    ref = type & 1;
+    stable = (unsigned char *)calloc(nblk, 1);
+    mvs = (DSV_MV *)calloc(nblk, sizeof(DSV_MV));
+    rc = (!stable || !mvs) ? DSVG_ERR_NOMEM : parse_picture_body(&r, (uint8_t *)data, (unsigned)len, &g, ref, stable, mvs, &job) ? DSVG_ERR_ARG : DSVG_OK;
+    if (!rc) {
+        memset(out, 0, nblk * sizeof(*out));
+        for (i = 0; i < nblk; i++) {
+            out[i].stable = stable[i] & 1;
+            if (!ref) continue;
+            out[i].mode = mvs[i].mode ? 1 : 0;
+            if (mvs[i].mode) out[i].submask = mvs[i].submask;
+            else { out[i].mvx = mvs[i].u.mv.x; out[i].mvy = mvs[i].u.mv.y; }
+        }
+        *blk_w = bw_; *blk_h = bh_; *has_ref = ref;
+    }
+    free(stable); free(mvs);
+    return rc;
+}
+
+int dsv1_draw_info_clip(int device, void *clip, int w, int h, int subsamp, int n, int blk_w, int blk_h, const dsv1_blockinfo *info, int mode,
+                        int on_device)
+{
+    DSV_MV *mvs;
+    unsigned char *stable;
+    size_t nblk, i;
+    int rc;
+    if (!clip || !info || w < 1 || h < 1 || n < 1 || mode < 1 || mode > 7 || blk_w < DSV_MIN_BLOCK_SIZE || blk_w > DSV_MAX_BLOCK_SIZE ||
+        blk_h < DSV_MIN_BLOCK_SIZE || blk_h > DSV_MAX_BLOCK_SIZE ||
+        (subsamp != DSV_SUBSAMP_444 && subsamp != DSV_SUBSAMP_422 && subsamp != DSV_SUBSAMP_420 && subsamp != DSV_SUBSAMP_411)) return DSVG_ERR_ARG;
+    nblk = (size_t)((w + blk_w - 1) / blk_w) * (size_t)((h + blk_h - 1) / blk_h) * (size_t)n;
+    stable = (unsigned char *)calloc(nblk, 1);
+    mvs = (DSV_MV *)calloc(nblk, sizeof(DSV_MV));
+    if (!stable || !mvs) { free(stable); free(mvs); return DSVG_ERR_NOMEM; }
+    for (i = 0; i < nblk; i++) {
+        stable[i] = info[i].stable & 1;
+        mvs[i].mode = info[i].mode ? 1 : 0;
+        if (info[i].mode) mvs[i].submask = info[i].submask;
+        else { mvs[i].u.mv.x = info[i].mvx; mvs[i].u.mv.y = info[i].mvy; }
+    }
+    rc = dsvg_draw_info_planar(device, clip, w, h, subsamp, n, blk_w, blk_h, (const dsvg_mv *)mvs, stable, mode, on_device);
+    free(stable); free(mvs);
+    return rc;
+}

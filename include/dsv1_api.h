@@ -95,7 +95,7 @@ typedef struct {                 /* same fields, order and sizes as dsv_encoder.
 typedef struct {                 /* dsv_decoder.h:35-43 */
     DSV_META vidmeta;
     void *ref;                   /* reference: DSV_IMAGE*; here: opaque device session handle */
-    int draw_info;               /* accepted and ignored: debug overlays are out of scope */
+    int draw_info;               /* set by the user: DSV_DRAW_* bits, drawn on the GPU (debug overlays, below) */
     int got_metadata;
 } DSV_DECODER;
 
@@ -653,6 +653,46 @@ int  dsv1_batch_set_source_denoise(dsv1_batch *b, const dsv1_denoise *dn);      
 int  dsv1_batch_denoise_reset(dsv1_batch *b, int source);                             /* -1 = every source */
 int  dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn);
 int  dsv1_resladder_denoise_reset(dsv1_resladder *r, int source);
+
+/* ---- extension: debug overlays (csrc/k_drawinfo.hip; stated in Python in tests/_drawinfo.py) ----
+ * The reference decoder's -drawinfo (draw_info dsv_decoder.c:147-243), drawn on the device ahead of the output pass: what an encoder
+ * decided, on the decoded luma of every picture that has a reference (P pictures; I pictures and chroma are untouched, and so are the
+ * pictures later ones predict from -- the overlay goes onto a copy).  Blocks are walked in raster order, block (i, j) at x = i blk_w,
+ * y = j blk_h, and a later writer of a pixel wins:
+ *   grid     any non-zero mode: luma row y is 0 (once per block row, before its blocks), then column x, rows y .. min(y + blk_h, h) - 1;
+ *   dash     DSV_DRAW_STABHQ, blocks whose stability flag has bit 0: (x + blk_w/2 + k, y + blk_h/2), k = -(blk_w/4) .. blk_w/4, is 255
+ *            for odd k, 0 for even k;
+ *   vector   DSV_DRAW_MOVECS, inter blocks: the walk of csrc/dsvg_drawvec.h from the block's centre (x + blk_w/2, y + blk_h/2) towards the
+ *            centre + (mv.x, mv.y), the vector raw, as pixels: every point up to, not including, the end is 0 (a zero vector: the centre);
+ *   dots     DSV_DRAW_IBLOCK, intra blocks: 255 at (x + blk_w (1 + 2a) / 4, y + blk_h (1 + 2b) / 4) for every set submask bit a + 2b.
+ * Everything is clipped to the luma plane.  DEVIATION: the reference does not bounds-check its dots, so with a dimension that is no
+ * multiple of the block size the dots of its edge blocks land outside the luma plane, in chroma; here such a dot is not drawn.  On
+ * block-multiple geometries the result is the reference's, byte for byte.
+ * dsv_dec honours DSV_DECODER.draw_info as the reference does (any non-zero value: the grid; bits 1, 2, 4 the rest; others ignored).
+ * dsv1_decbatch_set_draw_info: mode 0 .. 7 (else DSVG_ERR_ARG) for every later call and every output setting -- the overlay is on the
+ * decoded luma before the one output pass, so a frame is export(overlay(plain decode)); it outlives a rebuilt context.  With mode 0
+ * nothing is allocated, copied or launched.
+ * dsv1_packet_blockinfo (host only): the side information of one picture packet of a w x h stream as the decoders parse it: the block
+ * size, whether the picture has a reference and one dsv1_blockinfo per block in raster order (n: room in `out`, at least
+ * ceil(w / blk_w) * ceil(h / blk_h)).  Without a reference only `stable` is filled.  DSVG_ERR_ARG for anything but a well-formed
+ * picture packet, or too small an n.
+ * dsv1_draw_info_clip: the same overlay on n tightly packed planar frames in place (host or device memory; synchronous), frame i from
+ * the table info + i * ceil(w / blk_w) * ceil(h / blk_h); block sizes 16 .. 64, mode 1 .. 7, a subsampling the library knows.
+ * Not offered: overlays on the encoder's reconstructions, drawing into chroma, the reference's out-of-plane dots, colours or labels. */
+#define DSV_DRAW_STABHQ 1        /* dsv_decoder.h:38-40 */
+#define DSV_DRAW_MOVECS 2
+#define DSV_DRAW_IBLOCK 4
+typedef struct {
+    int16_t mvx, mvy;            /* inter blocks */
+    uint8_t mode;                /* 0 inter, 1 intra */
+    uint8_t submask;             /* intra blocks: DSV_MASK_INTRA* bits */
+    uint8_t stable;              /* bit 0 of the stream's stability flag */
+    uint8_t reserved;
+} dsv1_blockinfo;
+int  dsv1_decbatch_set_draw_info(dsv1_decbatch *d, int mode);
+int  dsv1_packet_blockinfo(const uint8_t *data, size_t len, int w, int h, int *blk_w, int *blk_h, int *has_ref, dsv1_blockinfo *out, size_t n);
+int  dsv1_draw_info_clip(int device, void *clip, int w, int h, int subsamp, int n, int blk_w, int blk_h, const dsv1_blockinfo *info, int mode,
+                         int on_device);
 
 #ifdef __cplusplus
 }

@@ -372,6 +372,18 @@ int dsvg_export_recons(dsvg_ctx *ctx, int n, const int *recon_slots, const int *
  * staged (the destination goes up first, as above).  Any w, h >= 1.  Synchronous. */
 int dsvg_export_planar(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsvg_pixout *fmt, int on_device);
 
+/* Debug overlay of decoded pictures (csrc/k_drawinfo.hip; include/dsv1_api.h, debug overlays).  dsvg_ctx_draw_info: with mode != 0 (bits
+ * 1 / 2 / 4: stability dashes, motion vectors, intra dots; any non-zero value: the block grid) every picture with a reference of the
+ * dsvg_decode_pictures calls that follow is copied, behind its reconstruction and on the same stream, to a scratch frame of the context
+ * (one per job of a call, allocated when first needed) and drawn on there from the call's own block tables.  Until the next decoder
+ * call dsvg_pack_recons / dsvg_export_recons / dsvg_download_recon / dsvg_download_recon_frame of that slot read the scratch frame; the
+ * slot itself -- what later pictures predict from, dsvg_download_recon_raw -- stays clean.  Mode 0: no allocation, copy or launch.
+ * dsvg_draw_info_planar: the overlay on n tightly packed planar frames in place, frame i from mvs / stable + i * nblocks (host tables;
+ * stable: bit 0); blk 16 .. 64, mode 1 .. 7.  Synchronous. */
+int dsvg_ctx_draw_info(dsvg_ctx *ctx, int mode);
+int dsvg_draw_info_planar(int device, void *clip, int w, int h, int subsamp, int n, int blk_w, int blk_h, const dsvg_mv *mvs,
+                          const unsigned char *stable, int mode, int on_device);
+
 /* Decoder side: coefficient (run,value) pairs parsed on the host are scattered + dequantised,
  * inverse transformed and motion compensated on the device (dsv_dec dsv_decoder.c:379-436). */
 typedef struct {
