@@ -66,6 +66,38 @@ class InvStep(_C.Structure):
                 "bytes": self.bytes, "cover": (self.cover, self.cx, self.cy)}
 
 
+BATCH_NO_SMALL_SPLIT, BATCH_NO_PAR_ENQUEUE, BATCH_NO_LAZY_BORDER, BATCH_NO_MC_FUSION, BATCH_PROFILED = 1, 2, 4, 8, 16      # DSVG_BATCH_*
+
+
+class PicJob(_C.Structure):
+    """dsvg_pic_job (include/dsvg.h): one picture of a coding call"""
+    _fields_ = [("src_slot", _C.c_int), ("ref_recon_slot", _C.c_int), ("recon_slot", _C.c_int), ("quant", _C.c_int), ("mvs", _C.c_void_p),
+                ("stable_blocks", _C.c_void_p), ("out_slot", _C.c_int), ("no_intra_blocks", _C.c_int), ("has_reach", _C.c_int),
+                ("mv_reach", _C.c_short * 4), ("border_hint", _C.c_int)]
+
+
+class RcJob(_C.Structure):
+    """dsvg_rc_job (include/dsvg.h): the rate-controlled stream a picture of a coding call belongs to"""
+    _fields_ = [("rc_slot", _C.c_int), ("prefix_len", _C.c_int), ("forced_intra", _C.c_int)]
+
+
+class BatchPlan(_C.Structure):
+    """dsvg_batch_plan (include/dsvg.h): the plan of a coding call, arrays of the caller's"""
+    _fields_ = [("cap_steps", _C.c_int), ("cap_jobs", _C.c_int), ("cap_groups", _C.c_int), ("cap_ilist", _C.c_int),
+                ("nI", _C.c_void_p), ("order", _C.c_void_p), ("mvu", _C.c_void_p), ("stu", _C.c_void_p), ("mvcp", _C.c_void_p),
+                ("stcp", _C.c_void_p), ("ext", _C.c_void_p), ("rc_next", _C.c_void_p), ("ioff", _C.c_void_p), ("icnt", _C.c_void_p),
+                ("noint", _C.c_void_p), ("keeps", _C.c_void_p), ("ilist", _C.c_void_p),
+                ("nblk", _C.c_int), ("mc_fused", _C.c_int), ("base", _C.c_int), ("total", _C.c_int), ("ng", _C.c_int), ("gk", _C.c_int * 5),
+                ("iln", _C.c_int), ("nmv", _C.c_int), ("nst", _C.c_int), ("mv_contig", _C.c_int), ("par_enqueue", _C.c_int)]
+
+
+class BatchRefused(RuntimeError):
+    """dsvg_code_batch_plan did not answer with a plan: rc and text are what the coding call itself would return and set"""
+    def __init__(self, rc, text):
+        super().__init__("dsvg_code_batch_plan failed rc=%d: %s" % (rc, text))
+        self.rc, self.text = rc, text
+
+
 class ResRung(_C.Structure):
     """dsv1_res_rung: one geometry of a resolution ladder and its rate rungs"""
     _fields_ = [("width", _C.c_int), ("height", _C.c_int), ("nrates", _C.c_int), ("rates", _C.POINTER(Encoder))]
@@ -303,6 +335,41 @@ def inv_plan(w, h, fmt, group, isP, with_tail=1, insym=0, patch_kernel=0, fuse_b
     if n < 0:
         _chk(n, "dsvg_inv_plan")
     return [steps[i].as_dict() for i in range(n)], fb.value
+
+
+def code_batch_plan(w, h, fmt, n_recon_slots, n_src_slots, max_jobs, out_slots, code_streams, switches, nsteps, njobs, jobs, rc=None):
+    """what dsvg_code_batch (rc: dsvg_code_batch_rc) decides on the host for `jobs` (a ctypes array of PicJob, jobs[step * njobs + j]; rc
+    one of RcJob) in an encoder context created with these arguments, with the A/B switches of the mask `switches` (BATCH_*): a dict of
+    dsvg_batch_plan's fields, the arrays as numpy arrays cut to their lengths (ext: [total, 8]; the per-share ones: [nsteps, ng]).
+    Raises BatchRefused with the call's own code and text for jobs the call refuses.  Needs no device"""
+    total = max(nsteps * njobs, 1)
+    d = Dispatch()                                          # (the block size of the geometry: how long the intra list can get)
+    nblk = -(-w // d.blk_w) * -(-h // d.blk_h) if lib().dsvg_dispatch_plan(w, h, fmt, _C.byref(d)) == 0 else 1
+    groups = max(nsteps, 1) * 4
+    arr = {"nI": _np.zeros(max(nsteps, 1), _np.int32), "order": _np.zeros(total, _np.int32), "mvu": _np.zeros(total, _np.int32),
+           "stu": _np.zeros(total, _np.int32), "mvcp": _np.zeros(total, _np.uint8), "stcp": _np.zeros(total, _np.uint8),
+           "ext": _np.zeros(total * 8, _np.int16), "rc_next": _np.zeros(total, _np.int32), "ioff": _np.zeros(groups, _np.int32),
+           "icnt": _np.zeros(groups, _np.int32), "noint": _np.zeros(groups, _np.uint8), "keeps": _np.zeros(groups, _np.uint8),
+           "ilist": _np.zeros(total * nblk, _np.int32)}
+    p = BatchPlan(cap_steps=len(arr["nI"]), cap_jobs=total, cap_groups=groups, cap_ilist=total * nblk)
+    for k, a in arr.items():
+        setattr(p, k, a.ctypes.data)
+    # (bound here, not in lib(): an A/B build named by DSV1_SO may be older than this query)
+    lib().dsvg_code_batch_plan.argtypes = [_C.c_int] * 8 + [_C.c_uint, _C.c_int, _C.c_int, _C.POINTER(PicJob), _C.POINTER(RcJob), _C.POINTER(BatchPlan)]
+    r = lib().dsvg_code_batch_plan(w, h, fmt, n_recon_slots, n_src_slots, max_jobs, out_slots, code_streams, switches, nsteps, njobs, jobs, rc,
+                                   _C.byref(p))
+    if r != 0:
+        raise BatchRefused(r, lib().dsvg_last_error().decode())
+    d = {k: getattr(p, k) for k in ("nblk", "mc_fused", "base", "total", "ng", "iln", "nmv", "nst", "mv_contig", "par_enqueue")}
+    d["gk"] = tuple(p.gk)[:p.ng + 1]
+    for k in ("order", "mvu", "stu", "mvcp", "stcp", "rc_next"):
+        d[k] = arr[k][:p.total]
+    d["nI"] = arr["nI"][:nsteps]
+    d["ext"] = arr["ext"][:p.total * 8].reshape(p.total, 8)
+    for k in ("ioff", "icnt", "noint", "keeps"):
+        d[k] = arr[k][:nsteps * p.ng].reshape(nsteps, p.ng)
+    d["ilist"] = arr["ilist"][:p.iln]
+    return d
 
 
 def make_encoder_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1, kbps=0, scd=1, ipct=50, pyrlevels=0, stabref=0,

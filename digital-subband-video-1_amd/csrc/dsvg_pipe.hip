@@ -7,16 +7,14 @@
 // results.  The host only ever sees: MV fields, mean luma, per-plane (DC, nruns, payload bytes).
 #include <stdlib.h>
 #include <algorithm>
-#include <unordered_map>
 #include <cstddef>
 #include "dsvg_host.hpp"
+#include "dsvg_batch_plan.h"
 #include <ctime>
 extern "C" void dsv1_par_for(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);     // host/dsv1_util.c: the worker pool
 extern "C" void dsv1_par_for_long(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);
 
 #define OPCHK(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
-#define DSVG_MAX_CODE_STREAMS 4
 
 // ---- stream placement ------------------------------------------------------------------------------------------
 // The runtime maps HIP streams onto a handful of hardware queues (4 by default), least-loaded first, counting every
@@ -198,6 +196,10 @@ struct dsvg_ctx {
     dsvg_rc_state *rc_state_d = nullptr;
     RcJobDev *rcj_d = nullptr, *rcj_h = nullptr;
     int rc_slots = 0;
+    // coding calls (dsvg_batch_plan.h): what their plan reads of the context (batch_geo, at creation), and the plan of the call being
+    // enqueued -- kept here so that its vectors are allocated once, not per call
+    BatchGeo bgeo = {};
+    BatchPlan plan;
     size_t nz_off[3] = {0, 0, 0}, nz_total = 0;
     int chunk_off[3] = {0, 0, 0}, chunks_per_job = 0, max_chunks = 0;
     size_t bits_off[3] = {0, 0, 0}, bits_cap[3] = {0, 0, 0}, bits_per_job = 0;
@@ -532,6 +534,22 @@ extern "C" int dsvg_geom_check(int width, int height, int subsamp)
     return geom_check(width, height, subsamp, geo);
 }
 
+// What the plan of a coding call reads of a context (dsvg_batch_plan.h), from the arguments of its creation: dsvg_ctx_create_blk takes
+// out_slots, rc_slots, mc_fused and the lazy border from here, and dsvg_code_batch_plan asks the plan about the same record without a
+// context.  code_streams is the call's own (dsvg_ctx_code_streams may change it from call to call).
+static BatchGeo batch_geo(const CtxGeo &geo, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots, bool mc_fusion, bool lazy_border)
+{
+    BatchGeo B = {};
+    B.nblk = geo.nbh * geo.nbv; B.n_recon = n_recon_slots; B.n_src = n_src_slots; B.max_jobs = max_jobs;
+    B.out_slots = std::max(out_slots, max_jobs);
+    B.rc_slots = std::max(n_recon_slots, max_jobs);
+    B.mc_fused = mc_fusable(geo.MG) && mc_fusion;
+    B.lazy_border = lazy_border;
+    B.blk_w = geo.MG.blk_w; B.blk_h = geo.MG.blk_h; B.nbh = geo.MG.nbh; B.hs = geo.MG.hs; B.vs = geo.MG.vs;
+    for (int pl = 0; pl < 2; pl++) { B.w[pl] = geo.MG.w[pl]; B.h[pl] = geo.MG.h[pl]; }
+    return B;
+}
+
 // What the forward launchers decide for an encoder context of this geometry (default block size and pyramid depth, the chroma
 // table of the motion search on): the context's geometry tables, handed to the launchers' own decision functions
 extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out)
@@ -598,7 +616,6 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         dsvg_set_error("block size %dx%d: multiples of 4 in 16..64 (dsv_decoder.c:351-356)", blk_w, blk_h);
         return DSVG_ERR_ARG;
     }
-    if (out_slots < max_jobs) out_slots = max_jobs;
     if (!out || width < 32 || height < 32 || n_src_slots < 1 || n_recon_slots < 1 || max_jobs < 1) {
         dsvg_set_error("bad ctx_create arguments");
         return DSVG_ERR_ARG;
@@ -610,14 +627,16 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
     *out = nullptr;
     c->device = device;
     c->w = width; c->h = height; c->fmt = subsamp;
-    c->n_src = n_src_slots; c->n_recon = n_recon_slots; c->max_jobs = max_jobs; c->out_slots = out_slots;
-    c->nwin = (out_slots + max_jobs - 1) / max_jobs + 1;
     {
         CtxGeo geo;
         make_ctx_geo(geo, width, height, subsamp, blk_w, blk_h);
         c->bw = geo.bw; c->bh = geo.bh; c->nbh = geo.nbh; c->nbv = geo.nbv;
         c->L[0] = geo.L; c->CL = geo.CL; c->G = geo.G; c->MG = geo.MG;
+        c->bgeo = batch_geo(geo, n_src_slots, n_recon_slots, max_jobs, out_slots, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_LAZY_BORDER"));
     }
+    out_slots = c->bgeo.out_slots;                          // (at least max_jobs)
+    c->n_src = n_src_slots; c->n_recon = n_recon_slots; c->max_jobs = max_jobs; c->out_slots = out_slots;
+    c->nwin = (out_slots + max_jobs - 1) / max_jobs + 1;
     c->nblk = c->nbh * c->nbv;
     c->levels = pyramid_levels > 0 ? std::min(pyramid_levels, DSVG_MAX_PYRAMID) : auto_pyramid_levels(width, height, c->nbh, c->nbv);
     for (int l = 1; l <= c->levels; l++) make_frame_layout(c->L[l], subsamp, rsu(width, l), rsu(height, l));
@@ -628,13 +647,13 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
             delete c; return DSVG_ERR_UNSUPPORTED;
         }
     if ((width | height) & 1) { dsvg_set_error("odd luma dimensions are not supported (intra B4T needs even planes)"); delete c; return DSVG_ERR_UNSUPPORTED; }
-    c->mc_fused = mc_fusable(c->MG) && !getenv("DSV1_NO_MC_FUSION");
+    c->mc_fused = c->bgeo.mc_fused != 0;
     c->no_inplace_pred = getenv("DSV1_NO_INPLACE_PRED") != nullptr;
     c->no_dec_sym = getenv("DSV1_NO_DEC_SYM") != nullptr;
     c->no_dec_sym_I = getenv("DSV1_NO_DEC_SYM_I") != nullptr;
     c->no_patch_kernel = getenv("DSV1_NO_PATCH_KERNEL") != nullptr;
     c->no_list_pack = getenv("DSV1_NO_LIST_PACK") != nullptr;
-    c->no_lazy_border = getenv("DSV1_NO_LAZY_BORDER") != nullptr;
+    c->no_lazy_border = !c->bgeo.lazy_border;
     for (int g2 = 0; g2 < 2; g2++) {
         HzPlane hp; make_hz_plane(hp, CL.w[g2 ? 1 : 0], CL.h[g2 ? 1 : 0], 100, 1, g2, c->nbh, c->nbv);
         const bool ov = (2 * hp.s_w[0] > hp.s_w[1]) || (2 * hp.s_h[0] > hp.s_h[1]) || (2 * hp.s_w[1] > hp.s_w[2]) || (2 * hp.s_h[1] > hp.s_h[2]);
@@ -724,7 +743,7 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
     if ((rc = dmalloc(&c->mvs, (size_t)c->nblk * O, true))) return fail(rc);
     if ((rc = dmalloc(&c->stable, (size_t)c->nblk * O, true))) return fail(rc);
     if ((rc = dmalloc(&c->jobs_d, O, true))) return fail(rc);
-    c->rc_slots = std::max(n_recon_slots, max_jobs);
+    c->rc_slots = c->bgeo.rc_slots;
     if ((rc = dmalloc(&c->rc_state_d, (size_t)c->rc_slots, true))) return fail(rc);
     if ((rc = dmalloc(&c->rcj_d, O, true))) return fail(rc);
     if ((rc = hmalloc(&c->rcj_h, std::max(S, O)))) return fail(rc);
@@ -1284,49 +1303,6 @@ static void fill_job(dsvg_ctx *c, JobDev &jb, int t, int isP, int quant, int d =
     for (int i = 0; i < 8; i++) jb.ext[i] = DSVG_BORDER;
 }
 
-// How far a picture with motion field `mv` reads beyond the edges of its reference: the window of an inter block starts at
-// the clamped position k_mc / k_fwd_mc_* use (bmc.c:248-255) and is read with a margin of up to 2 pixels before and 3
-// after (4-tap luma filter, staging); accumulated (max) into ext[0..3] luma / ext[4..7] chroma of the reference's job.
-static void border_reach(const dsvg_ctx *c, const DMV *mv, const short *reach, short *ext)
-{
-    const McGeo &G = c->MG;
-    int need[8] = {16, 16, 8, 8, 16, 16, 8, 8};           // referenced at all: intra blocks and staging touch the first pixels
-    if (reach) {
-        // the caller's summary of the vectors: as if the block with the longest vector sat at the edge it points to
-        for (int pl = 0; pl < 2; pl++) {
-            const int sh = pl ? G.hs : 0, sv = pl ? G.vs : 0;
-            int *n = need + 4 * pl;
-            n[0] = std::max(n[0], 2 - (reach[0] >> sh));
-            n[1] = std::max(n[1], (reach[1] >> sh) + 4);
-            n[2] = std::max(n[2], 2 - (reach[2] >> sv));
-            n[3] = std::max(n[3], (reach[3] >> sv) + 4);
-        }
-    } else
-    for (int b = 0; b < c->nblk; b++) {
-        if (mv[b].mode != 0) continue;
-        const int bi = b % G.nbh, bj = b / G.nbh;
-        for (int pl = 0; pl < 2; pl++) {
-            const int sh = pl ? G.hs : 0, sv = pl ? G.vs : 0;
-            const int bw = G.blk_w >> sh, bh = G.blk_h >> sv, pw = G.w[pl], ph = G.h[pl];
-            const int x = bi * bw, y = bj * bh;
-            if (x >= pw || y >= ph) continue;
-            const int cw = std::min(bw, pw - x), ch = std::min(bh, ph - y);
-            const int dx = mv[b].x >> sh, dy = mv[b].y >> sv;
-            const int wx = std::min(std::max(x + (dx >> 1), -DSVG_BORDER), pw - bw + DSVG_BORDER - 1);
-            const int wy = std::min(std::max(y + (dy >> 1), -DSVG_BORDER), ph - bh + DSVG_BORDER - 1);
-            int *n = need + 4 * pl;
-            n[0] = std::max(n[0], 2 - wx);
-            n[1] = std::max(n[1], wx + cw + 3 - (pw - 1));
-            n[2] = std::max(n[2], 2 - wy);
-            n[3] = std::max(n[3], wy + ch + 3 - (ph - 1));
-        }
-    }
-    bool whole = false;
-    for (int i = 0; i < 8; i++) whole = whole || need[i] > DSVG_BORDER - 4;       // reaches the border's last pixels (or the byte
-    for (int i = 0; i < 8; i++)                                                  // after them = the next row's first): everything
-        ext[i] = (short)std::max((int)ext[i], whole ? DSVG_BORDER : need[i]);
-}
-
 // enqueue the reconstruction half shared by encoder and decoder: inverse transform (+prediction) and
 // border extension of kept reconstructions, for device jobs [0,nI) intra and [nI,n) inter
 // insym: details come from the symbol planes -- bit 0: I pictures, bit 1: luma of P pictures, bit 2: chroma of P pictures
@@ -1372,35 +1348,92 @@ static int enqueue_recon(dsvg_ctx *c, int nI, int n, int d0 = 0, int insym = 0, 
     return DSVG_OK;
 }
 
+// The launch sequence of one coding stream (group g) for frame steps [t_first, t_end) of a planned call.  The groups' sequences are
+// independent of each other (different HIP streams, disjoint jobs), so for calls with many small frame steps -- where the HOST's enqueue
+// rate is what the device waits for: 13 launches x 30 steps x 4 us -- each group is enqueued by a thread of its own (round 4).
+static int enqueue_group(dsvg_ctx *c, const BatchPlan &P, const dsvg_rc_job *rcj, int g, int t_first, int t_end)
+{
+    const int base = P.base, njobs = P.njobs, NG = P.NG;
+    const int *gk = P.gk;
+    const bool sse = c->q[DSVG_Q_SSE].on, ssim = c->q[DSVG_Q_SSIM].on, xres = c->q[DSVG_Q_XSSE].on || c->q[DSVG_Q_XSSIM].on;
+    hipStream_t st = g ? c->stx[g] : c->st;
+    if (rcj && t_first == 0)       // the quantisers of the first frame step, from the state the streams' last packets left
+        launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, base + gk[g], gk[g + 1] - gk[g], 0);
+    for (int t = t_first; t < t_end; t++) {
+        const int k0 = gk[g], n = gk[g + 1] - gk[g];                                // device jobs [k0, k0 + n) of the step
+        const int d0 = base + t * njobs + k0;
+        const int nI = std::min(std::max(P.nI[t] - k0, 0), n);                      // I jobs among them come first
+        const JobDev *jd = c->jobs_d + d0;
+        const int fz = c->llq ? 4 : 3;                                              // fused quantiser (4: the LL region's too); levels 4..5 launched once below
+        if (nI > 0) {
+            launch_fwd_sbt(st, jd, nI, c->G, 0, 1, 0, 1, &c->prof, 0, fz);
+            launch_fwd_sbt(st, jd, nI, c->G, 1, 2, 0, 1, &c->prof, 0, fz);
+        }
+        if (n > nI) {
+            const int nP = n - nI;
+            const DMV *mv0 = P.mv_contig ? c->mvs + (size_t)(d0 + nI) * c->nblk : nullptr;     // (shared tables: JobDev.mvs)
+            if (c->mc_fused) {
+                // inter blocks are predicted inside the forward transform; k_mc only serves the intra blocks (block means)
+                if (P.icnt[NG * t + g]) launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0, c->ilist_d + (size_t)base * c->nblk + P.ioff[NG * t + g], P.icnt[NG * t + g]);
+                const int gw = P.icnt[NG * t + g] || !P.noint[NG * t + g];      // intra blocks somewhere in these pictures (or not known)
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, &c->prof, 0, fz, &c->MG, mv0, gw);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, &c->prof, 0, fz, &c->MG, mv0, gw);
+            } else {
+                launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, &c->prof, 0, fz);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, &c->prof, 0, fz);
+            }
+        }
+        // levels >= 6 in LDS; the LL quantiser (inside the tail kernel and k_fwd_haar_mid<4> when llq, else k_hz_quant<true>);
+        // then the reconstruction (P pictures: straight from the symbol planes), then the entropy stage:
+        // k_hz_collect* is the LAST reader of the sparse symbol planes and clears what it reads
+        launch_fwd_mid4(st, jd, n, c->G, 0, 3, c->llq, &c->prof);                  // levels 4..5 of all planes, I and P jobs alike
+        if (c->llq) launch_tail_q(st, jd, n, c->G, 0, 3, &c->prof);
+        else {
+            launch_sbt_tail(st, jd, n, c->G, 0, 3, 0, &c->prof);
+            launch_hz_quant(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0,
+                            (c->CL.w3[0] * c->CL.h3[0] + HZ_CHUNK - 1) / HZ_CHUNK);
+        }
+        // (pictures nobody predicts from -- intra-only streams -- have no reconstruction to make (dsv_encoder.c:665); a group without a single kept reconstruction skips the inverse transform altogether)
+        // Measured pictures all need theirs: a job without a kept slot gets it in its work frame (JobDev.xf), where the inverse
+        // kernels put it; k_sse / k_ssim read it there, in stream order behind the reconstruction and before anything can overwrite it.
+        // With both measurements on, k_ssim makes the SSE too: one pass over the pictures
+        const bool keeps = sse || ssim || xres || P.keeps[NG * t + g];
+        if (keeps) OPCHK(enqueue_recon(c, nI, n, d0, 7, st, true, c->llq));
+        if (ssim) launch_ssim(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSIM].dev, sse ? c->q[DSVG_Q_SSE].dev : nullptr);
+        else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSE].dev);
+        // (the same place and ordering argument: the reconstruction upscaled to the reference geometry, k_xres_quality)
+        if (xres) launch_xres(st, jd, n, c->L[0], c->xg, c->xref_d, c->psum, c->q[DSVG_Q_XSSE].on ? c->q[DSVG_Q_XSSE].dev : nullptr, c->q[DSVG_Q_XSSIM].on ? c->q[DSVG_Q_XSSIM].dev : nullptr);
+        launch_hz_pack(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
+        // rate control: the sizes of these packets -> the quantiser tables of the same streams' pictures of the next step
+        if (rcj) launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, d0, n, 1);
+    }
+    return DSVG_OK;
+}
+
 // Enqueue nsteps frame steps of njobs pictures each (jobs[step*njobs + j]); step k+1 may use the
 // reconstructions step k produces.  All host-built tables of the whole call travel in ONE set of
 // host-to-device copies up front, then the kernel chains of the steps follow back to back.
 // The out slots of the call must form one contiguous block (they also index the device tables).
 // rcj (dsvg_code_batch_rc): the frame quantisers are chosen ON THE DEVICE by the rate control of each job's stream -- k_rc before
-// the first frame step and after every step's k_hz_scan (k_rc.hip); jobs[].quant is ignored
+// the first frame step and after every step's k_hz_scan (k_rc.hip); jobs[].quant is ignored.
+// Plan (plan_code_batch, dsvg_batch_plan.h: every check and every decision), commit, job records, uploads, enqueue, join.
 static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_job *jobs, const dsvg_rc_job *rcj)
 {
-    if (!c || !jobs || nsteps < 1 || njobs < 1 || njobs > c->max_jobs || nsteps * njobs > c->out_slots) {
-        dsvg_set_error("bad code_batch arguments"); return DSVG_ERR_ARG;
-    }
-    if (rcj)
-        for (int i = 0; i < nsteps * njobs; i++) {
-            if (rcj[i].rc_slot < 0 || rcj[i].rc_slot >= c->rc_slots || rcj[i].prefix_len < 0) { dsvg_set_error("bad rate-control job %d", i); return DSVG_ERR_ARG; }
-            if (i >= njobs && rcj[i].rc_slot != rcj[i - njobs].rc_slot) { dsvg_set_error("a stream must keep its position from frame step to frame step (rate-control job %d)", i); return DSVG_ERR_ARG; }
-            for (int k = i - i % njobs; k < i; k++)
-                if (rcj[k].rc_slot == rcj[i].rc_slot) { dsvg_set_error("two pictures of one rate-controlled stream in one frame step (jobs %d, %d)", k, i); return DSVG_ERR_ARG; }
-        }
-    HIPCHK(hipSetDevice(c->device));
-    const bool sse = c->q[DSVG_Q_SSE].on;                         // quality measurement of this call's pictures (dsvg_ctx_sse_enable)
-    const bool ssim = c->q[DSVG_Q_SSIM].on;                       // (dsvg_ctx_ssim_enable)
-    const bool xres = c->q[DSVG_Q_XSSE].on || c->q[DSVG_Q_XSSIM].on;   // (dsvg_ctx_xres_enable)
+    if (!c) { dsvg_set_error("bad code_batch arguments"); return DSVG_ERR_ARG; }
     static const bool cprof = getenv("DSV1_HOST_PROF") != nullptr;
     const auto cnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tc0 = cprof ? cnow() : 0.0;
-    const int total = nsteps * njobs;
-    int base = jobs[0].out_slot;
-    for (int i = 1; i < total; i++) base = std::min(base, jobs[i].out_slot);
-    if (base < 0 || base + total > c->out_slots) { dsvg_set_error("out slots of a batch must be a contiguous block"); return DSVG_ERR_ARG; }
+    BatchPlan &P = c->plan;
+    {   // a refused call leaves the context as it found it: no event recorded, no call counted, no reference frame taken
+        BatchGeo geo = c->bgeo;
+        geo.code_streams = c->code_streams;
+        const int rc = plan_code_batch(geo, batch_switches(), nsteps, njobs, jobs, rcj, c->prof.mask != 0, c->ilist_h, P);
+        if (rc) { dsvg_set_error("%s", P.err); return rc; }
+    }
+    const int total = P.total, base = P.base, NG = P.NG;
+    HIPCHK(hipSetDevice(c->device));
+    const bool xres = c->q[DSVG_Q_XSSE].on || c->q[DSVG_Q_XSSIM].on;   // (dsvg_ctx_xres_enable)
     // source frames are produced on the analysis stream: make the coding stream wait for them
     HIPCHK(hipEventRecord(c->ev_a, c->st_a));
     HIPCHK(hipStreamWaitEvent(c->st, c->ev_a, 0));
@@ -1414,142 +1447,36 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             if (e >= 0 && !seen[e]) { seen[e] = 1; HIPCHK(hipEventSynchronize(c->ev_coded[e])); }
         }
     }
-    // Two coding streams, each with half of the pictures of every frame step: the chain of a step has a dozen small,
-    // latency-bound kernels (levels >= 4, LL quantiser, scan) during which one half leaves the chip to the other
-    // half's large kernels.  Needs steps of one picture type (the device order is I jobs, then P jobs) and enough jobs.
-    std::vector<int> nIs(nsteps);
-    for (int t = 0; t < nsteps; t++) {
-        int nI = 0;
-        for (int i = 0; i < njobs; i++) nI += jobs[(size_t)t * njobs + i].ref_recon_slot < 0;
-        nIs[t] = nI;
-    }
-    int NG = std::min(std::min(c->code_streams, DSVG_MAX_CODE_STREAMS), njobs / 8);
-    // Small frame steps (ABR streams, a GPU's share of a few 4K GOPs, one stream's chains) are bound by the latency of the chain's
-    // dozen launches, not by the chip: two halves on two streams run side by side (round 4; DSV1_NO_SMALL_SPLIT=1: one stream)
-    static const bool no_small_split = getenv("DSV1_NO_SMALL_SPLIT") != nullptr;
-    if (NG < 2 && njobs >= 2 && c->code_streams >= 2 && !no_small_split) NG = 2;
-    if (NG < 1) NG = 1;
-    bool anyP = false;
-    for (int t = 0; t < nsteps; t++) {
-        if (nIs[t] != 0 && nIs[t] != njobs) NG = 1;
-        anyP = anyP || nIs[t] == 0;
-    }
-    if (!anyP) NG = 1;               // I pictures only: their kernels are large and gain nothing (intra-only measured 3 % slower split)
-    if (NG > 1) {
-        // The groups run on different streams and are only joined at the end of the call: a reconstruction written by
-        // group g in step k may be read as a reference in step k+1 only by group g (same stream = ordered), and no two
-        // groups may write one slot.  Callers that keep stream s at position s of every step satisfy this; any other
-        // job order takes the single-stream path instead of racing.
-        std::vector<int> writer((size_t)c->n_recon, -1);
-        for (int t = 0; t < nsteps && NG > 1; t++) {
-            const dsvg_pic_job *js = jobs + (size_t)t * njobs;
-            std::vector<int> ord;
-            for (int i = 0; i < njobs; i++) if (js[i].ref_recon_slot < 0) ord.push_back(i);
-            for (int i = 0; i < njobs; i++) if (js[i].ref_recon_slot >= 0) ord.push_back(i);
-            std::vector<int> now((size_t)c->n_recon, -1);
-            for (int k = 0; k < njobs; k++) {
-                const dsvg_pic_job &j = js[ord[k]];
-                int gg = 0;                                          // group of device position k (the gk[] split below)
-                while (gg + 1 < NG && k >= (int)((long)njobs * (gg + 1) / NG)) gg++;
-                if (j.ref_recon_slot >= 0 && j.ref_recon_slot < c->n_recon && writer[j.ref_recon_slot] >= 0 && writer[j.ref_recon_slot] != gg) NG = 1;
-                if (j.recon_slot >= 0 && j.recon_slot < c->n_recon) {
-                    if (now[j.recon_slot] >= 0 && now[j.recon_slot] != gg) NG = 1;
-                    if (writer[j.recon_slot] >= 0 && writer[j.recon_slot] != gg) NG = 1;     // overwriting what another group may still read
-                    now[j.recon_slot] = gg;
-                }
-            }
-            for (int r = 0; r < c->n_recon; r++) if (now[r] >= 0) writer[r] = now[r];
+    // what the call leaves in the context, per picture in device order: its type and whether it is measured (fetch), the reference frame
+    // it takes, its reconstruction slot and the border extents written there (what dsvg_recon_border reports)
+    if (c->slot_isP.size() != (size_t)c->out_slots) c->slot_isP.assign((size_t)c->out_slots, 0);
+    if (c->slot_ext.size() != (size_t)c->n_recon * 8) c->slot_ext.assign((size_t)c->n_recon * 8, (short)DSVG_BORDER);
+    for (int i = 0; i < total; i++) {
+        const dsvg_pic_job &j = jobs[i - i % njobs + P.order[(size_t)i]];
+        c->slot_isP[(size_t)j.out_slot] = (char)(j.ref_recon_slot >= 0);
+        const uint8_t *xr = nullptr;
+        if (xres) {
+            // the reference frame dsvg_ctx_xres_refs set for the slot, taken by this call (none: the picture is not measured)
+            xr = c->xref_next[(size_t)j.out_slot];
+            c->xref_next[(size_t)j.out_slot] = nullptr;
+            c->xref_h[j.out_slot] = xr;
         }
-    }
-    int gk[DSVG_MAX_CODE_STREAMS + 1];                        // device jobs [gk[g], gk[g+1]) of every step -> stream g
-    for (int g = 0; g <= NG; g++) gk[g] = (int)((long)njobs * g / NG);
-    std::vector<int> ioff((size_t)NG * nsteps, 0), icnt((size_t)NG * nsteps, 0);
-    std::vector<char> noint((size_t)NG * nsteps, 1);          // every P picture of the (step, group) was scanned for intra blocks (and icnt says how many)
-    int *il = c->ilist_h + (size_t)base * c->nblk;         // intra blocks of each (step, group)'s P pictures (mc_fused)
-    int iln = 0;
-    std::vector<const dsvg_pic_job *> dj((size_t)total);   // the caller's job behind every device job
-    std::vector<int> dpos(rcj ? (size_t)total : 0);        // rate control: device position of the caller's job i of step t
-    for (int t = 0; t < nsteps; t++) {
-        const dsvg_pic_job *js = jobs + (size_t)t * njobs;
-        // device order inside a step: intra jobs first, then inter jobs (kernels are specialised per type)
-        std::vector<int> order;
-        for (int i = 0; i < njobs; i++) if (js[i].ref_recon_slot < 0) order.push_back(i);
-        for (int i = 0; i < njobs; i++) if (js[i].ref_recon_slot >= 0) order.push_back(i);
-        for (int k = 0; k < njobs; k++) {
-            const dsvg_pic_job &j = js[order[k]];
-            const int isP = j.ref_recon_slot >= 0;
-            const int d = base + t * njobs + k;
-            int g = 0;
-            while (k >= gk[g + 1]) g++;
-            if (k == gk[g]) ioff[NG * t + g] = iln;
-            if (j.src_slot < 0 || j.src_slot >= c->n_src || j.ref_recon_slot >= c->n_recon || j.recon_slot >= c->n_recon ||
-                j.out_slot < base || j.out_slot >= base + total || !j.stable_blocks || (isP && !j.mvs)) {
-                dsvg_set_error("bad picture job (step %d job %d)", t, order[k]); return DSVG_ERR_ARG;
-            }
-            dj[(size_t)t * njobs + k] = &j;
-            if (c->slot_isP.size() != (size_t)c->out_slots) c->slot_isP.assign((size_t)c->out_slots, 0);
-            c->slot_isP[(size_t)j.out_slot] = (char)isP;
-            const uint8_t *xr = nullptr;
-            if (xres) {
-                // the reference frame dsvg_ctx_xres_refs set for the slot, taken by this call (none: the picture is not measured)
-                xr = c->xref_next[(size_t)j.out_slot];
-                c->xref_next[(size_t)j.out_slot] = nullptr;
-                c->xref_h[j.out_slot] = xr;
-            }
-            for (int kind = 0; kind < DSVG_Q_KINDS; kind++) {
-                dsvg_ctx::Quality &q = c->q[kind];
-                if (!q.measured.empty()) q.measured[(size_t)j.out_slot] = (char)(q.on && (kind < DSVG_Q_XSSE || xr));
-            }
-            if (rcj) dpos[(size_t)t * njobs + order[k]] = k;
-            if (isP && !c->mc_fused) noint[NG * t + g] = 0;
-            if (isP && c->mc_fused && !j.no_intra_blocks) {
-                // index relative to the first P job of the group's launch
-                const int k0 = std::max(gk[g], nIs[t]);
-                const DMV *mv = reinterpret_cast<const DMV *>(j.mvs);
-                for (int b = 0; b < c->nblk; b++)
-                    if (mv[b].mode != 0) il[iln++] = (k - k0) * c->nblk + b;
-            }
-            icnt[NG * t + g] = iln - ioff[NG * t + g];
+        for (int kind = 0; kind < DSVG_Q_KINDS; kind++) {
+            dsvg_ctx::Quality &q = c->q[kind];
+            if (!q.measured.empty()) q.measured[(size_t)j.out_slot] = (char)(q.on && (kind < DSVG_Q_XSSE || xr));
         }
+        c->slots_h[base + i] = j.recon_slot;
+        if (j.recon_slot >= 0) memcpy(&c->slot_ext[(size_t)j.recon_slot * 8], &P.ext[(size_t)i * 8], sizeof(short) * 8);
     }
-    // Block tables shared between jobs (quality ladders, dsv1_ladder_open: every rung of a source passes the SAME host arrays for
-    // the source's motion field and stability flags): jobs of the call that pass the same pointer get one device copy.  Keyed on
-    // the pointer, not the content -- a call that shares no pointer keeps the layout it always had (device job base + i's tables
-    // at table index i) and uploads the same bytes.  mvu / stu: table index of job i; mvcp / stcp: job i is the one copied.
-    // (Several jobs may now read one source slot: no coding kernel writes it -- JobDev.src / srcp are const, and the in-place
-    // luma / chroma of slot_y / slot_cu / slot_cv is the caller's clip, read only.)
-    std::vector<int> mvu((size_t)total), stu((size_t)total);
-    std::vector<char> mvcp((size_t)total, 0), stcp((size_t)total, 0);
-    int nmv = 0, nst = 0;
-    {
-        std::unordered_map<const void *, int> mvk, stk;
-        std::vector<char> mvdone((size_t)total, 0);
-        for (int i = 0; i < total; i++) {
-            const dsvg_pic_job &j = *dj[(size_t)i];
-            const auto s = stk.emplace(j.stable_blocks, nst);
-            if (s.second) { stcp[(size_t)i] = 1; nst++; }
-            stu[(size_t)i] = s.first->second;
-            if (!j.mvs) mvu[(size_t)i] = nmv++;                          // (I pictures need none: never shared)
-            else {
-                const auto m = mvk.emplace(j.mvs, nmv);
-                if (m.second) nmv++;
-                mvu[(size_t)i] = m.first->second;
-            }
-            if (j.ref_recon_slot >= 0 && !mvdone[(size_t)mvu[(size_t)i]]) { mvdone[(size_t)mvu[(size_t)i]] = 1; mvcp[(size_t)i] = 1; }
-        }
-    }
-    const bool mv_contig = nmv == total;                     // the vectors of consecutive device jobs lie back to back (mvs0 of the kernels)
     {   // the job records themselves (quantiser tables of three planes, pointers, copies of the block tables): independent per
         // job, built on the session layer's worker pool (1 920 jobs: 1.5 ms on one thread)
-        struct BuildCtx {
-            dsvg_ctx *c; const std::vector<const dsvg_pic_job *> *dj; int base, njobs;
-            const std::vector<int> *mvu, *stu; const std::vector<char> *mvcp, *stcp;
-        } bc = {c, &dj, base, njobs, &mvu, &stu, &mvcp, &stcp};
+        struct BuildCtx { dsvg_ctx *c; const BatchPlan *P; const dsvg_pic_job *jobs; } bc = {c, &P, jobs};
         dsv1_par_for(total, [](void *vp, int idx, int) {
             BuildCtx &B = *static_cast<BuildCtx *>(vp);
             dsvg_ctx *c = B.c;
-            const dsvg_pic_job &j = *(*B.dj)[(size_t)idx];
-            const int k = idx % B.njobs, d = B.base + idx;
+            const BatchPlan &P = *B.P;
+            const int k = idx % P.njobs, d = P.base + idx;
+            const dsvg_pic_job &j = B.jobs[idx - k + P.order[(size_t)idx]];
             const int isP = j.ref_recon_slot >= 0;
             JobDev &jb = c->jobs_h[d];
             fill_job(c, jb, k, isP, j.quant, d);
@@ -1573,65 +1500,38 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             // the reconstruction goes to another slot than the reference: the prediction is written straight into it and the
             // inverse transform only touches the tiles that carry a residual (ping-pong slots, see dsv1_enc.c)
             if (isP && jb.recon && j.recon_slot != j.ref_recon_slot && !c->no_inplace_pred) jb.pred = jb.recon;
-            c->slots_h[d] = j.recon_slot;
-            const size_t um = (size_t)B.base + (size_t)(*B.mvu)[(size_t)idx], us = (size_t)B.base + (size_t)(*B.stu)[(size_t)idx];
+            const size_t um = (size_t)P.base + (size_t)P.mvu[(size_t)idx], us = (size_t)P.base + (size_t)P.stu[(size_t)idx];
             jb.mvs = c->mvs + um * c->nblk;
             jb.stable = c->stable + us * c->nblk;
-            if ((*B.stcp)[(size_t)idx]) memcpy(c->stable_h + us * c->nblk, j.stable_blocks, (size_t)c->nblk);
-            if ((*B.mvcp)[(size_t)idx]) memcpy(c->mv_h + um * c->nblk, j.mvs, (size_t)c->nblk * sizeof(DMV));
+            if (P.stcp[(size_t)idx]) memcpy(c->stable_h + us * c->nblk, j.stable_blocks, (size_t)c->nblk);
+            if (P.mvcp[(size_t)idx]) memcpy(c->mv_h + um * c->nblk, j.mvs, (size_t)c->nblk * sizeof(DMV));
+            memcpy(jb.ext, &P.ext[(size_t)idx * 8], sizeof(short) * 8);      // how far the reconstruction's border is written
         }, &bc);
-    }
-    if (!c->no_lazy_border) {
-        // Borders of the reconstructions: a reconstruction is read beyond its edges only by the pictures that predict from it,
-        // and only as far as their motion vectors point -- which is known here (the vectors of every picture of the call are).
-        // A slot rewritten within the call gets the reach of the pictures in between; a slot that outlives the call gets the
-        // whole border unless the caller vouches that no later call predicts from it (border_hint).
-        std::vector<int> writer((size_t)c->n_recon, -1);
-        for (int t = 0; t < nsteps; t++) {
-            for (int k = 0; k < njobs; k++) {
-                const dsvg_pic_job *j = dj[(size_t)t * njobs + k];
-                const int w = j->ref_recon_slot >= 0 ? writer[j->ref_recon_slot] : -1;
-                if (w >= 0) border_reach(c, reinterpret_cast<const DMV *>(j->mvs), j->has_reach ? j->mv_reach : nullptr, c->jobs_h[base + w].ext);
-            }
-            for (int k = 0; k < njobs; k++) {
-                const dsvg_pic_job *j = dj[(size_t)t * njobs + k];
-                for (int i = 0; i < 8; i++) c->jobs_h[base + t * njobs + k].ext[i] = 0;   // (a picture without a reconstruction too: nobody reads the border of its work frame -- advisor round 5)
-                if (j->recon_slot < 0) continue;
-                writer[j->recon_slot] = t * njobs + k;
-            }
-        }
-        for (int r = 0; r < c->n_recon; r++)
-            if (writer[r] >= 0 && !dj[writer[r]]->border_hint)
-                for (int i = 0; i < 8; i++) c->jobs_h[base + writer[r]].ext[i] = DSVG_BORDER;
     }
     if (getenv("DSV1_BORDER_DEBUG"))
         for (int t = 0; t < nsteps; t++) {
-            const short *e = c->jobs_h[base + t * njobs].ext;
+            const short *e = &P.ext[(size_t)t * njobs * 8], *r = jobs[(size_t)t * njobs + P.order[(size_t)t * njobs]].mv_reach;
             fprintf(stderr, "[dsvg border] step %d job 0: luma %d %d %d %d chroma %d %d %d %d; reach %d %d %d %d\n", t, e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[7],
-                    dj[(size_t)t * njobs]->mv_reach[0], dj[(size_t)t * njobs]->mv_reach[1], dj[(size_t)t * njobs]->mv_reach[2], dj[(size_t)t * njobs]->mv_reach[3]);
+                    r[0], r[1], r[2], r[3]);
         }
-    if (c->slot_ext.size() != (size_t)c->n_recon * 8) c->slot_ext.assign((size_t)c->n_recon * 8, (short)DSVG_BORDER);
-    for (int i = 0; i < total; i++)                             // (what dsvg_recon_border reports)
-        if (dj[i]->recon_slot >= 0) memcpy(&c->slot_ext[(size_t)dj[i]->recon_slot * 8], c->jobs_h[base + i].ext, sizeof(short) * 8);
     if (rcj) {
         // the rate-control table of every device job: its stream's state, the bytes in front of the quantiser field, and the
         // device job of the stream's next picture (same caller position in the next frame step)
-        for (int t = 0; t < nsteps; t++)
-            for (int i = 0; i < njobs; i++) {
-                RcJobDev &r = c->rcj_h[base + t * njobs + dpos[(size_t)t * njobs + i]];
-                const dsvg_rc_job &q = rcj[(size_t)t * njobs + i];
-                r.slot = q.rc_slot; r.prefix_len = q.prefix_len; r.forced_intra = q.forced_intra;
-                r.next = t + 1 < nsteps ? base + (t + 1) * njobs + dpos[(size_t)(t + 1) * njobs + i] : -1;
-            }
+        for (int i = 0; i < total; i++) {
+            RcJobDev &r = c->rcj_h[base + i];
+            const dsvg_rc_job &q = rcj[i - i % njobs + P.order[(size_t)i]];
+            r.slot = q.rc_slot; r.prefix_len = q.prefix_len; r.forced_intra = q.forced_intra;
+            r.next = P.rc_next[(size_t)i];
+        }
         HIPCHK(hipMemcpyAsync(c->rcj_d + base, c->rcj_h + base, sizeof(RcJobDev) * total, hipMemcpyHostToDevice, c->st));
     }
     const double tc1 = cprof ? cnow() : 0.0;
     tl_mark(c, c->st, "tab0");
-    if (iln) HIPCHK(hipMemcpyAsync(c->ilist_d + (size_t)base * c->nblk, il, sizeof(int) * (size_t)iln, hipMemcpyHostToDevice, c->st));
+    if (P.iln) HIPCHK(hipMemcpyAsync(c->ilist_d + (size_t)base * c->nblk, c->ilist_h + (size_t)base * c->nblk, sizeof(int) * (size_t)P.iln, hipMemcpyHostToDevice, c->st));
     for (int r = 0; r < link_repeat(); r++) {
     HIPCHK(hipMemcpyAsync(c->jobs_d + base, c->jobs_h + base, sizeof(JobDev) * total, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->stable + (size_t)base * c->nblk, c->stable_h + (size_t)base * c->nblk, (size_t)c->nblk * nst, hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemcpyAsync(c->mvs + (size_t)base * c->nblk, c->mv_h + (size_t)base * c->nblk, (size_t)c->nblk * nmv * sizeof(DMV), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->stable + (size_t)base * c->nblk, c->stable_h + (size_t)base * c->nblk, (size_t)c->nblk * P.nst, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->mvs + (size_t)base * c->nblk, c->mv_h + (size_t)base * c->nblk, (size_t)c->nblk * P.nmv * sizeof(DMV), hipMemcpyHostToDevice, c->st));
     }
     HIPCHK(hipMemcpyAsync(c->slots_d + 2 * c->out_slots + base, c->slots_h + base, sizeof(int) * total, hipMemcpyHostToDevice, c->st));
     // the measurements' sums of the call's out slots start at zero (k_sse / k_ssim add into them); before the fork: every coding stream is behind it
@@ -1652,85 +1552,22 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             HIPCHK(hipStreamWaitEvent(c->stx[g], c->ev_fork, 0));
         }
     }
-    // The launch sequence of one coding stream (group g), frame step by frame step.  The groups' sequences are independent of each
-    // other (different HIP streams, disjoint jobs), so for calls with many small frame steps -- where the HOST's enqueue rate is
-    // what the device waits for: 13 launches x 30 steps x 4 us -- each group is enqueued by a thread of its own (round 4).
-    auto enqueue_steps = [&](int g, int t_first, int t_end) -> int {
-        hipStream_t st = g ? c->stx[g] : c->st;
-        if (rcj && t_first == 0)       // the quantisers of the first frame step, from the state the streams' last packets left
-            launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, base + gk[g], gk[g + 1] - gk[g], 0);
-        for (int t = t_first; t < t_end; t++) {
-            const int k0 = gk[g], n = gk[g + 1] - gk[g];                                // device jobs [k0, k0 + n) of the step
-            const int d0 = base + t * njobs + k0;
-            const int nI = std::min(std::max(nIs[t] - k0, 0), n);                       // I jobs among them come first
-            const JobDev *jd = c->jobs_d + d0;
-            const int fz = c->llq ? 4 : 3;                                              // fused quantiser (4: the LL region's too); levels 4..5 launched once below
-            if (nI > 0) {
-                launch_fwd_sbt(st, jd, nI, c->G, 0, 1, 0, 1, &c->prof, 0, fz);
-                launch_fwd_sbt(st, jd, nI, c->G, 1, 2, 0, 1, &c->prof, 0, fz);
-            }
-            if (n > nI) {
-                const int nP = n - nI;
-                const DMV *mv0 = mv_contig ? c->mvs + (size_t)(d0 + nI) * c->nblk : nullptr;     // (shared tables: JobDev.mvs)
-                if (c->mc_fused) {
-                    // inter blocks are predicted inside the forward transform; k_mc only serves the intra blocks (block means)
-                    if (icnt[NG * t + g]) launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0, c->ilist_d + (size_t)base * c->nblk + ioff[NG * t + g], icnt[NG * t + g]);
-                    const int gw = icnt[NG * t + g] || !noint[NG * t + g];      // intra blocks somewhere in these pictures (or not known)
-                    launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, &c->prof, 0, fz, &c->MG, mv0, gw);
-                    launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, &c->prof, 0, fz, &c->MG, mv0, gw);
-                } else {
-                    launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0);
-                    launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, &c->prof, 0, fz);
-                    launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, &c->prof, 0, fz);
-                }
-            }
-            // levels >= 6 in LDS; the LL quantiser (inside the tail kernel and k_fwd_haar_mid<4> when llq, else k_hz_quant<true>);
-            // then the reconstruction (P pictures: straight from the symbol planes), then the entropy stage:
-            // k_hz_collect* is the LAST reader of the sparse symbol planes and clears what it reads
-            launch_fwd_mid4(st, jd, n, c->G, 0, 3, c->llq, &c->prof);                  // levels 4..5 of all planes, I and P jobs alike
-            if (c->llq) launch_tail_q(st, jd, n, c->G, 0, 3, &c->prof);
-            else {
-                launch_sbt_tail(st, jd, n, c->G, 0, 3, 0, &c->prof);
-                launch_hz_quant(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0,
-                                (c->CL.w3[0] * c->CL.h3[0] + HZ_CHUNK - 1) / HZ_CHUNK);
-            }
-            // (pictures nobody predicts from -- intra-only streams -- have no reconstruction to make (dsv_encoder.c:665); a group without a single kept reconstruction skips the inverse transform altogether)
-            // Measured pictures all need theirs: a job without a kept slot gets it in its work frame (JobDev.xf), where the inverse
-            // kernels put it; k_sse / k_ssim read it there, in stream order behind the reconstruction and before anything can overwrite it.
-            // With both measurements on, k_ssim makes the SSE too: one pass over the pictures
-            bool keeps = sse || ssim || xres;
-            for (int k = k0; k < k0 + n && !keeps; k++) keeps = dj[(size_t)t * njobs + k]->recon_slot >= 0;
-            if (keeps) OPCHK(enqueue_recon(c, nI, n, d0, 7, st, true, c->llq));
-            if (ssim) launch_ssim(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSIM].dev, sse ? c->q[DSVG_Q_SSE].dev : nullptr);
-            else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSE].dev);
-            // (the same place and ordering argument: the reconstruction upscaled to the reference geometry, k_xres_quality)
-            if (xres) launch_xres(st, jd, n, c->L[0], c->xg, c->xref_d, c->psum, c->q[DSVG_Q_XSSE].on ? c->q[DSVG_Q_XSSE].dev : nullptr, c->q[DSVG_Q_XSSIM].on ? c->q[DSVG_Q_XSSIM].dev : nullptr);
-            launch_hz_pack(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
-            // rate control: the sizes of these packets -> the quantiser tables of the same streams' pictures of the next step
-            if (rcj) launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, d0, n, 1);
-        }
-        return DSVG_OK;
-    };
-    {
-        static const bool no_par_enqueue = getenv("DSV1_NO_PAR_ENQUEUE") != nullptr;      // (A/B)
-        // (the event brackets of the profiling hooks are kept in one list: profiled calls are enqueued by this thread alone)
-        if (NG > 1 && nsteps * 13 >= 100 && njobs < 64 && !c->prof.mask && !no_par_enqueue) {
-            // (HIP's last error and this library's error text are per THREAD: each worker checks its own launches and hands its text over)
-            struct PE { decltype(enqueue_steps) *f; int device, nsteps, rc[DSVG_MAX_CODE_STREAMS]; char msg[DSVG_MAX_CODE_STREAMS][256]; } pe = {&enqueue_steps, c->device, nsteps, {0}, {{0}}};
-            dsv1_par_for_long(NG, [](void *vp, int g, int) {
-                PE &P = *static_cast<PE *>(vp);
-                if (hipSetDevice(P.device) != hipSuccess) { P.rc[g] = DSVG_ERR_HIP; snprintf(P.msg[g], sizeof P.msg[g], "hipSetDevice failed on an enqueue thread"); return; }      // (the current device is per thread)
-                (void)hipGetLastError();
-                P.rc[g] = (*P.f)(g, 0, P.nsteps);
-                const hipError_t e = hipGetLastError();
-                if (P.rc[g]) snprintf(P.msg[g], sizeof P.msg[g], "%s", dsvg_last_error());
-                else if (e != hipSuccess) { P.rc[g] = DSVG_ERR_HIP; snprintf(P.msg[g], sizeof P.msg[g], "launch failed on coding stream %d: %s", g, hipGetErrorString(e)); }
-            }, &pe);
-            for (int g = 0; g < NG; g++) if (pe.rc[g]) { dsvg_set_error("%s", pe.msg[g]); return pe.rc[g]; }
-        } else {
-            for (int t = 0; t < nsteps; t++)
-                for (int g = 0; g < NG; g++) OPCHK(enqueue_steps(g, t, t + 1));
-        }
+    if (P.par_enqueue) {
+        // (HIP's last error and this library's error text are per THREAD: each worker checks its own launches and hands its text over)
+        struct PE { dsvg_ctx *c; const BatchPlan *P; const dsvg_rc_job *rcj; int rc[DSVG_MAX_CODE_STREAMS]; char msg[DSVG_MAX_CODE_STREAMS][256]; } pe = {c, &P, rcj, {0}, {{0}}};
+        dsv1_par_for_long(NG, [](void *vp, int g, int) {
+            PE &E = *static_cast<PE *>(vp);
+            if (hipSetDevice(E.c->device) != hipSuccess) { E.rc[g] = DSVG_ERR_HIP; snprintf(E.msg[g], sizeof E.msg[g], "hipSetDevice failed on an enqueue thread"); return; }      // (the current device is per thread)
+            (void)hipGetLastError();
+            E.rc[g] = enqueue_group(E.c, *E.P, E.rcj, g, 0, E.P->nsteps);
+            const hipError_t e = hipGetLastError();
+            if (E.rc[g]) snprintf(E.msg[g], sizeof E.msg[g], "%s", dsvg_last_error());
+            else if (e != hipSuccess) { E.rc[g] = DSVG_ERR_HIP; snprintf(E.msg[g], sizeof E.msg[g], "launch failed on coding stream %d: %s", g, hipGetErrorString(e)); }
+        }, &pe);
+        for (int g = 0; g < NG; g++) if (pe.rc[g]) { dsvg_set_error("%s", pe.msg[g]); return pe.rc[g]; }
+    } else {
+        for (int t = 0; t < nsteps; t++)
+            for (int g = 0; g < NG; g++) OPCHK(enqueue_group(c, P, rcj, g, t, t + 1));
     }
     if (NG > 1) { tl_mark(c, c->st, "code1a"); tl_mark(c, c->stx[1], "code1b"); }
     for (int g = 1; g < NG; g++) {
@@ -1745,6 +1582,44 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
         for (int i = 0; i < total; i++) c->slot_ev[base + i] = e;
     }
     HIPCHK(hipGetLastError());
+    return DSVG_OK;
+}
+
+// What plan_code_batch decides for a call of an encoder context created with these arguments (include/dsvg.h), without a device:
+// the context's own derivation of BatchGeo on the geometry tables, with the switches the caller names instead of the environment's
+extern "C" int dsvg_code_batch_plan(int width, int height, int subsamp, int n_recon_slots, int n_src_slots, int max_jobs, int out_slots, int code_streams,
+                                    unsigned switches, int nsteps, int njobs, const dsvg_pic_job *jobs, const dsvg_rc_job *rc, dsvg_batch_plan *out)
+{
+    if (!out || n_src_slots < 1 || n_recon_slots < 1 || max_jobs < 1) { dsvg_set_error("bad code_batch_plan arguments"); return DSVG_ERR_ARG; }
+    CtxGeo geo;
+    int r = geom_check(width, height, subsamp, geo);
+    if (r) return r;
+    BatchGeo B = batch_geo(geo, n_src_slots, n_recon_slots, max_jobs, out_slots, !(switches & DSVG_BATCH_NO_MC_FUSION), !(switches & DSVG_BATCH_NO_LAZY_BORDER));
+    B.code_streams = code_streams;
+    const BatchSwitches sw = { (switches & DSVG_BATCH_NO_SMALL_SPLIT) != 0, (switches & DSVG_BATCH_NO_PAR_ENQUEUE) != 0 };
+    std::vector<int> ilist(B.mc_fused ? (size_t)B.out_slots * B.nblk : 0);
+    BatchPlan P;
+    if ((r = plan_code_batch(B, sw, nsteps, njobs, jobs, rc, (switches & DSVG_BATCH_PROFILED) != 0, ilist.data(), P))) { dsvg_set_error("%s", P.err); return r; }
+    const int total = P.total, nsg = nsteps * P.NG;
+    out->nblk = B.nblk; out->mc_fused = B.mc_fused;
+    out->base = P.base; out->total = total; out->ng = P.NG;
+    static_assert(sizeof out->gk / sizeof out->gk[0] == DSVG_MAX_CODE_STREAMS + 1, "dsvg_batch_plan.gk holds every group boundary");
+    for (int g = 0; g <= DSVG_MAX_CODE_STREAMS; g++) out->gk[g] = g <= P.NG ? P.gk[g] : 0;
+    out->iln = P.iln; out->nmv = P.nmv; out->nst = P.nst; out->mv_contig = P.mv_contig; out->par_enqueue = P.par_enqueue;
+    if (!out->nI || !out->order || !out->mvu || !out->stu || !out->mvcp || !out->stcp || !out->ext || !out->rc_next || !out->ioff || !out->icnt ||
+        !out->noint || !out->keeps || !out->ilist) { dsvg_set_error("code_batch_plan: null array"); return DSVG_ERR_ARG; }
+    if (out->cap_steps < nsteps || out->cap_jobs < total || out->cap_groups < nsg || out->cap_ilist < P.iln) {
+        dsvg_set_error("code_batch_plan: the arrays are too small (%d steps, %d jobs, %d step groups, %d intra blocks)", nsteps, total, nsg, P.iln);
+        return DSVG_ERR_ARG;
+    }
+    for (int t = 0; t < nsteps; t++) out->nI[t] = P.nI[t];
+    for (int i = 0; i < total; i++) {
+        out->order[i] = P.order[i]; out->mvu[i] = P.mvu[i]; out->stu[i] = P.stu[i]; out->mvcp[i] = P.mvcp[i]; out->stcp[i] = P.stcp[i];
+        out->rc_next[i] = rc ? P.rc_next[i] : -1;
+        for (int k = 0; k < 8; k++) out->ext[i * 8 + k] = P.ext[(size_t)i * 8 + k];
+    }
+    for (int i = 0; i < nsg; i++) { out->ioff[i] = P.ioff[i]; out->icnt[i] = P.icnt[i]; out->noint[i] = P.noint[i]; out->keeps[i] = P.keeps[i]; }
+    for (int i = 0; i < P.iln; i++) out->ilist[i] = ilist[(size_t)P.base * B.nblk + i];
     return DSVG_OK;
 }
 

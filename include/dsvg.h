@@ -495,6 +495,48 @@ typedef struct dsvg_inv_step {
 int dsvg_inv_plan(int width, int height, int subsamp, int group, int isP, int with_tail, int insym, int patch_kernel, int fuse_border,
                   unsigned switches, int njobs, dsvg_inv_step *steps, int cap, int *fb);
 
+/* The plan of a coding call (tests): what dsvg_code_batch / dsvg_code_batch_rc (rc != NULL) decide on the host for these jobs in an
+ * encoder context created with these arguments, without a device -- the call's own plan (plan_code_batch, csrc/dsvg_batch_plan.h: the
+ * call commits it and enqueues from it), on the geometry tables of dsvg_ctx_create.  code_streams as dsvg_ctx_code_streams sets it;
+ * switches: a mask of DSVG_BATCH_* for the A/B switches DSV1_NO_SMALL_SPLIT, DSV1_NO_PAR_ENQUEUE, DSV1_NO_LAZY_BORDER, DSV1_NO_MC_FUSION,
+ * whatever the environment says, and PROFILED for a context with kernel timing on (dsvg_prof_enable).  Returns DSVG_OK, a negative
+ * DSVG_ERR_* for a geometry dsvg_ctx_create refuses, the code and text the call itself answers for jobs it refuses, or DSVG_ERR_ARG
+ * for arrays that are missing or too small (the scalars are filled in then).
+ * Device job d = t * njobs + k is the picture at position k of frame step t in device order (I pictures first); sg = ng * t + g is
+ * coding stream g's share of step t, device positions [gk[g], gk[g + 1]).  The caller sets the arrays and their capacities:
+ *   cap_steps:  nI[t], the I pictures of step t;
+ *   cap_jobs:   order[d] = the caller's index inside its step of device job d; mvu[d] / stu[d] = index of the job's vector / flag table
+ *               among the call's tables (jobs that pass one pointer share one), mvcp[d] / stcp[d] = 1: this job's host table is the one
+ *               uploaded; ext[8 d + i] = how far the job's reconstruction gets its border written (as dsvg_recon_border); rc_next[d] =
+ *               base + the device job of the same rate-controlled stream's next picture (-1: none, or no rc);
+ *   cap_groups: ioff[sg] / icnt[sg] = the share's intra blocks in ilist, entries (position among the share's P pictures) * nblk +
+ *               block; noint[sg] = 1: icnt says all there is to know (0: motion compensation is not fused, the blocks were not listed);
+ *               keeps[sg] = 1: a picture of the share keeps its reconstruction;
+ *   cap_ilist:  ilist, iln entries.
+ * Append-only: later versions add fields at the end. */
+#define DSVG_BATCH_NO_SMALL_SPLIT  1
+#define DSVG_BATCH_NO_PAR_ENQUEUE  2
+#define DSVG_BATCH_NO_LAZY_BORDER  4
+#define DSVG_BATCH_NO_MC_FUSION    8
+#define DSVG_BATCH_PROFILED        16
+typedef struct dsvg_batch_plan {
+    int cap_steps, cap_jobs, cap_groups, cap_ilist;
+    int *nI;
+    int *order, *mvu, *stu;
+    unsigned char *mvcp, *stcp;
+    short *ext;
+    int *rc_next;
+    int *ioff, *icnt;
+    unsigned char *noint, *keeps;
+    int *ilist;
+    int nblk, mc_fused;            /* of the geometry: blocks per picture, motion compensation fused into the forward transform */
+    int base, total, ng, gk[5];    /* first out slot, pictures, coding streams and their split of a step */
+    int iln, nmv, nst, mv_contig;  /* intra-list entries; vector / flag tables uploaded; nmv == total */
+    int par_enqueue;               /* every coding stream is enqueued by a thread of its own */
+} dsvg_batch_plan;
+int dsvg_code_batch_plan(int width, int height, int subsamp, int n_recon_slots, int n_src_slots, int max_jobs, int out_slots, int code_streams,
+                         unsigned switches, int nsteps, int njobs, const dsvg_pic_job *jobs, const dsvg_rc_job *rc, dsvg_batch_plan *out);
+
 #ifdef __cplusplus
 }
 #endif
