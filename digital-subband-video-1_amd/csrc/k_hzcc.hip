@@ -1537,6 +1537,7 @@ __global__ __launch_bounds__(256) void k_hz_codes(JobDev *__restrict__ jobs, int
 // C. runs -> scan positions: q_1 = run_1, q_m = q_{m-1} + 1 + run_m, one workgroup per (picture, plane).  Eight
 // consecutive entries per thread and pass (two 16-byte loads; entry 0, the DC, adds nothing), wave scan of the thread
 // totals, waves chained through LDS.
+#define POS_ITEMS 8               // entries per thread and pass (two int4 loads / stores)
 __global__ __launch_bounds__(PARSE_THREADS) void k_hz_positions(JobDev *__restrict__ jobs, int c0)
 {
     const int c = c0 + (int)blockIdx.y;
@@ -1555,15 +1556,15 @@ __global__ __launch_bounds__(PARSE_THREADS) void k_hz_positions(JobDev *__restri
     if (tid == 0) s_q = 0ull;
     __syncthreads();
     int count = 0;
-    for (int base = 0; base <= nent; base += PARSE_THREADS * 8) {
-        const int mb = base + tid * 8;
+    for (int base = 0; base <= nent; base += PARSE_THREADS * POS_ITEMS) {
+        const int mb = base + tid * POS_ITEMS;
         int4 ra = make_int4(0, 0, 0, 0), rb = make_int4(0, 0, 0, 0);
         if (mb <= nent) ra = *reinterpret_cast<const int4 *>(R + mb);
         if (mb + 4 <= nent) rb = *reinterpret_cast<const int4 *>(R + mb + 4);
-        const int rv[8] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
-        unsigned long long pre[8], tot = 0;
+        const int rv[POS_ITEMS] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w};
+        unsigned long long pre[POS_ITEMS], tot = 0;
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
+        for (int i = 0; i < POS_ITEMS; i++) {
             const int m = mb + i;
             tot += (m >= 1 && m <= nent) ? (unsigned long long)(unsigned)rv[i] + (m > 1 ? 1ull : 0ull) : 0ull;
             pre[i] = tot;
@@ -1578,21 +1579,21 @@ __global__ __launch_bounds__(PARSE_THREADS) void k_hz_positions(JobDev *__restri
         __syncthreads();
         unsigned long long q0 = s_q + (inc - tot);                        // positions before this thread's entries
         for (int w = 0; w < wv; w++) q0 += s_w64[w];
-        int out[8], nok = 0;
+        int out[POS_ITEMS], nok = 0;
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
+        for (int i = 0; i < POS_ITEMS; i++) {
             const int m = mb + i;
             const unsigned long long q = q0 + pre[i];
             const bool ok = m >= 1 && m <= nent && q < (unsigned long long)nscan;
             out[i] = ok ? (int)q : rv[i];
             nok += ok;
         }
-        if (mb + 7 <= nent) {
+        if (mb + POS_ITEMS - 1 <= nent) {
             *reinterpret_cast<int4 *>(R + mb) = make_int4(mb == 0 ? 0 : out[0], out[1], out[2], out[3]);
             *reinterpret_cast<int4 *>(R + mb + 4) = make_int4(out[4], out[5], out[6], out[7]);
         } else {                                                          // tail: never write past entry nent
 #pragma unroll
-            for (int i = 0; i < 8; i++)
+            for (int i = 0; i < POS_ITEMS; i++)
                 if (mb + i >= 1 && mb + i <= nent) R[mb + i] = out[i];
         }
         // positions are increasing, so the valid entries form a prefix: counting them is enough
@@ -1625,6 +1626,9 @@ __global__ __launch_bounds__(256) void k_hz_scatter_lv(const JobDev *__restrict_
     // and level group 0 of the others; launches 1, 2 then only serve the planes that keep int32 coefficients
     if (phase < 0 ? (!jb.dec_sym[c] && ph != 0) : (jb.dec_sym[c] || ph != phase)) return;
     if (p == 0) {                                                     // unquantised DC (hzcc.c:495)
+        // a parsable plane whose first run is 0 puts entry 1 on the DC's cell as well: the reference writes it and then the DC
+        // over it (hzcc.c:340, 495), so only entry 0 stores here
+        if (i != 0) return;
         (jb.coef + jb.hz_coef_off[c])[0] = v;
         if (jb.dec_sym[c] && (v < -jb.dec_lim[0] || v > jb.dec_lim[0])) atomicOr(jb.dec_flag, 1);
         return;
