@@ -304,6 +304,9 @@ def lib():
                                             _C.POINTER(_C.c_int), _C.c_void_p, _C.c_size_t]
         L.dsv1_draw_info_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int,
                                           _C.c_int]
+        L.dsv1_decbatch_set_output_scale.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_decbatch_out_dims.argtypes = [_C.c_void_p, _C.POINTER(_C.c_int), _C.POINTER(_C.c_int)]
+        L.dsvg_ctx_output_scale.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int]
         _lib = L
     return _lib
 
@@ -1284,6 +1287,25 @@ class DecBatch:
         if self.L.dsv1_decbatch_set_output_rgb(self.h, None if rf is None else _C.byref(rf)) != 0:
             raise ValueError("not a valid RGB output format for these streams (subsampling 0x%x)" % self.fmt)
         self._output_changed()
+
+    def set_output_scale(self, w, h=None, filt=SCALE_CUBIC):
+        """from the next decode() on, frames are handed out at w x h in the place of the streams' size, resampled in the output pass
+        (dsv1_decbatch_set_output_scale; filt: SCALE_TENT / SCALE_CUBIC); None or 0, 0 switches it off.  Scale first, format second:
+        the call drops the output format in force (packed planar frames of the scaled geometry again), and set_output_format /
+        set_output_rgb called after it resolve for w x h.  frame_bytes and out_dims follow; ValueError (and scale and format as
+        they were) for a ratio outside 1/8 .. 8 on an axis of a plane, a size that is not positive or an unknown filter."""
+        if w is None:
+            w, h = 0, 0
+        if self.L.dsv1_decbatch_set_output_scale(self.h, int(w), int(0 if h is None else h), int(filt)) != 0:
+            raise ValueError("not a valid output scale for these streams: %r x %r, filter %r" % (w, h, filt))
+        self._output_changed()
+
+    @property
+    def out_dims(self):
+        """(w, h) of the luma plane of the frames handed out under the setting in force (dsv1_decbatch_out_dims)"""
+        w, h = _C.c_int(0), _C.c_int(0)
+        _chk(self.L.dsv1_decbatch_out_dims(self.h, _C.byref(w), _C.byref(h)), "dsv1_decbatch_out_dims")
+        return w.value, h.value
 
     def set_draw_info(self, mode):
         """from the next decode() on, the debug overlay of mode 0 .. 7 (DSV_DRAW_* bits; 0: off) is drawn onto the luma of every picture

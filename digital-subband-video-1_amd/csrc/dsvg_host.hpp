@@ -72,7 +72,8 @@ struct Slab {
     X(KID_INV_TILE_S1_SYM_F, "void k_inv_haar_tile<true, 1, true>") X(KID_INV_TILE_S1_SYM, "void k_inv_haar_tile<false, 1, true>") \
     X(KID_INV_B4T, "void k_inv_b4t<false>") X(KID_INV_B4T_SYM, "void k_inv_b4t<true>") \
     X(KID_PIXOUT_PLANAR, "void k_pixout<0, false>") X(KID_PIXOUT_PLANAR16, "void k_pixout<0, true>") X(KID_PIXOUT_SEMI, "void k_pixout<1, false>") \
-    X(KID_PIXOUT_SEMI16, "void k_pixout<1, true>") X(KID_PIXOUT_YUYV, "void k_pixout<2, false>") X(KID_PIXOUT_UYVY, "void k_pixout<3, false>")
+    X(KID_PIXOUT_SEMI16, "void k_pixout<1, true>") X(KID_PIXOUT_YUYV, "void k_pixout<2, false>") X(KID_PIXOUT_UYVY, "void k_pixout<3, false>") \
+    X(KID_SCALE_SLOTS, "k_scale_slots")
 enum {
 #define X(id, name) id,
     DSVG_KERNEL_IDS(X)

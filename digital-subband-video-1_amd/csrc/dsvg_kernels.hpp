@@ -145,6 +145,20 @@ int xres_geo_build(XresGeo &G, const FrameLayout &L, int rw, int rh, int filter)
 void xres_geo_free(XresGeo &G);
 void launch_xres(hipStream_t st, const JobDev *jobs, int njobs, const FrameLayout &L, const XresGeo &G, const uint8_t *const *xref,
                  const HzPlaneSum *psum0, unsigned long long *xsse, unsigned long long *xssim);
+// k_scale.hip: one geometry of the exact integer resampler (tables of dsv1_resample_weights in device memory, the tile height and the
+// exact LDS bound chosen from them), and its entry that reads reconstruction slots for the decoders' output pass: entry i of the
+// (slot, output frame) pairs tab_d reads the bordered frame at slab + slot * sfb and writes packed planar frame dst + frame * dfb
+struct ScalePlane;
+struct ScaleGeo {
+    ScalePlane *planes_d = nullptr;      // [3] + tables, one allocation
+    int ntiles = 0;
+    size_t lds = 0;
+    int th_tile = 0, rows_cap = 0, th_cap = 0, tv_cap = 0, span_cap = 0;
+    size_t dfb = 0, sbytes = 0;          // bytes of a packed destination frame; sample bytes of a source frame
+};
+int  scale_geo_build(ScaleGeo &G, const FrameLayout &L, int fmt, int dw, int dh, int filter);   // source: frames of layout L; replaces G's tables only on success
+void scale_geo_free(ScaleGeo &G);
+void launch_scale_slots(hipStream_t st, const ScaleGeo &G, const uint8_t *slab, size_t sfb, const int *tab_d, int n, uint8_t *dst, size_t dfb, Prof *pf = nullptr);
 // k_drawinfo.hip: the decoders' debug overlay (mode: DSV_DRAW_* bits, non-zero) onto the luma planes of n pictures -- picture i at
 // luma0 + i * pic_pitch, w x h at row stride `stride` -- from their block tables, picture i at mvs + i * nblk and stable + i * nblk
 // (nblk = ceil(w / bw) * ceil(h / bh)); two launches in stream order, every store inside the plane

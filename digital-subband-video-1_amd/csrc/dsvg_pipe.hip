@@ -272,6 +272,16 @@ struct dsvg_ctx {
     uint8_t *draw_scratch = nullptr;
     std::vector<int> draw_at;
     bool draw_any = false;
+    // Decoder, output scale (dsvg_ctx_output_scale, k_scale_slots): with a size set, the output pass resamples every picture it hands out
+    // to osc_w x osc_h at the context's subsampling -- straight into the destination for packed planar output, into osc_scratch (packed
+    // planar frames osc_fb apart, one per reconstruction slot, allocated by the first pass that needs it) in front of a format.
+    // osc_tab_d: that format pass's (scratch frame, output frame) pairs.  Off: nothing of this exists or runs.
+    bool osc_on = false;
+    int osc_w = 0, osc_h = 0, osc_filter = -1;
+    ScaleGeo osc;
+    uint8_t *osc_scratch = nullptr;
+    size_t osc_fb = 0;
+    int *osc_tab_d = nullptr;
     int *ilist_h = nullptr, *ilist_d = nullptr;   // intra blocks of the P pictures of a batch (pinned / device), indexed like jobs_h
     // host-resident input: two device ingest buffers filled on a copy stream of their own, so the upload of the
     // next batch runs under the analysis and coding of the current one
@@ -432,8 +442,9 @@ static void ctx_free(dsvg_ctx *c)
     for (int i = 0; i < 6; i++) c->src[i].release();
     c->recon.release(); c->xf.release(); c->pred.release();
     xres_geo_free(c->xg);
+    scale_geo_free(c->osc);
     void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->draw_scratch, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, (void *)c->xref_d};
+                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->draw_scratch, c->osc_scratch, c->osc_tab_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, (void *)c->xref_d};
     for (void *p : d) if (p) (void)hipFree(p);
     void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, (void *)c->xref_h};
     for (void *p : hh) if (p) (void)hipHostFree(p);
@@ -1933,6 +1944,28 @@ extern "C" int dsvg_ctx_draw_info(dsvg_ctx *c, int mode)
     return DSVG_OK;
 }
 
+extern "C" int dsvg_ctx_output_scale(dsvg_ctx *c, int out_w, int out_h, int filter)
+{
+    if (!c) { dsvg_set_error("null context"); return DSVG_ERR_ARG; }
+    if (out_w == 0 && out_h == 0) {
+        if (c->osc_on) { OPCHK(dec_resolve(c)); c->osc_on = false; }       // (the tables stay for the next switch-on)
+        return DSVG_OK;
+    }
+    if (filter != 0 && filter != 1) { dsvg_set_error("dsvg_ctx_output_scale: bad filter %d", filter); return DSVG_ERR_ARG; }
+    if (out_w < 1 || out_h < 1) { dsvg_set_error("dsvg_ctx_output_scale: bad size %dx%d", out_w, out_h); return DSVG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    OPCHK(dec_resolve(c));                               // a recorded pass is replayed, if at all, under the setting it was made with
+    if (!c->osc.planes_d || c->osc_w != out_w || c->osc_h != out_h || c->osc_filter != filter) {
+        HIPCHK(hipDeviceSynchronize());                 // (no pass in flight may still read the tables or the scratch being replaced)
+        OPCHK(scale_geo_build(c->osc, c->L[0], c->fmt, out_w, out_h, filter));   // (refused: the setting in force stays)
+        if (c->osc_scratch) { (void)hipFree(c->osc_scratch); c->osc_scratch = nullptr; }
+        c->osc_w = out_w; c->osc_h = out_h; c->osc_filter = filter;
+        c->osc_fb = (c->osc.dfb + 255) & ~(size_t)255;
+    }
+    c->osc_on = true;
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_download_recon(dsvg_ctx *c, int recon_slot, uint8_t *yuv_out)
 {
     if (!c || !yuv_out || recon_slot < 0 || recon_slot >= c->n_recon) return DSVG_ERR_ARG;
@@ -2016,31 +2049,46 @@ extern "C" int dsvg_download_recon_raw(dsvg_ctx *c, int recon_slot, uint8_t *raw
 // The output pass of decoded pictures: n reconstruction slots to frames of `out`, in the context's packed planar frames (fmt == nullptr,
 // k_pack_n: frame i at position i) or in an output format (k_pixout: frame i at position index[i]; index == nullptr: i).  Device
 // output is written optimistically and recorded while the decoder call's escape flags are not back (dsvg_ctx::DecPending); host
-// output settles the call first, since it synchronises anyway.
+// output settles the call first, since it synchronises anyway.  With an output scale set (dsvg_ctx_output_scale) the pictures are
+// resampled on the way (k_scale_slots): packed planar frames of the scaled geometry straight into the destination, or into the
+// context's scratch, which the format's pass (k_pixout, k_rgbout) then reads in place of the slots.
 static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, void *out, size_t pitch, int on_device, const dsvg_pixout *fmt)
 {
     if (!c || !slots || !out || n < 1 || n > c->n_recon) { dsvg_set_error("bad %s arguments", fmt ? "export_recons" : "pack_recons"); return DSVG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
     const FrameLayout &L = c->L[0];
+    const bool sc = c->osc_on;
     PoSource S;
     for (int p = 0; p < 3; p++) { S.w[p] = L.w[p]; S.h[p] = L.h[p]; S.pitch[p] = L.stride[p]; S.off[p] = (long long)L.off[p]; }
     S.fb = (long long)L.pitch;
-    const size_t fb = fmt ? fmt->frame_bytes : (size_t)L.w[0] * L.h[0] + 2 * (size_t)L.w[1] * L.h[1];
+    if (sc) {                                           // what a format reads then: the scratch's packed planar frames of the scaled geometry
+        long long o = 0;
+        for (int p = 0; p < 3; p++) {
+            S.w[p] = p ? rsu(c->osc_w, fmt_hs(c->fmt)) : c->osc_w; S.h[p] = p ? rsu(c->osc_h, fmt_vs(c->fmt)) : c->osc_h;
+            S.pitch[p] = S.w[p]; S.off[p] = o;
+            o += (long long)S.w[p] * S.h[p];
+        }
+        S.fb = (long long)c->osc_fb;
+    }
+    const size_t fb = fmt ? fmt->frame_bytes : sc ? c->osc.dfb : (size_t)L.w[0] * L.h[0] + 2 * (size_t)L.w[1] * L.h[1];
     if (pitch < fb) { dsvg_set_error("output pitch smaller than a frame"); return DSVG_ERR_ARG; }
     if (fmt && pixout_check(fmt, S, pitch)) { dsvg_set_error("the output format does not fit the context's frames"); return DSVG_ERR_ARG; }
-    // the table the kernel reads: the slots (k_pack_n), or (slot, output frame) pairs (k_pixout)
-    std::vector<int> pairs;
+    // the table the kernel reads: the slots (k_pack_n), or (slot, output frame) pairs (k_pixout).  Scaled: (slot, frame i) pairs for
+    // k_scale_slots -- frame i of the destination, or of the scratch, which a format then reads by its own (frame i, output frame) pairs
+    std::vector<int> pairs, fpairs;
     int last = 0;
     for (int i = 0; i < n; i++) {
         if (slots[i] < 0 || slots[i] >= c->n_recon) { dsvg_set_error("slot out of range"); return DSVG_ERR_ARG; }
-        if (!fmt) continue;
-        const int o = index ? index[i] : i;
+        if (!fmt && !sc) continue;
+        const int o = fmt && index ? index[i] : i;
         if (o < 0) { dsvg_set_error("negative output frame index"); return DSVG_ERR_ARG; }
-        pairs.push_back(slots[i]); pairs.push_back(o);
+        pairs.push_back(slots[i]); pairs.push_back(sc ? i : o);
+        if (sc && fmt && index) { fpairs.push_back(i); fpairs.push_back(o); }
         last = std::max(last, o);
     }
-    const int *tab = fmt ? pairs.data() : slots;
-    const size_t tab_bytes = sizeof(int) * (size_t)n * (fmt ? 2 : 1);
+    const int tw = fmt || sc ? 2 : 1;                   // ints per table entry
+    const int *tab = tw == 2 ? pairs.data() : slots;
+    const size_t tab_bytes = sizeof(int) * (size_t)n * tw;
     dsvg_ctx::DecPending &P = c->dec_pending;
     if (!on_device) OPCHK(dec_resolve(c));              // (a flagged decoder call is repeated first)
     else if (P.active && !P.in_redo && P.slots.empty()) {
@@ -2056,14 +2104,16 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
     std::vector<int> shown;
     std::vector<char> alt((size_t)n, 0);
     if (c->draw_any) {
-        shown.assign(tab, tab + (size_t)n * (fmt ? 2 : 1));
+        shown.assign(tab, tab + (size_t)n * tw);
         for (int i = 0; i < n; i++) {
-            int &e = shown[(size_t)i * (fmt ? 2 : 1)];
+            int &e = shown[(size_t)i * tw];
             if (c->draw_at[(size_t)e] >= 0) { e = c->draw_at[(size_t)e]; alt[(size_t)i] = 1; }
         }
         tab = shown.data();
     }
     if (!c->otab_d) HIPCHK(hipMalloc((void **)&c->otab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
+    if (sc && fmt && !c->osc_scratch) HIPCHK(hipMalloc((void **)&c->osc_scratch, c->osc_fb * (size_t)c->n_recon + 256));
+    if (!fpairs.empty() && !c->osc_tab_d) HIPCHK(hipMalloc((void **)&c->osc_tab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
     // One pass at a time: the first coding stream waits for the pass before, which keeps the passes in order and the table whole.
     // Round 5: device output of four pictures or more goes to the second coding stream -- beside the next call's entropy decoding, which
     // touches neither the reconstructions nor the caller's frames (70 us of a 620 us step of 64 pictures).  Whatever rewrites a
@@ -2079,6 +2129,7 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
         HIPCHK(hipStreamWaitEvent(st, c->ev_pack[0], 0));
     }
     HIPCHK(hipMemcpyAsync(c->otab_d, tab, tab_bytes, hipMemcpyHostToDevice, st));   // pageable: staged by the runtime
+    if (!fpairs.empty()) HIPCHK(hipMemcpyAsync(c->osc_tab_d, fpairs.data(), sizeof(int) * fpairs.size(), hipMemcpyHostToDevice, st));
     uint8_t *dst = (uint8_t *)out;
     size_t dpitch = pitch, span = 0;
     if (!on_device) {
@@ -2105,9 +2156,11 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
     for (int i0 = 0, i1; i0 < n; i0 = i1) {
         for (i1 = i0 + 1; i1 < n && alt[(size_t)i1] == alt[(size_t)i0]; i1++) ;
         const uint8_t *slab = alt[(size_t)i0] ? c->draw_scratch : c->recon.p;
-        if (fmt) OPCHK(launch_pixout(st, fmt, S, slab, c->otab_d + 2 * (size_t)i0, i1 - i0, dst, dpitch, &c->prof));
+        if (sc) launch_scale_slots(st, c->osc, slab, L.pitch, c->otab_d + 2 * (size_t)i0, i1 - i0, fmt ? c->osc_scratch : dst, fmt ? c->osc_fb : dpitch, &c->prof);
+        else if (fmt) OPCHK(launch_pixout(st, fmt, S, slab, c->otab_d + 2 * (size_t)i0, i1 - i0, dst, dpitch, &c->prof));
         else launch_pack_n(st, dst + (size_t)i0 * dpitch, dpitch, slab, L, c->otab_d + i0, i1 - i0, &c->prof);
     }
+    if (sc && fmt) OPCHK(launch_pixout(st, fmt, S, c->osc_scratch, fpairs.empty() ? nullptr : c->osc_tab_d, n, dst, dpitch, &c->prof));
     if (st != c->st) { HIPCHK(hipEventRecord(c->ev_pack[1], st)); c->pack_pending = true; }
     if (!on_device) {
         if (fmt) HIPCHK(hipMemcpyAsync(out, dst, span, hipMemcpyDeviceToHost, st));

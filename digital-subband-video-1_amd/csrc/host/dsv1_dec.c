@@ -326,6 +326,7 @@ struct dsv1_decbatch {
     int out_set;                     /* an output format is in force (dsv1_decbatch_set_output_format); else the packed planar pass */
     dsvg_pixout out;                 /* ... resolved for the streams' geometry: it does not depend on the block size */
     int draw_mode;                   /* debug overlay (dsv1_decbatch_set_draw_info): handed to every context the batch builds */
+    int sc_w, sc_h, sc_filter;       /* output scale (dsv1_decbatch_set_output_scale; 0 x 0: off): handed on likewise; the formats resolve for it */
 };
 
 void dsv1_decbatch_close(dsv1_decbatch *d)
@@ -376,13 +377,17 @@ static int set_output(dsv1_decbatch *d, int rc, const dsvg_pixout *F, int on)
     return DSVG_OK;
 }
 
+/* the geometry the output formats resolve for: the streams', or the output scale's */
+static int out_w(const dsv1_decbatch *d) { return d->sc_w ? d->sc_w : d->meta.width; }
+static int out_h(const dsv1_decbatch *d) { return d->sc_w ? d->sc_h : d->meta.height; }
+
 int dsv1_decbatch_set_output_format(dsv1_decbatch *d, const dsv1_pix_format *pf, int out_subsamp)
 {
     dsvg_pixout F;
     if (!d) return DSVG_ERR_ARG;
     if (!pf) { d->out_set = 0; return DSVG_OK; }
-    return set_output(d, dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, DSV1_CHROMA_NONE, &F), &F,
-                      !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp)));
+    return set_output(d, dsv1_pixout_of(pf, out_w(d), out_h(d), d->meta.subsamp, out_subsamp, DSV1_CHROMA_NONE, &F), &F,
+                      !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, out_w(d), out_h(d), d->meta.subsamp)));
 }
 
 /* every pair, the ones that double chroma included; `upsample` is validated always and read only where something goes up */
@@ -391,8 +396,8 @@ int dsv1_decbatch_set_output_format_up(dsv1_decbatch *d, const dsv1_pix_format *
     dsvg_pixout F;
     if (!d || (upsample != DSV1_CHROMA_REPLICATE && upsample != DSV1_CHROMA_LINEAR)) return DSVG_ERR_ARG;
     if (!pf) { d->out_set = 0; return DSVG_OK; }
-    return set_output(d, dsv1_pixout_of(pf, d->meta.width, d->meta.height, d->meta.subsamp, out_subsamp, upsample, &F), &F,
-                      !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, d->meta.width, d->meta.height, d->meta.subsamp)));
+    return set_output(d, dsv1_pixout_of(pf, out_w(d), out_h(d), d->meta.subsamp, out_subsamp, upsample, &F), &F,
+                      !(out_subsamp == d->meta.subsamp && dsv1_pix_is_default(pf, out_w(d), out_h(d), d->meta.subsamp)));
 }
 
 int dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf)
@@ -400,7 +405,25 @@ int dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf)
     dsvg_pixout F;
     if (!d) return DSVG_ERR_ARG;
     if (!rf) { d->out_set = 0; return DSVG_OK; }
-    return set_output(d, dsv1_rgbout_of(rf, d->meta.width, d->meta.height, d->meta.subsamp, &F), &F, 1);
+    return set_output(d, dsv1_rgbout_of(rf, out_w(d), out_h(d), d->meta.subsamp, &F), &F, 1);
+}
+
+/* scale first, format second: the call drops the format in force; a refusal leaves both as they were */
+int dsv1_decbatch_set_output_scale(dsv1_decbatch *d, int w, int h, int filter)
+{
+    int rc;
+    if (!d) return DSVG_ERR_ARG;
+    if ((rc = dsvg_ctx_output_scale(d->ctx, w, h, filter))) return rc;
+    d->sc_w = w; d->sc_h = h; d->sc_filter = filter;
+    d->out_set = 0;
+    return DSVG_OK;
+}
+
+int dsv1_decbatch_out_dims(const dsv1_decbatch *d, int *w, int *h)
+{
+    if (!d || !w || !h) return DSVG_ERR_ARG;
+    *w = out_w(d); *h = out_h(d);
+    return DSVG_OK;
 }
 
 int dsv1_decbatch_set_draw_info(dsv1_decbatch *d, int mode)
@@ -415,7 +438,12 @@ int dsv1_decbatch_set_draw_info(dsv1_decbatch *d, int mode)
 size_t dsv1_decbatch_out_frame_bytes(const dsv1_decbatch *d)
 {
     if (!d) return 0;
-    return d->out_set ? d->out.frame_bytes : d->g.frame_bytes;
+    if (d->out_set) return d->out.frame_bytes;
+    if (d->sc_w) {
+        const int hs = (d->meta.subsamp >> 2) & 3, vs = d->meta.subsamp & 3;
+        return (size_t)d->sc_w * d->sc_h + 2 * (size_t)((d->sc_w + (1 << hs) - 1) >> hs) * (size_t)((d->sc_h + (1 << vs) - 1) >> vs);
+    }
+    return d->g.frame_bytes;
 }
 
 /* host part of one stream's packet: header + side information (a few hundred bytes) -> pj[s], status[s], fnum[s] */
@@ -466,7 +494,7 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
     parse_ctx pc;
     if (!d || !packets || !yuv_out || !status || !fnum) return DSVG_ERR_ARG;
     if (out_pitch == 0) out_pitch = dsv1_decbatch_out_frame_bytes(d);
-    else if (d->out_set && out_pitch < d->out.frame_bytes) return DSVG_ERR_ARG;      /* (the packed planar pass refuses its own) */
+    else if ((d->out_set || d->sc_w) && out_pitch < dsv1_decbatch_out_frame_bytes(d)) return DSVG_ERR_ARG;   /* (the unscaled packed planar pass refuses its own) */
     {   /* The block size is the streams' to choose (dsv_decoder.c:335-360); the batch shares one context, so it follows the
          * first picture packet of a call as long as no stream holds a reference picture (i.e. at the streams' start or where
          * every stream restarts with an I picture); a change in mid-GOP is an error of that stream (parse_stream). */
@@ -486,6 +514,7 @@ int dsv1_decbatch_decode(dsv1_decbatch *d, const DSV_BUF *packets, void *yuv_out
                 dsvg_ctx_destroy(d->ctx);
                 d->ctx = nc;
                 dsvg_ctx_draw_info(d->ctx, d->draw_mode);
+                if (d->sc_w && (rc = dsvg_ctx_output_scale(d->ctx, d->sc_w, d->sc_h, d->sc_filter))) return rc;
                 dsvg_ctx_geom(d->ctx, &d->g);
                 d->nblk = d->g.nblocks_h * d->g.nblocks_v;
                 free(d->stable); free(d->mvs);

@@ -23,6 +23,13 @@
 // LDS = rows x 256 + 2 (64 Th + TH Tv) + 32 x span bytes, bounded exactly on the host from the tables (scaler_geo): 31 KB for
 // 1080p -> 720p (TH 64, 102 rows), 42 KB for 1080p -> 540p, 62 KB at the worst ratio (8, cubic; TH 16): 2 to 5 workgroups per CU
 // of gfx950's 160 KB.  74 VGPRs, no scratch.
+// The tile body (scale_tile) has two entries.  k_scale reads tightly packed planar frames: rows of a plane are the plane's width apart,
+// frame blockIdx.y at src + y * sfb, written to dst + y * dfb.  k_scale_slots reads bordered reconstruction slots for the decoders'
+// output pass (output_pass, dsvg_pipe.hip): a plane's pixel (0, 0) at soff and its rows spitch apart (FrameLayout::off / stride), and
+// entry i of a (slot, output frame) table names the slot at slab + slot * sfb and the output frame at dst + frame * dfb.  It clamps
+// source indices exactly as the packed entry does and never reads a border sample for its value: a border is written only as far as
+// its readers reach.  gfx950, both entries: 74 VGPRs, 62 SGPRs, no scratch, no static LDS (the dynamic LDS above), 6 waves per SIMD by
+// registers.
 // A 16-byte load is issued only for an aligned chunk that holds at least one byte of the row's needed columns: it never leaves the
 // 16-byte block of a sample that exists.
 #include <algorithm>
@@ -42,13 +49,15 @@ struct ScalePlane {              // one plane's geometry and tables (device memo
     const short *hq;
     const int *vs;
     const short *vq;
+    long long spitch;            // k_scale_slots: distance of the source plane's rows (k_scale: the plane's width)
 };
 
 // LDS of a workgroup (sizes from the host): Hs int[rows_cap][SC_TW] | qh short[SC_TW * th_cap] | qv short[TH * tv_cap] | stage
 // byte[SC_RG][span_cap]
-__global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restrict__ planes, const uint8_t *__restrict__ src,
-                                                      uint8_t *__restrict__ dst, long long sfb, long long dfb, int TH, int rows_cap,
-                                                      int th_cap, int tv_cap, int span_cap)
+// sframe / dframe: the source and the destination frame of this workgroup; SLOTS: source rows are P.spitch apart, not P.sw
+template <bool SLOTS>
+__device__ __forceinline__ void scale_tile(const ScalePlane *__restrict__ planes, const uint8_t *__restrict__ sframe, uint8_t *__restrict__ dframe,
+                                           int TH, int rows_cap, int th_cap, int tv_cap, int span_cap)
 {
     extern __shared__ int4 sc_lds[];
     int *Hs = (int *)sc_lds;
@@ -66,7 +75,8 @@ __global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restri
     const int c0 = P.hs[x0], c1 = P.hs[x0 + nx - 1] + th - 1;
     const int lo = max(c0, 0), hi = min(c1, sw - 1);
     const int span = hi - lo + 1;
-    const uint8_t *plane = src + (long long)blockIdx.y * sfb + P.soff;
+    const uint8_t *plane = sframe + P.soff;
+    const long long spitch = SLOTS ? P.spitch : (long long)sw;
     const int nch = (span + 15) / 16 + 1;                          // 16-byte chunks a row segment can touch
     const int tid = threadIdx.x;
     // the tile's weights, once: its columns' horizontal and its rows' vertical taps
@@ -80,7 +90,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restri
         for (int it = tid; it < ng * nch; it += SC_THREADS) {
             const int i = it / nch, k = it - i * nch;
             const int sr = min(max(r0 + g + i, 0), sh - 1);
-            const uint8_t *row = plane + (long long)sr * sw;
+            const uint8_t *row = plane + (long long)sr * spitch;
             const uintptr_t a0 = ((uintptr_t)(row + lo)) & ~(uintptr_t)15, a = a0 + 16u * (uintptr_t)k;
             if (a <= (uintptr_t)(row + hi)) {
                 const int4 v = *(const int4 *)a;
@@ -120,24 +130,32 @@ __global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restri
         uint32_t o4[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) o4[j] = (uint32_t)min(max((V[j] + (1 << 19)) >> 20, 0), 255);
-        uint8_t *d = dst + (long long)blockIdx.y * dfb + P.doff + (long long)(y0 + yy) * dw + x0 + xq;
+        uint8_t *d = dframe + P.doff + (long long)(y0 + yy) * dw + x0 + xq;
         if (xq + 4 <= nx && ((uintptr_t)d & 3) == 0) *(uint32_t *)d = o4[0] | (o4[1] << 8) | (o4[2] << 16) | (o4[3] << 24);
         else
             for (int j = 0; j < 4 && xq + j < nx; j++) d[j] = (uint8_t)o4[j];
     }
 }
 
+__global__ __launch_bounds__(SC_THREADS) void k_scale(const ScalePlane *__restrict__ planes, const uint8_t *__restrict__ src,
+                                                      uint8_t *__restrict__ dst, long long sfb, long long dfb, int TH, int rows_cap,
+                                                      int th_cap, int tv_cap, int span_cap)
+{
+    scale_tile<false>(planes, src + (long long)blockIdx.y * sfb, dst + (long long)blockIdx.y * dfb, TH, rows_cap, th_cap, tv_cap, span_cap);
+}
+
+// tab: (slot, output frame) pairs, entry blockIdx.y
+__global__ __launch_bounds__(SC_THREADS) void k_scale_slots(const ScalePlane *__restrict__ planes, const uint8_t *__restrict__ slab,
+                                                            const int *__restrict__ tab, uint8_t *__restrict__ dst, long long sfb,
+                                                            long long dfb, int TH, int rows_cap, int th_cap, int tv_cap, int span_cap)
+{
+    const int slot = tab[2 * blockIdx.y], frame = tab[2 * blockIdx.y + 1];
+    scale_tile<true>(planes, slab + (long long)slot * sfb, dst + (long long)frame * dfb, TH, rows_cap, th_cap, tv_cap, span_cap);
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 extern "C" int dsv1_resample_taps(int S, int D, int filter);
 extern "C" int dsv1_resample_weights(int S, int D, int filter, int32_t *start, int16_t *q, int T);
-
-struct ScaleGeo {
-    ScalePlane *planes_d = nullptr;      // [3] + tables, one allocation
-    int ntiles = 0;
-    size_t lds = 0;
-    int th_tile = 0, rows_cap = 0, th_cap = 0, tv_cap = 0, span_cap = 0;
-    size_t dfb = 0;
-};
 
 struct dsvg_scaler {
     int device = 0, sw = 0, sh = 0, fmt = 0, filter = 0;
@@ -147,11 +165,14 @@ struct dsvg_scaler {
 
 static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-// tables of one geometry: [3] ScalePlane, then per plane hs int[dw], hq short[dw th], vs int[dh], vq short[dh tv]
-static int scaler_geo(dsvg_scaler *s, int dw, int dh, ScaleGeo &G)
+// tables of one geometry: [3] ScalePlane, then per plane hs int[dw], hq short[dw th], vs int[dh], vq short[dh tv].  The source is
+// packed planar frames of sw x sh at subsampling fmt, or (L != nullptr) the bordered frames of that layout: its planes' dims, offsets
+// and strides (k_scale_slots)
+static int scaler_geo(int sw, int sh, int fmt, int filter, const FrameLayout *L, int dw, int dh, ScaleGeo &G)
 {
-    const int hsh = fmt_hs(s->fmt), vsh = fmt_vs(s->fmt);
-    const int SW[3] = {s->sw, rsu(s->sw, hsh), rsu(s->sw, hsh)}, SH[3] = {s->sh, rsu(s->sh, vsh), rsu(s->sh, vsh)};
+    const int hsh = fmt_hs(fmt), vsh = fmt_vs(fmt);
+    const int SW[3] = {L ? L->w[0] : sw, L ? L->w[1] : rsu(sw, hsh), L ? L->w[2] : rsu(sw, hsh)};
+    const int SH[3] = {L ? L->h[0] : sh, L ? L->h[1] : rsu(sh, vsh), L ? L->h[2] : rsu(sh, vsh)};
     const int DW[3] = {dw, rsu(dw, hsh), rsu(dw, hsh)}, DH[3] = {dh, rsu(dh, vsh), rsu(dh, vsh)};
     ScalePlane pl[3];
     std::vector<std::vector<int32_t>> hs(3), vs(3);
@@ -161,11 +182,11 @@ static int scaler_geo(dsvg_scaler *s, int dw, int dh, ScaleGeo &G)
     long long so = 0, dof = 0;
     for (int p = 0; p < 3; p++) {
         // (dsv1_resample_*: for a downscale the tables are dsv1_scale_weights'; the callers have checked the direction they allow)
-        const int th = dsv1_resample_taps(SW[p], DW[p], s->filter), tv = dsv1_resample_taps(SH[p], DH[p], s->filter);
+        const int th = dsv1_resample_taps(SW[p], DW[p], filter), tv = dsv1_resample_taps(SH[p], DH[p], filter);
         if (th < 0 || tv < 0) { dsvg_set_error("scale %dx%d -> %dx%d: ratio outside 1/8..8", SW[p], SH[p], DW[p], DH[p]); return DSVG_ERR_ARG; }
         hs[p].resize(DW[p]); hq[p].resize((size_t)DW[p] * th); vs[p].resize(DH[p]); vq[p].resize((size_t)DH[p] * tv);
-        if (dsv1_resample_weights(SW[p], DW[p], s->filter, hs[p].data(), hq[p].data(), th) ||
-            dsv1_resample_weights(SH[p], DH[p], s->filter, vs[p].data(), vq[p].data(), tv)) { dsvg_set_error("weight tables"); return DSVG_ERR_ARG; }
+        if (dsv1_resample_weights(SW[p], DW[p], filter, hs[p].data(), hq[p].data(), th) ||
+            dsv1_resample_weights(SH[p], DH[p], filter, vs[p].data(), vq[p].data(), tv)) { dsvg_set_error("weight tables"); return DSVG_ERR_ARG; }
         // (the kernel's row and column ranges need starts that never decrease; its int32 bounds need sum |q| < 2 * 16384 in every row,
         // which Catmull-Rom's negative lobes keep in both directions -- asserted for every table built)
         for (int i = 1; i < DW[p]; i++) if (hs[p][i] < hs[p][i - 1]) { dsvg_set_error("weight table starts decrease"); return DSVG_ERR_ARG; }
@@ -180,7 +201,8 @@ static int scaler_geo(dsvg_scaler *s, int dw, int dh, ScaleGeo &G)
             }
         }
         pl[p].sw = SW[p]; pl[p].sh = SH[p]; pl[p].dw = DW[p]; pl[p].dh = DH[p]; pl[p].th = th; pl[p].tv = tv;
-        pl[p].soff = so; pl[p].doff = dof;
+        pl[p].soff = L ? (long long)L->off[p] : so; pl[p].doff = dof;
+        pl[p].spitch = L ? (long long)L->stride[p] : (long long)SW[p];
         so += (long long)SW[p] * SH[p]; dof += (long long)DW[p] * DH[p];
         th_cap = std::max(th_cap, th); tv_cap = std::max(tv_cap, tv);
         offs[p][0] = off; off = align16(off + sizeof(int32_t) * DW[p]);
@@ -216,6 +238,7 @@ static int scaler_geo(dsvg_scaler *s, int dw, int dh, ScaleGeo &G)
     G.th_cap = th_cap; G.tv_cap = tv_cap; G.span_cap = span_cap;
     G.ntiles = tile0;
     G.dfb = (size_t)dof;
+    G.sbytes = (size_t)so;
     HIPCHK(hipMalloc((void **)&G.planes_d, off));
     uint8_t *base = (uint8_t *)G.planes_d;
     std::vector<uint8_t> h(off, 0);
@@ -246,7 +269,7 @@ static int scaler_create_impl(dsvg_scaler *s, int ngeom, const int *dw, const in
     HIPCHK(hipSetDevice(s->device));
     s->geo.resize((size_t)ngeom);
     for (int g = 0; g < ngeom; g++) {
-        const int rc = scaler_geo(s, dw[g], dh[g], s->geo[(size_t)g]);
+        const int rc = scaler_geo(s->sw, s->sh, s->fmt, s->filter, nullptr, dw[g], dh[g], s->geo[(size_t)g]);
         if (rc) return rc;
     }
     return DSVG_OK;
@@ -279,4 +302,30 @@ extern "C" int dsvg_scaler_run(dsvg_scaler *s, void *stream, int g, const void *
     }
     HIPCHK(hipGetLastError());
     return DSVG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the decoders' output pass
+void scale_geo_free(ScaleGeo &G)
+{
+    if (G.planes_d) (void)hipFree(G.planes_d);
+    G = ScaleGeo();
+}
+
+int scale_geo_build(ScaleGeo &G, const FrameLayout &L, int fmt, int dw, int dh, int filter)
+{
+    ScaleGeo N;
+    const int rc = scaler_geo(L.w[0], L.h[0], fmt, filter, &L, dw, dh, N);
+    if (rc) { scale_geo_free(N); return rc; }
+    scale_geo_free(G);
+    G = N;
+    return DSVG_OK;
+}
+
+void launch_scale_slots(hipStream_t st, const ScaleGeo &G, const uint8_t *slab, size_t sfb, const int *tab_d, int n, uint8_t *dst, size_t dfb, Prof *pf)
+{
+    if (pf) pf->begin(st, KID_SCALE_SLOTS, (double)n * ((double)G.sbytes + (double)G.dfb));
+    for (int f0 = 0; f0 < n; f0 += 65535)                 // (gridDim.y; one launch for any call the decoders make)
+        hipLaunchKernelGGL(k_scale_slots, dim3(G.ntiles, std::min(65535, n - f0)), dim3(SC_THREADS), G.lds, st, G.planes_d, slab, tab_d + 2 * (size_t)f0,
+                           dst, (long long)sfb, (long long)dfb, G.th_tile, G.rows_cap, G.th_cap, G.tv_cap, G.span_cap);
+    if (pf) pf->end(st);
 }

@@ -690,6 +690,25 @@ typedef struct {
     uint8_t reserved;
 } dsv1_blockinfo;
 int  dsv1_decbatch_set_draw_info(dsv1_decbatch *d, int mode);
+
+/* ---- extension: decoder output scale (csrc/k_scale.hip, k_scale_slots; stated in numpy in tests/_resample.py) ----
+ * dsv1_decbatch_set_output_scale: the batched decoder hands out its pictures at out_w x out_h in the place of the streams' size --
+ * proxies, thumbnails, a fixed display size -- resampled inside its one output pass, so the full-size frames never leave the
+ * reconstruction slots.  The definition is dsv1_resample_clip's: every plane on its own, at the streams' subsampling (chroma planes
+ * of rshift_up(out_w) x rshift_up(out_h)), exact integers, filter DSV1_SCALE_TENT or DSV1_SCALE_CUBIC; any ratio with
+ * 1/8 <= source / output <= 8 on every axis of every plane, up or down, each axis on its own.
+ * Order of the pass: the debug overlay at the streams' resolution, then the scale at the streams' subsampling, then the output
+ * format's chroma halving or doubling, depth, packing or RGB matrix: a frame is export(resample(overlay(plain decode))).
+ * SCALE FIRST, FORMAT SECOND.  The call drops whatever output format is in force: output is packed planar frames of the scaled
+ * geometry again.  dsv1_decbatch_set_output_format, _format_up and _set_output_rgb called after it resolve for the scaled geometry
+ * (a dsv1_pix_format with explicit pitches has to fit it).  0, 0 switches the scale off, and drops the format as well.
+ * DSVG_ERR_ARG -- a ratio out of range, an unknown filter, a size that is not positive, d == NULL -- leaves scale and format in
+ * force as they were.  Between calls; from the next decode call on; the setting outlives a rebuilt context.  The reference pictures
+ * stay at full size.  dsv1_decbatch_out_frame_bytes follows (packed planar: the scaled frame); a smaller out_pitch is DSVG_ERR_ARG.
+ * dsv1_decbatch_out_dims: the luma size of the frames handed out under the setting in force (the streams' own with the scale off).
+ * Not offered: a scale in the frame-at-a-time dsv_dec (a DSV_FRAME has the stream's geometry), one size per stream. */
+int  dsv1_decbatch_set_output_scale(dsv1_decbatch *d, int out_w, int out_h, int filter);   /* 0, 0: off; filter: DSV1_SCALE_* */
+int  dsv1_decbatch_out_dims(const dsv1_decbatch *d, int *w, int *h);
 int  dsv1_packet_blockinfo(const uint8_t *data, size_t len, int w, int h, int *blk_w, int *blk_h, int *has_ref, dsv1_blockinfo *out, size_t n);
 int  dsv1_draw_info_clip(int device, void *clip, int w, int h, int subsamp, int n, int blk_w, int blk_h, const dsv1_blockinfo *info, int mode,
                          int on_device);

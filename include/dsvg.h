@@ -381,6 +381,17 @@ int dsvg_export_planar(int device, const void *src, int w, int h, int subsamp, i
  * dsvg_draw_info_planar: the overlay on n tightly packed planar frames in place, frame i from mvs / stable + i * nblocks (host tables;
  * stable: bit 0); blk 16 .. 64, mode 1 .. 7.  Synchronous. */
 int dsvg_ctx_draw_info(dsvg_ctx *ctx, int mode);
+/* Output scale of decoded pictures (csrc/k_scale.hip, k_scale_slots; include/dsv1_api.h, decoder output scale).  With a size set,
+ * dsvg_pack_recons / dsvg_export_recons hand out every picture resampled to out_w x out_h at the context's subsampling: each plane on
+ * its own with the tables of dsv1_resample_weights (filter: DSV1_SCALE_TENT / _CUBIC), read from the reconstruction -- or from the
+ * overlay's scratch frame where dsvg_ctx_draw_info drew -- with its indices clamped to the plane, never from the border.
+ * dsvg_pack_recons then writes packed planar frames of the scaled geometry (out_pitch at least such a frame) in its one pass;
+ * dsvg_export_recons takes a dsvg_pixout resolved for the scaled geometry, and its pass reads the scaled frames from a scratch of the
+ * context (allocated when first needed).  Stream placement, ordering and the second pass of a flagged decoder call as before.
+ * 0, 0 switches it off; off is the default and allocates, copies and launches nothing.  DSVG_ERR_ARG, the setting in force unchanged:
+ * a plane's axis outside 1/8 <= source / output <= 8, an unknown filter, a size that is not positive.  A pending decoder call is
+ * settled first.  dsvg_download_recon* and the references are not scaled. */
+int dsvg_ctx_output_scale(dsvg_ctx *ctx, int out_w, int out_h, int filter);
 int dsvg_draw_info_planar(int device, void *clip, int w, int h, int subsamp, int n, int blk_w, int blk_h, const dsvg_mv *mvs,
                           const unsigned char *stable, int mode, int on_device);
 
