@@ -152,6 +152,20 @@ class Denoise(_C.Structure):
         super().__init__(luma, chroma)
 
 
+class Reframe(_C.Structure):
+    """dsv1_reframe: the window (x, y, w, h) of in_w x in_h frames placed at (dst_x, dst_y) on a canvas of out_w x out_h, `fill`
+    (Y, U, V) elsewhere: crop, pad, letterbox and pillarbox in one.  include/dsv1_api.h, Reframe, has the definition."""
+    _fields_ = [("in_w", _C.c_int), ("in_h", _C.c_int), ("x", _C.c_int), ("y", _C.c_int), ("w", _C.c_int), ("h", _C.c_int),
+                ("out_w", _C.c_int), ("out_h", _C.c_int), ("dst_x", _C.c_int), ("dst_y", _C.c_int), ("fill", _C.c_uint8 * 3),
+                ("reserved", _C.c_uint8)]
+
+    def __init__(self, in_w, in_h, window=None, out=None, dst=(0, 0), fill=(16, 128, 128)):
+        """window: (x, y, w, h), None: the whole input; out: (out_w, out_h), None: the window's size"""
+        x, y, w, h = window if window is not None else (0, 0, in_w, in_h)
+        ow, oh = out if out is not None else (w, h)
+        super().__init__(in_w, in_h, x, y, w, h, ow, oh, dst[0], dst[1], (_C.c_uint8 * 3)(*fill), 0)
+
+
 class BlockInfo(_C.Structure):
     """dsv1_blockinfo: one block's side information (packet_blockinfo, draw_info_clip)"""
     _fields_ = [("mvx", _C.c_int16), ("mvy", _C.c_int16), ("mode", _C.c_uint8), ("submask", _C.c_uint8), ("stable", _C.c_uint8),
@@ -296,6 +310,16 @@ def lib():
         L.dsv1_batch_denoise_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsv1_resladder_set_denoise.argtypes = [_C.c_void_p, _C.POINTER(Denoise)]
         L.dsv1_resladder_denoise_reset.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_reframe_valid.argtypes = [_C.POINTER(Reframe), _C.c_int]
+        L.dsv1_reframe_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_void_p, _C.POINTER(Reframe), _C.c_int, _C.c_int]
+        L.dsv1_line_sums_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_int]
+        L.dsv1_bars_from_sums.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int)]
+        L.dsv1_detect_bars_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int,
+                                            _C.POINTER(_C.c_int), _C.c_int]
+        L.dsv1_batch_set_source_reframe.argtypes = [_C.c_void_p, _C.POINTER(Reframe)]
+        L.dsv1_resladder_open_reframed.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(Reframe), _C.POINTER(PixFormat),
+                                                   _C.c_int, _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int, _C.c_int, _C.c_int,
+                                                   _C.c_int, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         L.dsvg_inv_plan.argtypes = [_C.c_int] * 9 + [_C.c_uint, _C.c_int, _C.POINTER(InvStep), _C.c_int, _C.POINTER(_C.c_int)]
@@ -498,6 +522,20 @@ class Batch:
         """a discontinuity: the next picture of `source` (-1: every source) is filtered as a stream's first (dsv1_batch_denoise_reset)"""
         _chk(self.L.dsv1_batch_denoise_reset(self.h, source), "dsv1_batch_denoise_reset")
 
+    def set_source_reframe(self, rf):
+        """from the next submit on the clips are rf.in_w x rf.in_h and reframed on the GPU onto the batch's geometry as Reframe rf says,
+        as the LAST source pass (dsv1_batch_set_source_reframe); None, or the identity, switches it off.  Only with nothing in flight
+        and no source format, RGB format, deinterlacer or noise filter set: those are set AFTER it and resolve at the input geometry.
+        The input-length check follows."""
+        _chk(self.L.dsv1_batch_set_source_reframe(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_reframe")
+        self._in_dims = (rf.in_w, rf.in_h) if rf is not None else (self.width, self.height)
+        self.frame_bytes = self._in_dims[0] * self._in_dims[1] + 2 * _chroma_size(self._in_dims[0], self._in_dims[1], self.fmt)
+
+    @property
+    def in_dims(self):
+        """(width, height) of the frames that come in: the batch's geometry, or the input of the reframe set"""
+        return getattr(self, "_in_dims", (self.width, self.height))
+
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
 
@@ -512,16 +550,18 @@ class Batch:
         else:
             _chk(self.L.dsv1_batch_set_source_format_sub(self.h, _C.byref(pf) if pf is not None else None, src_subsamp),
                  "dsv1_batch_set_source_format_sub")
-        planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, src_subsamp)
-        self.frame_bytes = pix_frame_bytes(pf, self.width, self.height, src_subsamp) if pf is not None else planar
+        iw, ih = self.in_dims
+        planar = iw * ih + 2 * _chroma_size(iw, ih, src_subsamp)
+        self.frame_bytes = pix_frame_bytes(pf, iw, ih, src_subsamp) if pf is not None else planar
 
     def set_source_rgb(self, rf):
         """from the next submit on, encode() / submit() take RGB clips of RgbFormat rf (dsv1_batch_set_source_rgb), converted on the
         GPU to the batch's subsampling; None switches back to packed planar 8-bit.  Between batches only; replaces a source format
         set before.  The input-length check follows."""
         _chk(self.L.dsv1_batch_set_source_rgb(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_rgb")
-        planar = self.width * self.height + 2 * _chroma_size(self.width, self.height, self.fmt)
-        self.frame_bytes = rgb_frame_bytes(rf, self.width, self.height) if rf is not None else planar
+        iw, ih = self.in_dims
+        planar = iw * ih + 2 * _chroma_size(iw, ih, self.fmt)
+        self.frame_bytes = rgb_frame_bytes(rf, iw, ih) if rf is not None else planar
 
     def dropped_recons(self):
         """(dropped, remedied): reference pictures coded without a reconstruction because nobody predicts from them / coded again
@@ -855,6 +895,67 @@ def denoise_clip(clip, w, h, fmt, dn, state=None, device=0, n=None, out=None, st
     return res, new
 
 
+def reframe_clip(clip, rf, fmt, device=0, n=None, out=None):
+    """reframe packed planar 8-bit frames on the GPU (dsv1_reframe_clip) as Reframe rf says: clip numpy uint8 [frames][frame bytes of
+    rf.in_w x rf.in_h] (host), which returns numpy uint8 [frames][frame bytes of rf.out_w x rf.out_h]; or a device pointer with n
+    frames and `out` a device pointer for the result."""
+    L = lib()
+    if n is not None:
+        _chk(L.dsv1_reframe_clip(device, clip, n, out, _C.byref(rf), fmt, 1), "dsv1_reframe_clip")
+        return out
+    if not L.dsv1_reframe_valid(_C.byref(rf), fmt):
+        raise ValueError("not a valid reframe at subsampling 0x%x" % fmt)
+    a, frames = _host_clip(clip, rf.in_w * rf.in_h + 2 * _chroma_size(rf.in_w, rf.in_h, fmt))
+    res = _host_out(out, frames, rf.out_w * rf.out_h + 2 * _chroma_size(rf.out_w, rf.out_h, fmt))
+    _chk(L.dsv1_reframe_clip(device, a.ctypes.data, frames, res.ctypes.data, _C.byref(rf), fmt, 0), "dsv1_reframe_clip")
+    return res
+
+
+def line_sums_clip(clip, w, h, fmt, device=0, n=None):
+    """the sums of every luma row and column of a clip, on the GPU (dsv1_line_sums_clip): clip numpy uint8 [frames][frame_bytes]
+    (host), or a device pointer with n frames.  Returns (row_sum numpy uint32 [frames][h], col_sum numpy uint32 [frames][w])."""
+    L = lib()
+    if n is None:
+        a, frames = _host_clip(clip, w * h + 2 * _chroma_size(w, h, fmt))
+        src, dev = a.ctypes.data, 0
+    else:
+        src, frames, dev = clip, n, 1
+    rows = _np.zeros((max(frames, 0), h), dtype=_np.uint32)
+    cols = _np.zeros((max(frames, 0), w), dtype=_np.uint32)
+    _chk(L.dsv1_line_sums_clip(device, src, w, h, fmt, frames, rows.ctypes.data, cols.ctypes.data, dev), "dsv1_line_sums_clip")
+    return rows, cols
+
+
+def bars_from_sums(row_sum, col_sum, thresh=24, align=2):
+    """the content rectangle (x, y, w, h) of a clip from its line sums (dsv1_bars_from_sums; ffmpeg cropdetect's rule: a line is
+    content if its mean exceeds thresh in any frame; rounded inward to `align`), or None when nothing is content.  Host only."""
+    r = _np.ascontiguousarray(row_sum, dtype=_np.uint32)
+    c = _np.ascontiguousarray(col_sum, dtype=_np.uint32)
+    r, c = r.reshape(-1, r.shape[-1]), c.reshape(-1, c.shape[-1])
+    if r.shape[0] != c.shape[0]:
+        raise ValueError("row sums of %d frames, column sums of %d" % (r.shape[0], c.shape[0]))
+    rect = (_C.c_int * 4)()
+    rc = lib().dsv1_bars_from_sums(r.ctypes.data, c.ctypes.data, c.shape[1], r.shape[1], r.shape[0], thresh, align, rect)
+    if rc < 0:
+        raise ValueError("dsv1_bars_from_sums: thresh %d / align %d refused (rc=%d)" % (thresh, align, rc))
+    return tuple(rect) if rc else None
+
+
+def detect_bars_clip(clip, w, h, fmt, thresh=24, align=2, device=0, n=None):
+    """line sums on the GPU and the bars rule in one call (dsv1_detect_bars_clip): the content rectangle (x, y, w, h) or None"""
+    L = lib()
+    if n is None:
+        a, frames = _host_clip(clip, w * h + 2 * _chroma_size(w, h, fmt))
+        src, dev = a.ctypes.data, 0
+    else:
+        src, frames, dev = clip, n, 1
+    rect = (_C.c_int * 4)()
+    rc = L.dsv1_detect_bars_clip(device, src, w, h, fmt, frames, thresh, align, rect, dev)
+    if rc < 0:
+        _chk(rc, "dsv1_detect_bars_clip")
+    return tuple(rect) if rc else None
+
+
 def export_clip(clip, w, h, fmt, pf, out_subsamp=None, device=0, n=None, out=None, upsample=None):
     """packed planar 8-bit frames (w x h at subsampling fmt) to frames of PixFormat pf at subsampling out_subsamp (None: fmt) on the
     GPU (dsv1_export_clip), chroma halved on the way where out_subsamp asks for it: clip numpy uint8 [frames][frame_bytes] (host), or
@@ -1035,10 +1136,12 @@ class ResLadder:
     k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
 
     def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None, src_rgb=None,
-                 src_subsamp=None):
+                 src_subsamp=None, reframe=None):
         """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit); src_rgb: their RgbFormat
         instead (dsv1_resladder_open_rgb); src_subsamp: the subsampling of the source clips where it is not fmt
-        (dsv1_resladder_open_src_sub) -- 4:4:4 or 4:2:2, chroma halved to fmt by the converter"""
+        (dsv1_resladder_open_src_sub) -- 4:4:4 or 4:2:2, chroma halved to fmt by the converter; reframe: a Reframe of the w x h
+        sources (dsv1_resladder_open_reframed), the last pass in front of the scales: its canvas stands for the source from there on
+        (self.width x self.height, the rungs' ratio limits, src_psnr / src_ssim), the clips handed in stay w x h"""
         if src_format is not None and src_rgb is not None:
             raise ValueError("src_format and src_rgb exclude each other")
         if src_subsamp is not None and src_rgb is not None:
@@ -1053,7 +1156,14 @@ class ResLadder:
         rr = (ResRung * max(len(geoms), 1))(*[ResRung(gw, gh, len(r), a) for (gw, gh, r), a in zip(geoms, self._arrs)])
         meta = Meta()
         meta.width, meta.height, meta.subsamp = w, h, fmt
-        if src_rgb is not None:
+        if reframe is not None:
+            _chk(self.L.dsv1_resladder_open_reframed(_C.byref(self.h), _C.byref(meta), _C.byref(reframe),
+                                                     None if src_format is None else _C.byref(src_format),
+                                                     fmt if src_subsamp is None else src_subsamp,
+                                                     None if src_rgb is None else _C.byref(src_rgb), rr, len(geoms), device, nsources,
+                                                     frames_per_call, filt), "dsv1_resladder_open_reframed")
+            self.width, self.height = reframe.out_w, reframe.out_h
+        elif src_rgb is not None:
             _chk(self.L.dsv1_resladder_open_rgb(_C.byref(self.h), _C.byref(meta), _C.byref(src_rgb), rr, len(geoms), device, nsources,
                                                 frames_per_call, filt), "dsv1_resladder_open_rgb")
         elif src_subsamp is not None:

@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_denoise.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_denoise.hip, k_reframe.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -124,6 +124,19 @@ void dsvg_denoise_destroy(dsvg_denoise *d);
 int  dsvg_denoise_run(dsvg_denoise *d, void *stream, const void *src_dev, int n, void *dst_dev);
 int  dsvg_denoise_clip(dsvg_denoise *d, void *stream, const void *src_dev, int n, const void *state_in_dev, void *state_out_dev, void *dst_dev);
 int  dsvg_denoise_reset(dsvg_denoise *d, int source);
+
+/* ---- reframe and line sums (include/dsv1_api.h, Reframe; k_reframe.hip; host side: host/dsv1_reframe.c) ----
+ * A reframe of one (dsv1_reframe, subsampling): nframes frames of in_w x in_h -> nframes frames of out_w x out_h; it keeps no state
+ * and owns no device memory.  The line sums of one geometry: nframes frames -> row sums [nframes][h] and column sums [nframes][w] of
+ * the luma, uint32 in device memory (the column sums are zeroed on the stream first). */
+typedef struct dsvg_reframe dsvg_reframe;
+int  dsvg_reframe_create(dsvg_reframe **out, int device, const dsv1_reframe *rf, int subsamp);
+void dsvg_reframe_destroy(dsvg_reframe *r);
+int  dsvg_reframe_run(dsvg_reframe *r, void *stream, const void *src_dev, int nframes, void *dst_dev);
+typedef struct dsvg_linesums dsvg_linesums;
+int  dsvg_linesums_create(dsvg_linesums **out, int device, int w, int h, int subsamp);
+void dsvg_linesums_destroy(dsvg_linesums *s);
+int  dsvg_linesums_run(dsvg_linesums *s, void *stream, const void *src_dev, int nframes, void *row_dev, void *col_dev);
 
 #ifdef __cplusplus
 }

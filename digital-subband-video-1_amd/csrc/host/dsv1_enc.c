@@ -1220,7 +1220,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer or a noise filter is set"); return DSVG_ERR_ARG; }
+    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer, a noise filter or a reframe is set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1231,13 +1231,14 @@ static int set_source_format(dsv1_batch *b, const dsv1_pix_format *pf, int src_s
     dsv1_pix_layout L;
     const DSV_META *m = &b->enc[0].vidmeta;
     if (!pf && src_subsamp != m->subsamp) pf = &planar8;
-    if (pf && dsv1_pix_layout_of(pf, m->width, m->height, src_subsamp, m->subsamp, &L)) {
-        dsv1_log(1, "%s: not a valid pixel format for %dx%d, subsampling 0x%x into 0x%x", who, m->width, m->height, src_subsamp, m->subsamp);
+    /* (the frames that come in: the batch's geometry, or the input of the reframe set before) */
+    if (pf && dsv1_pix_layout_of(pf, b->src.w, b->src.h, src_subsamp, m->subsamp, &L)) {
+        dsv1_log(1, "%s: not a valid pixel format for %dx%d, subsampling 0x%x into 0x%x", who, b->src.w, b->src.h, src_subsamp, m->subsamp);
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "%s with batches in flight or clips staged", who); return DSVG_ERR_ARG; }
     /* nothing in flight: every batch that read one of the chain's clips has been collected */
-    return dsv1_srcchain_set_format(&b->src, src_subsamp == m->subsamp && dsv1_pix_is_default(pf, m->width, m->height, m->subsamp) ? NULL : &L, NULL);
+    return dsv1_srcchain_set_format(&b->src, src_subsamp == m->subsamp && dsv1_pix_is_default(pf, b->src.w, b->src.h, m->subsamp) ? NULL : &L, NULL);
 }
 
 int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
@@ -1260,8 +1261,8 @@ int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
     if (!b) return DSVG_ERR_ARG;
     if (!rf) return dsv1_batch_set_source_format(b, NULL);
     m = &b->enc[0].vidmeta;
-    if (dsv1_rgb_layout_of(rf, m->width, m->height, m->subsamp, &L)) {
-        dsv1_log(1, "dsv1_batch_set_source_rgb: not a valid RGB format for %dx%d, subsampling 0x%x", m->width, m->height, m->subsamp);
+    if (dsv1_rgb_layout_of(rf, b->src.w, b->src.h, m->subsamp, &L)) {
+        dsv1_log(1, "dsv1_batch_set_source_rgb: not a valid RGB format for %dx%d, subsampling 0x%x", b->src.w, b->src.h, m->subsamp);
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_rgb with batches in flight or clips staged"); return DSVG_ERR_ARG; }
@@ -1303,6 +1304,27 @@ int dsv1_batch_denoise_reset(dsv1_batch *b, int source)
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_denoise_reset with batches in flight"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_denoise_reset(&b->src, source);
 }
+
+/* the reframe: the last pass of the chain; it changes the geometry the other passes are built for, so only while none of them is set */
+int dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf)
+{
+    const DSV_META *m;
+    if (!b) return DSVG_ERR_ARG;
+    m = &b->enc[0].vidmeta;
+    if (rf && (!dsv1_reframe_valid(rf, m->subsamp) || rf->out_w != m->width || rf->out_h != m->height)) {
+        dsv1_log(1, "dsv1_batch_set_source_reframe: not a valid reframe onto %dx%d, subsampling 0x%x", m->width, m->height, m->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_reframe with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (b->src.pc || b->src.dd || b->src.dn) {
+        dsv1_log(1, "dsv1_batch_set_source_reframe with a source format, a deinterlacer or a noise filter set: clear them first, set them again after it");
+        return DSVG_ERR_ARG;
+    }
+    return dsv1_srcchain_set_reframe(&b->src, rf);
+}
+
+/* tests: 1 while the batch's source chain holds a lane (a stream and device memory of its own), 0 with no pass set */
+int dsv1_batch_has_source_lane(const dsv1_batch *b) { return b && b->src.lane != NULL; }
 
 /* a clip of the batch's source format -> the clip the chain's passes leave for the next submit's parity (device memory the chain owns,
  * read as a held clip until that batch's collect); the context's frame-load stream waits for the passes on the device */

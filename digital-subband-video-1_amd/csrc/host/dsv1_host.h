@@ -123,22 +123,27 @@ static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
     return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
 }
 
-/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, deinterlacer and noise filter with their
+/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, deinterlacer, noise filter and reframe with their
  * settings, and each pass's output clip per call parity (a batch of that parity reads the last one as a held clip until its collect).
  * A chain with no pass set holds no lane -- no stream, no device memory -- unless the session keeps it (keep_lane: a resolution
  * ladder uploads and scales on it).  The setters replace or (NULL) clear one pass; on an error the chain is as it was.  The session
- * checks that nothing is in flight, and its arguments, before it calls one. */
-enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_SCALE };
+ * checks that nothing is in flight, and its arguments, before it calls one.
+ * TWO GEOMETRIES.  w x h (fb) is what convert, deinterlace and denoise are built for: the frames that come in.  ow x oh (ofb) is the
+ * clip the chain hands on: the session's geometry.  They differ only while a reframe -- the LAST pass -- is set; it may be set, changed
+ * or cleared only while no other pass is set (the session checks), and the passes set after it resolve at w x h. */
+enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_REFRAME, DSV1_SRC_SCALE };
 typedef struct {
     int device, w, h, subsamp, nsrc, F, keep_lane;
-    size_t fb, raw_fb;                  /* the packed planar frame; the converter's source frame */
+    int ow, oh;                         /* the geometry handed on (the session's) */
+    size_t fb, raw_fb, ofb;             /* the packed planar frame that comes in; the converter's source frame; the frame handed on */
     dsvg_lane *lane;
     dsvg_pixconv *pc;
     dsvg_deint *dd;
     dsv1_deint dd_set;
     dsvg_denoise *dn;
     dsv1_denoise dn_set;
-    void *clip[3][2];
+    dsvg_reframe *rf;
+    void *clip[4][2];
 } dsv1_srcchain;
 void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp, int nsrc, int F, int keep_lane);
 void dsv1_srcchain_close(dsv1_srcchain *c);            /* waits for the lane; frees everything */
@@ -146,19 +151,24 @@ int  dsv1_srcchain_lane(dsv1_srcchain *c);             /* creates the lane where
 int  dsv1_srcchain_set_format(dsv1_srcchain *c, const dsv1_pix_layout *L, const dsv1_rgb_layout *R);      /* one of them, or neither: no converter */
 int  dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di);         /* (resets the noise filter's state) */
 int  dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn);
+/* a valid reframe whose canvas is ow x oh, or NULL / the identity: none.  DSVG_ERR_ARG, chain as it was, while another pass is set */
+int  dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf);
+int  dsv1_reframe_is_identity(const dsv1_reframe *rf);  /* dsv1_reframe.c: window = input = canvas at 0, 0 */
 int  dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source);                 /* DSVG_ERR_ARG where the pass is not set */
 int  dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source);
-static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->dd || c->dn; }
+static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->dd || c->dn || c->rf; }
 int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, or F / 2 at field rate */
 size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c); /* ... and the bytes of a call's clip */
-/* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> deinterlace -> denoise are
- * set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where nothing ran) */
+/* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> deinterlace -> denoise ->
+ * reframe are set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where nothing ran) */
 int  dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out);
 /* the standalone clip calls: one pass (DSV1_SRC_*; SCALE: a scaler's geometry 0) over n frames on a lane of the call's own.  in[0] the
  * clip, in[1] an optional second input (the deinterlacer's prev, the filter's state_in); out[0] the result, out[1] the filter's
  * state_out.  Host memory is uploaded / allocated / downloaded, device memory used in place; the call waits for the pass. */
 typedef struct { const void *in[2]; size_t in_bytes[2]; void *out[2]; size_t out_bytes[2]; } dsv1_clip_io;
 int  dsv1_pass_clip(int device, int kind, void *pass, int n, const dsv1_clip_io *io, int on_device);
+/* dsv1_enc.c: whether the batch's source chain holds a lane right now (tests: a chain with no pass set holds none) */
+int dsv1_batch_has_source_lane(const dsv1_batch *b);
 /* dsv1_enc.c: source-resolution figures of a batch (dsvg_ctx_xres_enable; resolution ladders): stream k = s * R + r, frame t of a
  * call is measured against frame s * frames_per_call + t of the reference clip named for the next submit (device memory, kept until
  * that batch's collect); the figures of the batch collected last, [(k * F + t) * 3 + p].  Enable only between batches. */

@@ -168,13 +168,14 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
     return dsv1_resladder_open_src(out, src, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
-static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp, const dsv1_rgb_format *rf,
-                              const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter);
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_reframe *frm, const dsv1_pix_format *pf, int src_subsamp,
+                              const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call,
+                              int filter);
 
 int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs, int ngeoms,
                             int device, int nsources, int frames_per_call, int filter)
 {
-    return resladder_open_fmt(out, src, pf, src ? src->subsamp : 0, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, NULL, pf, src ? src->subsamp : 0, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* sources at src_subsamp: the converter halves their chroma to src->subsamp on the way */
@@ -183,7 +184,7 @@ int dsv1_resladder_open_src_sub(dsv1_resladder **out, const DSV_META *src, const
 {
     static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
     if (!pf && src && src_subsamp != src->subsamp) pf = &planar8;
-    return resladder_open_fmt(out, src, pf, src_subsamp, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, NULL, pf, src_subsamp, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* RGB sources: the RGB import pass (k_rgb.hip) in the converter's place, everything else as dsv1_resladder_open_src */
@@ -192,12 +193,33 @@ int dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const dsv
 {
     if (out) *out = NULL;
     if (!rf) return DSVG_ERR_ARG;
-    return resladder_open_fmt(out, src, NULL, src ? src->subsamp : 0, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, NULL, NULL, src ? src->subsamp : 0, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
-static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp, const dsv1_rgb_format *rf,
-                              const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter)
+/* sources of geometry *src = the reframe's input, reframed behind the other passes: the CANVAS stands for the source from the scales on */
+int dsv1_resladder_open_reframed(dsv1_resladder **out, const DSV_META *src, const dsv1_reframe *rf, const dsv1_pix_format *pf, int src_subsamp,
+                                 const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call,
+                                 int filter)
 {
+    static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
+    if (out) *out = NULL;
+    if (!src || (pf && rgb)) return DSVG_ERR_ARG;
+    if (rf && (!dsv1_reframe_valid(rf, src->subsamp) || rf->in_w != src->width || rf->in_h != src->height)) {
+        dsv1_log(1, "dsv1_resladder_open_reframed: not a valid reframe of %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (rgb) src_subsamp = src->subsamp;
+    else if (!pf && src_subsamp != src->subsamp) pf = &planar8;
+    return resladder_open_fmt(out, src, rf, pf, src_subsamp, rgb, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_reframe *frm, const dsv1_pix_format *pf, int src_subsamp,
+                              const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call,
+                              int filter)
+{
+    /* cw x ch: what stands for the source behind the chain -- the reframe's canvas, or the source itself; the passes in front of the
+     * reframe and the caller's clips are src->width x src->height */
+    const int cw = frm && src ? frm->out_w : src ? src->width : 0, ch = frm && src ? frm->out_h : src ? src->height : 0;
     dsv1_resladder *r;
     dsv1_pix_layout pl;
     dsv1_rgb_layout rl;
@@ -223,9 +245,9 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
             dsv1_log(1, "dsv1_resladder_open: geometry %d needs 1 to %d rate rungs", g, DSV1_MAX_RUNGS);
             return DSVG_ERR_ARG;
         }
-        if (scale_dims_ok(src->width, src->height, src->subsamp, G->width, G->height, filter)) {
+        if (scale_dims_ok(cw, ch, src->subsamp, G->width, G->height, filter)) {
             dsv1_log(1, "dsv1_resladder_open: geometry %d (%dx%d) is not a downscale of %dx%d by at most 8 on every axis and plane", g, G->width,
-                     G->height, src->width, src->height);
+                     G->height, cw, ch);
             return DSVG_ERR_ARG;
         }
         for (k = 0; k < G->nrates; k++) {
@@ -251,8 +273,8 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     r = (dsv1_resladder *)calloc(1, sizeof(*r));
     if (!r) return DSVG_ERR_NOMEM;
     r->ngeom = ngeoms; r->nsrc = nsources; r->F = frames_per_call; r->ntot = ntot;
-    r->sw = src->width; r->sh = src->height;
-    dsv1_srcchain_init(&r->src, device, src->width, src->height, src->subsamp, nsources, frames_per_call, 1);
+    r->sw = cw; r->sh = ch;
+    dsv1_srcchain_init(&r->src, device, cw, ch, src->subsamp, nsources, frames_per_call, 1);
     r->tmp = (DSV_BUF *)calloc((size_t)nsources * maxr, sizeof(DSV_BUF));
     r->q[DSVG_Q_SSE].v = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
     r->q[DSVG_Q_SSIM].v = (uint64_t *)calloc((size_t)3 * nsources * ntot * frames_per_call, sizeof(uint64_t));
@@ -261,13 +283,13 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
         r->w[g] = rungs[g].width; r->h[g] = rungs[g].height; r->nr[g] = rungs[g].nrates;
         r->off[g + 1] = r->off[g] + rungs[g].nrates;
         r->gfb[g] = dsv1_frame_bytes(r->w[g], r->h[g], src->subsamp);
-        r->same[g] = r->w[g] == src->width && r->h[g] == src->height;
+        r->same[g] = r->w[g] == cw && r->h[g] == ch;
         r->scale_idx[g] = -1;
         if (!r->same[g]) { r->scale_idx[g] = nscaled; dw[nscaled] = r->w[g]; dh[nscaled] = r->h[g]; nscaled++; }
     }
     /* the lane exists even when no geometry is scaled: host input is uploaded through it */
-    if ((rc = dsvg_scaler_create(&r->sc, device, src->width, src->height, src->subsamp, nscaled, dw, dh, filter)) ||
-        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_set_format(&r->src, pf ? &pl : NULL, rf ? &rl : NULL))) { dsv1_resladder_close(r); return rc; }
+    if ((rc = dsvg_scaler_create(&r->sc, device, cw, ch, src->subsamp, nscaled, dw, dh, filter)) ||
+        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_set_reframe(&r->src, frm)) || (rc = dsv1_srcchain_set_format(&r->src, pf ? &pl : NULL, rf ? &rl : NULL))) { dsv1_resladder_close(r); return rc; }
     for (g = 0; g < ngeoms; g++) {
         if ((rc = dsv1_ladder_open(&r->lad[g], rungs[g].rates, rungs[g].nrates, device, nsources, frames_per_call))) break;
         r->ngeom = g + 1;

@@ -1,4 +1,4 @@
-/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace -> denoise on one lane (dsvg_pixfmt.h), for
+/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace -> denoise -> reframe on one lane (dsvg_pixfmt.h), for
  * batches (dsv1_enc.c) and resolution ladders (dsv1_scale.c), and the sequence the standalone clip calls share. */
 #include "dsv1_host.h"
 
@@ -6,7 +6,8 @@ void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp,
 {
     memset(c, 0, sizeof(*c));
     c->device = device; c->w = w; c->h = h; c->subsamp = subsamp; c->nsrc = nsrc; c->F = F; c->keep_lane = keep_lane;
-    c->fb = dsv1_frame_bytes(w, h, subsamp);
+    c->ow = w; c->oh = h;
+    c->fb = c->ofb = dsv1_frame_bytes(w, h, subsamp);
 }
 
 int dsv1_srcchain_lane(dsv1_srcchain *c) { return c->lane ? DSVG_OK : dsvg_lane_create(&c->lane, c->device); }
@@ -25,6 +26,7 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
     dsvg_pixconv_destroy(c->pc);
     dsvg_deint_destroy(c->dd);
     dsvg_denoise_destroy(c->dn);
+    dsvg_reframe_destroy(c->rf);
     dsvg_lane_destroy(c->lane);                         /* (and the clips) */
     memset(c, 0, sizeof(*c));
 }
@@ -33,11 +35,12 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
  * On an error the chain is as it was and p is still the caller's. */
 static int chain_install(dsv1_srcchain *c, int k, void *p)
 {
+    const size_t fb = k == DSV1_SRC_REFRAME ? c->ofb : c->fb;
     void *clip[2] = {NULL, NULL};
     int rc, j;
     if (!p && !c->clip[k][0]) return DSVG_OK;
     rc = dsv1_srcchain_lane(c);
-    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], c->fb * (size_t)c->nsrc * (size_t)c->F);
+    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], fb * (size_t)c->nsrc * (size_t)c->F);
     if (!rc) rc = dsvg_lane_sync(c->lane);
     if (rc) {
         if (c->lane) for (j = 0; j < 2; j++) (void)dsvg_lane_free(c->lane, clip[j]);
@@ -47,6 +50,7 @@ static int chain_install(dsv1_srcchain *c, int k, void *p)
     switch (k) {
     case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; break;
     case DSV1_SRC_DEINTERLACE: dsvg_deint_destroy(c->dd); c->dd = (dsvg_deint *)p; break;
+    case DSV1_SRC_REFRAME:     dsvg_reframe_destroy(c->rf); c->rf = (dsvg_reframe *)p; break;
     default:                   dsvg_denoise_destroy(c->dn); c->dn = (dsvg_denoise *)p; break;
     }
     for (j = 0; j < 2; j++) {
@@ -90,6 +94,22 @@ int dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn)
     return DSVG_OK;
 }
 
+/* the frames that come in take the reframe's input geometry (the session's own again without one): only while no other pass is set,
+ * whose clips and state are sized for the geometry in force */
+int dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf)
+{
+    dsvg_reframe *r = NULL;
+    int rc;
+    if (c->pc || c->dd || c->dn) return DSVG_ERR_ARG;
+    if (rf && (rf->out_w != c->ow || rf->out_h != c->oh)) return DSVG_ERR_ARG;
+    if (rf && dsv1_reframe_is_identity(rf)) rf = NULL;
+    if (rf && (rc = dsvg_reframe_create(&r, c->device, rf, c->subsamp))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_REFRAME, r))) { dsvg_reframe_destroy(r); return rc; }
+    c->w = rf ? rf->in_w : c->ow; c->h = rf ? rf->in_h : c->oh;
+    c->fb = dsv1_frame_bytes(c->w, c->h, c->subsamp);
+    return DSVG_OK;
+}
+
 int dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source) { return c->dd ? dsvg_deint_reset(c->dd, source) : DSVG_ERR_ARG; }
 int dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source) { return c->dn ? dsvg_denoise_reset(c->dn, source) : DSVG_ERR_ARG; }
 
@@ -121,6 +141,10 @@ int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device
         if ((rc = dsvg_denoise_run(c->dn, st, clip, c->F, c->clip[DSV1_SRC_DENOISE][par]))) return rc;
         clip = c->clip[DSV1_SRC_DENOISE][par];
     }
+    if (c->rf) {
+        if ((rc = dsvg_reframe_run(c->rf, st, clip, c->nsrc * c->F, c->clip[DSV1_SRC_REFRAME][par]))) return rc;
+        clip = c->clip[DSV1_SRC_REFRAME][par];
+    }
     *out = clip;
     return DSVG_OK;
 }
@@ -142,6 +166,7 @@ int dsv1_pass_clip(int device, int kind, void *pass, int n, const dsv1_clip_io *
         case DSV1_SRC_CONVERT:     rc = dsvg_pixconv_run((dsvg_pixconv *)pass, st, din[0], n, dout[0]); break;
         case DSV1_SRC_DEINTERLACE: rc = dsvg_deint_clip((dsvg_deint *)pass, st, din[0], n, din[1], dout[0]); break;
         case DSV1_SRC_DENOISE:     rc = dsvg_denoise_clip((dsvg_denoise *)pass, st, din[0], n, din[1], dout[1], dout[0]); break;
+        case DSV1_SRC_REFRAME:     rc = dsvg_reframe_run((dsvg_reframe *)pass, st, din[0], n, dout[0]); break;
         default:                   rc = dsvg_scaler_run((dsvg_scaler *)pass, st, 0, din[0], n, dout[0]); break;
         }
     for (k = 0; !on_device && k < 2 && !rc; k++)

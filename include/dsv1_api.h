@@ -654,6 +654,66 @@ int  dsv1_batch_denoise_reset(dsv1_batch *b, int source);                       
 int  dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn);
 int  dsv1_resladder_denoise_reset(dsv1_resladder *r, int source);
 
+/* ---- extension: reframe -- crop, pad, letterbox, pillarbox -- and bar detection (csrc/k_reframe.hip; stated in numpy in
+ * tests/_reframe.py) ----
+ * The picture's frame: film sources with black bars, decoder surfaces with junk rows (1920x1088), a 4:3 or 2.39:1 source inside a 16:9
+ * ladder, captures with dirty edge columns.  A dsv1_pix_format cannot express a window (its planes lie back to back at pitch x rows),
+ * so this is a pass of its own: a window of the incoming picture placed on a canvas of the coded size, a fill colour elsewhere.
+ * Input and output are the tightly packed planar 8-bit frames every other entry point reads, n in and n out.
+ * INDEXING.  Every plane p on its own, with its shifts (hs_p, vs_p): 0 for luma, the subsampling's for chroma.  X0 = x >> hs_p,
+ * W = rshift_up(w, hs_p), DX = dst_x >> hs_p; Y0, H, DY likewise with vs_p.  out_p[Y][X] = in_p[Y - DY + Y0][X - DX + X0] where
+ * DX <= X < DX + W and DY <= Y < DY + H, and fill[p] elsewhere.
+ * VALID (dsv1_reframe_valid, host only, 1 / 0): every size >= 1; 0 <= x, x + w <= in_w, 0 <= y, y + h <= in_h; 0 <= dst_x, dst_x + w <=
+ * out_w, 0 <= dst_y, dst_y + h <= out_h; x and dst_x multiples of 1 << hs, y and dst_y of 1 << vs (w and h need not be); reserved == 0;
+ * the subsampling one the library knows (4:4:4, 4:2:2, 4:2:0, 4:1:1).  The chroma window then lies inside both chroma planes: with
+ * x = X0 << hs, X0 + W = X0 + ceil(w / 2^hs) = ceil((x + w) / 2^hs) <= ceil(in_w / 2^hs), the input chroma plane's width, and with
+ * dst_x = DX << hs in the same way DX + W <= ceil(out_w / 2^hs); rows likewise.  Anything else is DSVG_ERR_ARG before any device work.
+ * LINE SUMS, on luma only: row_sum[t][r] the sum of row r of frame t, col_sum[t][c] the sum of column c; uint32_t, exact for every size
+ * the library takes.  dsv1_line_sums_clip: src host or device memory (on_device), the sums always to host memory; synchronous.
+ * BARS (dsv1_bars_from_sums, host only): ffmpeg cropdetect's rule -- a line's mean against a limit, the union taken over the frames.
+ * Row r is content if in any frame row_sum[t][r] > (uint64_t)thresh * w, a column likewise with h.  x0, x1 the first and last content
+ * columns, y0, y1 the first and last content rows; the rectangle is rounded INWARD to align: x = roundup(x0, align), w =
+ * rounddown(x1 + 1, align) - x, y and h likewise.  Returns 1 with rect = {x, y, w, h} when both sizes are positive; 0 with rect all zero
+ * when nothing is content or the rounding leaves nothing; DSVG_ERR_ARG for thresh outside 0 .. 254 or align not a power of two in
+ * 1 .. 64.  Known consequence of the rule: a column's mean includes the rows of horizontal bars (and a row's the columns of vertical
+ * ones), so a letterboxed picture needs more light in a column to count than the limit says.  dsv1_detect_bars_clip does both steps.
+ * SESSIONS.  The reframe is the LAST pass of the source chain: convert -> deinterlace -> denoise -> reframe, then the scales of a
+ * resolution ladder or the frame load.  The passes in front of it run at in_w x in_h; denoising rows that are then cut away is accepted
+ * waste.  dsv1_batch_set_source_reframe (plain batches, quality ladders, chain mode): out_w x out_h must be the batch's geometry.  It
+ * changes the geometry the other passes are built for, so it may be set, changed or cleared only with nothing in flight, nothing
+ * staged, and no source format, RGB format, deinterlacer or noise filter set -- else DSVG_ERR_ARG with the setting left as it was (an
+ * invalid struct too).  Formats and passes set AFTER it resolve at in_w x in_h; clips are then in_w x in_h.  NULL clears it, and so does
+ * the identity (window = input = canvas at 0, 0): no pass, no copy, no lane.  Clip ownership is dsv1_batch_set_source_format's;
+ * dsv1_batch_stage is refused while it is set.
+ * dsv1_resladder_open_reframed: src is the geometry handed in and must equal rf->in_w x in_h; at most one of pf (at src_subsamp) / rgb;
+ * rf == NULL behaves as the existing opens.  The CANVAS takes the source's place everywhere behind the chain: the scaler's source
+ * geometry, the 1 .. 8 ratio check of the rungs (a rung larger than the canvas is refused although it is smaller than the input), a
+ * geometry "of the source's size", the clip get_src_sse / get_src_ssim measure against.  dsv1_resladder_set_deinterlace / _set_denoise
+ * act in front of the reframe.
+ * Not offered: the drop-in dsv_enc; one window per source; windows that move from call to call (pan and scan); bar detection inside a
+ * session (the coded size depends on it, so it runs before open); a crop in the decoders' output pass; fusing the window into the
+ * frame load. */
+typedef struct {
+    int in_w, in_h;     /* the frames that come in (after conversion / deinterlacing / noise filter) */
+    int x, y, w, h;     /* the window of them that is kept */
+    int out_w, out_h;   /* the canvas: the frames that go on */
+    int dst_x, dst_y;   /* where the window's top left lands on the canvas */
+    uint8_t fill[3];    /* Y, U, V of every canvas sample outside the window */
+    uint8_t reserved;   /* 0 */
+} dsv1_reframe;
+int  dsv1_reframe_valid(const dsv1_reframe *rf, int subsamp);
+int  dsv1_reframe_clip(int device, const void *src, int n, void *dst, const dsv1_reframe *rf, int subsamp, int on_device);
+int  dsv1_line_sums_clip(int device, const void *src, int w, int h, int subsamp, int n, uint32_t *row_sum /* [n][h] */,
+                         uint32_t *col_sum /* [n][w] */, int on_device);
+int  dsv1_bars_from_sums(const uint32_t *row_sum, const uint32_t *col_sum, int w, int h, int n, int thresh, int align,
+                         int rect[4] /* x, y, w, h */);
+int  dsv1_detect_bars_clip(int device, const void *src, int w, int h, int subsamp, int n, int thresh, int align, int rect[4],
+                           int on_device);
+int  dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf);            /* NULL or the identity = off */
+int  dsv1_resladder_open_reframed(dsv1_resladder **out, const DSV_META *src, const dsv1_reframe *rf, const dsv1_pix_format *pf,
+                                  int src_subsamp, const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device,
+                                  int nsources, int frames_per_call, int filter);
+
 /* ---- extension: debug overlays (csrc/k_drawinfo.hip; stated in Python in tests/_drawinfo.py) ----
  * The reference decoder's -drawinfo (draw_info dsv_decoder.c:147-243), drawn on the device ahead of the output pass: what an encoder
  * decided, on the decoded luma of every picture that has a reference (P pictures; I pictures and chroma are untouched, and so are the
