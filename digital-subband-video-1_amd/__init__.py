@@ -143,6 +143,19 @@ class Deint(_C.Structure):
         super().__init__(mode, tff)
 
 
+IVTC_C, IVTC_P = 0, 1                    # DSV1_IVTC_*: a frame's match
+
+
+class Ivtc(_C.Structure):
+    """dsv1_ivtc: inverse telecine of 3:2 pulled-down film -- the field order of the source (tff = 1: the top field is the earlier
+    one) and the comb measure's noise threshold nt (0 .. 254).  5n frames in, the 4n film frames out.  include/dsv1_api.h, Inverse
+    telecine, has the definition."""
+    _fields_ = [("tff", _C.c_int), ("nt", _C.c_int), ("reserved", _C.c_int * 2)]
+
+    def __init__(self, tff=1, nt=0):
+        super().__init__(tff, nt, (_C.c_int * 2)(0, 0))
+
+
 class Denoise(_C.Structure):
     """dsv1_denoise: the temporal noise filter's strengths, luma for plane 0 and chroma for planes 1 and 2, each 0 .. 512 and not both
     0; a plane with strength 0 is copied.  include/dsv1_api.h, Temporal noise reduction, has the definition."""
@@ -302,6 +315,19 @@ def lib():
         L.dsv1_batch_deinterlace_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsv1_resladder_set_deinterlace.argtypes = [_C.c_void_p, _C.POINTER(Deint)]
         L.dsv1_resladder_deinterlace_reset.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_ivtc_out_frames.argtypes = [_C.POINTER(Ivtc), _C.c_int]
+        L.dsv1_ivtc_state_bytes.argtypes = [_C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_ivtc_state_bytes.restype = _C.c_size_t
+        L.dsv1_field_metrics_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int, _C.c_void_p,
+                                              _C.c_int]
+        L.dsv1_field_order_from_metrics.argtypes = [_C.c_void_p, _C.c_int, _C.c_int]
+        L.dsv1_detect_field_order_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_ivtc_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_void_p,
+                                     _C.POINTER(Ivtc), _C.c_void_p, _C.c_void_p, _C.c_int]
+        L.dsv1_batch_set_source_ivtc.argtypes = [_C.c_void_p, _C.POINTER(Ivtc)]
+        L.dsv1_batch_ivtc_reset.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_set_ivtc.argtypes = [_C.c_void_p, _C.POINTER(Ivtc)]
+        L.dsv1_resladder_ivtc_reset.argtypes = [_C.c_void_p, _C.c_int]
         L.dsv1_denoise_state_bytes.argtypes = [_C.c_int, _C.c_int, _C.c_int]
         L.dsv1_denoise_state_bytes.restype = _C.c_size_t
         L.dsv1_denoise_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p, _C.c_void_p,
@@ -498,8 +524,23 @@ class Batch:
 
     @property
     def in_frames(self):
-        """input frames per source and call: frames_per_call, or half of it behind a field-rate deinterlacer"""
+        """input frames per source and call: frames_per_call, half of it behind a field-rate deinterlacer, 5/4 of it in front of the
+        inverse telecine"""
+        if getattr(self, "_ivtc", False):
+            return self.F // 4 * 5
         return self.F // 2 if getattr(self, "_deint_field", False) else self.F
+
+    def set_source_ivtc(self, iv):
+        """from the next submit on the clips are 3:2 pulled-down film and inverse telecined on the GPU as Ivtc iv says, behind the source
+        format's conversion, in the deinterlacer's place and exclusive with it (dsv1_batch_set_source_ivtc); None switches it off.
+        Between batches only; forgets every source's state.  frames_per_call counts coded pictures and must be a multiple of 4: a call
+        takes in_frames = 5 * frames_per_call / 4 frames per source."""
+        _chk(self.L.dsv1_batch_set_source_ivtc(self.h, _C.byref(iv) if iv is not None else None), "dsv1_batch_set_source_ivtc")
+        self._ivtc = iv is not None
+
+    def ivtc_reset(self, source=-1):
+        """a discontinuity: the next frame of `source` (-1: every source) is a stream's first picture (dsv1_batch_ivtc_reset)"""
+        _chk(self.L.dsv1_batch_ivtc_reset(self.h, source), "dsv1_batch_ivtc_reset")
 
     def set_source_deinterlace(self, di):
         """from the next submit on the clips are interlaced and deinterlaced on the GPU as Deint di says, behind the source format's
@@ -872,6 +913,86 @@ def deinterlace_clip(clip, w, h, fmt, di, prev=None, device=0, n=None, out=None)
     return res
 
 
+def ivtc_out_frames(iv, n):
+    """4n / 5, the pictures n telecined frames leave (dsv1_ivtc_out_frames); ValueError unless iv is valid and n a multiple of 5"""
+    r = lib().dsv1_ivtc_out_frames(_C.byref(iv), n)
+    if r < 0:
+        raise ValueError("not an inverse telecine call: tff %d, nt %d, %d frames" % (iv.tff, iv.nt, n))
+    return r
+
+
+def ivtc_clip(clip, w, h, fmt, iv, state=None, device=0, n=None, out=None, state_out=None):
+    """inverse telecine of packed planar 8-bit frames of one stream on the GPU (dsv1_ivtc_clip) as Ivtc iv says: clip numpy uint8
+    [5k frames][frame_bytes] and state what the call before returned or None (host), which returns (pictures numpy uint8
+    [4k][frame_bytes], match uint8 [5k], drop uint8 [k], state uint8 [frame_bytes + w * h]); or device pointers with n frames, `out` a
+    device pointer for the result and state / state_out device pointers or None, which returns (out, match, drop)."""
+    L = lib()
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    sb = fb + w * h
+    frames = n if n is not None else _host_clip(clip, fb)[1]
+    nout = ivtc_out_frames(iv, frames)
+    match = _np.zeros(frames, dtype=_np.uint8)
+    drop = _np.zeros(frames // 5, dtype=_np.uint8)
+    if n is not None:
+        _chk(L.dsv1_ivtc_clip(device, clip, w, h, fmt, n, state, state_out, out, _C.byref(iv), match.ctypes.data, drop.ctypes.data, 1), "dsv1_ivtc_clip")
+        return out, match, drop
+    a, frames = _host_clip(clip, fb)
+    p = None
+    if state is not None:
+        p = _np.ascontiguousarray(state, dtype=_np.uint8).reshape(-1)
+        if p.size != sb:
+            raise ValueError("a state is %d bytes, got %d" % (sb, p.size))
+    res = _np.zeros((nout, fb), dtype=_np.uint8)
+    new = _np.zeros(sb, dtype=_np.uint8)
+    _chk(L.dsv1_ivtc_clip(device, a.ctypes.data, w, h, fmt, frames, p.ctypes.data if p is not None else None, new.ctypes.data, res.ctypes.data,
+                          _C.byref(iv), match.ctypes.data, drop.ctypes.data, 0), "dsv1_ivtc_clip")
+    return res, match, drop, new
+
+
+def field_metrics_clip(clip, w, h, fmt, prev=None, nt=0, device=0, n=None):
+    """the four comb sums mc0 mc1 mp0 mp1 of every frame's luma, on the GPU (dsv1_field_metrics_clip): clip numpy uint8
+    [frames][frame_bytes] and prev one frame or None (host), or device pointers with n frames.  Returns numpy uint32 [frames][4]."""
+    L = lib()
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is None:
+        a, frames = _host_clip(clip, fb)
+        src, dev = a.ctypes.data, 0
+        if prev is not None:
+            pa = _np.ascontiguousarray(prev, dtype=_np.uint8).reshape(-1)
+            if pa.size != fb:
+                raise ValueError("prev is one frame of %d bytes, got %d" % (fb, pa.size))
+            prev = pa.ctypes.data
+    else:
+        src, frames, dev = clip, n, 1
+    met = _np.zeros((max(frames, 0), 4), dtype=_np.uint32)
+    _chk(L.dsv1_field_metrics_clip(device, src, w, h, fmt, frames, prev, nt, met.ctypes.data, dev), "dsv1_field_metrics_clip")
+    return met
+
+
+def field_order_from_metrics(metrics, first_has_prev=False):
+    """the field order a clip's metrics vote for (dsv1_field_order_from_metrics): 1 top field first, 0 bottom field first, -1
+    undetermined (static or progressive material, or texture too fine for the motion).  Host only."""
+    m = _np.ascontiguousarray(metrics, dtype=_np.uint32).reshape(-1, 4)
+    r = lib().dsv1_field_order_from_metrics(m.ctypes.data, m.shape[0], 1 if first_has_prev else 0)
+    if r < -1:
+        raise ValueError("dsv1_field_order_from_metrics refused %d frames (rc=%d)" % (m.shape[0], r))
+    return r
+
+
+def detect_field_order_clip(clip, w, h, fmt, nt=0, device=0, n=None):
+    """field metrics on the GPU and the vote in one call (dsv1_detect_field_order_clip): 1 / 0 / -1"""
+    L = lib()
+    if n is None:
+        a, frames = _host_clip(clip, w * h + 2 * _chroma_size(w, h, fmt))
+        src, dev = a.ctypes.data, 0
+    else:
+        src, frames, dev = clip, n, 1
+    r = L.dsv1_detect_field_order_clip(device, src, w, h, fmt, frames, nt, dev)
+    if r < -1:
+        _chk(r, "dsv1_detect_field_order_clip")
+    return r
+
+
 def denoise_clip(clip, w, h, fmt, dn, state=None, device=0, n=None, out=None, state_out=None):
     """temporal noise reduction of packed planar 8-bit pictures of one stream on the GPU (dsv1_denoise_clip) as Denoise dn says: clip
     numpy uint8 [pictures][frame_bytes] and state what the call before returned or None (host), which returns (numpy uint8
@@ -1220,6 +1341,16 @@ class ResLadder:
     def deinterlace_reset(self, source=-1):
         """a discontinuity in `source` (-1: every source): dsv1_resladder_deinterlace_reset"""
         _chk(self.L.dsv1_resladder_deinterlace_reset(self.h, source), "dsv1_resladder_deinterlace_reset")
+
+    def set_ivtc(self, iv):
+        """the sources are 3:2 pulled-down film: inverse telecine them on the GPU as Ivtc iv says, behind the conversion and in front of
+        the scales (dsv1_resladder_set_ivtc); None switches it off.  Between calls only; contract as Batch.set_source_ivtc."""
+        _chk(self.L.dsv1_resladder_set_ivtc(self.h, _C.byref(iv) if iv is not None else None), "dsv1_resladder_set_ivtc")
+        self._ivtc = iv is not None
+
+    def ivtc_reset(self, source=-1):
+        """a discontinuity in `source` (-1: every source): dsv1_resladder_ivtc_reset"""
+        _chk(self.L.dsv1_resladder_ivtc_reset(self.h, source), "dsv1_resladder_ivtc_reset")
 
     def set_denoise(self, dn):
         """the sources pass the temporal noise filter on the GPU as Denoise dn says, behind the conversion and the deinterlacer and in

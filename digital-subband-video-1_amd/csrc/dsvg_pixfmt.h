@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_denoise.hip, k_reframe.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -111,6 +111,25 @@ void dsvg_deint_destroy(dsvg_deint *d);
 int  dsvg_deint_run(dsvg_deint *d, void *stream, const void *src_dev, int nin, void *dst_dev);
 int  dsvg_deint_clip(dsvg_deint *d, void *stream, const void *src_dev, int n, const void *prev_dev, void *dst_dev);
 int  dsvg_deint_reset(dsvg_deint *d, int source);
+
+/* ---- inverse telecine and field metrics (include/dsv1_api.h, Inverse telecine; k_ivtc.hip; host side: host/dsv1_ivtc.c; the two
+ * decision rules: dsvg_ivtc_rules.h) ----
+ * An inverse telecine of one (geometry, subsampling, field order, nt) for nsrc sources, nin frames per source and call (a multiple of
+ * 5), its decision tables in device memory and -- with_state -- each source's state.  _run takes a call's clip ([source][nin frames] ->
+ * [source][4 nin / 5 pictures]) and refreshes the states; _reset forgets one source's (-1: all).  _clip is the standalone pass of one
+ * stream (nsrc == 1) with explicit states (frame bytes + w * h each, device memory, either may be NULL, they may be the same) and none
+ * kept; _tables: where the last call's match [nsrc][nin] and drop [nsrc][nin / 5] lie in device memory.  The field metrics of n frames
+ * of one stream: [n][4] uint32 in device memory (zeroed on the stream first). */
+int  dsv1_ivtc_valid(const dsv1_ivtc *iv);              /* 1: tff 0 / 1, nt 0 .. 254, reserved 0 */
+typedef struct dsvg_ivtc dsvg_ivtc;
+int  dsvg_ivtc_create(dsvg_ivtc **out, int device, int w, int h, int subsamp, const dsv1_ivtc *iv, int nsrc, int nin, int with_state);
+void dsvg_ivtc_destroy(dsvg_ivtc *d);
+int  dsvg_ivtc_run(dsvg_ivtc *d, void *stream, const void *src_dev, void *dst_dev);
+int  dsvg_ivtc_clip(dsvg_ivtc *d, void *stream, const void *src_dev, const void *state_in_dev, void *state_out_dev, void *dst_dev);
+void dsvg_ivtc_tables(const dsvg_ivtc *d, const void **match_dev, const void **drop_dev);
+int  dsvg_ivtc_reset(dsvg_ivtc *d, int source);
+int  dsvg_field_metrics_run(int device, void *stream, const void *src_dev, int w, int h, int subsamp, int n, const void *prev_dev, int nt,
+                            void *metrics_dev);
 
 /* ---- temporal noise reduction (include/dsv1_api.h, Temporal noise reduction; k_denoise.hip; host side: host/dsv1_denoise.c) ----
  * A noise filter of one (geometry, subsampling, strengths) for nsrc sources and -- with_state -- each source's state in device memory:

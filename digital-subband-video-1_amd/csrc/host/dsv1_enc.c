@@ -1279,7 +1279,29 @@ int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_deinterlace with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (di && b->src.iv) { dsv1_log(1, "dsv1_batch_set_source_deinterlace while an inverse telecine is set: clear it first"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_set_deinterlace(&b->src, di);
+}
+
+/* inverse telecine, in the deinterlacer's place: the setter, and one source's discontinuity */
+int dsv1_batch_set_source_ivtc(dsv1_batch *b, const dsv1_ivtc *iv)
+{
+    if (!b) return DSVG_ERR_ARG;
+    if (iv && !dsv1_ivtc_valid(iv)) { dsv1_log(1, "dsv1_batch_set_source_ivtc: tff %d / nt %d is not an inverse telecine", iv->tff, iv->nt); return DSVG_ERR_ARG; }
+    if (iv && (b->F < 4 || b->F % 4)) {
+        dsv1_log(1, "dsv1_batch_set_source_ivtc: frames_per_call (%d) must be a multiple of 4", b->F);
+        return DSVG_ERR_ARG;
+    }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_ivtc with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (iv && b->src.dd) { dsv1_log(1, "dsv1_batch_set_source_ivtc while a deinterlacer is set: clear it first"); return DSVG_ERR_ARG; }
+    return dsv1_srcchain_set_ivtc(&b->src, iv);
+}
+
+int dsv1_batch_ivtc_reset(dsv1_batch *b, int source)
+{
+    if (!b || !b->src.iv || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_ivtc_reset with batches in flight"); return DSVG_ERR_ARG; }
+    return dsv1_srcchain_ivtc_reset(&b->src, source);
 }
 
 int dsv1_batch_deinterlace_reset(dsv1_batch *b, int source)
@@ -1316,8 +1338,8 @@ int dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf)
         return DSVG_ERR_ARG;
     }
     if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_reframe with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (b->src.pc || b->src.dd || b->src.dn) {
-        dsv1_log(1, "dsv1_batch_set_source_reframe with a source format, a deinterlacer or a noise filter set: clear them first, set them again after it");
+    if (b->src.pc || b->src.dd || b->src.iv || b->src.dn) {
+        dsv1_log(1, "dsv1_batch_set_source_reframe with a source format, a deinterlacer, an inverse telecine or a noise filter set: clear them first, set them again after it");
         return DSVG_ERR_ARG;
     }
     return dsv1_srcchain_set_reframe(&b->src, rf);

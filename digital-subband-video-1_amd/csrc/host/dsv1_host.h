@@ -131,7 +131,8 @@ static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
  * TWO GEOMETRIES.  w x h (fb) is what convert, deinterlace and denoise are built for: the frames that come in.  ow x oh (ofb) is the
  * clip the chain hands on: the session's geometry.  They differ only while a reframe -- the LAST pass -- is set; it may be set, changed
  * or cleared only while no other pass is set (the session checks), and the passes set after it resolve at w x h. */
-enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_REFRAME, DSV1_SRC_SCALE };
+enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_REFRAME, DSV1_SRC_SCALE,
+       DSV1_SRC_IVTC };                 /* (the inverse telecine: exclusive with the deinterlacer, whose place and clips it takes) */
 typedef struct {
     int device, w, h, subsamp, nsrc, F, keep_lane;
     int ow, oh;                         /* the geometry handed on (the session's) */
@@ -140,6 +141,9 @@ typedef struct {
     dsvg_pixconv *pc;
     dsvg_deint *dd;
     dsv1_deint dd_set;
+    dsvg_ivtc *iv;                      /* the inverse telecine, in the deinterlacer's place (never both) */
+    dsv1_ivtc iv_set;
+    int conv_frames;                    /* frames per source the converter's clips hold */
     dsvg_denoise *dn;
     dsv1_denoise dn_set;
     dsvg_reframe *rf;
@@ -151,13 +155,18 @@ int  dsv1_srcchain_lane(dsv1_srcchain *c);             /* creates the lane where
 int  dsv1_srcchain_set_format(dsv1_srcchain *c, const dsv1_pix_layout *L, const dsv1_rgb_layout *R);      /* one of them, or neither: no converter */
 int  dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di);         /* (resets the noise filter's state) */
 int  dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn);
+/* the inverse telecine (resets the noise filter's state).  A call then brings 5 F / 4 frames per source: the converter's clips are
+ * allocated again for them, and again for F when it is cleared; on an error the chain is as it was.  The session checks that F is a
+ * multiple of 4 and that no deinterlacer is set (and no inverse telecine when it sets a deinterlacer). */
+int  dsv1_srcchain_set_ivtc(dsv1_srcchain *c, const dsv1_ivtc *iv);
+int  dsv1_srcchain_ivtc_reset(dsv1_srcchain *c, int source);                        /* DSVG_ERR_ARG where the pass is not set */
 /* a valid reframe whose canvas is ow x oh, or NULL / the identity: none.  DSVG_ERR_ARG, chain as it was, while another pass is set */
 int  dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf);
 int  dsv1_reframe_is_identity(const dsv1_reframe *rf);  /* dsv1_reframe.c: window = input = canvas at 0, 0 */
 int  dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source);                 /* DSVG_ERR_ARG where the pass is not set */
 int  dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source);
-static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->dd || c->dn || c->rf; }
-int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, or F / 2 at field rate */
+static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->dd || c->iv || c->dn || c->rf; }
+int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, F / 2 at field rate, 5 F / 4 in front of the inverse telecine */
 size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c); /* ... and the bytes of a call's clip */
 /* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> deinterlace -> denoise ->
  * reframe are set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where nothing ran) */

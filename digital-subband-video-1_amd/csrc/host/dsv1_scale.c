@@ -397,7 +397,28 @@ int dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di)
         return DSVG_ERR_ARG;
     }
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_deinterlace with calls in flight"); return DSVG_ERR_ARG; }
+    if (di && r->src.iv) { dsv1_log(1, "dsv1_resladder_set_deinterlace while an inverse telecine is set: clear it first"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_set_deinterlace(&r->src, di);
+}
+
+int dsv1_resladder_set_ivtc(dsv1_resladder *r, const dsv1_ivtc *iv)
+{
+    if (!r) return DSVG_ERR_ARG;
+    if (iv && !dsv1_ivtc_valid(iv)) { dsv1_log(1, "dsv1_resladder_set_ivtc: tff %d / nt %d is not an inverse telecine", iv->tff, iv->nt); return DSVG_ERR_ARG; }
+    if (iv && (r->F < 4 || r->F % 4)) {
+        dsv1_log(1, "dsv1_resladder_set_ivtc: frames_per_call (%d) must be a multiple of 4", r->F);
+        return DSVG_ERR_ARG;
+    }
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_ivtc with calls in flight"); return DSVG_ERR_ARG; }
+    if (iv && r->src.dd) { dsv1_log(1, "dsv1_resladder_set_ivtc while a deinterlacer is set: clear it first"); return DSVG_ERR_ARG; }
+    return dsv1_srcchain_set_ivtc(&r->src, iv);
+}
+
+int dsv1_resladder_ivtc_reset(dsv1_resladder *r, int source)
+{
+    if (!r || !r->src.iv || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_ivtc_reset with calls in flight"); return DSVG_ERR_ARG; }
+    return dsv1_srcchain_ivtc_reset(&r->src, source);
 }
 
 int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)

@@ -1,4 +1,4 @@
-/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace -> denoise -> reframe on one lane (dsvg_pixfmt.h), for
+/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace or inverse telecine -> denoise -> reframe on one lane (dsvg_pixfmt.h), for
  * batches (dsv1_enc.c) and resolution ladders (dsv1_scale.c), and the sequence the standalone clip calls share. */
 #include "dsv1_host.h"
 
@@ -25,38 +25,54 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
     if (c->lane) (void)dsvg_lane_sync(c->lane);        /* (the passes' kernels read the memory their destroy frees) */
     dsvg_pixconv_destroy(c->pc);
     dsvg_deint_destroy(c->dd);
+    dsvg_ivtc_destroy(c->iv);
     dsvg_denoise_destroy(c->dn);
     dsvg_reframe_destroy(c->rf);
     dsvg_lane_destroy(c->lane);                         /* (and the clips) */
     memset(c, 0, sizeof(*c));
 }
 
+/* the frames per source the converter writes: what a call brings.  (Never fewer than F: a field-rate deinterlacer may be cleared
+ * behind a converter that stays.) */
+static int conv_frames_for(const dsv1_srcchain *c, int with_ivtc) { return with_ivtc ? c->F / 4 * 5 : c->F; }
+
 /* pass p (NULL: none) takes slot k (DSV1_SRC_*): its two clips first, and only then does the pass set before go, with its clips.
- * On an error the chain is as it was and p is still the caller's. */
+ * The inverse telecine lives in the deinterlacer's slot; it changes what a call brings, so where a converter is installed its two
+ * clips are allocated again for that many frames in the same step.  On an error the chain is as it was and p is still the caller's. */
 static int chain_install(dsv1_srcchain *c, int k, void *p)
 {
+    const int slot = k == DSV1_SRC_IVTC ? DSV1_SRC_DEINTERLACE : k;
     const size_t fb = k == DSV1_SRC_REFRAME ? c->ofb : c->fb;
-    void *clip[2] = {NULL, NULL};
+    const int cf = conv_frames_for(c, k == DSV1_SRC_IVTC ? p != NULL : c->iv != NULL);
+    const int reconv = k == DSV1_SRC_IVTC && c->pc && cf != c->conv_frames;
+    void *clip[2] = {NULL, NULL}, *conv[2] = {NULL, NULL};
     int rc, j;
-    if (!p && !c->clip[k][0]) return DSVG_OK;
+    if (!p && !c->clip[slot][0]) return DSVG_OK;
     rc = dsv1_srcchain_lane(c);
-    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], fb * (size_t)c->nsrc * (size_t)c->F);
+    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], fb * (size_t)c->nsrc * (size_t)(k == DSV1_SRC_CONVERT ? cf : c->F));
+    for (j = 0; reconv && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &conv[j], fb * (size_t)c->nsrc * (size_t)cf);
     if (!rc) rc = dsvg_lane_sync(c->lane);
     if (rc) {
-        if (c->lane) for (j = 0; j < 2; j++) (void)dsvg_lane_free(c->lane, clip[j]);
+        if (c->lane) for (j = 0; j < 2; j++) { (void)dsvg_lane_free(c->lane, clip[j]); (void)dsvg_lane_free(c->lane, conv[j]); }
         chain_release(c);
         return rc;
     }
     switch (k) {
-    case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; break;
+    case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; c->conv_frames = p ? cf : 0; break;
     case DSV1_SRC_DEINTERLACE: dsvg_deint_destroy(c->dd); c->dd = (dsvg_deint *)p; break;
+    case DSV1_SRC_IVTC:        dsvg_ivtc_destroy(c->iv); c->iv = (dsvg_ivtc *)p; break;
     case DSV1_SRC_REFRAME:     dsvg_reframe_destroy(c->rf); c->rf = (dsvg_reframe *)p; break;
     default:                   dsvg_denoise_destroy(c->dn); c->dn = (dsvg_denoise *)p; break;
     }
     for (j = 0; j < 2; j++) {
-        (void)dsvg_lane_free(c->lane, c->clip[k][j]);
-        c->clip[k][j] = clip[j];
+        (void)dsvg_lane_free(c->lane, c->clip[slot][j]);
+        c->clip[slot][j] = clip[j];
+        if (reconv) {
+            (void)dsvg_lane_free(c->lane, c->clip[DSV1_SRC_CONVERT][j]);
+            c->clip[DSV1_SRC_CONVERT][j] = conv[j];
+        }
     }
+    if (reconv) c->conv_frames = cf;
     chain_release(c);
     return DSVG_OK;
 }
@@ -76,10 +92,25 @@ int dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di)
 {
     dsvg_deint *dd = NULL;
     int rc;
+    if (c->iv) return di ? DSVG_ERR_ARG : DSVG_OK;      /* (its slot is the inverse telecine's) */
     if (di && (rc = dsvg_deint_create(&dd, c->device, c->w, c->h, c->subsamp, di, c->nsrc, 1))) return rc;
     if ((rc = chain_install(c, DSV1_SRC_DEINTERLACE, dd))) { dsvg_deint_destroy(dd); return rc; }
     memset(&c->dd_set, 0, sizeof(c->dd_set));
     if (di) c->dd_set = *di;
+    return c->dn ? dsvg_denoise_reset(c->dn, -1) : DSVG_OK;     /* the pictures the noise filter sees change meaning */
+}
+
+int dsv1_srcchain_set_ivtc(dsv1_srcchain *c, const dsv1_ivtc *iv)
+{
+    dsvg_ivtc *p = NULL;
+    int rc;
+    if (c->dd) return iv ? DSVG_ERR_ARG : DSVG_OK;      /* (its slot is the deinterlacer's) */
+    if (iv && (c->F < 4 || c->F % 4)) return DSVG_ERR_ARG;
+    if (!iv && !c->iv) return DSVG_OK;
+    if (iv && (rc = dsvg_ivtc_create(&p, c->device, c->w, c->h, c->subsamp, iv, c->nsrc, c->F / 4 * 5, 1))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_IVTC, p))) { dsvg_ivtc_destroy(p); return rc; }
+    memset(&c->iv_set, 0, sizeof(c->iv_set));
+    if (iv) c->iv_set = *iv;
     return c->dn ? dsvg_denoise_reset(c->dn, -1) : DSVG_OK;     /* the pictures the noise filter sees change meaning */
 }
 
@@ -100,7 +131,7 @@ int dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf)
 {
     dsvg_reframe *r = NULL;
     int rc;
-    if (c->pc || c->dd || c->dn) return DSVG_ERR_ARG;
+    if (c->pc || c->dd || c->iv || c->dn) return DSVG_ERR_ARG;
     if (rf && (rf->out_w != c->ow || rf->out_h != c->oh)) return DSVG_ERR_ARG;
     if (rf && dsv1_reframe_is_identity(rf)) rf = NULL;
     if (rf && (rc = dsvg_reframe_create(&r, c->device, rf, c->subsamp))) return rc;
@@ -111,9 +142,14 @@ int dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf)
 }
 
 int dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source) { return c->dd ? dsvg_deint_reset(c->dd, source) : DSVG_ERR_ARG; }
+int dsv1_srcchain_ivtc_reset(dsv1_srcchain *c, int source) { return c->iv ? dsvg_ivtc_reset(c->iv, source) : DSVG_ERR_ARG; }
 int dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source) { return c->dn ? dsvg_denoise_reset(c->dn, source) : DSVG_ERR_ARG; }
 
-int dsv1_srcchain_frames_in(const dsv1_srcchain *c) { return c->dd && c->dd_set.mode == DSV1_DEINT_FIELD ? c->F / 2 : c->F; }
+int dsv1_srcchain_frames_in(const dsv1_srcchain *c)
+{
+    if (c->iv) return c->F / 4 * 5;
+    return c->dd && c->dd_set.mode == DSV1_DEINT_FIELD ? c->F / 2 : c->F;
+}
 size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c)
 {
     return (c->pc ? c->raw_fb : c->fb) * (size_t)c->nsrc * (size_t)dsv1_srcchain_frames_in(c);
@@ -135,6 +171,10 @@ int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device
     }
     if (c->dd) {
         if ((rc = dsvg_deint_run(c->dd, st, clip, nin, c->clip[DSV1_SRC_DEINTERLACE][par]))) return rc;
+        clip = c->clip[DSV1_SRC_DEINTERLACE][par];
+    }
+    if (c->iv) {
+        if ((rc = dsvg_ivtc_run(c->iv, st, clip, c->clip[DSV1_SRC_DEINTERLACE][par]))) return rc;
         clip = c->clip[DSV1_SRC_DEINTERLACE][par];
     }
     if (c->dn) {

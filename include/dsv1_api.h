@@ -591,7 +591,7 @@ int  dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf);
  * DSVG_ERR_ARG at the setter.  The frame rate in vidmeta is the caller's statement.  In a resolution ladder the deinterlaced clip
  * stands for the source everywhere: the scales, a geometry of the source's size, get_src_sse / get_src_ssim.  An invalid mode or tff
  * is DSVG_ERR_ARG before any device work and leaves the setting as it was.
- * Not offered: the drop-in dsv_enc, inverse telecine, field order detection, any lookahead. */
+ * Not offered: the drop-in dsv_enc, any lookahead.  (Inverse telecine and field order detection: the next section.) */
 #define DSV1_DEINT_FRAME 0
 #define DSV1_DEINT_FIELD 1
 typedef struct { int mode; int tff; } dsv1_deint;
@@ -605,6 +605,75 @@ int  dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di);    
 int  dsv1_batch_deinterlace_reset(dsv1_batch *b, int source);                         /* -1 = every source */
 int  dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di);
 int  dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source);
+
+/* ---- extension: inverse telecine and field order detection (csrc/k_ivtc.hip; stated in numpy in tests/_ivtc.py) ----
+ * Much 29.97i material is film that was 3:2 pulled down: film frames A B C D arrive as the frames (At,Ab) (Bt,Bb) (Bt,Cb) (Ct,Db)
+ * (Dt,Db) -- three progressive, two combed, one field sent twice.  Deinterlacing it throws away half the vertical detail of pictures
+ * that are all there.  This pass weaves the four film frames back exactly and drops the fifth: 5n frames in, 4n out, tightly packed
+ * planar 8-bit frames as everywhere.  Causal, no lookahead, every decision made on the device.
+ * All decisions read luma only, W x H.  Line y belongs to field y & 1; p = tff ? 0 : 1 is the parity of the field that is first in
+ * time; cur is frame t of a stream, prv frame t - 1, or absent.
+ * COMB.  Kept lines of parity q from frame K, the lines of parity 1 - q from frame O: over every y with (y & 1) == 1 - q, y - 1 >= 0,
+ *   y + 1 <= H - 1 (border lines without two neighbours are left out) and every x, a = K[y-1][x], b = K[y+1][x], o = O[y][x],
+ *   e = max(min(a, b) - o, o - max(a, b), 0); comb(K, q, O) = the sum of e over the samples where e > nt.
+ * FIELD METRICS of frame t, four uint32_t: mc[q] = comb(cur, q, cur), mp[q] = comb(cur, q, prv), q = 0, 1; mp = 0 where prv is absent.
+ *   Stored as mc0 mc1 mp0 mp1.  A sum is at most 255 * W * ceil(H / 2); the calls below take a luma of at most 16843008 samples
+ *   (255 * W * H < 2^32 - 1: exact in uint32_t for every size the library encodes, 4K and beyond) and refuse anything larger.
+ * MATCH.  match[t] = P (1) if prv is present and mp[p] < mc[p], else C (0).  Keeping the first field in time makes P and C enough: a
+ *   film frame covers at least two consecutive fields, so the kept field's partner is the opposite field just before it (prv's) or
+ *   just after it (cur's own).
+ * WOVEN PICTURE V_t, every plane at its own dimensions (the chroma planes alternate fields line by line, as in the deinterlacer):
+ *   lines of parity p from cur, the others from prv if the match is P, else from cur.  A plane with one line is cur's.
+ * DECIMATION.  Input is grouped in cycles of 5 from the start of the stream.  D_t = the luma SAD of V_t against V_(t-1), UINT32_MAX for
+ *   the first picture of a stream.  In each cycle the picture with the smallest D is dropped (drop[c] = 0 .. 4, on ties the earliest);
+ *   the other four go out in order.  n must be a multiple of 5.
+ * STATE a stream carries between calls, dsv1_ivtc_state_bytes: its last input frame (frame_bytes), then the luma of its last woven
+ *   picture (w * h), which may be one that was dropped.  Calls take whole cycles, so the output of a stream does not depend on how it is
+ *   cut into calls.
+ * FIELD ORDER from the same metrics (dsv1_field_order_from_metrics, host only): every frame that has a prv (t >= 1, and t = 0 where
+ *   first_has_prev) votes tff if mp[0] < mp[1] and bff if mp[1] < mp[0]: mp[0] weaves the top field of t with the bottom field of t - 1,
+ *   one field time apart under tff, three under bff.  1 (tff) if tff_votes > 2 * bff_votes, 0 (bff) if bff_votes > 2 * tff_votes, -1
+ *   otherwise.  The vote is for material that moves and is smooth against its motion: texture that decorrelates within one field's
+ *   motion does not separate the orders, telecined film decides only three votes of five, and on static material mp equals mc, so a
+ *   frame's vote there compares the vertical detail of its own two fields (no vote at all where there is none) and says nothing
+ *   about time.
+ * dsv1_ivtc_match / dsv1_ivtc_pick (host only) are the two decision rules the kernels run, compiled from the same header
+ *   (csrc/dsvg_ivtc_rules.h): match [n] from metrics [n][4]; drop [n / 5] from D [n].
+ *   dsv1_detect_field_order_clip does both steps over a clip with no prev and answers 1 / 0 / -1 or an error below -1: DSVG_ERR_ARG
+ *   and its kin; since -1 is an answer, a HIP runtime failure comes back as DSVG_ERR_NODEVICE (dsvg_last_error has the text).
+ * dsv1_field_metrics_clip: src and prev (one frame, or NULL) host or device memory (on_device), the metrics always to host memory.
+ * dsv1_ivtc_clip: n frames of one stream -> 4n / 5 pictures.  state_in: what the call before left, or NULL: the stream starts here;
+ *   state_out: receives the state, or NULL; it may be state_in.  src, states and dst host or device memory (on_device); match_out [n]
+ *   and drop_out [n / 5] always host memory, either may be NULL.  dst must not overlap src.  Synchronous; any w, h >= 1 within the bound
+ *   above and every subsampling the library knows; nothing outside the frames and the states is read or written.
+ * SESSIONS.  The pass takes the deinterlacer's place in the source chain: convert -> inverse telecine -> denoise -> reframe.  It is
+ * exclusive with the deinterlacer: setting either while the other is set is DSVG_ERR_ARG with the settings left as they were.  Setting,
+ * changing or clearing it forgets its own state and the noise filter's (the pictures change meaning); _reset forgets the state of one
+ * source (-1: every source): its next picture is a first picture.  The setters and _reset only with nothing in flight (DSVG_ERR_ARG
+ * otherwise; _reset with no inverse telecine set too).  frames_per_call counts coded pictures: a call takes 5 * frames_per_call / 4
+ * input frames per source, and frames_per_call % 4 != 0 is DSVG_ERR_ARG at the setter.  Like the other passes it is set after a
+ * reframe, never before.  Clip ownership is dsv1_batch_set_source_format's; dsv1_batch_stage is refused while it is set.  The frame
+ * rate in vidmeta stays the caller's statement.  An invalid dsv1_ivtc is DSVG_ERR_ARG before any device work.
+ * Not offered: the drop-in dsv_enc; lookahead or n-matches; mixed or hybrid content handling, and post-processing of frames that stay
+ * combed; cadences other than cycle 5; reading the decisions back from a session; automatic application of a detected order. */
+#define DSV1_IVTC_C 0
+#define DSV1_IVTC_P 1
+typedef struct { int tff; int nt; int reserved[2]; } dsv1_ivtc;   /* tff 0 / 1, nt 0 .. 254, reserved 0; else DSVG_ERR_ARG */
+int    dsv1_ivtc_out_frames(const dsv1_ivtc *iv, int n);          /* 4n / 5; DSVG_ERR_ARG unless n >= 0 and n % 5 == 0; host only */
+size_t dsv1_ivtc_state_bytes(int w, int h, int subsamp);          /* frame_bytes + w * h; 0 for w, h < 1 or an unknown subsampling; host only */
+int    dsv1_field_metrics_clip(int device, const void *src, int w, int h, int subsamp, int n, const void *prev, int nt,
+                               uint32_t *metrics /* [n][4]: mc0 mc1 mp0 mp1, host */, int on_device);
+int    dsv1_field_order_from_metrics(const uint32_t *metrics, int n, int first_has_prev);   /* 1 / 0 / -1; DSVG_ERR_ARG for NULL or n < 1 */
+int    dsv1_detect_field_order_clip(int device, const void *src, int w, int h, int subsamp, int n, int nt, int on_device);
+int    dsv1_ivtc_match(const uint32_t *metrics, int n, int first_has_prev, int tff, uint8_t *match);
+int    dsv1_ivtc_pick(const uint32_t *D, int n, uint8_t *drop /* [n / 5] */);
+int    dsv1_ivtc_clip(int device, const void *src, int w, int h, int subsamp, int n, const void *state_in, void *state_out,
+                      void *dst, const dsv1_ivtc *iv, uint8_t *match_out /* [n] or NULL */, uint8_t *drop_out /* [n / 5] or NULL */,
+                      int on_device);
+int    dsv1_batch_set_source_ivtc(dsv1_batch *b, const dsv1_ivtc *iv);     /* NULL = off; batches, quality ladders, chain mode */
+int    dsv1_batch_ivtc_reset(dsv1_batch *b, int source);                   /* -1 = every source */
+int    dsv1_resladder_set_ivtc(dsv1_resladder *r, const dsv1_ivtc *iv);
+int    dsv1_resladder_ivtc_reset(dsv1_resladder *r, int source);
 
 /* ---- extension: temporal noise reduction (csrc/k_denoise.hip; stated in numpy in tests/_denoise.py) ----
  * Camera and film noise is uncorrelated from picture to picture: motion compensation cannot predict it and every P picture codes it
