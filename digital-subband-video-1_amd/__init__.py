@@ -179,6 +179,12 @@ class Reframe(_C.Structure):
         super().__init__(in_w, in_h, x, y, w, h, ow, oh, dst[0], dst[1], (_C.c_uint8 * 3)(*fill), 0)
 
 
+class Orient:
+    """the eight orientations (DSV1_ORIENT_*; include/dsv1_api.h, Orientation): bit 2 transposes first, bit 0 then mirrors the columns
+    of the result, bit 1 its rows.  ROT90 and ROT270 are clockwise."""
+    NONE, HFLIP, VFLIP, ROT180, TRANSPOSE, ROT90, ROT270, TRANSVERSE = range(8)
+
+
 class BlockInfo(_C.Structure):
     """dsv1_blockinfo: one block's side information (packet_blockinfo, draw_info_clip)"""
     _fields_ = [("mvx", _C.c_int16), ("mvy", _C.c_int16), ("mode", _C.c_uint8), ("submask", _C.c_uint8), ("stable", _C.c_uint8),
@@ -346,6 +352,17 @@ def lib():
         L.dsv1_resladder_open_reframed.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(Reframe), _C.POINTER(PixFormat),
                                                    _C.c_int, _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int, _C.c_int, _C.c_int,
                                                    _C.c_int, _C.c_int]
+        L.dsv1_orient_valid.argtypes = [_C.c_int, _C.c_int]
+        L.dsv1_orient_dims.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int), _C.POINTER(_C.c_int)]
+        L.dsv1_orient_compose.argtypes = [_C.c_int, _C.c_int]
+        L.dsv1_orient_inverse.argtypes = [_C.c_int]
+        L.dsv1_orient_from_exif.argtypes = [_C.c_int]
+        L.dsv1_orient_from_matrix.argtypes = [_C.POINTER(_C.c_int32)]
+        L.dsv1_orient_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int, _C.c_int]
+        L.dsv1_batch_set_source_orient.argtypes = [_C.c_void_p, _C.c_int]
+        L.dsv1_resladder_open_oriented.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.c_int, _C.POINTER(Reframe),
+                                                   _C.POINTER(PixFormat), _C.c_int, _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int,
+                                                   _C.c_int, _C.c_int, _C.c_int, _C.c_int]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         L.dsvg_inv_plan.argtypes = [_C.c_int] * 9 + [_C.c_uint, _C.c_int, _C.POINTER(InvStep), _C.c_int, _C.POINTER(_C.c_int)]
@@ -569,12 +586,24 @@ class Batch:
         and no source format, RGB format, deinterlacer or noise filter set: those are set AFTER it and resolve at the input geometry.
         The input-length check follows."""
         _chk(self.L.dsv1_batch_set_source_reframe(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_reframe")
-        self._in_dims = (rf.in_w, rf.in_h) if rf is not None else (self.width, self.height)
+        self._in_dims = self._oriented_dims = (rf.in_w, rf.in_h) if rf is not None else (self.width, self.height)
+        self.frame_bytes = self._in_dims[0] * self._in_dims[1] + 2 * _chroma_size(self._in_dims[0], self._in_dims[1], self.fmt)
+
+    def set_source_orient(self, orient):
+        """from the next submit on the clips are oriented on the GPU by code `orient` (Orient.*; dsv1_batch_set_source_orient) behind
+        the noise filter and in front of the reframe; 0 switches it off.  The oriented picture is the reframe's input (set BEFORE
+        this) or the batch's geometry; the clips come in at the raw geometry, orient_dims(orient_inverse(orient), ...) of it.  Only
+        with nothing in flight and no source format, RGB format, deinterlacer, inverse telecine or noise filter set: those are set
+        AFTER it and resolve at the raw geometry.  The input-length check follows."""
+        _chk(self.L.dsv1_batch_set_source_orient(self.h, orient), "dsv1_batch_set_source_orient")
+        mw, mh = getattr(self, "_oriented_dims", (self.width, self.height))
+        self._in_dims = orient_dims(orient_inverse(orient), mw, mh)
         self.frame_bytes = self._in_dims[0] * self._in_dims[1] + 2 * _chroma_size(self._in_dims[0], self._in_dims[1], self.fmt)
 
     @property
     def in_dims(self):
-        """(width, height) of the frames that come in: the batch's geometry, or the input of the reframe set"""
+        """(width, height) of the frames that come in: the batch's geometry, or the input of the reframe set, turned back by the
+        orientation set"""
         return getattr(self, "_in_dims", (self.width, self.height))
 
     def set_fnum(self, stream, fnum):
@@ -1032,6 +1061,61 @@ def reframe_clip(clip, rf, fmt, device=0, n=None, out=None):
     return res
 
 
+def orient_dims(orient, w, h):
+    """(width, height) of w x h frames oriented by code `orient` (dsv1_orient_dims)"""
+    ow, oh = _C.c_int(0), _C.c_int(0)
+    if lib().dsv1_orient_dims(orient, w, h, _C.byref(ow), _C.byref(oh)):
+        raise ValueError("orient_dims: code %d / %dx%d refused" % (orient, w, h))
+    return ow.value, oh.value
+
+
+def _orient_code(rc, what):
+    if rc < 0:
+        raise ValueError("%s refused (rc=%d)" % (what, rc))
+    return rc
+
+
+def orient_compose(a, b):
+    """the one code equal to applying a and then b (dsv1_orient_compose)"""
+    return _orient_code(lib().dsv1_orient_compose(a, b), "orient_compose(%d, %d)" % (a, b))
+
+
+def orient_inverse(a):
+    """the code that undoes a (dsv1_orient_inverse)"""
+    return _orient_code(lib().dsv1_orient_inverse(a), "orient_inverse(%d)" % a)
+
+
+def orient_from_exif(tag):
+    """EXIF orientation tag 1 .. 8 -> code (dsv1_orient_from_exif)"""
+    return _orient_code(lib().dsv1_orient_from_exif(tag), "orient_from_exif(%d)" % tag)
+
+
+def orient_from_matrix(m):
+    """an MP4 / QuickTime track display matrix (9 int32, 16.16 fixed point) -> code (dsv1_orient_from_matrix); scale, shear and other
+    angles raise ValueError"""
+    m = [int(x) for x in m]
+    if len(m) != 9:
+        raise ValueError("a display matrix has 9 entries")
+    return _orient_code(lib().dsv1_orient_from_matrix((_C.c_int32 * 9)(*m)), "orient_from_matrix")
+
+
+def orient_clip(clip, w, h, fmt, orient, device=0, n=None, out=None):
+    """orient packed planar 8-bit frames of w x h on the GPU (dsv1_orient_clip) by code `orient`: clip numpy uint8 [frames][frame
+    bytes] (host), which returns numpy uint8 [frames][frame bytes] of orient_dims(orient, w, h); or a device pointer with n frames and
+    `out` a device pointer for the result.  Code 0 copies."""
+    L = lib()
+    if n is not None:
+        _chk(L.dsv1_orient_clip(device, clip, w, h, fmt, n, out, orient, 1), "dsv1_orient_clip")
+        return out
+    if not L.dsv1_orient_valid(orient, fmt):
+        raise ValueError("%d is not an orientation at subsampling 0x%x" % (orient, fmt))
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    a, frames = _host_clip(clip, fb)
+    res = _host_out(out, frames, fb)
+    _chk(L.dsv1_orient_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, orient, 0), "dsv1_orient_clip")
+    return res
+
+
 def line_sums_clip(clip, w, h, fmt, device=0, n=None):
     """the sums of every luma row and column of a clip, on the GPU (dsv1_line_sums_clip): clip numpy uint8 [frames][frame_bytes]
     (host), or a device pointer with n frames.  Returns (row_sum numpy uint32 [frames][h], col_sum numpy uint32 [frames][w])."""
@@ -1257,12 +1341,14 @@ class ResLadder:
     k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
 
     def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None, src_rgb=None,
-                 src_subsamp=None, reframe=None):
+                 src_subsamp=None, reframe=None, orient=0):
         """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit); src_rgb: their RgbFormat
         instead (dsv1_resladder_open_rgb); src_subsamp: the subsampling of the source clips where it is not fmt
         (dsv1_resladder_open_src_sub) -- 4:4:4 or 4:2:2, chroma halved to fmt by the converter; reframe: a Reframe of the w x h
         sources (dsv1_resladder_open_reframed), the last pass in front of the scales: its canvas stands for the source from there on
-        (self.width x self.height, the rungs' ratio limits, src_psnr / src_ssim), the clips handed in stay w x h"""
+        (self.width x self.height, the rungs' ratio limits, src_psnr / src_ssim), the clips handed in stay w x h; orient: an Orient
+        code (dsv1_resladder_open_oriented) applied to the w x h sources in front of the reframe, whose input is then the oriented
+        geometry -- without a reframe the oriented picture stands for the source"""
         if src_format is not None and src_rgb is not None:
             raise ValueError("src_format and src_rgb exclude each other")
         if src_subsamp is not None and src_rgb is not None:
@@ -1277,7 +1363,14 @@ class ResLadder:
         rr = (ResRung * max(len(geoms), 1))(*[ResRung(gw, gh, len(r), a) for (gw, gh, r), a in zip(geoms, self._arrs)])
         meta = Meta()
         meta.width, meta.height, meta.subsamp = w, h, fmt
-        if reframe is not None:
+        if orient:
+            _chk(self.L.dsv1_resladder_open_oriented(_C.byref(self.h), _C.byref(meta), orient, None if reframe is None else _C.byref(reframe),
+                                                     None if src_format is None else _C.byref(src_format),
+                                                     fmt if src_subsamp is None else src_subsamp,
+                                                     None if src_rgb is None else _C.byref(src_rgb), rr, len(geoms), device, nsources,
+                                                     frames_per_call, filt), "dsv1_resladder_open_oriented")
+            self.width, self.height = (reframe.out_w, reframe.out_h) if reframe is not None else orient_dims(orient, w, h)
+        elif reframe is not None:
             _chk(self.L.dsv1_resladder_open_reframed(_C.byref(self.h), _C.byref(meta), _C.byref(reframe),
                                                      None if src_format is None else _C.byref(src_format),
                                                      fmt if src_subsamp is None else src_subsamp,

@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -152,6 +152,13 @@ typedef struct dsvg_reframe dsvg_reframe;
 int  dsvg_reframe_create(dsvg_reframe **out, int device, const dsv1_reframe *rf, int subsamp);
 void dsvg_reframe_destroy(dsvg_reframe *r);
 int  dsvg_reframe_run(dsvg_reframe *r, void *stream, const void *src_dev, int nframes, void *dst_dev);
+/* ---- orientation (include/dsv1_api.h, Orientation; k_orient.hip; host side: host/dsv1_orient.c) ----
+ * One code for frames that come in at w x h: nframes frames -> nframes frames of dsv1_orient_dims(orient, w, h); it keeps no state
+ * and owns no device memory.  Code 0 is a device-to-device copy on the stream (the standalone call's; a session sets no pass for it). */
+typedef struct dsvg_orient dsvg_orient;
+int  dsvg_orient_create(dsvg_orient **out, int device, int orient, int w, int h, int subsamp);
+void dsvg_orient_destroy(dsvg_orient *o);
+int  dsvg_orient_run(dsvg_orient *o, void *stream, const void *src_dev, int nframes, void *dst_dev);
 typedef struct dsvg_linesums dsvg_linesums;
 int  dsvg_linesums_create(dsvg_linesums **out, int device, int w, int h, int subsamp);
 void dsvg_linesums_destroy(dsvg_linesums *s);

@@ -1220,7 +1220,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer, a noise filter or a reframe is set"); return DSVG_ERR_ARG; }
+    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer, a noise filter, an orientation or a reframe is set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1342,7 +1342,26 @@ int dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf)
         dsv1_log(1, "dsv1_batch_set_source_reframe with a source format, a deinterlacer, an inverse telecine or a noise filter set: clear them first, set them again after it");
         return DSVG_ERR_ARG;
     }
+    if (b->src.orn) { dsv1_log(1, "dsv1_batch_set_source_reframe while an orientation is set: clear it first, set it again after the reframe"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_set_reframe(&b->src, rf);
+}
+
+/* the orientation: in front of the reframe, behind the other passes, whose geometry it changes: only while none of those is set */
+int dsv1_batch_set_source_orient(dsv1_batch *b, int orient)
+{
+    const DSV_META *m;
+    if (!b) return DSVG_ERR_ARG;
+    m = &b->enc[0].vidmeta;
+    if (!dsv1_orient_valid(orient, m->subsamp)) {
+        dsv1_log(1, "dsv1_batch_set_source_orient: %d is not an orientation of subsampling 0x%x", orient, m->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_orient with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    if (b->src.pc || b->src.dd || b->src.iv || b->src.dn) {
+        dsv1_log(1, "dsv1_batch_set_source_orient with a source format, a deinterlacer, an inverse telecine or a noise filter set: clear them first, set them again after it");
+        return DSVG_ERR_ARG;
+    }
+    return dsv1_srcchain_set_orient(&b->src, orient);
 }
 
 /* tests: 1 while the batch's source chain holds a lane (a stream and device memory of its own), 0 with no pass set */

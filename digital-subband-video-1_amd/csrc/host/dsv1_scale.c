@@ -168,14 +168,14 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
     return dsv1_resladder_open_src(out, src, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
-static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_reframe *frm, const dsv1_pix_format *pf, int src_subsamp,
-                              const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call,
-                              int filter);
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *frm, const dsv1_pix_format *pf,
+                              int src_subsamp, const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
+                              int frames_per_call, int filter);
 
 int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs, int ngeoms,
                             int device, int nsources, int frames_per_call, int filter)
 {
-    return resladder_open_fmt(out, src, NULL, pf, src ? src->subsamp : 0, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, 0, NULL, pf, src ? src->subsamp : 0, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* sources at src_subsamp: the converter halves their chroma to src->subsamp on the way */
@@ -184,7 +184,7 @@ int dsv1_resladder_open_src_sub(dsv1_resladder **out, const DSV_META *src, const
 {
     static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
     if (!pf && src && src_subsamp != src->subsamp) pf = &planar8;
-    return resladder_open_fmt(out, src, NULL, pf, src_subsamp, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, 0, NULL, pf, src_subsamp, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* RGB sources: the RGB import pass (k_rgb.hip) in the converter's place, everything else as dsv1_resladder_open_src */
@@ -193,7 +193,7 @@ int dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const dsv
 {
     if (out) *out = NULL;
     if (!rf) return DSVG_ERR_ARG;
-    return resladder_open_fmt(out, src, NULL, NULL, src ? src->subsamp : 0, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, 0, NULL, NULL, src ? src->subsamp : 0, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* sources of geometry *src = the reframe's input, reframed behind the other passes: the CANVAS stands for the source from the scales on */
@@ -201,25 +201,40 @@ int dsv1_resladder_open_reframed(dsv1_resladder **out, const DSV_META *src, cons
                                  const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call,
                                  int filter)
 {
+    return dsv1_resladder_open_oriented(out, src, DSV1_ORIENT_NONE, rf, pf, src_subsamp, rgb, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+/* sources of the RAW geometry *src, oriented behind the other passes and in front of the reframe: the reframe's input is the oriented
+ * geometry, and without a reframe the oriented picture stands for the source from the scales on */
+int dsv1_resladder_open_oriented(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *rf, const dsv1_pix_format *pf,
+                                 int src_subsamp, const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
+                                 int frames_per_call, int filter)
+{
     static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
+    int mw, mh;
     if (out) *out = NULL;
     if (!src || (pf && rgb)) return DSVG_ERR_ARG;
-    if (rf && (!dsv1_reframe_valid(rf, src->subsamp) || rf->in_w != src->width || rf->in_h != src->height)) {
-        dsv1_log(1, "dsv1_resladder_open_reframed: not a valid reframe of %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
+    if (!dsv1_orient_valid(orient, src->subsamp) || dsv1_orient_dims(orient, src->width, src->height, &mw, &mh)) {
+        dsv1_log(1, "dsv1_resladder_open_oriented: %d is not an orientation of %dx%d sources of subsampling 0x%x", orient, src->width, src->height, src->subsamp);
+        return DSVG_ERR_ARG;
+    }
+    if (rf && (!dsv1_reframe_valid(rf, src->subsamp) || rf->in_w != mw || rf->in_h != mh)) {
+        dsv1_log(1, "dsv1_resladder_open: not a valid reframe of %dx%d pictures (the sources, oriented) of subsampling 0x%x", mw, mh, src->subsamp);
         return DSVG_ERR_ARG;
     }
     if (rgb) src_subsamp = src->subsamp;
     else if (!pf && src_subsamp != src->subsamp) pf = &planar8;
-    return resladder_open_fmt(out, src, rf, pf, src_subsamp, rgb, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, orient, rf, pf, src_subsamp, rgb, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
-static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const dsv1_reframe *frm, const dsv1_pix_format *pf, int src_subsamp,
-                              const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call,
-                              int filter)
+static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *frm, const dsv1_pix_format *pf,
+                              int src_subsamp, const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
+                              int frames_per_call, int filter)
 {
-    /* cw x ch: what stands for the source behind the chain -- the reframe's canvas, or the source itself; the passes in front of the
-     * reframe and the caller's clips are src->width x src->height */
-    const int cw = frm && src ? frm->out_w : src ? src->width : 0, ch = frm && src ? frm->out_h : src ? src->height : 0;
+    /* cw x ch: what stands for the source behind the chain -- the reframe's canvas, or the source itself, oriented (the callers pass a
+     * valid code); the passes in front of the orientation and the caller's clips are src->width x src->height */
+    const int tr = orient & 4;
+    const int cw = frm && src ? frm->out_w : src ? (tr ? src->height : src->width) : 0, ch = frm && src ? frm->out_h : src ? (tr ? src->width : src->height) : 0;
     dsv1_resladder *r;
     dsv1_pix_layout pl;
     dsv1_rgb_layout rl;
@@ -289,7 +304,8 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, const d
     }
     /* the lane exists even when no geometry is scaled: host input is uploaded through it */
     if ((rc = dsvg_scaler_create(&r->sc, device, cw, ch, src->subsamp, nscaled, dw, dh, filter)) ||
-        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_set_reframe(&r->src, frm)) || (rc = dsv1_srcchain_set_format(&r->src, pf ? &pl : NULL, rf ? &rl : NULL))) { dsv1_resladder_close(r); return rc; }
+        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_set_reframe(&r->src, frm)) || (rc = dsv1_srcchain_set_orient(&r->src, orient)) ||
+        (rc = dsv1_srcchain_set_format(&r->src, pf ? &pl : NULL, rf ? &rl : NULL))) { dsv1_resladder_close(r); return rc; }
     for (g = 0; g < ngeoms; g++) {
         if ((rc = dsv1_ladder_open(&r->lad[g], rungs[g].rates, rungs[g].nrates, device, nsources, frames_per_call))) break;
         r->ngeom = g + 1;

@@ -1,4 +1,4 @@
-/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace or inverse telecine -> denoise -> reframe on one lane (dsvg_pixfmt.h), for
+/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace or inverse telecine -> denoise -> orient -> reframe on one lane (dsvg_pixfmt.h), for
  * batches (dsv1_enc.c) and resolution ladders (dsv1_scale.c), and the sequence the standalone clip calls share. */
 #include "dsv1_host.h"
 
@@ -6,8 +6,8 @@ void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp,
 {
     memset(c, 0, sizeof(*c));
     c->device = device; c->w = w; c->h = h; c->subsamp = subsamp; c->nsrc = nsrc; c->F = F; c->keep_lane = keep_lane;
-    c->ow = w; c->oh = h;
-    c->fb = c->ofb = dsv1_frame_bytes(w, h, subsamp);
+    c->mw = c->ow = w; c->mh = c->oh = h;
+    c->fb = c->mfb = c->ofb = dsv1_frame_bytes(w, h, subsamp);
 }
 
 int dsv1_srcchain_lane(dsv1_srcchain *c) { return c->lane ? DSVG_OK : dsvg_lane_create(&c->lane, c->device); }
@@ -27,6 +27,7 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
     dsvg_deint_destroy(c->dd);
     dsvg_ivtc_destroy(c->iv);
     dsvg_denoise_destroy(c->dn);
+    dsvg_orient_destroy(c->orn);
     dsvg_reframe_destroy(c->rf);
     dsvg_lane_destroy(c->lane);                         /* (and the clips) */
     memset(c, 0, sizeof(*c));
@@ -42,7 +43,7 @@ static int conv_frames_for(const dsv1_srcchain *c, int with_ivtc) { return with_
 static int chain_install(dsv1_srcchain *c, int k, void *p)
 {
     const int slot = k == DSV1_SRC_IVTC ? DSV1_SRC_DEINTERLACE : k;
-    const size_t fb = k == DSV1_SRC_REFRAME ? c->ofb : c->fb;
+    const size_t fb = k == DSV1_SRC_REFRAME ? c->ofb : k == DSV1_SRC_ORIENT ? c->mfb : c->fb;
     const int cf = conv_frames_for(c, k == DSV1_SRC_IVTC ? p != NULL : c->iv != NULL);
     const int reconv = k == DSV1_SRC_IVTC && c->pc && cf != c->conv_frames;
     void *clip[2] = {NULL, NULL}, *conv[2] = {NULL, NULL};
@@ -61,6 +62,7 @@ static int chain_install(dsv1_srcchain *c, int k, void *p)
     case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; c->conv_frames = p ? cf : 0; break;
     case DSV1_SRC_DEINTERLACE: dsvg_deint_destroy(c->dd); c->dd = (dsvg_deint *)p; break;
     case DSV1_SRC_IVTC:        dsvg_ivtc_destroy(c->iv); c->iv = (dsvg_ivtc *)p; break;
+    case DSV1_SRC_ORIENT:      dsvg_orient_destroy(c->orn); c->orn = (dsvg_orient *)p; break;
     case DSV1_SRC_REFRAME:     dsvg_reframe_destroy(c->rf); c->rf = (dsvg_reframe *)p; break;
     default:                   dsvg_denoise_destroy(c->dn); c->dn = (dsvg_denoise *)p; break;
     }
@@ -126,18 +128,34 @@ int dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn)
 }
 
 /* the frames that come in take the reframe's input geometry (the session's own again without one): only while no other pass is set,
- * whose clips and state are sized for the geometry in force */
+ * whose clips and state are sized for the geometry in force (the orientation is set behind it, and turns that geometry) */
 int dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf)
 {
     dsvg_reframe *r = NULL;
     int rc;
-    if (c->pc || c->dd || c->iv || c->dn) return DSVG_ERR_ARG;
+    if (c->pc || c->dd || c->iv || c->dn || c->orn) return DSVG_ERR_ARG;
     if (rf && (rf->out_w != c->ow || rf->out_h != c->oh)) return DSVG_ERR_ARG;
     if (rf && dsv1_reframe_is_identity(rf)) rf = NULL;
     if (rf && (rc = dsvg_reframe_create(&r, c->device, rf, c->subsamp))) return rc;
     if ((rc = chain_install(c, DSV1_SRC_REFRAME, r))) { dsvg_reframe_destroy(r); return rc; }
-    c->w = rf ? rf->in_w : c->ow; c->h = rf ? rf->in_h : c->oh;
-    c->fb = dsv1_frame_bytes(c->w, c->h, c->subsamp);
+    c->w = c->mw = rf ? rf->in_w : c->ow; c->h = c->mh = rf ? rf->in_h : c->oh;
+    c->fb = c->mfb = dsv1_frame_bytes(c->w, c->h, c->subsamp);
+    return DSVG_OK;
+}
+
+/* the frames that come in are the oriented geometry (the reframe's input, or the session's own) turned back by the inverse code: only
+ * while no pass in front of it is set, whose clips and state are sized for the raw geometry in force */
+int dsv1_srcchain_set_orient(dsv1_srcchain *c, int orient)
+{
+    dsvg_orient *o = NULL;
+    int rc, rw, rh;
+    if (c->pc || c->dd || c->iv || c->dn) return DSVG_ERR_ARG;
+    if (!dsv1_orient_valid(orient, c->subsamp) || dsv1_orient_dims(dsv1_orient_inverse(orient), c->mw, c->mh, &rw, &rh)) return DSVG_ERR_ARG;
+    if (orient && (rc = dsvg_orient_create(&o, c->device, orient, rw, rh, c->subsamp))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_ORIENT, o))) { dsvg_orient_destroy(o); return rc; }
+    c->orient = orient;
+    c->w = rw; c->h = rh;
+    c->fb = dsv1_frame_bytes(rw, rh, c->subsamp);
     return DSVG_OK;
 }
 
@@ -181,6 +199,10 @@ int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device
         if ((rc = dsvg_denoise_run(c->dn, st, clip, c->F, c->clip[DSV1_SRC_DENOISE][par]))) return rc;
         clip = c->clip[DSV1_SRC_DENOISE][par];
     }
+    if (c->orn) {
+        if ((rc = dsvg_orient_run(c->orn, st, clip, c->nsrc * c->F, c->clip[DSV1_SRC_ORIENT][par]))) return rc;
+        clip = c->clip[DSV1_SRC_ORIENT][par];
+    }
     if (c->rf) {
         if ((rc = dsvg_reframe_run(c->rf, st, clip, c->nsrc * c->F, c->clip[DSV1_SRC_REFRAME][par]))) return rc;
         clip = c->clip[DSV1_SRC_REFRAME][par];
@@ -206,6 +228,7 @@ int dsv1_pass_clip(int device, int kind, void *pass, int n, const dsv1_clip_io *
         case DSV1_SRC_CONVERT:     rc = dsvg_pixconv_run((dsvg_pixconv *)pass, st, din[0], n, dout[0]); break;
         case DSV1_SRC_DEINTERLACE: rc = dsvg_deint_clip((dsvg_deint *)pass, st, din[0], n, din[1], dout[0]); break;
         case DSV1_SRC_DENOISE:     rc = dsvg_denoise_clip((dsvg_denoise *)pass, st, din[0], n, din[1], dout[1], dout[0]); break;
+        case DSV1_SRC_ORIENT:      rc = dsvg_orient_run((dsvg_orient *)pass, st, din[0], n, dout[0]); break;
         case DSV1_SRC_REFRAME:     rc = dsvg_reframe_run((dsvg_reframe *)pass, st, din[0], n, dout[0]); break;
         default:                   rc = dsvg_scaler_run((dsvg_scaler *)pass, st, 0, din[0], n, dout[0]); break;
         }

@@ -783,6 +783,62 @@ int  dsv1_resladder_open_reframed(dsv1_resladder **out, const DSV_META *src, con
                                   int src_subsamp, const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device,
                                   int nsources, int frames_per_call, int filter);
 
+/* ---- extension: orientation -- rotate, flip, transpose: the eight orientations (csrc/k_orient.hip; stated in numpy in
+ * tests/_orient.py) ----
+ * Phone and tablet footage stored in sensor order beside a rotation tag or display matrix, mirrored or upside-down captures, portrait
+ * video that is stood upright before it is pillarboxed into a 16:9 ladder.  A dsv1_pix_format has only positive pitches and a
+ * dsv1_reframe keeps rows as rows, so this is a pass of its own.  Input and output are the tightly packed planar 8-bit frames every
+ * other entry point reads, n in and n out.
+ * DEFINITION.  Every plane on its own, at its own dimensions: input plane I of IH rows of IW samples, output plane O.
+ *   0 NONE        O[y][x] = I[y][x]              IW x IH        4 TRANSPOSE   O[y][x] = I[x][y]              IH x IW
+ *   1 HFLIP       O[y][x] = I[y][IW-1-x]         IW x IH        5 ROT90       O[y][x] = I[IH-1-x][y]         IH x IW   (clockwise)
+ *   2 VFLIP       O[y][x] = I[IH-1-y][x]         IW x IH        6 ROT270      O[y][x] = I[x][IW-1-y]         IH x IW   (90 counter-clockwise)
+ *   3 ROT180      O[y][x] = I[IH-1-y][IW-1-x]    IW x IH        7 TRANSVERSE  O[y][x] = I[IH-1-x][IW-1-y]    IH x IW
+ * The code is a bit set: bit 2 transposes first, bit 0 then mirrors the columns of the result, bit 1 then its rows.  The luma geometry
+ * going out is w x h for codes 0-3 and h x w for codes 4-7 (dsv1_orient_dims).
+ * VALID (dsv1_orient_valid, host only, 1 / 0): the code in 0 .. 7, the subsampling one the library knows, and for codes 4-7 equal
+ * horizontal and vertical chroma shifts -- 4:4:4 and 4:2:0.  With hs == vs the transposed chroma plane of rshift_up(h) x rshift_up(w)
+ * samples is exactly the chroma plane of the h x w output, odd sizes included; at 4:2:2 or 4:1:1 it would be a plane of no subsampling
+ * the codec has: DSVG_ERR_ARG before any device work.  A 4:2:2 source reaches a rotation through the converter's 4:2:2 -> 4:2:0 halving
+ * (dsv1_batch_set_source_format_sub), which runs in front of this pass.  Any w, h >= 1.
+ * CHROMA SITING.  Planes are mirrored independently.  With an odd luma size under subsampling the last chroma sample covers one luma
+ * sample, not two, so a mirror moves the chroma siting by half a chroma sample along that axis.  This is accepted.
+ * HOST HELPERS (no device): dsv1_orient_compose(a, b) is the one code equal to applying a and then b; dsv1_orient_inverse;
+ * dsv1_orient_from_exif maps EXIF orientation tags 1 .. 8 to codes 0, 1, 3, 2, 4, 5, 7, 6; dsv1_orient_from_matrix reads an MP4 /
+ * QuickTime track display matrix, 16.16 fixed point, a = m[0], b = m[1], c = m[3], d = m[4] (m[2], m[5], m[8] and the translation m[6],
+ * m[7] are ignored): the source sample at column p, row q is shown at column a p + c q, row b p + d q.  With b == c == 0, a and d each
+ * +-65536: (+,+) NONE, (-,+) HFLIP, (+,-) VFLIP, (-,-) ROT180.  With a == d == 0, b and c each +-65536, as (b, c): (+,+) TRANSPOSE,
+ * (+,-) ROT90, (-,+) ROT270, (-,-) TRANSVERSE.  Scale, shear and other angles -- and every argument out of range -- are DSVG_ERR_ARG.
+ * dsv1_orient_clip: src and dst host or device memory (on_device), w x h the frames that come in; synchronous; code 0 copies.
+ * SESSIONS.  The pass sits between the noise filter and the reframe: convert -> deinterlace or inverse telecine -> denoise -> orient ->
+ * reframe.  The deinterlacer has to see rows as fields, so it comes first; the reframe's window is chosen on the upright picture, so it
+ * comes after.  dsv1_batch_set_source_orient (plain batches, quality ladders, chain mode): the ORIENTED geometry is the reframe's input,
+ * or the batch's geometry without one; clips then come in at the RAW geometry, dsv1_orient_dims(dsv1_orient_inverse(orient), ...) of
+ * it, and formats and passes set afterwards resolve there.  It changes the geometry those passes are built for, so it may be set,
+ * changed or cleared only with nothing in flight, nothing staged, and no source format, RGB format, deinterlacer, inverse telecine or
+ * noise filter set -- else, and for a code that is not valid at the batch's subsampling, DSVG_ERR_ARG with the setting left as it was.
+ * A reframe is set BEFORE the orientation: dsv1_batch_set_source_reframe is refused while an orientation is set.  Code 0 clears it: no
+ * pass, no copy, no lane.  Clip ownership is dsv1_batch_set_source_format's; dsv1_batch_stage is refused while it is set.
+ * dsv1_resladder_open_oriented is dsv1_resladder_open_reframed with the code: src is the raw geometry handed in; with a reframe,
+ * rf->in_w x in_h must be the oriented geometry; without one the oriented picture stands for the source everywhere behind the chain
+ * (the scaler's source, the ratio check, a geometry "of the source's size", the clip get_src_sse / get_src_ssim measure against).
+ * orient == 0 behaves as dsv1_resladder_open_reframed.
+ * Not offered: the drop-in dsv_enc; orientation in the decoders' output pass; arbitrary angles; transposing 4:2:2 or 4:1:1; one
+ * orientation per source of a batch; an orientation that changes between calls; fusing the pass into the reframe or the frame load. */
+enum { DSV1_ORIENT_NONE, DSV1_ORIENT_HFLIP, DSV1_ORIENT_VFLIP, DSV1_ORIENT_ROT180, DSV1_ORIENT_TRANSPOSE, DSV1_ORIENT_ROT90,
+       DSV1_ORIENT_ROT270, DSV1_ORIENT_TRANSVERSE };
+int  dsv1_orient_valid(int orient, int subsamp);
+int  dsv1_orient_dims(int orient, int w, int h, int *ow, int *oh);
+int  dsv1_orient_compose(int a, int b);
+int  dsv1_orient_inverse(int a);
+int  dsv1_orient_from_exif(int tag);
+int  dsv1_orient_from_matrix(const int32_t m[9]);
+int  dsv1_orient_clip(int device, const void *src, int w, int h, int subsamp, int n, void *dst, int orient, int on_device);
+int  dsv1_batch_set_source_orient(dsv1_batch *b, int orient);                          /* 0 = off */
+int  dsv1_resladder_open_oriented(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *rf, const dsv1_pix_format *pf,
+                                  int src_subsamp, const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device,
+                                  int nsources, int frames_per_call, int filter);
+
 /* ---- extension: debug overlays (csrc/k_drawinfo.hip; stated in Python in tests/_drawinfo.py) ----
  * The reference decoder's -drawinfo (draw_info dsv_decoder.c:147-243), drawn on the device ahead of the output pass: what an encoder
  * decided, on the decoded luma of every picture that has a reference (P pictures; I pictures and chroma are untouched, and so are the
