@@ -66,6 +66,32 @@ class InvStep(_C.Structure):
                 "bytes": self.bytes, "cover": (self.cover, self.cx, self.cy)}
 
 
+FWD_GROUP_STEP = 2                                                                           # DSVG_FWD_GROUP_STEP
+FWD_NO_XCD_ORDER, FWD_NO_MC_FUSION, FWD_NO_LLQ = 1, 2, 4                                     # DSVG_FWD_NO_*
+
+
+class FwdStep(_C.Structure):
+    """dsvg_fwd_step (include/dsvg.h): one launch of the forward transform's plan"""
+    _fields_ = [("kernel", _C.c_int), ("grid", _C.c_int * 3), ("xcd", _C.c_int), ("block", _C.c_int * 2), ("lds", _C.c_uint),
+                ("args", _C.c_int * 4), ("bytes", _C.c_double)]
+
+    def as_dict(self):
+        return {"kernel": lib().dsvg_prof_kernel_name(self.kernel).decode(), "grid": tuple(self.grid), "xcd": self.xcd,
+                "block": tuple(self.block), "lds": self.lds, "args": tuple(self.args), "bytes": self.bytes}
+
+
+class HmeStep(_C.Structure):
+    """dsvg_hme_step (include/dsvg.h): one launch of the motion search's plan"""
+    _fields_ = [("kernel", _C.c_int), ("l0", _C.c_int), ("nkbf", _C.c_int), ("part", _C.c_int), ("level", _C.c_int), ("count", _C.c_int),
+                ("fullx", _C.c_int), ("fully", _C.c_int), ("inv_per", _C.c_uint), ("inv_row", _C.c_uint), ("grid", _C.c_int * 2),
+                ("block", _C.c_int), ("bytes", _C.c_double), ("cont", _C.c_int)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k in ("l0", "nkbf", "part", "level", "count", "fullx", "fully", "inv_per", "inv_row", "block", "bytes", "cont")}
+        d.update(kernel=lib().dsvg_prof_kernel_name(self.kernel).decode(), grid=tuple(self.grid))
+        return d
+
+
 BATCH_NO_SMALL_SPLIT, BATCH_NO_PAR_ENQUEUE, BATCH_NO_LAZY_BORDER, BATCH_NO_MC_FUSION, BATCH_PROFILED = 1, 2, 4, 8, 16      # DSVG_BATCH_*
 
 
@@ -405,6 +431,30 @@ def inv_plan(w, h, fmt, group, isP, with_tail=1, insym=0, patch_kernel=0, fuse_b
     if n < 0:
         _chk(n, "dsvg_inv_plan")
     return [steps[i].as_dict() for i in range(n)], fb.value
+
+
+def fwd_plan(w, h, fmt, group, isP=0, general_whole=0, switches=0, njobs=1):
+    """the forward launches of plane group `group` (0 luma, 1 the chroma pair) of njobs I or P pictures in the frame step of an encoder
+    of this geometry, or (FWD_GROUP_STEP) what the step launches once for all planes, with the A/B switches of the mask `switches`
+    (FWD_NO_*): ([step dicts in launch order], the DSVG_FWD_* mask or -1); needs no device"""
+    L = lib()                                               # (bound here, not in lib(): an A/B build named by DSV1_SO may be older than this query)
+    L.dsvg_fwd_plan.argtypes = [_C.c_int] * 6 + [_C.c_uint, _C.c_int, _C.POINTER(FwdStep), _C.c_int, _C.POINTER(_C.c_int)]
+    steps, mask = (FwdStep * 5)(), _C.c_int(0)
+    n = L.dsvg_fwd_plan(w, h, fmt, group, isP, general_whole, switches, njobs, steps, 5, _C.byref(mask))
+    if n < 0:
+        _chk(n, "dsvg_fwd_plan")
+    return [steps[i].as_dict() for i in range(n)], mask.value
+
+
+def hme_plan(w, h, fmt, npairs=1, csum_table=1):
+    """the launches of the motion search of npairs pairs in an encoder of this geometry: [step dicts in launch order]; needs no device"""
+    L = lib()
+    L.dsvg_hme_plan.argtypes = [_C.c_int] * 5 + [_C.POINTER(HmeStep), _C.c_int]
+    steps = (HmeStep * 14)()
+    n = L.dsvg_hme_plan(w, h, fmt, csum_table, npairs, steps, 14)
+    if n < 0:
+        _chk(n, "dsvg_hme_plan")
+    return [steps[i].as_dict() for i in range(n)]
 
 
 def code_batch_plan(w, h, fmt, n_recon_slots, n_src_slots, max_jobs, out_slots, code_streams, switches, nsteps, njobs, jobs, rc=None):

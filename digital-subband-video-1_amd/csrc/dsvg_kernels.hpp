@@ -39,12 +39,9 @@ struct HmeArgs {
 // k_sbt.hip
 int  sbt_tail_supported(const SbtGeo &g);
 void sbt_set_func_attributes();
-void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, int from_src, Prof *pf = nullptr, int with_tail = 1, int fused = 0,
-                    const struct McGeo *mc = nullptr, const DMV *mvs0 = nullptr,    // mc: motion compensation fused into the P forward transform
-                    int general_whole = 1);   // mc: 0 = the caller knows that no block of these pictures is intra (the general kernel then only runs on the strips of the grid the geometry asks for)
 bool mc_fusable(const struct McGeo &MG);
-// the decisions of launch_fwd_sbt (general kernel: a mask of DSVG_FWD_*) and launch_hme (per level; csum: see dsvg_dispatch), as
-// functions of the geometry alone, and where the launchers note what they last decided (dsvg_dispatch_last / dsvg_dispatch_plan)
+// the decisions behind the forward plan (general kernel: a mask of DSVG_FWD_*) and the motion search's (per level; csum: see
+// dsvg_dispatch), as functions of the geometry alone, and where the executors note what the plans said (dsvg_dispatch_last)
 int  fwd_general_mask(const SbtGeo3 &G, const struct McGeo &mc, int c0, int npl, int general_whole);
 struct HmeLevelPlan { int nkbf, fullx, fully, nfull, nrest, parts; };
 HmeLevelPlan hme_level_plan(const struct HmeArgs &A, int level);
@@ -52,7 +49,7 @@ int  hme_csum_plan(const struct HmeArgs &A, int *fullx, int *fully);
 void dispatch_note_fwd(int group, int mask);
 void dispatch_note_hme(const struct HmeArgs &A, int level, const HmeLevelPlan &P);
 void dispatch_note_csum(int csum);
-void dispatch_note_threads(int tail, int scan);      // the workgroup sizes launch_tail_q / the k_hz_scan launch took (0: not this one)
+void dispatch_note_threads(int tail, int scan);      // the workgroup sizes the k_tail_q step / the k_hz_scan launch took (0: not this one)
 // The inverse transform of planes [c0, c0+npl) of njobs pictures (all P or all I) as a pure function of the geometry, the caller's
 // flags and the A/B switches: every launch in order, decided once.  launch_inv_plan runs a plan and decides nothing; the border
 // question of enqueue_recon (InvPlan.fb) and the device-free query dsvg_inv_plan read the same plan.
@@ -79,9 +76,30 @@ void launch_inv_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3
                     int insym = 0, int patch_kernel = 0,    // patch_kernel: sparse P pictures (flags valid, prediction given): unfiltered planes take k_inv_patch_c
                     int fuse_border = 0);                   // the kernels also write the reconstruction's border (JobDev.ext) where the plan says they can (InvPlan.fb)
 void launch_inv54_all(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, Prof *pf = nullptr);   // levels 5..4 of all planes: then launch_inv_sbt(.., with_tail | 2)
-void launch_sbt_tail(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int inverse, Prof *pf = nullptr);
-void launch_fwd_mid4(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, bool llq, Prof *pf = nullptr);   // levels 4..5: launch_fwd_sbt does it itself unless fused >= 3
-void launch_tail_q(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, Prof *pf = nullptr);   // fused >= 2 pictures: forward tail + LL quantiser + inverse tail
+InvPlan inv_tail_plan(const SbtGeo3 &G, int njobs, int c0, int npl);        // the LDS tails of planes [c0, c0+npl) of all jobs in one launch
+// The forward transform of planes [c0, c0+npl) of njobs pictures (all P or all I) the same way: fwd_sbt_plan decides every launch
+// of a plane group, fwd_step_plan the launches a frame step makes once for all planes and jobs (levels 4..5, then the LDS tail --
+// with the LL quantiser and the inverse tail where llq); launch_fwd_plan runs a plan and decides nothing.  A step is an InvStep
+// (cover unused); a: from_src | the general kernel's bxofs, byofs, bxstep, bystep | k_fwd_haar_mid<4>: the LL quantiser.
+typedef InvStep FwdStep;
+struct FwdPlan {
+    int n;
+    FwdStep s[5];
+    bool report;             // a P plane group: the executor reports mask (dispatch_note_fwd)
+    int mask;                // DSVG_FWD_*: where the general kernel goes; -1: motion compensation is not fused
+};
+struct FwdOpts {
+    bool quantise;           // the kernels quantise and write symbol planes (the encoder), not int32 coefficients
+    bool llq;                // own_mid4: k_fwd_haar_mid<4> quantises the LL region (JobDev.llq set by the caller)
+    bool own_mid4, own_tail; // levels 4..5 / the LDS tail are this plane group's own launches, not the frame step's (fwd_step_plan)
+};
+// mc: motion compensation fused into the P forward transform; general_whole = 0: the caller knows that no block of these pictures
+// is intra (the general kernel then only runs on the strips of the grid the geometry asks for); plain: DSV1_NO_XCD_ORDER
+FwdPlan fwd_sbt_plan(const SbtGeo3 &G, int njobs, int c0, int npl, int isP, int from_src, const FwdOpts &o, const struct McGeo *mc, int general_whole, bool plain);
+FwdPlan fwd_step_plan(const SbtGeo3 &G, int njobs, bool llq);
+void launch_fwd_plan(hipStream_t st, const JobDev *jobs, const SbtGeo3 &G, int c0, int npl, const FwdPlan &P, Prof *pf, const struct McGeo *mc = nullptr, const DMV *mvs0 = nullptr);
+void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, int from_src, const FwdOpts &o, Prof *pf = nullptr,
+                    const struct McGeo *mc = nullptr, const DMV *mvs0 = nullptr, int general_whole = 1);
 // k_hzcc.hip
 void launch_hz_encode(hipStream_t st, const JobDev *jobs, int njobs, int job_chunks, Prof *pf = nullptr, double samples = 0,
                       int nplain = -1, int ll_chunks = 1);
@@ -164,5 +182,24 @@ void launch_scale_slots(hipStream_t st, const ScaleGeo &G, const uint8_t *slab, 
 // (nblk = ceil(w / bw) * ceil(h / bh)); two launches in stream order, every store inside the plane
 void launch_drawinfo(hipStream_t st, uint8_t *luma0, size_t pic_pitch, int w, int h, int stride, int bw, int bh, int mode,
                      const DMV *mvs, const uint8_t *stable, int n);
-// k_hme.hip
+// k_hme.hip: the motion search of npairs pairs as a plan of the geometry fields of HmeArgs and of whether it has the chroma table:
+// k_hme_csum if any, the one or two k_hme_level launches of every level from the top down, k_hme_detail.  launch_hme_plan runs it.
+struct HmeStep {
+    int kid;                         // KID_HME_*
+    int l0, nkbf, part;              // k_hme_level<L0, NKBF, PART>
+    int level, cnt;                  // the level and its blocks per pair in this launch (nfull / nrest / nvx * nvy)
+    int fullx, fully;                // k_hme_level, k_hme_csum
+    unsigned inv_per, inv_row;       // min(floor(2^32 / d), 2^32 - 1) of cnt and of the row length the block index is split by
+    int gx, gy, bx;                  // the grid (k_hme_level: gx workgroups, launched as xcd_grid(gx)) and the block
+    double bytes;                    // the algorithmic bytes of Prof::begin (0 where cont)
+    bool cont;                       // no bracket of its own: the launch continues the previous step's (level 0's PART 2)
+};
+struct HmePlan {
+    int n;
+    HmeStep s[2 * 6 + 2];            // (six levels, as HmeArgs.L)
+    int levels, csum;                // what the executor reports (dispatch_note_*), with lv[0..levels]
+    HmeLevelPlan lv[6];
+};
+HmePlan hme_plan(const HmeArgs &A, int npairs, bool table);
+void launch_hme_plan(hipStream_t st, const HmeArgs &A, int npairs, const HmePlan &P, Prof *pf = nullptr);
 void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf = nullptr);

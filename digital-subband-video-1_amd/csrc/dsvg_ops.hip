@@ -126,7 +126,8 @@ extern "C" int dsvg_op_fwd_sbt(const dsvg_plane *src, dsvg_coefs *dst, int isP)
     HIPCHK(hipMemcpyAsync(djb, &jb, sizeof(jb), hipMemcpyHostToDevice, S.st));
     SbtGeo3 G; memset(&G, 0, sizeof(G));
     make_sbt_geo(G.g[0], W, H, src->w, ph, dstride, 0, 0, 0, 0);
-    launch_fwd_sbt(S.st, djb, 1, G, 0, 1, isP, 0);
+    const FwdOpts whole = { /* quantise */ false, /* llq */ false, /* own_mid4 */ true, /* own_tail */ true };   // int32 coefficients of every level
+    launch_fwd_sbt(S.st, djb, 1, G, 0, 1, isP, 0, whole);
     HIPCHK(hipMemcpyAsync(dst->data, dco, (size_t)W * H * 4, hipMemcpyDeviceToHost, S.st));
     return S.sync();
 }

@@ -143,6 +143,7 @@ struct dsvg_ctx {
     hipEvent_t ev_mark[2] = {nullptr, nullptr};     // dsvg_ctx_mark
     int w = 0, h = 0, fmt = 0, bw = 0, bh = 0, nbh = 0, nbv = 0, nblk = 0, levels = 0;
     FrameLayout L[6];
+    HmeArgs hme;                     // the motion search's arguments, geometry half (make_hme_geo)
     CoefLayout CL;
     SbtGeo3 G;
     McGeo MG;
@@ -522,6 +523,20 @@ static void make_ctx_geo(CtxGeo &o, int width, int height, int subsamp, int blk_
     }
 }
 
+// The geometry half of the motion search's arguments -- all that hme_plan reads -- of a context of these tables: the pyramid's depth
+// (pyramid_levels = 0: the encoder's own) and its levels' layouts.  The context keeps it (dsvg_ctx.hme: dsvg_analyse adds the pointers);
+// dsvg_dispatch_plan and dsvg_hme_plan ask the plan about the same record.
+static void make_hme_geo(HmeArgs &A, const CtxGeo &geo, int width, int height, int subsamp, int pyramid_levels = 0)
+{
+    memset(&A, 0, sizeof(A));
+    A.levels = pyramid_levels > 0 ? std::min(pyramid_levels, DSVG_MAX_PYRAMID) : auto_pyramid_levels(width, height, geo.nbh, geo.nbv);
+    A.L[0] = geo.L;
+    for (int l = 1; l <= A.levels; l++) make_frame_layout(A.L[l], subsamp, rsu(width, l), rsu(height, l));
+    A.nxb = geo.nbh; A.nyb = geo.nbv; A.nblk = geo.nbh * geo.nbv; A.blk_w = geo.bw; A.blk_h = geo.bh;
+}
+// how the encoder's frame step calls the forward transform of a plane group: quantised, levels 4..5 and the tail launched once per step
+static const FwdOpts FWD_FRAME_STEP = { /* quantise */ true, /* llq */ false, /* own_mid4 */ false, /* own_tail */ false };
+
 // What dsvg_ctx_create (encoder block size) answers for a geometry, without a device: the resolution ladder refuses a geometry before
 // it allocates anything (dsv1_resladder_open).  The same checks, in the same order, as the context creation below.
 static int geom_check(int width, int height, int subsamp, CtxGeo &geo)
@@ -571,21 +586,18 @@ extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispa
     if (rc) return rc;
     memset(out, 0, sizeof(*out));
     out->blk_w = geo.bw; out->blk_h = geo.bh;
-    HmeArgs A; memset(&A, 0, sizeof(A));
-    A.levels = auto_pyramid_levels(width, height, geo.nbh, geo.nbv);
-    A.L[0] = geo.L;
-    for (int l = 1; l <= A.levels; l++) make_frame_layout(A.L[l], subsamp, rsu(width, l), rsu(height, l));
-    A.nxb = geo.nbh; A.nyb = geo.nbv; A.nblk = geo.nbh * geo.nbv; A.blk_w = geo.bw; A.blk_h = geo.bh;
     out->fusable = mc_fusable(geo.MG) ? 1 : 0;
     // (code_batch_impl passes general_whole from the pictures' intra blocks; with FWD_FAST_INTRA it does not enter the decision)
-    for (int g = 0; g < 2; g++) out->fwd[g] = out->fusable ? fwd_general_mask(geo.G, geo.MG, g ? 1 : 0, g ? 2 : 1, 0) : -1;
-    out->hme_levels = A.levels;
-    for (int l = 0; l <= A.levels; l++) {
-        const HmeLevelPlan P = hme_level_plan(A, l);
+    for (int g = 0; g < 2; g++) out->fwd[g] = fwd_sbt_plan(geo.G, 1, g ? 1 : 0, g ? 2 : 1, 1, 0, FWD_FRAME_STEP, out->fusable ? &geo.MG : nullptr, 0, false).mask;
+    HmeArgs A;
+    make_hme_geo(A, geo, width, height, subsamp);
+    const HmePlan H = hme_plan(A, 1, true);
+    out->hme_levels = H.levels;
+    for (int l = 0; l <= H.levels; l++) {
+        const HmeLevelPlan &P = H.lv[l];
         out->hme[l][0] = P.nkbf; out->hme[l][1] = P.fullx; out->hme[l][2] = P.fully; out->hme[l][3] = P.parts;
     }
-    int fullx, fully;
-    out->csum = hme_csum_plan(A, &fullx, &fully);
+    out->csum = H.csum;
     out->tail_threads = out->scan_threads = -1;      // (a function of the jobs per launch, not of the geometry)
     return DSVG_OK;
 }
@@ -612,6 +624,53 @@ extern "C" int dsvg_inv_plan(int width, int height, int subsamp, int group, int 
         o.cover = s.cover; o.cx = s.cx; o.cy = s.cy;
     }
     if (fb) *fb = P.fb;
+    return P.n;
+}
+
+// The forward plans of an encoder context of this geometry (include/dsvg.h): fwd_sbt_plan as enqueue_group asks it for a plane group of
+// njobs I or P pictures, or fwd_step_plan, on the context's geometry tables, with the switches the caller names instead of the environment's
+extern "C" int dsvg_fwd_plan(int width, int height, int subsamp, int group, int isP, int general_whole, unsigned switches, int njobs,
+                             dsvg_fwd_step *steps, int cap, int *mask)
+{
+    if (group < 0 || group > DSVG_FWD_GROUP_STEP || njobs < 1 || cap < 0 || (cap > 0 && !steps)) { dsvg_set_error("bad fwd_plan arguments"); return DSVG_ERR_ARG; }
+    CtxGeo geo;
+    const int rc = geom_check(width, height, subsamp, geo);
+    if (rc) return rc;
+    const bool fused = mc_fusable(geo.MG) && !(switches & DSVG_FWD_NO_MC_FUSION);
+    const FwdPlan P = group == DSVG_FWD_GROUP_STEP ? fwd_step_plan(geo.G, njobs, !(switches & DSVG_FWD_NO_LLQ))
+                                                   : fwd_sbt_plan(geo.G, njobs, group ? 1 : 0, group ? 2 : 1, isP, !isP, FWD_FRAME_STEP, fused ? &geo.MG : nullptr,
+                                                                  general_whole, (switches & DSVG_FWD_NO_XCD_ORDER) != 0);
+    for (int i = 0; i < P.n && i < cap; i++) {
+        const FwdStep &s = P.s[i];
+        dsvg_fwd_step &o = steps[i];
+        o.kernel = s.kid;
+        o.grid[0] = s.gx; o.grid[1] = s.gy; o.grid[2] = s.gz; o.xcd = s.xcd ? (s.plain ? 2 : 1) : 0;
+        o.block[0] = s.bx; o.block[1] = s.by; o.lds = (unsigned)s.lds;
+        for (int k = 0; k < 4; k++) o.args[k] = s.a[k];
+        o.bytes = s.bytes;
+    }
+    if (mask) *mask = P.mask;
+    return P.n;
+}
+
+// The motion search's plan for npairs pairs of such a context (default pyramid depth), with or without the chroma table
+extern "C" int dsvg_hme_plan(int width, int height, int subsamp, int csum_table, int npairs, dsvg_hme_step *steps, int cap)
+{
+    if (npairs < 1 || cap < 0 || (cap > 0 && !steps)) { dsvg_set_error("bad hme_plan arguments"); return DSVG_ERR_ARG; }
+    CtxGeo geo;
+    const int rc = geom_check(width, height, subsamp, geo);
+    if (rc) return rc;
+    HmeArgs A;
+    make_hme_geo(A, geo, width, height, subsamp);
+    const HmePlan P = hme_plan(A, npairs, csum_table != 0);
+    for (int i = 0; i < P.n && i < cap; i++) {
+        const HmeStep &s = P.s[i];
+        dsvg_hme_step &o = steps[i];
+        o.kernel = s.kid; o.l0 = s.l0; o.nkbf = s.nkbf; o.part = s.part;
+        o.level = s.level; o.count = s.cnt; o.fullx = s.fullx; o.fully = s.fully; o.inv_per = s.inv_per; o.inv_row = s.inv_row;
+        o.grid[0] = s.gx; o.grid[1] = s.gy; o.block = s.bx;
+        o.bytes = s.bytes; o.cont = s.cont;
+    }
     return P.n;
 }
 
@@ -643,14 +702,15 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         make_ctx_geo(geo, width, height, subsamp, blk_w, blk_h);
         c->bw = geo.bw; c->bh = geo.bh; c->nbh = geo.nbh; c->nbv = geo.nbv;
         c->L[0] = geo.L; c->CL = geo.CL; c->G = geo.G; c->MG = geo.MG;
+        make_hme_geo(c->hme, geo, width, height, subsamp, pyramid_levels);
+        c->levels = c->hme.levels;
+        for (int l = 1; l <= c->levels; l++) c->L[l] = c->hme.L[l];
         c->bgeo = batch_geo(geo, n_src_slots, n_recon_slots, max_jobs, out_slots, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_LAZY_BORDER"));
     }
     out_slots = c->bgeo.out_slots;                          // (at least max_jobs)
     c->n_src = n_src_slots; c->n_recon = n_recon_slots; c->max_jobs = max_jobs; c->out_slots = out_slots;
     c->nwin = (out_slots + max_jobs - 1) / max_jobs + 1;
     c->nblk = c->nbh * c->nbv;
-    c->levels = pyramid_levels > 0 ? std::min(pyramid_levels, DSVG_MAX_PYRAMID) : auto_pyramid_levels(width, height, c->nbh, c->nbv);
-    for (int l = 1; l <= c->levels; l++) make_frame_layout(c->L[l], subsamp, rsu(width, l), rsu(height, l));
     const CoefLayout &CL = c->CL;
     for (int p = 0; p < 3; p++)
         if (!sbt_tail_supported(c->G.g[p])) {
@@ -1260,14 +1320,13 @@ extern "C" int dsvg_analyse(dsvg_ctx *c, int npairs, const int *cur_slots, const
     const size_t per = (size_t)(c->levels + 1) * c->nblk;
     // (every vector a later level, k_hme_detail or the copy below reads is written by the launch of its level -- blocks beyond a
     // pyramid level's frame write their zero vector themselves: no clearing of the field, 116 MB per 320-GOP step through a slow fill)
-    HmeArgs A; memset(&A, 0, sizeof(A));
-    for (int l = 0; l <= c->levels; l++) { A.L[l] = c->L[l]; A.slab[l] = c->src[l].p; }
+    HmeArgs A = c->hme;
+    for (int l = 0; l <= c->levels; l++) A.slab[l] = c->src[l].p;
     A.cur_slots = c->slots_d; A.ref_slots = c->slots_d + c->out_slots;
     A.slot_cu = c->slot_cu_d; A.slot_cv = c->slot_cv_d; A.slot_cs = c->slot_cs_d;
     A.slot_y = c->ydirect_ok ? c->slot_y_d : nullptr; A.deep_r = c->deep_r;
     A.mvf = c->mvf; A.aux_tex = c->aux_tex; A.aux_var = c->aux_var;
     A.csum = getenv("DSV1_NO_CHROMA_SUMS") ? nullptr : c->csum;
-    A.levels = c->levels; A.nxb = c->nbh; A.nyb = c->nbv; A.nblk = c->nblk; A.blk_w = c->bw; A.blk_h = c->bh;
     tl_mark(c, c->st_a, "hme0");
     launch_hme(c->st_a, A, npairs, &c->prof);
     tl_mark(c, c->st_a, "hme1");
@@ -1322,7 +1381,7 @@ static int enqueue_recon(dsvg_ctx *c, int nI, int n, int d0 = 0, int insym = 0, 
 {
     if (!st) st = c->st;
     const JobDev *jd = c->jobs_d + d0;
-    if (!tail_done) launch_sbt_tail(st, jd, n, c->G, 0, 3, 1, &c->prof);      // all planes, I and P jobs alike (encoder with llq: k_tail_q did it)
+    if (!tail_done) launch_inv_plan(st, jd, c->G, 0, 3, inv_tail_plan(c->G, n, 0, 3), &c->prof);      // all planes, I and P jobs alike (encoder with llq: k_tail_q did it)
     // levels 5..4 of every plane of every job (I and P alike) in ONE launch (round 4: up to three launches less per frame step)
     static const bool no54all = getenv("DSV1_NO_INV54_ALL") != nullptr;       // (A/B)
     const int wt = no54all ? 0 : 2;
@@ -1375,10 +1434,10 @@ static int enqueue_group(dsvg_ctx *c, const BatchPlan &P, const dsvg_rc_job *rcj
         const int d0 = base + t * njobs + k0;
         const int nI = std::min(std::max(P.nI[t] - k0, 0), n);                      // I jobs among them come first
         const JobDev *jd = c->jobs_d + d0;
-        const int fz = c->llq ? 4 : 3;                                              // fused quantiser (4: the LL region's too); levels 4..5 launched once below
+        const FwdOpts &fq = FWD_FRAME_STEP;                                         // quantised; levels 4..5 and the tail launched once below
         if (nI > 0) {
-            launch_fwd_sbt(st, jd, nI, c->G, 0, 1, 0, 1, &c->prof, 0, fz);
-            launch_fwd_sbt(st, jd, nI, c->G, 1, 2, 0, 1, &c->prof, 0, fz);
+            launch_fwd_sbt(st, jd, nI, c->G, 0, 1, 0, 1, fq, &c->prof);
+            launch_fwd_sbt(st, jd, nI, c->G, 1, 2, 0, 1, fq, &c->prof);
         }
         if (n > nI) {
             const int nP = n - nI;
@@ -1387,21 +1446,19 @@ static int enqueue_group(dsvg_ctx *c, const BatchPlan &P, const dsvg_rc_job *rcj
                 // inter blocks are predicted inside the forward transform; k_mc only serves the intra blocks (block means)
                 if (P.icnt[NG * t + g]) launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0, c->ilist_d + (size_t)base * c->nblk + P.ioff[NG * t + g], P.icnt[NG * t + g]);
                 const int gw = P.icnt[NG * t + g] || !P.noint[NG * t + g];      // intra blocks somewhere in these pictures (or not known)
-                launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, &c->prof, 0, fz, &c->MG, mv0, gw);
-                launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, &c->prof, 0, fz, &c->MG, mv0, gw);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, fq, &c->prof, &c->MG, mv0, gw);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, fq, &c->prof, &c->MG, mv0, gw);
             } else {
                 launch_mc(st, jd + nI, nP, c->MG, 1, &c->prof, mv0);
-                launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, &c->prof, 0, fz);
-                launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, &c->prof, 0, fz);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 0, 1, 1, 0, fq, &c->prof);
+                launch_fwd_sbt(st, jd + nI, nP, c->G, 1, 2, 1, 0, fq, &c->prof);
             }
         }
         // levels >= 6 in LDS; the LL quantiser (inside the tail kernel and k_fwd_haar_mid<4> when llq, else k_hz_quant<true>);
         // then the reconstruction (P pictures: straight from the symbol planes), then the entropy stage:
         // k_hz_collect* is the LAST reader of the sparse symbol planes and clears what it reads
-        launch_fwd_mid4(st, jd, n, c->G, 0, 3, c->llq, &c->prof);                  // levels 4..5 of all planes, I and P jobs alike
-        if (c->llq) launch_tail_q(st, jd, n, c->G, 0, 3, &c->prof);
-        else {
-            launch_sbt_tail(st, jd, n, c->G, 0, 3, 0, &c->prof);
+        launch_fwd_plan(st, jd, c->G, 0, 3, fwd_step_plan(c->G, n, c->llq), &c->prof);   // levels 4..5, tail: all planes, I and P jobs alike
+        if (!c->llq) {
             launch_hz_quant(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0,
                             (c->CL.w3[0] * c->CL.h3[0] + HZ_CHUNK - 1) / HZ_CHUNK);
         }

@@ -1490,51 +1490,85 @@ HmeLevelPlan hme_level_plan(const HmeArgs &A, int level)
     return P;
 }
 
-void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf)
+// The motion search of npairs pairs, every launch in order: what hme_csum_plan and hme_level_plan decide, with the grids and figures
+// (table: the search has the chroma table, HmeArgs.csum)
+HmePlan hme_plan(const HmeArgs &A, int npairs, bool table)
 {
-    int csum = 0;
-    if (A.csum) {
-        // (full level-0 blocks, as the level loop below defines them)
+    HmePlan P;
+    memset(&P, 0, sizeof(P));
+    P.levels = A.levels;
+    const double cpx = (double)A.L[0].w[1] * A.L[0].h[1] + (double)A.L[0].w[2] * A.L[0].h[2];      // a frame's chroma planes
+    if (table) {
         int fullx, fully;
-        csum = hme_csum_plan(A, &fullx, &fully);
-        if (csum) {
-            if (pf) pf->begin(st, KID_HME_CSUM, (double)npairs * ((double)A.L[0].w[1] * A.L[0].h[1] + (double)A.L[0].w[2] * A.L[0].h[2]));      // every frame's chroma once
-            hipLaunchKernelGGL(k_hme_csum, dim3(fully, 2 * npairs), dim3(256), 0, st, A, fullx, fully);
-            if (pf) pf->end(st);
+        P.csum = hme_csum_plan(A, &fullx, &fully);
+        if (P.csum) {
+            HmeStep &s = P.s[P.n++];
+            s.kid = KID_HME_CSUM; s.fullx = fullx; s.fully = fully; s.gx = fully; s.gy = 2 * npairs; s.bx = 256;
+            s.bytes = (double)npairs * cpx;                                                        // every frame's chroma once
         }
     }
-    dispatch_note_csum(csum);
+    const auto uinv = [](int d) { return (unsigned)std::min<unsigned long long>(0x100000000ull / (unsigned long long)std::max(d, 1), 0xffffffffull); };
     for (int level = A.levels; level >= 0; level--) {
         const int step = 1 << level;
         const int nvx = (A.nxb + step - 1) / step, nvy = (A.nyb + step - 1) / step;
         double px = 2.0 * npairs * (double)A.L[level].w[0] * A.L[level].h[0];           // src + ref luma once
-        if (level == 0 && !A.csum)  // level 0 also reads both frames' chroma planes (c_maxvar hme.c:269-300,669-681) unless k_hme_csum has read them
-            px += 2.0 * npairs * ((double)A.L[0].w[1] * A.L[0].h[1] + (double)A.L[0].w[2] * A.L[0].h[2]);
-        if (pf) pf->begin(st, level > 0 ? KID_HME_LEVEL : KID_HME_LEVEL0, px);
-        const dim3 blk(NT * HME_WPG);
-        const HmeLevelPlan lp = hme_level_plan(A, level);
-        dispatch_note_hme(A, level, lp);
-        const int nkbf = lp.nkbf, fullx = lp.fullx, fully = lp.fully, nfull = lp.nfull, nrest = lp.nrest;
-        auto uinv = [](int d) { return (unsigned)std::min<unsigned long long>(0x100000000ull / (unsigned long long)std::max(d, 1), 0xffffffffull); };
+        if (level == 0 && !table)   // level 0 also reads both frames' chroma planes (c_maxvar hme.c:269-300,669-681) unless k_hme_csum has read them
+            px += 2.0 * npairs * cpx;
+        const HmeLevelPlan lp = P.lv[level] = hme_level_plan(A, level);
+        // one launch of cnt blocks per pair for every PART the level's plan names; the launches of a level share one bracket
         // (inv_row: the row length the launch's block index is split by -- PART 1: fullx; PART 0 / 3: nvx; PART 2 divides by its two strip widths itself)
-#define HME_LAUNCH(L0, N, P, cnt) hipLaunchKernelGGL((k_hme_level<L0, N, P>), dim3(xcd_grid(((cnt) * npairs + HME_WPG - 1) / HME_WPG)), blk, 0, st, A, level, npairs, fullx, fully, \
-                                                     uinv(cnt), uinv((P) == 1 ? fullx : nvx))
-#define HME_FULL(L0) do { switch (nkbf) { case 16: HME_LAUNCH(L0, 16, 1, nfull); break; case 12: HME_LAUNCH(L0, 12, 1, nfull); break; \
-                                          default: HME_LAUNCH(L0, 8, 1, nfull); } } while (0)
-        // (the branches below are the ones hme_level_plan names in its `parts`)
-        if (nfull > 0 && level > 0) {
-            switch (nkbf) { case 16: HME_LAUNCH(false, 16, 3, nvx * nvy); break; case 12: HME_LAUNCH(false, 12, 3, nvx * nvy); break;
-                            default: HME_LAUNCH(false, 8, 3, nvx * nvy); }
-        } else if (nfull > 0) {
-            HME_FULL(true);
-            if (nrest > 0) HME_LAUNCH(true, 0, 2, nrest);
-        } else if (level > 0) HME_LAUNCH(false, 0, 0, nvx * nvy);
-        else HME_LAUNCH(true, 0, 0, nvx * nvy);
-        if (pf) pf->end(st);
+        bool cont = false;
+        const auto launch = [&](int part, int nkbf, int cnt) {
+            HmeStep &s = P.s[P.n++];
+            s.kid = level > 0 ? KID_HME_LEVEL : KID_HME_LEVEL0; s.l0 = level == 0; s.nkbf = nkbf; s.part = part;
+            s.level = level; s.cnt = cnt; s.fullx = lp.fullx; s.fully = lp.fully;
+            s.inv_per = uinv(cnt); s.inv_row = uinv(part == 1 ? lp.fullx : nvx);
+            s.gx = (cnt * npairs + HME_WPG - 1) / HME_WPG; s.gy = 1; s.bx = NT * HME_WPG;
+            s.bytes = cont ? 0.0 : px; s.cont = cont; cont = true;
+        };
+        if (lp.parts & 1 << 3) launch(3, lp.nkbf, nvx * nvy);
+        if (lp.parts & 1 << 1) launch(1, lp.nkbf, lp.nfull);
+        if (lp.parts & 1 << 2) launch(2, 0, lp.nrest);
+        if (lp.parts & 1 << 0) launch(0, 0, nvx * nvy);
     }
-    if (pf) pf->begin(st, KID_HME_DETAIL, 0.0);
-    hipLaunchKernelGGL(k_hme_detail, dim3((A.nblk + 255) / 256, npairs), dim3(256), 0, st, A);
-    if (pf) pf->end(st);
+    HmeStep &s = P.s[P.n++];
+    s.kid = KID_HME_DETAIL; s.gx = (A.nblk + 255) / 256; s.gy = npairs; s.bx = 256;
+    return P;
+}
+
+// run a plan: one launch per step, each instance of k_hme_level named here and nowhere else
+void launch_hme_plan(hipStream_t st, const HmeArgs &A, int npairs, const HmePlan &P, Prof *pf)
+{
+#define HME_KEY(L0, N, PART) (((L0) ? 256 : 0) | (N) << 2 | (PART))
+#define HME_LEVEL(L0, N, PART) case HME_KEY(L0, N, PART): \
+    hipLaunchKernelGGL((k_hme_level<L0, N, PART>), dim3(xcd_grid(s.gx)), dim3(s.bx), 0, st, A, s.level, npairs, s.fullx, s.fully, s.inv_per, s.inv_row); break
+    dispatch_note_csum(P.csum);
+    for (int l = 0; l <= P.levels; l++) dispatch_note_hme(A, l, P.lv[l]);
+    for (int i = 0; i < P.n; i++) {
+        const HmeStep &s = P.s[i];
+        if (pf && !s.cont) pf->begin(st, s.kid, s.bytes);
+        if (s.kid == KID_HME_CSUM) hipLaunchKernelGGL(k_hme_csum, dim3(s.gx, s.gy), dim3(s.bx), 0, st, A, s.fullx, s.fully);
+        else if (s.kid == KID_HME_DETAIL) hipLaunchKernelGGL(k_hme_detail, dim3(s.gx, s.gy), dim3(s.bx), 0, st, A);
+        else switch (HME_KEY(s.l0, s.nkbf, s.part)) {
+            HME_LEVEL(false, 16, 3);
+            HME_LEVEL(false, 12, 3);
+            HME_LEVEL(false, 8, 3);
+            HME_LEVEL(true, 16, 1);
+            HME_LEVEL(true, 12, 1);
+            HME_LEVEL(true, 8, 1);
+            HME_LEVEL(true, 0, 2);
+            HME_LEVEL(false, 0, 0);
+            HME_LEVEL(true, 0, 0);
+        }
+        if (pf && !(i + 1 < P.n && P.s[i + 1].cont)) pf->end(st);
+    }
+#undef HME_KEY
+#undef HME_LEVEL
+}
+
+void launch_hme(hipStream_t st, const HmeArgs &A, int npairs, Prof *pf)
+{
+    launch_hme_plan(st, A, npairs, hme_plan(A, npairs, A.csum != nullptr), pf);
 }
 
 #ifdef DSVG_CLOCK_PROBE

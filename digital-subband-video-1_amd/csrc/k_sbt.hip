@@ -3270,7 +3270,7 @@ bool mc_fusable(const McGeo &MG)
 
 // levels 4..5 (LL3 -> LL5) of planes [c0, c0+npl) of njobs jobs in one launch (the grid is sized for the largest plane; the
 // threads of a smaller plane beyond its band leave at once); llq: with the LL quantiser
-void launch_fwd_mid4(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, bool llq, Prof *pf)
+static void mid4_step(FwdStep &s, const SbtGeo3 &G, int njobs, int c0, int npl, bool llq)
 {
     int w5 = 1, h5 = 1;
     double s3 = 0;
@@ -3278,13 +3278,23 @@ void launch_fwd_mid4(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo
         w5 = std::max(w5, G.g[c].w5); h5 = std::max(h5, G.g[c].h5);
         s3 += (double)G.g[c].w3 * G.g[c].h3 * njobs;
     }
-    PB(KID_FWD_HAAR_MID4, s3 * 8.0);
-    if (llq) hipLaunchKernelGGL((k_fwd_haar_mid<4, false, true>), grid3(w5, h5, njobs * npl), dim3(64, 4), 0, st, jobs, G, c0, npl);
-    else     hipLaunchKernelGGL((k_fwd_haar_mid<4, false>), grid3(w5, h5, njobs * npl), dim3(64, 4), 0, st, jobs, G, c0, npl);
-    PE();
+    const dim3 gr = grid3(w5, h5, njobs * npl);
+    s.kid = KID_FWD_HAAR_MID4; s.gx = gr.x; s.gy = gr.y; s.gz = gr.z; s.bx = 64; s.by = 4; s.a[0] = llq; s.bytes = s3 * 8.0;
 }
 
-// Where launch_fwd_sbt sends the general kernel of planes [c0, c0+npl) of a P picture: a mask of DSVG_FWD_* (include/dsvg.h)
+// the LDS tails (k_fwd_tail, k_inv_tail, k_tail_q) of planes [c0, c0+npl) of all jobs in ONE launch (dynamic LDS sized for the largest plane)
+static void tail_step(InvStep &s, int kid, const SbtGeo3 &G, int njobs, int c0, int npl, int threads = TAIL_THREADS)
+{
+    size_t lds = 0;
+    double s5 = 0;
+    for (int c = c0; c < c0 + npl; c++) {
+        lds = std::max(lds, (size_t)G.g[c].w5 * G.g[c].h5 * 4);
+        s5 += (double)G.g[c].w5 * G.g[c].h5 * njobs;
+    }
+    s.kid = kid; s.gx = njobs * npl; s.gy = s.gz = 1; s.bx = threads; s.by = 1; s.lds = lds; s.bytes = s5 * 8.0;
+}
+
+// Where fwd_sbt_plan sends the general kernel of planes [c0, c0+npl) of a P picture: a mask of DSVG_FWD_* (include/dsvg.h)
 int fwd_general_mask(const SbtGeo3 &G, const McGeo &mc, int c0, int npl, int general_whole)
 {
     bool whole = general_whole != 0 && !FWD_FAST_INTRA, top = false, bottom = false, left = false, right = false;
@@ -3305,107 +3315,125 @@ int fwd_general_mask(const SbtGeo3 &G, const McGeo &mc, int c0, int npl, int gen
            (right ? DSVG_FWD_RIGHT : 0) | (full.y == 1 ? DSVG_FWD_ROW1 : 0) | (full.x == 1 ? DSVG_FWD_COL1 : 0);
 }
 
-void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP,
-                    int from_src, Prof *pf, int with_tail, int fused, const McGeo *mc, const DMV *mvs0, int general_whole)
+FwdPlan fwd_sbt_plan(const SbtGeo3 &G, int njobs, int c0, int npl, int isP, int from_src, const FwdOpts &o, const McGeo *mc, int general_whole, bool plain)
 {
+    FwdPlan P;
+    memset(&P, 0, sizeof(P));
     const SbtGeo &g = G.g[c0];
     const int nz = njobs * npl;
-    const double smp = (double)g.W * g.H * nz, s3 = (double)g.w3 * g.h3 * nz;
-    const bool llq = fused == 2 || fused == 4;       // the LL quantiser in k_fwd_haar_mid<4> (JobDev.llq set by the caller)
-    if (isP && fused && mc) {
+    const double smp = (double)g.W * g.H * nz;
+    const dim3 full = grid3(g.w3, g.h3, nz);
+    const bool q = o.quantise;
+    // a gx x gy x nz grid of 64 x 4 threads
+    const auto step = [&](int kid, int gx, int gy, double bytes) -> FwdStep & {
+        FwdStep &s = P.s[P.n++];
+        s.kid = kid; s.gx = gx; s.gy = gy; s.gz = nz; s.bx = 64; s.by = 4; s.bytes = bytes;
+        return s;
+    };
+    P.report = isP != 0; P.mask = -1;
+    if (isP && q && mc) {
         // motion compensation inside the transform: reference + source in, prediction + symbols out
         // two launches over the same grid: the lean kernel codes the common patches (few registers, no edge logic: it runs
         // at the HBM rate of its 3 B/sample: reference + source in, prediction out), the general kernel everything else
         // (picture edges, intra blocks, cells shared between scan regions) and returns at once for the common ones
-        PB(c0 == 0 ? KID_FWD_MC_FAST_Y : KID_FWD_MC_FAST_C, smp * 3.0);
-        const dim3 fg = grid3(g.w3, g.h3, nz);
-        if (c0 == 0) hipLaunchKernelGGL((k_fwd_mc_fast<0>), tile_grid(fg.x, fg.y, fg.z), dim3(64, 4), 0, st, jobs, G, *mc, c0, npl, mvs0, mk_xcd_grid((int)fg.x, (int)fg.y, (int)fg.z), xcd_plain());
-        else         hipLaunchKernelGGL((k_fwd_mc_fast<1>), tile_grid(fg.x, fg.y, fg.z), dim3(64, 4), 0, st, jobs, G, *mc, c0, npl, mvs0, mk_xcd_grid((int)fg.x, (int)fg.y, (int)fg.z), xcd_plain());
-        PE();
+        FwdStep &f = step(c0 == 0 ? KID_FWD_MC_FAST_Y : KID_FWD_MC_FAST_C, full.x, full.y, smp * 3.0);
+        f.xcd = true; f.plain = plain;
         // Where can a patch fail fwd_fast_sel?  Intra blocks (anywhere: the caller knows), otherwise only in the first /
         // last row or column of patches (cells shared between scan regions, a ragged picture edge) -- unless a patch can
         // span two columns of the stability map, which depends on the geometry alone.  The general kernel is launched
-        // over the whole grid, over the strips that can hold such patches, or not at all.
-        const int gm = fwd_general_mask(G, *mc, c0, npl, general_whole);
-        dispatch_note_fwd(c0 != 0, gm);
+        // over the whole grid, over the strips that can hold such patches, or not at all (each launch a bracket of 0 bytes).
+        const int gm = P.mask = fwd_general_mask(G, *mc, c0, npl, general_whole);
         const bool whole = gm & DSVG_FWD_WHOLE, top = gm & DSVG_FWD_TOP, bottom = gm & DSVG_FWD_BOTTOM, left = gm & DSVG_FWD_LEFT, right = gm & DSVG_FWD_RIGHT;
-        const dim3 full = grid3(g.w3, g.h3, nz);
-        auto general = [&](dim3 gr, int bxo, int byo, int bxs, int bys) {
-            PB(c0 == 0 ? KID_FWD_MC_PIX_Y : KID_FWD_MC_PIX_C, 0.0);
-            if (c0 == 0) hipLaunchKernelGGL((k_fwd_mc_pix<0>), gr, dim3(64, 4), 0, st, jobs, G, *mc, c0, npl, mvs0, 1, bxo, byo, bxs, bys);
-            else         hipLaunchKernelGGL((k_fwd_mc_pix<1>), gr, dim3(64, 4), 0, st, jobs, G, *mc, c0, npl, mvs0, 1, bxo, byo, bxs, bys);
-            PE();
+        const int fy = (int)full.y, fx = (int)full.x;
+        const auto general = [&](int gx, int gy, int bxo, int byo, int bxs, int bys) {
+            FwdStep &s = step(c0 == 0 ? KID_FWD_MC_PIX_Y : KID_FWD_MC_PIX_C, gx, gy, 0.0);
+            s.a[0] = bxo; s.a[1] = byo; s.a[2] = bxs; s.a[3] = bys;
         };
-        if (whole) general(full, 0, 0, 1, 1);
+        if (whole) general(fx, fy, 0, 0, 1, 1);
         else {
             // the top and bottom strips in one launch (two block rows: 0 and the last), likewise left and right
-            const int fy = (int)full.y, fx = (int)full.x;
-            if ((top || bottom) && fy == 1) general(dim3(full.x, 1, nz), 0, 0, 1, 1);
-            else if (top && bottom) general(dim3(full.x, 2, nz), 0, 0, 1, fy - 1);
-            else if (top) general(dim3(full.x, 1, nz), 0, 0, 1, 1);
-            else if (bottom) general(dim3(full.x, 1, nz), 0, fy - 1, 1, 1);
-            if ((left || right) && fx == 1) general(dim3(1, full.y, nz), 0, 0, 1, 1);
-            else if (left && right) general(dim3(2, full.y, nz), 0, 0, fx - 1, 1);
-            else if (left) general(dim3(1, full.y, nz), 0, 0, 1, 1);
-            else if (right) general(dim3(1, full.y, nz), fx - 1, 0, 1, 1);
+            if ((top || bottom) && fy == 1) general(fx, 1, 0, 0, 1, 1);
+            else if (top && bottom) general(fx, 2, 0, 0, 1, fy - 1);
+            else if (top) general(fx, 1, 0, 0, 1, 1);
+            else if (bottom) general(fx, 1, 0, fy - 1, 1, 1);
+            if ((left || right) && fx == 1) general(1, fy, 0, 0, 1, 1);
+            else if (left && right) general(2, fy, 0, 0, fx - 1, 1);
+            else if (left) general(1, fy, 0, 0, 1, 1);
+            else if (right) general(1, fy, fx - 1, 0, 1, 1);
         }
     } else if (isP) {
-        dispatch_note_fwd(c0 != 0, -1);
-        PB(fused ? KID_FWD_HAAR_PIX_Q : KID_FWD_HAAR_PIX, smp * (fused ? 3.0 : 5.0));   // 1 B/sample in, 4 B/sample out (details + LL3); fused: 2 B symbols
-        if (fused) hipLaunchKernelGGL((k_fwd_haar_pix<true>), grid3(g.w3, g.h3, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, from_src);
-        else       hipLaunchKernelGGL((k_fwd_haar_pix<false>), grid3(g.w3, g.h3, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, from_src);
-        PE();
+        step(q ? KID_FWD_HAAR_PIX_Q : KID_FWD_HAAR_PIX, full.x, full.y, smp * (q ? 3.0 : 5.0)).a[0] = from_src;   // 1 B/sample in, 4 B/sample out (details + LL3); quantised: 2 B symbols
     } else {
-        PB(fused ? KID_FWD_B4T_Q : KID_FWD_B4T, smp * (fused ? 3.5 : 5.0));   // 1 in, LL1 1 + details 3 out; fused: LL1 1 + symbols 1.5 out
-        if (fused) hipLaunchKernelGGL((k_fwd_b4t<true>), grid3((g.W + 7) / 8, (g.H + 7) / 8, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, from_src);
-        else       hipLaunchKernelGGL((k_fwd_b4t<false>), grid3((g.W + 7) / 8, (g.H + 7) / 8, nz), dim3(64, 4), 0, st, jobs, G, c0, npl, from_src);
-        PE();
-        PB(fused ? KID_FWD_HAAR_MID2_Q : KID_FWD_HAAR_MID2, smp * (fused ? 1.4 : 2.0));        // LL1 (1/4) in, levels 2..3 out
-        if (fused) hipLaunchKernelGGL((k_fwd_haar_mid<2, true>), grid3(g.w3, g.h3, nz), dim3(64, 4), 0, st, jobs, G, c0, npl);
-        else       hipLaunchKernelGGL((k_fwd_haar_mid<2, false>), grid3(g.w3, g.h3, nz), dim3(64, 4), 0, st, jobs, G, c0, npl);
-        PE();
+        const dim3 b4 = grid3((g.W + 7) / 8, (g.H + 7) / 8, nz);
+        step(q ? KID_FWD_B4T_Q : KID_FWD_B4T, b4.x, b4.y, smp * (q ? 3.5 : 5.0)).a[0] = from_src;   // 1 in, LL1 1 + details 3 out; quantised: LL1 1 + symbols 1.5 out
+        step(q ? KID_FWD_HAAR_MID2_Q : KID_FWD_HAAR_MID2, full.x, full.y, smp * (q ? 1.4 : 2.0));   // LL1 (1/4) in, levels 2..3 out
     }
-    // levels 4..5 (LL3 -> LL5) for every picture type (fused >= 3: the caller launches them once for all planes and jobs
-    // of the frame step, launch_fwd_mid4)
-    if (fused < 3) launch_fwd_mid4(st, jobs, njobs, G, c0, npl, llq, pf);
-    if (with_tail) {
-        PB(KID_FWD_TAIL, (double)g.w5 * g.h5 * nz * 8.0);
-        hipLaunchKernelGGL(k_fwd_tail, dim3(nz), dim3(TAIL_THREADS), (size_t)g.w5 * g.h5 * 4, st, jobs, G, c0, npl);
-        PE();
-    }
+    // levels 4..5 (LL3 -> LL5) and the LDS tail for every picture type, unless the frame step launches them (fwd_step_plan)
+    if (o.own_mid4) mid4_step(P.s[P.n++], G, njobs, c0, npl, o.llq);
+    if (o.own_tail) tail_step(P.s[P.n++], KID_FWD_TAIL, G, njobs, c0, npl);
+    return P;
 }
 
-// the LDS tails of planes [c0, c0+npl) of all jobs in ONE launch (dynamic LDS sized for the largest plane)
-void launch_sbt_tail(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int inverse, Prof *pf)
+// what a frame step launches once for all planes of its njobs pictures, I and P alike: levels 4..5, then the levels >= 6 in LDS --
+// llq: with the LL quantiser in both, and the inverse tail behind it (k_tail_q)
+FwdPlan fwd_step_plan(const SbtGeo3 &G, int njobs, bool llq)
 {
-    size_t lds = 0;
-    double s3 = 0;
-    for (int c = c0; c < c0 + npl; c++) {
-        lds = std::max(lds, (size_t)G.g[c].w5 * G.g[c].h5 * 4);
-        s3 += (double)G.g[c].w5 * G.g[c].h5 * njobs;
-    }
-    PB(inverse ? KID_INV_TAIL : KID_FWD_TAIL, s3 * 8.0);
-    if (inverse) hipLaunchKernelGGL(k_inv_tail, dim3(njobs * npl), dim3(TAIL_THREADS), lds, st, jobs, G, c0, npl);
-    else         hipLaunchKernelGGL(k_fwd_tail, dim3(njobs * npl), dim3(TAIL_THREADS), lds, st, jobs, G, c0, npl);
-    PE();
-}
-
-// encoder: forward tail + LL quantiser + inverse tail of planes [c0, c0+npl) of all jobs in one launch
-void launch_tail_q(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, Prof *pf)
-{
-    size_t lds = 0;
-    double s3 = 0;
-    for (int c = c0; c < c0 + npl; c++) {
-        lds = std::max(lds, (size_t)G.g[c].w5 * G.g[c].h5 * 4);
-        s3 += (double)G.g[c].w5 * G.g[c].h5 * njobs;
-    }
-    PB(KID_TAIL_Q, s3 * 8.0);
+    FwdPlan P;
+    memset(&P, 0, sizeof(P));
+    P.mask = -1;
+    mid4_step(P.s[P.n++], G, njobs, 0, 3, llq);
     // few workgroups (a small batch: the kernel is a link of a latency-bound chain): 1024 threads per band; many: 256 -- a
     // 16-wave workgroup would wait for a whole CU's worth of free wave slots beside the other coding stream's kernels
-    dispatch_note_threads(njobs * npl <= 96 ? 1024 : TAIL_THREADS, 0);
-    if (njobs * npl <= 96) hipLaunchKernelGGL((k_tail_q<1024>), dim3(njobs * npl), dim3(1024), lds, st, jobs, G, c0, npl);
-    else hipLaunchKernelGGL((k_tail_q<TAIL_THREADS>), dim3(njobs * npl), dim3(TAIL_THREADS), lds, st, jobs, G, c0, npl);
-    PE();
+    tail_step(P.s[P.n++], llq ? KID_TAIL_Q : KID_FWD_TAIL, G, njobs, 0, 3, llq && njobs * 3 <= 96 ? 1024 : TAIL_THREADS);
+    return P;
+}
+
+// run a plan: one launch per step, each template instance of a forward kernel named here and nowhere else
+void launch_fwd_plan(hipStream_t st, const JobDev *jobs, const SbtGeo3 &G, int c0, int npl, const FwdPlan &P, Prof *pf, const McGeo *mc, const DMV *mvs0)
+{
+#define FWD_MC_FAST(kid, C) case kid: hipLaunchKernelGGL((k_fwd_mc_fast<C>), grid, block, 0, st, jobs, G, *mc, c0, npl, mvs0, mk_xcd_grid(s.gx, s.gy, s.gz), (int)s.plain); break
+#define FWD_MC_PIX(kid, C)  case kid: hipLaunchKernelGGL((k_fwd_mc_pix<C>), grid, block, 0, st, jobs, G, *mc, c0, npl, mvs0, 1, s.a[0], s.a[1], s.a[2], s.a[3]); break
+#define FWD_SRC(kid, ...)   case kid: hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, st, jobs, G, c0, npl, s.a[0]); break
+#define FWD_PLANES(...)     hipLaunchKernelGGL((__VA_ARGS__), grid, block, s.lds, st, jobs, G, c0, npl)
+    if (P.report) dispatch_note_fwd(c0 != 0, P.mask);
+    for (int i = 0; i < P.n; i++) {
+        const FwdStep &s = P.s[i];
+        const dim3 grid = s.xcd ? tile_grid(s.gx, s.gy, s.gz) : dim3(s.gx, s.gy, s.gz), block(s.bx, s.by);
+        PB(s.kid, s.bytes);
+        switch (s.kid) {
+        case KID_FWD_HAAR_MID4:
+            if (s.a[0]) FWD_PLANES(k_fwd_haar_mid<4, false, true>);
+            else        FWD_PLANES(k_fwd_haar_mid<4, false>);
+            break;
+        FWD_MC_FAST(KID_FWD_MC_FAST_Y, 0);
+        FWD_MC_FAST(KID_FWD_MC_FAST_C, 1);
+        FWD_MC_PIX(KID_FWD_MC_PIX_Y, 0);
+        FWD_MC_PIX(KID_FWD_MC_PIX_C, 1);
+        FWD_SRC(KID_FWD_HAAR_PIX_Q, k_fwd_haar_pix<true>);
+        FWD_SRC(KID_FWD_HAAR_PIX, k_fwd_haar_pix<false>);
+        FWD_SRC(KID_FWD_B4T_Q, k_fwd_b4t<true>);
+        FWD_SRC(KID_FWD_B4T, k_fwd_b4t<false>);
+        case KID_FWD_HAAR_MID2_Q: FWD_PLANES(k_fwd_haar_mid<2, true>); break;
+        case KID_FWD_HAAR_MID2:   FWD_PLANES(k_fwd_haar_mid<2, false>); break;
+        case KID_FWD_TAIL:        FWD_PLANES(k_fwd_tail); break;
+        case KID_TAIL_Q:
+            dispatch_note_threads(s.bx, 0);
+            if (s.bx == 1024) FWD_PLANES(k_tail_q<1024>);
+            else              FWD_PLANES(k_tail_q<TAIL_THREADS>);
+            break;
+        }
+        PE();
+    }
+#undef FWD_MC_FAST
+#undef FWD_MC_PIX
+#undef FWD_SRC
+#undef FWD_PLANES
+}
+
+void launch_fwd_sbt(hipStream_t st, const JobDev *jobs, int njobs, const SbtGeo3 &G, int c0, int npl, int isP, int from_src, const FwdOpts &o, Prof *pf,
+                    const McGeo *mc, const DMV *mvs0, int general_whole)
+{
+    launch_fwd_plan(st, jobs, G, c0, npl, fwd_sbt_plan(G, njobs, c0, npl, isP, from_src, o, mc, general_whole, xcd_plain() != 0), pf, mc, mvs0);
 }
 
 // decoder: the prediction of every inter block left of block column ex0 / above block row ey0 (see k_mc_patch), luma then chroma
@@ -3492,10 +3520,7 @@ InvPlan inv_sbt_plan(const SbtGeo3 &G, int njobs, int c0, int npl, int isP, int 
         s.a[0] = tx; s.a[1] = -ty - 1;
         s.cover = DSVG_INV_COVER_FROM; s.cx = tx; s.cy = ty;
     };
-    if (with_tail & 1) {
-        InvStep &s = step(KID_INV_TAIL, nz, 1, (double)g.w5 * g.h5 * nz * 8.0);
-        s.gz = 1; s.bx = TAIL_THREADS; s.lds = (size_t)g.w5 * g.h5 * 4;
-    }
+    if (with_tail & 1) tail_step(P.s[P.n++], KID_INV_TAIL, G, njobs, c0, npl);
     if (!(with_tail & 2))     // levels 5..4 (LL5 -> LL3) for every picture type (with_tail & 2: launch_inv54_all did them for all planes)
         step(filt ? KID_INV_TILE_54_F : KID_INV_TILE_54, (g.w5 + IT_TX - 1) / IT_TX, (g.h5 + IT_TY - 1) / IT_TY, s3 * 8.0);
     if (!isP) {
@@ -3549,6 +3574,14 @@ InvPlan inv_sbt_plan(const SbtGeo3 &G, int njobs, int c0, int npl, int isP, int 
             whole(filt ? KID_INV_TILE_PIX_SYM_F : KID_INV_TILE_PIX_SYM, smp * 2.5);
     } else
         whole(filt ? KID_INV_TILE_PIX_F : KID_INV_TILE_PIX, smp * 6.0);
+    return P;
+}
+
+InvPlan inv_tail_plan(const SbtGeo3 &G, int njobs, int c0, int npl)
+{
+    InvPlan P;
+    memset(&P, 0, sizeof(P));
+    tail_step(P.s[P.n++], KID_INV_TAIL, G, njobs, c0, npl);
     return P;
 }
 

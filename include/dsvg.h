@@ -449,11 +449,13 @@ int dsvg_prof_get(dsvg_ctx *ctx, int kid, double *ms, long *launches, double *al
  * PART p)} of motion-search level l; csum: 0 = k_hme_csum not launched, 1 = launched, 2 = launched and every workgroup returns
  * at once for reasons the host knows (fullx > 64, chroma block width not a multiple of 16), -1: not decided.
  * tail_threads / scan_threads: the workgroup size of the last k_tail_q / k_hz_scan launch (1024 for few jobs per launch, else 256).
- * dsvg_dispatch_last: what launch_fwd_sbt / launch_hme / launch_tail_q / the scan launch last decided in this process (the
- * launchers fill it in; fusable: whether the last P plane group took the fused kernels).
- * dsvg_dispatch_plan: what they decide for an encoder context of this geometry, without a device -- the launchers' own decision
- * functions on the geometry tables of dsvg_ctx_create (one set-up, shared with the context; the GPU tests still compare both
- * queries on a live context); tail_threads / scan_threads = -1 (they depend on the jobs per launch). */
+ * dsvg_dispatch_last: what the last forward plan of a P plane group, the last motion-search plan, the last k_tail_q step and the
+ * scan launch said in this process (the plans' executors, launch_fwd_plan / launch_hme_plan, fill it in; fusable: whether the last
+ * P plane group took the fused kernels).
+ * dsvg_dispatch_plan: the same figures for an encoder context of this geometry, without a device -- read from the plans themselves
+ * (fwd_sbt_plan, hme_plan: see dsvg_fwd_plan / dsvg_hme_plan below) on the geometry tables of dsvg_ctx_create (one set-up, shared
+ * with the context; the GPU tests still compare both queries on a live context); tail_threads / scan_threads = -1 (they depend on
+ * the jobs per launch). */
 #define DSVG_FWD_WHOLE  1
 #define DSVG_FWD_TOP    2
 #define DSVG_FWD_BOTTOM 4
@@ -505,6 +507,48 @@ typedef struct dsvg_inv_step {
 } dsvg_inv_step;
 int dsvg_inv_plan(int width, int height, int subsamp, int group, int isP, int with_tail, int insym, int patch_kernel, int fuse_border,
                   unsigned switches, int njobs, dsvg_inv_step *steps, int cap, int *fb);
+
+/* The launches of the forward transform and of the motion search (tests), without a device: the plans the encoder's launchers run
+ * step by step (fwd_sbt_plan / fwd_step_plan -> launch_fwd_plan, hme_plan -> launch_hme_plan: the executors decide nothing), on the
+ * geometry tables of dsvg_ctx_create.
+ * dsvg_fwd_plan: group 0 luma, 1 the chroma pair of njobs pictures (isP: all P, else all I) as the frame step of dsvg_code_batch asks
+ * for them -- quantised, motion compensation fused where the geometry allows, general_whole = 0: no picture has an intra block --, or
+ * group DSVG_FWD_GROUP_STEP: what the step launches once for all planes of its njobs pictures (levels 4..5, then k_tail_q, or
+ * k_fwd_tail with DSVG_FWD_NO_LLQ).  switches: DSVG_FWD_NO_* for DSV1_NO_XCD_ORDER, DSV1_NO_MC_FUSION, DSV1_NO_LLQ, whatever the
+ * environment says.  *mask (may be null): the DSVG_FWD_* mask of a P plane group, or -1.  A step: kernel, grid, xcd and bytes as in
+ * dsvg_inv_step; block, dynamic LDS bytes; args = the kernel's trailing integers (k_fwd_mc_pix: bxofs, byofs, bxstep, bystep -- thread
+ * block (x, y) of the launch works on block (bxofs + x * bxstep, byofs + y * bystep) of the full grid; k_fwd_b4t / k_fwd_haar_pix:
+ * from_src; k_fwd_haar_mid<4>: 1 = with the LL quantiser).  k_tail_q's variant is its block size.
+ * dsvg_hme_plan: the motion search of npairs pairs (csum_table: with the chroma table, as a context has it): k_hme_csum if any, the
+ * launches of every level from the top down, k_hme_detail.  A step: kernel; l0, nkbf, part = the k_hme_level<L0, NKBF, PART>
+ * instance; level; count = the level's blocks per pair in this launch; fullx, fully; inv_per, inv_row = min(floor(2^32 / d),
+ * 2^32 - 1) of count and of the row length the block index is split by; grid (k_hme_level: grid[0] workgroups, launched rounded up
+ * to a multiple of 8), block; bytes (0 where cont); cont = 1: the launch has no profiler bracket of its own, it continues the previous step's.
+ * Both write the first min(steps, cap) steps in launch order and return the number of steps, or a negative DSVG_ERR_*. */
+#define DSVG_FWD_GROUP_STEP   2
+#define DSVG_FWD_NO_XCD_ORDER 1
+#define DSVG_FWD_NO_MC_FUSION 2
+#define DSVG_FWD_NO_LLQ       4
+typedef struct dsvg_fwd_step {
+    int kernel;
+    int grid[3], xcd;
+    int block[2];
+    unsigned lds;
+    int args[4];
+    double bytes;
+} dsvg_fwd_step;
+int dsvg_fwd_plan(int width, int height, int subsamp, int group, int isP, int general_whole, unsigned switches, int njobs,
+                  dsvg_fwd_step *steps, int cap, int *mask);
+typedef struct dsvg_hme_step {
+    int kernel;
+    int l0, nkbf, part;
+    int level, count, fullx, fully;
+    unsigned inv_per, inv_row;
+    int grid[2], block;
+    double bytes;
+    int cont;
+} dsvg_hme_step;
+int dsvg_hme_plan(int width, int height, int subsamp, int csum_table, int npairs, dsvg_hme_step *steps, int cap);
 
 /* The plan of a coding call (tests): what dsvg_code_batch / dsvg_code_batch_rc (rc != NULL) decide on the host for these jobs in an
  * encoder context created with these arguments, without a device -- the call's own plan (plan_code_batch, csrc/dsvg_batch_plan.h: the

@@ -1,12 +1,13 @@
 """The product's plan for the analysis and forward half of one encoder picture, restated from the host code (host arithmetic only).
 
 Given a geometry (w, h, fmt) this says which block size the encoder takes, whether motion compensation is fused into the forward
-transform, which branch `launch_fwd_sbt` (csrc/k_sbt.hip) takes for the general kernel of luma and of the chroma pair, what
-`launch_hme` (csrc/k_hme.hip) launches per pyramid level, and how many launches and algorithmic bytes (the `PB(...)` /
-`pf->begin(...)` brackets the per-kernel profiler adds up) each forward and motion-search kernel gets per picture.  It restates the
+transform, which branch `fwd_sbt_plan` (csrc/k_sbt.hip) takes for the general kernel of luma and of the chroma pair, what
+`hme_plan` (csrc/k_hme.hip) launches per pyramid level, and how many launches and algorithmic bytes (the steps' `bytes`, which
+the executors hand to the per-kernel profiler's brackets) each forward and motion-search kernel gets per picture.  It restates the
 product's planning, not the reference: what is right is decided by the oracle; this module only says which code a geometry
 reaches, so that the tests can name the branch a case is there for and check that it was taken -- on the GPU against the profiler
-and dsvg_dispatch_last, on the CPU against dsvg_dispatch_plan (the launchers' own decision functions) over the whole sweep.
+and dsvg_dispatch_last, on the CPU against the plans the launchers execute (dsvg_dispatch_plan, dsvg_fwd_plan, dsvg_hme_plan)
+over the matrix and a sample of the sweep.
 
 Every rule cites the line it restates.  Line numbers refer to csrc/k_sbt.hip unless another file is named.
 """
@@ -71,28 +72,28 @@ def fusable(w, h, fmt):
 
 @functools.lru_cache(maxsize=None)
 def x_facts(W, pw, nbh):
-    """the horizontal half of fwd_general_mask for one plane (k_sbt.hip:3288-3306): (left, right, whole, one column of thread
+    """the horizontal half of fwd_general_mask for one plane (k_sbt.hip:3298-3316): (left, right, whole, one column of thread
     blocks)"""
     sw0, sw1, sw2 = rsu(W, 3), rsu(W, 2), rsu(W, 1)
-    left = 2 * sw0 > sw1 or 2 * sw1 > sw2                                                    # :3295
-    right = (pw & 7) != 0                                                                    # :3297 (mc.w[c]: the pixel plane)
-    d1, d2 = (nbh << 14) // sw2, (nbh << 14) // sw1                                          # :3299
+    left = 2 * sw0 > sw1 or 2 * sw1 > sw2                                                    # :3305
+    right = (pw & 7) != 0                                                                    # :3307 (mc.w[c]: the pixel plane)
+    d1, d2 = (nbh << 14) // sw2, (nbh << 14) // sw1                                          # :3309
     whole = any(((4 * i * d1) >> 14) != (((4 * i + 3) * d1) >> 14) or ((2 * i * d2) >> 14) != (((2 * i + 1) * d2) >> 14)
-                for i in range(sw0))                                                         # :3300-3301
-    return left, right, whole, (sw0 + 63) // 64 == 1                                         # grid3 (:3247), :3303
+                for i in range(sw0))                                                         # :3310-3311
+    return left, right, whole, (sw0 + 63) // 64 == 1                                         # grid3 (:3247), :3313
 
 
 @functools.lru_cache(maxsize=None)
 def y_facts(H, ph):
     """the vertical half: (top, bottom, one row of thread blocks)"""
     sh0, sh1, sh2 = rsu(H, 3), rsu(H, 2), rsu(H, 1)
-    top = 2 * sh0 > sh1 or 2 * sh1 > sh2                                                     # :3296
-    bottom = (ph & 7) != 0                                                                   # :3298 (gc.ph)
+    top = 2 * sh0 > sh1 or 2 * sh1 > sh2                                                     # :3306
+    bottom = (ph & 7) != 0                                                                   # :3308 (gc.ph)
     return top, bottom, (sh0 + 3) // 4 == 1                                                  # grid3: 4 patch rows per thread block
 
 
 def general_mask(w, h, fmt, group):
-    """fwd_general_mask (k_sbt.hip:3288-3306) of plane group 0 (luma) / 1 (the chroma pair, whose planes are alike), as the
+    """fwd_general_mask (k_sbt.hip:3298-3316) of plane group 0 (luma) / 1 (the chroma pair, whose planes are alike), as the
     encoder calls it (dsvg_pipe.hip: launch_fwd_sbt(.., &c->MG, mv0, gw); with FWD_FAST_INTRA = 1 (k_sbt.hip:852) `gw` does not
     enter the decision)"""
     pw, ph, W, H = plane_dims(w, h, fmt)[group]
@@ -103,14 +104,41 @@ def general_mask(w, h, fmt, group):
 
 
 def general_branch(mask):
-    """the branch launch_fwd_sbt takes for the general kernel (k_sbt.hip:3339-3351): (name, launches).  Names: 'whole', or
+    """the branch fwd_sbt_plan takes for the general kernel (k_sbt.hip:3352-3363): (name, launches).  Names: 'whole', or
     '<rows>|<cols>' with rows in - / row1 (a one-row grid: fy == 1) / T+B / T / B and cols in - / col1 / L+R / L / R"""
     if mask & WHOLE:
-        return "whole", 1                                                                    # :3339
+        return "whole", 1                                                                    # :3352
     t, b, l, r = mask & TOP, mask & BOTTOM, mask & LEFT, mask & RIGHT
-    rows = "row1" if (t or b) and mask & ROW1 else "T+B" if t and b else "T" if t else "B" if b else "-"     # :3343-3346
-    cols = "col1" if (l or r) and mask & COL1 else "L+R" if l and r else "L" if l else "R" if r else "-"     # :3347-3350
+    rows = "row1" if (t or b) and mask & ROW1 else "T+B" if t and b else "T" if t else "B" if b else "-"     # :3355-3358
+    cols = "col1" if (l or r) and mask & COL1 else "L+R" if l and r else "L" if l else "R" if r else "-"     # :3359-3362
     return rows + "|" + cols, (rows != "-") + (cols != "-")
+
+
+def general_strips(mask, fx, fy):
+    """the general kernel's launches over the fx x fy grid of thread blocks of a plane group (grid3 of its first plane, :3325), the
+    strip ladder of fwd_sbt_plan (k_sbt.hip:3352-3363): [(grid x, grid y, bxofs, byofs, bxstep, bystep)] -- thread block (x, y) of a
+    launch works on block (bxofs + x * bxstep, byofs + y * bystep) of the full grid (k_fwd_mc_pix)"""
+    if mask & WHOLE:
+        return [(fx, fy, 0, 0, 1, 1)]                                                        # :3352
+    t, b, l, r = mask & TOP, mask & BOTTOM, mask & LEFT, mask & RIGHT
+    out = []
+    if (t or b) and fy == 1:
+        out.append((fx, 1, 0, 0, 1, 1))                                                      # :3355
+    elif t and b:
+        out.append((fx, 2, 0, 0, 1, fy - 1))                                                 # :3356: block rows 0 and fy - 1
+    elif t:
+        out.append((fx, 1, 0, 0, 1, 1))                                                      # :3357
+    elif b:
+        out.append((fx, 1, 0, fy - 1, 1, 1))                                                 # :3358
+    if (l or r) and fx == 1:
+        out.append((1, fy, 0, 0, 1, 1))                                                      # :3359
+    elif l and r:
+        out.append((2, fy, 0, 0, fx - 1, 1))                                                 # :3360: block columns 0 and fx - 1
+    elif l:
+        out.append((1, fy, 0, 0, 1, 1))                                                      # :3361
+    elif r:
+        out.append((1, fy, fx - 1, 0, 1, 1))                                                 # :3362
+    return out
 
 
 def hme_level(w, h, level):
@@ -159,7 +187,7 @@ def hme_class(w, h, fmt):
 
 
 def tail_threads(njobs):
-    """the variants of k_tail_q (k_sbt.hip:3405-3406) and k_hz_scan (k_hzcc.hip:1764-1765) for njobs jobs of three planes"""
+    """the variants of k_tail_q (fwd_step_plan, k_sbt.hip:3387) and k_hz_scan (k_hzcc.hip:1764-1765) for njobs jobs of three planes"""
     return 1024 if 3 * njobs <= 96 else 256
 
 
@@ -191,16 +219,16 @@ class Plan:
         self.hme = tuple(hme_level(w, h, l)[:4] for l in range(self.levels + 1))
         self.csum = hme_csum(w, h, fmt)
         self.hme_cls = hme_class(w, h, fmt)
-        # coefficient samples of luma and of the chroma pair (smp, :3313), level-3 and level-5 cells of all planes
+        # coefficient samples of luma and of the chroma pair (smp, :3324), level-3 and level-5 cells of all planes
         self.smp = (float(D[0][2] * D[0][3]), float(D[1][2] * D[1][3] * 2))
         s3 = float(sum(rsu(d[2], 3) * rsu(d[3], 3) for d in D))
         s5 = float(sum(rsu(d[2], 5) * rsu(d[3], 5) for d in D))
-        # every picture: levels 4..5 of all planes in one launch (launch_fwd_mid4 :3273-3285, from code_batch_impl), then the
-        # tail with the LL quantiser (launch_tail_q :3394-3408)
+        # every picture: levels 4..5 of all planes in one launch (mid4_step :3273-3284), then the tail with the LL quantiser
+        # (tail_step :3286-3295): fwd_step_plan :3379-3389, from enqueue_group (dsvg_pipe.hip)
         self.common = {}
         _add(self.common, K_MID4, s3 * 8.0)
         _add(self.common, K_TAIL_Q, s5 * 8.0)
-        # I pictures, luma then the chroma pair: k_fwd_b4t<true> + k_fwd_haar_mid<2, true> (:3359-3366, fused)
+        # I pictures, luma then the chroma pair: k_fwd_b4t<true> + k_fwd_haar_mid<2, true> (:3367-3369, quantised)
         self.i_kernels = dict(self.common)
         for smp in self.smp:
             _add(self.i_kernels, K_B4T_Q, smp * 3.5)
@@ -209,7 +237,7 @@ class Plan:
     def p_kernels(self, intra):
         k = dict(self.common)
         if self.fusable:
-            # :3320-3351: the lean kernel over the whole grid, the general kernel per branch; k_mc serves the intra blocks by list
+            # :3334-3363: the lean kernel over the whole grid, the general kernel per branch; k_mc serves the intra blocks by list
             # (dsvg_pipe.hip: `if (icnt[..]) launch_mc(.., list)`, k_bmc.hip:386-391)
             for g, (fast, pix) in enumerate(((K_FAST_Y, K_PIX_Y), (K_FAST_C, K_PIX_C))):
                 _add(k, fast, self.smp[g] * 3.0)
@@ -219,16 +247,16 @@ class Plan:
             if intra:
                 _add(k, K_MC, 0.0)
         else:
-            # k_mc over every block (k_bmc.hip:393: pixel planes, 4 B/sample), then k_fwd_haar_pix<true> (:3354-3357)
+            # k_mc over every block (k_bmc.hip:393: pixel planes, 4 B/sample), then k_fwd_haar_pix<true> (:3365)
             _add(k, K_MC, float(sum(d[0] * d[1] for d in self.dims)) * 4.0)
             for smp in self.smp:
                 _add(k, K_HAAR_PIX_Q, smp * 3.0)
-        # the motion search of the picture's pair (launch_hme k_hme.hip:1493-1538, npairs = 1; the chroma table is on)
+        # the motion search of the picture's pair (hme_plan k_hme.hip:1495-1537, npairs = 1; the chroma table is on)
         cpx = float(self.dims[1][0] * self.dims[1][1] + self.dims[2][0] * self.dims[2][1])
         if self.csum:
-            _add(k, K_HME_CSUM, cpx)                                                         # k_hme.hip:1501
+            _add(k, K_HME_CSUM, cpx)                                                         # k_hme.hip:1507
         for l in range(self.levels, 0, -1):
-            _add(k, K_HME_UP, 2.0 * rsu(self.w, l) * rsu(self.h, l))                         # k_hme.hip:1510,1513: one bracket per level
+            _add(k, K_HME_UP, 2.0 * rsu(self.w, l) * rsu(self.h, l))                         # k_hme.hip:1514,1527: one bracket per level
         _add(k, K_HME_L0, 2.0 * self.w * self.h)                                             # (level 0's PART 1 + PART 2 share one bracket)
         _add(k, K_HME_DETAIL, 0.0)                                                           # k_hme.hip:1535
         return k

@@ -99,6 +99,35 @@ def test_encoder_frame_by_frame(pkg, g, content):
         b.close()
 
 
+def test_frame_steps_run_the_product_plans(pkg):
+    """the smallest fusable and the smallest non-fusable geometry of the matrix, one I and one P frame step of the dense content on
+    a live context: per kernel, the profiler's launches and bytes are the sums over the steps of dsvg_fwd_plan (luma, the chroma
+    pair, the step's common launches) and, for the P picture, dsvg_hme_plan.  (k_mc is launch_mc's, not the forward plan's.)"""
+    area = lambda g: g[0] * g[1]
+    for g in (min((g for g in FC.GEOMETRIES if P.fusable(*g)), key=area), min((g for g in FC.GEOMETRIES if not P.fusable(*g)), key=area)):
+        w, h, fmt = g
+        clip, _, _, intra = oracle(g, "dense")
+        b = pkg.Batch(pkg.make_encoder_cfg(w, h, fmt, **FC.cli("dense")), 1, 1)
+        try:
+            b.code_streams(1)
+            watched = [k for k in P.FORWARD_KERNELS + P.SEARCH_KERNELS if k != P.K_MC]
+            for t in (0, 1):
+                b.prof_enable(watched)
+                b.encode(clip[t].reshape(1, 1, -1))
+                got = {k: v[1:] for k, v in ((k, b.prof_get(k)) for k in watched) if v[1]}
+                want = {}
+                for group in (0, 1, pkg.FWD_GROUP_STEP):
+                    for s in pkg.fwd_plan(w, h, fmt, group, isP=t, general_whole=int(t and intra[0] > 0))[0]:
+                        P._add(want, s["kernel"], s["bytes"])
+                for s in pkg.hme_plan(w, h, fmt) if t else []:
+                    if not s["cont"]:
+                        P._add(want, s["kernel"], s["bytes"])
+                assert got == want, "%s frame %d: the profiler counted %s, the plans' steps add up to %s" % (FC.case_id(g), t, got, want)
+            b.prof_enable([])
+        finally:
+            b.close()
+
+
 def hme_geometries():
     """one geometry per motion-search class: the cases that are there for an 'hme' value"""
     seen, out = set(), []
@@ -163,7 +192,7 @@ def test_motion_search_every_level(pkg, prod, orc, g):
 # are k_fwd_haar_mid<4>'s, level 6 on k_tail_q's own.  (Three levels would need a chroma plane of at most 8 samples a side, which
 # the smallest luma the encoder takes, 32x32, does not give in any format.)
 WIDE_GEOMETRIES = [(32, 32, FC.F420), (64, 32, FC.F420), (128, 64, FC.F420)]
-WIDE_STREAMS = 36                         # one coding stream: 3 * 36 > 96 jobs of three planes reach launch_tail_q (k_sbt.hip:3405-3407) and the
+WIDE_STREAMS = 36                         # one coding stream: 3 * 36 > 96 jobs of three planes reach the 256-thread k_tail_q (k_sbt.hip:3387) and the
                                           # scan launch (k_hzcc.hip:1764-1766); with the default two coding streams each would get 18
 
 
