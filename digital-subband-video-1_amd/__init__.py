@@ -211,6 +211,58 @@ class Orient:
     NONE, HFLIP, VFLIP, ROT180, TRANSPOSE, ROT90, ROT270, TRANSVERSE = range(8)
 
 
+class Levels(_C.Structure):
+    """dsv1_levels: three 256-entry tables, one per plane (Y, U, V), out_p[i] = lut[p][in_p[i]] (include/dsv1_api.h, Levels).  The
+    builders are the library's host-only ones, exact integers: identity(), range(src_full, dst_full), adjust(...), a.compose(b) (a
+    first).  Any other curve: fill .lut / from_tables()."""
+    _fields_ = [("lut", (_C.c_uint8 * 256) * 3)]
+
+    @classmethod
+    def identity(cls):
+        lv = cls()
+        _chk(lib().dsv1_levels_identity(_C.byref(lv)), "dsv1_levels_identity")
+        return lv
+
+    @classmethod
+    def range(cls, src_full, dst_full):
+        """full-range (1) or limited-range (0) YCbCr in, the other (or the same: the identity) out (dsv1_levels_range)"""
+        lv = cls()
+        if lib().dsv1_levels_range(_C.byref(lv), int(src_full), int(dst_full)):
+            raise ValueError("Levels.range(%r, %r): the flags are 0 or 1" % (src_full, dst_full))
+        return lv
+
+    @classmethod
+    def adjust(cls, in_black=0, in_white=255, out_black=0, out_white=255, sat_q8=256):
+        """black and white point of the luma, saturation of the chroma in 1/256 (dsv1_levels_adjust)"""
+        lv = cls()
+        if lib().dsv1_levels_adjust(_C.byref(lv), in_black, in_white, out_black, out_white, sat_q8):
+            raise ValueError("Levels.adjust(%d, %d, %d, %d, %d) refused" % (in_black, in_white, out_black, out_white, sat_q8))
+        return lv
+
+    @classmethod
+    def from_tables(cls, tables):
+        """tables: anything numpy reads as uint8 [3][256]"""
+        t = _np.ascontiguousarray(tables, dtype=_np.uint8)
+        if t.shape != (3, 256):
+            raise ValueError("levels are three tables of 256 entries")
+        lv = cls()
+        _C.memmove(_C.byref(lv), t.ctypes.data, 768)
+        return lv
+
+    def compose(self, then):
+        """the tables equal to applying self and then `then` (dsv1_levels_compose)"""
+        out = Levels()
+        _chk(lib().dsv1_levels_compose(_C.byref(self), _C.byref(then), _C.byref(out)), "dsv1_levels_compose")
+        return out
+
+    def is_identity(self):
+        return bool(lib().dsv1_levels_is_identity(_C.byref(self)))
+
+    def tables(self):
+        """numpy uint8 [3][256], a copy"""
+        return _np.frombuffer(bytes(self), dtype=_np.uint8).reshape(3, 256).copy()
+
+
 class BlockInfo(_C.Structure):
     """dsv1_blockinfo: one block's side information (packet_blockinfo, draw_info_clip)"""
     _fields_ = [("mvx", _C.c_int16), ("mvy", _C.c_int16), ("mode", _C.c_uint8), ("submask", _C.c_uint8), ("stable", _C.c_uint8),
@@ -389,6 +441,18 @@ def lib():
         L.dsv1_resladder_open_oriented.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.c_int, _C.POINTER(Reframe),
                                                    _C.POINTER(PixFormat), _C.c_int, _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int,
                                                    _C.c_int, _C.c_int, _C.c_int, _C.c_int]
+        L.dsv1_levels_identity.argtypes = [_C.POINTER(Levels)]
+        L.dsv1_levels_range.argtypes = [_C.POINTER(Levels), _C.c_int, _C.c_int]
+        L.dsv1_levels_adjust.argtypes = [_C.POINTER(Levels)] + [_C.c_int] * 5
+        L.dsv1_levels_compose.argtypes = [_C.POINTER(Levels)] * 3
+        L.dsv1_levels_is_identity.argtypes = [_C.POINTER(Levels)]
+        L.dsv1_range_from_histogram.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.POINTER(_C.c_int)]
+        L.dsv1_points_from_histogram.argtypes = [_C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int), _C.POINTER(_C.c_int)]
+        L.dsv1_levels_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.POINTER(Levels), _C.c_int]
+        L.dsv1_histogram_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_int]
+        L.dsv1_detect_range_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int), _C.c_int]
+        L.dsv1_batch_set_source_levels.argtypes = [_C.c_void_p, _C.POINTER(Levels)]
+        L.dsv1_resladder_set_levels.argtypes = [_C.c_void_p, _C.POINTER(Levels)]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         L.dsvg_inv_plan.argtypes = [_C.c_int] * 9 + [_C.c_uint, _C.c_int, _C.POINTER(InvStep), _C.c_int, _C.POINTER(_C.c_int)]
@@ -629,6 +693,13 @@ class Batch:
     def denoise_reset(self, source=-1):
         """a discontinuity: the next picture of `source` (-1: every source) is filtered as a stream's first (dsv1_batch_denoise_reset)"""
         _chk(self.L.dsv1_batch_denoise_reset(self.h, source), "dsv1_batch_denoise_reset")
+
+    def set_source_levels(self, lv):
+        """from the next submit on the clips pass Levels lv on the GPU (dsv1_batch_set_source_levels), directly behind the source format's
+        conversion and in front of the deinterlacer or the inverse telecine; None or the identity switches it off.  Set AFTER a reframe
+        and an orientation.  Between batches only; forgets the deinterlacer's history, the inverse telecine's and the noise filter's
+        state of every source."""
+        _chk(self.L.dsv1_batch_set_source_levels(self.h, _C.byref(lv) if lv is not None else None), "dsv1_batch_set_source_levels")
 
     def set_source_reframe(self, rf):
         """from the next submit on the clips are rf.in_w x rf.in_h and reframed on the GPU onto the batch's geometry as Reframe rf says,
@@ -1166,6 +1237,76 @@ def orient_clip(clip, w, h, fmt, orient, device=0, n=None, out=None):
     return res
 
 
+def levels_clip(clip, w, h, fmt, lv, device=0, n=None, out=None):
+    """pass packed planar 8-bit frames of w x h through Levels lv on the GPU (dsv1_levels_clip): clip numpy uint8 [frames][frame bytes]
+    (host), which returns numpy uint8 [frames][frame bytes]; or a device pointer with n frames and `out` a device pointer for the
+    result.  `out` may be the clip itself."""
+    L = lib()
+    if n is not None:
+        _chk(L.dsv1_levels_clip(device, clip, w, h, fmt, n, out, _C.byref(lv), 1), "dsv1_levels_clip")
+        return out
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    a, frames = _host_clip(clip, fb)
+    res = _host_out(out, frames, fb)
+    _chk(L.dsv1_levels_clip(device, a.ctypes.data, w, h, fmt, frames, res.ctypes.data, _C.byref(lv), 0), "dsv1_levels_clip")
+    return res
+
+
+def histogram_clip(clip, w, h, fmt, device=0, n=None):
+    """the histogram of every plane of every frame of a clip, on the GPU (dsv1_histogram_clip): clip numpy uint8 [frames][frame_bytes]
+    (host), or a device pointer with n frames.  Returns numpy uint32 [frames][3][256]."""
+    L = lib()
+    if n is None:
+        a, frames = _host_clip(clip, w * h + 2 * _chroma_size(w, h, fmt))
+        src, dev = a.ctypes.data, 0
+    else:
+        src, frames, dev = clip, n, 1
+    hist = _np.zeros((max(frames, 0), 3, 256), dtype=_np.uint32)
+    _chk(L.dsv1_histogram_clip(device, src, w, h, fmt, frames, hist.ctypes.data, dev), "dsv1_histogram_clip")
+    return hist
+
+
+def _hist(hist):
+    g = _np.ascontiguousarray(hist, dtype=_np.uint32)
+    if g.ndim < 2 or g.shape[-2:] != (3, 256) or not g.size:
+        raise ValueError("a histogram is uint32 [frames][3][256]")
+    return g, g.size // 768
+
+
+def range_from_histogram(hist, ppm=1000):
+    """True where more than ppm millionths of the samples lie outside the limited range (dsv1_range_from_histogram): full-range.
+    Host only."""
+    g, n = _hist(hist)
+    full = _C.c_int(0)
+    if lib().dsv1_range_from_histogram(g.ctypes.data, n, ppm, _C.byref(full)):
+        raise ValueError("dsv1_range_from_histogram: ppm %d refused" % ppm)
+    return bool(full.value)
+
+
+def points_from_histogram(hist, low_ppm=1000, high_ppm=1000):
+    """(black, white) of the luma: at most low_ppm millionths of the samples lie below black, high_ppm above white
+    (dsv1_points_from_histogram), or None where black >= white.  Host only."""
+    g, n = _hist(hist)
+    b, w = _C.c_int(0), _C.c_int(0)
+    rc = lib().dsv1_points_from_histogram(g.ctypes.data, n, low_ppm, high_ppm, _C.byref(b), _C.byref(w))
+    if rc < 0:
+        raise ValueError("dsv1_points_from_histogram: ppm %d / %d refused" % (low_ppm, high_ppm))
+    return (b.value, w.value) if rc else None
+
+
+def detect_range_clip(clip, w, h, fmt, ppm=1000, device=0, n=None):
+    """the histogram on the GPU and the range rule in one call (dsv1_detect_range_clip): True for a full-range clip"""
+    L = lib()
+    if n is None:
+        a, frames = _host_clip(clip, w * h + 2 * _chroma_size(w, h, fmt))
+        src, dev = a.ctypes.data, 0
+    else:
+        src, frames, dev = clip, n, 1
+    full = _C.c_int(0)
+    _chk(L.dsv1_detect_range_clip(device, src, w, h, fmt, frames, ppm, _C.byref(full), dev), "dsv1_detect_range_clip")
+    return bool(full.value)
+
+
 def line_sums_clip(clip, w, h, fmt, device=0, n=None):
     """the sums of every luma row and column of a clip, on the GPU (dsv1_line_sums_clip): clip numpy uint8 [frames][frame_bytes]
     (host), or a device pointer with n frames.  Returns (row_sum numpy uint32 [frames][h], col_sum numpy uint32 [frames][w])."""
@@ -1494,6 +1635,12 @@ class ResLadder:
     def ivtc_reset(self, source=-1):
         """a discontinuity in `source` (-1: every source): dsv1_resladder_ivtc_reset"""
         _chk(self.L.dsv1_resladder_ivtc_reset(self.h, source), "dsv1_resladder_ivtc_reset")
+
+    def set_levels(self, lv):
+        """from the next call on the source clips pass Levels lv on the GPU, directly behind the conversion (dsv1_resladder_set_levels);
+        None or the identity switches it off.  The levelled clip stands for the source everywhere behind it, src_psnr / src_ssim
+        included.  Between calls only; contract as Batch.set_source_levels."""
+        _chk(self.L.dsv1_resladder_set_levels(self.h, _C.byref(lv) if lv is not None else None), "dsv1_resladder_set_levels")
 
     def set_denoise(self, dn):
         """the sources pass the temporal noise filter on the GPU as Denoise dn says, behind the conversion and the deinterlacer and in

@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip, k_levels.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -159,6 +159,20 @@ typedef struct dsvg_orient dsvg_orient;
 int  dsvg_orient_create(dsvg_orient **out, int device, int orient, int w, int h, int subsamp);
 void dsvg_orient_destroy(dsvg_orient *o);
 int  dsvg_orient_run(dsvg_orient *o, void *stream, const void *src_dev, int nframes, void *dst_dev);
+/* ---- levels and the histogram (include/dsv1_api.h, Levels; k_levels.hip; host side: host/dsv1_levels.c) ----
+ * Three tables for frames of w x h: nframes frames -> nframes frames, out_p[i] = lut[p][in_p[i]], dst == src allowed (the pass is
+ * pointwise); it keeps no state and owns 1 KiB of device memory, the tables.  In a session it runs directly behind the converter:
+ * convert -> levels -> deinterlace or inverse telecine -> denoise -> orient -> reframe.  The histogram: nframes frames ->
+ * uint32 [nframes][3][256] in device memory, zeroed on the stream first. */
+typedef struct dsvg_levels dsvg_levels;
+int  dsvg_levels_create(dsvg_levels **out, int device, const dsv1_levels *lv, int w, int h, int subsamp);
+void dsvg_levels_destroy(dsvg_levels *l);
+int  dsvg_levels_run(dsvg_levels *l, void *stream, const void *src_dev, int nframes, void *dst_dev);
+int  dsvg_levels_set_replicas(dsvg_levels *l, int rep);   /* measurements: the copies of the table in LDS, 32 (default) or 1 */
+typedef struct dsvg_histogram dsvg_histogram;
+int  dsvg_histogram_create(dsvg_histogram **out, int device, int w, int h, int subsamp);
+void dsvg_histogram_destroy(dsvg_histogram *g);
+int  dsvg_histogram_run(dsvg_histogram *g, void *stream, const void *src_dev, int nframes, void *hist_dev);
 typedef struct dsvg_linesums dsvg_linesums;
 int  dsvg_linesums_create(dsvg_linesums **out, int device, int w, int h, int subsamp);
 void dsvg_linesums_destroy(dsvg_linesums *s);

@@ -1220,7 +1220,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, a deinterlacer, a noise filter, an orientation or a reframe is set"); return DSVG_ERR_ARG; }
+    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, levels, a deinterlacer, a noise filter, an orientation or a reframe is set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1343,6 +1343,7 @@ int dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf)
         return DSVG_ERR_ARG;
     }
     if (b->src.orn) { dsv1_log(1, "dsv1_batch_set_source_reframe while an orientation is set: clear it first, set it again after the reframe"); return DSVG_ERR_ARG; }
+    if (b->src.lv) { dsv1_log(1, "dsv1_batch_set_source_reframe while levels are set: clear them first, set them again after the reframe"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_set_reframe(&b->src, rf);
 }
 
@@ -1361,7 +1362,17 @@ int dsv1_batch_set_source_orient(dsv1_batch *b, int orient)
         dsv1_log(1, "dsv1_batch_set_source_orient with a source format, a deinterlacer, an inverse telecine or a noise filter set: clear them first, set them again after it");
         return DSVG_ERR_ARG;
     }
+    if (b->src.lv) { dsv1_log(1, "dsv1_batch_set_source_orient while levels are set: clear them first, set them again after the orientation"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_set_orient(&b->src, orient);
+}
+
+/* levels: directly behind the converter, at the raw geometry; NULL or the identity clears the pass.  Setting, changing or clearing it
+ * forgets the history and state of the passes behind it */
+int dsv1_batch_set_source_levels(dsv1_batch *b, const dsv1_levels *lv)
+{
+    if (!b) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_levels with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    return dsv1_srcchain_set_levels(&b->src, lv);
 }
 
 /* tests: 1 while the batch's source chain holds a lane (a stream and device memory of its own), 0 with no pass set */

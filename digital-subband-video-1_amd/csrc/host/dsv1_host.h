@@ -123,17 +123,17 @@ static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
     return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
 }
 
-/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, deinterlacer, noise filter, orientation and reframe with their
+/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, levels, deinterlacer, noise filter, orientation and reframe with their
  * settings, and each pass's output clip per call parity (a batch of that parity reads the last one as a held clip until its collect).
  * A chain with no pass set holds no lane -- no stream, no device memory -- unless the session keeps it (keep_lane: a resolution
  * ladder uploads and scales on it).  The setters replace or (NULL) clear one pass; on an error the chain is as it was.  The session
  * checks that nothing is in flight, and its arguments, before it calls one.
- * THREE GEOMETRIES.  RAW, w x h (fb), is what convert, deinterlace and denoise are built for: the frames that come in.  ORIENTED,
+ * THREE GEOMETRIES.  RAW, w x h (fb), is what convert, levels, deinterlace and denoise are built for: the frames that come in.  ORIENTED,
  * mw x mh (mfb), is what the orientation leaves and the reframe reads.  CANVAS, ow x oh (ofb), is the clip the chain hands on: the
  * session's geometry.  Raw and oriented differ only while a transposing orientation is set, oriented and canvas only while a reframe
  * -- the LAST pass -- is set.  The reframe may be set, changed or cleared only while no other pass is set, the orientation only while
  * none but the reframe is (the session checks); the passes set after them resolve at w x h. */
-enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_ORIENT, DSV1_SRC_REFRAME, DSV1_SRC_SCALE,
+enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_ORIENT, DSV1_SRC_REFRAME, DSV1_SRC_LEVELS, DSV1_SRC_SCALE,
        DSV1_SRC_IVTC };                 /* (the inverse telecine: exclusive with the deinterlacer, whose place and clips it takes) */
 typedef struct {
     int device, w, h, subsamp, nsrc, F, keep_lane;
@@ -146,13 +146,14 @@ typedef struct {
     dsv1_deint dd_set;
     dsvg_ivtc *iv;                      /* the inverse telecine, in the deinterlacer's place (never both) */
     dsv1_ivtc iv_set;
-    int conv_frames;                    /* frames per source the converter's clips hold */
+    int conv_frames;                    /* frames per source the converter's clips, and the levels', hold */
+    dsvg_levels *lv;                    /* directly behind the converter; its clips are sized as the converter's */
     dsvg_denoise *dn;
     dsv1_denoise dn_set;
     dsvg_orient *orn;
     int orient;                         /* the code set (0: no pass) */
     dsvg_reframe *rf;
-    void *clip[5][2];
+    void *clip[6][2];
 } dsv1_srcchain;
 void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp, int nsrc, int F, int keep_lane);
 void dsv1_srcchain_close(dsv1_srcchain *c);            /* waits for the lane; frees everything */
@@ -170,13 +171,15 @@ int  dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf);
 /* a code valid at the chain's subsampling; 0: none.  The oriented geometry stays, the raw one becomes what the inverse code makes of
  * it.  DSVG_ERR_ARG, chain as it was, while a pass other than the reframe is set */
 int  dsv1_srcchain_set_orient(dsv1_srcchain *c, int orient);
+/* tables, or NULL / the identity: none.  Forgets the deinterlacer's history, the inverse telecine's and the noise filter's state */
+int  dsv1_srcchain_set_levels(dsv1_srcchain *c, const dsv1_levels *lv);
 int  dsv1_reframe_is_identity(const dsv1_reframe *rf);  /* dsv1_reframe.c: window = input = canvas at 0, 0 */
 int  dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source);                 /* DSVG_ERR_ARG where the pass is not set */
 int  dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source);
-static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->dd || c->iv || c->dn || c->orn || c->rf; }
+static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->lv || c->dd || c->iv || c->dn || c->orn || c->rf; }
 int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, F / 2 at field rate, 5 F / 4 in front of the inverse telecine */
 size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c); /* ... and the bytes of a call's clip */
-/* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> deinterlace -> denoise ->
+/* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> levels -> deinterlace -> denoise ->
  * orient -> reframe are set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where nothing ran) */
 int  dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out);
 /* the standalone clip calls: one pass (DSV1_SRC_*; SCALE: a scaler's geometry 0) over n frames on a lane of the call's own.  in[0] the

@@ -444,6 +444,14 @@ int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)
     return dsv1_srcchain_deinterlace_reset(&r->src, source);
 }
 
+/* the levelled clip stands for the source everywhere behind the chain */
+int dsv1_resladder_set_levels(dsv1_resladder *r, const dsv1_levels *lv)
+{
+    if (!r) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_levels with calls in flight"); return DSVG_ERR_ARG; }
+    return dsv1_srcchain_set_levels(&r->src, lv);
+}
+
 int dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn)
 {
     if (!r) return DSVG_ERR_ARG;

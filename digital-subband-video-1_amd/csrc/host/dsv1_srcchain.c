@@ -1,4 +1,4 @@
-/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> deinterlace or inverse telecine -> denoise -> orient -> reframe on one lane (dsvg_pixfmt.h), for
+/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> levels -> deinterlace or inverse telecine -> denoise -> orient -> reframe on one lane (dsvg_pixfmt.h), for
  * batches (dsv1_enc.c) and resolution ladders (dsv1_scale.c), and the sequence the standalone clip calls share. */
 #include "dsv1_host.h"
 
@@ -24,6 +24,7 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
 {
     if (c->lane) (void)dsvg_lane_sync(c->lane);        /* (the passes' kernels read the memory their destroy frees) */
     dsvg_pixconv_destroy(c->pc);
+    dsvg_levels_destroy(c->lv);
     dsvg_deint_destroy(c->dd);
     dsvg_ivtc_destroy(c->iv);
     dsvg_denoise_destroy(c->dn);
@@ -33,35 +34,38 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
     memset(c, 0, sizeof(*c));
 }
 
-/* the frames per source the converter writes: what a call brings.  (Never fewer than F: a field-rate deinterlacer may be cleared
+/* the frames per source the converter and the levels write: what a call brings.  (Never fewer than F: a field-rate deinterlacer may be cleared
  * behind a converter that stays.) */
 static int conv_frames_for(const dsv1_srcchain *c, int with_ivtc) { return with_ivtc ? c->F / 4 * 5 : c->F; }
 
 /* pass p (NULL: none) takes slot k (DSV1_SRC_*): its two clips first, and only then does the pass set before go, with its clips.
- * The inverse telecine lives in the deinterlacer's slot; it changes what a call brings, so where a converter is installed its two
- * clips are allocated again for that many frames in the same step.  On an error the chain is as it was and p is still the caller's. */
+ * The inverse telecine lives in the deinterlacer's slot; it changes what a call brings, so where a converter or the levels are
+ * installed their two clips are allocated again for that many frames in the same step.  On an error the chain is as it was and p is still the caller's. */
 static int chain_install(dsv1_srcchain *c, int k, void *p)
 {
     const int slot = k == DSV1_SRC_IVTC ? DSV1_SRC_DEINTERLACE : k;
     const size_t fb = k == DSV1_SRC_REFRAME ? c->ofb : k == DSV1_SRC_ORIENT ? c->mfb : c->fb;
     const int cf = conv_frames_for(c, k == DSV1_SRC_IVTC ? p != NULL : c->iv != NULL);
-    const int reconv = k == DSV1_SRC_IVTC && c->pc && cf != c->conv_frames;
-    void *clip[2] = {NULL, NULL}, *conv[2] = {NULL, NULL};
+    const int resize = k == DSV1_SRC_IVTC && cf != c->conv_frames;
+    const int reconv = resize && c->pc, relev = resize && c->lv;
+    void *clip[2] = {NULL, NULL}, *conv[2] = {NULL, NULL}, *lev[2] = {NULL, NULL};
     int rc, j;
     if (!p && !c->clip[slot][0]) return DSVG_OK;
     rc = dsv1_srcchain_lane(c);
-    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], fb * (size_t)c->nsrc * (size_t)(k == DSV1_SRC_CONVERT ? cf : c->F));
+    for (j = 0; p && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &clip[j], fb * (size_t)c->nsrc * (size_t)(k == DSV1_SRC_CONVERT || k == DSV1_SRC_LEVELS ? cf : c->F));
     for (j = 0; reconv && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &conv[j], fb * (size_t)c->nsrc * (size_t)cf);
+    for (j = 0; relev && j < 2 && !rc; j++) rc = dsvg_lane_alloc(c->lane, &lev[j], fb * (size_t)c->nsrc * (size_t)cf);
     if (!rc) rc = dsvg_lane_sync(c->lane);
     if (rc) {
-        if (c->lane) for (j = 0; j < 2; j++) { (void)dsvg_lane_free(c->lane, clip[j]); (void)dsvg_lane_free(c->lane, conv[j]); }
+        if (c->lane) for (j = 0; j < 2; j++) { (void)dsvg_lane_free(c->lane, clip[j]); (void)dsvg_lane_free(c->lane, conv[j]); (void)dsvg_lane_free(c->lane, lev[j]); }
         chain_release(c);
         return rc;
     }
     switch (k) {
-    case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; c->conv_frames = p ? cf : 0; break;
+    case DSV1_SRC_CONVERT:     dsvg_pixconv_destroy(c->pc); c->pc = (dsvg_pixconv *)p; break;
     case DSV1_SRC_DEINTERLACE: dsvg_deint_destroy(c->dd); c->dd = (dsvg_deint *)p; break;
     case DSV1_SRC_IVTC:        dsvg_ivtc_destroy(c->iv); c->iv = (dsvg_ivtc *)p; break;
+    case DSV1_SRC_LEVELS:      dsvg_levels_destroy(c->lv); c->lv = (dsvg_levels *)p; break;
     case DSV1_SRC_ORIENT:      dsvg_orient_destroy(c->orn); c->orn = (dsvg_orient *)p; break;
     case DSV1_SRC_REFRAME:     dsvg_reframe_destroy(c->rf); c->rf = (dsvg_reframe *)p; break;
     default:                   dsvg_denoise_destroy(c->dn); c->dn = (dsvg_denoise *)p; break;
@@ -73,8 +77,12 @@ static int chain_install(dsv1_srcchain *c, int k, void *p)
             (void)dsvg_lane_free(c->lane, c->clip[DSV1_SRC_CONVERT][j]);
             c->clip[DSV1_SRC_CONVERT][j] = conv[j];
         }
+        if (relev) {
+            (void)dsvg_lane_free(c->lane, c->clip[DSV1_SRC_LEVELS][j]);
+            c->clip[DSV1_SRC_LEVELS][j] = lev[j];
+        }
     }
-    if (reconv) c->conv_frames = cf;
+    c->conv_frames = cf;
     chain_release(c);
     return DSVG_OK;
 }
@@ -88,6 +96,21 @@ int dsv1_srcchain_set_format(dsv1_srcchain *c, const dsv1_pix_layout *L, const d
     if ((rc = chain_install(c, DSV1_SRC_CONVERT, pc))) { dsvg_pixconv_destroy(pc); return rc; }
     c->raw_fb = L ? L->frame_bytes : R ? R->frame_bytes : 0;
     return DSVG_OK;
+}
+
+/* directly behind the converter, at the raw geometry.  The pictures every pass behind it sees change meaning: their history and state
+ * go (the sessions allow the call only with nothing in flight) */
+int dsv1_srcchain_set_levels(dsv1_srcchain *c, const dsv1_levels *lv)
+{
+    dsvg_levels *l = NULL;
+    int rc;
+    if (lv && dsv1_levels_is_identity(lv)) lv = NULL;
+    if (!lv && !c->lv) return DSVG_OK;                  /* (none before, none now: the pictures keep their meaning) */
+    if (lv && (rc = dsvg_levels_create(&l, c->device, lv, c->w, c->h, c->subsamp))) return rc;
+    if ((rc = chain_install(c, DSV1_SRC_LEVELS, l))) { dsvg_levels_destroy(l); return rc; }
+    if (c->dd && (rc = dsvg_deint_reset(c->dd, -1))) return rc;
+    if (c->iv && (rc = dsvg_ivtc_reset(c->iv, -1))) return rc;
+    return c->dn ? dsvg_denoise_reset(c->dn, -1) : DSVG_OK;
 }
 
 int dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di)
@@ -133,7 +156,7 @@ int dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf)
 {
     dsvg_reframe *r = NULL;
     int rc;
-    if (c->pc || c->dd || c->iv || c->dn || c->orn) return DSVG_ERR_ARG;
+    if (c->pc || c->lv || c->dd || c->iv || c->dn || c->orn) return DSVG_ERR_ARG;
     if (rf && (rf->out_w != c->ow || rf->out_h != c->oh)) return DSVG_ERR_ARG;
     if (rf && dsv1_reframe_is_identity(rf)) rf = NULL;
     if (rf && (rc = dsvg_reframe_create(&r, c->device, rf, c->subsamp))) return rc;
@@ -149,7 +172,7 @@ int dsv1_srcchain_set_orient(dsv1_srcchain *c, int orient)
 {
     dsvg_orient *o = NULL;
     int rc, rw, rh;
-    if (c->pc || c->dd || c->iv || c->dn) return DSVG_ERR_ARG;
+    if (c->pc || c->lv || c->dd || c->iv || c->dn) return DSVG_ERR_ARG;
     if (!dsv1_orient_valid(orient, c->subsamp) || dsv1_orient_dims(dsv1_orient_inverse(orient), c->mw, c->mh, &rw, &rh)) return DSVG_ERR_ARG;
     if (orient && (rc = dsvg_orient_create(&o, c->device, orient, rw, rh, c->subsamp))) return rc;
     if ((rc = chain_install(c, DSV1_SRC_ORIENT, o))) { dsvg_orient_destroy(o); return rc; }
@@ -186,6 +209,10 @@ int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device
     if (c->pc) {
         if ((rc = dsvg_pixconv_run(c->pc, st, clip, c->nsrc * nin, c->clip[DSV1_SRC_CONVERT][par]))) return rc;
         clip = c->clip[DSV1_SRC_CONVERT][par];
+    }
+    if (c->lv) {
+        if ((rc = dsvg_levels_run(c->lv, st, clip, c->nsrc * nin, c->clip[DSV1_SRC_LEVELS][par]))) return rc;
+        clip = c->clip[DSV1_SRC_LEVELS][par];
     }
     if (c->dd) {
         if ((rc = dsvg_deint_run(c->dd, st, clip, nin, c->clip[DSV1_SRC_DEINTERLACE][par]))) return rc;
@@ -228,6 +255,7 @@ int dsv1_pass_clip(int device, int kind, void *pass, int n, const dsv1_clip_io *
         case DSV1_SRC_CONVERT:     rc = dsvg_pixconv_run((dsvg_pixconv *)pass, st, din[0], n, dout[0]); break;
         case DSV1_SRC_DEINTERLACE: rc = dsvg_deint_clip((dsvg_deint *)pass, st, din[0], n, din[1], dout[0]); break;
         case DSV1_SRC_DENOISE:     rc = dsvg_denoise_clip((dsvg_denoise *)pass, st, din[0], n, din[1], dout[1], dout[0]); break;
+        case DSV1_SRC_LEVELS:      rc = dsvg_levels_run((dsvg_levels *)pass, st, din[0], n, dout[0]); break;
         case DSV1_SRC_ORIENT:      rc = dsvg_orient_run((dsvg_orient *)pass, st, din[0], n, dout[0]); break;
         case DSV1_SRC_REFRAME:     rc = dsvg_reframe_run((dsvg_reframe *)pass, st, din[0], n, dout[0]); break;
         default:                   rc = dsvg_scaler_run((dsvg_scaler *)pass, st, 0, din[0], n, dout[0]); break;

@@ -646,7 +646,7 @@ int  dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source);
  *   state_out: receives the state, or NULL; it may be state_in.  src, states and dst host or device memory (on_device); match_out [n]
  *   and drop_out [n / 5] always host memory, either may be NULL.  dst must not overlap src.  Synchronous; any w, h >= 1 within the bound
  *   above and every subsampling the library knows; nothing outside the frames and the states is read or written.
- * SESSIONS.  The pass takes the deinterlacer's place in the source chain: convert -> inverse telecine -> denoise -> reframe.  It is
+ * SESSIONS.  The pass takes the deinterlacer's place in the source chain: convert -> levels -> inverse telecine -> denoise -> orient -> reframe.  It is
  * exclusive with the deinterlacer: setting either while the other is set is DSVG_ERR_ARG with the settings left as they were.  Setting,
  * changing or clearing it forgets its own state and the noise filter's (the pictures change meaning); _reset forgets the state of one
  * source (-1: every source): its next picture is a first picture.  The setters and _reset only with nothing in flight (DSVG_ERR_ARG
@@ -746,7 +746,7 @@ int  dsv1_resladder_denoise_reset(dsv1_resladder *r, int source);
  * when nothing is content or the rounding leaves nothing; DSVG_ERR_ARG for thresh outside 0 .. 254 or align not a power of two in
  * 1 .. 64.  Known consequence of the rule: a column's mean includes the rows of horizontal bars (and a row's the columns of vertical
  * ones), so a letterboxed picture needs more light in a column to count than the limit says.  dsv1_detect_bars_clip does both steps.
- * SESSIONS.  The reframe is the LAST pass of the source chain: convert -> deinterlace -> denoise -> reframe, then the scales of a
+ * SESSIONS.  The reframe is the LAST pass of the source chain: convert -> levels -> deinterlace -> denoise -> orient -> reframe, then the scales of a
  * resolution ladder or the frame load.  The passes in front of it run at in_w x in_h; denoising rows that are then cut away is accepted
  * waste.  dsv1_batch_set_source_reframe (plain batches, quality ladders, chain mode): out_w x out_h must be the batch's geometry.  It
  * changes the geometry the other passes are built for, so it may be set, changed or cleared only with nothing in flight, nothing
@@ -810,7 +810,7 @@ int  dsv1_resladder_open_reframed(dsv1_resladder **out, const DSV_META *src, con
  * +-65536: (+,+) NONE, (-,+) HFLIP, (+,-) VFLIP, (-,-) ROT180.  With a == d == 0, b and c each +-65536, as (b, c): (+,+) TRANSPOSE,
  * (+,-) ROT90, (-,+) ROT270, (-,-) TRANSVERSE.  Scale, shear and other angles -- and every argument out of range -- are DSVG_ERR_ARG.
  * dsv1_orient_clip: src and dst host or device memory (on_device), w x h the frames that come in; synchronous; code 0 copies.
- * SESSIONS.  The pass sits between the noise filter and the reframe: convert -> deinterlace or inverse telecine -> denoise -> orient ->
+ * SESSIONS.  The pass sits between the noise filter and the reframe: convert -> levels -> deinterlace or inverse telecine -> denoise -> orient ->
  * reframe.  The deinterlacer has to see rows as fields, so it comes first; the reframe's window is chosen on the upright picture, so it
  * comes after.  dsv1_batch_set_source_orient (plain batches, quality ladders, chain mode): the ORIENTED geometry is the reframe's input,
  * or the batch's geometry without one; clips then come in at the RAW geometry, dsv1_orient_dims(dsv1_orient_inverse(orient), ...) of
@@ -838,6 +838,71 @@ int  dsv1_batch_set_source_orient(dsv1_batch *b, int orient);                   
 int  dsv1_resladder_open_oriented(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *rf, const dsv1_pix_format *pf,
                                   int src_subsamp, const dsv1_rgb_format *rgb, const dsv1_res_rung *rungs, int ngeoms, int device,
                                   int nsources, int frames_per_call, int filter);
+
+/* ---- extension: levels -- range conversion and per-plane tables; histograms (csrc/k_levels.hip; stated in numpy in tests/_levels.py) ----
+ * Phone, webcam and MJPEG sources are full-range YCbCr; coded as they are they play back with crushed blacks and clipped whites.  Black
+ * and white point correction and a saturation trim are the same kind of work: pointwise per plane.  One definition covers them, three
+ * 256-entry tables, one per plane (Y, U, V); every content is valid.
+ * DEFINITION.  out_p[i] = lut[p][in_p[i]] for every sample i of plane p.  Frames are the tightly packed planar 8-bit frames every other
+ * entry point reads, n in and n out at the same geometry; every subsampling the library knows, any w, h >= 1.  The identity
+ * (lut[p][v] == v everywhere) means "off".
+ * BUILDERS (host only; exact integers, no floating point, nothing depends on a libm).  r(a / b) rounds the exact rational half up:
+ * floor((2 a + b) / (2 b)) with a true floor for negative a, the r() of the RGB section.  clamp() is to 0 .. 255.
+ *   dsv1_levels_identity(lv)                    lut[p][v] = v.
+ *   dsv1_levels_range(lv, src_full, dst_full)   equal flags: the identity.
+ *       full -> limited (1, 0):  Y = 16 + r(v * 219 / 255)               C = 128 + r((v - 128) * 224 / 255)
+ *       limited -> full (0, 1):  Y = clamp(r((v - 16) * 255 / 219))      C = clamp(128 + r((v - 128) * 255 / 224))
+ *     Full to limited maps 0 and 255 to 16 and 235 (luma), 16 and 240 (chroma).  Limited to full: THE CLAMP BINDS -- luma below 16
+ *     and above 235 saturates, chroma 240 gives 255, and chroma 16 gives 1 (128 - 127.5 rounded half up), not 0.  Flags outside
+ *     0 / 1: DSVG_ERR_ARG.
+ *   dsv1_levels_adjust(lv, in_black, in_white, out_black, out_white, sat_q8)
+ *       luma:   v <= in_black gives out_black; v >= in_white gives out_white; else
+ *               out_black + r((v - in_black) * (out_white - out_black) / (in_white - in_black))
+ *       chroma: clamp(128 + r((v - 128) * sat_q8 / 256))                  (sat_q8 256: unchanged; 0: grey)
+ *     Valid: 0 <= in_black < in_white <= 255, 0 <= out_black <= out_white <= 255, 0 <= sat_q8 <= 1024.
+ *   dsv1_levels_compose(a, b, out)              out[p][v] = b[p][a[p][v]]: a first.  out may be a or b.
+ *   dsv1_levels_is_identity(lv)                 1 / 0.
+ * Every builder returns DSVG_ERR_ARG for an invalid argument (NULL included) and leaves *lv untouched then.  Gamma and other curves
+ * are the caller's tables: no builder is offered for them.
+ * HISTOGRAM.  hist[t][p][v] is the number of samples of plane p of frame t with value v: uint32_t [n][3][256], exact for every size
+ * the library takes.  dsv1_histogram_clip computes it on the GPU; hist is always host memory and the call is synchronous.
+ *   dsv1_range_from_histogram(hist, n, ppm, &full), host only: outside = the luma samples < 16 or > 235 plus the chroma samples < 16
+ *     or > 240, total = every sample, both summed over the n frames; full = outside * 1000000 > (uint64_t)ppm * total.  ppm outside
+ *     0 .. 1000000 or n < 1: DSVG_ERR_ARG.  Returns DSVG_OK.
+ *   dsv1_points_from_histogram(hist, n, low_ppm, high_ppm, &black, &white), host only, luma only, summed over the frames: black is the
+ *     largest b with count(Y < b) * 1e6 <= low_ppm * total_Y, white the smallest w with count(Y > w) * 1e6 <= high_ppm * total_Y,
+ *     both in 0 .. 255.
+ *     Returns 1 when black < white, else 0 with both zero; ppm outside 0 .. 1000000, n < 1 or NULL: DSVG_ERR_ARG.
+ *   dsv1_detect_range_clip is dsv1_histogram_clip and then dsv1_range_from_histogram.
+ * dsv1_levels_clip: src and dst host or device memory (on_device); synchronous; dst may equal src, any other overlap is the caller's
+ * error; a plane whose table is the identity is still copied.  Invalid arguments -- w, h < 1, an unknown subsampling, NULL pointers,
+ * n < 1 -- are DSVG_ERR_ARG before any device work.
+ * SESSIONS.  The pass sits directly behind the converter or the RGB import and in front of the deinterlacer or the inverse telecine, so
+ * their thresholds and the noise filter's see standard-range pictures: convert -> levels -> deinterlace or inverse telecine ->
+ * denoise -> orient -> reframe.  It runs at the raw geometry over the frames a call brings.  dsv1_batch_set_source_levels (plain
+ * batches, quality ladders, chain mode) and dsv1_resladder_set_levels: NULL or the identity clears the pass -- no pass, no copy, and no
+ * lane if nothing else needs one.  It is set AFTER the reframe and the orientation (dsv1_batch_set_source_reframe and _orient are
+ * refused while levels are set), otherwise in any order relative to the format, the deinterlacer, the inverse telecine and the noise
+ * filter.  Setting, changing or clearing it forgets the deinterlacer's history, the inverse telecine's state and the noise filter's
+ * state of every source: the pictures change meaning.  Only with nothing in flight (and nothing staged), else DSVG_ERR_ARG with the
+ * setting left as it was.  dsv1_batch_stage is refused while it is set; clip ownership is dsv1_batch_set_source_format's.  In a
+ * resolution ladder the levelled clip stands for the source everywhere behind it, get_src_sse / get_src_ssim included.
+ * Not offered: the drop-in dsv_enc; levels in the decoders' output pass; hue rotation or any operation that mixes planes; tables
+ * that change from picture to picture inside one call's clip; a histogram or auto-levels inside a session; fusing the tables into the
+ * converter's launch. */
+typedef struct { uint8_t lut[3][256]; } dsv1_levels;     /* Y, U, V; every content is valid */
+int  dsv1_levels_identity(dsv1_levels *lv);
+int  dsv1_levels_range(dsv1_levels *lv, int src_full, int dst_full);
+int  dsv1_levels_adjust(dsv1_levels *lv, int in_black, int in_white, int out_black, int out_white, int sat_q8);
+int  dsv1_levels_compose(const dsv1_levels *a, const dsv1_levels *b, dsv1_levels *out);
+int  dsv1_levels_is_identity(const dsv1_levels *lv);
+int  dsv1_range_from_histogram(const uint32_t *hist, int n, int ppm, int *full);
+int  dsv1_points_from_histogram(const uint32_t *hist, int n, int low_ppm, int high_ppm, int *black, int *white);
+int  dsv1_levels_clip(int device, const void *src, int w, int h, int subsamp, int n, void *dst, const dsv1_levels *lv, int on_device);
+int  dsv1_histogram_clip(int device, const void *src, int w, int h, int subsamp, int n, uint32_t *hist, int on_device);
+int  dsv1_detect_range_clip(int device, const void *src, int w, int h, int subsamp, int n, int ppm, int *full, int on_device);
+int  dsv1_batch_set_source_levels(dsv1_batch *b, const dsv1_levels *lv);               /* NULL or the identity = off */
+int  dsv1_resladder_set_levels(dsv1_resladder *r, const dsv1_levels *lv);
 
 /* ---- extension: debug overlays (csrc/k_drawinfo.hip; stated in Python in tests/_drawinfo.py) ----
  * The reference decoder's -drawinfo (draw_info dsv_decoder.c:147-243), drawn on the device ahead of the output pass: what an encoder
