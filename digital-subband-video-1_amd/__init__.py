@@ -263,6 +263,41 @@ class Levels(_C.Structure):
         return _np.frombuffer(bytes(self), dtype=_np.uint8).reshape(3, 256).copy()
 
 
+class Overlay(_C.Structure):
+    """dsv1_overlay: one timed bitmap of an overlay list (include/dsv1_api.h, Overlays).  planes: numpy uint8, the bitmap's Y (w x h), U,
+    V (chroma size of w x h at the session's subsampling) and A (w x h, straight alpha) one after the other -- overlay_from_rgba makes
+    them from an RGBA image -- kept alive with the object; None leaves the pointer NULL.  x, y: top left on the canvas; source: -1 for
+    every source; t0, dur: first picture and number of pictures (0: for ever); fade_in, fade_out in pictures (0 .. 65535); opacity
+    0 .. 256."""
+    _fields_ = [("planes", _C.c_void_p), ("w", _C.c_int), ("h", _C.c_int), ("x", _C.c_int), ("y", _C.c_int), ("source", _C.c_int),
+                ("opacity", _C.c_int), ("t0", _C.c_int64), ("dur", _C.c_uint32), ("fade_in", _C.c_uint16), ("fade_out", _C.c_uint16),
+                ("reserved", _C.c_int)]
+
+    def __init__(self, planes, w, h, x=0, y=0, source=-1, t0=0, dur=0, fade_in=0, fade_out=0, opacity=256, reserved=0):
+        if not 0 <= fade_in <= 65535 or not 0 <= fade_out <= 65535 or not 0 <= dur < 1 << 32:
+            raise ValueError("Overlay: fade_in and fade_out are 0 .. 65535, dur 0 .. 2^32 - 1")
+        self._keep = None if planes is None else _np.ascontiguousarray(planes, dtype=_np.uint8).reshape(-1)
+        super().__init__(None if planes is None else self._keep.ctypes.data, w, h, x, y, source, opacity, t0, dur, fade_in, fade_out,
+                         reserved)
+
+
+class OverlayItem(_C.Structure):
+    """dsv1_overlay_item: one item of a call's overlay plan (overlay_plan)"""
+    _fields_ = [("overlay", _C.c_int), ("source", _C.c_int), ("frame", _C.c_int), ("op", _C.c_int), ("layer", _C.c_int)]
+
+
+def _overlay_array(overlays):
+    """(ctypes array of dsv1_overlay or None, n); the Overlay objects -- and so their bitmaps -- outlive the call that uses it"""
+    ovs = list(overlays) if overlays is not None else []
+    if not ovs:
+        return None, 0
+    arr = (Overlay * len(ovs))()
+    for i, o in enumerate(ovs):
+        _C.memmove(_C.byref(arr, i * _C.sizeof(Overlay)), _C.byref(o), _C.sizeof(Overlay))
+    arr._keep = ovs
+    return arr, len(ovs)
+
+
 class BlockInfo(_C.Structure):
     """dsv1_blockinfo: one block's side information (packet_blockinfo, draw_info_clip)"""
     _fields_ = [("mvx", _C.c_int16), ("mvy", _C.c_int16), ("mode", _C.c_uint8), ("submask", _C.c_uint8), ("stable", _C.c_uint8),
@@ -453,6 +488,20 @@ def lib():
         L.dsv1_detect_range_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int), _C.c_int]
         L.dsv1_batch_set_source_levels.argtypes = [_C.c_void_p, _C.POINTER(Levels)]
         L.dsv1_resladder_set_levels.argtypes = [_C.c_void_p, _C.POINTER(Levels)]
+        L.dsv1_overlay_bytes.restype = _C.c_size_t
+        L.dsv1_overlay_bytes.argtypes = [_C.c_int] * 3
+        L.dsv1_overlay_valid.argtypes = [_C.POINTER(Overlay)] + [_C.c_int] * 4
+        L.dsv1_overlay_opacity_at.argtypes = [_C.POINTER(Overlay), _C.c_int64]
+        L.dsv1_overlay_plan.restype = _C.c_longlong
+        L.dsv1_overlay_plan.argtypes = [_C.POINTER(Overlay), _C.c_int, _C.c_int, _C.c_int, _C.POINTER(_C.c_int64), _C.c_int, _C.c_int, _C.c_int,
+                                        _C.POINTER(OverlayItem), _C.c_longlong, _C.POINTER(_C.c_int)]
+        L.dsv1_overlay_from_rgba.argtypes = [_C.c_void_p] + [_C.c_int] * 7 + [_C.c_void_p]
+        L.dsv1_overlay_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(Overlay), _C.c_int, _C.c_int64,
+                                        _C.c_int]
+        L.dsv1_batch_set_source_overlays.argtypes = [_C.c_void_p, _C.POINTER(Overlay), _C.c_int]
+        L.dsv1_batch_overlay_seek.argtypes = [_C.c_void_p, _C.c_int, _C.c_int64]
+        L.dsv1_resladder_set_overlays.argtypes = [_C.c_void_p, _C.POINTER(Overlay), _C.c_int]
+        L.dsv1_resladder_overlay_seek.argtypes = [_C.c_void_p, _C.c_int, _C.c_int64]
         L.dsvg_dispatch_last.argtypes = [_C.POINTER(Dispatch)]
         L.dsvg_dispatch_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.POINTER(Dispatch)]
         L.dsvg_inv_plan.argtypes = [_C.c_int] * 9 + [_C.c_uint, _C.c_int, _C.POINTER(InvStep), _C.c_int, _C.POINTER(_C.c_int)]
@@ -700,6 +749,18 @@ class Batch:
         and an orientation.  Between batches only; forgets the deinterlacer's history, the inverse telecine's and the noise filter's
         state of every source."""
         _chk(self.L.dsv1_batch_set_source_levels(self.h, _C.byref(lv) if lv is not None else None), "dsv1_batch_set_source_levels")
+
+    def set_source_overlays(self, overlays):
+        """from the next submit on the Overlay objects of the list are blended onto the clips on the GPU, in list order, as the LAST
+        source pass (dsv1_batch_set_source_overlays); None or an empty list switches it off.  The bitmaps are copied.  Every source's
+        picture counter starts at 0 and advances by frames_per_call per call.  Only with nothing in flight and nothing staged; one
+        invalid item refuses the list and leaves the setting as it was."""
+        arr, n = _overlay_array(overlays)
+        _chk(self.L.dsv1_batch_set_source_overlays(self.h, arr, n), "dsv1_batch_set_source_overlays")
+
+    def overlay_seek(self, source, t):
+        """the next picture of `source` (-1: every source) is picture t of the overlays' clock (dsv1_batch_overlay_seek)"""
+        _chk(self.L.dsv1_batch_overlay_seek(self.h, source, t), "dsv1_batch_overlay_seek")
 
     def set_source_reframe(self, rf):
         """from the next submit on the clips are rf.in_w x rf.in_h and reframed on the GPU onto the batch's geometry as Reframe rf says,
@@ -1307,6 +1368,63 @@ def detect_range_clip(clip, w, h, fmt, ppm=1000, device=0, n=None):
     return bool(full.value)
 
 
+def overlay_bytes(w, h, fmt):
+    """the bytes of an overlay bitmap's four planes (dsv1_overlay_bytes)"""
+    return int(lib().dsv1_overlay_bytes(w, h, fmt))
+
+
+def overlay_valid(ov, W, H, fmt, nsources=1):
+    """whether Overlay ov is valid on a canvas of W x H in format fmt in a session of nsources sources (dsv1_overlay_valid).  Host only."""
+    return bool(lib().dsv1_overlay_valid(_C.byref(ov), W, H, fmt, nsources))
+
+
+def overlay_opacity_at(ov, t):
+    """the opacity, 0 .. 256, Overlay ov has on picture t (dsv1_overlay_opacity_at).  Host only."""
+    return int(lib().dsv1_overlay_opacity_at(_C.byref(ov), t))
+
+
+def overlay_plan(overlays, nsources, frames, counters, W, H, fmt):
+    """the plan of one call (dsv1_overlay_plan): ([(overlay, source, frame, op, layer), ...] in the order source, frame, overlay,
+    layers).  counters: every source's picture counter at the call's first frame.  Host only."""
+    arr, n = _overlay_array(overlays)
+    cnt = (_C.c_int64 * nsources)(*[int(c) for c in counters])
+    L = lib()
+    need = L.dsv1_overlay_plan(arr, n, nsources, frames, cnt, W, H, fmt, None, 0, None)
+    if need < 0:
+        raise ValueError("dsv1_overlay_plan refused the list (rc=%d)" % need)
+    items = (OverlayItem * max(need, 1))()
+    layers = _C.c_int(0)
+    got = L.dsv1_overlay_plan(arr, n, nsources, frames, cnt, W, H, fmt, items, need, _C.byref(layers))
+    assert got == need
+    return [(it.overlay, it.source, it.frame, it.op, it.layer) for it in items[:need]], layers.value
+
+
+def overlay_from_rgba(rgba, w, h, order, matrix, full_range, fmt, pitch=0):
+    """an overlay bitmap's planes (numpy uint8: Y, U, V, A) from an RGB(A) image of w x h in memory order `order` (RGB_*), converted
+    with `matrix` (MATRIX_*) at full or limited range to format fmt (dsv1_overlay_from_rgba).  Host only."""
+    a = _np.ascontiguousarray(rgba, dtype=_np.uint8).reshape(-1)
+    out = _np.zeros(overlay_bytes(w, h, fmt), dtype=_np.uint8)
+    if not out.size or lib().dsv1_overlay_from_rgba(a.ctypes.data, pitch, w, h, order, matrix, full_range, fmt, out.ctypes.data):
+        raise ValueError("dsv1_overlay_from_rgba refused %dx%d order %d matrix %d range %d format 0x%x" % (w, h, order, matrix, full_range, fmt))
+    return out
+
+
+def overlay_clip(clip, w, h, fmt, overlays, t_first=0, device=0, n=None):
+    """blend the Overlay objects of a list onto packed planar 8-bit frames of w x h on the GPU (dsv1_overlay_clip); frame i is picture
+    t_first + i of source 0.  clip numpy uint8 [frames][frame bytes] (host): returns the composited copy; or a device pointer with n
+    frames: blended in place."""
+    L = lib()
+    arr, cnt = _overlay_array(overlays)
+    if n is not None:
+        _chk(L.dsv1_overlay_clip(device, clip, w, h, fmt, n, arr, cnt, t_first, 1), "dsv1_overlay_clip")
+        return clip
+    fb = w * h + 2 * _chroma_size(w, h, fmt)
+    a, frames = _host_clip(clip, fb)
+    res = a.reshape(frames, fb).copy()
+    _chk(L.dsv1_overlay_clip(device, res.ctypes.data, w, h, fmt, frames, arr, cnt, t_first, 0), "dsv1_overlay_clip")
+    return res
+
+
 def line_sums_clip(clip, w, h, fmt, device=0, n=None):
     """the sums of every luma row and column of a clip, on the GPU (dsv1_line_sums_clip): clip numpy uint8 [frames][frame_bytes]
     (host), or a device pointer with n frames.  Returns (row_sum numpy uint32 [frames][h], col_sum numpy uint32 [frames][w])."""
@@ -1641,6 +1759,17 @@ class ResLadder:
         None or the identity switches it off.  The levelled clip stands for the source everywhere behind it, src_psnr / src_ssim
         included.  Between calls only; contract as Batch.set_source_levels."""
         _chk(self.L.dsv1_resladder_set_levels(self.h, _C.byref(lv) if lv is not None else None), "dsv1_resladder_set_levels")
+
+    def set_overlays(self, overlays):
+        """from the next call on the Overlay objects of the list are blended onto the source clips on the GPU, on the canvas in front of
+        the scales (dsv1_resladder_set_overlays); None or an empty list switches it off.  The overlaid clip stands for the source
+        everywhere behind it, src_psnr / src_ssim included.  Between calls only; contract as Batch.set_source_overlays."""
+        arr, n = _overlay_array(overlays)
+        _chk(self.L.dsv1_resladder_set_overlays(self.h, arr, n), "dsv1_resladder_set_overlays")
+
+    def overlay_seek(self, source, t):
+        """the next picture of `source` (-1: every source) is picture t of the overlays' clock (dsv1_resladder_overlay_seek)"""
+        _chk(self.L.dsv1_resladder_overlay_seek(self.h, source, t), "dsv1_resladder_overlay_seek")
 
     def set_denoise(self, dn):
         """the sources pass the temporal noise filter on the GPU as Denoise dn says, behind the conversion and the deinterlacer and in

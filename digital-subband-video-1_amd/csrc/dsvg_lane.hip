@@ -100,6 +100,15 @@ extern "C" int dsvg_lane_copy_in(dsvg_lane *l, int buf, const void *dev, size_t 
     return lane_copy(l, buf, dev, bytes, dptr, hipMemcpyDeviceToDevice);
 }
 
+// device memory to device memory on the lane's stream, neither side an upload buffer (a pass that works in place on a copy)
+extern "C" int dsvg_lane_copy_dd(dsvg_lane *l, void *dst_dev, const void *src_dev, size_t bytes)
+{
+    if (!l || !dst_dev || !src_dev || !bytes) { dsvg_set_error("bad lane copy arguments"); return DSVG_ERR_ARG; }
+    HIPCHK(hipSetDevice(l->device));
+    HIPCHK(hipMemcpyAsync(dst_dev, src_dev, bytes, hipMemcpyDeviceToDevice, l->st));
+    return DSVG_OK;
+}
+
 extern "C" int dsvg_lane_download(dsvg_lane *l, void *host, const void *dptr, size_t bytes)
 {
     if (!l || !host || !dptr) return DSVG_ERR_ARG;

@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip, k_levels.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip, k_levels.hip, k_overlay.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -58,6 +58,7 @@ int  dsvg_lane_alloc(dsvg_lane *l, void **dptr, size_t bytes);
 int  dsvg_lane_free(dsvg_lane *l, void *dptr);
 int  dsvg_lane_upload(dsvg_lane *l, int buf, const void *host, size_t bytes, void **dptr);
 int  dsvg_lane_copy_in(dsvg_lane *l, int buf, const void *dev, size_t bytes, void **dptr);
+int  dsvg_lane_copy_dd(dsvg_lane *l, void *dst_dev, const void *src_dev, size_t bytes);       /* device to device on the stream */
 int  dsvg_lane_download(dsvg_lane *l, void *host, const void *dptr, size_t bytes);
 int  dsvg_lane_order(dsvg_lane *l, dsvg_ctx *ctx);
 int  dsvg_lane_sync(dsvg_lane *l);
@@ -173,6 +174,17 @@ typedef struct dsvg_histogram dsvg_histogram;
 int  dsvg_histogram_create(dsvg_histogram **out, int device, int w, int h, int subsamp);
 void dsvg_histogram_destroy(dsvg_histogram *g);
 int  dsvg_histogram_run(dsvg_histogram *g, void *stream, const void *src_dev, int nframes, void *hist_dev);
+/* ---- overlays (include/dsv1_api.h, Overlays; k_overlay.hip; the plan: dsvg_overlay_plan.h; host side: host/dsv1_overlay.c) ----
+ * A list of n valid placements on frames of w x h for nsrc sources: the bitmaps (and their chroma alpha planes) are packed into device
+ * memory at create, the caller's are free on return.  _run blends IN PLACE a call's clip, [source][nframes] frames, counters[s] the
+ * picture source s's first frame is: the call is planned (dsvg_overlay_plan), the table goes up on the stream into the buffer of call
+ * parity `par`, one launch per layer follows; nothing active: nothing is enqueued.  _active: the items such a call would blend (pure).
+ * In a session it is the LAST pass: ... -> orient -> reframe -> overlay. */
+typedef struct dsvg_overlay dsvg_overlay;
+int  dsvg_overlay_create(dsvg_overlay **out, int device, const dsv1_overlay *list, int n, int w, int h, int subsamp, int nsrc);
+void dsvg_overlay_destroy(dsvg_overlay *o);
+long long dsvg_overlay_active(const dsvg_overlay *o, int nframes, const int64_t *counters);
+int  dsvg_overlay_run(dsvg_overlay *o, void *stream, int par, void *clip_dev, int nframes, const int64_t *counters);
 typedef struct dsvg_linesums dsvg_linesums;
 int  dsvg_linesums_create(dsvg_linesums **out, int device, int w, int h, int subsamp);
 void dsvg_linesums_destroy(dsvg_linesums *s);

@@ -1220,7 +1220,7 @@ static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 }
 int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
 {
-    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, levels, a deinterlacer, a noise filter, an orientation or a reframe is set"); return DSVG_ERR_ARG; }
+    if (b && dsv1_srcchain_any(&b->src)) { dsv1_log(1, "dsv1_batch_stage is not offered while a source pixel format, levels, a deinterlacer, a noise filter, an orientation, a reframe or overlays are set"); return DSVG_ERR_ARG; }
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
@@ -1375,6 +1375,29 @@ int dsv1_batch_set_source_levels(dsv1_batch *b, const dsv1_levels *lv)
     return dsv1_srcchain_set_levels(&b->src, lv);
 }
 
+/* overlays: the LAST pass, on the batch's geometry; NULL or 0 clears it.  The list is checked whole before anything changes */
+int dsv1_batch_set_source_overlays(dsv1_batch *b, const dsv1_overlay *list, int n)
+{
+    const DSV_META *m;
+    int i;
+    if (!b || n < 0 || n > DSV1_MAX_OVERLAYS) return DSVG_ERR_ARG;
+    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_overlays with batches in flight or clips staged"); return DSVG_ERR_ARG; }
+    m = &b->enc[0].vidmeta;
+    for (i = 0; list && i < n; i++)
+        if (!dsv1_overlay_valid(&list[i], m->width, m->height, m->subsamp, b->nsrc)) {
+            dsv1_log(1, "dsv1_batch_set_source_overlays: item %d is not a valid overlay on %dx%d, subsampling 0x%x, %d sources", i, m->width, m->height, m->subsamp, b->nsrc);
+            return DSVG_ERR_ARG;
+        }
+    return dsv1_srcchain_set_overlays(&b->src, list, n);
+}
+
+/* the next picture of `source` (-1: every source) is picture t of the overlays' clock */
+int dsv1_batch_overlay_seek(dsv1_batch *b, int source, int64_t t)
+{
+    if (!b) return DSVG_ERR_ARG;
+    return dsv1_srcchain_overlay_seek(&b->src, source, t);
+}
+
 /* tests: 1 while the batch's source chain holds a lane (a stream and device memory of its own), 0 with no pass set */
 int dsv1_batch_has_source_lane(const dsv1_batch *b) { return b && b->src.lane != NULL; }
 
@@ -1382,11 +1405,13 @@ int dsv1_batch_has_source_lane(const dsv1_batch *b) { return b && b->src.lane !=
  * read as a held clip until that batch's collect); the context's frame-load stream waits for the passes on the device */
 static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 {
+    const void *in = *yuv;
     int rc;
     if (!*yuv) return DSVG_ERR_ARG;
     if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
     if (b->pending[b->parity]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
     if ((rc = dsv1_srcchain_run(&b->src, b->parity, *yuv, yuv_on_device, yuv))) return rc;
+    if (*yuv == in) return DSVG_OK;                     /* (overlays alone and none active in this call: nothing was enqueued, the clip is the caller's still) */
     if ((rc = dsvg_lane_order(b->src.lane, b->ctx))) return rc;
     /* a plain device clip is the caller's again when submit returns */
     if (yuv_on_device == 1 && (rc = dsvg_lane_sync(b->src.lane))) return rc;
@@ -1396,9 +1421,10 @@ static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 int dsv1_batch_submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
     if (b && dsv1_srcchain_any(&b->src)) {
+        const void *in = yuv;
         int rc;
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
-        return batch_submit_impl(b, yuv, 1, out, 0, 1);
+        if (yuv != in) return batch_submit_impl(b, yuv, 1, out, 0, 1);
     }
     /* a device clip's chroma stays where it is (the coding kernels read it until the batch is collected) only when the caller
      * said it holds the clip that long: DSV1_CLIP_HELD.  A plain device clip is copied whole -- the call is done with it when
@@ -1464,8 +1490,9 @@ int dsv1_batch_encode(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF
     if (!b || !out) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_encode with batches in flight"); return DSVG_ERR_ARG; }
     if (dsv1_srcchain_any(&b->src)) {
+        const void *in = yuv;
         if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
-        yuv_on_device = 1;
+        if (yuv != in) yuv_on_device = 1;
     }
     if ((rc = batch_submit_impl(b, yuv, yuv_on_device, out, 0, 1))) return rc;
     return dsv1_batch_collect(b, out);

@@ -123,7 +123,7 @@ static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
     return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
 }
 
-/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, levels, deinterlacer, noise filter, orientation and reframe with their
+/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, levels, deinterlacer, noise filter, orientation, reframe and overlays with their
  * settings, and each pass's output clip per call parity (a batch of that parity reads the last one as a held clip until its collect).
  * A chain with no pass set holds no lane -- no stream, no device memory -- unless the session keeps it (keep_lane: a resolution
  * ladder uploads and scales on it).  The setters replace or (NULL) clear one pass; on an error the chain is as it was.  The session
@@ -133,7 +133,8 @@ static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
  * session's geometry.  Raw and oriented differ only while a transposing orientation is set, oriented and canvas only while a reframe
  * -- the LAST pass -- is set.  The reframe may be set, changed or cleared only while no other pass is set, the orientation only while
  * none but the reframe is (the session checks); the passes set after them resolve at w x h. */
-enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_ORIENT, DSV1_SRC_REFRAME, DSV1_SRC_LEVELS, DSV1_SRC_SCALE,
+enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_ORIENT, DSV1_SRC_REFRAME, DSV1_SRC_LEVELS, DSV1_SRC_OVERLAY,
+       DSV1_SRC_SCALE,
        DSV1_SRC_IVTC };                 /* (the inverse telecine: exclusive with the deinterlacer, whose place and clips it takes) */
 typedef struct {
     int device, w, h, subsamp, nsrc, F, keep_lane;
@@ -153,7 +154,11 @@ typedef struct {
     dsvg_orient *orn;
     int orient;                         /* the code set (0: no pass) */
     dsvg_reframe *rf;
-    void *clip[6][2];
+    /* the overlays: the LAST pass, on the canvas, IN PLACE on whatever clip of the chain's own reaches it; its two clips exist only
+     * once a caller's device clip reached it with no other pass set (copied there first).  ov_t[s]: source s's picture counter */
+    dsvg_overlay *ov;
+    int64_t *ov_t;
+    void *clip[7][2];
 } dsv1_srcchain;
 void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp, int nsrc, int F, int keep_lane);
 void dsv1_srcchain_close(dsv1_srcchain *c);            /* waits for the lane; frees everything */
@@ -176,11 +181,19 @@ int  dsv1_srcchain_set_levels(dsv1_srcchain *c, const dsv1_levels *lv);
 int  dsv1_reframe_is_identity(const dsv1_reframe *rf);  /* dsv1_reframe.c: window = input = canvas at 0, 0 */
 int  dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source);                 /* DSVG_ERR_ARG where the pass is not set */
 int  dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source);
-static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return c->pc || c->lv || c->dd || c->iv || c->dn || c->orn || c->rf; }
+/* a list of n valid placements on the canvas (the bitmaps are copied), or NULL / 0: none.  The counters start at 0.  It changes no
+ * geometry: any order relative to the other setters.  _seek: source s's (-1: every source's) next picture is t; DSVG_ERR_ARG where no
+ * list is set */
+int  dsv1_srcchain_set_overlays(dsv1_srcchain *c, const dsv1_overlay *list, int n);
+int  dsv1_srcchain_overlay_seek(dsv1_srcchain *c, int source, int64_t t);
+/* the passes that write a clip of their own (everything but the overlays) */
+static inline int dsv1_srcchain_writes(const dsv1_srcchain *c) { return c->pc || c->lv || c->dd || c->iv || c->dn || c->orn || c->rf; }
+static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return dsv1_srcchain_writes(c) || c->ov; }
 int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, F / 2 at field rate, 5 F / 4 in front of the inverse telecine */
 size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c); /* ... and the bytes of a call's clip */
 /* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> levels -> deinterlace -> denoise ->
- * orient -> reframe are set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where nothing ran) */
+ * orient -> reframe -> overlay are set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where
+ * nothing ran: no pass set, or overlays alone with none active in the call -- then host memory comes back as host memory unless the session keeps the lane) */
 int  dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out);
 /* the standalone clip calls: one pass (DSV1_SRC_*; SCALE: a scaler's geometry 0) over n frames on a lane of the call's own.  in[0] the
  * clip, in[1] an optional second input (the deinterlacer's prev, the filter's state_in); out[0] the result, out[1] the filter's

@@ -380,6 +380,12 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         if ((rc = dsv1_srcchain_run(&r->src, par, yuv, yuv_on_device, &dsrc))) return rc;
         if (!yuv_on_device) { r->up_bytes += dsv1_srcchain_bytes_in(&r->src); r->up_calls++; }
     }
+    if (dsrc == yuv && plain_dev && (r->q[DSVG_Q_XSSE].on || r->q[DSVG_Q_XSSIM].on)) {
+        /* (overlays alone and none active in this call: the clip came back as it went in; the figures read it until collect) */
+        void *d;
+        if ((rc = dsvg_lane_copy_in(r->src.lane, par, yuv, dsv1_srcchain_bytes_in(&r->src), &d))) return rc;
+        dsrc = d;
+    }
     /* the resladder's own memory is held until collect (a plain device clip: the sync at the end waits for whatever read it) */
     if (dsrc != yuv) yuv_on_device = DSV1_CLIP_HELD;
     for (g = 0; g < r->ngeom; g++) {
@@ -450,6 +456,26 @@ int dsv1_resladder_set_levels(dsv1_resladder *r, const dsv1_levels *lv)
     if (!r) return DSVG_ERR_ARG;
     if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_levels with calls in flight"); return DSVG_ERR_ARG; }
     return dsv1_srcchain_set_levels(&r->src, lv);
+}
+
+/* the overlaid clip stands for the source everywhere behind the chain: the scales read it, and so do the source-resolution figures */
+int dsv1_resladder_set_overlays(dsv1_resladder *r, const dsv1_overlay *list, int n)
+{
+    int i;
+    if (!r || n < 0 || n > DSV1_MAX_OVERLAYS) return DSVG_ERR_ARG;
+    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_overlays with calls in flight"); return DSVG_ERR_ARG; }
+    for (i = 0; list && i < n; i++)
+        if (!dsv1_overlay_valid(&list[i], r->src.ow, r->src.oh, r->src.subsamp, r->nsrc)) {
+            dsv1_log(1, "dsv1_resladder_set_overlays: item %d is not a valid overlay on %dx%d, subsampling 0x%x, %d sources", i, r->src.ow, r->src.oh, r->src.subsamp, r->nsrc);
+            return DSVG_ERR_ARG;
+        }
+    return dsv1_srcchain_set_overlays(&r->src, list, n);
+}
+
+int dsv1_resladder_overlay_seek(dsv1_resladder *r, int source, int64_t t)
+{
+    if (!r) return DSVG_ERR_ARG;
+    return dsv1_srcchain_overlay_seek(&r->src, source, t);
 }
 
 int dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn)

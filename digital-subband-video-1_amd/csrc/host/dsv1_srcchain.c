@@ -1,4 +1,4 @@
-/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> levels -> deinterlace or inverse telecine -> denoise -> orient -> reframe on one lane (dsvg_pixfmt.h), for
+/* dsv1_srcchain.c -- the source side of a session (dsv1_host.h): convert -> levels -> deinterlace or inverse telecine -> denoise -> orient -> reframe -> overlay on one lane (dsvg_pixfmt.h), for
  * batches (dsv1_enc.c) and resolution ladders (dsv1_scale.c), and the sequence the standalone clip calls share. */
 #include "dsv1_host.h"
 
@@ -30,6 +30,8 @@ void dsv1_srcchain_close(dsv1_srcchain *c)
     dsvg_denoise_destroy(c->dn);
     dsvg_orient_destroy(c->orn);
     dsvg_reframe_destroy(c->rf);
+    dsvg_overlay_destroy(c->ov);
+    free(c->ov_t);
     dsvg_lane_destroy(c->lane);                         /* (and the clips) */
     memset(c, 0, sizeof(*c));
 }
@@ -182,6 +184,44 @@ int dsv1_srcchain_set_orient(dsv1_srcchain *c, int orient)
     return DSVG_OK;
 }
 
+/* the overlays: behind everything, on the canvas; no geometry changes, so no other pass minds.  The pass's own two clips are allocated by
+ * the first call that needs them (dsv1_srcchain_run) and go with the list */
+int dsv1_srcchain_set_overlays(dsv1_srcchain *c, const dsv1_overlay *list, int n)
+{
+    dsvg_overlay *o = NULL;
+    int64_t *t = NULL;
+    int rc, j;
+    if (!list || n < 1) { list = NULL; n = 0; }
+    if (!n && !c->ov) return DSVG_OK;
+    if (n) {
+        if (!(t = (int64_t *)calloc((size_t)c->nsrc, sizeof(*t)))) return DSVG_ERR_NOMEM;
+        if ((rc = dsvg_overlay_create(&o, c->device, list, n, c->ow, c->oh, c->subsamp, c->nsrc)) || (rc = dsv1_srcchain_lane(c))) {
+            dsvg_overlay_destroy(o);
+            free(t);
+            return rc;
+        }
+    }
+    if (c->lane) (void)dsvg_lane_sync(c->lane);        /* (the old list's launches read its bitmaps) */
+    dsvg_overlay_destroy(c->ov);
+    free(c->ov_t);
+    c->ov = o; c->ov_t = t;
+    for (j = 0; j < 2 && !n; j++) {
+        (void)dsvg_lane_free(c->lane, c->clip[DSV1_SRC_OVERLAY][j]);
+        c->clip[DSV1_SRC_OVERLAY][j] = NULL;
+    }
+    chain_release(c);
+    return DSVG_OK;
+}
+
+int dsv1_srcchain_overlay_seek(dsv1_srcchain *c, int source, int64_t t)
+{
+    int s;
+    if (!c->ov || source < -1 || source >= c->nsrc) return DSVG_ERR_ARG;
+    for (s = 0; s < c->nsrc; s++)
+        if (source < 0 || source == s) c->ov_t[s] = t;
+    return DSVG_OK;
+}
+
 int dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source) { return c->dd ? dsvg_deint_reset(c->dd, source) : DSVG_ERR_ARG; }
 int dsv1_srcchain_ivtc_reset(dsv1_srcchain *c, int source) { return c->iv ? dsvg_ivtc_reset(c->iv, source) : DSVG_ERR_ARG; }
 int dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source) { return c->dn ? dsvg_denoise_reset(c->dn, source) : DSVG_ERR_ARG; }
@@ -199,13 +239,23 @@ size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c)
 int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out)
 {
     const int nin = dsv1_srcchain_frames_in(c);
+    /* the items the overlays would blend in this call */
+    const long long act = c->ov ? dsvg_overlay_active(c->ov, c->F, c->ov_t) : 0;
     void *st = dsvg_lane_stream(c->lane), *d;
-    int rc;
+    int rc, own = 0, s;                                 /* own: the clip lies in memory of the chain's */
     if (!c->lane || !clip || !out) return DSVG_ERR_ARG;
+    if (!act && !dsv1_srcchain_writes(c) && (on_device || !c->keep_lane)) {
+        /* overlays alone and none active: no upload, no copy, no launch -- the clip goes on as it came, only the pictures count */
+        for (s = 0; c->ov && s < c->nsrc; s++) c->ov_t[s] += c->F;
+        *out = clip;
+        return DSVG_OK;
+    }
     if (!on_device) {
         if ((rc = dsvg_lane_upload(c->lane, par, clip, dsv1_srcchain_bytes_in(c), &d))) return rc;
         clip = d;
+        own = 1;
     }
+    if (dsv1_srcchain_writes(c)) own = 1;
     if (c->pc) {
         if ((rc = dsvg_pixconv_run(c->pc, st, clip, c->nsrc * nin, c->clip[DSV1_SRC_CONVERT][par]))) return rc;
         clip = c->clip[DSV1_SRC_CONVERT][par];
@@ -233,6 +283,19 @@ int dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device
     if (c->rf) {
         if ((rc = dsvg_reframe_run(c->rf, st, clip, c->nsrc * c->F, c->clip[DSV1_SRC_REFRAME][par]))) return rc;
         clip = c->clip[DSV1_SRC_REFRAME][par];
+    }
+    if (c->ov) {
+        if (act) {
+            if (!own) {
+                /* the caller's device memory is never written: a copy into a clip of the pass first */
+                const size_t bytes = c->ofb * (size_t)c->nsrc * (size_t)c->F;
+                if (!c->clip[DSV1_SRC_OVERLAY][par] && (rc = dsvg_lane_alloc(c->lane, &c->clip[DSV1_SRC_OVERLAY][par], bytes))) return rc;
+                if ((rc = dsvg_lane_copy_dd(c->lane, c->clip[DSV1_SRC_OVERLAY][par], clip, bytes))) return rc;
+                clip = c->clip[DSV1_SRC_OVERLAY][par];
+            }
+            if ((rc = dsvg_overlay_run(c->ov, st, par, (void *)clip, c->F, c->ov_t))) return rc;
+        }
+        for (s = 0; s < c->nsrc; s++) c->ov_t[s] += c->F;
     }
     *out = clip;
     return DSVG_OK;

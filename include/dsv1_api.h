@@ -904,6 +904,81 @@ int  dsv1_detect_range_clip(int device, const void *src, int w, int h, int subsa
 int  dsv1_batch_set_source_levels(dsv1_batch *b, const dsv1_levels *lv);               /* NULL or the identity = off */
 int  dsv1_resladder_set_levels(dsv1_resladder *r, const dsv1_levels *lv);
 
+/* ---- extension: overlays -- logos, watermarks, bitmap subtitles and slates burned into the sources (csrc/k_overlay.hip; the plan:
+ * csrc/dsvg_overlay_plan.h; stated in numpy in tests/_overlay.py) ----
+ * Alpha compositing of a list of timed bitmaps, with fades, as the LAST source pass.  Exact integers; nothing here rounds in floating
+ * point.  (The decoders' draw_info below is a different thing: debug drawing on decoded pictures.)
+ * DEFINITION.  A BITMAP is four 8-bit planes, tightly packed in this order: Y (w x h), U and V (cw x ch, cw = rshift_up(w, hs), ch =
+ * rshift_up(h, vs) at the session's subsampling), A (w x h, straight alpha, not premultiplied).  A PLACEMENT (dsv1_overlay) puts it with
+ * its top left at x, y of the canvas -- the coded geometry, behind the reframe -- on pictures t0 .. t0 + dur - 1 (dur 0: for ever) of
+ * source `source` (-1: every source), at `opacity` 0 .. 256, fading in over fade_in pictures and out over fade_out.
+ *   The opacity of picture t (dsv1_overlay_opacity_at, host only): 0 for t < t0 and, with dur > 0, for t >= t0 + dur; otherwise
+ *     a = min(t - t0 + 1, fade_in + 1),  b = fade_out + 1 with dur == 0, else min(t0 + dur - t, fade_out + 1),
+ *     op = r(opacity * a * b / ((fade_in + 1) * (fade_out + 1))), r() the round-half-up of the levels section, in 64-bit arithmetic.
+ *   Chroma alpha: A_c[Y][X] = r(sum / count) over the bitmap's own alpha samples that chroma sample covers -- 1, 2 or 4 at 4:2:0,
+ *     1 .. 4 in a row at 4:1:1, fewer where an odd w or h ends inside the sample.  (Not weighted by anything but the count.)
+ *   The blend, for every plane and every sample the bitmap covers, alpha = A (luma) or A_c (chroma):
+ *     k = alpha * op (0 .. 65280),  out = (in * (65280 - k) + ov * k + 32640) / 65280, the division a floor -- 65280 = 256 * 255: a
+ *     shift, then an exact division by 255.  k == 0 gives in; alpha == 255 with op == 256 gives ov; the numerator stays below 2^24.
+ *     Samples outside every overlay keep their bytes.
+ *   Order: overlays composite in list order, later on top; each blend reads the result of the one before.
+ * VALID (dsv1_overlay_valid, host only, 1 / 0): w, h >= 1; 0 <= x, x + w <= W, 0 <= y, y + h <= H; x a multiple of 1 << hs and y of
+ * 1 << vs (w and h need not be); opacity in 0 .. 256; source in -1 .. S - 1; a subsampling the library knows (4:4:4, 4:2:2, 4:2:0,
+ * 4:1:1); reserved == 0; planes not NULL.  (fade_in and fade_out are 0 .. 65535 by their type.)  Anything else is DSVG_ERR_ARG before
+ * any device work.
+ * THE PLAN (dsv1_overlay_plan, host only, no device): the items (overlay, source, frame in call, op) with op > 0 of a call of F frames
+ * of S sources whose first pictures are counters[s], in the order source, frame, overlay, each with a layer: 1 + the largest layer of an
+ * earlier item of the same source and frame whose luma rectangle intersects it, 1 where there is none.  Items of one layer never touch
+ * the same byte; the pass is one launch per layer over every plane, source and frame of the call, sized by the items' area, and nothing
+ * at all -- no launch, no upload, no copy -- for a call in which nothing is active.  Returns the number of items (the first `room` are
+ * written; NULL / 0 counts) or DSVG_ERR_ARG; *nlayers is written when everything fitted.
+ * dsv1_overlay_clip: in place and synchronous, on host or device memory (on_device); frame i is picture t_first + i of source 0 (the
+ * list is valid for S == 1: source 0 or -1).
+ * dsv1_overlay_from_rgba (host only): an RGBA image of `pitch` bytes a row (0: tight) in one of the 4-byte or 3-byte packed orders
+ * (DSV1_RGB_*; planar orders: three tight planes of pitch bytes a row one after the other) -> the four planes into out_planes
+ * (dsv1_overlay_bytes(w, h, subsamp) bytes).  Y, U, V are the RGB import's: r() of the forward table, the chroma halved horizontally
+ * first and then vertically, (a + b + 1) >> 1 with the last column / row repeated -- at 4:1:1 horizontally twice; A is the alpha bytes,
+ * 255 for orders without alpha.
+ * SESSIONS.  The pass is the LAST of the source chain: convert -> levels -> deinterlace or inverse telecine -> denoise -> orient ->
+ * reframe -> overlay, then the scales of a resolution ladder or the frame load.  It changes no geometry, so it may be set, replaced or
+ * cleared in any order relative to the other passes -- but only with nothing in flight and nothing staged, else DSVG_ERR_ARG with the
+ * setting left as it was; one invalid item refuses the whole list the same way.  dsv1_batch_set_source_overlays (plain batches, quality
+ * ladders, chain mode): n in 0 .. DSV1_MAX_OVERLAYS; NULL or 0 clears -- no pass, and no lane if nothing else needs one.  The bitmaps are
+ * copied: the caller's memory is free on return.  Every source keeps a picture counter: 0 when a list is set, advanced by
+ * frames_per_call by every call, across calls as the noise filter's state is; dsv1_batch_overlay_seek(b, source or -1, t) sets it
+ * (DSVG_ERR_ARG where no list is set).  The clip: where it reaches the pass in memory of the chain's own (another pass's output, or the
+ * upload of a host clip) it is blended where it lies; a caller's device clip (plain or held) is first copied device-to-device into a
+ * clip of the pass, and is never written.  A call in which nothing is active, with no other pass set, takes the path of a batch with
+ * nothing set.  dsv1_batch_stage is refused while a list is set.  dsv1_resladder_set_overlays / _overlay_seek: the pass runs on the
+ * canvas in front of the scales, and the overlaid clip stands for the source everywhere behind it, get_src_sse / get_src_ssim included.
+ * Not offered: the drop-in dsv_enc; overlays in the decoders' output pass; overlays that move or scale; text rendering; premultiplied
+ * alpha; bitmaps partly off the canvas; replacing the list with batches in flight; alpha-weighted chroma. */
+#define DSV1_MAX_OVERLAYS 4096
+typedef struct {
+    const uint8_t *planes;      /* Y, U, V, A */
+    int w, h;
+    int x, y;                   /* top left on the canvas */
+    int source;                 /* -1: every source */
+    int opacity;                /* 0 .. 256 */
+    int64_t t0;                 /* the first picture */
+    uint32_t dur;               /* pictures; 0: for ever */
+    uint16_t fade_in, fade_out; /* pictures */
+    int reserved;               /* 0 */
+} dsv1_overlay;
+typedef struct { int overlay, source, frame, op, layer; } dsv1_overlay_item;
+size_t dsv1_overlay_bytes(int w, int h, int subsamp);           /* of a bitmap's four planes; 0 for invalid arguments */
+int  dsv1_overlay_valid(const dsv1_overlay *ov, int W, int H, int subsamp, int S);
+int  dsv1_overlay_opacity_at(const dsv1_overlay *ov, int64_t t);
+long long dsv1_overlay_plan(const dsv1_overlay *list, int n, int S, int F, const int64_t *counters, int W, int H, int subsamp,
+                            dsv1_overlay_item *items, long long room, int *nlayers);
+int  dsv1_overlay_from_rgba(const void *rgba, int pitch, int w, int h, int order, int matrix, int full_range, int subsamp, uint8_t *out_planes);
+int  dsv1_overlay_clip(int device, void *clip, int w, int h, int subsamp, int n, const dsv1_overlay *list, int count, int64_t t_first,
+                       int on_device);
+int  dsv1_batch_set_source_overlays(dsv1_batch *b, const dsv1_overlay *list, int n);   /* NULL or 0 = off */
+int  dsv1_batch_overlay_seek(dsv1_batch *b, int source, int64_t t);
+int  dsv1_resladder_set_overlays(dsv1_resladder *r, const dsv1_overlay *list, int n);
+int  dsv1_resladder_overlay_seek(dsv1_resladder *r, int source, int64_t t);
+
 /* ---- extension: debug overlays (csrc/k_drawinfo.hip; stated in Python in tests/_drawinfo.py) ----
  * The reference decoder's -drawinfo (draw_info dsv_decoder.c:147-243), drawn on the device ahead of the output pass: what an encoder
  * decided, on the decoded luma of every picture that has a reference (P pictures; I pictures and chroma are untouched, and so are the
