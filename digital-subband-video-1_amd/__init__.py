@@ -93,6 +93,8 @@ class HmeStep(_C.Structure):
 
 
 BATCH_NO_SMALL_SPLIT, BATCH_NO_PAR_ENQUEUE, BATCH_NO_LAZY_BORDER, BATCH_NO_MC_FUSION, BATCH_PROFILED = 1, 2, 4, 8, 16      # DSVG_BATCH_*
+DEC_NO_SYM, DEC_NO_SYM_I, DEC_ONE_STREAM, DEC_NO_MC_PATCH, DEC_NO_INPLACE_PRED, DEC_NO_SYM_OV, DEC_NO_MC_FUSION, DEC_PROFILED = (
+    1, 2, 4, 8, 16, 32, 64, 128)                                                                                           # DSVG_DEC_*
 
 
 class PicJob(_C.Structure):
@@ -121,6 +123,35 @@ class BatchRefused(RuntimeError):
     """dsvg_code_batch_plan did not answer with a plan: rc and text are what the coding call itself would return and set"""
     def __init__(self, rc, text):
         super().__init__("dsvg_code_batch_plan failed rc=%d: %s" % (rc, text))
+        self.rc, self.text = rc, text
+
+
+class DecJob(_C.Structure):
+    """dsvg_dec_job (include/dsvg.h): one picture of a decoder call"""
+    _fields_ = [("ref_recon_slot", _C.c_int), ("recon_slot", _C.c_int), ("quant", _C.c_int), ("mvs", _C.c_void_p), ("stable_blocks", _C.c_void_p),
+                ("plane_data", _C.c_void_p * 3), ("plane_len", _C.c_uint32 * 3)]
+
+
+MV_DTYPE = _np.dtype({"names": ["x", "y", "mode", "submask", "lo_var", "lo_tex", "high_detail"], "formats": ["<i2", "<i2", "u1", "u1", "u1", "u1", "u1"],
+                      "offsets": [0, 2, 4, 5, 6, 7, 8], "itemsize": 12})      # dsvg_mv (its union holds an int32: 12 bytes)
+
+
+class DecPlan(_C.Structure):
+    """dsvg_dec_plan (include/dsvg.h): the plan of a decoder call, arrays of the caller's"""
+    _fields_ = [("cap_jobs", _C.c_int), ("cap_ilist", _C.c_int), ("order", _C.c_void_p), ("path", _C.c_void_p), ("dec_sym", _C.c_void_p),
+                ("wide", _C.c_void_p), ("inplace", _C.c_void_p), ("dc", _C.c_void_p), ("runs", _C.c_void_p), ("len", _C.c_void_p),
+                ("bitpos", _C.c_void_p), ("blob_off", _C.c_void_p), ("meta_off", _C.c_void_p), ("ilist", _C.c_void_p),
+                ("nblk", _C.c_int), ("nbh", _C.c_int), ("mc_patch", _C.c_int), ("sym_ok", _C.c_int * 2), ("ov", _C.c_int * 2),
+                ("second_stream", _C.c_int), ("nchunks", _C.c_int * 3), ("lim", (_C.c_int * 16) * 2), ("nI", _C.c_int),
+                ("blob", _C.c_longlong), ("nmeta", _C.c_longlong), ("max_entries", _C.c_int), ("max_chunks", _C.c_int),
+                ("insym", _C.c_int), ("f0", _C.c_int), ("anysym", _C.c_int), ("scatter_one", _C.c_int), ("resolve", _C.c_int), ("fork", _C.c_int),
+                ("mc", _C.c_int), ("ex0", _C.c_int), ("ey0", _C.c_int), ("iln", _C.c_int), ("draw0", _C.c_int), ("draw1", _C.c_int)]
+
+
+class DecodeRefused(RuntimeError):
+    """dsvg_decode_plan did not answer with a plan: rc and text are what the decoder call itself would return and set"""
+    def __init__(self, rc, text):
+        super().__init__("dsvg_decode_plan failed rc=%d: %s" % (rc, text))
         self.rc, self.text = rc, text
 
 
@@ -603,6 +634,37 @@ def code_batch_plan(w, h, fmt, n_recon_slots, n_src_slots, max_jobs, out_slots, 
         d[k] = arr[k][:nsteps * p.ng].reshape(nsteps, p.ng)
     d["ilist"] = arr["ilist"][:p.iln]
     return d
+
+
+def decode_plan(w, h, fmt, n_recon_slots, max_jobs, switches, force32, draw_mode, njobs, jobs):
+    """what dsvg_decode_pictures decides on the host for `jobs` (a ctypes array of DecJob) in a context created with these arguments,
+    with the A/B switches of the mask `switches` (DEC_*): a dict of dsvg_dec_plan's fields, the arrays as numpy arrays cut to their
+    lengths (the per-plane ones: [njobs, 3]; lim: [2, 16]).  Raises DecodeRefused with the call's own code and text for jobs the call
+    refuses.  Needs no device"""
+    n = max(njobs, 1)
+    d = Dispatch()                                          # (the block size of the geometry: how long the list can get)
+    nblk = -(-w // d.blk_w) * -(-h // d.blk_h) if lib().dsvg_dispatch_plan(w, h, fmt, _C.byref(d)) == 0 else 1
+    arr = {"order": _np.zeros(n, _np.int32), "path": _np.zeros(n, _np.int32), "dec_sym": _np.zeros(3 * n, _np.int32),
+           "wide": _np.zeros(n, _np.uint8), "inplace": _np.zeros(n, _np.uint8), "dc": _np.zeros(3 * n, _np.int32),
+           "runs": _np.zeros(3 * n, _np.int32), "len": _np.zeros(3 * n, _np.int32), "bitpos": _np.zeros(3 * n, _np.int64),
+           "blob_off": _np.zeros(3 * n, _np.int64), "meta_off": _np.zeros(3 * n, _np.int64), "ilist": _np.zeros(n * nblk, _np.int32)}
+    p = DecPlan(cap_jobs=n, cap_ilist=n * nblk)
+    for k, a in arr.items():
+        setattr(p, k, a.ctypes.data)
+    lib().dsvg_decode_plan.argtypes = [_C.c_int] * 5 + [_C.c_uint, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(DecJob), _C.POINTER(DecPlan)]
+    r = lib().dsvg_decode_plan(w, h, fmt, n_recon_slots, max_jobs, switches, int(force32), draw_mode, njobs, jobs, _C.byref(p))
+    if r != 0:
+        raise DecodeRefused(r, lib().dsvg_last_error().decode())
+    out = {k: getattr(p, k) for k in ("nblk", "nbh", "mc_patch", "second_stream", "nI", "blob", "nmeta", "max_entries", "max_chunks", "insym", "f0",
+                                      "anysym", "scatter_one", "resolve", "fork", "mc", "ex0", "ey0", "iln", "draw0", "draw1")}
+    out["sym_ok"], out["ov"], out["nchunks"] = tuple(p.sym_ok), tuple(p.ov), tuple(p.nchunks)
+    out["lim"] = _np.array([list(p.lim[0]), list(p.lim[1])], dtype=_np.int64)
+    for k in ("order", "path", "wide", "inplace"):
+        out[k] = arr[k][:njobs]
+    for k in ("dec_sym", "dc", "runs", "len", "bitpos", "blob_off", "meta_off"):
+        out[k] = arr[k][:3 * njobs].reshape(njobs, 3)
+    out["ilist"] = arr["ilist"][:p.iln]
+    return out
 
 
 def make_encoder_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1, kbps=0, scd=1, ipct=50, pyrlevels=0, stabref=0,

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include "dsvg_host.hpp"
 #include "dsvg_batch_plan.h"
+#include "dsvg_dec_plan.h"
 #include <ctime>
 extern "C" void dsv1_par_for(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);     // host/dsv1_util.c: the worker pool
 extern "C" void dsv1_par_for_long(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);
@@ -171,7 +172,6 @@ struct dsvg_ctx {
     bool no_patch_kernel = false;    // DSV1_NO_PATCH_KERNEL: chroma of P pictures stays on the tile kernel (A/B switch)
     bool no_dec_sym_I = false;       // DSV1_NO_DEC_SYM_I: the decoder's I pictures keep int32 coefficients (A/B switch)
     bool no_dec_sym = false;         // DSV1_NO_DEC_SYM: the decoder keeps int32 coefficients for P pictures too (A/B switch)
-    bool dec_sym_ok[2] = {false, false};   // luma / chroma planes have no cell shared between scan regions
     HzPlaneSum *psum = nullptr;
     uint8_t *bits = nullptr;
     DMV *mvs = nullptr;
@@ -257,7 +257,10 @@ struct dsvg_ctx {
         std::vector<int> slots, index; void *out = nullptr; size_t pitch = 0;
         bool has_fmt = false; dsvg_pixout fmt;
     } dec_pending;
-    bool dec_ov[2] = {false, false};    // luma / chroma planes have cells shared between scan regions (k_hz_dec_resolve)
+    // decoder calls (dsvg_dec_plan.h): what their plan reads of the context (dec_geo, at creation), and the plan of the call being
+    // enqueued -- kept here so that its vector is allocated once, not per call
+    DecGeo dgeo = {};
+    DecPlan dec_plan;
     long dec_redone = 0;                // calls decoded again on the int32 path (tests)
     HzParseChunk *dec_meta = nullptr;            // decoder: k_hz_parse -> k_hz_codes records of one call
     size_t dec_meta_cap = 0;
@@ -576,6 +579,31 @@ static BatchGeo batch_geo(const CtxGeo &geo, int n_src_slots, int n_recon_slots,
     return B;
 }
 
+// What the plan of a decoder call reads of a context (dsvg_dec_plan.h), from the arguments of its creation: dsvg_ctx_create_blk keeps it, and
+// dsvg_decode_plan asks the plan about the same record without a context.  second_stream is the call's own (a coding call may create
+// the stream later).
+static DecGeo dec_geo(const CtxGeo &geo, int n_recon_slots, int max_jobs, bool mc_fusion, bool sym_ov)
+{
+    DecGeo D = {};
+    const CoefLayout &CL = geo.CL;
+    D.n_recon = n_recon_slots; D.max_jobs = max_jobs; D.nblk = geo.nbh * geo.nbv;
+    for (int p = 0; p < 3; p++) {
+        HzPlane hp; make_hz_plane(hp, CL.w[p], CL.h[p], 100, 0, p, geo.nbh, geo.nbv);
+        D.cw[p] = CL.w[p]; D.ch[p] = CL.h[p]; D.nchunks[p] = hp.nchunks;
+        D.pw[p] = geo.MG.w[p]; D.ph[p] = geo.MG.h[p];
+    }
+    for (int g2 = 0; g2 < 2; g2++) {
+        HzPlane hp; make_hz_plane(hp, CL.w[g2 ? 1 : 0], CL.h[g2 ? 1 : 0], 100, 1, g2, geo.nbh, geo.nbv);
+        const bool ov = (2 * hp.s_w[0] > hp.s_w[1]) || (2 * hp.s_h[0] > hp.s_h[1]) || (2 * hp.s_w[1] > hp.s_w[2]) || (2 * hp.s_h[1] > hp.s_h[2]);
+        // (the fused inverse from symbol planes also wants the level-1 bands 4-aligned and the plane's LL5 path as usual)
+        D.sym_ok[g2] = (CL.off[g2 ? 1 : 0] & 3) == 0 && (CL.off[2] & 3) == 0 && !(ov && !sym_ov);
+        D.ov[g2] = ov;
+    }
+    D.mc_patch = mc_fusable(geo.MG) && mc_fusion;          // (such a context has an intra list)
+    D.nbh = geo.MG.nbh; D.nbv = geo.MG.nbv; D.blk_w = geo.MG.blk_w; D.blk_h = geo.MG.blk_h; D.hs = geo.MG.hs; D.vs = geo.MG.vs;
+    return D;
+}
+
 // What the forward launchers decide for an encoder context of this geometry (default block size and pyramid depth, the chroma
 // table of the motion search on): the context's geometry tables, handed to the launchers' own decision functions
 extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out)
@@ -706,6 +734,7 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         c->levels = c->hme.levels;
         for (int l = 1; l <= c->levels; l++) c->L[l] = c->hme.L[l];
         c->bgeo = batch_geo(geo, n_src_slots, n_recon_slots, max_jobs, out_slots, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_LAZY_BORDER"));
+        c->dgeo = dec_geo(geo, n_recon_slots, max_jobs, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_DEC_SYM_OV"));
     }
     out_slots = c->bgeo.out_slots;                          // (at least max_jobs)
     c->n_src = n_src_slots; c->n_recon = n_recon_slots; c->max_jobs = max_jobs; c->out_slots = out_slots;
@@ -725,13 +754,6 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
     c->no_patch_kernel = getenv("DSV1_NO_PATCH_KERNEL") != nullptr;
     c->no_list_pack = getenv("DSV1_NO_LIST_PACK") != nullptr;
     c->no_lazy_border = !c->bgeo.lazy_border;
-    for (int g2 = 0; g2 < 2; g2++) {
-        HzPlane hp; make_hz_plane(hp, CL.w[g2 ? 1 : 0], CL.h[g2 ? 1 : 0], 100, 1, g2, c->nbh, c->nbv);
-        const bool ov = (2 * hp.s_w[0] > hp.s_w[1]) || (2 * hp.s_h[0] > hp.s_h[1]) || (2 * hp.s_w[1] > hp.s_w[2]) || (2 * hp.s_h[1] > hp.s_h[2]);
-        // (the fused inverse from symbol planes also wants the level-1 bands 4-aligned and the plane's LL5 path as usual)
-        c->dec_sym_ok[g2] = (CL.off[g2 ? 1 : 0] & 3) == 0 && (CL.off[2] & 3) == 0 && !(ov && getenv("DSV1_NO_DEC_SYM_OV"));
-        c->dec_ov[g2] = ov;
-    }
     // two coding streams by default: with the analysis and fetch streams that is four, the number of hardware queues
     // the runtime maps streams onto (three coding streams measured 18.5 ms per step against 14.3 with two and 15.4 with one)
     { const char *e = getenv("DSV1_CODE_STREAMS"); c->code_streams = e ? atoi(e) : 2; }
@@ -2242,19 +2264,8 @@ extern "C" int dsvg_export_recons(dsvg_ctx *c, int n, const int *recon_slots, co
 }
 
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct Rd {                          // MSB-first reader (bs.c:111-125,148-157,209-219), bounded: past `end` bits read as 1
-    const uint8_t *p; unsigned pos, end;
-    unsigned bit() { if (pos >= end) return 1u; unsigned b = (p[pos >> 3] >> (7 - (pos & 7))) & 1u; pos++; return b; }
-    unsigned bits(int n) { unsigned v = 0; while (n--) v = (v << 1) | bit(); return v; }
-    unsigned ueg() { unsigned m = 1; int k = 0; while (!bit() && k++ < 32) m = (m << 1) | bit(); return m - 1; }
-    int seg() { int v = (int)ueg(); return (v && bit()) ? -v : v; }
-    int neg() { int v = (int)ueg() + 1; return bit() ? -v : v; }
-    void align() { pos = (pos + 7u) & ~7u; }
-};
-}
-
-static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool force32);
+static int dec_plan(dsvg_ctx *c, DecPlan &P, int njobs, const dsvg_dec_job *jobs, bool force32);
+static int decode_impl(dsvg_ctx *c, const DecPlan &P, const dsvg_dec_job *jobs);
 
 // look at the flags of the last decoder call (see dsvg_ctx::dec_pending); decode it again on the int32 path if it asks for it
 static int dec_resolve(dsvg_ctx *c)
@@ -2275,7 +2286,9 @@ static int dec_resolve(dsvg_ctx *c)
     const std::vector<int> slots = P.slots, index = P.index;
     void *out = P.out; const size_t pitch = P.pitch;
     const bool has_fmt = P.has_fmt; const dsvg_pixout fmt = P.fmt;
-    int rc = decode_impl(c, (int)jobs.size(), jobs.data(), true);
+    DecPlan R;                                           // (the context's plan holds the call that waits behind this repeat)
+    int rc = dec_plan(c, R, (int)jobs.size(), jobs.data(), true);
+    if (!rc) rc = decode_impl(c, R, jobs.data());
     if (!rc && !slots.empty()) rc = output_pass(c, (int)slots.size(), slots.data(), index.empty() ? nullptr : index.data(), out, pitch, 1, has_fmt ? &fmt : nullptr);
     P.in_redo = false;
     P.active = false;
@@ -2286,33 +2299,43 @@ extern "C" long dsvg_ctx_decoder_redone(const dsvg_ctx *c) { return c ? c->dec_r
 
 extern "C" int dsvg_decode_pictures(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs)
 {
-    if (!c || !jobs || njobs < 1 || njobs > c->max_jobs) { dsvg_set_error("bad decode_pictures arguments"); return DSVG_ERR_ARG; }
+    if (!c) { dsvg_set_error("bad decode_pictures arguments"); return DSVG_ERR_ARG; }
+    // a refused call leaves the context as it found it: the call before is not settled, no parity flipped, no staging written
+    OPCHK(dec_plan(c, c->dec_plan, njobs, jobs, false));
     OPCHK(dec_resolve(c));                               // the call before may have to be decoded again first (its pictures are references)
-    return decode_impl(c, njobs, jobs, false);
+    return decode_impl(c, c->dec_plan, jobs);
 }
 
-static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool force32)
+// the A/B switches of a decoder call: the context's own, read at its creation, and the process's, read once
+static DecSwitches dec_switches(const dsvg_ctx *c)
 {
-    HIPCHK(hipSetDevice(c->device));
+    static const bool one_stream = getenv("DSV1_DEC_ONE_STREAM") != nullptr, no_mc_patch = getenv("DSV1_NO_MC_PATCH") != nullptr;
+    return { c->no_dec_sym, c->no_dec_sym_I, one_stream, no_mc_patch, c->no_inplace_pred };
+}
+
+// the plan of a call of this context (plan_decode, dsvg_dec_plan.h: every check and every decision)
+static int dec_plan(dsvg_ctx *c, DecPlan &P, int njobs, const dsvg_dec_job *jobs, bool force32)
+{
+    DecGeo geo = c->dgeo;
+    geo.second_stream = c->stx[1] && c->ev_join[1];
+    const int rc = plan_decode(geo, dec_switches(c), njobs, jobs, force32, c->prof.mask != 0, c->draw_mode, P);
+    if (rc) dsvg_set_error("%s", P.err);
+    return rc;
+}
+
+// Commit a planned call to the context and upload it: the parity's pinned staging (job records, payloads, block tables, the pending
+// record), then the six uploads.  k: the call's parity, for dec_enqueue.
+static int dec_commit(dsvg_ctx *c, const DecPlan &P, const dsvg_dec_job *jobs, int &k)
+{
+    const int njobs = P.njobs;
     if (c->draw_any) { std::fill(c->draw_at.begin(), c->draw_at.end(), -1); c->draw_any = false; }
-    std::vector<int> ord;
-    for (int i = 0; i < njobs; i++) if (jobs[i].ref_recon_slot < 0) ord.push_back(i);
-    const int nI = (int)ord.size();
-    for (int i = 0; i < njobs; i++) if (jobs[i].ref_recon_slot >= 0) ord.push_back(i);
     // Host staging (payload blob, job / flag / vector tables) is double-buffered by call parity: a call only waits for
     // the uploads of the call before the previous one, so the caller's parsing of the next packets overlaps the device.
-    const int k = c->dec_par;
-    c->dec_par ^= 1;
+    k = c->dec_par;
     if (!c->ev_dec[k]) HIPCHK(hipEventCreateWithFlags(&c->ev_dec[k], hipEventDisableTiming));
     else HIPCHK(hipEventSynchronize(c->ev_dec[k]));
-    size_t blob = 0;
-    for (int t = 0; t < njobs; t++)
-        for (int p = 0; p < 3; p++) {
-            const dsvg_dec_job &j = jobs[ord[t]];
-            // the reference's bound (dsv_decoder.c:397-398: twice the int32 coefficient plane), not the encoder's output capacity
-            if (!j.plane_data[p] || (size_t)j.plane_len[p] > (size_t)c->CL.w[p] * c->CL.h[p] * 8) { dsvg_set_error("plane %d of decode job %d: bad length", p, ord[t]); return DSVG_ERR_ARG; }
-            blob += ((size_t)j.plane_len[p] + 64 + 15) & ~(size_t)15;
-        }
+    c->dec_par ^= 1;
+    const size_t blob = P.blob, nmeta = P.nmeta;
     if (blob > c->dec_cap[k]) {
         if (c->dec_h[k]) (void)hipHostFree(c->dec_h[k]);
         if (c->dec_d[k]) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipFree(c->dec_d[k]); }
@@ -2323,9 +2346,6 @@ static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool fo
         c->dec_cap[k] = cap;
     }
     // per 128-bit payload chunk one hand-over record between the parse kernels (device only, consumed in stream order)
-    size_t nmeta = 0;
-    for (int t = 0; t < njobs; t++)
-        for (int p = 0; p < 3; p++) nmeta += (size_t)jobs[ord[t]].plane_len[p] / 16 + 2;
     if (nmeta > c->dec_meta_cap) {
         if (c->dec_meta) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipFree(c->dec_meta); c->dec_meta = nullptr; c->dec_meta_cap = 0; }
         const size_t cap = nmeta * 2 + 4096;
@@ -2333,153 +2353,108 @@ static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool fo
         c->dec_meta_cap = cap;
     }
     const size_t hb = (size_t)k * c->max_jobs;          // this parity's part of the pinned tables
-    const bool sparse = !c->no_dec_sym && !force32;
     if (!c->dec_flag_d) {
         HIPCHK(hipMalloc((void **)&c->dec_flag_d, sizeof(int) * 2 * (size_t)c->max_jobs));
         HIPCHK(hipHostMalloc((void **)&c->dec_flag_h, sizeof(int) * 2 * (size_t)c->max_jobs, hipHostMallocDefault));
         for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_flag[i], hipEventDisableTiming));
     }
-    dsvg_ctx::DecPending &P = c->dec_pending;
-    const bool was_redo = P.in_redo;
-    if (!was_redo) { P.jobs.resize((size_t)njobs); P.slots.clear(); }
-    int max_entries = 0, max_chunks = 0;
-    size_t moff = 0;
-    const CoefLayout &CL = c->CL;
-    size_t off = 0;
+    dsvg_ctx::DecPending &pend = c->dec_pending;
+    const bool was_redo = pend.in_redo;
+    if (!was_redo) { pend.jobs.resize((size_t)njobs); pend.slots.clear(); }
+    int lim[2][16];
+    dec_limits(false, lim[0]);
+    dec_limits(true, lim[1]);
     for (int t = 0; t < njobs; t++) {
-        const dsvg_dec_job &j = jobs[ord[t]];
-        const int isP = j.ref_recon_slot >= 0;
-        if (j.recon_slot < 0 || j.recon_slot >= c->n_recon || j.ref_recon_slot >= c->n_recon || !j.stable_blocks || (isP && !j.mvs)) {
-            dsvg_set_error("bad decode job %d", ord[t]); return DSVG_ERR_ARG;
-        }
+        const DecPlanJob &o = P.job[(size_t)t];
+        const dsvg_dec_job &j = jobs[o.src];
         JobDev &jb = c->jobs_h[hb + t];
-        fill_job(c, jb, t, isP, j.quant);
-        jb.ref = isP ? c->recon.p + (size_t)j.ref_recon_slot * c->L[0].pitch : nullptr;
+        fill_job(c, jb, t, o.isP, j.quant);
+        jb.ref = o.isP ? c->recon.p + (size_t)j.ref_recon_slot * c->L[0].pitch : nullptr;
         jb.recon = c->recon.p + (size_t)j.recon_slot * c->L[0].pitch;
         jb.dec_flag = c->dec_flag_d + hb + t;
-        {   // range of a P picture of 8-bit video per transform level: detail <= 4 x the LL below, LL = 4/5 of that (level 1 of a
-            // P picture unscaled), a dequantised value <= twice its coefficient (hzcc.c:94-128: a non-zero symbol needs 2|v| > q)
-            long ll = 512;
-            jb.dec_lim[1] = 2 * 510;
-            for (int lv = 2; lv < 16; lv++) {
-                const long det = 4 * ll;
-                jb.dec_lim[lv] = (int)std::min<long>(2 * det, 0x3fffffff);
-                ll = std::min<long>(det * 4 / 5, 0x1fffffff);
-            }
-            jb.dec_lim[0] = (int)std::min<long>(2 * ll, 0x3fffffff);
-        }
-        // I pictures (round 3): symbols into the zero-kept planes as well -- the encoder's I-picture inverse (k_inv_haar_tile<.,1,true>,
-        // k_inv_b4t<true>) dequantises them in 32 bits, so the only thing they cannot hold is a symbol beyond int16; needs both
-        // plane kinds on the symbol path (the I kernels take luma and chroma alike)
-        const bool sparseI = sparse && c->dec_sym_ok[0] && c->dec_sym_ok[1] && !c->no_dec_sym_I;
-        if (!isP && sparseI) {
-            jb.sym = c->symP + (size_t)t * c->nz_total;
-            for (int p = 0; p < 3; p++) jb.dec_sym[p] = 1;
-            for (int lv = 0; lv < 16; lv++) jb.dec_lim[lv] = 0x3fffffff;
-        }
-        if (isP && sparse) {
-            // sparse decode of P pictures: the detail entries go to the zero-kept int16 symbol planes and the fused inverse
-            // of the encoder reconstructs from them (no 12 MB of int32 coefficients to clear and to read per picture); a
-            // plane whose scan regions share cells takes it too: k_hz_dec_resolve flags the rare picture in which an absent later
-            // symbol must leave the earlier region's VALUE in place (hzcc.c:295-435), and that call is decoded again from
-            // int32 coefficients (dec_resolve)
-            jb.sym = c->symP + (size_t)t * c->nz_total;
-            jb.nzf = c->nzf + (size_t)t * (c->nz_total >> 2);          // (marks the job as sparse for the inverse; the flags themselves are the encoder's)
-            for (int p = 0; p < 3; p++) jb.dec_sym[p] = c->dec_sym_ok[p < 1 ? 0 : 1];
-            if (j.recon_slot != j.ref_recon_slot && !c->no_inplace_pred) jb.pred = jb.recon;     // prediction written in place (ping-pong slots)
-        }
+        memcpy(jb.dec_lim, lim[o.wide ? 1 : 0], sizeof jb.dec_lim);
+        if (o.path != DEC_PATH_I32) jb.sym = c->symP + (size_t)t * c->nz_total;
+        if (o.path == DEC_PATH_SYM_P) jb.nzf = c->nzf + (size_t)t * (c->nz_total >> 2);      // (marks the job as sparse for the inverse; the flags themselves are the encoder's)
+        for (int p = 0; p < 3; p++) jb.dec_sym[p] = o.dec_sym[p];
+        if (o.inplace) jb.pred = jb.recon;              // prediction written in place
         c->slots_h[hb + t] = j.recon_slot;
         memcpy(c->stable_h + (hb + t) * c->nblk, j.stable_blocks, (size_t)c->nblk);
-        if (isP) memcpy(c->mv_h + (hb + t) * c->nblk, j.mvs, (size_t)c->nblk * sizeof(DMV));
+        if (o.isP) memcpy(c->mv_h + (hb + t) * c->nblk, j.mvs, (size_t)c->nblk * sizeof(DMV));
         if (!was_redo) {                                // what a repetition of this call needs, out of the pinned staging (intact until the parity comes round again)
-            dsvg_dec_job &sj = P.jobs[(size_t)t];
+            dsvg_dec_job &sj = pend.jobs[(size_t)t];
             sj = j;
             sj.stable_blocks = c->stable_h + (hb + t) * c->nblk;
             sj.mvs = reinterpret_cast<const dsvg_mv *>(c->mv_h + (hb + t) * c->nblk);
         }
         jb.bits = c->dec_d[k];                          // the payloads of the call travel as one blob
         for (int p = 0; p < 3; p++) {
-            // the host reads only the plane header (hzcc.c:479-483,307-311): SEG(DC), the 32-bit run count; the
-            // code chain is parsed on the device (k_hz_parse) from the uploaded bytes
-            Rd rd{j.plane_data[p], 0, (unsigned)j.plane_len[p] * 8u};
-            jb.dec_dc[p] = rd.seg();
-            rd.align();
-            jb.dec_runs[p] = (int)rd.bits(32);
-            rd.align();
-            jb.dec_bitpos[p] = (long long)rd.pos;
-            jb.dec_len[p] = (int)j.plane_len[p];
+            jb.dec_dc[p] = o.dc[p];
+            jb.dec_runs[p] = o.runs[p];
+            jb.dec_bitpos[p] = o.bitpos[p];
+            jb.dec_len[p] = o.len[p];
             jb.dec_cnt[p] = 0;
-            max_entries = std::max(max_entries, std::min(jb.dec_runs[p], jb.hz[p].nchunks * HZ_CHUNK - 1) + 1);
-            jb.dec_meta[p] = c->dec_meta + moff;
-            moff += (size_t)j.plane_len[p] / 16 + 2;
-            max_chunks = std::max(max_chunks, (int)(j.plane_len[p] / 16 + 2));
-            jb.bits_off[p] = off;
-            uint8_t *stage = c->dec_h[k] + off;
-            if (!was_redo) P.jobs[(size_t)t].plane_data[p] = stage;
+            jb.dec_meta[p] = c->dec_meta + o.moff[p];
+            jb.bits_off[p] = o.boff[p];
+            uint8_t *stage = c->dec_h[k] + o.boff[p];
+            if (!was_redo) pend.jobs[(size_t)t].plane_data[p] = stage;
             memcpy(stage, j.plane_data[p], j.plane_len[p]);
             memset(stage + j.plane_len[p], 0, 64);
-            off += ((size_t)j.plane_len[p] + 64 + 15) & ~(size_t)15;
         }
     }
-    const bool symI = sparse && c->dec_sym_ok[0] && c->dec_sym_ok[1] && !c->no_dec_sym_I && nI > 0;      // the call's I pictures are on the symbol path
-    const int insym = !sparse ? 0 : (symI ? 1 : 0) | (c->dec_sym_ok[0] ? 2 : 0) | (c->dec_sym_ok[1] ? 4 : 0);
-    const int f0 = symI ? 0 : nI;                      // first job that may raise a flag / holds symbols to take down again
-    const bool anysym = ((insym & 6) && njobs > nI) || symI;
-    HIPCHK(hipMemcpyAsync(c->dec_d[k], c->dec_h[k], off, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemcpyAsync(c->dec_d[k], c->dec_h[k], blob, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->jobs_d, c->jobs_h + hb, sizeof(JobDev) * njobs, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->stable, c->stable_h + hb * c->nblk, (size_t)c->nblk * njobs, hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->mvs, c->mv_h + hb * c->nblk, (size_t)c->nblk * njobs * sizeof(DMV), hipMemcpyHostToDevice, c->st));
     HIPCHK(hipMemcpyAsync(c->slots_d + 2 * c->out_slots, c->slots_h + hb, sizeof(int) * njobs, hipMemcpyHostToDevice, c->st));
-    if (anysym) HIPCHK(hipMemsetAsync(c->dec_flag_d + hb, 0, sizeof(int) * (size_t)njobs, c->st));
+    if (P.anysym) HIPCHK(hipMemsetAsync(c->dec_flag_d + hb, 0, sizeof(int) * (size_t)njobs, c->st));
     // (round 5, measured dead end: the six commands above as ONE kernel that reads the pinned tables in place -- 3 180-3 220 against 3 250 frames/s)
     HIPCHK(hipEventRecord(c->ev_dec[k], c->st));
+    return DSVG_OK;
+}
+
+// The launches of a committed call, from its plan: clear, parse and scatter, resolve and flag copy, the fork, motion compensation, the
+// join, the pack wait, the reconstruction, unscatter, overlay.
+static int dec_enqueue(dsvg_ctx *c, const DecPlan &P, int k)
+{
+    const int njobs = P.njobs, nI = P.nI, f0 = P.f0;
+    const size_t hb = (size_t)k * c->max_jobs;          // this parity's part of the pinned tables
+    dsvg_ctx::DecPending &pend = c->dec_pending;
+    const bool was_redo = pend.in_redo;
     launch_dec_clear(c->st, c->jobs_d, njobs);
-    launch_hz_parse_scatter(c->st, c->jobs_d, njobs, 0, 3, max_entries, max_chunks, &c->prof, (insym & 6) == 6 && (nI == 0 || symI));
-    if (anysym) {
+    launch_hz_parse_scatter(c->st, c->jobs_d, njobs, 0, 3, P.max_entries, P.max_chunks, &c->prof, P.scatter_one);
+    if (P.anysym) {
         // what the symbol planes cannot hold (JobDev.dec_flag): shared cells that keep the earlier region's value; symbols
         // beyond int16 were flagged by the scatter itself.  The flags travel back now and are read by dec_resolve later.
-        if ((c->dec_ov[0] && c->dec_sym_ok[0]) || (c->dec_ov[1] && c->dec_sym_ok[1])) launch_hz_dec_resolve(c->st, c->jobs_d + f0, njobs - f0, 0, 3);
+        if (P.resolve) launch_hz_dec_resolve(c->st, c->jobs_d + f0, njobs - f0, 0, 3);
         HIPCHK(hipMemcpyAsync(c->dec_flag_h + hb, c->dec_flag_d + hb, sizeof(int) * (size_t)njobs, hipMemcpyDeviceToHost, c->st));
         HIPCHK(hipEventRecord(c->ev_flag[k], c->st));
-        if (!was_redo) { P.active = true; P.parity = k; P.njobs = njobs; }
-    } else if (!was_redo) P.active = false;
+        if (!was_redo) { pend.active = true; pend.parity = k; pend.njobs = njobs; }
+    } else if (!was_redo) pend.active = false;
     // Round 5: the motion compensation of a step depends on the step before (its reconstructions) and on this call's tables, not on this
     // call's entropy decoding: it runs on the second coding stream beside the parse chain (five latency-bound kernels, 160 us of a 620 us
     // step of 64 pictures) and joins in front of the inverse transform.  The fork waits for ev_dec -- recorded on the first stream behind
     // this call's uploads, i.e. behind everything of the step before -- so nothing of that step still reads the prediction frames.
     hipStream_t sm = c->st;
-    {
-        static const bool one_stream = getenv("DSV1_DEC_ONE_STREAM") != nullptr;      // (A/B)
-        if (njobs > nI && njobs >= 4 && !one_stream && !c->prof.mask && c->stx[1] && c->ev_join[1]) {      // (a call of one picture gains nothing: 3 110-3 230 against 3 160-3 340 frames/s)
-            sm = c->stx[1];
-            HIPCHK(hipStreamWaitEvent(sm, c->ev_dec[k], 0));
-        }
+    if (P.fork) {
+        sm = c->stx[1];
+        HIPCHK(hipStreamWaitEvent(sm, c->ev_dec[k], 0));
     }
-    if (njobs > nI) {
-        static const bool no_mc_patch = getenv("DSV1_NO_MC_PATCH") != nullptr;
-        if (c->mc_fused && c->ilist_h && !no_mc_patch) {
+    if (P.mc != DEC_MC_NONE) {
+        if (P.mc == DEC_MC_PATCH) {
             // the encoder's lean motion compensation by itself (k_mc_patch: a thread per 8x8 patch) for the inter blocks; k_mc, by
-            // list, for the intra blocks and for the block columns / rows from (ex0, ey0) on, which hold ragged patches in some
-            // plane (the two kernels share that predicate)
-            const McGeo &M = c->MG;
-            int ex0 = M.nbh, ey0 = M.nbv;
-            for (int p = 0; p < 3; p++) {
-                const int bw = M.blk_w >> (p ? M.hs : 0), bh = M.blk_h >> (p ? M.vs : 0);
-                if (M.w[p] & 7) ex0 = std::min(ex0, (M.w[p] & ~7) / bw);
-                if (M.h[p] & 7) ey0 = std::min(ey0, (M.h[p] & ~7) / bh);
-            }
+            // list (dec_intra_list), for the intra blocks and for the block columns / rows from (ex0, ey0) on, which hold ragged
+            // patches in some plane (the two kernels share that predicate).  The list is the one host effect left to this stage: it
+            // goes straight into the parity's pinned list HERE, behind the parse chain's launches, where the device has work while
+            // the host walks the blocks (in front of the uploads the 64-picture call with host output measured 0.8 % slower)
             int *il = c->ilist_h + hb * c->nblk, iln = 0;
-            for (int t = nI; t < njobs; t++) {
-                const DMV *mv = c->mv_h + (hb + t) * c->nblk;
-                for (int b = 0; b < c->nblk; b++)
-                    if (mv[b].mode != 0 || b % M.nbh >= ex0 || b / M.nbh >= ey0) il[iln++] = (t - nI) * c->nblk + b;
-            }
+            for (int t = nI; t < njobs; t++)
+                iln += dec_intra_list(c->dgeo, reinterpret_cast<const dsvg_mv *>(c->mv_h + (hb + t) * c->nblk), (t - nI) * c->nblk, P.ex0, P.ey0, il + iln);
             const DMV *mv0 = c->mvs + (size_t)nI * c->nblk;
             if (iln) {
                 HIPCHK(hipMemcpyAsync(c->ilist_d + hb * c->nblk, il, sizeof(int) * (size_t)iln, hipMemcpyHostToDevice, sm));
                 launch_mc(sm, c->jobs_d + nI, njobs - nI, c->MG, 0, &c->prof, mv0, c->ilist_d + hb * c->nblk, iln);
             }
-            launch_mc_patch(sm, c->jobs_d + nI, njobs - nI, c->G, c->MG, mv0, ex0, ey0, &c->prof);
+            launch_mc_patch(sm, c->jobs_d + nI, njobs - nI, c->G, c->MG, mv0, P.ex0, P.ey0, &c->prof);
         } else launch_mc(sm, c->jobs_d + nI, njobs - nI, c->MG, 0, &c->prof);
         if (sm != c->st) {
             HIPCHK(hipEventRecord(c->ev_join[1], sm));
@@ -2490,24 +2465,81 @@ static int decode_impl(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs, bool fo
         HIPCHK(hipStreamWaitEvent(c->st, c->ev_pack[1], 0));
         c->pack_pending = false;
     }
-    OPCHK(enqueue_recon(c, nI, njobs, 0, insym));
-    if (anysym) launch_hz_unscatter(c->st, c->jobs_d + f0, njobs - f0, max_entries);
-    if (c->draw_mode && njobs > nI) {
+    OPCHK(enqueue_recon(c, nI, njobs, 0, P.insym));
+    if (P.anysym) launch_hz_unscatter(c->st, c->jobs_d + f0, njobs - f0, P.max_entries);
+    if (P.draw0 < P.draw1) {
         // debug overlay on the call's P pictures (jobs nI .. njobs - 1, whose tables lie in c->mvs / c->stable in that order): each is
         // copied to the scratch frame of its job and drawn on there, in stream order behind its reconstruction
         const FrameLayout &L = c->L[0];
+        const int d0 = P.draw0;
         if (!c->draw_scratch) HIPCHK(hipMalloc((void **)&c->draw_scratch, L.pitch * (size_t)c->max_jobs + 256));
         if (c->draw_at.empty()) c->draw_at.assign((size_t)c->n_recon, -1);
-        for (int t = nI; t < njobs; t++) {
-            const int slot = jobs[ord[t]].recon_slot;
+        for (int t = d0; t < P.draw1; t++) {
+            const int slot = c->slots_h[hb + t];
             HIPCHK(hipMemcpyAsync(c->draw_scratch + (size_t)t * L.pitch, c->recon.p + (size_t)slot * L.pitch, L.bytes, hipMemcpyDeviceToDevice, c->st));
             c->draw_at[(size_t)slot] = t;
         }
         c->draw_any = true;
-        launch_drawinfo(c->st, c->draw_scratch + (size_t)nI * L.pitch + L.off[0], L.pitch, L.w[0], L.h[0], L.stride[0], c->bw, c->bh, c->draw_mode,
-                        c->mvs + (size_t)nI * c->nblk, c->stable + (size_t)nI * c->nblk, njobs - nI);
+        launch_drawinfo(c->st, c->draw_scratch + (size_t)d0 * L.pitch + L.off[0], L.pitch, L.w[0], L.h[0], L.stride[0], c->bw, c->bh, c->draw_mode,
+                        c->mvs + (size_t)d0 * c->nblk, c->stable + (size_t)d0 * c->nblk, P.draw1 - d0);
     }
     HIPCHK(hipGetLastError());
+    return DSVG_OK;
+}
+
+// A planned call (dec_plan: a call it refuses never gets here): commit, uploads, enqueue.
+static int decode_impl(dsvg_ctx *c, const DecPlan &P, const dsvg_dec_job *jobs)
+{
+    HIPCHK(hipSetDevice(c->device));
+    int k = 0;
+    OPCHK(dec_commit(c, P, jobs, k));
+    return dec_enqueue(c, P, k);
+}
+
+// What plan_decode decides for a call of a context created with these arguments (include/dsvg.h), without a device: the context's own
+// derivation of DecGeo on the geometry tables, with the switches the caller names instead of the environment's
+extern "C" int dsvg_decode_plan(int width, int height, int subsamp, int n_recon_slots, int max_jobs, unsigned switches, int force32, int draw_mode,
+                                int njobs, const dsvg_dec_job *jobs, dsvg_dec_plan *out)
+{
+    if (!out || n_recon_slots < 1 || max_jobs < 1) { dsvg_set_error("bad decode_plan arguments"); return DSVG_ERR_ARG; }
+    CtxGeo geo;
+    int r = geom_check(width, height, subsamp, geo);
+    if (r) return r;
+    DecGeo D = dec_geo(geo, n_recon_slots, max_jobs, !(switches & DSVG_DEC_NO_MC_FUSION), !(switches & DSVG_DEC_NO_SYM_OV));
+    D.second_stream = max_jobs >= 16;                    // (dsvg_ctx_create_blk: throughput contexts pick their coding streams at creation)
+    const DecSwitches sw = { (switches & DSVG_DEC_NO_SYM) != 0, (switches & DSVG_DEC_NO_SYM_I) != 0, (switches & DSVG_DEC_ONE_STREAM) != 0,
+                             (switches & DSVG_DEC_NO_MC_PATCH) != 0, (switches & DSVG_DEC_NO_INPLACE_PRED) != 0 };
+    DecPlan P;
+    if ((r = plan_decode(D, sw, njobs, jobs, force32 != 0, (switches & DSVG_DEC_PROFILED) != 0, draw_mode, P))) { dsvg_set_error("%s", P.err); return r; }
+    out->nblk = D.nblk; out->nbh = D.nbh; out->mc_patch = D.mc_patch; out->second_stream = D.second_stream;
+    for (int g = 0; g < 2; g++) { out->sym_ok[g] = D.sym_ok[g]; out->ov[g] = D.ov[g]; }
+    for (int p = 0; p < 3; p++) out->nchunks[p] = D.nchunks[p];
+    dec_limits(false, out->lim[0]);
+    dec_limits(true, out->lim[1]);
+    out->nI = P.nI; out->blob = (long long)P.blob; out->nmeta = (long long)P.nmeta; out->max_entries = P.max_entries; out->max_chunks = P.max_chunks;
+    out->insym = P.insym; out->f0 = P.f0; out->anysym = P.anysym; out->scatter_one = P.scatter_one; out->resolve = P.resolve; out->fork = P.fork;
+    out->mc = P.mc; out->ex0 = P.ex0; out->ey0 = P.ey0; out->draw0 = P.draw0; out->draw1 = P.draw1;
+    std::vector<int> ilist(P.mc == DEC_MC_PATCH ? (size_t)(njobs - P.nI) * D.nblk : 0);
+    int iln = 0;
+    for (int t = P.nI; t < njobs && P.mc == DEC_MC_PATCH; t++)
+        iln += dec_intra_list(D, jobs[P.job[(size_t)t].src].mvs, (t - P.nI) * D.nblk, P.ex0, P.ey0, ilist.data() + iln);
+    out->iln = iln;
+    if (!out->order || !out->path || !out->dec_sym || !out->wide || !out->inplace || !out->dc || !out->runs || !out->len || !out->bitpos ||
+        !out->blob_off || !out->meta_off || !out->ilist) { dsvg_set_error("decode_plan: null array"); return DSVG_ERR_ARG; }
+    if (out->cap_jobs < njobs || out->cap_ilist < iln) {
+        dsvg_set_error("decode_plan: the arrays are too small (%d jobs, %d listed blocks)", njobs, iln);
+        return DSVG_ERR_ARG;
+    }
+    for (int t = 0; t < njobs; t++) {
+        const DecPlanJob &o = P.job[(size_t)t];
+        out->order[t] = o.src; out->path[t] = o.path; out->wide[t] = o.wide; out->inplace[t] = o.inplace;
+        for (int p = 0; p < 3; p++) {
+            const int i = 3 * t + p;
+            out->dec_sym[i] = o.dec_sym[p]; out->dc[i] = o.dc[p]; out->runs[i] = o.runs[p]; out->len[i] = o.len[p];
+            out->bitpos[i] = o.bitpos[p]; out->blob_off[i] = (long long)o.boff[p]; out->meta_off[i] = (long long)o.moff[p];
+        }
+    }
+    for (int i = 0; i < iln; i++) out->ilist[i] = ilist[(size_t)i];
     return DSVG_OK;
 }
 

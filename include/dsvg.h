@@ -592,6 +592,53 @@ typedef struct dsvg_batch_plan {
 int dsvg_code_batch_plan(int width, int height, int subsamp, int n_recon_slots, int n_src_slots, int max_jobs, int out_slots, int code_streams,
                          unsigned switches, int nsteps, int njobs, const dsvg_pic_job *jobs, const dsvg_rc_job *rc, dsvg_batch_plan *out);
 
+/* The plan of a decoder call (tests): what dsvg_decode_pictures decides on the host for these jobs in a context created with these
+ * arguments (the encoder's own block size), without a device -- the call's own plan (plan_decode, csrc/dsvg_dec_plan.h: the call commits
+ * it and enqueues from it), on the geometry tables of dsvg_ctx_create.  switches: a mask of DSVG_DEC_* for the A/B switches
+ * DSV1_NO_DEC_SYM, DSV1_NO_DEC_SYM_I, DSV1_DEC_ONE_STREAM, DSV1_NO_MC_PATCH, DSV1_NO_INPLACE_PRED, DSV1_NO_DEC_SYM_OV, DSV1_NO_MC_FUSION,
+ * whatever the environment says, and PROFILED for a context with kernel timing on.  force32: the repeat of a flagged call on int32
+ * coefficients; draw_mode as dsvg_ctx_draw_info sets it.  Returns DSVG_OK, a negative DSVG_ERR_* for a geometry dsvg_ctx_create
+ * refuses, the code and text the call itself answers for jobs it refuses, or DSVG_ERR_ARG for arrays that are missing or too small
+ * (the scalars are filled in then).  The jobs' payloads are read (each plane's header).
+ * Device job d is the picture at position d in device order (I pictures first).  The caller sets the arrays and their capacities:
+ *   cap_jobs:  order[d] = the caller's index of device job d; path[d] = 0 int32 coefficients, 1 an I picture, 2 a P picture on the int16
+ *              symbol planes; wide[d] = 1: lim[1] holds the job's limits, else lim[0]; inplace[d] = 1: the prediction is written
+ *              into the reconstruction slot; per plane at [3 d + p]: dec_sym (the plane takes symbols), dc, runs, len (the plane
+ *              header and the payload's bytes), bitpos (first bit of the code chain), blob_off (bytes, in the call's payload blob),
+ *              meta_off (in the call's parse records);
+ *   cap_ilist: ilist, iln entries: per P picture the blocks k_mc takes by list beside k_mc_patch, (position among the P pictures) *
+ *              nblk + block (mc == 2 only).
+ * Append-only: later versions add fields at the end. */
+#define DSVG_DEC_NO_SYM           1
+#define DSVG_DEC_NO_SYM_I         2
+#define DSVG_DEC_ONE_STREAM       4
+#define DSVG_DEC_NO_MC_PATCH      8
+#define DSVG_DEC_NO_INPLACE_PRED  16
+#define DSVG_DEC_NO_SYM_OV        32
+#define DSVG_DEC_NO_MC_FUSION     64
+#define DSVG_DEC_PROFILED         128
+typedef struct dsvg_dec_plan {
+    int cap_jobs, cap_ilist;
+    int *order, *path, *dec_sym;
+    unsigned char *wide, *inplace;
+    int *dc, *runs, *len;
+    long long *bitpos, *blob_off, *meta_off;
+    int *ilist;
+    /* of the geometry: blocks per picture and per row, patch motion compensation possible, luma / chroma planes that can take symbols
+     * and that have cells shared between scan regions, a second coding stream exists, scan chunks per plane */
+    int nblk, nbh, mc_patch, sym_ok[2], ov[2], second_stream, nchunks[3];
+    int lim[2][16];                /* the sixteen per-level limits: [0] a P picture's ranges, [1] wide */
+    int nI;                        /* I pictures of the call */
+    long long blob, nmeta;         /* bytes of the payload blob, parse records */
+    int max_entries, max_chunks;   /* the parse / scatter grids */
+    int insym, f0, anysym;         /* enqueue_recon's insym; first job that may raise a flag; some plane is on the symbol path */
+    int scatter_one, resolve, fork;  /* one scatter launch (else three); k_hz_dec_resolve runs; motion compensation on the second stream */
+    int mc, ex0, ey0, iln;         /* 0 no P picture, 1 k_mc, 2 k_mc_patch plus k_mc by list; ragged 8x8 patches from block (ex0, ey0) on */
+    int draw0, draw1;              /* device jobs [draw0, draw1) get the debug overlay */
+} dsvg_dec_plan;
+int dsvg_decode_plan(int width, int height, int subsamp, int n_recon_slots, int max_jobs, unsigned switches, int force32, int draw_mode,
+                     int njobs, const dsvg_dec_job *jobs, dsvg_dec_plan *out);
+
 #ifdef __cplusplus
 }
 #endif
