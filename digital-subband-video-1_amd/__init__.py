@@ -97,6 +97,25 @@ DEC_NO_SYM, DEC_NO_SYM_I, DEC_ONE_STREAM, DEC_NO_MC_PATCH, DEC_NO_INPLACE_PRED, 
     1, 2, 4, 8, 16, 32, 64, 128)                                                                                           # DSVG_DEC_*
 
 
+LOAD_NO_UNPACK_SIDES, LOAD_NO_LEVEL_SIDES, LOAD_NO_FUSE_LEVEL2 = 1, 2, 4                                                  # DSVG_LOAD_NO_*
+UNPACK_BODIES = ("none", "scalar", "v16", "fused1", "fused2")                                                              # DSVG_UNPACK_*
+BORDER_KERNELS = (None, "k_extend", "k_extend16")                                                                          # DSVG_BORDER_*
+LOAD_KERNELS = ("k_unpack", "k_extend", "k_extend16", "k_ds2x", "k_luma_sum")                                              # kernel ids 0..4
+
+
+class LoadLevel(_C.Structure):
+    """dsvg_load_level (include/dsvg.h): one level of a source load's plan"""
+    _fields_ = [(k, _C.c_int) for k in ("w", "h", "border", "tb_only", "ds2x", "ds2x_sides", "ds2x_tail", "src_odd_w", "src_odd_h")]
+
+
+class LoadPlan(_C.Structure):
+    """dsvg_load_plan_out (include/dsvg.h): the plan of a source load"""
+    _fields_ = [("levels", _C.c_int), ("sides", _C.c_int), ("fuse1", _C.c_int), ("fuse2", _C.c_int), ("sides1", _C.c_int), ("sides2", _C.c_int),
+                ("body", _C.c_int * 3), ("grid_planes", _C.c_int), ("level", LoadLevel * 6), ("luma_sum", _C.c_int), ("luma_sum_dword", _C.c_int),
+                ("ring_x16", _C.c_int), ("ring_y4", _C.c_int), ("chroma_in_place_ok", _C.c_int), ("luma_in_place_ok", _C.c_int),
+                ("launches", _C.c_int * 5), ("bytes", _C.c_double * 5)]
+
+
 class PicJob(_C.Structure):
     """dsvg_pic_job (include/dsvg.h): one picture of a coding call"""
     _fields_ = [("src_slot", _C.c_int), ("ref_recon_slot", _C.c_int), ("recon_slot", _C.c_int), ("quant", _C.c_int), ("mvs", _C.c_void_p),
@@ -599,6 +618,28 @@ def hme_plan(w, h, fmt, npairs=1, csum_table=1):
     if n < 0:
         _chk(n, "dsvg_hme_plan")
     return [steps[i].as_dict() for i in range(n)]
+
+
+def load_plan(w, h, fmt, pyramid_levels=0, with_pyramid=1, src_mod16=0, pitch_mod16=0, switches=0, n=1, n_chroma_in_place=0, n_luma_in_place=0):
+    """what a source load of n frames decides in a context of this geometry (pyramid_levels as dsvg_ctx_create takes it), for a source at
+    this address and frame distance modulo 16, with the A/B switches of the mask `switches` (LOAD_NO_*): a dict of dsvg_load_plan_out's fields, the
+    bodies and kernels by name, `levels` a list of per-level dicts, `kernels` {kernel name: (launches, algorithmic bytes)} of the
+    kernels that run; needs no device"""
+    L = lib()
+    L.dsvg_load_plan.argtypes = [_C.c_int] * 7 + [_C.c_uint, _C.c_int, _C.c_int, _C.c_int, _C.POINTER(LoadPlan)]
+    p = LoadPlan()
+    _chk(L.dsvg_load_plan(w, h, fmt, pyramid_levels, with_pyramid, src_mod16, pitch_mod16, switches, n, n_chroma_in_place, n_luma_in_place, _C.byref(p)), "dsvg_load_plan")
+    d = {k: getattr(p, k) for k in ("sides", "fuse1", "fuse2", "sides1", "sides2", "grid_planes", "luma_sum", "luma_sum_dword", "ring_x16", "ring_y4",
+                                    "chroma_in_place_ok", "luma_in_place_ok")}
+    d["body"] = tuple(UNPACK_BODIES[b] for b in p.body)
+    d["levels"] = []
+    for l in range(p.levels + 1):
+        o = p.level[l]
+        lv = {k: getattr(o, k) for k in ("w", "h", "tb_only", "ds2x", "ds2x_sides", "ds2x_tail", "src_odd_w", "src_odd_h")}
+        lv["border"] = BORDER_KERNELS[o.border]
+        d["levels"].append(lv)
+    d["kernels"] = {LOAD_KERNELS[k]: (p.launches[k], p.bytes[k]) for k in range(5) if p.launches[k]}
+    return d
 
 
 def code_batch_plan(w, h, fmt, n_recon_slots, n_src_slots, max_jobs, out_slots, code_streams, switches, nsteps, njobs, jobs, rc=None):

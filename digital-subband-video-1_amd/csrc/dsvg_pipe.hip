@@ -11,6 +11,7 @@
 #include "dsvg_host.hpp"
 #include "dsvg_batch_plan.h"
 #include "dsvg_dec_plan.h"
+#include "dsvg_load_plan.h"
 #include <ctime>
 extern "C" void dsv1_par_for(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);     // host/dsv1_util.c: the worker pool
 extern "C" void dsv1_par_for_long(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);
@@ -241,6 +242,7 @@ struct dsvg_ctx {
     long ydirect_frames = 0;
     int *slot_cs_h = nullptr, *slot_cs_d = nullptr;
     bool cdirect_ok = false;         // the geometry allows in-place chroma (even chroma planes, rows of whole 8-byte patches)
+    LoadGeo lgeo = {};               // what the plan of a source load reads of the context (dsvg_load_plan.h)
     long cdirect_frames = 0;         // frames loaded that way (tests)
     int dec_par = 0;
     // Decoder, sparse symbol path: a call is enqueued optimistically; its scatter stage flags pictures the int16 symbol planes
@@ -604,6 +606,59 @@ static DecGeo dec_geo(const CtxGeo &geo, int n_recon_slots, int max_jobs, bool m
     return D;
 }
 
+// What the plan of a source load reads of a context (dsvg_load_plan.h), from the layouts of its pyramid (make_hme_geo) and its block
+// size: dsvg_ctx_create_blk keeps it, and dsvg_load_plan asks the plan about the same record without a context.  slabs: the source
+// slabs of levels 0 .. levels, or null: bases as Slab::alloc gives them (multiples of 16).
+static LoadGeo load_geo(const HmeArgs &A, const Slab *slabs)
+{
+    LoadGeo G = {};
+    G.levels = A.levels;
+    for (int l = 0; l <= A.levels; l++) {
+        const FrameLayout &L = A.L[l];
+        G.w[l] = L.w[0]; G.h[l] = L.h[0];
+        bool ok = (L.pitch % 16) == 0 && (!slabs || ((uintptr_t)slabs[l].p % 16) == 0);
+        for (int c = 0; c < (l ? 1 : 3); c++) ok = ok && (L.stride[c] % 16) == 0 && (L.off[c] % 16) == 0;
+        G.lay16[l] = ok;
+    }
+    const FrameLayout &L0 = A.L[0], &LT = A.L[A.levels];
+    G.cw = L0.w[1]; G.ch = L0.h[1];
+    G.c_alike = L0.w[1] == L0.w[2] && L0.h[1] == L0.h[2] && L0.stride[1] == L0.stride[2];
+    G.l2_dword = A.levels >= 2 && (A.L[2].stride[0] & 3) == 0 && (A.L[2].off[0] & 3) == 0 && (A.L[2].pitch & 3) == 0;
+    G.sum_dword = (LT.stride[0] & 3) == 0 && (LT.off[0] & 3) == 0 && (LT.pitch & 3) == 0 && (!slabs || ((uintptr_t)slabs[A.levels].p & 3) == 0);
+    const int deep_r = (2 << A.levels) + 8;         // a level-0 vector's reach (k_hme.hip, `deep`) + the nine-point search, half-pel lattice, window slack
+    G.ring_x16 = (A.blk_w + 2 * deep_r + 15) / 16;
+    G.ring_y4 = (A.blk_h + 2 * deep_r + 3) / 4;
+    return G;
+}
+// The A/B switches of the source load: the process's own, read once -- this sits on the enqueue path.  plan_load itself takes them as
+// an argument, so a caller can ask it about any setting.
+static const LoadSwitches &load_switches()
+{
+    static const LoadSwitches sw = { getenv("DSV1_NO_UNPACK_SIDES") != nullptr, getenv("DSV1_NO_LEVEL_SIDES") != nullptr,
+                                     getenv("DSV1_NO_FUSE_LEVEL2") != nullptr };
+    return sw;
+}
+static_assert(KID_UNPACK == LOAD_K_UNPACK && KID_EXTEND == LOAD_K_EXTEND && KID_EXTEND16 == LOAD_K_EXTEND16 && KID_DS2X == LOAD_K_DS2X &&
+              KID_LUMA_SUM == LOAD_K_LUMA_SUM, "dsvg_load_plan's kernel order is the profiler's");
+
+// The plan of a source load of n frames in a context of this geometry (include/dsvg.h): plan_load, which load_core launches from, on the
+// geometry tables of dsvg_ctx_create, with the switches the caller names instead of the environment's
+extern "C" int dsvg_load_plan(int width, int height, int subsamp, int pyramid_levels, int with_pyramid, int src_mod16, int pitch_mod16, unsigned switches,
+                              int n, int n_chroma_in_place, int n_luma_in_place, dsvg_load_plan_out *out)
+{
+    if (!out || n < 1 || pyramid_levels < 0 || src_mod16 < 0 || src_mod16 > 15 || pitch_mod16 < 0 || pitch_mod16 > 15 || n_chroma_in_place < 0 || n_chroma_in_place > n || n_luma_in_place < 0 || n_luma_in_place > n_chroma_in_place) {
+        dsvg_set_error("bad load_plan arguments"); return DSVG_ERR_ARG;
+    }
+    CtxGeo geo;
+    const int rc = geom_check(width, height, subsamp, geo);
+    if (rc) return rc;
+    HmeArgs A;
+    make_hme_geo(A, geo, width, height, subsamp, pyramid_levels);
+    const LoadSwitches sw = { (switches & DSVG_LOAD_NO_UNPACK_SIDES) != 0, (switches & DSVG_LOAD_NO_LEVEL_SIDES) != 0, (switches & DSVG_LOAD_NO_FUSE_LEVEL2) != 0 };
+    plan_load(load_geo(A, nullptr), sw, with_pyramid != 0, src_mod16, pitch_mod16, n, n_chroma_in_place, n_luma_in_place, *out);
+    return DSVG_OK;
+}
+
 // What the forward launchers decide for an encoder context of this geometry (default block size and pyramid depth, the chroma
 // table of the motion search on): the context's geometry tables, handed to the launchers' own decision functions
 extern "C" int dsvg_dispatch_plan(int width, int height, int subsamp, dsvg_dispatch *out)
@@ -880,16 +935,15 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         if (hipHostMalloc((void **)&c->slot_y_h, 8 * ns + 64, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&c->slot_y_d, 8 * ns + 64) != hipSuccess) { dsvg_set_error("slot tables: out of memory"); return fail(DSVG_ERR_HIP); }
         memset(c->slot_y_h, 0, 8 * ns);
         if (hipMemset(c->slot_y_d, 0, 8 * ns + 64) != hipSuccess) { dsvg_set_error("slot tables: upload failed"); return fail(DSVG_ERR_HIP); }
-        c->cdirect_ok = (c->L[0].w[1] % 8) == 0 && (c->L[0].h[1] % 2) == 0 && c->L[0].w[1] == c->L[0].w[2] && c->L[0].h[1] == c->L[0].h[2] &&
-                        c->L[0].stride[1] == c->L[0].stride[2] && !getenv("DSV1_NO_CHROMA_IN_PLACE");
+        // (the geometry's side of both rules: dsvg_load_plan.h)
+        c->lgeo = load_geo(c->hme, c->src);
+        c->cdirect_ok = load_chroma_in_place_geo(c->lgeo) && !getenv("DSV1_NO_CHROMA_IN_PLACE");
         // luma in place (round 5): the geometry must take the motion search's full-block body and k_unpack's fused pyramid levels 1 and 2
         // (the bordered copy is then read by the level-0 search alone), and the ring must leave an interior worth the trouble
         c->deep_r = (2 << c->levels) + 8;               // a level-0 vector's reach (k_hme.hip, `deep`) + the nine-point search, half-pel lattice, window slack
-        c->ring_x16 = (c->bw + 2 * c->deep_r + 15) / 16;
-        c->ring_y4 = (c->bh + 2 * c->deep_r + 3) / 4;
-        c->ydirect_ok = c->cdirect_ok && c->levels >= 2 && (c->L[0].w[0] % 16) == 0 && (c->L[0].h[0] % 4) == 0 && unpack_fuses_level1(c->L[0]) &&
-                        unpack_fuses_level2(c->L[0], c->L[1], c->L[2]) && 2 * 16 * c->ring_x16 + 64 <= c->L[0].w[0] && 2 * 4 * c->ring_y4 + 64 <= c->L[0].h[0] &&
-                        c->ring_x16 < 256 && c->ring_y4 < 256 && !getenv("DSV1_NO_LUMA_IN_PLACE") && !getenv("DSV1_NO_FUSE_LEVEL2");
+        c->ring_x16 = c->lgeo.ring_x16;
+        c->ring_y4 = c->lgeo.ring_y4;
+        c->ydirect_ok = c->cdirect_ok && load_luma_in_place_geo(c->lgeo) && !getenv("DSV1_NO_LUMA_IN_PLACE") && !getenv("DSV1_NO_FUSE_LEVEL2");
     }
     (void)J;
     // the pipeline streams are non-blocking (no implicit ordering against the NULL stream the memsets above ran on)
@@ -1183,31 +1237,22 @@ static int load_core(dsvg_ctx *c, int first_slot, int n, const uint8_t *dsrc, si
             HIPCHK(hipMemcpyAsync(c->slot_cs_d, c->slot_cs_h, 4 * (size_t)c->n_src, hipMemcpyHostToDevice, c->st_l));
         }
     }
-    // the first pyramid level comes out of the unpack kernel when the luma plane allows it (one read of the frame less)
-    // (the kernel's fused path needs 16-byte aligned frames: a caller's odd device pointer takes the separate passes)
-    const bool fuse1 = with_pyramid && c->levels >= 1 && unpack_fuses_level1(c->L[0]) && ((uintptr_t)dsrc & 15) == 0 && (pitch & 15) == 0;
-    const bool sides = unpack_writes_sides(dsrc, pitch, c->src[0].p, c->L[0]) && !getenv("DSV1_NO_UNPACK_SIDES");
-    // the pyramid levels whose width allows it get their side borders from the kernel that writes their rows as well
-    static const bool no_lsides = getenv("DSV1_NO_LEVEL_SIDES") != nullptr;
-    const bool sides1 = fuse1 && sides && !no_lsides && level_sides_ok(c->src[1].p, c->L[1]);
-    // ... and the second level with it (one pass over level 1 less) when both are exact halvings
-    static const bool no_fuse2 = getenv("DSV1_NO_FUSE_LEVEL2") != nullptr;
-    const bool fuse2 = fuse1 && !no_fuse2 && c->levels >= 2 && unpack_fuses_level2(c->L[0], c->L[1], c->L[2]);
-    const bool sides2 = fuse2 && sides && !no_lsides && level_sides_ok(c->src[2].p, c->L[2]);
+    // what the load launches: decided in one place (plan_load, dsvg_load_plan.h), from the geometry, the source's alignment and the
+    // switches; the launches below follow the plan
+    if (n_chroma < 0) n_chroma = n;
+    dsvg_load_plan_out P;
+    plan_load(c->lgeo, load_switches(), with_pyramid != 0, (int)((uintptr_t)dsrc & 15), (int)(pitch & 15), n, n - n_chroma, n_ring, P);
     tl_mark(c, c->st_l, "load0");
-    launch_unpack(c->st_l, dsrc, pitch, c->src[0].p, c->L[0], first_slot, n, &c->prof, tab_d, fuse1 ? c->src[1].p : nullptr, fuse1 ? &c->L[1] : nullptr, sides, sides1,
-                  fuse2 ? c->src[2].p : nullptr, fuse2 ? &c->L[2] : nullptr, sides2, n_chroma, c->ring_x16, c->ring_y4, n_ring);
-    launch_extend(c->st_l, c->src[0].p, c->L[0], first_slot, n, 3, tab_d, &c->prof, nullptr, sides);
-    if (with_pyramid) {
-        for (int l = 1; l <= c->levels; l++) {
-            const bool fused = (l == 1 && fuse1) || (l == 2 && fuse2);
-            bool ls = fused ? (l == 1 ? sides1 : sides2) : false;
-            if (!fused) {
-                ls = !no_lsides && level_sides_ok(c->src[l].p, c->L[l]);
-                launch_ds2x(c->st_l, c->src[l - 1].p, c->L[l - 1], c->src[l].p, c->L[l], first_slot, n, &c->prof, tab_d, ls);
-            }
-            launch_extend(c->st_l, c->src[l].p, c->L[l], first_slot, n, 1, tab_d, &c->prof, nullptr, ls);
-        }
+    launch_unpack(c->st_l, dsrc, pitch, c->src[0].p, c->L[0], first_slot, n, &c->prof, tab_d, P.fuse1 ? c->src[1].p : nullptr, P.fuse1 ? &c->L[1] : nullptr,
+                  P.sides != 0, P.sides1 != 0, P.fuse2 ? c->src[2].p : nullptr, P.fuse2 ? &c->L[2] : nullptr, P.sides2 != 0, n_chroma, P.ring_x16, P.ring_y4, n_ring);
+    for (int l = 0; l <= c->levels; l++) {
+        const dsvg_load_level &o = P.level[l];
+        if (o.border == DSVG_BORDER_NONE) continue;                     // (the pyramid's levels without the pyramid)
+        if (o.ds2x) launch_ds2x(c->st_l, c->src[l - 1].p, c->L[l - 1], c->src[l].p, c->L[l], first_slot, n, &c->prof, tab_d, o.ds2x_sides != 0);
+        launch_extend(c->st_l, c->src[l].p, c->L[l], first_slot, n, l ? 1 : 3, tab_d, &c->prof, nullptr, o.tb_only != 0);
+    }
+    if (P.luma_sum) {
+        // (a mapped load clears the sums of ALL slots, a contiguous one those of its own: include/dsvg.h, dsvg_load_frames_map)
         if (tab_d) HIPCHK(hipMemsetAsync(c->luma_sums, 0, sizeof(unsigned) * c->n_src, c->st_l));
         else       HIPCHK(hipMemsetAsync(c->luma_sums + first_slot, 0, sizeof(unsigned) * n, c->st_l));
         launch_luma_sum(c->st_l, c->src[c->levels].p, c->L[c->levels], first_slot, n, c->luma_sums, &c->prof, tab_d);
@@ -2122,6 +2167,16 @@ extern "C" int dsvg_download_recon_raw(dsvg_ctx *c, int recon_slot, uint8_t *raw
     OPCHK(dsvg_extend_recon(c, recon_slot));            // the encoder writes only the part of the border that is read
     OPCHK(dsvg_ctx_sync(c));
     HIPCHK(hipMemcpy(raw_out, c->recon.p + (size_t)recon_slot * c->L[0].pitch, bytes, hipMemcpyDeviceToHost));
+    return DSVG_OK;
+}
+
+// a source slot's allocation at one pyramid level, as the loads enqueued so far leave it (tests): waits for the load stream alone
+extern "C" int dsvg_download_source_raw(dsvg_ctx *c, int src_slot, int level, uint8_t *raw_out, size_t bytes)
+{
+    if (!c || !raw_out || src_slot < 0 || src_slot >= c->n_src || level < 0 || level > c->levels || bytes > c->L[level].bytes) return DSVG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->st_l));
+    HIPCHK(hipMemcpy(raw_out, c->src[level].p + (size_t)src_slot * c->L[level].pitch, bytes, hipMemcpyDeviceToHost));
     return DSVG_OK;
 }
 

@@ -423,24 +423,9 @@ __global__ __launch_bounds__(256) void k_frame_add(uint8_t *__restrict__ dst, Fr
 
 static inline int nblk(long items, int cap) { long b = (items + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
 
-// slab1 / L1: when given (and the luma plane qualifies, see unpack_fuses_level1) the first pyramid level is produced
-// by the same kernel
-int unpack_fuses_level1(const FrameLayout &L) { return (L.w[0] & 15) == 0 && (L.h[0] & 1) == 0; }
-// ... and the second one too: four source rows per thread, both levels exact halvings
-int unpack_fuses_level2(const FrameLayout &L, const FrameLayout &L1, const FrameLayout &L2)
-{
-    return unpack_fuses_level1(L) && (L.h[0] & 3) == 0 && L1.w[0] * 2 == L.w[0] && L1.h[0] * 2 == L.h[0] && L2.w[0] * 4 == L.w[0] && L2.h[0] * 4 == L.h[0] &&
-           (L2.stride[0] & 3) == 0 && (L2.off[0] & 3) == 0 && (L2.pitch & 3) == 0;
-}
-// can k_unpack write the side borders (and launch_extend be told tb_only)?  every plane on a 16-byte path of k_unpack and
-// of k_extend16
-bool unpack_writes_sides(const uint8_t *yuv, size_t yuv_pitch, const uint8_t *slab, const FrameLayout &L)
-{
-    bool ok = ((uintptr_t)yuv % 16) == 0 && (yuv_pitch % 16) == 0 && ((uintptr_t)slab % 16) == 0 && (L.pitch % 16) == 0 &&
-              ((size_t)L.w[0] * L.h[0] % 16) == 0 && ((size_t)L.w[1] * L.h[1] % 16) == 0;
-    for (int c = 0; c < 3; c++) ok = ok && (L.w[c] % 16) == 0 && (L.stride[c] % 16) == 0 && (L.off[c] % 16) == 0;
-    return ok;
-}
+// slab1 / L1, slab2 / L2: when given (the caller's plan says when the luma plane and the source qualify: plan_load, dsvg_load_plan.h) the
+// first pyramid level / the first two are produced by the same kernel; sides, sides1, sides2: with the side borders of the picture
+// rows of all planes / of those levels
 void launch_unpack(hipStream_t st, const uint8_t *yuv, size_t yuv_pitch, uint8_t *slab, const FrameLayout &L, int first, int n, Prof *pf, const int *slot_tab,
                    uint8_t *slab1, const FrameLayout *L1, bool sides, bool sides1, uint8_t *slab2, const FrameLayout *L2, bool sides2, int n_chroma, int ring_x16, int ring_y4, int n_ring)
 {
@@ -489,11 +474,6 @@ void launch_extend(hipStream_t st, uint8_t *slab, const FrameLayout &L, int firs
     if (v16) hipLaunchKernelGGL(k_extend16, dim3(nblk(it16, 256), nplanes, n), dim3(256), 0, st, slab, L, first, nplanes, slot_tab, jobs, tb_only ? 1 : 0);
     else     hipLaunchKernelGGL(k_extend, dim3(nblk(items, 256), nplanes, n), dim3(256), 0, st, slab, L, first, nplanes, slot_tab);
     if (pf) pf->end(st);
-}
-// can the kernel that writes a level's luma rows (k_ds2x, or k_unpack for the first level) write their side borders too?
-bool level_sides_ok(const uint8_t *slab, const FrameLayout &L)
-{
-    return (L.w[0] % 16) == 0 && (L.stride[0] % 16) == 0 && (L.off[0] % 16) == 0 && (L.pitch % 16) == 0 && ((uintptr_t)slab % 16) == 0;
 }
 void launch_ds2x(hipStream_t st, const uint8_t *sslab, const FrameLayout &SL, uint8_t *dslab, const FrameLayout &DL, int first, int n, Prof *pf, const int *slot_tab, bool sides)
 {

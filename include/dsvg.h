@@ -189,7 +189,11 @@ int dsvg_ingest_part(dsvg_ctx *ctx, void *dptr, size_t offset, const void *host,
 int dsvg_load_frames(dsvg_ctx *ctx, int first_slot, int n, const void *yuv, int yuv_on_device, int with_pyramid);
 /* same, frame i read from yuv + i*frame_pitch bytes (device pointer only) */
 int dsvg_load_frames_strided(dsvg_ctx *ctx, int first_slot, int n, const void *yuv_dev, size_t frame_pitch, int with_pyramid);
-/* same, frame i (at yuv_dev + i*frame_pitch) goes to source slot slots[i]: one launch set for a whole batch */
+/* same, frame i (at yuv_dev + i*frame_pitch) goes to source slot slots[i]: one launch set for a whole batch.
+ * Luma sums: a load with the pyramid replaces the sums (dsvg_get_luma_sums / dsvg_get_avg_luma) of the slots it loads -- a second
+ * load of a slot does not add to the first.  The mapped loads (this call and dsvg_load_frames_map_ex) clear the sums of ALL the
+ * context's slots first, not only of the slots they load: after one, the sum of a slot the call did not name reads 0.  The
+ * contiguous loads above touch the sums of their own slots alone. */
 int dsvg_load_frames_map(dsvg_ctx *ctx, int n, const int *slots, const void *yuv_dev, size_t frame_pitch, int with_pyramid);
 /* same with chroma_in_place (one flag per frame, or NULL): a flagged frame's chroma planes are not copied -- the forward
  * transform and the motion search's chroma test read them from the caller's clip; only its luma gets the bordered copy and
@@ -325,6 +329,13 @@ int dsvg_download_recon_raw(dsvg_ctx *ctx, int recon_slot, uint8_t *raw_out, siz
 int dsvg_recon_border(dsvg_ctx *ctx, int recon_slot, short ext_out[8]);
 int dsvg_download_recon_asis(dsvg_ctx *ctx, int recon_slot, uint8_t *raw_out, size_t bytes);
 int dsvg_extend_recon(dsvg_ctx *ctx, int recon_slot);
+/* The same view of a SOURCE slot (tests): the first `bytes` bytes of source slot `src_slot` at pyramid level `level` (0 = the frame
+ * itself, 1 .. the context's pyramid levels), exactly as the device holds them, in the reference frame layout of that level's
+ * dimensions (rsu(width, level) x rsu(height, level): Y,U,V allocations back to back, 64-px borders).  Levels above 0 carry luma
+ * only: their chroma allocations are never written.  Of a frame loaded with its chroma (or luma) in place, the slot holds what
+ * earlier loads left in those planes (in the luma interior inside the ring).  Waits for the loads enqueued so far; completes
+ * nothing and changes nothing. */
+int dsvg_download_source_raw(dsvg_ctx *ctx, int src_slot, int level, uint8_t *raw_out, size_t bytes);
 /* a frame allocation in the reference layout (as dsvg_download_recon_raw returns it) into a reconstruction slot: how a decoder
  * carries its reference picture over when the stream changes its block size and a new context is needed.  Syncs. */
 int dsvg_upload_recon_raw(dsvg_ctx *ctx, int recon_slot, const uint8_t *raw, size_t bytes);
@@ -638,6 +649,49 @@ typedef struct dsvg_dec_plan {
 } dsvg_dec_plan;
 int dsvg_decode_plan(int width, int height, int subsamp, int n_recon_slots, int max_jobs, unsigned switches, int force32, int draw_mode,
                      int njobs, const dsvg_dec_job *jobs, dsvg_dec_plan *out);
+
+/* The plan of a source load (tests): what dsvg_load_frames / _strided / _map / _map_ex decide on the host for n frames in a context of
+ * this geometry, without a device -- the load's own plan (plan_load, csrc/dsvg_load_plan.h: the load launches from it and decides
+ * nothing itself).  pyramid_levels as dsvg_ctx_create takes it (0: the encoder's own); src_mod16, pitch_mod16: the source pointer and
+ * the distance between two frames modulo 16 (dsvg_load_frames: 0 and the bytes of a packed frame modulo 16); switches: a mask of
+ * DSVG_LOAD_NO_* for the A/B switches DSV1_NO_UNPACK_SIDES, DSV1_NO_LEVEL_SIDES, DSV1_NO_FUSE_LEVEL2, whatever the environment says;
+ * n_chroma_in_place / n_luma_in_place: the frames of the call that took dsvg_load_frames_map_ex's flag (the second only where
+ * luma_in_place_ok).  Returns DSVG_OK or a negative DSVG_ERR_* for a geometry dsvg_ctx_create refuses.
+ *   sides: k_unpack writes the side borders of the picture rows of all three planes; fuse1 / fuse2: it writes pyramid level 1 / levels 1
+ *   and 2 as well; sides1 / sides2: with those levels' side borders.  body[p]: the body of k_unpack plane p of the call's first frame
+ *   takes, DSVG_UNPACK_* (every frame's where pitch_mod16 is 0, else a later frame takes the scalar or the 16-byte body as its own address falls; NONE: no frame of the call copies its chroma); grid_planes: the
+ *   launch's planes.  level[l], l = 0 .. levels (level 0 alone without the pyramid): the luma plane; border = the kernel that writes the
+ *   level's border, tb_only = only the rows above and below; ds2x = k_ds2x writes the level, with the side borders (ds2x_sides), with a
+ *   last dword of a row that is not whole (ds2x_tail), from a level of odd width / height, whose last column / row of means reads a
+ *   border pixel (src_odd_w / src_odd_h).  luma_sum: k_luma_sum runs, on the top level; luma_sum_dword: four samples per load.
+ *   ring_x16, ring_y4: of a luma-in-place frame's bordered copy only the border and the picture's outer ring_x16 x 16 columns and
+ *   ring_y4 x 4 rows are written.  chroma_in_place_ok / luma_in_place_ok: the geometry allows the flag's two effects (the context also
+ *   asks DSV1_NO_CHROMA_IN_PLACE, DSV1_NO_LUMA_IN_PLACE and DSV1_NO_FUSE_LEVEL2).  launches[k], bytes[k]: the launches and the
+ *   algorithmic bytes the profiler books for kernel id k = k_unpack, k_extend, k_extend16, k_ds2x, k_luma_sum (ids 0..4).
+ * Append-only: later versions add fields at the end. */
+#define DSVG_LOAD_NO_UNPACK_SIDES 1
+#define DSVG_LOAD_NO_LEVEL_SIDES  2
+#define DSVG_LOAD_NO_FUSE_LEVEL2  4
+enum { DSVG_UNPACK_NONE, DSVG_UNPACK_SCALAR, DSVG_UNPACK_V16, DSVG_UNPACK_FUSED1, DSVG_UNPACK_FUSED2 };
+enum { DSVG_BORDER_NONE, DSVG_BORDER_EXTEND, DSVG_BORDER_EXTEND16 };
+typedef struct dsvg_load_level {
+    int w, h;
+    int border, tb_only;
+    int ds2x, ds2x_sides, ds2x_tail, src_odd_w, src_odd_h;
+} dsvg_load_level;
+typedef struct dsvg_load_plan_out {
+    int levels;
+    int sides, fuse1, fuse2, sides1, sides2;
+    int body[3], grid_planes;
+    dsvg_load_level level[DSVG_MAX_PYRAMID + 1];
+    int luma_sum, luma_sum_dword;
+    int ring_x16, ring_y4;
+    int chroma_in_place_ok, luma_in_place_ok;
+    int launches[5];
+    double bytes[5];
+} dsvg_load_plan_out;
+int dsvg_load_plan(int width, int height, int subsamp, int pyramid_levels, int with_pyramid, int src_mod16, int pitch_mod16, unsigned switches,
+                   int n, int n_chroma_in_place, int n_luma_in_place, dsvg_load_plan_out *out);
 
 #ifdef __cplusplus
 }
