@@ -1502,6 +1502,92 @@ def overlay_plan(overlays, nsources, frames, counters, W, H, fmt):
     return [(it.overlay, it.source, it.frame, it.op, it.layer) for it in items[:need]], layers.value
 
 
+class SubmitSrc(_C.Structure):
+    """dsv1_submit_src: a source's decision state"""
+    _fields_ = [("next_fnum", _C.c_uint32), ("prev_gop", _C.c_uint32), ("gop", _C.c_int), ("force_metadata", _C.c_int),
+                ("do_scd", _C.c_int), ("prev_avg_luma", _C.c_int), ("scene_change_delta", _C.c_int)]
+
+
+class SubmitPic(_C.Structure):
+    """dsv1_submit_pic: a picture's decisions"""
+    _fields_ = [("fnum", _C.c_uint32), ("gop_start", _C.c_int), ("is_ref", _C.c_int), ("has_ref", _C.c_int), ("forced_intra", _C.c_int),
+                ("isP", _C.c_int), ("n_intra", _C.c_int), ("reach", _C.c_short * 4), ("cur_slot", _C.c_int), ("ref_slot", _C.c_int),
+                ("out_slot", _C.c_int)]
+
+
+class SubmitStream(_C.Structure):
+    """dsv1_submit_stream: an output stream's state"""
+    _fields_ = [("rpar", _C.c_ubyte), ("has_recon", _C.c_ubyte), ("border_skipped", _C.c_ubyte), ("recon_dropped", _C.c_ubyte),
+                ("next_gop", _C.c_ubyte)]
+
+
+class SubmitJob(_C.Structure):
+    """dsv1_submit_job: one device job of a submit's plan"""
+    _fields_ = [("pic", _C.c_int), ("ref_recon_slot", _C.c_int), ("recon_slot", _C.c_int), ("out_slot", _C.c_int),
+                ("border_hint", _C.c_int), ("remedy", _C.c_int)]
+
+
+class SubmitCall(_C.Structure):
+    """dsv1_submit_call: nsteps frame steps of njobs jobs each, from job `first` on"""
+    _fields_ = [("nsteps", _C.c_int), ("njobs", _C.c_int), ("first", _C.c_int)]
+
+
+class SubmitQuery(_C.Structure):
+    """dsv1_submit_query: the geometry and mode of one submit, and how much of each table its plan wrote"""
+    _fields_ = [("S", _C.c_int), ("R", _C.c_int), ("F", _C.c_int), ("nf", _C.c_int), ("chains", _C.c_int), ("gcount", _C.c_uint),
+                ("par", _C.c_int), ("npix_small", _C.c_int), ("nblk", _C.c_int), ("intra_pct_thresh", _C.c_int), ("abr", _C.c_int),
+                ("serial", _C.c_int), ("keep_all", _C.c_int), ("nf_prev", _C.c_int), ("carry", _C.c_int * 2), ("npairs", _C.c_int),
+                ("next", _C.c_int), ("nremedy", _C.c_int), ("njobs", _C.c_int), ("ncalls", _C.c_int), ("dropped", _C.c_int)]
+
+
+class SubmitTables(_C.Structure):
+    """dsv1_submit_tables: the tables a plan writes"""
+    _fields_ = [("pics", _C.POINTER(SubmitPic)), ("pair_cur", _C.POINTER(_C.c_int)), ("pair_ref", _C.POINTER(_C.c_int)),
+                ("pair_pic", _C.POINTER(_C.c_int)), ("ext", _C.POINTER(_C.c_int)), ("remedy_streams", _C.POINTER(_C.c_int)),
+                ("remedy", _C.POINTER(SubmitJob)), ("jobs", _C.POINTER(SubmitJob)), ("calls", _C.POINTER(SubmitCall)),
+                ("scratch", _C.POINTER(_C.c_int))]
+
+
+def _fields(x):
+    return {n: (list(getattr(x, n)) if hasattr(getattr(x, n), "__len__") else int(getattr(x, n))) for n, _ in x._fields_}
+
+
+def submit_plan(q, src, st, luma, n_intra, prev=None):
+    """the plan of one submit (dsv1_submit_plan), no device.  q: SubmitQuery; src: list of SubmitSrc, one per source; st: list of
+    SubmitStream, one per output stream -- all three are updated as the submit would leave them.  luma: raw luma sums by source slot
+    ((2F + 1) * S of them); n_intra[stream * F + t]: the intra blocks of a motion-search candidate; prev: the SubmitPic array the call
+    before returned as ["_pics"].  Returns a dict of lists of dicts: pics, pairs (cur, ref, pic), ext, remedy_streams, remedy, jobs,
+    calls, and dropped.  Raises ValueError where the submit is refused."""
+    S, R, F = q.S, q.R, q.F
+    N = S * R
+    a_src = (SubmitSrc * S)(*src)
+    a_st = (SubmitStream * N)(*st)
+    a_luma = (_C.c_uint * ((2 * F + 1) * S))(*[int(v) for v in luma])
+    a_ni = (_C.c_int * (N * F))(*[int(v) for v in n_intra])
+    pics = (SubmitPic * (N * F))()
+    pc, pr, pp = (_C.c_int * (S * F))(), (_C.c_int * (S * F))(), (_C.c_int * (S * F))()
+    ext = (_C.c_int * N)()
+    rem, jobs, calls = (SubmitJob * N)(), (SubmitJob * (N * F))(), (SubmitCall * F)()
+    scratch = (_C.c_int * (4 * (F + 1)))()
+    rems = (_C.c_int * N)()
+    P = _C.POINTER
+    tb = SubmitTables(pics, pc, pr, pp, ext, rems, rem, jobs, calls, scratch)
+    L = lib()
+    L.dsv1_submit_plan.restype = _C.c_int
+    L.dsv1_submit_plan.argtypes = [P(SubmitQuery), P(SubmitSrc), P(SubmitStream), P(_C.c_uint), P(_C.c_int), P(SubmitPic), P(SubmitTables)]
+    rc = L.dsv1_submit_plan(_C.byref(q), a_src, a_st, a_luma, a_ni, prev, _C.byref(tb))
+    if rc:
+        raise ValueError("dsv1_submit_plan refused the call (rc=%d)" % rc)
+    for i in range(S):
+        src[i] = a_src[i]
+    for i in range(N):
+        st[i] = a_st[i]
+    return {"_pics": pics, "pics": [_fields(p) for p in pics],
+            "pairs": [(pc[i], pr[i], pp[i]) for i in range(q.npairs)], "ext": list(ext[:q.next]),
+            "remedy_streams": list(rems[:q.nremedy]), "remedy": [_fields(j) for j in rem[:q.nremedy]],
+            "jobs": [_fields(j) for j in jobs[:q.njobs]], "calls": [_fields(c) for c in calls[:q.ncalls]], "dropped": q.dropped}
+
+
 def overlay_from_rgba(rgba, w, h, order, matrix, full_range, fmt, pitch=0):
     """an overlay bitmap's planes (numpy uint8: Y, U, V, A) from an RGB(A) image of w x h in memory order `order` (RGB_*), converted
     with `matrix` (MATRIX_*) at full or limited range to format fmt (dsv1_overlay_from_rgba).  Host only."""

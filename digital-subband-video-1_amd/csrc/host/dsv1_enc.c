@@ -15,16 +15,17 @@
 #include "dsv1_host.h"
 #include "dsvg_rc.h"              /* the rate control, shared with the device (k_rc.hip) */
 
+#include "dsv1_submit_plan.h"     /* what a submit decides: pure functions; this file checks, commits and enqueues */
+
 typedef struct {
-    DSV_FNUM fnum;
-    int gop_start, is_ref, has_ref, forced_intra, isP, quant, n_intra;
-    short reach[4];                  /* min / max of the inter blocks' mv.x >> 1, mv.y >> 1 */
-    int cur_slot, ref_slot, out_slot;
+    dsv1_submit_pic d;               /* the picture's decisions (FIRST: the plans step over these records) */
+    int quant;
     DSV_MV *mvs;
     unsigned char *stable;
     uint8_t *prefix;            /* packet bytes up to (not including) the 11-bit quantiser */
     unsigned prefix_len;
 } pic_t;
+typedef char pic_t_begins_with_its_decisions[offsetof(pic_t, d) == 0 ? 1 : -1];
 
 typedef struct { uint8_t *pkt; size_t cap; } pkt_scratch;   /* packet staging buffer (one per assembling thread) */
 typedef struct { dsv1_batch *b; pic_t *pics; volatile int rc; int nf; } side_ctx;   /* rc: a worker's failure (scratch allocation), checked after the parallel loop; nf: the frames of THIS batch (a background loop outlives the submit call) */
@@ -57,16 +58,24 @@ struct dsv1_batch {
     void *staged_dev[2];
     int nstaged;
     int *slots_cur, *slots_ref, *pair_pic, *out_slots;
-    unsigned char *rpar;             /* per stream: which of its two reconstruction slots holds the current reference */
-    unsigned char *has_recon;        /* per stream: a reference picture has been coded */
-    unsigned char *border_skipped;   /* per stream: the last reconstruction was coded with border_hint (next picture: a GOP start) */
+    /* per output stream (dsv1_submit_stream): rpar = which of its two reconstruction slots holds the current reference, has_recon = a
+     * reference picture has been coded, border_skipped = the last reconstruction was coded with border_hint (next picture: a GOP
+     * start), recon_dropped (below), next_gop = the stream's next frame number starts a GOP.  st is the state, written ONLY by the two
+     * commit steps of a submit; st_new is what a plan makes of it.  dec / dec_new: the sources' decision state the same way (the
+     * encoders hold it between calls) */
+    dsv1_submit_stream *st, *st_new;
+    dsv1_submit_src *dec, *dec_new;
+    dsv1_submit_job *sjobs;          /* [nstreams * F] the plan's jobs in enqueue order, and its calls */
+    dsv1_submit_call *calls;
+    int *ext;                        /* [nstreams] reconstructions to extend after all */
+    unsigned char *inpl;             /* [nsrc * F] which frames of a held clip stay in place */
     /* Round 5: a picture nobody predicts from gets no reconstruction (dsvg_pic_job.recon_slot = -1: no inverse transform).  Inside a call
      * that is known exactly (the next picture of the stream has no reference: it starts a GOP or a scene).  For a call's LAST picture it
      * is known when the next frame number starts a GOP (dsv_encoder.c:702-708) -- unless the caller renumbers the stream in between
      * (dsv1_batch_set_fnum); the next submit then finds a P picture where a GOP start was promised and codes the dropped picture once
      * more, this time keeping its reconstruction (remedy_dropped: same source slot, vectors, flags and quantiser -- they are still in
-     * the other half of pics[] -- the packet is discarded).  ABR streams keep their last reconstruction (their quantisers live on the device). */
-    unsigned char *recon_dropped;    /* per stream: the last picture of the batch before was coded without a reconstruction */
+     * the other half of pics[] -- the packet is discarded).  ABR streams keep their last reconstruction (their quantisers live on the device).
+     * recon_dropped: the last picture of the batch before was coded without a reconstruction */
     int nf_prev;                     /* frames per stream of the batch before */
     int keep_all;                    /* DSV1_RECON_ALL=1: reconstruct every reference picture, read or not */
     long n_dropped, n_remedied;
@@ -89,7 +98,7 @@ struct dsv1_batch {
      * that decides what a chain is -- GOP starts, scene changes, forced-intra P pictures, the stability flags -- depends on
      * source pixels only and is replayed serially on the host first (the always-exact two-pass scheme). */
     int chains;
-    int *ch_start, *ch_len, *ch_pair, *ch_cur;   /* per chain of the call: first picture, length, reconstruction slot pair, slot of the pair that holds its newest reconstruction */
+    int *ch;                         /* the chain plan's scratch (dsv1_sp_plan_chains) */
     int carry_pair, carry_cur;       /* the pair / slot that holds the reconstruction of the call's last picture (the next call may predict from it) */
     /* Quality measurement (dsv1_batch_sse_enable): the device sums the squared errors of every picture per plane into its out slot
      * (dsvg_ctx_sse_enable).  The two batches in flight use the two halves of the out slots, so batch i's sums stay on the device
@@ -104,7 +113,6 @@ struct dsv1_batch {
     dsv1_srcchain src;
 };
 
-/* source slot of frame number g (per-stream counter) of stream s */
 /* host-side phase timing (DSV1_HOST_PROF=1): where a batch's wall time goes inside submit / collect */
 #include <time.h>
 #include <stddef.h>
@@ -150,14 +158,13 @@ const char *dsv1_host_prof_name(int k) { return k >= 0 && k < HP_N ? hp_nm[k] : 
  * parallel loop over them on the worker pool (dsv1_par_for).  Workers: DSV1_HOST_THREADS, else min(12, cores / ranks on the node / 2); never more than streams. */
 #include <pthread.h>
 #include <unistd.h>
-static int slot_of(const dsv1_batch *b, int s, unsigned g) { return (int)(g % (unsigned)b->rows) * b->nsrc + s; }     /* s: source */
 
 void *dsv1_batch_ctx(dsv1_batch *b) { return b ? (void *)b->ctx : NULL; }
 int dsv1_batch_recon_slot(const dsv1_batch *b, int stream)
 {
-    if (!b || stream < 0 || stream >= b->nstreams || !b->has_recon[stream]) return -1;
+    if (!b || stream < 0 || stream >= b->nstreams || !b->st[stream].has_recon) return -1;
     if (b->chains) return b->carry_cur;
-    return stream + b->nstreams * b->rpar[stream];
+    return stream + b->nstreams * b->st[stream].rpar;
 }
 
 /* the allocations of batch_open_on / dsv1_batch_open go through here so that a test can make the n-th one fail
@@ -189,8 +196,8 @@ void dsv1_batch_close(dsv1_batch *b)
     }
     free(b->pics); free(b->mvpool); free(b->stabpool); free(b->prefixpool);
     free(b->slots_cur); free(b->slots_ref); free(b->pair_pic); free(b->out_slots);
-    free(b->luma); free(b->mv_tmp); free(b->jobs); free(b->outs); free(b->rcjobs); free(b->sc0.pkt); free(b->rpar); free(b->has_recon); free(b->border_skipped); free(b->recon_dropped);
-    free(b->ch_start); free(b->ch_len); free(b->ch_pair); free(b->ch_cur);
+    free(b->luma); free(b->mv_tmp); free(b->jobs); free(b->outs); free(b->rcjobs); free(b->sc0.pkt);
+    free(b->st); free(b->dec); free(b->sjobs); free(b->calls); free(b->ext); free(b->inpl); free(b->ch);
     free(b->rc_dev); free(b->rc_par);
     for (i = 0; i < DSVG_Q_KINDS; i++) free(b->q[i].v);
     free(b);
@@ -232,10 +239,13 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     B_ALLOC(slots_ref, int, np, sizeof(int));
     B_ALLOC(pair_pic, int, np, sizeof(int));
     B_ALLOC(out_slots, int, np, sizeof(int));
-    B_ALLOC(rpar, unsigned char, nstreams, 1);
-    B_ALLOC(has_recon, unsigned char, nstreams, 1);
-    B_ALLOC(border_skipped, unsigned char, nstreams, 1);
-    B_ALLOC(recon_dropped, unsigned char, nstreams, 1);
+    B_ALLOC(st, dsv1_submit_stream, 2 * (size_t)nstreams, sizeof(dsv1_submit_stream));
+    B_ALLOC(dec, dsv1_submit_src, 2 * (size_t)nsrc, sizeof(dsv1_submit_src));
+    b->st_new = b->st + nstreams; b->dec_new = b->dec + nsrc;
+    B_ALLOC(sjobs, dsv1_submit_job, np, sizeof(dsv1_submit_job));
+    B_ALLOC(calls, dsv1_submit_call, F, sizeof(dsv1_submit_call));
+    B_ALLOC(ext, int, nstreams, sizeof(int));
+    B_ALLOC(inpl, unsigned char, (size_t)nsrc * F, 1);
     B_ALLOC(luma, unsigned, (size_t)b->rows * nsrc, sizeof(unsigned));
     B_ALLOC(mv_tmp, DSV_MV, (size_t)nsrc * F * b->nblk, sizeof(DSV_MV));
     B_ALLOC(jobs, dsvg_pic_job, np, sizeof(dsvg_pic_job));
@@ -245,12 +255,7 @@ static int batch_open_on(dsv1_batch **out, DSV_ENCODER *encs, int own, int devic
     B_ALLOC(rc_par, dsvg_rc_state, 2 * (size_t)nstreams, sizeof(dsvg_rc_state));
     { const char *e = getenv("DSV1_ABR_SERIAL"); b->abr_dev = !chains && !(e && atoi(e) != 0); }
     { const char *e = getenv("DSV1_RECON_ALL"); b->keep_all = e && atoi(e) != 0; }
-    if (chains) {
-        B_ALLOC(ch_start, int, (size_t)F + 1, sizeof(int));
-        B_ALLOC(ch_len, int, (size_t)F + 1, sizeof(int));
-        B_ALLOC(ch_pair, int, (size_t)F + 1, sizeof(int));
-        B_ALLOC(ch_cur, int, (size_t)F + 1, sizeof(int));
-    }
+    if (chains) B_ALLOC(ch, int, 4 * ((size_t)F + 1), sizeof(int));
     b->sc0.cap = (size_t)b->prefix_cap + b->g.plane_out_cap[0] + 2 * b->g.plane_out_cap[1] + 256;
     b->sc0.pkt = (uint8_t *)b_calloc(1, b->sc0.cap);
     if (!b->sc0.pkt) goto nomem;
@@ -458,7 +463,7 @@ static void stability_update(DSV_ENCODER *e, pic_t *pc, int nblk)
         /* (acc / div == 0 with C's truncating division and div >= 1 is -div < acc < div -- the accumulators are signed 16-bit
          * fields and may wrap: no division per block) */
 #define NEAR0(a) ((a) < div && (a) > -div)
-        if (pc->isP) {
+        if (pc->d.isP) {
             const DSV_MV *mv = &pc->mvs[i];
             if (mv->mode == 0) {
                 e->stability[i].x += abs(mv->u.mv.x) >> 2;
@@ -574,7 +579,7 @@ static int assemble(dsv1_batch *b, int s, pic_t *pc, const dsvg_pic_out *po, DSV
     size_t need = (size_t)pc->prefix_len + 64;
     (void)sc;
     for (p = 0; p < 3; p++) need += po->nbytes[p] + 48;
-    if (pc->gop_start) {
+    if (pc->d.gop_start) {
         uint8_t mb[64];
         const unsigned n = write_meta_packet(e, mb);
         if (dsv1_buf_append(out, mb, n)) return DSVG_ERR_ARG;
@@ -582,9 +587,9 @@ static int assemble(dsv1_batch *b, int s, pic_t *pc, const dsvg_pic_out *po, DSV
     if (b->abr_dev && e->rc_mode != DSV_RATE_CONTROL_CRF) {
         /* the device chose this picture's quantiser (k_rc): replay the choice here -- it also advances this stream's host-side
          * state -- and refuse the batch if the two disagree (same code on both sides: include/dsvg_rc.h) */
-        pc->quant = pick_quant_par(e, par, pc->isP, pc->forced_intra);
+        pc->quant = pick_quant_par(e, par, pc->d.isP, pc->d.forced_intra);
         if (pc->quant != po->rc_quant) {
-            dsv1_log(1, "rate control: stream %d picture %u: the device coded with quantiser %d, the host replay says %d", s, (unsigned)pc->fnum, (int)po->rc_quant, pc->quant);
+            dsv1_log(1, "rate control: stream %d picture %u: the device coded with quantiser %d, the host replay says %d", s, (unsigned)pc->d.fnum, (int)po->rc_quant, pc->quant);
             return DSVG_ERR_RC;
         }
     }
@@ -617,10 +622,10 @@ static int assemble(dsv1_batch *b, int s, pic_t *pc, const dsvg_pic_out *po, DSV
     bw_align(&w);
     len = bw_bytes(&w);
     if (b->abr_dev && e->rc_mode != DSV_RATE_CONTROL_CRF && len != po->rc_pkt_len) {
-        dsv1_log(1, "rate control: stream %d picture %u: packet of %u bytes, the device counted %u", s, (unsigned)pc->fnum, len, (unsigned)po->rc_pkt_len);
+        dsv1_log(1, "rate control: stream %d picture %u: packet of %u bytes, the device counted %u", s, (unsigned)pc->d.fnum, len, (unsigned)po->rc_pkt_len);
         return DSVG_ERR_RC;
     }
-    rc_after_packet(e, par, pc->isP, len);
+    rc_after_packet(e, par, pc->d.isP, len);
     link_packet(e, pkt, len, 0);
     out->len += len;
     return DSVG_OK;
@@ -639,28 +644,9 @@ static void side_stream(void *ctx, int s, int tid)
     (void)tid;
     for (t = 0; t < b->nf_cur; t++) {
         pic_t *pc = &c->pics[s * b->R * F + t];
-        if (pc->has_ref) {
-            int nintra = 0, i;
-            int x0 = 0, x1 = 0, y0 = 0, y1 = 0;           /* full-pel reach of the inter blocks' vectors */
-            for (i = 0; i < nblk; i++) {
-                const DSV_MV *m = &pc->mvs[i];
-                if (m->mode != 0) { nintra++; continue; }
-                {
-                    const int dx = m->u.mv.x >> 1, dy = m->u.mv.y >> 1;
-                    if (dx < x0) x0 = dx;
-                    if (dx > x1) x1 = dx;
-                    if (dy < y0) y0 = dy;
-                    if (dy > y1) y1 = dy;
-                }
-            }
-            pc->n_intra = nintra;
-            pc->reach[0] = (short)x0; pc->reach[1] = (short)x1; pc->reach[2] = (short)y0; pc->reach[3] = (short)y1;
-            pc->forced_intra = 0;
-            if (nintra * 100 / nblk > e->intra_pct_thresh) { pc->has_ref = 0; pc->forced_intra = 1; }
-        }
-        pc->isP = pc->has_ref;
+        dsv1_sp_pic_side(&pc->d, (const dsvg_mv *)pc->mvs, nblk, e->intra_pct_thresh);
         stability_update(e, pc, nblk);
-        if (pc->isP) e->refresh_ctr++;               /* dsv_enc dsv_encoder.c:812-814 */
+        if (pc->d.isP) e->refresh_ctr++;               /* dsv_enc dsv_encoder.c:812-814 */
     }
 }
 static void prefix_one(const dsv1_batch *b, pic_t *pc, uint8_t *tmp);
@@ -683,15 +669,15 @@ static void prefix_one(const dsv1_batch *b, pic_t *pc, uint8_t *tmp)
     bitw w;
     memset(pc->prefix, 0, (size_t)b->prefix_cap);
     bw_init(&w, pc->prefix);
-    write_pkt_hdr(&w, DSV_PT_PIC | (pc->is_ref << 1) | pc->has_ref);
+    write_pkt_hdr(&w, DSV_PT_PIC | (pc->d.is_ref << 1) | pc->d.has_ref);
     bw_align(&w);
-    bw_bits(&w, 32, pc->fnum);
+    bw_bits(&w, 32, pc->d.fnum);
     bw_align(&w);
     bw_ueg(&w, (unsigned)b->g.blk_w >> 2);
     bw_ueg(&w, (unsigned)b->g.blk_h >> 2);
     bw_align(&w);
     stability_write(pc, b->nblk, &w, tmp);
-    if (pc->has_ref) {
+    if (pc->d.has_ref) {
         bw_align(&w);
         motion_pass(b, pc, &w, tmp);
     }
@@ -708,91 +694,30 @@ static void prefix_picture(void *ctx, int t, int tid)
     free(tmp);
 }
 
-/* Chain mode, step 5 of a submit: the call's pictures -- decisions, motion fields and stability flags all known -- fall into
- * chains (a picture without a reference starts one; the call's first picture continues the chain the call before left open
- * when it is a P picture).  Chains do not depend on each other, so frame step k codes the k-th picture of every chain of a
- * round (at most `chains` side by side); consecutive steps with the same number of live chains go to the device as one
- * dsvg_code_batch call.  Calls are ordered against each other on the coding streams, so a slot pair may be reused by a later
- * round, and a chain may change its position from call to call. */
-static int code_chains(dsv1_batch *b, pic_t *pics, int nf, int par)
+/* the device jobs of n entries of a plan: dsv1_sp_fill_job writes what was decided, this adds the caller's half -- the quantiser and
+ * the pointers to the picture's tables */
+static void job_from_plan(dsvg_pic_job *j, const pic_t *pc, const dsv1_submit_job *sj)
 {
-    const int C = b->chains;
-    DSV_ENCODER *e = &b->enc[0];
-    int nch = 0, t, g0, rc, os = par * b->F;
-    for (t = 0; t < nf; t++) {
-        if (t == 0 || !pics[t].isP) { b->ch_start[nch] = t; b->ch_len[nch] = 0; nch++; }
-        b->ch_len[nch - 1]++;
-        pics[t].quant = pick_quant(e, pics[t].isP, pics[t].forced_intra);
-    }
-    if (pics[0].isP && b->carry_cur < 0) { dsv1_log(1, "a P picture without a reference picture on the device"); return DSVG_ERR_ARG; }
-    for (g0 = 0; g0 < nch; g0 += C) {
-        const int gn = nch - g0 < C ? nch - g0 : C;
-        int c, L = 0, k = 0, nextpair = 0;
-        for (c = g0; c < g0 + gn; c++) {
-            if (b->ch_len[c] > L) L = b->ch_len[c];
-            if (c == 0 && pics[0].isP) { b->ch_pair[c] = b->carry_pair; b->ch_cur[c] = b->carry_cur; continue; }
-            /* C + 1 pairs: the one the open chain of the call before lives in is left alone while that chain goes on (round 0) */
-            if (g0 == 0 && pics[0].isP && nextpair == b->carry_pair) nextpair++;
-            b->ch_pair[c] = nextpair++;
-            b->ch_cur[c] = -1;
-        }
-        while (k < L) {
-            int nj = 0, k2, kk, idx = 0;
-            for (c = g0; c < g0 + gn; c++) nj += b->ch_len[c] > k;
-            for (k2 = k + 1; k2 < L; k2++) {
-                int n2 = 0;
-                for (c = g0; c < g0 + gn; c++) n2 += b->ch_len[c] > k2;
-                if (n2 != nj) break;
-            }
-            for (kk = k; kk < k2; kk++)
-                for (c = g0; c < g0 + gn; c++) {
-                    pic_t *pc;
-                    dsvg_pic_job *j;
-                    int tt, last_of_chain;
-                    if (b->ch_len[c] <= kk) continue;
-                    tt = b->ch_start[c] + kk;
-                    pc = &pics[tt];
-                    j = &b->jobs[idx++];
-                    memset(j, 0, sizeof(*j));
-                    j->src_slot = pc->cur_slot;
-                    j->ref_recon_slot = pc->isP ? b->ch_cur[c] : -1;
-                    /* (a chain's last picture whose successor starts the next chain of this submit has no reader: no reconstruction,
-                     * struct dsv1_batch, recon_dropped) */
-                    if (pc->is_ref && kk + 1 == b->ch_len[c] && tt + 1 < nf && !b->keep_all) {
-                        j->recon_slot = -1;
-                        b->n_dropped++;
-                    } else
-                    if (pc->is_ref) {
-                        /* the pair's other slot: the prediction is written straight into it (dsvg_code_batch) */
-                        b->ch_cur[c] = 2 * b->ch_pair[c] + (b->ch_cur[c] == 2 * b->ch_pair[c] ? 1 : 0);
-                        j->recon_slot = b->ch_cur[c];
-                    } else j->recon_slot = -1;
-                    j->quant = pc->quant;
-                    j->mvs = (const dsvg_mv *)pc->mvs;
-                    j->stable_blocks = pc->stable;
-                    pc->out_slot = os++;
-                    j->out_slot = pc->out_slot;
-                    j->no_intra_blocks = pc->isP && pc->n_intra == 0;
-                    j->has_reach = pc->isP;
-                    memcpy(j->mv_reach, pc->reach, sizeof pc->reach);
-                    /* who predicts from this reconstruction?  The chain's next picture -- in this call (the device then writes
-                     * the border as far as that picture's vectors reach), or in a later one (0: the whole border).  The chain's
-                     * last picture: nobody, when the stream's next picture is known to be an I picture (it starts the next chain
-                     * of this submit, or it starts a GOP: dsv_encoder.c:702-708); else unknown */
-                    last_of_chain = kk + 1 == b->ch_len[c];
-                    if (!last_of_chain) j->border_hint = kk + 1 < k2;
-                    else if (tt + 1 < nf) j->border_hint = 1;
-                    else j->border_hint = e->force_metadata || (DSV_FNUM)(e->prev_gop + (DSV_FNUM)e->gop) <= e->next_fnum;
-                    if (tt + 1 == nf) b->border_skipped[0] = (unsigned char)(j->border_hint && j->recon_slot >= 0);
-                }
-            if ((rc = dsvg_code_batch(b->ctx, k2 - k, nj, b->jobs))) return rc;
-            k = k2;
-        }
-    }
-    if (pics[nf - 1].is_ref) {
-        b->carry_pair = b->ch_pair[nch - 1]; b->carry_cur = b->ch_cur[nch - 1];
-        b->has_recon[0] = 1;
-    }
+    dsv1_sp_fill_job(j, &pc->d, sj);
+    j->quant = pc->quant;
+    j->mvs = (const dsvg_mv *)pc->mvs;
+    j->stable_blocks = pc->stable;
+}
+static void jobs_from_plan(const pic_t *pics, const dsv1_submit_job *sj, int n, dsvg_pic_job *jobs)
+{
+    int i;
+    for (i = 0; i < n; i++) job_from_plan(&jobs[i], &pics[sj[i].pic], &sj[i]);
+}
+
+/* Step 8 of a submit, CRF: the plan's calls, jobs in b->jobs.  Batch mode: one call of the whole batch (one upload).  Chain mode
+ * (dsv1_sp_plan_chains): chains do not depend on each other, so frame step k codes the k-th picture of every chain of a round;
+ * calls are ordered against each other on the coding streams, so a slot pair may be reused by a later round, and a chain may change
+ * its position from call to call. */
+static int code_calls(dsv1_batch *b, int ncalls)
+{
+    int k, rc;
+    for (k = 0; k < ncalls; k++)
+        if ((rc = dsvg_code_batch(b->ctx, b->calls[k].nsteps, b->calls[k].njobs, b->jobs + b->calls[k].first))) return rc;
     return DSVG_OK;
 }
 
@@ -836,40 +761,18 @@ static void asm_piece(void *ctx, int first, int count)
  * (each quantiser needs the previous packet size) runs frame step by frame step and leaves nothing
  * pending except the already assembled packets. */
 static int stage_n(dsv1_batch *b, const void *yuv_host, int nf);
-static int code_chains(dsv1_batch *b, pic_t *pics, int nf, int par);
 static void prefix_picture(void *ctx, int t, int tid);
-/* the streams listed in b->out_slots[0..n) had the reconstruction of their last picture dropped and need it after all (struct dsv1_batch,
- * recon_dropped): code those pictures again, each into the free slot of its stream's pair.  Everything a picture was coded from is still
- * there -- its source frame (the ring keeps a call's last frames for the next call's motion search, copied whole), the reconstruction it
- * predicted from (its stream's current slot: nothing has been kept since), its vectors, flags and quantiser (the other half of pics[]).
- * The packets go to the first out slots of the half this submit is about to use and are never fetched.  Rare (a renumbered stream): the
- * device is drained before and after instead of ordering the extra call against the streams of its neighbours. */
+/* n streams had the reconstruction of their last picture dropped and need it after all (struct dsv1_batch, recon_dropped): those pictures
+ * are coded again as dsv1_sp_plan_remedy planned (b->sjobs), each into the free slot of its stream's pair.  Everything a picture was coded
+ * from is still there -- its source frame (the ring keeps a call's last frames for the next call's motion search, copied whole), the
+ * reconstruction it predicted from (its stream's current slot: nothing has been kept since), its vectors, flags and quantiser (the other
+ * half of pics[]).  The packets go to the first out slots of the half this submit is about to use and are never fetched.  Rare (a
+ * renumbered stream): the device is drained before and after instead of ordering the extra call against the streams of its neighbours. */
 static int remedy_dropped(dsv1_batch *b, int n, int par)
 {
-    const int S = b->nstreams, F = b->F;
-    const pic_t *prev = b->pics + (size_t)(par ^ 1) * S * F;
-    int i, rc;
-    if (b->nf_prev < 1) return DSVG_ERR_ARG;
+    int rc;
     if ((rc = dsvg_ctx_sync(b->ctx))) return rc;
-    for (i = 0; i < n; i++) {
-        const int s = b->out_slots[i];
-        const pic_t *pp = &prev[s * F + b->nf_prev - 1];
-        dsvg_pic_job *j = &b->jobs[i];
-        memset(j, 0, sizeof(*j));
-        j->src_slot = pp->cur_slot;
-        j->ref_recon_slot = pp->isP ? s + S * b->rpar[s] : -1;
-        b->rpar[s] ^= 1;
-        b->has_recon[s] = 1;
-        j->recon_slot = s + S * b->rpar[s];
-        j->quant = pp->quant;
-        j->mvs = (const dsvg_mv *)pp->mvs;
-        j->stable_blocks = pp->stable;
-        j->out_slot = par * S * F + i;
-        j->no_intra_blocks = pp->isP && pp->n_intra == 0;
-        j->has_reach = 0;
-        j->border_hint = 0;                          /* the whole border */
-        b->n_remedied++;
-    }
+    jobs_from_plan(b->pics + (size_t)(par ^ 1) * b->nstreams * b->F, b->sjobs, n, b->jobs);
     /* (I and P pictures may be mixed here: one frame step of n jobs on one coding stream) */
     if ((rc = dsvg_code_batch(b->ctx, 1, n, b->jobs))) return rc;
     return dsvg_ctx_sync(b->ctx);
@@ -941,224 +844,182 @@ long dsv1_batch_dropped_recons(const dsv1_batch *b, long *remedied)
     return b->n_dropped;
 }
 
-/* A ladder (struct dsv1_batch): steps 1-4 run per SOURCE (S sources, lead rung s * R), step 5 per OUTPUT stream (N = S * R) */
+/* STEP 1 of every submit, THE CHECK: whatever can be refused on the arguments and the batch alone is refused here -- before a source
+ * pass runs (batch_convert), a staged clip is popped, a frame is loaded or a frame number is given out: a refused submit leaves the
+ * session as it found it.  (One refusal cannot be made here: chain mode's "a P picture without a reference picture on the device"
+ * depends on the motion search; it stays in step 6, after the sources' state has moved.) */
+static int submit_check(const dsv1_batch *b, const void *yuv, int yuv_on_device, const DSV_BUF *abr_out, int nf)
+{
+    int abr;
+    if (!b || !yuv) return DSVG_ERR_ARG;
+    if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
+    if (nf > b->F || (nf > 0 && nf < b->F && b->nstreams != 1)) { dsv1_log(1, "a short batch needs a single stream"); return DSVG_ERR_ARG; }
+    if (b->pending[b->parity]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
+    if (!yuv_on_device && b->nstaged && b->staged_host[0] != yuv) { dsv1_log(1, "a different clip was staged for this submit"); return DSVG_ERR_ARG; }
+    abr = b->enc[0].rc_mode != DSV_RATE_CONTROL_CRF;
+    if (abr && !b->abr_dev && !abr_out) return DSVG_ERR_ARG;        /* the serial path assembles as it goes */
+    if (abr && b->chains) return DSVG_ERR_ARG;
+    if ((b->q[DSVG_Q_XSSE].on || b->q[DSVG_Q_XSSIM].on) && !b->chains && !b->xres_clip) {
+        dsv1_log(1, "source-resolution figures on, but no reference clip named for this submit");
+        return DSVG_ERR_ARG;
+    }
+    return DSVG_OK;
+}
+
+/* COMMIT 1 (step 3): what dsv1_sp_plan_pictures made of the sources' and the streams' state goes into the encoders (every rung follows
+ * its source) and into b->st */
+static void commit_sources(dsv1_batch *b, int nremedied)
+{
+    int s, r;
+    for (s = 0; s < b->nsrc; s++) {
+        const dsv1_submit_src *n = &b->dec_new[s];
+        DSV_ENCODER *e = &b->enc[s * b->R];                 /* the lead rung keeps the source's decision state */
+        if (!e->stability) {
+            e->stability = (struct DSV_STAB_ACC *)dsv_alloc((int)(sizeof(*e->stability) * b->nblk));
+            e->stable_blocks = (unsigned char *)dsv_alloc(b->nblk);
+        }
+        if (e->pyramid_levels == 0) e->pyramid_levels = b->g.pyramid_levels;
+        for (r = 0; r < b->R; r++) {
+            DSV_ENCODER *o = &b->enc[s * b->R + r];
+            o->next_fnum = n->next_fnum; o->prev_gop = n->prev_gop; o->force_metadata = n->force_metadata;
+            o->prev_avg_luma = n->prev_avg_luma; o->pyramid_levels = e->pyramid_levels;
+        }
+    }
+    memcpy(b->st, b->st_new, (size_t)b->nstreams * sizeof(*b->st));
+    b->n_remedied += nremedied;
+}
+
+/* A ladder (struct dsv1_batch): steps 2-5 run per SOURCE (S sources, lead rung s * R), steps 6-8 per OUTPUT stream (N = S * R).  The
+ * decisions are dsv1_submit_plan.h's; the encoders and the per-stream state are written in the two commit steps and nowhere else
+ * (but for the stability accumulators, which the side information updates as it goes: stability_update, the reference's own code). */
 static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *abr_out, int nf, int inplace_ok)
 {
-    int S, N, R, F, nblk, with_pyr, s, r, t, k, rc, npairs = 0, par, nremedy = 0;
-    size_t fb;
-    const DSV_ENCODER *e0;
+    const int S = b->nsrc, N = b->nstreams, R = b->R, F = b->F, nblk = b->nblk, par = b->parity;
+    const DSV_ENCODER *e0 = &b->enc[0];
+    const int with_pyr = e0->gop != DSV_GOP_INTRA, abr = e0->rc_mode != DSV_RATE_CONTROL_CRF;
+    const int devrc = abr && b->abr_dev, serial = abr && !devrc;       /* devrc: rate control on the device, enqueued like a CRF call */
     const uint8_t *dyuv = (const uint8_t *)yuv;
-    pic_t *pics;
+    pic_t *pics = b->pics + (size_t)par * N * F;
+    dsv1_sp_pictures pp;
+    side_ctx sc_;
+    int s, r, t, k, rc, t0, t1;
 
-    if (!b || !yuv) return DSVG_ERR_ARG;
     if (hp_on < 0) hp_on = getenv("DSV1_HOST_PROF") != NULL;
     HP_BEGIN();
-    S = b->nsrc; N = b->nstreams; R = b->R; F = b->F; nblk = b->nblk; fb = b->g.frame_bytes;
     if (nf <= 0) nf = F;
-    if (nf > F || (nf < F && N != 1)) { dsv1_log(1, "a short batch needs a single stream"); return DSVG_ERR_ARG; }
     b->nf_cur = nf;
-    e0 = &b->enc[0];
-    with_pyr = e0->gop != DSV_GOP_INTRA;
-    par = b->parity;
-    if (b->pending[par]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
-    pics = b->pics + (size_t)par * N * F;
+    /* 2. pop the stage; source-only preparation for every frame: bordered layout, pyramid, mean luma */
     if (!yuv_on_device) {
         /* host frames go through the context's double-buffered ingest (copy stream of its own): nothing here waits
          * for the device, and a clip announced with dsv1_batch_stage() is already on its way */
-        if (!b->nstaged) {
-            if ((rc = stage_n(b, yuv, nf))) return rc;
-        } else if (b->staged_host[0] != yuv) {
-            dsv1_log(1, "a different clip was staged for this submit");
-            return DSVG_ERR_ARG;
-        }
+        if (!b->nstaged && (rc = stage_n(b, yuv, nf))) return rc;
         dyuv = (const uint8_t *)b->staged_dev[0];
         b->staged_host[0] = b->staged_host[1]; b->staged_dev[0] = b->staged_dev[1];
         b->nstaged--;
     }
-    /* 1. source-only preparation for every frame: bordered layout, pyramid, mean luma */
+    /* A clip in the CALLER's device memory stays where it is as far as chroma goes (dsvg_load_frames_map_ex): the forward
+     * transform and the motion search read it there, only luma is copied (bordered + pyramid).  Each stream's last frame
+     * of the call is copied whole: the first frame of the next call may search against it when this clip is gone. */
     for (s = 0; s < S; s++)
-        for (t = 0; t < nf; t++) b->slots_cur[s * F + t] = slot_of(b, s, b->gcount + (unsigned)t);
-    {
-        /* A clip in the CALLER's device memory stays where it is as far as chroma goes (dsvg_load_frames_map_ex): the forward
-         * transform and the motion search read it there, only luma is copied (bordered + pyramid).  Each stream's last frame
-         * of the call is copied whole: the first frame of the next call may search against it when this clip is gone. */
-        unsigned char *inpl = NULL;
-        if (inplace_ok && yuv_on_device && (inpl = (unsigned char *)malloc((size_t)S * nf))) {
-            for (s = 0; s < S; s++)
-                for (t = 0; t < nf; t++) inpl[s * nf + t] = (unsigned char)(t + 1 < nf);
+        for (t = 0; t < nf; t++) {
+            b->slots_cur[s * F + t] = dsv1_sp_slot_of(S, b->rows, s, b->gcount + (unsigned)t);
+            b->inpl[s * nf + t] = (unsigned char)(t + 1 < nf);
         }
-        rc = dsvg_load_frames_map_ex(b->ctx, S * nf, b->slots_cur, dyuv, fb, with_pyr, inpl);     /* nf < F only with S == 1 */
-        free(inpl);
-        if (rc) return rc;
-    }
+    if ((rc = dsvg_load_frames_map_ex(b->ctx, S * nf, b->slots_cur, dyuv, b->g.frame_bytes, with_pyr, inplace_ok && yuv_on_device ? b->inpl : NULL))) return rc;     /* nf < F only with S == 1 */
     if (with_pyr && e0->do_scd)
         if ((rc = dsvg_get_luma_sums(b->ctx, 0, b->rows * S, b->luma))) return rc;
-
     HP_MARK(HP_LOAD);
-    /* 2. per source, in coding order: GOP / scene-change decisions; collect ME pairs */
+    /* 3. per source, in coding order: GOP / scene-change decisions, the motion-search pairs; COMMIT 1; then what the plan found owed
+     * from the call before */
     for (s = 0; s < S; s++) {
-        DSV_ENCODER *e = &b->enc[s * R];                    /* the lead rung keeps the source's decision state */
-        for (r = 1; r < R; r++) e->force_metadata |= b->enc[s * R + r].force_metadata;     /* (forced on any rung: a GOP start on all) */
-        if (!e->stability) {
-            e->stability = (struct DSV_STAB_ACC *)dsv_alloc((int)(sizeof(*e->stability) * nblk));
-            e->stable_blocks = (unsigned char *)dsv_alloc(nblk);
-        }
-        if (e->pyramid_levels == 0) e->pyramid_levels = b->g.pyramid_levels;
-        for (t = 0; t < nf; t++) {
-            pic_t *pc = &pics[s * R * F + t];
-            pc->fnum = e->next_fnum++;
-            pc->cur_slot = slot_of(b, s, b->gcount + (unsigned)t);
-            pc->ref_slot = slot_of(b, s, b->gcount + (unsigned)t + (unsigned)b->rows - 1u);
-            pc->out_slot = par * N * F + t * N + s * R;
-            pc->gop_start = 0; pc->forced_intra = 0;
-            if (e->force_metadata || (DSV_FNUM)(e->prev_gop + (DSV_FNUM)e->gop) <= pc->fnum) {
-                pc->gop_start = 1;
-                e->prev_gop = pc->fnum;
-                e->force_metadata = 0;
-            }
-            if (e->gop == DSV_GOP_INTRA) {
-                pc->is_ref = 0; pc->has_ref = 0;
-            } else {
-                pc->is_ref = 1;
-                pc->has_ref = !pc->gop_start;
-                if (e->do_scd) {
-                    const int al = (int)b->luma[pc->cur_slot] / (b->small_w * b->small_h);
-                    if (abs(e->prev_avg_luma - al) > e->scene_change_delta) { pc->has_ref = 0; pc->forced_intra = 1; }
-                    e->prev_avg_luma = al;
-                }
-            }
-            for (k = s * R; t == 0 && k < s * R + R; k++) {     /* (every rung of the source) */
-                if (pc->has_ref && b->border_skipped[k]) {
-                    /* the batch before promised a GOP start here (border_hint) and the caller changed the frame numbering
-                     * in between (dsv1_batch_set_fnum): give the reference its whole border after all */
-                    if ((rc = dsvg_extend_recon(b->ctx, b->chains ? b->carry_cur : k + N * b->rpar[k]))) return rc;
-                }
-                b->border_skipped[k] = 0;
-                if (b->recon_dropped[k]) {
-                    /* ... and a reconstruction it dropped: coded once more below, kept this time */
-                    if (pc->has_ref) b->out_slots[nremedy++] = k;
-                    b->recon_dropped[k] = 0;
-                }
-            }
-            if (pc->has_ref) {
-                b->slots_cur[npairs] = pc->cur_slot;
-                b->slots_ref[npairs] = pc->ref_slot;
-                b->pair_pic[npairs] = s * R * F + t;
-                npairs++;
-            }
-        }
-        for (r = 1; r < R; r++) {                           /* the other rungs follow the lead's decision state */
-            DSV_ENCODER *o = &b->enc[s * R + r];
-            o->next_fnum = e->next_fnum; o->prev_gop = e->prev_gop; o->force_metadata = e->force_metadata;
-            o->prev_avg_luma = e->prev_avg_luma; o->pyramid_levels = e->pyramid_levels;
-        }
+        const DSV_ENCODER *e = &b->enc[s * R];
+        dsv1_submit_src *c = &b->dec[s];
+        c->next_fnum = e->next_fnum; c->prev_gop = e->prev_gop; c->gop = (int)e->gop; c->do_scd = e->do_scd;
+        c->prev_avg_luma = e->prev_avg_luma; c->scene_change_delta = e->scene_change_delta;
+        for (c->force_metadata = 0, r = 0; r < R; r++) c->force_metadata |= b->enc[s * R + r].force_metadata;     /* (forced on any rung: a GOP start on all) */
     }
-    if (nremedy && (rc = remedy_dropped(b, nremedy, par))) return rc;
+    pp = dsv1_sp_plan_pictures(b->dec, b->dec_new, S, R, F, nf, b->rows, b->gcount, par, b->small_w * b->small_h, b->chains, b->carry_cur, b->luma,
+                               b->st, b->st_new, pics, sizeof(pic_t), b->slots_cur, b->slots_ref, b->pair_pic, b->ext, b->out_slots);
+    if (pp.nrem) {
+        if (b->nf_prev < 1) return DSVG_ERR_ARG;
+        dsv1_sp_plan_remedy(b->out_slots, pp.nrem, N, F, b->nf_prev, par, b->pics + (size_t)(par ^ 1) * N * F, sizeof(pic_t), b->st_new, b->sjobs);
+    }
+    commit_sources(b, pp.nrem);
+    /* the batch before promised a GOP start (border_hint) or dropped a reconstruction, and the caller changed the frame numbering in
+     * between (dsv1_batch_set_fnum): the reference gets its whole border after all / is coded once more, kept this time */
+    for (k = 0; k < pp.next; k++)
+        if ((rc = dsvg_extend_recon(b->ctx, b->ext[k]))) return rc;
+    if (pp.nrem && (rc = remedy_dropped(b, pp.nrem, par))) return rc;
     HP_MARK(HP_DECIDE);
-    /* 3. motion estimation for every inter candidate of the batch in one go */
-    if (npairs) {
-        if ((rc = dsvg_analyse(b->ctx, npairs, b->slots_cur, b->slots_ref, (dsvg_mv *)b->mv_tmp))) return rc;
-        for (k = 0; k < npairs; k++)
+    /* 4. motion estimation for every inter candidate of the batch in one go */
+    if (pp.npairs) {
+        if ((rc = dsvg_analyse(b->ctx, pp.npairs, b->slots_cur, b->slots_ref, (dsvg_mv *)b->mv_tmp))) return rc;
+        for (k = 0; k < pp.npairs; k++)
             memcpy(pics[b->pair_pic[k]].mvs, b->mv_tmp + (size_t)k * nblk, (size_t)nblk * sizeof(DSV_MV));
     }
     HP_MARK(HP_ANALYSE);
-    /* 4. per source, in coding order: forced intra, stability + motion side info -> packet prefix */
-    {
-        side_ctx sc_;
-        sc_.b = b; sc_.pics = pics;
-        dsv1_par_for(S, side_stream, &sc_);
-        for (s = 0; s < S; s++)
-            for (r = 1; r < R; r++) b->enc[s * R + r].refresh_ctr = b->enc[s * R].refresh_ctr;
-    }
+    /* 5. per source, in coding order: forced intra, stability flags, the vectors' reach */
+    sc_.b = b; sc_.pics = pics; sc_.rc = DSVG_OK; sc_.nf = nf;
+    dsv1_par_for(S, side_stream, &sc_);
+    for (s = 0; s < S; s++)
+        for (r = 1; r < R; r++) b->enc[s * R + r].refresh_ctr = b->enc[s * R].refresh_ctr;
     HP_MARK(HP_SIDEINFO);
-    /* 5. residual coding, frame step by frame step across all streams */
-    {
-        const int abr = e0->rc_mode != DSV_RATE_CONTROL_CRF;
-        const int devrc = abr && b->abr_dev;                    /* rate control on the device: enqueued like a CRF call */
-        const int serial = abr && !devrc;
-        side_ctx sc_;
-        sc_.b = b; sc_.pics = pics; sc_.rc = DSVG_OK; sc_.nf = nf;
-        if (serial && !abr_out) return DSVG_ERR_ARG;
-        if (abr && b->chains) return DSVG_ERR_ARG;
-        if (abr) {                                              /* ABR: the length of every packet prefix feeds the rate control */
-            /* the pictures are the parallel items (a picture's prefix depends on nothing but its own side information): the GPU
-             * waits for this -- with two 4K streams of 30 frames a loop over streams took 5 ms on two threads */
-            if (S == 1 || nf == F) dsv1_par_for(S * nf, prefix_picture, &sc_);
-            else dsv1_par_for(S, prefix_stream, &sc_);
-            if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
-        }
-        /* every rung of a source codes the lead's picture: its decisions, slots and tables (the pointers: one copy of each table,
-         * and one device copy -- dsvg_code_batch keys on them); the out slot is the rung's own */
-        for (s = 0; s < S && R > 1; s++)
-            for (r = 1; r < R; r++)
-                for (t = 0; t < nf; t++) {
-                    pic_t *pc = &pics[(s * R + r) * F + t];
-                    *pc = pics[s * R * F + t];
-                    pc->out_slot += r;
-                }
-        if ((b->q[DSVG_Q_XSSE].on || b->q[DSVG_Q_XSSIM].on) && !b->chains) {
-            /* the reference frame of every picture of the call: stream s (source s / R), frame t -> frame (s / R) * F + t */
-            int *fr = (int *)malloc(sizeof(int) * (size_t)N * nf), *os = (int *)malloc(sizeof(int) * (size_t)N * nf);
-            if (!fr || !os) { free(fr); free(os); return DSVG_ERR_NOMEM; }
-            for (s = 0; s < N; s++)
-                for (t = 0; t < nf; t++) { os[s * nf + t] = pics[s * F + t].out_slot; fr[s * nf + t] = (s / R) * F + t; }
-            rc = b->xres_clip ? dsvg_ctx_xres_refs(b->ctx, b->xres_clip, N * nf, os, fr) : DSVG_ERR_ARG;
-            free(fr); free(os);
-            b->xres_clip = NULL;
-            if (rc) { dsv1_log(1, "source-resolution figures on, but no reference clip named for this submit"); return rc; }
-        }
+    if (abr) {                                              /* ABR: the length of every packet prefix feeds the rate control */
+        /* the pictures are the parallel items (a picture's prefix depends on nothing but its own side information): the GPU
+         * waits for this -- with two 4K streams of 30 frames a loop over streams took 5 ms on two threads */
+        if (S == 1 || nf == F) dsv1_par_for(S * nf, prefix_picture, &sc_);
+        else dsv1_par_for(S, prefix_stream, &sc_);
+        if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
+    }
+    /* every rung of a source codes the lead's picture: its decisions, slots and tables (the pointers: one copy of each table,
+     * and one device copy -- dsvg_code_batch keys on them); the out slot is the rung's own */
+    for (s = 0; s < S && R > 1; s++)
+        for (r = 1; r < R; r++)
+            for (t = 0; t < nf; t++) {
+                pic_t *pc = &pics[(s * R + r) * F + t];
+                *pc = pics[s * R * F + t];
+                pc->d.out_slot += r;
+            }
+    if ((b->q[DSVG_Q_XSSE].on || b->q[DSVG_Q_XSSIM].on) && !b->chains) {
+        /* the reference frame of every picture of the call: stream s (source s / R), frame t -> frame (s / R) * F + t */
+        int *fr = (int *)malloc(sizeof(int) * (size_t)N * nf), *os = (int *)malloc(sizeof(int) * (size_t)N * nf);
+        if (!fr || !os) { free(fr); free(os); return DSVG_ERR_NOMEM; }
+        for (s = 0; s < N; s++)
+            for (t = 0; t < nf; t++) { os[s * nf + t] = pics[s * F + t].d.out_slot; fr[s * nf + t] = (s / R) * F + t; }
+        rc = dsvg_ctx_xres_refs(b->ctx, b->xres_clip, N * nf, os, fr);        /* (submit_check: a clip was named) */
+        free(fr); free(os);
+        b->xres_clip = NULL;
+        if (rc) { dsv1_log(1, "source-resolution figures on, but no reference clip named for this submit"); return rc; }
+    }
+    /* 6.-8. residual coding, frame step by frame step across all streams: the whole call at once -- but for the serial ABR path,
+     * one step at a time: the quantiser of step t + 1 needs the packet of step t */
+    for (t0 = 0; t0 < nf; t0 = t1) {
+        int ncalls = 1, dropped = 0, carry[2];
+        t1 = serial ? t0 + 1 : nf;
+        /* 6. reconstruction slots, dead reconstructions, border hints (chain mode: chains, rounds, calls), 7. the rate-control hand-over
+         * per stream in coding order, and the device jobs from both.  Batch mode: ONE pass over the step's jobs.  Then COMMIT 2 */
+        memcpy(b->st_new, b->st, (size_t)N * sizeof(*b->st));
+        carry[0] = b->carry_pair; carry[1] = b->carry_cur;
         if (b->chains) {
-            if ((rc = code_chains(b, pics, nf, par))) return rc;
-        } else
-        for (t = 0; t < nf; t++) {
-            for (s = 0; s < N; s++) {                           /* (s: an output stream from here on) */
-                pic_t *pc = &pics[s * F + t];
-                dsvg_pic_job *j = &b->jobs[(serial ? 0 : t * N) + s];
-                pc->quant = devrc ? 0 : pick_quant(&b->enc[s], pc->isP, pc->forced_intra);
-                if (devrc) { dsvg_rc_job *q = &b->rcjobs[t * N + s]; q->rc_slot = s; q->prefix_len = pc->prefix_len; q->forced_intra = pc->forced_intra; }
-                j->src_slot = pc->cur_slot;
-                /* two reconstruction slots per stream, used alternately: a P picture's prediction is written straight
-                 * into the slot its reconstruction will live in (the reference sits in the other one), so the inverse
-                 * transform only touches the tiles that carry a residual (dsvg_code_batch) */
-                j->ref_recon_slot = pc->isP ? s + N * b->rpar[s] : -1;
-                {
-                    /* who predicts from this picture?  The stream's next one -- when it has a reference at all.  Nobody: no reconstruction
-                     * (struct dsv1_batch, recon_dropped; the reference builds it and never looks at it, dsv_encoder.c:665-700) */
-                    int dead = 0;
-                    if (pc->is_ref && !serial && !b->keep_all) {
-                        const DSV_ENCODER *e = &b->enc[s];
-                        if (t + 1 < nf) dead = !pics[s * F + t + 1].has_ref;
-                        else dead = !abr && (e->force_metadata || (DSV_FNUM)(e->prev_gop + (DSV_FNUM)e->gop) <= e->next_fnum);
-                    }
-                    if (t + 1 == nf) b->recon_dropped[s] = (unsigned char)dead;
-                    b->n_dropped += dead;
-                    if (pc->is_ref && !dead) {
-                        b->rpar[s] ^= 1;
-                        b->has_recon[s] = 1;
-                        j->recon_slot = s + N * b->rpar[s];
-                    } else j->recon_slot = -1;
+            ncalls = dsv1_sp_plan_chains(pics, sizeof(pic_t), nf, b->chains, b->keep_all, par * F, carry, b->st_new, b->sjobs, b->calls, b->ch, &dropped);
+            if (ncalls < 0) { dsv1_log(1, "a P picture without a reference picture on the device"); return DSVG_ERR_ARG; }     /* (needs the motion search: not submit_check's) */
+            for (t = 0; t < nf; t++) pics[t].quant = pick_quant(&b->enc[0], pics[t].d.isP, pics[t].d.forced_intra);
+            jobs_from_plan(pics, b->sjobs, nf, b->jobs);
+        } else {
+            for (t = t0; t < t1; t++)
+                for (s = 0; s < N; s++) {                       /* (s: an output stream from here on) */
+                    pic_t *pc = &pics[s * F + t];
+                    dsv1_submit_job sj;
+                    dropped += dsv1_sp_plan_step_job(pics, sizeof(pic_t), N, F, nf, t, s, abr, serial, b->keep_all, &b->st_new[s], &sj);
+                    pc->quant = devrc ? 0 : pick_quant(&b->enc[s], pc->d.isP, pc->d.forced_intra);
+                    if (devrc) { dsvg_rc_job *q = &b->rcjobs[t * N + s]; q->rc_slot = s; q->prefix_len = pc->prefix_len; q->forced_intra = pc->d.forced_intra; }
+                    job_from_plan(&b->jobs[(t - t0) * N + s], pc, &sj);
                 }
-                j->quant = pc->quant;
-                j->mvs = (const dsvg_mv *)pc->mvs;
-                j->stable_blocks = pc->stable;
-                j->out_slot = pc->out_slot;
-                j->no_intra_blocks = pc->isP && pc->n_intra == 0;
-                j->has_reach = pc->isP;
-                memcpy(j->mv_reach, pc->reach, sizeof pc->reach);
-                /* who predicts from this reconstruction: the next picture of the stream -- in this call, or (last frame of
-                 * the batch) the first of the next one, which is known not to when it starts a GOP (dsv_encoder.c:702-708) */
-                j->border_hint = !serial && (t + 1 < nf || b->enc[s].force_metadata ||
-                                             (DSV_FNUM)(b->enc[s].prev_gop + (DSV_FNUM)b->enc[s].gop) <= b->enc[s].next_fnum);
-                if (t + 1 == nf) b->border_skipped[s] = (unsigned char)(j->border_hint && j->recon_slot >= 0);
-            }
-            if (serial) {
-                if ((rc = dsvg_code_pictures(b->ctx, N, b->jobs))) return rc;
-                for (s = 0; s < N; s++) b->out_slots[s] = pics[s * F + t].out_slot;
-                if ((rc = dsvg_fetch_pictures(b->ctx, N, b->out_slots, b->outs))) return rc;
-                for (s = 0; s < N; s++)
-                    if ((rc = assemble(b, s, &pics[s * F + t], &b->outs[s], &abr_out[s], &b->sc0, NULL))) return rc;
-            }
+            b->calls[0].nsteps = t1 - t0; b->calls[0].njobs = N; b->calls[0].first = 0;
         }
+        memcpy(b->st, b->st_new, (size_t)N * sizeof(*b->st));
+        b->carry_pair = carry[0]; b->carry_cur = carry[1];
+        b->n_dropped += dropped;
         if (devrc) {
             if (!b->rc_seeded) {                                /* the device takes over the streams' rate-control state */
                 for (s = 0; s < N; s++) rc_load(&b->rc_dev[s], &b->enc[s]);
@@ -1177,35 +1038,102 @@ static int batch_submit_impl(dsv1_batch *b, const void *yuv, int yuv_on_device, 
                 if (s0 >= 0 && (rc = dsvg_rc_set_params(b->ctx, s0, s1 - s0 + 1, b->rc_dev + s0))) return rc;
             }
             memcpy(b->rc_par + (size_t)par * N, b->rc_dev, (size_t)N * sizeof(dsvg_rc_state));     /* what this batch's replay uses */
-            if ((rc = dsvg_code_batch_rc(b->ctx, nf, N, b->jobs, b->rcjobs))) return rc;
-        } else
-        if (!serial && !b->chains && (rc = dsvg_code_batch(b->ctx, nf, N, b->jobs))) return rc;   /* whole batch, one upload */
-        HP_MARK(HP_ENQUEUE);
-        /* the bits of the packet prefixes: nobody waits for them before the packets are assembled, and the GPU is busy now */
-#ifdef AB_SYNC_PREFIX                                                 /* (A/B: tools/ab/variant.sh syncprefix host_dsv1_enc "" -DAB_SYNC_PREFIX) */
-        if (b->chains) dsv1_par_for(nf, prefix_picture, &sc_);
-        else if (!abr) dsv1_par_for(S, prefix_stream, &sc_);
-        if (0)
-#endif
-        if (!abr) {
-            /* round 6: in the BACKGROUND -- idle workers write them while this thread waits for the GPU in the next calls (the fetch of the batch
-             * before, the load and motion search of the batch after); dsv1_batch_collect of THIS batch joins.  Synchronous, the loop sat between the
-             * coding enqueue and the fetch on every step: 1.9 ms with 12 workers, 11.7 ms of a 43 ms step on 4 cores (profiles/r06_cpu_starved.txt) */
-            b->bg_sc[par] = sc_;
-            b->bg_on[par] = 1;
-            if (b->chains) dsv1_par_bg_begin(nf, prefix_picture, &b->bg_sc[par]);      /* (one stream: the pictures are the independent items) */
-            else dsv1_par_bg_begin(S, prefix_stream, &b->bg_sc[par]);      /* (per source; one loop at a time: this joins the loop of the batch before, if it still runs) */
-            b->bg_on[par ^ 1] = 0;
         }
-        if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
-        b->pending[par] = serial ? 2 : 1;               /* 2 = already assembled */
-        b->nf_pending[par] = nf;
+        /* 8. enqueue from the plan */
+        if (serial) {
+            if ((rc = dsvg_code_pictures(b->ctx, N, b->jobs))) return rc;
+            for (s = 0; s < N; s++) b->out_slots[s] = pics[s * F + t0].d.out_slot;
+            if ((rc = dsvg_fetch_pictures(b->ctx, N, b->out_slots, b->outs))) return rc;
+            for (s = 0; s < N; s++)
+                if ((rc = assemble(b, s, &pics[s * F + t0], &b->outs[s], &abr_out[s], &b->sc0, NULL))) return rc;
+        } else
+        if ((rc = devrc ? dsvg_code_batch_rc(b->ctx, nf, N, b->jobs, b->rcjobs) : code_calls(b, ncalls))) return rc;
     }
+    HP_MARK(HP_ENQUEUE);
+    /* 9. the bits of the packet prefixes: nobody waits for them before the packets are assembled, and the GPU is busy now */
+#ifdef AB_SYNC_PREFIX                                                 /* (A/B: tools/ab/variant.sh syncprefix host_dsv1_enc "" -DAB_SYNC_PREFIX) */
+    if (b->chains) dsv1_par_for(nf, prefix_picture, &sc_);
+    else if (!abr) dsv1_par_for(S, prefix_stream, &sc_);
+    if (0)
+#endif
+    if (!abr) {
+        /* round 6: in the BACKGROUND -- idle workers write them while this thread waits for the GPU in the next calls (the fetch of the batch
+         * before, the load and motion search of the batch after); dsv1_batch_collect of THIS batch joins.  Synchronous, the loop sat between the
+         * coding enqueue and the fetch on every step: 1.9 ms with 12 workers, 11.7 ms of a 43 ms step on 4 cores (profiles/r06_cpu_starved.txt) */
+        b->bg_sc[par] = sc_;
+        b->bg_on[par] = 1;
+        if (b->chains) dsv1_par_bg_begin(nf, prefix_picture, &b->bg_sc[par]);      /* (one stream: the pictures are the independent items) */
+        else dsv1_par_bg_begin(S, prefix_stream, &b->bg_sc[par]);      /* (per source; one loop at a time: this joins the loop of the batch before, if it still runs) */
+        b->bg_on[par ^ 1] = 0;
+    }
+    if (sc_.rc) { dsv1_log(1, "out of memory while writing the packet prefixes"); return sc_.rc; }
+    b->pending[par] = serial ? 2 : 1;               /* 2 = already assembled */
+    b->nf_pending[par] = nf;
     HP_MARK(HP_PREFIX);
     hp_batches++;
     b->gcount += (unsigned)nf;
     b->parity ^= 1;
     b->nf_prev = nf;
+    return DSVG_OK;
+}
+
+/* every submit: the check first, then the passes in front of the encoder (convert: the two public calls), then the call itself */
+static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device);
+static int submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *abr_out, int nf, int convert, int inplace_ok)
+{
+    int rc;
+    if ((rc = submit_check(b, yuv, yuv_on_device, abr_out, nf))) return rc;
+    if (convert && dsv1_srcchain_any(&b->src)) {
+        const void *in = yuv;
+        if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
+        if (yuv != in) { yuv_on_device = 1; inplace_ok = 1; }
+    }
+    return batch_submit_impl(b, yuv, yuv_on_device != 0, abr_out, nf, inplace_ok);
+}
+
+/* the same decisions without a device (include/dsv1_api.h, Submit plan): steps 3, 5 (n_intra in place of the motion fields) and 6 of
+ * batch_submit_impl on the caller's arrays */
+int dsv1_submit_plan(dsv1_submit_query *q, dsv1_submit_src *src, dsv1_submit_stream *st, const unsigned *luma, const int *n_intra,
+                     const dsv1_submit_pic *prev, const dsv1_submit_tables *tb)
+{
+    const size_t ps = sizeof(dsv1_submit_pic);
+    dsv1_sp_pictures pp;
+    dsv1_submit_pic *pics;
+    int S, R, F, N, nf, s, r, t, t0, t1;
+    if (!q || !src || !st || !luma || !n_intra || !tb || !tb->pics || !tb->pair_cur || !tb->pair_ref || !tb->pair_pic || !tb->ext || !tb->remedy_streams ||
+        !tb->remedy || !tb->jobs || !tb->calls || !tb->scratch) return DSVG_ERR_ARG;
+    S = q->S; R = q->R; F = q->F; N = S * R; nf = q->nf > 0 ? q->nf : F; pics = tb->pics;
+    if (S < 1 || R < 1 || F < 1 || q->chains < 0 || (q->chains && N != 1) || q->npix_small < 1 || q->nblk < 1) return DSVG_ERR_ARG;
+    if (nf > F || (nf < F && N != 1) || (q->serial && !q->abr) || (q->abr && q->chains)) return DSVG_ERR_ARG;
+    memset(pics, 0, ps * (size_t)N * F);
+    pp = dsv1_sp_plan_pictures(src, src, S, R, F, nf, 2 * F + 1, q->gcount, q->par, q->npix_small, q->chains, q->carry[1], luma, st, st, pics, ps,
+                               tb->pair_cur, tb->pair_ref, tb->pair_pic, tb->ext, tb->remedy_streams);
+    q->npairs = pp.npairs; q->next = pp.next; q->nremedy = pp.nrem;
+    if (pp.nrem) {
+        if (!prev || q->nf_prev < 1) return DSVG_ERR_ARG;
+        dsv1_sp_plan_remedy(tb->remedy_streams, pp.nrem, N, F, q->nf_prev, q->par, prev, ps, st, tb->remedy);
+    }
+    for (s = 0; s < S; s++)
+        for (t = 0; t < nf; t++) {
+            dsv1_sp_intra_decide(&pics[s * R * F + t], n_intra[s * R * F + t], q->nblk, q->intra_pct_thresh);
+            for (r = 1; r < R; r++) {
+                pics[(s * R + r) * F + t] = pics[s * R * F + t];
+                pics[(s * R + r) * F + t].out_slot += r;
+            }
+        }
+    q->ncalls = 0; q->dropped = 0; q->njobs = nf * N;
+    for (t0 = 0; t0 < nf; t0 = t1) {
+        int dropped = 0, n = 1;
+        t1 = q->serial ? t0 + 1 : nf;
+        if (q->chains) n = dsv1_sp_plan_chains(pics, ps, nf, q->chains, q->keep_all, q->par * F, q->carry, st, tb->jobs, tb->calls, tb->scratch, &dropped);
+        else {
+            dsv1_submit_call *c = &tb->calls[q->ncalls];
+            dropped = dsv1_sp_plan_steps(pics, ps, N, F, nf, t0, t1, q->abr, q->serial, q->keep_all, st, tb->jobs + t0 * N);
+            c->nsteps = t1 - t0; c->njobs = N; c->first = t0 * N;
+        }
+        if (n < 0) { dsv1_log(1, "a P picture without a reference picture on the device"); return DSVG_ERR_ARG; }
+        q->ncalls += n; q->dropped += dropped;
+    }
     return DSVG_OK;
 }
 
@@ -1407,9 +1335,6 @@ static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 {
     const void *in = *yuv;
     int rc;
-    if (!*yuv) return DSVG_ERR_ARG;
-    if (yuv_on_device < 0 || yuv_on_device > DSV1_CLIP_HELD) return DSVG_ERR_ARG;
-    if (b->pending[b->parity]) { dsv1_log(1, "batch submitted twice without collect"); return DSVG_ERR_ARG; }
     if ((rc = dsv1_srcchain_run(&b->src, b->parity, *yuv, yuv_on_device, yuv))) return rc;
     if (*yuv == in) return DSVG_OK;                     /* (overlays alone and none active in this call: nothing was enqueued, the clip is the caller's still) */
     if ((rc = dsvg_lane_order(b->src.lane, b->ctx))) return rc;
@@ -1420,16 +1345,10 @@ static int batch_convert(dsv1_batch *b, const void **yuv, int yuv_on_device)
 
 int dsv1_batch_submit(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF *out)
 {
-    if (b && dsv1_srcchain_any(&b->src)) {
-        const void *in = yuv;
-        int rc;
-        if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
-        if (yuv != in) return batch_submit_impl(b, yuv, 1, out, 0, 1);
-    }
     /* a device clip's chroma stays where it is (the coding kernels read it until the batch is collected) only when the caller
      * said it holds the clip that long: DSV1_CLIP_HELD.  A plain device clip is copied whole -- the call is done with it when
      * it returns, as it was before round 3 (advisor, round 3) */
-    return batch_submit_impl(b, yuv, yuv_on_device != 0, out, 0, yuv_on_device == DSV1_CLIP_HELD);
+    return submit(b, yuv, yuv_on_device, out, 0, 1, yuv_on_device == DSV1_CLIP_HELD);
 }
 
 /* Collect the OLDEST submitted batch: one gathered device-to-host copy, then packet assembly in
@@ -1460,7 +1379,7 @@ int dsv1_batch_collect(dsv1_batch *b, DSV_BUF *out)
         return rc_;
     }
     /* in submitted frame order ([stream][frame]: pics[s * F + t]); a short batch (nf < F) has a single stream: its pictures are the first nf entries */
-    for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].out_slot;
+    for (k = 0; k < S * nf; k++) b->out_slots[k] = pics[k].d.out_slot;
     if (b->pending[par] == 1) {
         HP_BEGIN();
         {
@@ -1489,12 +1408,7 @@ int dsv1_batch_encode(dsv1_batch *b, const void *yuv, int yuv_on_device, DSV_BUF
     int rc;
     if (!b || !out) return DSVG_ERR_ARG;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_encode with batches in flight"); return DSVG_ERR_ARG; }
-    if (dsv1_srcchain_any(&b->src)) {
-        const void *in = yuv;
-        if ((rc = batch_convert(b, &yuv, yuv_on_device))) return rc;
-        if (yuv != in) yuv_on_device = 1;
-    }
-    if ((rc = batch_submit_impl(b, yuv, yuv_on_device, out, 0, 1))) return rc;
+    if ((rc = submit(b, yuv, yuv_on_device, out, 0, 1, 1))) return rc;
     return dsv1_batch_collect(b, out);
 }
 
@@ -1503,7 +1417,7 @@ static int batch_encode_n(dsv1_batch *b, const void *yuv, int nf, DSV_BUF *out)
 {
     int rc;
     if (b->pending[0] || b->pending[1]) { dsv1_log(1, "batch encode with batches in flight"); return DSVG_ERR_ARG; }
-    if ((rc = batch_submit_impl(b, yuv, 0, out, nf, 1))) return rc;
+    if ((rc = submit(b, yuv, 0, out, nf, 0, 1))) return rc;
     return dsv1_batch_collect(b, out);
 }
 
@@ -1698,7 +1612,7 @@ static int sess_submit(enc_sess *ss)
 {
     int rc;
     /* the frames are on the device already (or on their way: the load waits for the last part on the device) */
-    if ((rc = batch_submit_impl(ss->b, ss->dev, 1, NULL, ss->fill, 0))) return rc;      /* (the ingest buffer is reused two batches on: chroma is copied) */
+    if ((rc = submit(ss->b, ss->dev, 1, NULL, ss->fill, 0, 0))) return rc;      /* (the ingest buffer is reused two batches on: chroma is copied) */
     ss->dev = NULL;
     ss->inflight++;
     ss->cur ^= 1;
@@ -1746,7 +1660,7 @@ static void sess_push_partial(enc_sess *ss)
         DSV_BUF acc = {NULL, 0};
         int rc;
         if (ss->gathered && ss->dev) {
-            rc = batch_submit_impl(ss->b, ss->dev, 1, &acc, ss->fill, 0);
+            rc = submit(ss->b, ss->dev, 1, &acc, ss->fill, 0, 0);
             ss->dev = NULL;
             if (!rc) rc = dsv1_batch_collect(ss->b, &acc);
         } else rc = batch_encode_n(ss->b, ss->pin[0], ss->fill, &acc);
@@ -1952,7 +1866,7 @@ int dsv_enc(DSV_ENCODER *enc, DSV_FRAME *frame, DSV_BUF *bufs)
         if (ss->fill < ss->F) return sess_ret(enc, ss, bufs);     /* (ABR: the group is not complete yet) */
         ss->fill = 0;
         if (ss->gathered) {                                     /* the group's frames are on the device already (or on their way) */
-            rc = batch_submit_impl(ss->b, ss->dev, 1, &acc, ss->F, 0);
+            rc = submit(ss->b, ss->dev, 1, &acc, ss->F, 0, 0);
             ss->dev = NULL;
             if (!rc) rc = dsv1_batch_collect(ss->b, &acc);
         } else rc = dsv1_batch_encode(ss->b, ss->pin[0], 0, &acc);

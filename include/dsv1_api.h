@@ -280,6 +280,59 @@ void *dsv1_batch_ctx(dsv1_batch *b);          /* the dsvg_ctx* (profiling hooks)
  * for dsvg_download_recon / dsvg_download_recon_raw; -1 if the stream has none yet */
 int   dsv1_batch_recon_slot(const dsv1_batch *b, int stream);
 
+/* ---- Submit plan (tests; csrc/host/dsv1_submit_plan.h; restated in tests/submit_plan.py) ----
+ * What a submit decides, as plain tables: the session plans its call with the same pure functions, commits the state they return and
+ * enqueues from their tables.  A call of nf frames of S sources x R rungs (output stream k = s * R + r), F frames per call at most;
+ * the pictures lie [stream][F].
+ *   dsv1_submit_src: a source's decision state (the encoder's fields; force_metadata OR-ed over the rungs).
+ *   dsv1_submit_pic: a picture's decisions.  has_ref after the GOP / scene-change rules is a motion-search candidate; isP is final
+ *     after the forced-intra rule (n_intra * 100 / nblk > intra_pct_thresh).  reach: min / max of the inter blocks' mv.x >> 1,
+ *     mv.y >> 1, each taken with 0.  cur_slot / ref_slot: source slots (a ring of 2F + 1 rows of S); out_slot: where the packet waits.
+ *   dsv1_submit_stream: an output stream's state.  rpar: which slot of its pair {k, k + N} holds the current reference; has_recon;
+ *     border_skipped / recon_dropped: the call's last picture was coded with a short border / without a reconstruction because
+ *     next_gop (the stream's next frame number starts a GOP) held.
+ *   dsv1_submit_job: one device job in enqueue order: pic = index of its picture; remedy = the whole border, no reach.
+ *   dsv1_submit_call: nsteps frame steps of njobs jobs each, jobs[first ..]. */
+typedef struct { uint32_t next_fnum, prev_gop; int gop, force_metadata, do_scd, prev_avg_luma, scene_change_delta; } dsv1_submit_src;
+typedef struct {
+    uint32_t fnum;
+    int gop_start, is_ref, has_ref, forced_intra, isP, n_intra;
+    short reach[4];
+    int cur_slot, ref_slot, out_slot;
+} dsv1_submit_pic;
+typedef struct { unsigned char rpar, has_recon, border_skipped, recon_dropped, next_gop; } dsv1_submit_stream;
+typedef struct { int pic, ref_recon_slot, recon_slot, out_slot, border_hint, remedy; } dsv1_submit_job;
+typedef struct { int nsteps, njobs, first; } dsv1_submit_call;
+typedef struct {
+    int S, R, F, nf;            /* nf < F needs S * R == 1 */
+    int chains;                 /* 0: batch mode; else chain mode (S = R = 1), this many chains side by side */
+    unsigned gcount;            /* frames per stream submitted before this call */
+    int par;                    /* the half of the out slots this call uses: calls alternate 0, 1 */
+    int npix_small;             /* pixels of the smallest pyramid level: luma sum / npix_small is the mean the scene-cut rule compares */
+    int nblk, intra_pct_thresh;
+    int abr, serial, keep_all;  /* ABR streams; their frame-by-frame host path; every reference picture reconstructed */
+    int nf_prev;                /* frames of the call before (a remedy needs its pictures) */
+    int carry[2];               /* chain mode, in and out: the pair / slot the open chain's newest reconstruction lives in (-1: none) */
+    int npairs, next, nremedy, njobs, ncalls, dropped;      /* out: how much of each table was written */
+} dsv1_submit_query;
+/* the tables a plan writes, all the caller's */
+typedef struct {
+    dsv1_submit_pic *pics;              /* [S * R * F] */
+    int *pair_cur, *pair_ref, *pair_pic;/* [S * F] each: the motion-search pairs (source slots, picture) */
+    int *ext;                           /* [S * R] reconstruction slots to extend after all */
+    int *remedy_streams;                /* [S * R] streams whose dropped reconstruction is needed after all ... */
+    dsv1_submit_job *remedy;            /* [S * R] ... and the remedy call's jobs (pic: index into the call before's pictures) */
+    dsv1_submit_job *jobs;              /* [S * R * F] in enqueue order */
+    dsv1_submit_call *calls;            /* [F] (serial: one call per frame step) */
+    int *scratch;                       /* [4 * (F + 1)] */
+} dsv1_submit_tables;
+/* One submit on plain arrays, no device.  In and out: q, src[S], st[S * R].  In: luma[(2F + 1) * S] raw sums by source slot (read with
+ * do_scd), n_intra[S * R * F] for the lead rungs' motion-search candidates (in place of a motion search), prev[S * R * F] the pictures
+ * of the call before (NULL: none).  Out: *tb.  DSVG_ERR_ARG for arguments a submit refuses, and for chain mode's P picture without a
+ * reference picture. */
+int   dsv1_submit_plan(dsv1_submit_query *q, dsv1_submit_src *src, dsv1_submit_stream *st, const unsigned *luma, const int *n_intra,
+                       const dsv1_submit_pic *prev, const dsv1_submit_tables *tb);
+
 /* ---- extension: the resampler of resolution ladders (csrc/k_scale.hip; stated in numpy in tests/_scale.py) ----
  * Downscale or identity: on each axis of each plane 1 <= S / D <= 8 (S source length, D destination length); every plane is scaled
  * on its own, from the source's chroma dims to the destination's (rshift_up); the format is kept.  Centre-aligned sample grids;
