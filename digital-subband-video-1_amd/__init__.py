@@ -642,6 +642,73 @@ def load_plan(w, h, fmt, pyramid_levels=0, with_pyramid=1, src_mod16=0, pitch_mo
     return d
 
 
+CTX_MEM_IDS = 84                                           # DSVG_CTX_MEM_IDS
+MEM_KINDS = ("device", "pinned", "slab")
+
+
+class CtxMemRow(_C.Structure):
+    _fields_ = [("id", _C.c_int), ("kind", _C.c_int), ("zeroed", _C.c_int), ("count", _C.c_size_t), ("size", _C.c_size_t), ("pad", _C.c_size_t),
+                ("bytes", _C.c_size_t)]
+
+
+def _mem_lib():
+    L = lib()
+    geo = [_C.c_int] * 10
+    L.dsvg_ctx_mem_name.restype = _C.c_char_p
+    L.dsvg_ctx_mem_name.argtypes = [_C.c_int]
+    L.dsvg_ctx_mem_plan.argtypes = geo + [_C.POINTER(CtxMemRow), _C.c_int, _C.POINTER(_C.c_size_t)]
+    L.dsvg_ctx_mem_grow.restype = _C.c_size_t
+    L.dsvg_ctx_mem_grow.argtypes = geo + [_C.c_int, _C.c_size_t, _C.c_size_t, _C.c_int]
+    L.dsvg_ctx_mem_live.argtypes = [_C.c_void_p, _C.POINTER(_C.c_size_t), _C.c_int]
+    L.dsvg_mem_outstanding.restype = None
+    L.dsvg_mem_outstanding.argtypes = [_C.POINTER(_C.c_size_t)]
+    L.dsvg_debug_fail_alloc_at.restype = None
+    L.dsvg_debug_fail_alloc_at.argtypes = [_C.c_int]
+    return L
+
+
+def ctx_mem_names():
+    """the short name of every buffer id of a context, creation-time and lazy, by id"""
+    L = _mem_lib()
+    return [L.dsvg_ctx_mem_name(i).decode() for i in range(CTX_MEM_IDS)]
+
+
+def ctx_mem_plan(w, h, fmt, pyramid_levels=0, n_src_slots=1, n_recon_slots=1, max_jobs=1, out_slots=1, blk_w=0, blk_h=0):
+    """the buffers dsvg_ctx_create_blk allocates for these arguments, in the order it allocates them: ([row dicts: id, name, kind, zeroed,
+    count, size, pad, bytes], {"device": bytes, "pinned": bytes}); needs no device"""
+    L = _mem_lib()
+    rows, tot = (CtxMemRow * CTX_MEM_IDS)(), (_C.c_size_t * 2)()
+    n = L.dsvg_ctx_mem_plan(w, h, fmt, pyramid_levels, n_src_slots, n_recon_slots, max_jobs, out_slots, blk_w, blk_h, rows, CTX_MEM_IDS, tot)
+    if n < 0:
+        _chk(n, "dsvg_ctx_mem_plan")
+    names = ctx_mem_names()
+    return ([{"id": r.id, "name": names[r.id], "kind": MEM_KINDS[r.kind], "zeroed": bool(r.zeroed), "count": r.count, "size": r.size, "pad": r.pad,
+              "bytes": r.bytes} for r in rows[:n]], {"device": tot[0], "pinned": tot[1]})
+
+
+def ctx_mem_grow(name, need, cap, few=False, **geo):
+    """the bytes the lazy buffer `name` takes when it holds `cap` elements and `need` are asked for, in a context of the arguments `geo` (those
+    of ctx_mem_plan: w, h, fmt, ...); needs no device"""
+    a = dict(pyramid_levels=0, n_src_slots=1, n_recon_slots=1, max_jobs=1, out_slots=1, blk_w=0, blk_h=0)
+    a.update(geo)
+    return int(_mem_lib().dsvg_ctx_mem_grow(a["w"], a["h"], a["fmt"], a["pyramid_levels"], a["n_src_slots"], a["n_recon_slots"], a["max_jobs"], a["out_slots"],
+                                            a["blk_w"], a["blk_h"], ctx_mem_names().index(name), need, cap, 1 if few else 0))
+
+
+def ctx_mem_live(ctx):
+    """{buffer name: bytes} the device context `ctx` holds now (every id; 0: not allocated)"""
+    b = (_C.c_size_t * CTX_MEM_IDS)()
+    _chk(_mem_lib().dsvg_ctx_mem_live(ctx, b, CTX_MEM_IDS), "dsvg_ctx_mem_live")
+    return dict(zip(ctx_mem_names(), (int(v) for v in b)))
+
+
+def mem_outstanding():
+    """(device bytes, pinned bytes) held by all live contexts of the process"""
+    o = (_C.c_size_t * 2)()
+    _mem_lib().dsvg_mem_outstanding(o)
+    return int(o[0]), int(o[1])
+
+
 def code_batch_plan(w, h, fmt, n_recon_slots, n_src_slots, max_jobs, out_slots, code_streams, switches, nsteps, njobs, jobs, rc=None):
     """what dsvg_code_batch (rc: dsvg_code_batch_rc) decides on the host for `jobs` (a ctypes array of PicJob, jobs[step * njobs + j]; rc
     one of RcJob) in an encoder context created with these arguments, with the A/B switches of the mask `switches` (BATCH_*): a dict of
@@ -795,6 +862,10 @@ class Batch:
         self.width, self.height, self.fmt = m.width, m.height, m.subsamp
         self._dev = []
         self._pin = []
+
+    def mem_live(self):
+        """{buffer name: bytes} the batch's device context holds now (ctx_mem_live)"""
+        return ctx_mem_live(self.ctx)
 
     def _input(self, yuv):
         """a host clip as the C entry points read it: nsources x F frames, whatever it is given (checked here)"""
@@ -2106,6 +2177,10 @@ class DecBatch:
     def ctx(self):
         """the device context (not cached: the batch builds a new one when its streams announce another block size)"""
         return self.L.dsv1_decbatch_ctx(self.h)
+
+    def mem_live(self):
+        """{buffer name: bytes} the batch's device context holds now (ctx_mem_live)"""
+        return ctx_mem_live(self.ctx)
 
     def _output_changed(self):
         self.frame_bytes = int(self.L.dsv1_decbatch_out_frame_bytes(self.h))

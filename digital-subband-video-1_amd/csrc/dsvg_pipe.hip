@@ -12,6 +12,8 @@
 #include "dsvg_batch_plan.h"
 #include "dsvg_dec_plan.h"
 #include "dsvg_load_plan.h"
+#include "dsvg_ctx_mem.h"
+#include <atomic>
 #include <ctime>
 extern "C" void dsv1_par_for(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);     // host/dsv1_util.c: the worker pool
 extern "C" void dsv1_par_for_long(int S, void (*fn)(void *ctx, int s, int tid), void *ctx);
@@ -162,8 +164,6 @@ struct dsvg_ctx {
     bool no_lazy_border = false;     // DSV1_NO_LAZY_BORDER=1: every reconstruction gets its whole border (A/B)
     bool no_list_pack = false;       // DSV1_NO_LIST_PACK=1: a wave per chunk for sparse pictures too (A/B)
     int32_t *llsym = nullptr;        // per work job: LL-region symbols of the encoder (JobDev.llsym)
-    int ll_off[3] = {0, 0, 0};
-    size_t ll_total = 0;
     bool llq = true;                 // the LL quantiser runs inside k_fwd_haar_mid<4> / k_tail_q (DSV1_NO_LLQ=1: k_hz_quant<true>, A/B)
     int16_t *symP = nullptr;         // the same for P pictures: kept ZERO between pictures (sparse stores, k_hz_collect clears)
     uint8_t *pflag = nullptr;        // per work job: flag byte per 8x8-pixel patch and plane (indexed like s3)
@@ -202,9 +202,11 @@ struct dsvg_ctx {
     // enqueued -- kept here so that its vectors are allocated once, not per call
     BatchGeo bgeo = {};
     BatchPlan plan;
-    size_t nz_off[3] = {0, 0, 0}, nz_total = 0;
-    int chunk_off[3] = {0, 0, 0}, chunks_per_job = 0, max_chunks = 0;
-    size_t bits_off[3] = {0, 0, 0}, bits_cap[3] = {0, 0, 0}, bits_per_job = 0;
+    // memory (dsvg_ctx_mem.h): what the sizes read of the context, and per buffer id what the context holds -- the allocation, its capacity in
+    // elements (lazy buffers) and its bytes.  The typed fields below are copies of mem[].p (ctx_fields).
+    CtxMemGeo mgeo = {};
+    CtxScan scan;                    // per-plane scan bookkeeping of a job: nz_off .. ll_total
+    struct Mem { void *p; size_t cap, bytes; int kind; } mem[CM_N] = {};
     // motion estimation
     DMV *mvf = nullptr;
     unsigned *aux_tex = nullptr;
@@ -213,7 +215,6 @@ struct dsvg_ctx {
     int *slots_d = nullptr;          // [3 * max_jobs]: cur, ref, recon tables
     unsigned *luma_sums = nullptr;   // [n_src]
     // host pinned staging
-    uint8_t *bits_h = nullptr;
     HzPlaneSum *psum_h = nullptr;
     DMV *mv_h = nullptr;
     uint8_t *stable_h = nullptr;
@@ -222,7 +223,6 @@ struct dsvg_ctx {
     DMV *amv_h = nullptr;            // analysis-stream staging (motion fields)
     unsigned *luma_h = nullptr;
     uint8_t *dec_h[2] = {nullptr, nullptr}, *dec_d[2] = {nullptr, nullptr};   // decoder: payload blob of one call (pinned / device), by call parity
-    size_t dec_cap[2] = {0, 0};
     hipEvent_t ev_dec[2] = {nullptr, nullptr};   // uploads of the call that last used that parity
     hipEvent_t ev_pack[2] = {nullptr, nullptr};  // decoder, round 5: the packing pass runs on the second coding stream ([0]: the reconstructions are there, [1]: the pass is done)
     bool pack_pending = false;                   // ... and the first stream has not yet been told to wait for it
@@ -265,9 +265,7 @@ struct dsvg_ctx {
     DecPlan dec_plan;
     long dec_redone = 0;                // calls decoded again on the int32 path (tests)
     HzParseChunk *dec_meta = nullptr;            // decoder: k_hz_parse -> k_hz_codes records of one call
-    size_t dec_meta_cap = 0;
     uint8_t *yuv_stage = nullptr;    // device staging for host-resident input frames
-    size_t yuv_stage_bytes = 0;
     int *ltab_d = nullptr;           // slot table of dsvg_load_frames_map
     int *otab_d = nullptr;           // table of the output pass: slots (k_pack_n) or (slot, output frame) pairs (k_pixout)
     // Decoder, debug overlay (dsvg_ctx_draw_info, k_drawinfo.hip): with a mode set, every P picture of a decoder call is copied behind its
@@ -293,13 +291,11 @@ struct dsvg_ctx {
     // next batch runs under the analysis and coding of the current one
     hipStream_t st_h = nullptr;
     uint8_t *ingest[2] = {nullptr, nullptr};
-    size_t ingest_bytes[2] = {0, 0};
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr};
     bool up_pending[2] = {false, false}, used_valid[2] = {false, false};
     int ingest_next = 0;
     unsigned long long *gtab_d = nullptr, *gtab_h = nullptr;   // gather table (3 words per plane payload)
     uint8_t *gath_d = nullptr, *gath_h = nullptr;              // compacted payloads (device / pinned host)
-    size_t gath_cap = 0;
     Prof prof;
 };
 
@@ -429,32 +425,96 @@ extern "C" int dsvg_ctx_fetch_prof(dsvg_ctx *c, double out[5], int reset)
     return DSVG_OK;
 }
 
+// ---- the context's memory: one allocator, one owner ---------------------------------------------------------------------------------
+// Every buffer of a context is allocated by ctx_alloc and freed by ctx_release, which keep the record dsvg_ctx::mem[id] and the process's
+// totals; sizes come from dsvg_ctx_mem.h.  hipMalloc / hipHostMalloc / hipFree / hipHostFree appear in this file in this pair alone (and
+// in dsvg_dev_alloc .. dsvg_host_free_on, whose memory the caller owns); slabs go through Slab::alloc / release (dsvg_common.hip).
+static std::atomic<long long> g_mem_out[2];       // [DSVG_MEM_DEVICE] (slabs among them), [DSVG_MEM_PINNED]
+static std::atomic<int> g_fail_at{0};             // dsvg_debug_fail_alloc_at: allocations to go until one fails
+static int ctx_alloc(dsvg_ctx *c, int id, int kind, size_t bytes, bool zero)
+{
+    dsvg_ctx::Mem &m = c->mem[id];
+    const int t = kind == DSVG_MEM_PINNED ? 1 : 0;
+    void *p = nullptr;
+    int rc = DSVG_OK;
+    if (g_fail_at.load() > 0 && g_fail_at.fetch_sub(1) == 1) { dsvg_set_error("%s (%zu bytes): out of memory", ctx_mem_name(id), bytes); return DSVG_ERR_HIP; }
+    if (kind == DSVG_MEM_SLAB) {
+        Slab s;
+        if ((rc = s.alloc(bytes - 2 * GUARD_BYTES))) { const std::string why = dsvg_last_error(); dsvg_set_error("%s (%zu bytes): %s", ctx_mem_name(id), bytes, why.c_str()); }
+        p = s.raw;                                   // (zeroed, and the device synchronised behind it)
+    } else {
+        const hipError_t e = t ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+        if (e != hipSuccess) { dsvg_set_error("%s (%zu bytes): %s", ctx_mem_name(id), bytes, hipGetErrorString(e)); return DSVG_ERR_HIP; }
+    }
+    if (!p) return rc;
+    m = {p, 0, bytes, kind};
+    g_mem_out[t] += (long long)bytes;
+    if (zero && kind == DSVG_MEM_PINNED) memset(p, 0, bytes);
+    if (zero && kind == DSVG_MEM_DEVICE) HIPCHK(hipMemset(p, 0, bytes));
+    return rc;
+}
+static void ctx_release(dsvg_ctx *c, int id)
+{
+    dsvg_ctx::Mem &m = c->mem[id];
+    if (!m.p) return;
+    if (m.kind == DSVG_MEM_SLAB) { Slab s; s.raw = (uint8_t *)m.p; s.release(); }
+    else if (m.kind == DSVG_MEM_PINNED) (void)hipHostFree(m.p);
+    else (void)hipFree(m.p);
+    g_mem_out[m.kind == DSVG_MEM_PINNED ? 1 : 0] -= (long long)m.bytes;
+    m = {};
+}
+// the typed fields, from the records
+static void ctx_fields(dsvg_ctx *c)
+{
+#define X(id, name, field) { const dsvg_ctx::Mem &m = c->mem[CM_##id]; c->field.raw = (uint8_t *)m.p; c->field.p = m.p ? c->field.raw + GUARD_BYTES : nullptr; c->field.bytes = m.p ? m.bytes - 2 * GUARD_BYTES : 0; }
+    DSVG_CTX_MEM_SLABS(X)
+#undef X
+#define X(id, name, field) c->field = (decltype(c->field))c->mem[CM_##id].p;
+    DSVG_CTX_MEM_BUFS(X) DSVG_CTX_MEM_LAZY(X)
+#undef X
+}
+static_assert(GUARD_BYTES == CTX_MEM_GUARD && DSVG_Q_KINDS == 4, "dsvg_ctx_mem.h restates both");
+// A buffer allocated on first use: at least `need` elements of buffer `id` (ctx_mem_grow: the new capacity; ctx_mem_lazy: the element,
+// the pad and the streams that may still read a buffer being replaced).  *grew: a new buffer was allocated.
+static int ctx_grow(dsvg_ctx *c, int id, size_t need, bool few = false, bool *grew = nullptr)
+{
+    dsvg_ctx::Mem &m = c->mem[id];
+    if (grew) *grew = false;
+    if (need <= m.cap) return DSVG_OK;            // (nothing asked for, nothing allocated)
+    const size_t cap = ctx_mem_grow(id, c->mgeo, need, m.cap, few);
+    const CtxMemLazy z = ctx_mem_lazy(id, c->mgeo);
+    if (m.p) {
+        if ((z.sync & CTX_SYNC_ST_H) && c->st_h) HIPCHK(hipStreamSynchronize(c->st_h));
+        if (z.sync & CTX_SYNC_ST) HIPCHK(hipStreamSynchronize(c->st));
+        if (z.sync & CTX_SYNC_ST_A) HIPCHK(hipStreamSynchronize(c->st_a));
+        if (z.sync & CTX_SYNC_ST_L) HIPCHK(hipStreamSynchronize(c->st_l));
+        ctx_release(c, id);
+    }
+    const int rc = ctx_alloc(c, id, z.kind, cap * z.size + z.pad, z.zeroed != 0);
+    if (!rc) m.cap = cap;
+    if (grew) *grew = !rc;
+    ctx_fields(c);
+    return rc;
+}
+extern "C" void dsvg_debug_fail_alloc_at(int n) { g_fail_at.store(n > 0 ? n : 0); }
+extern "C" void dsvg_mem_outstanding(size_t out[2]) { for (int t = 0; t < 2; t++) out[t] = (size_t)g_mem_out[t].load(); }
+extern "C" const char *dsvg_ctx_mem_name(int id) { return ctx_mem_name(id); }
+extern "C" int dsvg_ctx_mem_live(const dsvg_ctx *c, size_t *bytes_by_id, int n)
+{
+    if (!c || !bytes_by_id || n < 0 || n > CM_N) { dsvg_set_error("bad ctx_mem_live arguments"); return DSVG_ERR_ARG; }
+    for (int i = 0; i < n; i++) bytes_by_id[i] = c->mem[i].bytes;
+    return DSVG_OK;
+}
+
 static void ctx_free(dsvg_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->tl_on && !c->tl_quiet) { (void)hipDeviceSynchronize(); tl_dump(c); }
     tl_clear(c);
-    if (c->slot_y_d) (void)hipFree(c->slot_y_d);
-    if (c->slot_y_h) (void)hipHostFree(c->slot_y_h);
-    if (c->slot_cu_d) (void)hipFree(c->slot_cu_d);
-    if (c->slot_cv_d) (void)hipFree(c->slot_cv_d);
-    if (c->slot_cs_d) (void)hipFree(c->slot_cs_d);
-    if (c->slot_cu_h) (void)hipHostFree(c->slot_cu_h);
-    if (c->slot_cv_h) (void)hipHostFree(c->slot_cv_h);
-    if (c->slot_cs_h) (void)hipHostFree(c->slot_cs_h);
-    if (c->dec_flag_d) (void)hipFree(c->dec_flag_d);
-    if (c->dec_flag_h) (void)hipHostFree(c->dec_flag_h);
-    for (int i = 0; i < 6; i++) c->src[i].release();
-    c->recon.release(); c->xf.release(); c->pred.release();
+    for (int id = 0; id < CM_N; id++) ctx_release(c, id);
     xres_geo_free(c->xg);
     scale_geo_free(c->osc);
-    void *d[] = {c->coef, c->s3, c->s1, c->s5, c->sym, c->nzpos, c->nzval, c->chunks, c->psum, c->bits, c->mvs, c->stable,
-                 c->jobs_d, c->mvf, c->aux_tex, c->aux_var, c->csum, c->slots_d, c->luma_sums, c->yuv_stage, c->gtab_d, c->gath_d, c->ltab_d, c->otab_d, c->ingest[0], c->ingest[1], c->dec_d[0], c->dec_d[1], c->dec_meta, c->ilist_d, c->draw_scratch, c->osc_scratch, c->osc_tab_d, c->nzf, c->symP, c->pflag, c->cflag, c->stat, c->llsym, c->rc_state_d, c->rcj_d, (void *)c->xref_d};
-    for (void *p : d) if (p) (void)hipFree(p);
-    void *hh[] = {c->jobs_h, c->bits_h, c->psum_h, c->mv_h, c->stable_h, c->slots_h, c->luma_h, c->dec_h[0], c->dec_h[1], c->ilist_h, c->gtab_h, c->gath_h, c->aslots_h, c->amv_h, c->rcj_h, (void *)c->xref_h};
-    for (void *p : hh) if (p) (void)hipHostFree(p);
-    for (auto &q : c->q) { if (q.dev) (void)hipFree(q.dev); if (q.host) (void)hipHostFree(q.host); }
     if (c->st) (void)hipStreamDestroy(c->st);
     for (int i = 0; i < 2; i++) if (c->ev_mark[i]) (void)hipEventDestroy(c->ev_mark[i]);
     if (c->st_l && c->st_l != c->st_a) (void)hipStreamDestroy(c->st_l);
@@ -479,19 +539,6 @@ static void ctx_free(dsvg_ctx *c)
     for (hipEvent_t e : c->ev_coded) (void)hipEventDestroy(e);
     if (c->ev_user) (void)hipEventDestroy(c->ev_user);
     delete c;
-}
-
-template <typename T> static int dmalloc(T **p, size_t n, bool zero)
-{
-    HIPCHK(hipMalloc((void **)p, n * sizeof(T) + 256));
-    if (zero) HIPCHK(hipMemset(*p, 0, n * sizeof(T) + 256));
-    return DSVG_OK;
-}
-template <typename T> static int hmalloc(T **p, size_t n)
-{
-    HIPCHK(hipHostMalloc((void **)p, n * sizeof(T) + 64, hipHostMallocDefault));
-    memset(*p, 0, n * sizeof(T) + 64);
-    return DSVG_OK;
 }
 
 // The geometry tables of a context as functions of the picture alone: block geometry (blk_w = 0: the encoder's own block size), frame and
@@ -544,11 +591,9 @@ static const FwdOpts FWD_FRAME_STEP = { /* quantise */ true, /* llq */ false, /*
 
 // What dsvg_ctx_create (encoder block size) answers for a geometry, without a device: the resolution ladder refuses a geometry before
 // it allocates anything (dsv1_resladder_open).  The same checks, in the same order, as the context creation below.
-static int geom_check(int width, int height, int subsamp, CtxGeo &geo)
+// (geo_supported: the checks of the tables themselves, which creation and dsvg_ctx_mem_plan make of a decoder's block size too)
+static int geo_supported(const CtxGeo &geo, int width, int height)
 {
-    if (width < 32 || height < 32) { dsvg_set_error("bad ctx_create arguments"); return DSVG_ERR_ARG; }
-    if (subsamp != 0x0 && subsamp != 0x4 && subsamp != 0x5 && subsamp != 0x8) { dsvg_set_error("bad subsampling"); return DSVG_ERR_ARG; }
-    make_ctx_geo(geo, width, height, subsamp);
     const CoefLayout &CL = geo.CL;
     for (int p = 0; p < 3; p++)
         if (!sbt_tail_supported(geo.G.g[p])) { dsvg_set_error("plane %dx%d: LL5 band does not fit the LDS tail kernel", CL.w[p], CL.h[p]); return DSVG_ERR_UNSUPPORTED; }
@@ -558,6 +603,13 @@ static int geom_check(int width, int height, int subsamp, CtxGeo &geo)
         if (hp.nchunks > hz_scan_items_max()) { dsvg_set_error("plane too large for the scan kernel"); return DSVG_ERR_UNSUPPORTED; }
     }
     return DSVG_OK;
+}
+static int geom_check(int width, int height, int subsamp, CtxGeo &geo)
+{
+    if (width < 32 || height < 32) { dsvg_set_error("bad ctx_create arguments"); return DSVG_ERR_ARG; }
+    if (subsamp != 0x0 && subsamp != 0x4 && subsamp != 0x5 && subsamp != 0x8) { dsvg_set_error("bad subsampling"); return DSVG_ERR_ARG; }
+    make_ctx_geo(geo, width, height, subsamp);
+    return geo_supported(geo, width, height);
 }
 extern "C" int dsvg_geom_check(int width, int height, int subsamp)
 {
@@ -757,6 +809,72 @@ extern "C" int dsvg_hme_plan(int width, int height, int subsamp, int csum_table,
     return P.n;
 }
 
+// the argument checks of dsvg_ctx_create_blk that need no device (dsvg_ctx_mem_plan makes them too)
+static int ctx_args_check(int width, int height, int subsamp, int n_src_slots, int n_recon_slots, int max_jobs, int blk_w, int blk_h)
+{
+    if ((blk_w || blk_h) && (blk_w < 16 || blk_w > 64 || blk_h < 16 || blk_h > 64 || (blk_w & 3) || (blk_h & 3))) {
+        dsvg_set_error("block size %dx%d: multiples of 4 in 16..64 (dsv_decoder.c:351-356)", blk_w, blk_h);
+        return DSVG_ERR_ARG;
+    }
+    if (width < 32 || height < 32 || n_src_slots < 1 || n_recon_slots < 1 || max_jobs < 1) { dsvg_set_error("bad ctx_create arguments"); return DSVG_ERR_ARG; }
+    if (subsamp != 0x0 && subsamp != 0x4 && subsamp != 0x5 && subsamp != 0x8) { dsvg_set_error("bad subsampling"); return DSVG_ERR_ARG; }
+    return DSVG_OK;
+}
+// What the sizes of a context's buffers read of it (dsvg_ctx_mem.h), and its per-plane scan bookkeeping, from the tables of its
+// creation: dsvg_ctx_create_blk keeps both, and dsvg_ctx_mem_plan asks the plan about the same record without a context.
+static void ctx_mem_geo(CtxMemGeo &M, CtxScan &S, const CtxGeo &geo, const HmeArgs &A, const BatchGeo &B)
+{
+    const CoefLayout &CL = geo.CL;
+    int nchunks[3];
+    M = CtxMemGeo();
+    for (int p = 0; p < 3; p++) {
+        HzPlane hp; make_hz_plane(hp, CL.w[p], CL.h[p], 100, 0, p, geo.nbh, geo.nbv);
+        nchunks[p] = hp.nchunks;
+        M.ll[p] = (size_t)CL.w3[p] * CL.h3[p];
+    }
+    ctx_scan_layout(S, nchunks, CL.w, CL.h, M.ll);
+    M.levels = A.levels;
+    for (int l = 0; l <= A.levels; l++) M.pitch[l] = A.L[l].pitch;
+    M.total = CL.total; M.s3total = CL.s3total; M.s1total = CL.s1total; M.s5total = CL.s5total;
+    M.nz_total = S.nz_total; M.bits_per_job = S.bits_per_job; M.chunks_per_job = S.chunks_per_job; M.nblk = B.nblk;
+    M.n_src = B.n_src; M.n_recon = B.n_recon; M.max_jobs = B.max_jobs; M.out_slots = B.out_slots; M.rc_slots = B.rc_slots; M.mc_fused = B.mc_fused;
+    M.nwin = (B.out_slots + B.max_jobs - 1) / B.max_jobs + 1;
+    M.sz_chunk_sum = sizeof(HzChunkSum); M.sz_plane_sum = sizeof(HzPlaneSum); M.sz_mv = sizeof(DMV); M.sz_job = sizeof(JobDev);
+    M.sz_rc_job = sizeof(RcJobDev); M.sz_rc_state = sizeof(dsvg_rc_state); M.sz_parse_chunk = sizeof(HzParseChunk);
+}
+// the same for the arguments of a creation, checked as it checks them (the switches: the environment's, as at creation)
+static int ctx_mem_geo_of(CtxMemGeo &M, int width, int height, int subsamp, int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots,
+                          int blk_w, int blk_h)
+{
+    OPCHK(ctx_args_check(width, height, subsamp, n_src_slots, n_recon_slots, max_jobs, blk_w, blk_h));
+    CtxGeo geo;
+    make_ctx_geo(geo, width, height, subsamp, blk_w, blk_h);
+    OPCHK(geo_supported(geo, width, height));
+    HmeArgs A;
+    make_hme_geo(A, geo, width, height, subsamp, pyramid_levels);
+    CtxScan S;
+    ctx_mem_geo(M, S, geo, A, batch_geo(geo, n_src_slots, n_recon_slots, max_jobs, out_slots, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_LAZY_BORDER")));
+    return DSVG_OK;
+}
+extern "C" int dsvg_ctx_mem_plan(int width, int height, int subsamp, int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots,
+                                 int blk_w, int blk_h, dsvg_ctx_mem_row *rows, int cap, size_t totals[2])
+{
+    if (cap < 0 || (cap > 0 && !rows)) { dsvg_set_error("bad ctx_mem_plan arguments"); return DSVG_ERR_ARG; }
+    CtxMemGeo M;
+    OPCHK(ctx_mem_geo_of(M, width, height, subsamp, pyramid_levels, n_src_slots, n_recon_slots, max_jobs, out_slots, blk_w, blk_h));
+    dsvg_ctx_mem_row all[CM_N_CREATE];
+    const int n = plan_ctx_mem(M, all, totals);
+    for (int i = 0; i < n && i < cap; i++) rows[i] = all[i];
+    return n;
+}
+extern "C" size_t dsvg_ctx_mem_grow(int width, int height, int subsamp, int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots,
+                                    int blk_w, int blk_h, int id, size_t need, size_t cap, int few)
+{
+    CtxMemGeo M;
+    if (id < CM_N_CREATE || id >= CM_N || ctx_mem_geo_of(M, width, height, subsamp, pyramid_levels, n_src_slots, n_recon_slots, max_jobs, out_slots, blk_w, blk_h)) return 0;
+    return ctx_mem_lazy_bytes(id, M, ctx_mem_grow(id, M, need, cap, few != 0));
+}
+
 extern "C" int dsvg_ctx_create(dsvg_ctx **out, int device, int width, int height, int subsamp,
                                int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots)
 {
@@ -765,15 +883,8 @@ extern "C" int dsvg_ctx_create(dsvg_ctx **out, int device, int width, int height
 extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int height, int subsamp,
                                    int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots, int blk_w, int blk_h)
 {
-    if ((blk_w || blk_h) && (blk_w < 16 || blk_w > 64 || blk_h < 16 || blk_h > 64 || (blk_w & 3) || (blk_h & 3))) {
-        dsvg_set_error("block size %dx%d: multiples of 4 in 16..64 (dsv_decoder.c:351-356)", blk_w, blk_h);
-        return DSVG_ERR_ARG;
-    }
-    if (!out || width < 32 || height < 32 || n_src_slots < 1 || n_recon_slots < 1 || max_jobs < 1) {
-        dsvg_set_error("bad ctx_create arguments");
-        return DSVG_ERR_ARG;
-    }
-    if (subsamp != 0x0 && subsamp != 0x4 && subsamp != 0x5 && subsamp != 0x8) { dsvg_set_error("bad subsampling"); return DSVG_ERR_ARG; }
+    if (!out) { dsvg_set_error("bad ctx_create arguments"); return DSVG_ERR_ARG; }
+    OPCHK(ctx_args_check(width, height, subsamp, n_src_slots, n_recon_slots, max_jobs, blk_w, blk_h));
     if (dsvg_device_count() <= device) { dsvg_set_error("HIP device %d not present", device); return DSVG_ERR_NODEVICE; }
     HIPCHK(hipSetDevice(device));
     dsvg_ctx *c = new dsvg_ctx();
@@ -790,18 +901,14 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         for (int l = 1; l <= c->levels; l++) c->L[l] = c->hme.L[l];
         c->bgeo = batch_geo(geo, n_src_slots, n_recon_slots, max_jobs, out_slots, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_LAZY_BORDER"));
         c->dgeo = dec_geo(geo, n_recon_slots, max_jobs, !getenv("DSV1_NO_MC_FUSION"), !getenv("DSV1_NO_DEC_SYM_OV"));
+        const int rc = geo_supported(geo, width, height);
+        if (rc) { delete c; return rc; }
+        ctx_mem_geo(c->mgeo, c->scan, geo, c->hme, c->bgeo);
     }
     out_slots = c->bgeo.out_slots;                          // (at least max_jobs)
     c->n_src = n_src_slots; c->n_recon = n_recon_slots; c->max_jobs = max_jobs; c->out_slots = out_slots;
-    c->nwin = (out_slots + max_jobs - 1) / max_jobs + 1;
+    c->nwin = c->mgeo.nwin;
     c->nblk = c->nbh * c->nbv;
-    const CoefLayout &CL = c->CL;
-    for (int p = 0; p < 3; p++)
-        if (!sbt_tail_supported(c->G.g[p])) {
-            dsvg_set_error("plane %dx%d: LL5 band does not fit the LDS tail kernel", CL.w[p], CL.h[p]);
-            delete c; return DSVG_ERR_UNSUPPORTED;
-        }
-    if ((width | height) & 1) { dsvg_set_error("odd luma dimensions are not supported (intra B4T needs even planes)"); delete c; return DSVG_ERR_UNSUPPORTED; }
     c->mc_fused = c->bgeo.mc_fused != 0;
     c->no_inplace_pred = getenv("DSV1_NO_INPLACE_PRED") != nullptr;
     c->no_dec_sym = getenv("DSV1_NO_DEC_SYM") != nullptr;
@@ -812,19 +919,6 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
     // two coding streams by default: with the analysis and fetch streams that is four, the number of hardware queues
     // the runtime maps streams onto (three coding streams measured 18.5 ms per step against 14.3 with two and 15.4 with one)
     { const char *e = getenv("DSV1_CODE_STREAMS"); c->code_streams = e ? atoi(e) : 2; }
-    // per-plane scan bookkeeping
-    size_t nzo = 0, bo = 0; int cho = 0;
-    for (int p = 0; p < 3; p++) {
-        HzPlane hp; make_hz_plane(hp, CL.w[p], CL.h[p], 100, 0, p, c->nbh, c->nbv);
-        if (hp.nchunks > hz_scan_items_max()) { dsvg_set_error("plane too large for the scan kernel"); delete c; return DSVG_ERR_UNSUPPORTED; }
-        c->nz_off[p] = nzo; nzo += (size_t)hp.nchunks * HZ_CHUNK;
-        c->chunk_off[p] = cho; cho += hp.nchunks;
-        c->max_chunks = std::max(c->max_chunks, hp.nchunks);
-        c->bits_cap[p] = ((size_t)CL.w[p] * CL.h[p] * 2 + 255) & ~(size_t)255;    // 16 bits/coefficient bound
-        c->bits_off[p] = bo; bo += c->bits_cap[p] + 256;
-    }
-    c->nz_total = nzo; c->chunks_per_job = cho; c->bits_per_job = bo;
-
     int rc = DSVG_OK;
     // (a failed allocation also leaves HIP's per-thread last error set: it is taken here, or the next context's first
     // hipGetLastError check -- a smaller ladder tried after one that did not fit -- would report this failure as its own)
@@ -859,68 +953,18 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { dsvg_set_error("hipEventCreate failed"); return fail(DSVG_ERR_HIP); }
     c->slot_ev.assign((size_t)out_slots, -1);
     sbt_set_func_attributes();
-    for (int l = 0; l <= c->levels; l++)
-        if ((rc = c->src[l].alloc(c->L[l].pitch * (size_t)n_src_slots + 4096))) return fail(rc);
-    if ((rc = c->recon.alloc(c->L[0].pitch * (size_t)n_recon_slots + 4096))) return fail(rc);
-    if ((rc = c->xf.alloc(c->L[0].pitch * (size_t)max_jobs + 4096))) return fail(rc);
-    if ((rc = c->pred.alloc(c->L[0].pitch * (size_t)max_jobs + 4096))) return fail(rc);
-    const size_t J = (size_t)max_jobs, O = (size_t)out_slots, S = J * (size_t)c->nwin;
-    if ((rc = dmalloc(&c->coef, CL.total * J, true))) return fail(rc);
-    if ((rc = dmalloc(&c->s3, CL.s3total * J, true))) return fail(rc);
-    if ((rc = dmalloc(&c->s1, CL.s1total * J, true))) return fail(rc);
-    if ((rc = dmalloc(&c->s5, CL.s5total * J, true))) return fail(rc);
-    if ((rc = dmalloc(&c->nzpos, c->nz_total * J, false))) return fail(rc);
-    if ((rc = dmalloc(&c->nzval, c->nz_total * J, false))) return fail(rc);
-    if ((rc = dmalloc(&c->chunks, (size_t)c->chunks_per_job * J, true))) return fail(rc);
-    if ((rc = dmalloc(&c->sym, c->nz_total * J, true))) return fail(rc);
-    const size_t DT = 1;        // (one set of symbol / flag planes per work job; round 3's deferred entropy stage kept one per frame step: a measured dead end)
-    if ((rc = dmalloc(&c->nzf, (c->nz_total >> 2) * J * DT, true))) return fail(rc);
-    if ((rc = dmalloc(&c->symP, c->nz_total * J * DT, true))) return fail(rc);
-    if ((rc = dmalloc(&c->pflag, CL.s3total * J, true))) return fail(rc);
-    if ((rc = dmalloc(&c->cflag, (size_t)c->chunks_per_job * J * DT, true))) return fail(rc);
-    {   // LL symbol planes (int32, scan order), each plane's share padded to 8 entries (16-byte reads in k_hz_collect*)
-        size_t o = 0;
-        for (int p = 0; p < 3; p++) { c->ll_off[p] = (int)o; o += ((size_t)CL.w3[p] * CL.h3[p] + 7) & ~(size_t)7; }
-        c->ll_total = o;
-        if ((rc = dmalloc(&c->llsym, c->ll_total * J * DT, true))) return fail(rc);
+    {   // every buffer of the plan, in its order (slabs, work and result buffers, pinned staging, the source slots' plane tables)
+        dsvg_ctx_mem_row rows[CM_N_CREATE];
+        const int nrows = plan_ctx_mem(c->mgeo, rows, nullptr);
+        for (int i = 0; i < nrows; i++)
+            if ((rc = ctx_alloc(c, rows[i].id, rows[i].kind, rows[i].bytes, rows[i].zeroed != 0))) return fail(rc);
+        ctx_fields(c);
     }
     c->llq = !getenv("DSV1_NO_LLQ");
-    if ((rc = dmalloc(&c->stat, 8 * 64, true))) return fail(rc);
-    if ((rc = dmalloc(&c->psum, 3 * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->bits, c->bits_per_job * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->mvs, (size_t)c->nblk * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->stable, (size_t)c->nblk * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->jobs_d, O, true))) return fail(rc);
     c->rc_slots = c->bgeo.rc_slots;
-    if ((rc = dmalloc(&c->rc_state_d, (size_t)c->rc_slots, true))) return fail(rc);
-    if ((rc = dmalloc(&c->rcj_d, O, true))) return fail(rc);
-    if ((rc = hmalloc(&c->rcj_h, std::max(S, O)))) return fail(rc);
-    if ((rc = dmalloc(&c->mvf, (size_t)(c->levels + 1) * c->nblk * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->aux_tex, (size_t)c->nblk * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->aux_var, (size_t)c->nblk * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->csum, (size_t)c->nblk * 4 * (size_t)n_src_slots, true))) return fail(rc);
-    if ((rc = dmalloc(&c->slots_d, 3 * O, true))) return fail(rc);
-    if ((rc = dmalloc(&c->luma_sums, (size_t)n_src_slots, true))) return fail(rc);
-    if ((rc = hmalloc(&c->jobs_h, std::max(S, O)))) return fail(rc);
-    if ((rc = dmalloc(&c->gtab_d, 9 * O, true))) return fail(rc);
-    if ((rc = hmalloc(&c->gtab_h, 9 * O))) return fail(rc);
-    if ((rc = hmalloc(&c->psum_h, 3 * O))) return fail(rc);
-    if ((rc = hmalloc(&c->mv_h, (size_t)c->nblk * std::max(S, O)))) return fail(rc);
-    if ((rc = hmalloc(&c->stable_h, (size_t)c->nblk * std::max(S, O)))) return fail(rc);
-    if ((rc = hmalloc(&c->slots_h, 3 * std::max(S, O)))) return fail(rc);
-    if ((rc = hmalloc(&c->luma_h, (size_t)n_src_slots))) return fail(rc);
-    if ((rc = hmalloc(&c->aslots_h, 2 * O))) return fail(rc);
-    if ((rc = hmalloc(&c->amv_h, (size_t)c->nblk * O))) return fail(rc);
-    if (c->mc_fused) {
-        if ((rc = hmalloc(&c->ilist_h, (size_t)c->nblk * std::max(S, O)))) return fail(rc);
-        if ((rc = dmalloc(&c->ilist_d, (size_t)c->nblk * std::max(S, O), false))) return fail(rc);
-    }
     {   // every source slot's chroma starts as the bordered copy in the slab
         const size_t ns = (size_t)n_src_slots;
         c->slot_cu.resize(ns); c->slot_cv.resize(ns); c->slot_cs.assign(ns, c->L[0].stride[1]);
-        if (hipHostMalloc((void **)&c->slot_cu_h, 8 * ns + 64, hipHostMallocDefault) != hipSuccess || hipHostMalloc((void **)&c->slot_cv_h, 8 * ns + 64, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void **)&c->slot_cs_h, 4 * ns + 64, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&c->slot_cu_d, 8 * ns + 64) != hipSuccess ||
-            hipMalloc((void **)&c->slot_cv_d, 8 * ns + 64) != hipSuccess || hipMalloc((void **)&c->slot_cs_d, 4 * ns + 64) != hipSuccess) { dsvg_set_error("slot tables: out of memory"); return fail(DSVG_ERR_HIP); }
         for (size_t sl = 0; sl < ns; sl++) {
             c->slot_cu[sl] = c->src[0].p + sl * c->L[0].pitch + c->L[0].off[1];
             c->slot_cv[sl] = c->src[0].p + sl * c->L[0].pitch + c->L[0].off[2];
@@ -931,10 +975,7 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
             hipMemcpy(c->slot_cs_d, c->slot_cs_h, 4 * ns, hipMemcpyHostToDevice) != hipSuccess) { dsvg_set_error("slot tables: upload failed"); return fail(DSVG_ERR_HIP); }
         // in place: the forward transforms read whole 8-byte patch rows and never leave the picture when the chroma planes are
         // even (no extra coefficient column: frame.c:39-42) and a multiple of 8 wide; both chroma planes alike
-        c->slot_y.assign(ns, nullptr);
-        if (hipHostMalloc((void **)&c->slot_y_h, 8 * ns + 64, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&c->slot_y_d, 8 * ns + 64) != hipSuccess) { dsvg_set_error("slot tables: out of memory"); return fail(DSVG_ERR_HIP); }
-        memset(c->slot_y_h, 0, 8 * ns);
-        if (hipMemset(c->slot_y_d, 0, 8 * ns + 64) != hipSuccess) { dsvg_set_error("slot tables: upload failed"); return fail(DSVG_ERR_HIP); }
+        c->slot_y.assign(ns, nullptr);                  // (slot_y_h / slot_y_d: zeroed by the allocator)
         // (the geometry's side of both rules: dsvg_load_plan.h)
         c->lgeo = load_geo(c->hme, c->src);
         c->cdirect_ok = load_chroma_in_place_geo(c->lgeo) && !getenv("DSV1_NO_CHROMA_IN_PLACE");
@@ -945,7 +986,6 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         c->ring_y4 = c->lgeo.ring_y4;
         c->ydirect_ok = c->cdirect_ok && load_luma_in_place_geo(c->lgeo) && !getenv("DSV1_NO_LUMA_IN_PLACE") && !getenv("DSV1_NO_FUSE_LEVEL2");
     }
-    (void)J;
     // the pipeline streams are non-blocking (no implicit ordering against the NULL stream the memsets above ran on)
     if (hipDeviceSynchronize() != hipSuccess) { dsvg_set_error("hipDeviceSynchronize failed"); return fail(DSVG_ERR_HIP); }
     *out = c;
@@ -985,7 +1025,7 @@ extern "C" int dsvg_ctx_geom(const dsvg_ctx *c, dsvg_geom *g)
     g->blk_w = c->bw; g->blk_h = c->bh; g->nblocks_h = c->nbh; g->nblocks_v = c->nbv;
     g->pyramid_levels = c->levels;
     g->frame_bytes = (size_t)c->L[0].w[0] * c->L[0].h[0] + 2 * (size_t)c->L[0].w[1] * c->L[0].h[1];
-    for (int p = 0; p < 3; p++) g->plane_out_cap[p] = c->bits_cap[p];
+    for (int p = 0; p < 3; p++) g->plane_out_cap[p] = c->scan.bits_cap[p];
     g->frame_alloc_bytes = c->L[0].bytes;
     return DSVG_OK;
 }
@@ -1134,18 +1174,9 @@ static int ingest_reserve(dsvg_ctx *c, size_t bytes, int *kout)
     }
     const int k = c->ingest_next;
     c->ingest_next ^= 1;
-    if (c->ingest_bytes[k] < bytes) {
-        if (c->ingest[k]) {                      // the old buffer may still be read by load kernels / an earlier copy
-            HIPCHK(hipStreamSynchronize(c->st_h));
-            HIPCHK(hipStreamSynchronize(c->st_a));
-            HIPCHK(hipStreamSynchronize(c->st_l));
-            (void)hipFree(c->ingest[k]);
-            c->ingest[k] = nullptr; c->ingest_bytes[k] = 0;
-        }
-        HIPCHK(hipMalloc((void **)&c->ingest[k], bytes + 256));
-        c->ingest_bytes[k] = bytes;
-        c->used_valid[k] = false;
-    }
+    bool grew;                                   // (an old buffer may still be read by load kernels / an earlier copy: ctx_grow waits)
+    OPCHK(ctx_grow(c, CM_INGEST0 + k, bytes, false, &grew));
+    if (grew) c->used_valid[k] = false;
     if (c->used_valid[k]) HIPCHK(hipStreamWaitEvent(c->st_h, c->ev_used[k], 0));    // its last readers (analysis stream)
     *kout = k;
     return DSVG_OK;
@@ -1181,7 +1212,7 @@ extern "C" int dsvg_ingest_part(dsvg_ctx *c, void *dptr, size_t offset, const vo
     if (!c || !dptr || !host || !bytes) { dsvg_set_error("bad ingest arguments"); return DSVG_ERR_ARG; }
     for (int k = 0; k < 2; k++)
         if (c->ingest[k] && dptr == (void *)c->ingest[k]) {
-            if (offset + bytes > c->ingest_bytes[k]) { dsvg_set_error("ingest part beyond the reserved clip"); return DSVG_ERR_ARG; }
+            if (offset + bytes > c->mem[CM_INGEST0 + k].cap) { dsvg_set_error("ingest part beyond the reserved clip"); return DSVG_ERR_ARG; }
             HIPCHK(hipSetDevice(c->device));
             HIPCHK(hipMemcpyAsync(c->ingest[k] + offset, host, bytes, hipMemcpyHostToDevice, c->st_h));
             HIPCHK(hipEventRecord(c->ev_up[k], c->st_h));
@@ -1197,7 +1228,7 @@ static int ingest_acquire(dsvg_ctx *c, const void *dsrc)
 {
     for (int k = 0; k < 2; k++) {
         const uint8_t *b = c->ingest[k], *p = (const uint8_t *)dsrc;
-        if (b && p >= b && p < b + c->ingest_bytes[k]) {
+        if (b && p >= b && p < b + c->mem[CM_INGEST0 + k].cap) {
             if (c->up_pending[k]) {
                 if (hipStreamWaitEvent(c->st_l, c->ev_up[k], 0) != hipSuccess) return -2;
                 c->up_pending[k] = false;
@@ -1273,11 +1304,7 @@ extern "C" int dsvg_load_frames(dsvg_ctx *c, int first_slot, int n, const void *
     const size_t fb = (size_t)c->L[0].w[0] * c->L[0].h[0] + 2 * (size_t)c->L[0].w[1] * c->L[0].h[1];
     const uint8_t *dsrc = (const uint8_t *)yuv;
     if (!yuv_on_device) {
-        if (c->yuv_stage_bytes < fb * n) {
-            if (c->yuv_stage) { HIPCHK(hipStreamSynchronize(c->st_l)); (void)hipFree(c->yuv_stage); c->yuv_stage = nullptr; }
-            HIPCHK(hipMalloc((void **)&c->yuv_stage, fb * n + 256));
-            c->yuv_stage_bytes = fb * n;
-        }
+        OPCHK(ctx_grow(c, CM_YUV_STAGE, fb * n));
         HIPCHK(hipMemcpyAsync(c->yuv_stage, yuv, fb * n, hipMemcpyHostToDevice, c->st_l));
         dsrc = c->yuv_stage;
     }
@@ -1303,7 +1330,7 @@ extern "C" int dsvg_load_frames_map_ex(dsvg_ctx *c, int n, const int *slots, con
     HIPCHK(hipSetDevice(c->device));
     for (int i = 0; i < n; i++)
         if (slots[i] < 0 || slots[i] >= c->n_src) { dsvg_set_error("slot out of range"); return DSVG_ERR_ARG; }
-    if (!c->ltab_d) HIPCHK(hipMalloc((void **)&c->ltab_d, sizeof(int) * (size_t)c->n_src + 64));
+    OPCHK(ctx_grow(c, CM_LTAB_D, 1));
     const size_t ysz = (size_t)c->L[0].w[0] * c->L[0].h[0], csz = (size_t)c->L[0].w[1] * c->L[0].h[1];
     const bool can = chroma_in_place && c->cdirect_ok && ((uintptr_t)yuv_dev % 16) == 0 && (frame_pitch % 16) == 0 && (ysz % 16) == 0 && (csz % 16) == 0;
     std::vector<int> tab((size_t)n);
@@ -1420,19 +1447,19 @@ static void fill_job(dsvg_ctx *c, JobDev &jb, int t, int isP, int quant, int d =
     jb.s5 = c->s5 + (size_t)t * CL.s5total;
     jb.mvs = c->mvs + (size_t)d * c->nblk;
     jb.stable = c->stable + (size_t)d * c->nblk;
-    jb.nzpos = c->nzpos + (size_t)t * c->nz_total;
-    jb.nzval = c->nzval + (size_t)t * c->nz_total;
-    jb.chunks = c->chunks + (size_t)t * c->chunks_per_job;
-    jb.sym = c->sym + (size_t)t * c->nz_total;
+    jb.nzpos = c->nzpos + (size_t)t * c->scan.nz_total;
+    jb.nzval = c->nzval + (size_t)t * c->scan.nz_total;
+    jb.chunks = c->chunks + (size_t)t * c->scan.chunks_per_job;
+    jb.sym = c->sym + (size_t)t * c->scan.nz_total;
     jb.pflag = c->pflag + (size_t)t * CL.s3total;
-    jb.cflag = c->cflag + (size_t)t * c->chunks_per_job;
+    jb.cflag = c->cflag + (size_t)t * c->scan.chunks_per_job;
     jb.stat = c->stats_on ? c->stat : nullptr;
     jb.psum = c->psum + (size_t)t * 3;
-    jb.bits = c->bits + (size_t)t * c->bits_per_job;
+    jb.bits = c->bits + (size_t)t * c->scan.bits_per_job;
     for (int p = 0; p < 3; p++) {
         jb.pf_off[p] = (int)CL.s3off[p];
-        jb.bits_off[p] = c->bits_off[p]; jb.bits_cap[p] = c->bits_cap[p];
-        jb.nz_off[p] = c->nz_off[p]; jb.hz_coef_off[p] = CL.off[p]; jb.chunk_off[p] = c->chunk_off[p];
+        jb.bits_off[p] = c->scan.bits_off[p]; jb.bits_cap[p] = c->scan.bits_cap[p];
+        jb.nz_off[p] = c->scan.nz_off[p]; jb.hz_coef_off[p] = CL.off[p]; jb.chunk_off[p] = c->scan.chunk_off[p];
         make_hz_plane(jb.hz[p], CL.w[p], CL.h[p], quant, isP, p, c->nbh, c->nbv);
     }
     make_hqp(jb.hqp, quant, isP);
@@ -1526,7 +1553,7 @@ static int enqueue_group(dsvg_ctx *c, const BatchPlan &P, const dsvg_rc_job *rcj
         // k_hz_collect* is the LAST reader of the sparse symbol planes and clears what it reads
         launch_fwd_plan(st, jd, c->G, 0, 3, fwd_step_plan(c->G, n, c->llq), &c->prof);   // levels 4..5, tail: all planes, I and P jobs alike
         if (!c->llq) {
-            launch_hz_quant(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0,
+            launch_hz_quant(st, jd, n, c->scan.chunks_per_job, &c->prof, (double)c->CL.total, 0,
                             (c->CL.w3[0] * c->CL.h3[0] + HZ_CHUNK - 1) / HZ_CHUNK);
         }
         // (pictures nobody predicts from -- intra-only streams -- have no reconstruction to make (dsv_encoder.c:665); a group without a single kept reconstruction skips the inverse transform altogether)
@@ -1539,7 +1566,7 @@ static int enqueue_group(dsvg_ctx *c, const BatchPlan &P, const dsvg_rc_job *rcj
         else if (sse) launch_sse(st, jd, n, c->L[0], c->psum, c->q[DSVG_Q_SSE].dev);
         // (the same place and ordering argument: the reconstruction upscaled to the reference geometry, k_xres_quality)
         if (xres) launch_xres(st, jd, n, c->L[0], c->xg, c->xref_d, c->psum, c->q[DSVG_Q_XSSE].on ? c->q[DSVG_Q_XSSE].dev : nullptr, c->q[DSVG_Q_XSSIM].on ? c->q[DSVG_Q_XSSIM].dev : nullptr);
-        launch_hz_pack(st, jd, n, c->chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
+        launch_hz_pack(st, jd, n, c->scan.chunks_per_job, &c->prof, (double)c->CL.total, 0, c->no_list_pack ? -1 : nI);
         // rate control: the sizes of these packets -> the quantiser tables of the same streams' pictures of the next step
         if (rcj) launch_rc(st, c->jobs_d, c->rcj_d, c->rc_state_d, d0, n, 1);
     }
@@ -1618,14 +1645,14 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
             jb.fused = 1;                      // quantisation fused into the forward transform (I and P pictures)
             jb.llq = c->llq ? 1 : 0;           // ... and the LL region's into the kernels that produce it
             const size_t kk = (size_t)k;
-            jb.llsym = c->llsym + kk * c->ll_total;
-            for (int p = 0; p < 3; p++) jb.ll_off[p] = c->ll_off[p];
-            jb.cflag = c->cflag + kk * c->chunks_per_job;
+            jb.llsym = c->llsym + kk * c->scan.ll_total;
+            for (int p = 0; p < 3; p++) jb.ll_off[p] = c->scan.ll_off[p];
+            jb.cflag = c->cflag + kk * c->scan.chunks_per_job;
             // P pictures run sparse: zero-kept symbol planes + non-zero flags (k_hz_collect takes both down again)
-            jb.nzf = isP ? c->nzf + kk * (c->nz_total >> 2) : nullptr;
-            if (isP) jb.sym = c->symP + kk * c->nz_total;
+            jb.nzf = isP ? c->nzf + kk * (c->scan.nz_total >> 2) : nullptr;
+            if (isP) jb.sym = c->symP + kk * c->scan.nz_total;
             jb.psum = c->psum + (size_t)j.out_slot * 3;
-            jb.bits = c->bits + (size_t)j.out_slot * c->bits_per_job;
+            jb.bits = c->bits + (size_t)j.out_slot * c->scan.bits_per_job;
             jb.src = c->src[0].p + (size_t)j.src_slot * c->L[0].pitch;
             jb.srcp[0] = jb.src + c->L[0].off[0]; jb.srcs[0] = c->L[0].stride[0];
             if (c->slot_y[(size_t)j.src_slot]) { jb.srcp[0] = c->slot_y[(size_t)j.src_slot]; jb.srcs[0] = c->L[0].w[0]; }      // luma in place (round 5)
@@ -1841,19 +1868,13 @@ extern "C" int dsvg_fetch_pictures_cb(dsvg_ctx *c, int n, const int *out_slots, 
     // gather kernel and payload in two.  A plane that is longer (I pictures) sends the call down the general path below.
     if (few) {
         constexpr size_t K = 65536;
-        if (c->gath_cap < 4 * 3 * K + 64) {
-            if (c->gath_d) (void)hipFree(c->gath_d);
-            if (c->gath_h) (void)hipHostFree(c->gath_h);
-            c->gath_d = nullptr; c->gath_h = nullptr;
-            c->gath_cap = (size_t)1 << 20;
-            HIPCHK(hipMalloc((void **)&c->gath_d, c->gath_cap));
-            HIPCHK(hipHostMalloc((void **)&c->gath_h, c->gath_cap, hipHostMallocDefault));
-        }
+        OPCHK(ctx_grow(c, CM_GATH_D, 4 * 3 * K + 64, true));
+        OPCHK(ctx_grow(c, CM_GATH_H, 4 * 3 * K + 64, true));
         for (int i = 0; i < n; i++) {
             const int o = out_slots[i];
             HIPCHK(hipMemcpyAsync(c->psum_h + 3 * (size_t)o, c->psum + 3 * (size_t)o, sizeof(HzPlaneSum) * 3, hipMemcpyDeviceToHost, c->st_c));
             for (int p = 0; p < 3; p++)
-                HIPCHK(hipMemcpyAsync(c->gath_h + (3 * (size_t)i + p) * K, c->bits + (size_t)o * c->bits_per_job + c->bits_off[p], std::min(K, c->bits_cap[p]),
+                HIPCHK(hipMemcpyAsync(c->gath_h + (3 * (size_t)i + p) * K, c->bits + (size_t)o * c->scan.bits_per_job + c->scan.bits_off[p], std::min(K, c->scan.bits_cap[p]),
                                       hipMemcpyDeviceToHost, c->st_c));
         }
         HIPCHK(hipStreamSynchronize(c->st_c));
@@ -1862,8 +1883,8 @@ extern "C" int dsvg_fetch_pictures_cb(dsvg_ctx *c, int n, const int *out_slots, 
         for (int i = 0; i < n; i++)
             for (int p = 0; p < 3; p++) {
                 const HzPlaneSum &ps = c->psum_h[3 * (size_t)out_slots[i] + p];
-                if (ps.overflow) { dsvg_set_error("packed plane %d of out slot %d exceeds %zu bytes", p, out_slots[i], c->bits_cap[p]); return DSVG_ERR_OVERFLOW; }
-                fits = fits && (size_t)((ps.total_bits + 7) >> 3) <= std::min(K, c->bits_cap[p]);
+                if (ps.overflow) { dsvg_set_error("packed plane %d of out slot %d exceeds %zu bytes", p, out_slots[i], c->scan.bits_cap[p]); return DSVG_ERR_OVERFLOW; }
+                fits = fits && (size_t)((ps.total_bits + 7) >> 3) <= std::min(K, c->scan.bits_cap[p]);
             }
         if (fits) {
             for (int i = 0; i < n; i++) {
@@ -1895,23 +1916,17 @@ extern "C" int dsvg_fetch_pictures_cb(dsvg_ctx *c, int n, const int *out_slots, 
         const int o = out_slots[i];
         for (int p = 0; p < 3; p++) {
             const HzPlaneSum &ps = c->psum_h[3 * (size_t)o + p];
-            if (ps.overflow) { dsvg_set_error("packed plane %d of out slot %d exceeds %zu bytes", p, o, c->bits_cap[p]); return DSVG_ERR_OVERFLOW; }
+            if (ps.overflow) { dsvg_set_error("packed plane %d of out slot %d exceeds %zu bytes", p, o, c->scan.bits_cap[p]); return DSVG_ERR_OVERFLOW; }
             const size_t nb = (size_t)((ps.total_bits + 7) >> 3);
             unsigned long long *t = c->gtab_h + 3 * (3 * (size_t)i + p);
-            t[0] = (size_t)o * c->bits_per_job + c->bits_off[p];
+            t[0] = (size_t)o * c->scan.bits_per_job + c->scan.bits_off[p];
             t[1] = total;
             t[2] = nb;
             total += (nb + 15) & ~(size_t)15;
         }
     }
-    if (total + 64 > c->gath_cap) {
-        if (c->gath_d) (void)hipFree(c->gath_d);
-        if (c->gath_h) (void)hipHostFree(c->gath_h);
-        c->gath_d = nullptr; c->gath_h = nullptr;
-        c->gath_cap = total * 2 + (1u << 20);
-        HIPCHK(hipMalloc((void **)&c->gath_d, c->gath_cap));
-        HIPCHK(hipHostMalloc((void **)&c->gath_h, c->gath_cap, hipHostMallocDefault));
-    }
+    OPCHK(ctx_grow(c, CM_GATH_D, total + 64));
+    OPCHK(ctx_grow(c, CM_GATH_H, total + 64));
     tl_mark(c, c->st_c, "fetch0");
     HIPCHK(hipMemcpyAsync(c->gtab_d, c->gtab_h, sizeof(unsigned long long) * 9 * (size_t)n, hipMemcpyHostToDevice, c->st_c));
     launch_gather_bits(c->st_c, c->bits, c->gtab_d, 3 * n, c->gath_d);
@@ -1969,8 +1984,8 @@ static int quality_enable(dsvg_ctx *c, int kind, int on)
     if (on && !q.dev) {                         // (every call zeroes the sums of its out slots itself)
         HIPCHK(hipSetDevice(c->device));
         q.measured.assign((size_t)c->out_slots, 0);             // (first: sized wherever a table exists)
-        OPCHK(dmalloc(&q.dev, (size_t)3 * c->out_slots, false));
-        OPCHK(hmalloc(&q.host, (size_t)3 * c->out_slots));
+        OPCHK(ctx_grow(c, CM_Q_DEV0 + kind, 1));
+        OPCHK(ctx_grow(c, CM_Q_HOST0 + kind, 1));
     }
     q.on = on != 0;
     return DSVG_OK;
@@ -2029,8 +2044,8 @@ extern "C" int dsvg_ctx_xres_enable(dsvg_ctx *c, int sse_on, int ssim_on, int re
         c->xref_next.assign((size_t)c->out_slots, nullptr);                 // (frames of another geometry: set them again)
     }
     if (!c->xref_d) {
-        OPCHK(dmalloc(&c->xref_d, (size_t)c->out_slots, true));
-        OPCHK(hmalloc(&c->xref_h, (size_t)c->out_slots));
+        OPCHK(ctx_grow(c, CM_XREF_D, 1));
+        OPCHK(ctx_grow(c, CM_XREF_H, 1));
         c->xref_next.assign((size_t)c->out_slots, nullptr);
     }
     OPCHK(quality_enable(c, DSVG_Q_XSSE, sse_on));
@@ -2082,7 +2097,8 @@ extern "C" int dsvg_ctx_output_scale(dsvg_ctx *c, int out_w, int out_h, int filt
     if (!c->osc.planes_d || c->osc_w != out_w || c->osc_h != out_h || c->osc_filter != filter) {
         HIPCHK(hipDeviceSynchronize());                 // (no pass in flight may still read the tables or the scratch being replaced)
         OPCHK(scale_geo_build(c->osc, c->L[0], c->fmt, out_w, out_h, filter));   // (refused: the setting in force stays)
-        if (c->osc_scratch) { (void)hipFree(c->osc_scratch); c->osc_scratch = nullptr; }
+        ctx_release(c, CM_OSC_SCRATCH);
+        ctx_fields(c);
         c->osc_w = out_w; c->osc_h = out_h; c->osc_filter = filter;
         c->osc_fb = (c->osc.dfb + 255) & ~(size_t)255;
     }
@@ -2096,11 +2112,7 @@ extern "C" int dsvg_download_recon(dsvg_ctx *c, int recon_slot, uint8_t *yuv_out
     HIPCHK(hipSetDevice(c->device));
     OPCHK(dec_resolve(c));
     const size_t fb = (size_t)c->L[0].w[0] * c->L[0].h[0] + 2 * (size_t)c->L[0].w[1] * c->L[0].h[1];
-    if (c->yuv_stage_bytes < fb) {
-        if (c->yuv_stage) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipFree(c->yuv_stage); c->yuv_stage = nullptr; }
-        HIPCHK(hipMalloc((void **)&c->yuv_stage, fb + 256));
-        c->yuv_stage_bytes = fb;
-    }
+    OPCHK(ctx_grow(c, CM_YUV_STAGE, fb));
     launch_pack(c->st, c->yuv_stage, shown_frame(c, recon_slot), c->L[0]);
     HIPCHK(hipMemcpyAsync(yuv_out, c->yuv_stage, fb, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -2245,9 +2257,9 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
         }
         tab = shown.data();
     }
-    if (!c->otab_d) HIPCHK(hipMalloc((void **)&c->otab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
-    if (sc && fmt && !c->osc_scratch) HIPCHK(hipMalloc((void **)&c->osc_scratch, c->osc_fb * (size_t)c->n_recon + 256));
-    if (!fpairs.empty() && !c->osc_tab_d) HIPCHK(hipMalloc((void **)&c->osc_tab_d, 2 * sizeof(int) * (size_t)c->n_recon + 64));
+    OPCHK(ctx_grow(c, CM_OTAB_D, 1));
+    if (sc && fmt) OPCHK(ctx_grow(c, CM_OSC_SCRATCH, c->osc_fb * (size_t)c->n_recon));
+    if (!fpairs.empty()) OPCHK(ctx_grow(c, CM_OSC_TAB_D, 1));
     // One pass at a time: the first coding stream waits for the pass before, which keeps the passes in order and the table whole.
     // Round 5: device output of four pictures or more goes to the second coding stream -- beside the next call's entropy decoding, which
     // touches neither the reconstructions nor the caller's frames (70 us of a 620 us step of 64 pictures).  Whatever rewrites a
@@ -2272,11 +2284,7 @@ static int output_pass(dsvg_ctx *c, int n, const int *slots, const int *index, v
         // else the buffer goes up first, so that the copy back returns what the pass left alone
         if (!fmt) dpitch = (fb + 255) & ~(size_t)255;
         span = fmt ? pitch * (size_t)last + fmt->planes_bytes : dpitch * (size_t)n;
-        if (c->yuv_stage_bytes < span) {
-            if (c->yuv_stage) { HIPCHK(hipStreamSynchronize(c->st)); HIPCHK(hipStreamSynchronize(c->st_a)); HIPCHK(hipStreamSynchronize(c->st_l)); (void)hipFree(c->yuv_stage); c->yuv_stage = nullptr; }
-            HIPCHK(hipMalloc((void **)&c->yuv_stage, span + 256));
-            c->yuv_stage_bytes = span;
-        }
+        OPCHK(ctx_grow(c, CM_YUV_STAGE, span));
         dst = c->yuv_stage;
         bool dense = fmt && !index && fmt->planes_bytes == pitch;
         for (int s = 0; dense && s < fmt->nseg; s++) {
@@ -2391,26 +2399,14 @@ static int dec_commit(dsvg_ctx *c, const DecPlan &P, const dsvg_dec_job *jobs, i
     else HIPCHK(hipEventSynchronize(c->ev_dec[k]));
     c->dec_par ^= 1;
     const size_t blob = P.blob, nmeta = P.nmeta;
-    if (blob > c->dec_cap[k]) {
-        if (c->dec_h[k]) (void)hipHostFree(c->dec_h[k]);
-        if (c->dec_d[k]) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipFree(c->dec_d[k]); }
-        c->dec_h[k] = nullptr; c->dec_d[k] = nullptr; c->dec_cap[k] = 0;
-        const size_t cap = blob * 2 + (1u << 20);
-        HIPCHK(hipHostMalloc((void **)&c->dec_h[k], cap, hipHostMallocDefault));
-        HIPCHK(hipMalloc((void **)&c->dec_d[k], cap + 256));
-        c->dec_cap[k] = cap;
-    }
+    OPCHK(ctx_grow(c, CM_DEC_H0 + k, blob));
+    OPCHK(ctx_grow(c, CM_DEC_D0 + k, blob));
     // per 128-bit payload chunk one hand-over record between the parse kernels (device only, consumed in stream order)
-    if (nmeta > c->dec_meta_cap) {
-        if (c->dec_meta) { HIPCHK(hipStreamSynchronize(c->st)); (void)hipFree(c->dec_meta); c->dec_meta = nullptr; c->dec_meta_cap = 0; }
-        const size_t cap = nmeta * 2 + 4096;
-        HIPCHK(hipMalloc((void **)&c->dec_meta, cap * sizeof(HzParseChunk)));
-        c->dec_meta_cap = cap;
-    }
+    OPCHK(ctx_grow(c, CM_DEC_META, nmeta));
     const size_t hb = (size_t)k * c->max_jobs;          // this parity's part of the pinned tables
     if (!c->dec_flag_d) {
-        HIPCHK(hipMalloc((void **)&c->dec_flag_d, sizeof(int) * 2 * (size_t)c->max_jobs));
-        HIPCHK(hipHostMalloc((void **)&c->dec_flag_h, sizeof(int) * 2 * (size_t)c->max_jobs, hipHostMallocDefault));
+        OPCHK(ctx_grow(c, CM_DEC_FLAG_D, 1));
+        OPCHK(ctx_grow(c, CM_DEC_FLAG_H, 1));
         for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_flag[i], hipEventDisableTiming));
     }
     dsvg_ctx::DecPending &pend = c->dec_pending;
@@ -2428,8 +2424,8 @@ static int dec_commit(dsvg_ctx *c, const DecPlan &P, const dsvg_dec_job *jobs, i
         jb.recon = c->recon.p + (size_t)j.recon_slot * c->L[0].pitch;
         jb.dec_flag = c->dec_flag_d + hb + t;
         memcpy(jb.dec_lim, lim[o.wide ? 1 : 0], sizeof jb.dec_lim);
-        if (o.path != DEC_PATH_I32) jb.sym = c->symP + (size_t)t * c->nz_total;
-        if (o.path == DEC_PATH_SYM_P) jb.nzf = c->nzf + (size_t)t * (c->nz_total >> 2);      // (marks the job as sparse for the inverse; the flags themselves are the encoder's)
+        if (o.path != DEC_PATH_I32) jb.sym = c->symP + (size_t)t * c->scan.nz_total;
+        if (o.path == DEC_PATH_SYM_P) jb.nzf = c->nzf + (size_t)t * (c->scan.nz_total >> 2);      // (marks the job as sparse for the inverse; the flags themselves are the encoder's)
         for (int p = 0; p < 3; p++) jb.dec_sym[p] = o.dec_sym[p];
         if (o.inplace) jb.pred = jb.recon;              // prediction written in place
         c->slots_h[hb + t] = j.recon_slot;
@@ -2527,7 +2523,7 @@ static int dec_enqueue(dsvg_ctx *c, const DecPlan &P, int k)
         // copied to the scratch frame of its job and drawn on there, in stream order behind its reconstruction
         const FrameLayout &L = c->L[0];
         const int d0 = P.draw0;
-        if (!c->draw_scratch) HIPCHK(hipMalloc((void **)&c->draw_scratch, L.pitch * (size_t)c->max_jobs + 256));
+        OPCHK(ctx_grow(c, CM_DRAW_SCRATCH, 1));
         if (c->draw_at.empty()) c->draw_at.assign((size_t)c->n_recon, -1);
         for (int t = d0; t < P.draw1; t++) {
             const int slot = c->slots_h[hb + t];

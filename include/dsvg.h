@@ -693,6 +693,30 @@ typedef struct dsvg_load_plan_out {
 int dsvg_load_plan(int width, int height, int subsamp, int pyramid_levels, int with_pyramid, int src_mod16, int pitch_mod16, unsigned switches,
                    int n, int n_chroma_in_place, int n_luma_in_place, dsvg_load_plan_out *out);
 
+/* A context's memory (csrc/dsvg_ctx_mem.h).  Every buffer a context owns has an id, 0 .. DSVG_CTX_MEM_IDS - 1, and a short name
+ * (dsvg_ctx_mem_name).  dsvg_ctx_mem_plan: the buffers dsvg_ctx_create_blk allocates for these arguments, in the order it allocates
+ * them, without a device -- the same argument and geometry checks with the same codes; at most `cap` rows are written, the number of
+ * rows is returned (>= 0), totals[DSVG_MEM_DEVICE] = device bytes (slabs among them), totals[DSVG_MEM_PINNED] = pinned host bytes.
+ * Buffers allocated on first use are not in the plan: dsvg_ctx_mem_grow gives the bytes such a buffer takes in a context of these
+ * arguments when it holds `cap` elements and `need` are asked for (few: the fetch of a few pictures, gath_d / gath_h), 0 = not such an id.
+ * dsvg_ctx_mem_live: the bytes the context holds now, per id (n <= DSVG_CTX_MEM_IDS entries).  dsvg_mem_outstanding: device and pinned
+ * bytes held by all live contexts of the process.  dsvg_debug_fail_alloc_at (tests): the n-th allocation of a context from now on
+ * fails as out of memory, without a HIP call (0 = off). */
+#define DSVG_CTX_MEM_IDS 84
+enum { DSVG_MEM_DEVICE, DSVG_MEM_PINNED, DSVG_MEM_SLAB };
+typedef struct dsvg_ctx_mem_row {
+    int id, kind, zeroed;
+    size_t count, size, pad, bytes;          /* bytes = count * size + pad */
+} dsvg_ctx_mem_row;
+const char *dsvg_ctx_mem_name(int id);
+int dsvg_ctx_mem_plan(int width, int height, int subsamp, int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots,
+                      int blk_w, int blk_h, dsvg_ctx_mem_row *rows, int cap, size_t totals[2]);
+size_t dsvg_ctx_mem_grow(int width, int height, int subsamp, int pyramid_levels, int n_src_slots, int n_recon_slots, int max_jobs, int out_slots,
+                         int blk_w, int blk_h, int id, size_t need, size_t cap, int few);
+int dsvg_ctx_mem_live(const dsvg_ctx *ctx, size_t *bytes_by_id, int n);
+void dsvg_mem_outstanding(size_t out[2]);
+void dsvg_debug_fail_alloc_at(int n);
+
 #ifdef __cplusplus
 }
 #endif

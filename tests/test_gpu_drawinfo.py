@@ -114,8 +114,8 @@ def decoder_case(pkg, name, fmt):
     return _cases[(name, fmt)]
 
 
-def run(pkg, w, h, fmt, pics, modes, setting=None, on_device=False):
-    """the batch over the calls with modes[k] in force: [calls][streams][frame bytes]"""
+def run(pkg, w, h, fmt, pics, modes, setting=None, on_device=False, before_close=None):
+    """the batch over the calls with modes[k] in force: [calls][streams][frame bytes]; before_close(d): called after the last call"""
     d = pkg.DecBatch(w, h, fmt, len(pics))
     try:
         if setting:
@@ -133,6 +133,8 @@ def run(pkg, w, h, fmt, pics, modes, setting=None, on_device=False):
                 frames, status, fnum = d.decode(pk)
             assert list(status) == [0] * len(pics) and list(fnum) == [k] * len(pics)
             out.append(np.array(frames, copy=True))
+        if before_close:
+            before_close(d)
         return np.stack(out)
     finally:
         d.close()
