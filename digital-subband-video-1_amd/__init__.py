@@ -775,6 +775,65 @@ def decode_plan(w, h, fmt, n_recon_slots, max_jobs, switches, force32, draw_mode
     return out
 
 
+FETCH_NO_FAST = 1                                          # DSVG_FETCH_*
+
+
+class FetchPlan(_C.Structure):
+    """dsvg_fetch_plan_out (include/dsvg.h): the plan of a packet fetch, arrays of the caller's"""
+    _fields_ = [("cap_pics", _C.c_int), ("cap_pieces", _C.c_int), ("wait", _C.c_void_p), ("copies", _C.c_void_p), ("rows", _C.c_void_p),
+                ("nbytes", _C.c_void_p), ("pay", _C.c_void_p), ("piece", _C.c_void_p), ("piece_bytes", _C.c_void_p),
+                ("few", _C.c_int), ("stream_wait", _C.c_int), ("nwait", _C.c_int), ("lo", _C.c_int), ("hi", _C.c_int), ("fits", _C.c_int),
+                ("general", _C.c_int), ("nchunks", _C.c_int), ("grow_few", _C.c_ulonglong), ("total", _C.c_ulonglong), ("grow", _C.c_ulonglong)]
+
+
+class FetchRefused(RuntimeError):
+    """dsvg_fetch_plan did not answer with a plan: rc and text are what the fetch itself would return and set; grow_few, grow: what the
+    call had asked of its payload pair by then"""
+    def __init__(self, rc, text, grow_few=0, grow=0):
+        super().__init__("dsvg_fetch_plan failed rc=%d: %s" % (rc, text))
+        self.rc, self.text, self.grow_few, self.grow = rc, text, grow_few, grow
+
+
+def fetch_plan(ctx_out_slots, out_slots, slot_ev, slot_isP, nring, ncalls, has_cb, switches, bits_per_job, bits_off, bits_cap, total_bits, overflow,
+               nchunks=1, align=1):
+    """what dsvg_fetch_pictures_cb decides on the host for the out slots `out_slots` of a context with `ctx_out_slots` of them, whose
+    slots were coded last by the events slot_ev (indices into a ring of nring, -1: never) and hold P pictures where slot_isP says so
+    (may be short or empty), after ncalls coding calls, with the A/B switches of the mask `switches` (FETCH_*) and the plane summaries
+    total_bits / overflow ([n, 3]) as they come back: a dict of dsvg_fetch_plan_out's fields, the arrays as numpy arrays cut to their
+    lengths (copies, rows: [n, 3, 3]; nbytes, pay: [n, 3]; pieces: [(first, end, o0, o1)]).  Raises FetchRefused with the call's own
+    code and text.  Needs no device"""
+    n = len(out_slots)
+    m = max(n, 1)
+    arr = {"wait": _np.zeros(m, _np.int32), "copies": _np.zeros(9 * m, _np.uint64), "rows": _np.zeros(9 * m, _np.uint64),
+           "nbytes": _np.zeros(3 * m, _np.uint32), "pay": _np.zeros(3 * m, _np.uint64), "piece": _np.zeros(2 * max(nchunks, 1), _np.int32),
+           "piece_bytes": _np.zeros(2 * max(nchunks, 1), _np.uint64)}
+    p = FetchPlan(cap_pics=m, cap_pieces=max(nchunks, 1))
+    for k, a in arr.items():
+        setattr(p, k, a.ctypes.data)
+    slots = (_C.c_int * m)(*out_slots)
+    ev = (_C.c_int * max(len(slot_ev), 1))(*slot_ev)
+    isp = (_C.c_ubyte * max(len(slot_isP), 1))(*slot_isP)
+    bits = (_C.c_ulonglong * 7)(bits_per_job, *bits_off, *bits_cap)
+    tb = _np.ascontiguousarray(_np.asarray(total_bits, _np.uint64).reshape(-1))
+    ov = _np.ascontiguousarray(_np.asarray(overflow, _np.int32).reshape(-1))
+    assert len(tb) >= 3 * n and len(ov) >= 3 * n and len(slot_ev) >= ctx_out_slots
+    f = lib().dsvg_fetch_plan
+    f.argtypes = [_C.c_int, _C.c_int, _C.POINTER(_C.c_int), _C.POINTER(_C.c_int), _C.c_int, _C.POINTER(_C.c_ubyte), _C.c_int, _C.c_longlong, _C.c_int,
+                  _C.c_uint, _C.POINTER(_C.c_ulonglong), _C.c_void_p, _C.c_void_p, _C.c_int, _C.c_int, _C.POINTER(FetchPlan)]
+    r = f(ctx_out_slots, n, slots, ev, len(slot_isP), isp, nring, ncalls, int(bool(has_cb)), switches, bits, tb.ctypes.data, ov.ctypes.data,
+          nchunks, align, _C.byref(p))
+    if r != 0:
+        raise FetchRefused(r, lib().dsvg_last_error().decode(), p.grow_few, p.grow)
+    d = {k: getattr(p, k) for k in ("few", "stream_wait", "lo", "hi", "fits", "general", "nchunks", "grow_few", "total", "grow")}
+    d["wait"] = arr["wait"][:p.nwait].tolist()
+    d["copies"] = arr["copies"][:9 * n * p.few].reshape(-1, 3, 3)
+    d["rows"] = arr["rows"][:9 * n * p.general].reshape(-1, 3, 3)
+    d["nbytes"], d["pay"] = arr["nbytes"][:3 * n].reshape(n, 3), arr["pay"][:3 * n].reshape(n, 3)
+    d["pieces"] = [(int(arr["piece"][2 * j]), int(arr["piece"][2 * j + 1]), int(arr["piece_bytes"][2 * j]), int(arr["piece_bytes"][2 * j + 1]))
+                   for j in range(p.nchunks)]
+    return d
+
+
 def make_encoder_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1, kbps=0, scd=1, ipct=50, pyrlevels=0, stabref=0,
                      fps_num=30, fps_den=1):
     """fill a DSV_ENCODER exactly like the reference CLI does for these flags (dsv_main.c:423-489):

@@ -11,6 +11,7 @@
 #include "dsvg_host.hpp"
 #include "dsvg_batch_plan.h"
 #include "dsvg_dec_plan.h"
+#include "dsvg_fetch_plan.h"
 #include "dsvg_load_plan.h"
 #include "dsvg_ctx_mem.h"
 #include <atomic>
@@ -1603,11 +1604,9 @@ static int code_batch_impl(dsvg_ctx *c, int nsteps, int njobs, const dsvg_pic_jo
     // call completed long ago if its results were fetched -- make sure anyway
     const long call = c->ncalls++;
     {
-        std::vector<char> seen(c->ev_coded.size(), 0);           // the block may have been coded last by several calls
-        for (int i = 0; i < total; i++) {
-            const int e = c->slot_ev[base + i];
-            if (e >= 0 && !seen[e]) { seen[e] = 1; HIPCHK(hipEventSynchronize(c->ev_coded[e])); }
-        }
+        std::vector<int> evs;                                    // the block may have been coded last by several calls
+        coded_events_once(c->slot_ev.data(), c->ev_coded.size(), total, nullptr, base, evs);
+        for (int e : evs) HIPCHK(hipEventSynchronize(c->ev_coded[(size_t)e]));
     }
     // what the call leaves in the context, per picture in device order: its type and whether it is measured (fetch), the reference frame
     // it takes, its reconstruction slot and the border extents written there (what dsvg_recon_border reports)
@@ -1826,151 +1825,125 @@ extern "C" int dsvg_code_pictures(dsvg_ctx *c, int njobs, const dsvg_pic_job *jo
     return dsvg_code_batch(c, 1, njobs, jobs);
 }
 
+// What the plans of a fetch read of a context (dsvg_fetch_plan.h)
+static FetchGeo fetch_geo(int out_slots, const CtxScan &S)
+{
+    FetchGeo G = { out_slots, S.bits_per_job, {}, {} };
+    for (int p = 0; p < 3; p++) { G.bits_off[p] = S.bits_off[p]; G.bits_cap[p] = S.bits_cap[p]; }
+    return G;
+}
+// plan_fetch_layout on the plane summaries that have arrived in psum_h
+static int fetch_layout(const HzPlaneSum *psum_h, const FetchGeo &G, int n, const int *out_slots, bool few, int nchunks, int align, bool has_cb, FetchLayout &L)
+{
+    std::vector<FetchPlaneSize> size(3 * (size_t)n);
+    for (int i = 0; i < n; i++)
+        for (int p = 0; p < 3; p++) {
+            const HzPlaneSum &ps = psum_h[3 * (size_t)out_slots[i] + p];
+            size[3 * (size_t)i + p] = { ps.total_bits, ps.overflow };
+        }
+    const int rc = plan_fetch_layout(G, n, out_slots, size.data(), few, nchunks, align, has_cb, L);
+    if (rc) dsvg_set_error("%s", L.err);
+    return rc;
+}
+// the caller's records: the plane summaries of the slots, the payloads where the plan put them
+static void fill_pic_out(dsvg_pic_out *outs, int n, const int *out_slots, const FetchLayout &L, const HzPlaneSum *psum_h, const uint8_t *gath_h)
+{
+    for (int i = 0; i < n; i++) {
+        const HzPlaneSum *ps = psum_h + 3 * (size_t)out_slots[i];
+        dsvg_pic_out &po = outs[i];
+        for (int p = 0; p < 3; p++) {
+            po.dc[p] = ps[p].dc; po.nruns[p] = ps[p].nruns;
+            po.nbytes[p] = L.nbytes[3 * (size_t)i + p];
+            po.payload[p] = gath_h + L.pay[3 * (size_t)i + p];
+        }
+        po.rc_quant = ps[0].rc; po.rc_pkt_len = (uint32_t)ps[1].rc;
+    }
+}
+
+// Check, wait, sizes, layout, commit, enqueue: plan_fetch_wait and plan_fetch_layout (dsvg_fetch_plan.h) decide, this walks what they say.
 extern "C" int dsvg_fetch_pictures_cb(dsvg_ctx *c, int n, const int *out_slots, dsvg_pic_out *outs, int nchunks, int align, dsvg_fetch_cb cb, void *arg)
 {
-    if (nchunks < 1 || align < 1) { dsvg_set_error("bad fetch_pictures arguments"); return DSVG_ERR_ARG; }
-    if (!c || !outs || !out_slots || n < 1 || n > c->out_slots) { dsvg_set_error("bad fetch_pictures arguments"); return DSVG_ERR_ARG; }
+    if (!c || !outs) { dsvg_set_error("bad fetch_pictures arguments"); return DSVG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    for (int i = 0; i < n; i++)
-        if (out_slots[i] < 0 || out_slots[i] >= c->out_slots) { dsvg_set_error("out slot out of range"); return DSVG_ERR_ARG; }
-    // wait for the coding calls that produce these slots ON THE HOST (this call blocks for its results anyway) -- later
-    // batches already enqueued on the coding streams keep running, and the fetch stream never holds a pending wait: its
-    // hardware queue may be shared with a busy stream, which a queued wait would stall for the rest of the batch
     static const bool no_fast_fetch = getenv("DSV1_NO_FETCH_FAST") != nullptr;     // (A/B)
-    // the frame-serial callers (see below): the wait can sit in the fetch stream and the host makes ONE round trip -- but only when
-    // NOTHING else is in flight (every slot comes from the newest coding call: a queued wait on a fetch stream that shares its
-    // hardware queue with a busy coding stream would stall that stream) and no slot holds an I picture (their planes exceed the
-    // 64 KB the fast path brings back: it would pay the round trip twice)  [advisor, round 3]
     const double tfw = tl_now();
-    bool few = n <= 4 && !cb && !no_fast_fetch;
-    for (int i = 0; i < n && few; i++) {
-        const int e = c->slot_ev[out_slots[i]];
-        if (e >= 0 && e != (int)((c->ncalls - 1) % (long)c->ev_coded.size())) few = false;
-        if ((size_t)out_slots[i] < c->slot_isP.size() && !c->slot_isP[(size_t)out_slots[i]]) few = false;
+    const FetchGeo G = fetch_geo(c->out_slots, c->scan);
+    FetchWait W;                     // (per call, like the plan's pieces: a callback may fetch)
+    FetchLayout L;
+    {   // a refused call leaves the context as it found it
+        const int rc = plan_fetch_wait(G, {no_fast_fetch}, n, out_slots, c->slot_ev.data(), c->slot_isP.data(), c->slot_isP.size(), c->ev_coded.size(), c->ncalls,
+                                       nchunks, align, cb != nullptr, W);
+        if (rc) { dsvg_set_error("%s", W.err); return rc; }
     }
-    {
-        std::vector<char> seen(c->ev_coded.size(), 0);
-        for (int i = 0; i < n; i++) {
-            const int e = c->slot_ev[out_slots[i]];
-            if (e >= 0 && !seen[e]) {
-                seen[e] = 1;
-                if (few) HIPCHK(hipStreamWaitEvent(c->st_c, c->ev_coded[e], 0));
-                else HIPCHK(hipEventSynchronize(c->ev_coded[e]));
-            }
-        }
+    for (int e : W.events) {
+        if (W.stream_wait) HIPCHK(hipStreamWaitEvent(c->st_c, c->ev_coded[(size_t)e], 0));
+        else HIPCHK(hipEventSynchronize(c->ev_coded[(size_t)e]));
     }
     static const bool fprof = getenv("DSV1_HOST_PROF") != nullptr;
     const auto tnow = [] { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; };
     const double tf0 = tnow();
     c->fetch_acc[0] += tf0 - tfw; c->fetch_n++;
-    // A few pictures (the frame-serial callers: ABR streams, dsv_enc without lookahead): their plane summaries and the first 64 KB of
-    // every plane's payload come back in ONE round trip -- a P picture's planes are a few KB -- instead of sizes, gather table,
-    // gather kernel and payload in two.  A plane that is longer (I pictures) sends the call down the general path below.
-    if (few) {
-        constexpr size_t K = 65536;
-        OPCHK(ctx_grow(c, CM_GATH_D, 4 * 3 * K + 64, true));
-        OPCHK(ctx_grow(c, CM_GATH_H, 4 * 3 * K + 64, true));
+    // a few pictures in ONE round trip (plan_fetch_wait says when and why); a plane that does not fit sends the call down the general path
+    if (W.few) {
+        OPCHK(ctx_grow(c, CM_GATH_D, W.grow, true));
+        OPCHK(ctx_grow(c, CM_GATH_H, W.grow, true));
         for (int i = 0; i < n; i++) {
             const int o = out_slots[i];
             HIPCHK(hipMemcpyAsync(c->psum_h + 3 * (size_t)o, c->psum + 3 * (size_t)o, sizeof(HzPlaneSum) * 3, hipMemcpyDeviceToHost, c->st_c));
-            for (int p = 0; p < 3; p++)
-                HIPCHK(hipMemcpyAsync(c->gath_h + (3 * (size_t)i + p) * K, c->bits + (size_t)o * c->scan.bits_per_job + c->scan.bits_off[p], std::min(K, c->scan.bits_cap[p]),
-                                      hipMemcpyDeviceToHost, c->st_c));
+            for (int p = 0; p < 3; p++) {
+                const FetchCopy &k = W.copy[3 * (size_t)i + p];
+                HIPCHK(hipMemcpyAsync(c->gath_h + k.dst, c->bits + k.src, k.bytes, hipMemcpyDeviceToHost, c->st_c));
+            }
         }
         HIPCHK(hipStreamSynchronize(c->st_c));
         HIPCHK(hipGetLastError());
-        bool fits = true;
-        for (int i = 0; i < n; i++)
-            for (int p = 0; p < 3; p++) {
-                const HzPlaneSum &ps = c->psum_h[3 * (size_t)out_slots[i] + p];
-                if (ps.overflow) { dsvg_set_error("packed plane %d of out slot %d exceeds %zu bytes", p, out_slots[i], c->scan.bits_cap[p]); return DSVG_ERR_OVERFLOW; }
-                fits = fits && (size_t)((ps.total_bits + 7) >> 3) <= std::min(K, c->scan.bits_cap[p]);
-            }
-        if (fits) {
-            for (int i = 0; i < n; i++) {
-                dsvg_pic_out &po = outs[i];
-                for (int p = 0; p < 3; p++) {
-                    const HzPlaneSum &ps = c->psum_h[3 * (size_t)out_slots[i] + p];
-                    po.dc[p] = ps.dc; po.nruns[p] = ps.nruns;
-                    po.nbytes[p] = (uint32_t)((ps.total_bits + 7) >> 3);
-                    po.payload[p] = c->gath_h + (3 * (size_t)i + p) * K;
-                }
-                po.rc_quant = c->psum_h[3 * (size_t)out_slots[i]].rc; po.rc_pkt_len = (uint32_t)c->psum_h[3 * (size_t)out_slots[i] + 1].rc;
-            }
+        OPCHK(fetch_layout(c->psum_h, G, n, out_slots, true, nchunks, align, cb != nullptr, L));
+        if (L.fits) {
+            fill_pic_out(outs, n, out_slots, L, c->psum_h, c->gath_h);
             if (fprof) fprintf(stderr, "[dsvg fetch] %d picture(s), one round trip: %.2f ms\n", n, tnow() - tf0);
             return DSVG_OK;
         }
     }
     // 1. plane summaries (sizes)
-    int lo = out_slots[0], hi = out_slots[0];
-    for (int i = 1; i < n; i++) { lo = std::min(lo, out_slots[i]); hi = std::max(hi, out_slots[i]); }
-    HIPCHK(hipMemcpyAsync(c->psum_h + 3 * (size_t)lo, c->psum + 3 * (size_t)lo, sizeof(HzPlaneSum) * 3 * (size_t)(hi - lo + 1),
+    HIPCHK(hipMemcpyAsync(c->psum_h + 3 * (size_t)W.lo, c->psum + 3 * (size_t)W.lo, sizeof(HzPlaneSum) * 3 * (size_t)(W.hi - W.lo + 1),
                           hipMemcpyDeviceToHost, c->st_c));
     HIPCHK(hipStreamSynchronize(c->st_c));
     HIPCHK(hipGetLastError());
     const double tf1 = tnow();
     c->fetch_acc[1] += tf1 - tf0;
     // 2. compact every payload into one buffer on the device, then ONE device-to-host copy
-    size_t total = 0;
-    for (int i = 0; i < n; i++) {
-        const int o = out_slots[i];
-        for (int p = 0; p < 3; p++) {
-            const HzPlaneSum &ps = c->psum_h[3 * (size_t)o + p];
-            if (ps.overflow) { dsvg_set_error("packed plane %d of out slot %d exceeds %zu bytes", p, o, c->scan.bits_cap[p]); return DSVG_ERR_OVERFLOW; }
-            const size_t nb = (size_t)((ps.total_bits + 7) >> 3);
-            unsigned long long *t = c->gtab_h + 3 * (3 * (size_t)i + p);
-            t[0] = (size_t)o * c->scan.bits_per_job + c->scan.bits_off[p];
-            t[1] = total;
-            t[2] = nb;
-            total += (nb + 15) & ~(size_t)15;
-        }
-    }
-    OPCHK(ctx_grow(c, CM_GATH_D, total + 64));
-    OPCHK(ctx_grow(c, CM_GATH_H, total + 64));
+    OPCHK(fetch_layout(c->psum_h, G, n, out_slots, false, nchunks, align, cb != nullptr, L));
+    OPCHK(ctx_grow(c, CM_GATH_D, L.grow));
+    OPCHK(ctx_grow(c, CM_GATH_H, L.grow));
+    memcpy(c->gtab_h, L.rows.data(), sizeof(unsigned long long) * L.rows.size());
     tl_mark(c, c->st_c, "fetch0");
     HIPCHK(hipMemcpyAsync(c->gtab_d, c->gtab_h, sizeof(unsigned long long) * 9 * (size_t)n, hipMemcpyHostToDevice, c->st_c));
     launch_gather_bits(c->st_c, c->bits, c->gtab_d, 3 * n, c->gath_d);
     if (fprof) HIPCHK(hipStreamSynchronize(c->st_c));
     const double tf2 = fprof ? tnow() : 0.0;
-    for (int i = 0; i < n; i++) {
-        const int o = out_slots[i];
-        dsvg_pic_out &po = outs[i];
-        for (int p = 0; p < 3; p++) {
-            const HzPlaneSum &ps = c->psum_h[3 * (size_t)o + p];
-            po.dc[p] = ps.dc; po.nruns[p] = ps.nruns;
-            po.nbytes[p] = (uint32_t)((ps.total_bits + 7) >> 3);
-            po.payload[p] = c->gath_h + c->gtab_h[3 * (3 * (size_t)i + p) + 1];
-        }
-        po.rc_quant = c->psum_h[3 * (size_t)o].rc; po.rc_pkt_len = (uint32_t)c->psum_h[3 * (size_t)o + 1].rc;
-    }
-    // 3. the copy, in nchunks pieces that end on multiples of `align` pictures: the caller's work on a piece (packet
-    //    assembly) runs while the later pieces are still on the link
-    if (!cb) nchunks = 1;
-    nchunks = std::max(1, std::min(nchunks, n / align));
-    while ((int)c->ev_fetch.size() < nchunks) {
+    fill_pic_out(outs, n, out_slots, L, c->psum_h, c->gath_h);
+    // 3. the copy, in pieces that end on multiples of `align` pictures: the caller's work on a piece (packet assembly) runs while
+    //    the later pieces are still on the link
+    while ((int)c->ev_fetch.size() < L.nchunks) {
         hipEvent_t e;
         HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->ev_fetch.push_back(e);
     }
-    std::vector<int> cend((size_t)nchunks);
-    for (int j = 0; j < nchunks; j++) {
-        cend[j] = j + 1 == nchunks ? n : (int)((long)(n / align) * (j + 1) / nchunks) * align;
-        const int first = j ? cend[j - 1] : 0;
-        const size_t o0 = first < n ? (size_t)c->gtab_h[3 * (3 * (size_t)first) + 1] : total;
-        const size_t o1 = cend[j] < n ? (size_t)c->gtab_h[3 * (3 * (size_t)cend[j]) + 1] : total;
+    for (int j = 0; j < L.nchunks; j++) {
+        const FetchPiece &k = L.piece[(size_t)j];
         for (int r = 0; r < link_repeat(); r++)
-        if (o1 > o0) HIPCHK(hipMemcpyAsync(c->gath_h + o0, c->gath_d + o0, o1 - o0, hipMemcpyDeviceToHost, c->st_c));
+        if (k.o1 > k.o0) HIPCHK(hipMemcpyAsync(c->gath_h + k.o0, c->gath_d + k.o0, k.o1 - k.o0, hipMemcpyDeviceToHost, c->st_c));
         HIPCHK(hipEventRecord(c->ev_fetch[j], c->st_c));
     }
     tl_mark(c, c->st_c, "fetch1");
-    for (int j = 0; j < nchunks; j++) {
+    for (int j = 0; j < L.nchunks; j++) {
         HIPCHK(hipEventSynchronize(c->ev_fetch[j]));
-        const int first = j ? cend[j - 1] : 0;
-        if (cb && cend[j] > first) cb(arg, first, cend[j] - first);
+        const FetchPiece &k = L.piece[(size_t)j];
+        if (cb && k.end > k.first) cb(arg, k.first, k.end - k.first);
     }
     if (c->tl_on && c->tl.size() < 16384) c->tl.push_back({"asm_done", nullptr, tl_now()});
-    c->fetch_acc[2] += tnow() - tf1; c->fetch_acc[3] += (double)total;
-    if (fprof) fprintf(stderr, "[dsvg fetch] wait for coding + sizes %.2f ms, gather %.2f ms, D2H of %.1f MB (+ the caller's work on %d pieces) %.2f ms\n", tf1 - tf0, tf2 - tf1, total / 1e6, nchunks, tnow() - tf2);
+    c->fetch_acc[2] += tnow() - tf1; c->fetch_acc[3] += (double)L.total;
+    if (fprof) fprintf(stderr, "[dsvg fetch] wait for coding + sizes %.2f ms, gather %.2f ms, D2H of %.1f MB (+ the caller's work on %d pieces) %.2f ms\n", tf1 - tf0, tf2 - tf1, L.total / 1e6, L.nchunks, tnow() - tf2);
     HIPCHK(hipGetLastError());
     return DSVG_OK;
 }
@@ -2007,11 +1980,9 @@ static int quality_fetch(dsvg_ctx *c, int kind, const char *what, int n, const i
     if (n == 0) return DSVG_OK;
     HIPCHK(hipSetDevice(c->device));
     // behind the calls that coded those slots, on the fetch stream; one copy of the range they span
-    std::vector<char> seen(c->ev_coded.size(), 0);
-    for (int i = 0; i < n; i++) {
-        const int e = c->slot_ev[(size_t)out_slots[i]];
-        if (e >= 0 && !seen[(size_t)e]) { seen[(size_t)e] = 1; HIPCHK(hipStreamWaitEvent(c->st_c, c->ev_coded[(size_t)e], 0)); }
-    }
+    std::vector<int> evs;
+    coded_events_once(c->slot_ev.data(), c->ev_coded.size(), n, out_slots, 0, evs);
+    for (int e : evs) HIPCHK(hipStreamWaitEvent(c->st_c, c->ev_coded[(size_t)e], 0));
     HIPCHK(hipMemcpyAsync(q.host + (size_t)3 * lo, q.dev + (size_t)3 * lo, sizeof(unsigned long long) * 3 * (size_t)(hi - lo + 1), hipMemcpyDeviceToHost, c->st_c));
     HIPCHK(hipStreamSynchronize(c->st_c));
     for (int i = 0; i < n; i++) memcpy((unsigned long long *)out + (size_t)3 * i, q.host + (size_t)3 * out_slots[i], 3 * sizeof(unsigned long long));
@@ -2066,6 +2037,52 @@ extern "C" int dsvg_ctx_xres_refs(dsvg_ctx *c, const void *ref_clip, int n, cons
 extern "C" int dsvg_fetch_pictures(dsvg_ctx *c, int n, const int *out_slots, dsvg_pic_out *outs)
 {
     return dsvg_fetch_pictures_cb(c, n, out_slots, outs, 1, 1, nullptr, nullptr);
+}
+
+// What the two plans decide for a fetch (include/dsvg.h), without a device or a context: the call's own sequence -- the wait plan, the
+// layout of the path it chose, and the general layout behind a one-round-trip path whose planes do not fit
+extern "C" int dsvg_fetch_plan(int ctx_out_slots, int n, const int *out_slots, const int *slot_ev, int n_isP, const unsigned char *slot_isP, int nring,
+                               long long ncalls, int has_cb, unsigned switches, const unsigned long long bits[7], const unsigned long long *total_bits,
+                               const int *overflow, int nchunks, int align, dsvg_fetch_plan_out *out)
+{
+    if (!out || !slot_ev || ctx_out_slots < 1 || n_isP < 0 || (n_isP > 0 && !slot_isP) || nring < 1 || ncalls < 0 || !bits || !total_bits || !overflow) {
+        dsvg_set_error("bad fetch_plan arguments"); return DSVG_ERR_ARG;
+    }
+    out->few = out->stream_wait = out->nwait = out->lo = out->hi = out->fits = out->general = out->nchunks = 0;
+    out->grow_few = out->total = out->grow = 0;
+    const FetchGeo G = { ctx_out_slots, (size_t)bits[0], {(size_t)bits[1], (size_t)bits[2], (size_t)bits[3]}, {(size_t)bits[4], (size_t)bits[5], (size_t)bits[6]} };
+    FetchWait W;
+    FetchLayout L;
+    L.fits = false;
+    int r = plan_fetch_wait(G, {(switches & DSVG_FETCH_NO_FAST) != 0}, n, out_slots, slot_ev, (const char *)slot_isP, (size_t)n_isP, (size_t)nring, (long)ncalls,
+                            nchunks, align, has_cb != 0, W);
+    if (r) { dsvg_set_error("%s", W.err); return r; }
+    if (out->cap_pics < n || !out->wait || !out->copies || !out->rows || !out->nbytes || !out->pay) {
+        dsvg_set_error("fetch_plan: the arrays are missing or too small (%d pictures)", n); return DSVG_ERR_ARG;
+    }
+    out->few = W.few; out->stream_wait = W.stream_wait; out->nwait = (int)W.events.size(); out->lo = W.lo; out->hi = W.hi; out->grow_few = W.grow;
+    for (size_t i = 0; i < W.events.size(); i++) out->wait[i] = W.events[i];
+    for (size_t k = 0; k < W.copy.size(); k++) { out->copies[3 * k] = W.copy[k].src; out->copies[3 * k + 1] = W.copy[k].dst; out->copies[3 * k + 2] = W.copy[k].bytes; }
+    std::vector<FetchPlaneSize> size(3 * (size_t)n);
+    for (size_t k = 0; k < size.size(); k++) size[k] = { total_bits[k], overflow[k] };
+    if (W.few) {
+        if ((r = plan_fetch_layout(G, n, out_slots, size.data(), true, nchunks, align, has_cb != 0, L))) { dsvg_set_error("%s", L.err); return r; }
+        out->fits = L.fits;
+    }
+    if (!L.fits) {
+        if ((r = plan_fetch_layout(G, n, out_slots, size.data(), false, nchunks, align, has_cb != 0, L))) { dsvg_set_error("%s", L.err); return r; }
+        if (out->cap_pieces < L.nchunks || !out->piece || !out->piece_bytes) {
+            dsvg_set_error("fetch_plan: the piece arrays are missing or too small (%d pieces)", L.nchunks); return DSVG_ERR_ARG;
+        }
+        out->general = 1; out->total = L.total; out->grow = L.grow; out->nchunks = L.nchunks;
+        for (size_t k = 0; k < L.rows.size(); k++) out->rows[k] = L.rows[k];
+        for (int j = 0; j < L.nchunks; j++) {
+            const FetchPiece &k = L.piece[(size_t)j];
+            out->piece[2 * j] = k.first; out->piece[2 * j + 1] = k.end; out->piece_bytes[2 * j] = k.o0; out->piece_bytes[2 * j + 1] = k.o1;
+        }
+    }
+    for (size_t k = 0; k < 3 * (size_t)n; k++) { out->nbytes[k] = L.nbytes[k]; out->pay[k] = L.pay[k]; }
+    return DSVG_OK;
 }
 
 

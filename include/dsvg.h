@@ -693,6 +693,42 @@ typedef struct dsvg_load_plan_out {
 int dsvg_load_plan(int width, int height, int subsamp, int pyramid_levels, int with_pyramid, int src_mod16, int pitch_mod16, unsigned switches,
                    int n, int n_chroma_in_place, int n_luma_in_place, dsvg_load_plan_out *out);
 
+/* The plan of a packet fetch (tests): what dsvg_fetch_pictures(_cb) decides on the host, without a device or a context -- the call's own
+ * two plans (plan_fetch_wait, plan_fetch_layout, csrc/dsvg_fetch_plan.h: the call waits, grows, copies and calls back as they say) on
+ * what they read of a context, as plain arrays.  ctx_out_slots: the context's out slots; slot_ev[ctx_out_slots]: per out slot the index
+ * in the ring of nring coding events of the call that coded it last (-1: none); slot_isP[n_isP]: it holds a P picture (n_isP may be
+ * smaller than ctx_out_slots, 0 on a context that has coded nothing); ncalls: coding calls made; has_cb: a callback is given; switches:
+ * a mask of DSVG_FETCH_* for the A/B switch DSV1_NO_FETCH_FAST, whatever the environment says; bits[7]: the packed bits of a job
+ * (bytes per job, the three planes' offsets, the three planes' capacities); total_bits[3 i + p], overflow[3 i + p]: the plane
+ * summaries of out_slots[i] as they come back; nchunks, align: as dsvg_fetch_pictures_cb takes them.  Returns DSVG_OK, the code and
+ * text the call itself answers for arguments or an overflowed plane, or DSVG_ERR_ARG for arrays that are missing or too small.
+ *   few: the one-round-trip path (at most 4 pictures, no callback, every slot coded by the newest call or never, no I picture, switch
+ *   unset); stream_wait: the coding events wait[0 .. nwait) -- each once, in first-appearance order -- are waited for in the fetch stream,
+ *   else on the host; grow_few: what that path asks of the payload pair (elements, the `few` rule of dsvg_ctx_mem_grow) and copies[9 n]:
+ *   its copies per picture and plane (source byte in the packed bits, destination byte, bytes); fits: every plane lies within them.
+ *   general: the general path runs (not few, or few and not fits): the plane summaries of out slots lo .. hi come back in one copy,
+ *   rows[9 n] is the gather table (source byte, destination byte, bytes), total the bytes gathered, grow what it asks of the payload
+ *   pair, and the copy is made in nchunks pieces: pictures piece[2 j] .. piece[2 j + 1] - 1, bytes piece_bytes[2 j] .. piece_bytes[2 j + 1] - 1,
+ *   the callback called once per piece in this order.  nbytes[3 n], pay[3 n]: every payload's bytes and where it starts in the pinned
+ *   buffer, on the path that delivers.  A refused call reports no growth -- except that an overflowed plane found on the few path is
+ *   found after grow_few was taken.
+ * Append-only: later versions add fields at the end. */
+#define DSVG_FETCH_NO_FAST 1
+typedef struct dsvg_fetch_plan_out {
+    int cap_pics, cap_pieces;                /* in: pictures / pieces the caller's arrays hold */
+    int *wait;                               /* cap_pics */
+    unsigned long long *copies, *rows;       /* 9 * cap_pics each */
+    unsigned *nbytes;                        /* 3 * cap_pics */
+    unsigned long long *pay;                 /* 3 * cap_pics */
+    int *piece;                              /* 2 * cap_pieces */
+    unsigned long long *piece_bytes;         /* 2 * cap_pieces */
+    int few, stream_wait, nwait, lo, hi, fits, general, nchunks;
+    unsigned long long grow_few, total, grow;
+} dsvg_fetch_plan_out;
+int dsvg_fetch_plan(int ctx_out_slots, int n, const int *out_slots, const int *slot_ev, int n_isP, const unsigned char *slot_isP, int nring,
+                    long long ncalls, int has_cb, unsigned switches, const unsigned long long bits[7], const unsigned long long *total_bits,
+                    const int *overflow, int nchunks, int align, dsvg_fetch_plan_out *out);
+
 /* A context's memory (csrc/dsvg_ctx_mem.h).  Every buffer a context owns has an id, 0 .. DSVG_CTX_MEM_IDS - 1, and a short name
  * (dsvg_ctx_mem_name).  dsvg_ctx_mem_plan: the buffers dsvg_ctx_create_blk allocates for these arguments, in the order it allocates
  * them, without a device -- the same argument and geometry checks with the same codes; at most `cap` rows are written, the number of
