@@ -2380,8 +2380,14 @@ extern "C" long dsvg_ctx_decoder_redone(const dsvg_ctx *c) { return c ? c->dec_r
 extern "C" int dsvg_decode_pictures(dsvg_ctx *c, int njobs, const dsvg_dec_job *jobs)
 {
     if (!c) { dsvg_set_error("bad decode_pictures arguments"); return DSVG_ERR_ARG; }
+    // A P picture that updates its reference in place (recon_slot == ref_recon_slot) can be decoded only once: the second pass of a
+    // flagged call would predict from what the first pass wrote.  A call with such a picture takes the int32 path, which raises no
+    // flag, from the start (the plan's force32, as the second pass itself asks for it).
+    bool once = false;
+    if (jobs && njobs >= 1 && njobs <= c->max_jobs)
+        for (int i = 0; i < njobs; i++) once = once || (jobs[i].ref_recon_slot >= 0 && jobs[i].recon_slot == jobs[i].ref_recon_slot);
     // a refused call leaves the context as it found it: the call before is not settled, no parity flipped, no staging written
-    OPCHK(dec_plan(c, c->dec_plan, njobs, jobs, false));
+    OPCHK(dec_plan(c, c->dec_plan, njobs, jobs, once));
     OPCHK(dec_resolve(c));                               // the call before may have to be decoded again first (its pictures are references)
     return decode_impl(c, c->dec_plan, jobs);
 }

@@ -165,6 +165,48 @@ def test_bmc_matches_ref(ref, orc, w, h, fmt):
         A.check_ref(k + "/frame_add", ia.raw() if ref else None, ib.raw())
 
 
+def _mc_op_cases():
+    import mc_cases as M
+    return M.op_cases()
+
+
+@pytest.mark.parametrize("case", range(len(_mc_op_cases())), ids=["%s-%s-%d" % (g.name, r, s) for g, r, s in _mc_op_cases()])
+def test_bmc_built_fields_match_ref(ref, orc, case):
+    """the operator cases of tests/mc_cases.py: block sizes of the caller's choosing (test_bmc_matches_ref has those of block_dims
+    alone), vectors on, one inside and beyond every clamp limit, every submask, odd clipped blocks.  The pixels mc_cases marks
+    unpinned (taps outside the frame's allocation) are left out; the frames the operators write start zeroed"""
+    import mc_cases as M
+    geo, recipe, seed = _mc_op_cases()[case]
+    w, h, fmt = geo.w, geo.h, geo.fmt
+    rng = np.random.default_rng(4000 + case)
+    mv, _ = M.build_field(geo, recipe, seed)
+    keep = M.raw_mask(geo, M.unpinned_masks(geo, mv))
+    mvp = mv.ctypes.data_as(C.POINTER(A.MV))
+    meta = A.Meta(w, h, fmt, 30, 1, 1, 1)
+    prm = A.Params(C.pointer(meta), 1, 1, geo.bw, geo.bh, geo.nbh, geo.nbv)
+    extend = ref.dsv_extend_frame if ref else orc.orc_frame_extend
+    key = "bmc_built_%s_%s_%d" % (geo.name, recipe, seed)
+    reff = mk_frame_with(rng, w, h, fmt, smooth=False, extend_with=extend)
+    inp = mk_frame_with(rng, w, h, fmt, smooth=False, extend_with=extend)
+    A.known_answer(key + "/ref_frame", reff.raw())
+    A.known_answer(key + "/input", inp.raw())
+    ia, ib = A.BorderedFrame(w, h, fmt), A.BorderedFrame(w, h, fmt)
+    ia.buf[:] = inp.buf
+    ib.buf[:] = inp.buf
+    da, db = A.BorderedFrame(w, h, fmt), A.BorderedFrame(w, h, fmt)
+    if ref:
+        ref.dsv_sub_pred(mvp, C.byref(prm), da.ptr(), ia.ptr(), reff.ptr())
+    orc.orc_sub_pred(mvp, C.byref(prm), db.ptr(), ib.ptr(), reff.ptr())
+    A.check_ref(key + "/pred", da.raw()[keep] if ref else None, db.raw()[keep], "prediction differs")
+    A.check_ref(key + "/resid", ia.raw()[keep] if ref else None, ib.raw()[keep], "residual differs")
+    oa, ob = A.BorderedFrame(w, h, fmt), A.BorderedFrame(w, h, fmt)
+    ia.buf[:] = ib.buf                                    # (one residual for both: the unpinned pixels of the two may differ)
+    if ref:
+        ref.dsv_add_pred(mvp, C.byref(prm), ia.ptr(), oa.ptr(), reff.ptr())
+    orc.orc_add_pred(mvp, C.byref(prm), ib.ptr(), ob.ptr(), reff.ptr())
+    A.check_ref(key + "/add_pred", oa.raw()[keep] if ref else None, ob.raw()[keep])
+
+
 def test_frame_ops_match_ref(ref, orc):
     rng = np.random.default_rng(5)
     for (w, h, fmt) in [(352, 288, A.SUBSAMP_420), (101, 77, A.SUBSAMP_420), (64, 48, A.SUBSAMP_444)]:
