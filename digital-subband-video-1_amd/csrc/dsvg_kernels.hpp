@@ -35,6 +35,12 @@ struct HmeArgs {
     unsigned *csum;
     int levels, nxb, nyb, nblk, blk_w, blk_h;
 };
+// HmeArgs.deep_r: a level-0 vector's reach (k_hme.hip, `deep`: 2^(levels+1) - 1 full pixels) + the nine-point search, half-pel lattice, window
+// slack; and the ring of a luma-in-place frame's bordered copy that the blocks nearer an edge can touch: a block and twice deep_r in from
+// each edge, in 16-pixel columns / 4-row groups (k_unpack, slot-table bit 29)
+static inline int hme_deep_r(int levels) { return (2 << levels) + 8; }
+static inline int hme_ring_x16(int blk_w, int deep_r) { return (blk_w + 2 * deep_r + 15) / 16; }
+static inline int hme_ring_y4(int blk_h, int deep_r) { return (blk_h + 2 * deep_r + 3) / 4; }
 
 // k_sbt.hip
 int  sbt_tail_supported(const SbtGeo &g);

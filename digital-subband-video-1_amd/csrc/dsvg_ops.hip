@@ -383,10 +383,13 @@ extern "C" void dsvg_set_allocator(void *(*alloc_fn)(int), void (*free_fn)(void 
     g_op_free = alloc_fn && free_fn ? free_fn : dsv_free;
 }
 
-extern "C" int dsvg_op_hme(dsvg_hme *h, int *intra_pct)
+extern "C" int dsvg_op_hme(dsvg_hme *h, int *intra_pct) { return dsvg_op_hme_ex(h, intra_pct, 0u); }
+
+extern "C" int dsvg_op_hme_ex(dsvg_hme *h, int *intra_pct, unsigned flags)
 {
     if (!h || !h->params || !h->params->vidmeta) { dsvg_set_error("null argument"); return DSVG_ERR_ARG; }
     if (h->levels < 0 || h->levels > DSVG_MAX_PYRAMID) { dsvg_set_error("bad level count"); return DSVG_ERR_ARG; }
+    if (flags & ~(DSVG_HME_TABLE | DSVG_HME_IN_CLIP)) { dsvg_set_error("unknown flags %#x", flags); return DSVG_ERR_ARG; }
     OpScope S; OPCHK(S.init());
     const dsvg_params *p = h->params;
     const int nblk = p->nblocks_h * p->nblocks_v;
@@ -399,9 +402,33 @@ extern "C" int dsvg_op_hme(dsvg_hme *h, int *intra_pct)
         OPCHK(layout_from_host(Lr, h->ref[l], &br_, &nr));
         if (!same_layout(Ls, Lr)) { dsvg_set_error("src/ref layouts differ at level %d", l); return DSVG_ERR_ARG; }
         uint8_t *slab; OPCHK(S.slab(&slab, 2 * Ls.pitch + 4096));
+        A.L[l] = Ls; A.slab[l] = slab;
+        if (l == 0 && (flags & DSVG_HME_IN_CLIP)) {
+            // luma in place, as a batch context arranges it (dsvg_pipe.hip: slot_y, deep_r, ring_x16 / ring_y4): both luma planes packed, and bordered
+            // copies whose luma inside the ring holds what the search must never read -- the complement of the picture
+            const int w = Ls.w[0], hh = Ls.h[0];
+            if ((w % 16) || (hh % 4)) { dsvg_set_error("luma in place needs width %% 16 == 0 and height %% 4 == 0 (%dx%d)", w, hh); return DSVG_ERR_UNSUPPORTED; }
+            A.deep_r = hme_deep_r(h->levels);
+            const int rx = 16 * hme_ring_x16(A.blk_w, A.deep_r), ry = 4 * hme_ring_y4(A.blk_h, A.deep_r);
+            uint8_t *packed; OPCHK(S.slab(&packed, 2 * (size_t)w * hh + 4096));
+            unsigned long long hy[2], *dy; OPCHK(S.dev(&dy, 2));
+            const uint8_t *base[2] = {bs_, br_}; const size_t nb[2] = {ns, nr};
+            const dsvg_frame *fr[2] = {h->src[0], h->ref[0]};
+            for (int k = 0; k < 2; k++) {
+                std::vector<uint8_t> copy(base[k], base[k] + nb[k]);
+                uint8_t *y0 = copy.data() + Ls.off[0];
+                for (int y = ry; y < hh - ry; y++)
+                    for (int x = rx; x < w - rx; x++) y0[(size_t)y * Ls.stride[0] + x] ^= 0xff;
+                HIPCHK(hipMemcpy(slab + (size_t)k * Ls.pitch, copy.data(), nb[k], hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy2D(packed + (size_t)k * w * hh, (size_t)w, fr[k]->planes[0].data, (size_t)Ls.stride[0], (size_t)w, (size_t)hh, hipMemcpyHostToDevice));
+                hy[k] = (unsigned long long)(uintptr_t)(packed + (size_t)k * w * hh);
+            }
+            HIPCHK(hipMemcpyAsync(dy, hy, sizeof(hy), hipMemcpyHostToDevice, S.st));
+            A.slot_y = dy;
+            continue;
+        }
         HIPCHK(hipMemcpyAsync(slab, bs_, ns, hipMemcpyHostToDevice, S.st));
         HIPCHK(hipMemcpyAsync(slab + Ls.pitch, br_, nr, hipMemcpyHostToDevice, S.st));
-        A.L[l] = Ls; A.slab[l] = slab;
     }
     int *dslots; OPCHK(S.dev(&dslots, 2));
     const int slots[2] = {0, 1};
@@ -424,6 +451,7 @@ extern "C" int dsvg_op_hme(dsvg_hme *h, int *intra_pct)
     OPCHK(S.dev(&A.mvf, (size_t)(h->levels + 1) * nblk));
     OPCHK(S.dev(&A.aux_tex, (size_t)nblk));
     OPCHK(S.dev(&A.aux_var, (size_t)nblk));
+    if (flags & DSVG_HME_TABLE) OPCHK(S.dev(&A.csum, (size_t)2 * nblk * 4));         // [slot][block][4]: launch_hme plans with k_hme_csum's table
     launch_hme(S.st, A, 1);
     for (int l = 0; l <= h->levels; l++) h->mvf[l] = nullptr;
     auto drop = [&](int rc) { for (int l = 0; l <= h->levels; l++) { if (h->mvf[l]) g_op_free(h->mvf[l]); h->mvf[l] = nullptr; } return rc; };

@@ -678,9 +678,9 @@ static LoadGeo load_geo(const HmeArgs &A, const Slab *slabs)
     G.c_alike = L0.w[1] == L0.w[2] && L0.h[1] == L0.h[2] && L0.stride[1] == L0.stride[2];
     G.l2_dword = A.levels >= 2 && (A.L[2].stride[0] & 3) == 0 && (A.L[2].off[0] & 3) == 0 && (A.L[2].pitch & 3) == 0;
     G.sum_dword = (LT.stride[0] & 3) == 0 && (LT.off[0] & 3) == 0 && (LT.pitch & 3) == 0 && (!slabs || ((uintptr_t)slabs[A.levels].p & 3) == 0);
-    const int deep_r = (2 << A.levels) + 8;         // a level-0 vector's reach (k_hme.hip, `deep`) + the nine-point search, half-pel lattice, window slack
-    G.ring_x16 = (A.blk_w + 2 * deep_r + 15) / 16;
-    G.ring_y4 = (A.blk_h + 2 * deep_r + 3) / 4;
+    const int deep_r = hme_deep_r(A.levels);
+    G.ring_x16 = hme_ring_x16(A.blk_w, deep_r);
+    G.ring_y4 = hme_ring_y4(A.blk_h, deep_r);
     return G;
 }
 // The A/B switches of the source load: the process's own, read once -- this sits on the enqueue path.  plan_load itself takes them as
@@ -982,7 +982,7 @@ extern "C" int dsvg_ctx_create_blk(dsvg_ctx **out, int device, int width, int he
         c->cdirect_ok = load_chroma_in_place_geo(c->lgeo) && !getenv("DSV1_NO_CHROMA_IN_PLACE");
         // luma in place (round 5): the geometry must take the motion search's full-block body and k_unpack's fused pyramid levels 1 and 2
         // (the bordered copy is then read by the level-0 search alone), and the ring must leave an interior worth the trouble
-        c->deep_r = (2 << c->levels) + 8;               // a level-0 vector's reach (k_hme.hip, `deep`) + the nine-point search, half-pel lattice, window slack
+        c->deep_r = hme_deep_r(c->levels);
         c->ring_x16 = c->lgeo.ring_x16;
         c->ring_y4 = c->lgeo.ring_y4;
         c->ydirect_ok = c->cdirect_ok && load_luma_in_place_geo(c->lgeo) && !getenv("DSV1_NO_LUMA_IN_PLACE") && !getenv("DSV1_NO_FUSE_LEVEL2");

@@ -83,6 +83,16 @@ int dsvg_link_probe(int device, size_t bytes, int reps, double gbs[2]);
 /* dsv_add_pred bmc.c:333   */ int dsvg_op_add_pred(const dsvg_mv *mv, const dsvg_params *p, dsvg_frame *dif, dsvg_frame *out, const dsvg_frame *ref);
 /* dsv_frame_add bmc.c:304  */ int dsvg_op_frame_add(dsvg_frame *dst, const dsvg_frame *src);
 /* dsv_hme      hme.c:730   */ int dsvg_op_hme(dsvg_hme *hme, int *intra_pct); /* mvf[0..levels] from dsv_alloc: the caller frees them with dsv_free, as dsv_encoder.c:239-244 does */
+/* dsvg_op_hme with the two arrangements a batch context gives the level-0 search (flags 0: dsvg_op_hme itself):
+ *   DSVG_HME_TABLE    the chroma variance test of full blocks reads k_hme_csum's table instead of fetching the chroma blocks per block;
+ *   DSVG_HME_IN_CLIP  both level-0 luma planes are also given packed (row stride = the picture's width), as a caller's clip holds them: a
+ *                     block's source rows come from there unless its statistics window leaves the picture, its reference rows when it lies
+ *                     (2 << levels) + 8 pixels or more from every edge.  Of the bordered copies the search may then read only the border and
+ *                     a ring of a block and twice that distance in from each edge: the luma samples inside the ring are replaced by their
+ *                     complement on the device, so a read from the wrong copy changes the result.  Needs width % 16 == 0, height % 4 == 0. */
+#define DSVG_HME_TABLE   1u
+#define DSVG_HME_IN_CLIP 2u
+int dsvg_op_hme_ex(dsvg_hme *hme, int *intra_pct, unsigned flags);
 /* the allocator behind memory the operator calls hand to their caller (the motion fields above).  Default (or NULLs): this library's dsv_alloc /
  * dsv_free.  A build that keeps the reference's own dsv.c passes ITS pair, so that its dsv_free -- which steps back over a 16-byte header when
  * DSV_MEMORY_STATS is on, dsv.c:41-66 -- gets blocks its dsv_alloc made (oracle/opswap_shim.c does). */

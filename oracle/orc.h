@@ -136,6 +136,31 @@ void orc_frame_add(orc_frame *dst, const orc_frame *src);
 int  orc_hme_run(orc_hme *h);      /* fills h->mvf[0..levels] (calloc'd; caller frees), returns intra % */
 void orc_mv_pred(const orc_mv *vecs, const orc_params *p, int x, int y, int *px, int *py); /* dsv.c:200 */
 
+/* Per-block trace of the search: what refine_level (hme.c:378-728) saw and decided at one (level, block).  A second interface beside
+ * the ORC_COV_* counters below: orc_hme_run_trace(h, recs, cap) is orc_hme_run(h) that also fills recs[level * nblocks + i + j * nblocks_h]
+ * (cap >= (levels + 1) * nblocks records, or nothing is traced).  All members are int32, so that a record is 80 plain ints. */
+typedef struct {
+    int32_t visited;            /* 0: not a block of this level's grid; 1: searched; 2: outside the picture (zero vector, hme.c:441-444) */
+    int32_t level, i, j, bx, by, bw, bh;
+    int32_t par[5], par_on[5];  /* the five raw parent vectors (int16 x | y << 16; 0 where off the grid) and the on-grid flags */
+    int32_t n, cand[6];         /* candidates after de-duplication: cand[0] = 0 */
+    int32_t src_ok, valid;      /* the source block passes invalid_block; bit k: candidate k was scored */
+    int32_t cand_sad[6];        /* -1 where not scored */
+    int32_t pick;
+    int32_t sx, sy, cx, cy;     /* start vector (this level's pixels) before and after the clamp of hme.c:512-517 */
+    int32_t nine[9], nine_k;
+    int32_t best;               /* the winning SAD of the nine */
+    int32_t did_hp, hp_thr;     /* level 0: the half-pel search ran; the scaled full-pel SAD it had to beat */
+    int32_t hp[8], hp_k;        /* hp_k = -1: kept full-pel */
+    int32_t sat[6];             /* a sample of a compared half-pel window was clipped: H lo, H hi, V lo, V hi, D lo, D hi */
+    int32_t wrap[3];            /* sum * sum passed 2^32 in the variance of: the luma block, the zero-motion block, a chroma block (-1: chroma test not reached) */
+    int32_t src_var_neg;
+    int32_t cov_lo, cov_hi;     /* bit b of (cov_hi << 32 | cov_lo): this block counted ORC_COV_<b> */
+    int32_t mvx, mvy;           /* the vector written (level 0: half-pel units) */
+    int32_t rsv[6];
+} orc_hme_trace;
+int  orc_hme_run_trace(orc_hme *h, orc_hme_trace *recs, int cap);
+
 /* ---- session layer (dsv_encoder.c / dsv_decoder.c / dsv_main.c mapping) ---------------- */
 typedef struct {
     orc_meta meta;

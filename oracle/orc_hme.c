@@ -41,8 +41,16 @@ static int out_of_frame(const orc_frame *f, int x, int y, int w, int h)   /* inv
     return x < -b || y < -b || x + w > f->width + b || y + h > f->height + b;
 }
 
-/* 32x32 lattice of the 16x16 patch at `ref`: even rows F H F H.., odd rows V D V D.. */
-static void build_lattice(uint8_t *lat, const uint8_t *ref, int rs)
+/* trace only: *c (or NULL) gets 1 where the sample was clipped at 0, 2 where at 255 */
+static uint8_t sat8c(int v, uint8_t *c)
+{
+    if (c) *c = (uint8_t)(v < 0 ? 1 : (v > 255 ? 2 : 0));
+    return sat8(v);
+}
+
+/* 32x32 lattice of the 16x16 patch at `ref`: even rows F H F H.., odd rows V D V D..; clip: the same lattice of sat8c's flags */
+
+static void build_lattice(uint8_t *lat, const uint8_t *ref, int rs, uint8_t *clip)
 {
     int16_t hrow[(WIN + 2 + 4) * (WIN + 2)];
     for (int r = 0; r < WIN + 2 + 4; r++)
@@ -51,15 +59,25 @@ static void build_lattice(uint8_t *lat, const uint8_t *ref, int rs)
     for (int j = 0; j < WIN + 2; j++) {
         const uint8_t *row = ref + (ptrdiff_t)j * rs;
         uint8_t *e = lat + (2 * j) * LAT, *o = e + LAT;
+        uint8_t *ce = clip ? clip + (2 * j) * LAT : NULL, *co = clip ? ce + LAT : NULL;
         for (int i = 0; i < WIN + 2; i++) {
             const int16_t *m = hrow + j * (WIN + 2) + i;
             int d = 9 * (m[WIN + 2] + m[2 * (WIN + 2)]) - (m[0] + m[3 * (WIN + 2)]);
             e[2 * i] = row[i];
-            e[2 * i + 1] = sat8((tap_h(row + i) + 8) >> 4);
-            o[2 * i] = sat8((tap_v(row + i, rs) + 8) >> 4);
-            o[2 * i + 1] = sat8((d + 128) >> 8);
+            e[2 * i + 1] = sat8c((tap_h(row + i) + 8) >> 4, clip ? ce + 2 * i + 1 : NULL);
+            o[2 * i] = sat8c((tap_v(row + i, rs) + 8) >> 4, clip ? co + 2 * i : NULL);
+            o[2 * i + 1] = sat8c((d + 128) >> 8, clip ? co + 2 * i + 1 : NULL);
         }
     }
+}
+
+/* trace only: does sum * sum pass 2^32 in the variance of this block (the product wraps mod 2^32, hme.c:247-267) */
+static int var_wraps(const uint8_t *p, int s, int w, int h)
+{
+    unsigned long long s1 = 0;
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) s1 += p[(size_t)y * s + x];
+    return s1 * s1 >= (1ull << 32);
 }
 
 static int lattice_sad(const uint8_t *a, int as, const uint8_t *l)
@@ -175,7 +193,10 @@ static const int HP_X[8] = { 1, -1, 0, 0, -1, 1, -1, 1 };          /* hme.c:426-
 static const int HP_Y[8] = { 0, 0, 1, -1, -1, -1, 1, 1 };
 static const int PARENT_OFF[5][2] = { {0, 0}, {-2, 0}, {2, 0}, {0, -2}, {0, 2} };   /* hme.c:454 */
 
-static int refine(orc_hme *hme, int level)
+#define COV(b) do { int b_ = (b); orc_cov[b_]++; \
+                    if (T) { if (b_ < 32) T->cov_lo |= (int32_t)(1u << b_); else T->cov_hi |= (int32_t)(1u << (b_ - 32)); } } while (0)
+
+static int refine(orc_hme *hme, int level, orc_hme_trace *trace)
 {
     const orc_params *prm = hme->params;
     const orc_frame *src = hme->src[level], *ref = hme->ref[level];
@@ -193,6 +214,8 @@ static int refine(orc_hme *hme, int level)
     for (int j = 0; j < nyb; j += step) {
         for (int i = 0; i < nxb; i += step) {
             const int bx = (i * BW) >> level, by = (j * BH) >> level;
+            orc_hme_trace *T = trace ? &trace[(size_t)level * nxb * nyb + i + j * nxb] : NULL;
+            if (T) { T->visited = 2; T->level = level; T->i = i; T->j = j; T->bx = bx; T->by = by; }
             if (bx >= src->width || by >= src->height)
                 continue;                                   /* stays a zero inter vector */
             int remw = sp->w - bx, remh = sp->h - by;
@@ -212,6 +235,7 @@ static int refine(orc_hme *hme, int level)
                     int x = pi + PARENT_OFF[m][0] * step, y = pj + PARENT_OFF[m][1] * step;
                     if (x < 0 || x >= nxb || y < 0 || y >= nyb) continue;
                     int32_t v = parent[x + y * nxb].u.all;
+                    if (T) { T->par[m] = v; T->par_on[m] = 1; }
                     if (!v) continue;
                     int dup = 0;
                     for (int k = 0; k < n; k++) dup |= (cand[k] == v);
@@ -219,6 +243,12 @@ static int refine(orc_hme *hme, int level)
                 }
             }
             int pick = n - 1;
+            if (T) {
+                T->visited = 1; T->bw = bw; T->bh = bh; T->n = n;
+                for (int k = 0; k < n; k++) T->cand[k] = cand[k];
+                for (int k = 0; k < 6; k++) T->cand_sad[k] = -1;
+                T->src_ok = !out_of_frame(src, bx, by, bw, bh);
+            }
             if (n > 1) {
                 int best_score = INT_MAX;
                 for (int k = 0; k < n; k++) {
@@ -228,20 +258,24 @@ static int refine(orc_hme *hme, int level)
                     if (out_of_frame(ref, bx + dx, by + dy, bw, bh)) continue;
                     int sc = sad(sblk, sp->stride, rp->data + (bx + dx) + (ptrdiff_t)(by + dy) * rp->stride,
                                  rp->stride, bw, bh);
+                    if (T) { T->valid |= 1 << k; T->cand_sad[k] = sc; }
                     if (best_score > sc) { best_score = sc; pick = k; }
                 }
             }
             orc_mv start; start.u.all = cand[pick];
             int dx = clampi(start.u.mv.x >> level, -bw - bx, ref->width - bx);
             int dy = clampi(start.u.mv.y >> level, -bh - by, ref->height - by);
+            if (T) { T->pick = pick; T->sx = start.u.mv.x >> level; T->sy = start.u.mv.y >> level; T->cx = dx; T->cy = dy; }
 
             int best = INT_MAX, m = 0;
             for (int k = 0; k < 9; k++) {
                 int sc = sad(sblk, sp->stride,
                              rp->data + (bx + dx + FP_X[k]) + (ptrdiff_t)(by + dy + FP_Y[k]) * rp->stride,
                              rp->stride, bw, bh);
+                if (T) T->nine[k] = sc;
                 if (best > sc) { best = sc; m = k; }
             }
+            if (T) { T->nine_k = m; T->best = best; T->hp_k = -1; T->wrap[2] = -1; }
             dx += FP_X[m];
             dy += FP_Y[m];
 
@@ -249,6 +283,7 @@ static int refine(orc_hme *hme, int level)
             mv->mode = 0;
             mv->u.mv.x = (int16_t)(dx << level);
             mv->u.mv.y = (int16_t)(dy << level);
+            if (T) { T->mvx = mv->u.mv.x; T->mvy = mv->u.mv.y; }
             if (level != 0) continue;
 
             /* ---------------- level 0: half-pel refinement ---------------- */
@@ -262,16 +297,31 @@ static int refine(orc_hme *hme, int level)
                 uint8_t lat[(LAT + 2) * (LAT + 2)];
                 int best_hp = (int)((unsigned)(best * (WIN * WIN)) / yarea);
                 const uint8_t *rwin = rp->data + (wx + mv->u.mv.x) + (ptrdiff_t)(wy + mv->u.mv.y) * rp->stride;
-                build_lattice(lat, rwin - 1 - rp->stride, rp->stride);
+                uint8_t clip[(LAT + 2) * (LAT + 2)];
+                if (T) memset(clip, 0, sizeof clip);
+                build_lattice(lat, rwin - 1 - rp->stride, rp->stride, T ? clip : NULL);
                 const uint8_t *centre = lat + 2 + 2 * LAT;
                 int hm = -1;
+                if (T) { T->did_hp = 1; T->hp_thr = best_hp; }
                 for (int k = 0; k < 8; k++) {
                     int sc = lattice_sad(swin, sp->stride, centre + HP_X[k] + HP_Y[k] * LAT);
+                    if (T) {
+                        /* the plane of candidate k: H (x odd), V (y odd), D (both) */
+                        const int pl = (HP_X[k] & 1) ? ((HP_Y[k] & 1) ? 2 : 0) : 1;
+                        const uint8_t *c = clip + 2 + 2 * LAT + HP_X[k] + HP_Y[k] * LAT;
+                        T->hp[k] = sc;
+                        for (int y = 0; y < WIN; y++)
+                            for (int x = 0; x < WIN; x++) {
+                                const int f = c[2 * x + y * 2 * LAT];
+                                if (f) T->sat[2 * pl + f - 1] = 1;
+                            }
+                    }
                     if (best_hp > sc) { best_hp = sc; hm = k; }
                 }
+                if (T) T->hp_k = hm;
                 mv->u.mv.x = (int16_t)(mv->u.mv.x << 1);
                 mv->u.mv.y = (int16_t)(mv->u.mv.y << 1);
-                orc_cov[hm >= 0 ? ORC_COV_HP_REFINED : ORC_COV_HP_KEPT_FULLPEL]++;
+                COV(hm >= 0 ? ORC_COV_HP_REFINED : ORC_COV_HP_KEPT_FULLPEL);
                 if (hm >= 0) {
                     const uint8_t *l = centre + HP_X[hm] + HP_Y[hm] * LAT;
                     mv->u.mv.x = (int16_t)(mv->u.mv.x + HP_X[hm]);
@@ -282,7 +332,7 @@ static int refine(orc_hme *hme, int level)
                     best = (int)((unsigned)best_hp * yarea / (WIN * WIN));
                 }
             } else {
-                orc_cov[ORC_COV_HP_SKIPPED]++;
+                COV(ORC_COV_HP_SKIPPED);
                 mv->u.mv.x = (int16_t)(mv->u.mv.x << 1);
                 mv->u.mv.y = (int16_t)(mv->u.mv.y << 1);
             }
@@ -299,6 +349,12 @@ static int refine(orc_hme *hme, int level)
             unsigned thr_tex = 1;
             int thr_var = WIN * WIN;
 
+            if (T) {
+                T->mvx = mv->u.mv.x; T->mvy = mv->u.mv.y;
+                T->wrap[0] = var_wraps(sblk, sp->stride, bw, bh);
+                T->wrap[1] = var_wraps(zref, rp->stride, bw, bh);
+                T->src_var_neg = src_var < 0;
+            }
             mv->lo_tex = (luma_tex <= 2);
             mv->lo_var = (luma_var < yareasq);
 
@@ -315,9 +371,9 @@ static int refine(orc_hme *hme, int level)
                 if (nb->mode == 0 && !nb->lo_tex && !nb->lo_var) { thr_var *= WIN / 4; thr_tex++; }
             }
             mv->high_detail = (luma_tex > thr_tex && src_var > thr_var);
-            orc_cov[(mv->high_detail ? ORC_COV_NB0_HD : ORC_COV_NB0_PLAIN) + (int)thr_tex - 1]++;
-            orc_cov[mv->lo_tex ? ORC_COV_LO_TEX : (mv->lo_var ? ORC_COV_LO_VAR : ORC_COV_LO_NEITHER)]++;
-            if (mv->lo_tex && mv->lo_var) orc_cov[ORC_COV_LO_VAR]++;
+            COV((mv->high_detail ? ORC_COV_NB0_HD : ORC_COV_NB0_PLAIN) + (int)thr_tex - 1);
+            COV(mv->lo_tex ? ORC_COV_LO_TEX : (mv->lo_var ? ORC_COV_LO_VAR : ORC_COV_LO_NEITHER));
+            if (mv->lo_tex && mv->lo_var) COV(ORC_COV_LO_VAR);
 
             /* ---------------- intra decision ---------------- */
             int want_intra = 0;
@@ -332,15 +388,21 @@ static int refine(orc_hme *hme, int level)
                 int cbw = bw >> ORC_HSHIFT(fmt), cbh = bh >> ORC_VSHIFT(fmt);
                 unsigned cs = chroma_maxvar(src->planes, cbx, cby, cbw, cbh);
                 unsigned cr = chroma_maxvar(ref->planes, cbx, cby, cbw, cbh);
+                if (T) {
+                    T->wrap[2] = 0;
+                    for (int c = 1; c <= 2; c++)
+                        T->wrap[2] |= var_wraps(src->planes[c].data + cbx + (ptrdiff_t)cby * src->planes[c].stride, src->planes[c].stride, cbw, cbh) |
+                                      var_wraps(ref->planes[c].data + cbx + (ptrdiff_t)cby * ref->planes[c].stride, ref->planes[c].stride, cbw, cbh);
+                }
                 if (cr > 4 * cs) want_intra = 6;
             }
-            orc_cov[want_intra ? ORC_COV_INTRA_ZEROVAR + want_intra - 1 : ORC_COV_INTRA_NONE]++;
+            COV(want_intra ? ORC_COV_INTRA_ZEROVAR + want_intra - 1 : ORC_COV_INTRA_NONE);
             if (!want_intra) continue;
-            if (intra_unrepresentable(sblk, sp->stride, zref, rp->stride, bw, bh)) { orc_cov[ORC_COV_VETO_TAKEN]++; continue; }
-            orc_cov[ORC_COV_VETO_NOT_TAKEN]++;
+            if (intra_unrepresentable(sblk, sp->stride, zref, rp->stride, bw, bh)) { COV(ORC_COV_VETO_TAKEN); continue; }
+            COV(ORC_COV_VETO_NOT_TAKEN);
 
             mv->submask = 0xF;
-            orc_cov[src_tex > 1 ? ORC_COV_QUAD_VOTE : ORC_COV_LOWTEX_ALL_INTRA]++;
+            COV(src_tex > 1 ? ORC_COV_QUAD_VOTE : ORC_COV_LOWTEX_ALL_INTRA);
             if (src_tex > 1) {
                 const int qw = bw / 2, qh = bh / 2;
                 for (int k = 0; k < 4; k++) {
@@ -350,7 +412,7 @@ static int refine(orc_hme *hme, int level)
                         mv->submask &= (uint8_t)~(1u << k);
                 }
             }
-            if (src_tex > 1) orc_cov[ORC_COV_SUBMASK0 + mv->submask]++;
+            if (src_tex > 1) COV(ORC_COV_SUBMASK0 + mv->submask);
             if (mv->submask) {
                 mv->mode = 1;
                 nintra++;
@@ -360,12 +422,19 @@ static int refine(orc_hme *hme, int level)
     return nintra;
 }
 
-int orc_hme_run(orc_hme *h)
+#undef COV
+
+int orc_hme_run_trace(orc_hme *h, orc_hme_trace *recs, int cap)
 {
+    const int nblk = h->params->nblocks_h * h->params->nblocks_v;
     int nintra = 0;
-    for (int l = h->levels; l >= 0; l--) nintra = refine(h, l);
-    return nintra * 100 / (h->params->nblocks_h * h->params->nblocks_v);
+    if (recs && cap >= (h->levels + 1) * nblk) memset(recs, 0, (size_t)(h->levels + 1) * nblk * sizeof(*recs));
+    else recs = NULL;
+    for (int l = h->levels; l >= 0; l--) nintra = refine(h, l, recs);
+    return nintra * 100 / nblk;
 }
+
+int orc_hme_run(orc_hme *h) { return orc_hme_run_trace(h, NULL, 0); }
 
 static int pick_pred(int left, int top, int topleft)
 {
