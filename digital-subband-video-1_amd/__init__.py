@@ -917,7 +917,6 @@ class Batch:
     def _opened(self, cfg):
         self.ctx = self.L.dsv1_batch_ctx(self.h)
         m = cfg.vidmeta
-        self.frame_bytes = m.width * m.height + 2 * _chroma_size(m.width, m.height, m.subsamp)
         self.width, self.height, self.fmt = m.width, m.height, m.subsamp
         self._dev = []
         self._pin = []
@@ -935,13 +934,29 @@ class Batch:
                 self.nsources, "streams" if self.nsources == self.nstreams else "sources", fin, self.frame_bytes, a.size))
         return a
 
+    _SOURCE_INPUT = "dsv1_batch_source_input"
+
+    def _source_input(self):
+        """(frames per source and call, bytes per frame, (width, height) of the raw picture) a call must bring, straight from the
+        session's source chain (dsv1_batch_source_input, dsv1_resladder_source_input): nothing of it is kept here"""
+        v, fb = (_C.c_int * 3)(), _C.c_size_t()
+        _chk(getattr(self.L, self._SOURCE_INPUT)(self.h, v, _C.byref(fb)), self._SOURCE_INPUT)
+        return v[0], fb.value, (v[1], v[2])
+
     @property
     def in_frames(self):
         """input frames per source and call: frames_per_call, half of it behind a field-rate deinterlacer, 5/4 of it in front of the
         inverse telecine"""
-        if getattr(self, "_ivtc", False):
-            return self.F // 4 * 5
-        return self.F // 2 if getattr(self, "_deint_field", False) else self.F
+        return self._source_input()[0] if getattr(self, "h", None) else self.F
+
+    @property
+    def frame_bytes(self):
+        """bytes from frame to frame of the clips that come in: the source format's, at in_dims"""
+        return self._source_input()[1] if getattr(self, "h", None) else self._frame_bytes
+
+    @frame_bytes.setter
+    def frame_bytes(self, n):
+        self._frame_bytes = n                   # (an object without a session: the tests of the length check build one)
 
     def set_source_ivtc(self, iv):
         """from the next submit on the clips are 3:2 pulled-down film and inverse telecined on the GPU as Ivtc iv says, behind the source
@@ -949,7 +964,6 @@ class Batch:
         Between batches only; forgets every source's state.  frames_per_call counts coded pictures and must be a multiple of 4: a call
         takes in_frames = 5 * frames_per_call / 4 frames per source."""
         _chk(self.L.dsv1_batch_set_source_ivtc(self.h, _C.byref(iv) if iv is not None else None), "dsv1_batch_set_source_ivtc")
-        self._ivtc = iv is not None
 
     def ivtc_reset(self, source=-1):
         """a discontinuity: the next frame of `source` (-1: every source) is a stream's first picture (dsv1_batch_ivtc_reset)"""
@@ -960,7 +974,6 @@ class Batch:
         conversion (dsv1_batch_set_source_deinterlace); None switches it off.  Between batches only; forgets every source's history.
         frames_per_call counts coded pictures: with DEINT_FIELD a call takes in_frames = frames_per_call / 2 frames per source."""
         _chk(self.L.dsv1_batch_set_source_deinterlace(self.h, _C.byref(di) if di is not None else None), "dsv1_batch_set_source_deinterlace")
-        self._deint_field = di is not None and di.mode == DEINT_FIELD
 
     def deinterlace_reset(self, source=-1):
         """a discontinuity: the next frame of `source` (-1: every source) is deinterlaced as a stream's first (dsv1_batch_deinterlace_reset)"""
@@ -1001,8 +1014,6 @@ class Batch:
         and no source format, RGB format, deinterlacer or noise filter set: those are set AFTER it and resolve at the input geometry.
         The input-length check follows."""
         _chk(self.L.dsv1_batch_set_source_reframe(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_reframe")
-        self._in_dims = self._oriented_dims = (rf.in_w, rf.in_h) if rf is not None else (self.width, self.height)
-        self.frame_bytes = self._in_dims[0] * self._in_dims[1] + 2 * _chroma_size(self._in_dims[0], self._in_dims[1], self.fmt)
 
     def set_source_orient(self, orient):
         """from the next submit on the clips are oriented on the GPU by code `orient` (Orient.*; dsv1_batch_set_source_orient) behind
@@ -1011,15 +1022,12 @@ class Batch:
         with nothing in flight and no source format, RGB format, deinterlacer, inverse telecine or noise filter set: those are set
         AFTER it and resolve at the raw geometry.  The input-length check follows."""
         _chk(self.L.dsv1_batch_set_source_orient(self.h, orient), "dsv1_batch_set_source_orient")
-        mw, mh = getattr(self, "_oriented_dims", (self.width, self.height))
-        self._in_dims = orient_dims(orient_inverse(orient), mw, mh)
-        self.frame_bytes = self._in_dims[0] * self._in_dims[1] + 2 * _chroma_size(self._in_dims[0], self._in_dims[1], self.fmt)
 
     @property
     def in_dims(self):
         """(width, height) of the frames that come in: the batch's geometry, or the input of the reframe set, turned back by the
         orientation set"""
-        return getattr(self, "_in_dims", (self.width, self.height))
+        return self._source_input()[2]
 
     def set_fnum(self, stream, fnum):
         self.L.dsv1_batch_set_fnum(self.h, stream, fnum)
@@ -1031,22 +1039,15 @@ class Batch:
         halved on the way; pf None then means packed planar 8-bit at src_subsamp."""
         if src_subsamp is None:
             _chk(self.L.dsv1_batch_set_source_format(self.h, _C.byref(pf) if pf is not None else None), "dsv1_batch_set_source_format")
-            src_subsamp = self.fmt
         else:
             _chk(self.L.dsv1_batch_set_source_format_sub(self.h, _C.byref(pf) if pf is not None else None, src_subsamp),
                  "dsv1_batch_set_source_format_sub")
-        iw, ih = self.in_dims
-        planar = iw * ih + 2 * _chroma_size(iw, ih, src_subsamp)
-        self.frame_bytes = pix_frame_bytes(pf, iw, ih, src_subsamp) if pf is not None else planar
 
     def set_source_rgb(self, rf):
         """from the next submit on, encode() / submit() take RGB clips of RgbFormat rf (dsv1_batch_set_source_rgb), converted on the
         GPU to the batch's subsampling; None switches back to packed planar 8-bit.  Between batches only; replaces a source format
         set before.  The input-length check follows."""
         _chk(self.L.dsv1_batch_set_source_rgb(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_rgb")
-        iw, ih = self.in_dims
-        planar = iw * ih + 2 * _chroma_size(iw, ih, self.fmt)
-        self.frame_bytes = rgb_frame_bytes(rf, iw, ih) if rf is not None else planar
 
     def dropped_recons(self):
         """(dropped, remedied): reference pictures coded without a reconstruction because nobody predicts from them / coded again
@@ -1718,6 +1719,104 @@ def submit_plan(q, src, st, luma, n_intra, prev=None):
             "jobs": [_fields(j) for j in jobs[:q.njobs]], "calls": [_fields(c) for c in calls[:q.ncalls]], "dropped": q.dropped}
 
 
+SC_NONE, SC_CONVERT, SC_LEVELS, SC_DEINTERLACE, SC_IVTC, SC_DENOISE, SC_ORIENT, SC_REFRAME, SC_OVERLAY = range(9)
+SC_SLOTS, SC_MAX_STEPS = 7, 8
+SC_OP_SET, SC_OP_RESET, SC_OP_SEEK = range(3)
+SC_CALLER, SC_UPLOAD = -1, -2
+
+
+class SrcChainState(_C.Structure):
+    """dsv1_srcchain_state: a session's source chain as plain data"""
+    _fields_ = [("nsrc", _C.c_int), ("F", _C.c_int), ("subsamp", _C.c_int), ("keep_lane", _C.c_int), ("ow", _C.c_int), ("oh", _C.c_int),
+                ("kind", _C.c_int * SC_SLOTS), ("conv_rgb", _C.c_int), ("conv_fb", _C.c_size_t), ("deint_mode", _C.c_int),
+                ("orient", _C.c_int), ("in_w", _C.c_int), ("in_h", _C.c_int), ("ov_clip", _C.c_int * 2)]
+
+
+class SrcChainReq(_C.Structure):
+    """dsv1_srcchain_req: one setter, reset or seek call, its numbers resolved"""
+    _fields_ = [("op", _C.c_int), ("kind", _C.c_int), ("set", _C.c_int), ("valid", _C.c_int), ("identity", _C.c_int), ("busy", _C.c_int),
+                ("mode", _C.c_int), ("w", _C.c_int), ("h", _C.c_int), ("out_w", _C.c_int), ("out_h", _C.c_int), ("source", _C.c_int),
+                ("frame_bytes", _C.c_size_t)]
+
+
+class SrcChainGeom(_C.Structure):
+    """dsv1_srcchain_geom: the three geometries of a chain state and what a call brings"""
+    _fields_ = [("w", _C.c_int), ("h", _C.c_int), ("mw", _C.c_int), ("mh", _C.c_int), ("ow", _C.c_int), ("oh", _C.c_int),
+                ("conv_frames", _C.c_int), ("frames_in", _C.c_int), ("lane", _C.c_int), ("fb", _C.c_size_t), ("mfb", _C.c_size_t),
+                ("ofb", _C.c_size_t), ("frame_in_bytes", _C.c_size_t), ("bytes_in", _C.c_size_t)]
+
+
+class SrcChainSetPlan(_C.Structure):
+    """dsv1_srcchain_set_plan: the answer to a request"""
+    _fields_ = [("rc", _C.c_int), ("text", _C.c_int), ("noop", _C.c_int), ("next", SrcChainState), ("g", SrcChainGeom),
+                ("alloc", _C.c_size_t * SC_SLOTS), ("free_", _C.c_int * SC_SLOTS), ("reset", _C.c_int * SC_SLOTS)]
+
+
+class SrcChainStep(_C.Structure):
+    """dsv1_srcchain_step: one enqueued step of a call"""
+    _fields_ = [("kind", _C.c_int), ("pos", _C.c_int), ("nframes", _C.c_int), ("src", _C.c_int), ("dst", _C.c_int),
+                ("bytes", _C.c_size_t), ("alloc", _C.c_size_t)]
+
+
+class SrcChainCallPlan(_C.Structure):
+    """dsv1_srcchain_call_plan: one call's clip through the chain"""
+    _fields_ = [("rc", _C.c_int), ("bypass", _C.c_int), ("nsteps", _C.c_int), ("out", _C.c_int), ("advance", _C.c_int),
+                ("upload", _C.c_size_t), ("step", SrcChainStep * SC_MAX_STEPS)]
+
+
+class SrcChainRefused(ValueError):
+    """the source chain refuses the request or the call: rc and text are what the session would return and log"""
+    def __init__(self, rc, row, text):
+        super().__init__("the source chain refuses (rc=%d): %s" % (rc, text))
+        self.rc, self.row, self.text = rc, row, text
+
+
+_SC = {}
+
+
+def _sc():
+    """the three source-chain plan entry points, bound once, and the table's rows"""
+    if not _SC:
+        L, P = lib(), _C.POINTER
+        L.dsv1_srcchain_plan_text.restype, L.dsv1_srcchain_plan_text.argtypes = _C.c_char_p, [_C.c_int]
+        L.dsv1_srcchain_plan_set.restype, L.dsv1_srcchain_plan_set.argtypes = _C.c_int, [P(SrcChainState), P(SrcChainReq), P(SrcChainSetPlan)]
+        L.dsv1_srcchain_plan_call.restype = _C.c_int
+        L.dsv1_srcchain_plan_call.argtypes = [P(SrcChainState), _C.c_int, _C.c_int, _C.c_int, P(SrcChainCallPlan)]
+        texts = []
+        while L.dsv1_srcchain_plan_text(len(texts)) is not None:
+            texts.append(L.dsv1_srcchain_plan_text(len(texts)).decode())
+        _SC.update(set=L.dsv1_srcchain_plan_set, call=L.dsv1_srcchain_plan_call, texts=texts)
+    return _SC
+
+
+def srcchain_plan_texts():
+    """the rows of the chain's refusal table (dsv1_srcchain_plan_text); row 0 (no refusal) is empty"""
+    return list(_sc()["texts"])
+
+
+def srcchain_plan_set(state, req):
+    """the plan of one setter, reset or seek call (dsv1_srcchain_plan_set), no device: a SrcChainSetPlan; SrcChainRefused where the
+    session refuses"""
+    out = SrcChainSetPlan()
+    out.text = -1
+    rc = _sc()["set"](_C.byref(state), _C.byref(req), _C.byref(out))
+    if rc and out.text < 0:
+        raise ValueError("not a request of the source chain: op %d of kind %d" % (req.op, req.kind))
+    if rc:
+        raise SrcChainRefused(rc, out.text, _SC["texts"][out.text])
+    return out
+
+
+def srcchain_plan_call(state, form, active, par=0):
+    """the plan of one call (dsv1_srcchain_plan_call), no device.  form: 0 host, 1 plain device clip, 2 held; active: the overlays
+    blend something in it.  A SrcChainCallPlan; SrcChainRefused for a chain without a lane"""
+    out = SrcChainCallPlan()
+    rc = _sc()["call"](_C.byref(state), form, 1 if active else 0, par, _C.byref(out))
+    if rc:
+        raise SrcChainRefused(rc, 0, "no lane: nothing is set")
+    return out
+
+
 def overlay_from_rgba(rgba, w, h, order, matrix, full_range, fmt, pitch=0):
     """an overlay bitmap's planes (numpy uint8: Y, U, V, A) from an RGB(A) image of w x h in memory order `order` (RGB_*), converted
     with `matrix` (MATRIX_*) at full or limited range to format fmt (dsv1_overlay_from_rgba).  Host only."""
@@ -2020,10 +2119,6 @@ class ResLadder:
                                                 frames_per_call, filt), "dsv1_resladder_open_src")
         self.ntot = sum(n for _, _, n in self.geoms)
         self.nstreams = self.L.dsv1_resladder_nstreams(self.h)
-        sfmt = fmt if src_subsamp is None else src_subsamp
-        self.frame_bytes = w * h + 2 * _chroma_size(w, h, sfmt) if src_format is None else pix_frame_bytes(src_format, w, h, sfmt)
-        if src_rgb is not None:
-            self.frame_bytes = rgb_frame_bytes(src_rgb, w, h)
         self.ctx = self.L.dsv1_batch_ctx(self.L.dsv1_resladder_batch(self.h, 0))
         self._dev, self._pin, self._pending = [], [], []
 
@@ -2051,13 +2146,13 @@ class ResLadder:
                 self.nsources, fin, self.frame_bytes, a.size))
         return a
 
-    in_frames = Batch.in_frames
+    _SOURCE_INPUT = "dsv1_resladder_source_input"
+    _source_input, in_frames, frame_bytes, in_dims = Batch._source_input, Batch.in_frames, Batch.frame_bytes, Batch.in_dims
 
     def set_deinterlace(self, di):
         """the sources are interlaced: deinterlace them on the GPU as Deint di says, behind the conversion and in front of the scales
         (dsv1_resladder_set_deinterlace); None switches it off.  Between calls only; contract as Batch.set_source_deinterlace."""
         _chk(self.L.dsv1_resladder_set_deinterlace(self.h, _C.byref(di) if di is not None else None), "dsv1_resladder_set_deinterlace")
-        self._deint_field = di is not None and di.mode == DEINT_FIELD
 
     def deinterlace_reset(self, source=-1):
         """a discontinuity in `source` (-1: every source): dsv1_resladder_deinterlace_reset"""
@@ -2067,7 +2162,6 @@ class ResLadder:
         """the sources are 3:2 pulled-down film: inverse telecine them on the GPU as Ivtc iv says, behind the conversion and in front of
         the scales (dsv1_resladder_set_ivtc); None switches it off.  Between calls only; contract as Batch.set_source_ivtc."""
         _chk(self.L.dsv1_resladder_set_ivtc(self.h, _C.byref(iv) if iv is not None else None), "dsv1_resladder_set_ivtc")
-        self._ivtc = iv is not None
 
     def ivtc_reset(self, source=-1):
         """a discontinuity in `source` (-1: every source): dsv1_resladder_ivtc_reset"""

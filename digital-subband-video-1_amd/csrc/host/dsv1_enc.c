@@ -1152,182 +1152,96 @@ int dsv1_batch_stage(dsv1_batch *b, const void *yuv_host)
     return stage_n(b, yuv_host, b ? b->F : 0);
 }
 
-/* the two source-format setters: clips of *pf at src_subsamp (NULL: tight planar 8-bit) into the batch's subsampling */
+/* ---- the source side: every setter, reset and seek is the chain's one request path (dsv1_srcchain_request: validity, the plan of
+ * dsv1_srcchain_plan.h, one log line on a refusal, commit); here are the null check and the batch's `busy`.  Nothing in flight means
+ * every batch that read one of the chain's clips has been collected. ---- */
+#define BATCH_BUSY(b)     ((b)->pending[0] || (b)->pending[1] || (b)->nstaged)     /* setters: batches in flight or clips staged */
+#define BATCH_INFLIGHT(b) ((b)->pending[0] || (b)->pending[1])                     /* resets: batches in flight */
+
+/* the two source-format setters: clips of *pf at src_subsamp (NULL: tight planar 8-bit) into the batch's subsampling; the default
+ * format is no converter */
 static int set_source_format(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp, const char *who)
 {
     static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
-    dsv1_pix_layout L;
-    const DSV_META *m = &b->enc[0].vidmeta;
-    if (!pf && src_subsamp != m->subsamp) pf = &planar8;
-    /* (the frames that come in: the batch's geometry, or the input of the reframe set before) */
-    if (pf && dsv1_pix_layout_of(pf, b->src.w, b->src.h, src_subsamp, m->subsamp, &L)) {
-        dsv1_log(1, "%s: not a valid pixel format for %dx%d, subsampling 0x%x into 0x%x", who, b->src.w, b->src.h, src_subsamp, m->subsamp);
-        return DSVG_ERR_ARG;
-    }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "%s with batches in flight or clips staged", who); return DSVG_ERR_ARG; }
-    /* nothing in flight: every batch that read one of the chain's clips has been collected */
-    return dsv1_srcchain_set_format(&b->src, src_subsamp == m->subsamp && dsv1_pix_is_default(pf, b->src.w, b->src.h, m->subsamp) ? NULL : &L, NULL);
+    const int sub = b->enc[0].vidmeta.subsamp;
+    dsv1_src_format f = {pf, src_subsamp, NULL};
+    if (!pf && src_subsamp != sub) f.pf = &planar8;
+    if (src_subsamp == sub && dsv1_pix_is_default(f.pf, b->src.g.w, b->src.g.h, sub)) f.pf = NULL;
+    return dsv1_srcchain_request(&b->src, who, BATCH_BUSY(b), DSV1_SRC_CONVERT, &f);
 }
-
 int dsv1_batch_set_source_format(dsv1_batch *b, const dsv1_pix_format *pf)
 {
-    if (!b) return DSVG_ERR_ARG;
-    return set_source_format(b, pf, b->enc[0].vidmeta.subsamp, "dsv1_batch_set_source_format");
+    return b ? set_source_format(b, pf, b->enc[0].vidmeta.subsamp, "dsv1_batch_set_source_format") : DSVG_ERR_ARG;
 }
-
 int dsv1_batch_set_source_format_sub(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp)
 {
-    if (!b) return DSVG_ERR_ARG;
-    return set_source_format(b, pf, src_subsamp, "dsv1_batch_set_source_format_sub");
+    return b ? set_source_format(b, pf, src_subsamp, "dsv1_batch_set_source_format_sub") : DSVG_ERR_ARG;
 }
-
 /* the RGB twin: the RGB import pass in the converter's place; the two setters replace each other */
 int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
 {
-    dsv1_rgb_layout L;
-    const DSV_META *m;
-    if (!b) return DSVG_ERR_ARG;
-    if (!rf) return dsv1_batch_set_source_format(b, NULL);
-    m = &b->enc[0].vidmeta;
-    if (dsv1_rgb_layout_of(rf, b->src.w, b->src.h, m->subsamp, &L)) {
-        dsv1_log(1, "dsv1_batch_set_source_rgb: not a valid RGB format for %dx%d, subsampling 0x%x", b->src.w, b->src.h, m->subsamp);
-        return DSVG_ERR_ARG;
-    }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_rgb with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_format(&b->src, NULL, &L);
+    dsv1_src_format f = {NULL, 0, rf};
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_rgb", BATCH_BUSY(b), DSV1_SRC_CONVERT, &f) : DSVG_ERR_ARG;
 }
-
-/* deinterlacing: the setter, and one source's discontinuity */
-int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
-{
-    if (!b) return DSVG_ERR_ARG;
-    if (di && !dsv1_deint_valid(di)) { dsv1_log(1, "dsv1_batch_set_source_deinterlace: mode %d / tff %d is not a deinterlacer", di->mode, di->tff); return DSVG_ERR_ARG; }
-    if (di && di->mode == DSV1_DEINT_FIELD && (b->F & 1)) {
-        dsv1_log(1, "dsv1_batch_set_source_deinterlace: field rate needs an even frames_per_call (%d)", b->F);
-        return DSVG_ERR_ARG;
-    }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_deinterlace with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (di && b->src.iv) { dsv1_log(1, "dsv1_batch_set_source_deinterlace while an inverse telecine is set: clear it first"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_deinterlace(&b->src, di);
-}
-
-/* inverse telecine, in the deinterlacer's place: the setter, and one source's discontinuity */
-int dsv1_batch_set_source_ivtc(dsv1_batch *b, const dsv1_ivtc *iv)
-{
-    if (!b) return DSVG_ERR_ARG;
-    if (iv && !dsv1_ivtc_valid(iv)) { dsv1_log(1, "dsv1_batch_set_source_ivtc: tff %d / nt %d is not an inverse telecine", iv->tff, iv->nt); return DSVG_ERR_ARG; }
-    if (iv && (b->F < 4 || b->F % 4)) {
-        dsv1_log(1, "dsv1_batch_set_source_ivtc: frames_per_call (%d) must be a multiple of 4", b->F);
-        return DSVG_ERR_ARG;
-    }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_ivtc with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (iv && b->src.dd) { dsv1_log(1, "dsv1_batch_set_source_ivtc while a deinterlacer is set: clear it first"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_ivtc(&b->src, iv);
-}
-
-int dsv1_batch_ivtc_reset(dsv1_batch *b, int source)
-{
-    if (!b || !b->src.iv || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_ivtc_reset with batches in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_ivtc_reset(&b->src, source);
-}
-
-int dsv1_batch_deinterlace_reset(dsv1_batch *b, int source)
-{
-    if (!b || !b->src.dd || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_deinterlace_reset with batches in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_deinterlace_reset(&b->src, source);
-}
-
-/* temporal noise reduction: the setter, and one source's discontinuity */
-int dsv1_batch_set_source_denoise(dsv1_batch *b, const dsv1_denoise *dn)
-{
-    if (!b) return DSVG_ERR_ARG;
-    if (dn && !dsv1_denoise_valid(dn)) { dsv1_log(1, "dsv1_batch_set_source_denoise: luma %d / chroma %d is not a noise filter", dn->luma, dn->chroma); return DSVG_ERR_ARG; }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_denoise with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_denoise(&b->src, dn);
-}
-
-int dsv1_batch_denoise_reset(dsv1_batch *b, int source)
-{
-    if (!b || !b->src.dn || source < -1 || source >= b->nsrc) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1]) { dsv1_log(1, "dsv1_batch_denoise_reset with batches in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_denoise_reset(&b->src, source);
-}
-
-/* the reframe: the last pass of the chain; it changes the geometry the other passes are built for, so only while none of them is set */
-int dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf)
-{
-    const DSV_META *m;
-    if (!b) return DSVG_ERR_ARG;
-    m = &b->enc[0].vidmeta;
-    if (rf && (!dsv1_reframe_valid(rf, m->subsamp) || rf->out_w != m->width || rf->out_h != m->height)) {
-        dsv1_log(1, "dsv1_batch_set_source_reframe: not a valid reframe onto %dx%d, subsampling 0x%x", m->width, m->height, m->subsamp);
-        return DSVG_ERR_ARG;
-    }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_reframe with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (b->src.pc || b->src.dd || b->src.iv || b->src.dn) {
-        dsv1_log(1, "dsv1_batch_set_source_reframe with a source format, a deinterlacer, an inverse telecine or a noise filter set: clear them first, set them again after it");
-        return DSVG_ERR_ARG;
-    }
-    if (b->src.orn) { dsv1_log(1, "dsv1_batch_set_source_reframe while an orientation is set: clear it first, set it again after the reframe"); return DSVG_ERR_ARG; }
-    if (b->src.lv) { dsv1_log(1, "dsv1_batch_set_source_reframe while levels are set: clear them first, set them again after the reframe"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_reframe(&b->src, rf);
-}
-
-/* the orientation: in front of the reframe, behind the other passes, whose geometry it changes: only while none of those is set */
-int dsv1_batch_set_source_orient(dsv1_batch *b, int orient)
-{
-    const DSV_META *m;
-    if (!b) return DSVG_ERR_ARG;
-    m = &b->enc[0].vidmeta;
-    if (!dsv1_orient_valid(orient, m->subsamp)) {
-        dsv1_log(1, "dsv1_batch_set_source_orient: %d is not an orientation of subsampling 0x%x", orient, m->subsamp);
-        return DSVG_ERR_ARG;
-    }
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_orient with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    if (b->src.pc || b->src.dd || b->src.iv || b->src.dn) {
-        dsv1_log(1, "dsv1_batch_set_source_orient with a source format, a deinterlacer, an inverse telecine or a noise filter set: clear them first, set them again after it");
-        return DSVG_ERR_ARG;
-    }
-    if (b->src.lv) { dsv1_log(1, "dsv1_batch_set_source_orient while levels are set: clear them first, set them again after the orientation"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_orient(&b->src, orient);
-}
-
-/* levels: directly behind the converter, at the raw geometry; NULL or the identity clears the pass.  Setting, changing or clearing it
- * forgets the history and state of the passes behind it */
 int dsv1_batch_set_source_levels(dsv1_batch *b, const dsv1_levels *lv)
 {
-    if (!b) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_levels with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_levels(&b->src, lv);
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_levels", BATCH_BUSY(b), DSV1_SRC_LEVELS, lv) : DSVG_ERR_ARG;
 }
-
-/* overlays: the LAST pass, on the batch's geometry; NULL or 0 clears it.  The list is checked whole before anything changes */
+int dsv1_batch_set_source_deinterlace(dsv1_batch *b, const dsv1_deint *di)
+{
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_deinterlace", BATCH_BUSY(b), DSV1_SRC_DEINTERLACE, di) : DSVG_ERR_ARG;
+}
+int dsv1_batch_set_source_ivtc(dsv1_batch *b, const dsv1_ivtc *iv)
+{
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_ivtc", BATCH_BUSY(b), DSV1_SRC_IVTC, iv) : DSVG_ERR_ARG;
+}
+int dsv1_batch_set_source_denoise(dsv1_batch *b, const dsv1_denoise *dn)
+{
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_denoise", BATCH_BUSY(b), DSV1_SRC_DENOISE, dn) : DSVG_ERR_ARG;
+}
+int dsv1_batch_set_source_orient(dsv1_batch *b, int orient)
+{
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_orient", BATCH_BUSY(b), DSV1_SRC_ORIENT, &orient) : DSVG_ERR_ARG;
+}
+int dsv1_batch_set_source_reframe(dsv1_batch *b, const dsv1_reframe *rf)
+{
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_reframe", BATCH_BUSY(b), DSV1_SRC_REFRAME, rf) : DSVG_ERR_ARG;
+}
 int dsv1_batch_set_source_overlays(dsv1_batch *b, const dsv1_overlay *list, int n)
 {
-    const DSV_META *m;
-    int i;
-    if (!b || n < 0 || n > DSV1_MAX_OVERLAYS) return DSVG_ERR_ARG;
-    if (b->pending[0] || b->pending[1] || b->nstaged) { dsv1_log(1, "dsv1_batch_set_source_overlays with batches in flight or clips staged"); return DSVG_ERR_ARG; }
-    m = &b->enc[0].vidmeta;
-    for (i = 0; list && i < n; i++)
-        if (!dsv1_overlay_valid(&list[i], m->width, m->height, m->subsamp, b->nsrc)) {
-            dsv1_log(1, "dsv1_batch_set_source_overlays: item %d is not a valid overlay on %dx%d, subsampling 0x%x, %d sources", i, m->width, m->height, m->subsamp, b->nsrc);
-            return DSVG_ERR_ARG;
-        }
-    return dsv1_srcchain_set_overlays(&b->src, list, n);
+    dsv1_src_overlays o = {list, n};
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_overlays", BATCH_BUSY(b), DSV1_SRC_OVERLAY, &o) : DSVG_ERR_ARG;
 }
-
+/* one source's discontinuity (-1: every source's) */
+int dsv1_batch_deinterlace_reset(dsv1_batch *b, int source)
+{
+    return b ? dsv1_srcchain_signal(&b->src, "dsv1_batch_deinterlace_reset", BATCH_INFLIGHT(b), DSV1_SC_OP_RESET, DSV1_SRC_DEINTERLACE, source, 0) : DSVG_ERR_ARG;
+}
+int dsv1_batch_ivtc_reset(dsv1_batch *b, int source)
+{
+    return b ? dsv1_srcchain_signal(&b->src, "dsv1_batch_ivtc_reset", BATCH_INFLIGHT(b), DSV1_SC_OP_RESET, DSV1_SRC_IVTC, source, 0) : DSVG_ERR_ARG;
+}
+int dsv1_batch_denoise_reset(dsv1_batch *b, int source)
+{
+    return b ? dsv1_srcchain_signal(&b->src, "dsv1_batch_denoise_reset", BATCH_INFLIGHT(b), DSV1_SC_OP_RESET, DSV1_SRC_DENOISE, source, 0) : DSVG_ERR_ARG;
+}
 /* the next picture of `source` (-1: every source) is picture t of the overlays' clock */
 int dsv1_batch_overlay_seek(dsv1_batch *b, int source, int64_t t)
 {
-    if (!b) return DSVG_ERR_ARG;
-    return dsv1_srcchain_overlay_seek(&b->src, source, t);
+    return b ? dsv1_srcchain_signal(&b->src, "dsv1_batch_overlay_seek", 0, DSV1_SC_OP_SEEK, DSV1_SRC_OVERLAY, source, t) : DSVG_ERR_ARG;
 }
 
 /* tests: 1 while the batch's source chain holds a lane (a stream and device memory of its own), 0 with no pass set */
 int dsv1_batch_has_source_lane(const dsv1_batch *b) { return b && b->src.lane != NULL; }
+
+/* what a call must bring, straight from the chain */
+int dsv1_batch_source_input(const dsv1_batch *b, int in[3], size_t *frame_bytes)
+{
+    if (!b || !in || !frame_bytes) return DSVG_ERR_ARG;
+    in[0] = b->src.g.frames_in; in[1] = b->src.g.w; in[2] = b->src.g.h;
+    *frame_bytes = b->src.g.frame_in_bytes;
+    return DSVG_OK;
+}
 
 /* a clip of the batch's source format -> the clip the chain's passes leave for the next submit's parity (device memory the chain owns,
  * read as a held clip until that batch's collect); the context's frame-load stream waits for the passes on the device */

@@ -116,84 +116,47 @@ int  dsvg_scaler_create(dsvg_scaler **out, int device, int sw, int sh, int subsa
 void dsvg_scaler_destroy(dsvg_scaler *s);
 int  dsvg_scaler_run(dsvg_scaler *s, void *stream, int g, const void *src_dev, int nframes, void *dst_dev);
 
-/* the tightly packed planar frame */
-static inline size_t dsv1_frame_bytes(int w, int h, int subsamp)
-{
-    const int hs = (subsamp >> 2) & 3, vs = subsamp & 3;
-    return (size_t)w * h + 2 * (size_t)((w + (1 << hs) - 1) >> hs) * (size_t)((h + (1 << vs) - 1) >> vs);
-}
-
-/* dsv1_srcchain.c: the source side of a session -- a lane, the optional converter, levels, deinterlacer, noise filter, orientation, reframe and overlays with their
- * settings, and each pass's output clip per call parity (a batch of that parity reads the last one as a held clip until its collect).
- * A chain with no pass set holds no lane -- no stream, no device memory -- unless the session keeps it (keep_lane: a resolution
- * ladder uploads and scales on it).  The setters replace or (NULL) clear one pass; on an error the chain is as it was.  The session
- * checks that nothing is in flight, and its arguments, before it calls one.
- * THREE GEOMETRIES.  RAW, w x h (fb), is what convert, levels, deinterlace and denoise are built for: the frames that come in.  ORIENTED,
- * mw x mh (mfb), is what the orientation leaves and the reframe reads.  CANVAS, ow x oh (ofb), is the clip the chain hands on: the
- * session's geometry.  Raw and oriented differ only while a transposing orientation is set, oriented and canvas only while a reframe
- * -- the LAST pass -- is set.  The reframe may be set, changed or cleared only while no other pass is set, the orientation only while
- * none but the reframe is (the session checks); the passes set after them resolve at w x h. */
-enum { DSV1_SRC_CONVERT, DSV1_SRC_DEINTERLACE, DSV1_SRC_DENOISE, DSV1_SRC_ORIENT, DSV1_SRC_REFRAME, DSV1_SRC_LEVELS, DSV1_SRC_OVERLAY,
-       DSV1_SRC_SCALE,
-       DSV1_SRC_IVTC };                 /* (the inverse telecine: exclusive with the deinterlacer, whose place and clips it takes) */
+/* dsv1_srcchain.c: the source side of a session -- a lane, whichever of convert -> levels -> deinterlace or inverse telecine ->
+ * denoise -> orient -> reframe -> overlay are set, and each pass's output clip per call parity (a batch of that parity reads the last
+ * one as a held clip until its collect).  WHAT IS TAKEN AND REFUSED, the three geometries, the clips' sizes, what a setter forgets
+ * behind it and when the lane exists are dsv1_srcchain_plan.h's (which also holds dsv1_frame_bytes): this file resolves a request's
+ * arguments, asks the plan, and commits or enqueues what it says.  st is the plan's state of the chain, g what follows from it
+ * (g.w x g.h: the frames that come in; g.ow x g.oh: the clip handed on).  On an error the chain is as it was (dsv1_srcchain_request
+ * says what that means for a history). */
+#include "dsv1_srcchain_plan.h"
+enum { DSV1_SRC_CONVERT = DSV1_SC_CONVERT, DSV1_SRC_LEVELS, DSV1_SRC_DEINTERLACE, DSV1_SRC_IVTC, DSV1_SRC_DENOISE, DSV1_SRC_ORIENT, DSV1_SRC_REFRAME,
+       DSV1_SRC_OVERLAY, DSV1_SRC_SCALE };             /* chain order; SCALE: the standalone clip call's only */
 typedef struct {
-    int device, w, h, subsamp, nsrc, F, keep_lane;
-    int mw, mh;                         /* the oriented geometry: the reframe's input */
-    int ow, oh;                         /* the geometry handed on (the session's) */
-    size_t fb, raw_fb, mfb, ofb;        /* the packed planar frame that comes in; the converter's source frame; the oriented frame; the frame handed on */
+    int device;
+    dsv1_srcchain_state st;
+    dsv1_srcchain_geom g;
     dsvg_lane *lane;
-    dsvg_pixconv *pc;
-    dsvg_deint *dd;
-    dsv1_deint dd_set;
-    dsvg_ivtc *iv;                      /* the inverse telecine, in the deinterlacer's place (never both) */
-    dsv1_ivtc iv_set;
-    int conv_frames;                    /* frames per source the converter's clips, and the levels', hold */
-    dsvg_levels *lv;                    /* directly behind the converter; its clips are sized as the converter's */
-    dsvg_denoise *dn;
-    dsv1_denoise dn_set;
-    dsvg_orient *orn;
-    int orient;                         /* the code set (0: no pass) */
-    dsvg_reframe *rf;
-    /* the overlays: the LAST pass, on the canvas, IN PLACE on whatever clip of the chain's own reaches it; its two clips exist only
-     * once a caller's device clip reached it with no other pass set (copied there first).  ov_t[s]: source s's picture counter */
-    dsvg_overlay *ov;
-    int64_t *ov_t;
-    void *clip[7][2];
+    void *pass[DSV1_SC_SLOTS];          /* the pass at each position (its kind: st.kind) */
+    void *clip[DSV1_SC_SLOTS][2];       /* its output clip per call parity; the overlays': see dsv1_scp_call */
+    int64_t *ov_t;                      /* [nsrc] the overlays' picture counters */
 } dsv1_srcchain;
 void dsv1_srcchain_init(dsv1_srcchain *c, int device, int w, int h, int subsamp, int nsrc, int F, int keep_lane);
 void dsv1_srcchain_close(dsv1_srcchain *c);            /* waits for the lane; frees everything */
 int  dsv1_srcchain_lane(dsv1_srcchain *c);             /* creates the lane where there is none yet */
-int  dsv1_srcchain_set_format(dsv1_srcchain *c, const dsv1_pix_layout *L, const dsv1_rgb_layout *R);      /* one of them, or neither: no converter */
-int  dsv1_srcchain_set_deinterlace(dsv1_srcchain *c, const dsv1_deint *di);         /* (resets the noise filter's state) */
-int  dsv1_srcchain_set_denoise(dsv1_srcchain *c, const dsv1_denoise *dn);
-/* the inverse telecine (resets the noise filter's state).  A call then brings 5 F / 4 frames per source: the converter's clips are
- * allocated again for them, and again for F when it is cleared; on an error the chain is as it was.  The session checks that F is a
- * multiple of 4 and that no deinterlacer is set (and no inverse telecine when it sets a deinterlacer). */
-int  dsv1_srcchain_set_ivtc(dsv1_srcchain *c, const dsv1_ivtc *iv);
-int  dsv1_srcchain_ivtc_reset(dsv1_srcchain *c, int source);                        /* DSVG_ERR_ARG where the pass is not set */
-/* a valid reframe whose canvas is ow x oh, or NULL / the identity: none.  DSVG_ERR_ARG, chain as it was, while another pass is set */
-int  dsv1_srcchain_set_reframe(dsv1_srcchain *c, const dsv1_reframe *rf);
-/* a code valid at the chain's subsampling; 0: none.  The oriented geometry stays, the raw one becomes what the inverse code makes of
- * it.  DSVG_ERR_ARG, chain as it was, while a pass other than the reframe is set */
-int  dsv1_srcchain_set_orient(dsv1_srcchain *c, int orient);
-/* tables, or NULL / the identity: none.  Forgets the deinterlacer's history, the inverse telecine's and the noise filter's state */
-int  dsv1_srcchain_set_levels(dsv1_srcchain *c, const dsv1_levels *lv);
+/* ONE SETTER PATH for both sessions: resolve arg (NULL: clear the pass) with the kind's own check, dsv1_scp_set, on a refusal one
+ * log line "who: text", else create the pass and commit.  arg by kind: CONVERT dsv1_src_format; LEVELS dsv1_levels; DEINTERLACE
+ * dsv1_deint; IVTC dsv1_ivtc; DENOISE dsv1_denoise; ORIENT int; REFRAME dsv1_reframe; OVERLAY dsv1_src_overlays.  busy: the
+ * session's (batches in flight or clips staged; calls in flight).
+ * _signal: a reset (op DSV1_SC_OP_RESET: a discontinuity in `source`, -1 every source) or the overlays' seek (DSV1_SC_OP_SEEK: the
+ * next picture of `source` is t), by the same plan and log line. */
+typedef struct { const dsv1_pix_format *pf; int src_subsamp; const dsv1_rgb_format *rgb; } dsv1_src_format;    /* one of them, or neither: no converter */
+typedef struct { const dsv1_overlay *list; int n; } dsv1_src_overlays;
+int  dsv1_srcchain_request(dsv1_srcchain *c, const char *who, int busy, int kind, const void *arg);
+int  dsv1_srcchain_signal(dsv1_srcchain *c, const char *who, int busy, int op, int kind, int source, int64_t t);
 int  dsv1_reframe_is_identity(const dsv1_reframe *rf);  /* dsv1_reframe.c: window = input = canvas at 0, 0 */
-int  dsv1_srcchain_deinterlace_reset(dsv1_srcchain *c, int source);                 /* DSVG_ERR_ARG where the pass is not set */
-int  dsv1_srcchain_denoise_reset(dsv1_srcchain *c, int source);
-/* a list of n valid placements on the canvas (the bitmaps are copied), or NULL / 0: none.  The counters start at 0.  It changes no
- * geometry: any order relative to the other setters.  _seek: source s's (-1: every source's) next picture is t; DSVG_ERR_ARG where no
- * list is set */
-int  dsv1_srcchain_set_overlays(dsv1_srcchain *c, const dsv1_overlay *list, int n);
-int  dsv1_srcchain_overlay_seek(dsv1_srcchain *c, int source, int64_t t);
-/* the passes that write a clip of their own (everything but the overlays) */
-static inline int dsv1_srcchain_writes(const dsv1_srcchain *c) { return c->pc || c->lv || c->dd || c->iv || c->dn || c->orn || c->rf; }
-static inline int dsv1_srcchain_any(const dsv1_srcchain *c) { return dsv1_srcchain_writes(c) || c->ov; }
-int  dsv1_srcchain_frames_in(const dsv1_srcchain *c);  /* frames per source and call that come in: F, F / 2 at field rate, 5 F / 4 in front of the inverse telecine */
-size_t dsv1_srcchain_bytes_in(const dsv1_srcchain *c); /* ... and the bytes of a call's clip */
-/* a call's clip (host memory: uploaded into the buffer of the parity first) through whichever of convert -> levels -> deinterlace -> denoise ->
- * orient -> reframe -> overlay are set, enqueued on the lane; *out: the device clip that stands for the source from there on (the input itself where
- * nothing ran: no pass set, or overlays alone with none active in the call -- then host memory comes back as host memory unless the session keeps the lane) */
+static inline int dsv1_srcchain_any(const dsv1_srcchain *c)       /* a pass is set */
+{
+    int p, any = 0;
+    for (p = 0; p < DSV1_SC_SLOTS; p++) any |= c->st.kind[p];
+    return any;
+}
+/* a call's clip (host memory: uploaded into the buffer of the parity first) through the passes set, enqueued on the lane as
+ * dsv1_scp_call says; *out: the device clip that stands for the source from there on (the input itself where nothing was enqueued) */
 int  dsv1_srcchain_run(dsv1_srcchain *c, int par, const void *clip, int on_device, const void **out);
 /* the standalone clip calls: one pass (DSV1_SRC_*; SCALE: a scaler's geometry 0) over n frames on a lane of the call's own.  in[0] the
  * clip, in[1] an optional second input (the deinterlacer's prev, the filter's state_in); out[0] the result, out[1] the filter's

@@ -238,6 +238,7 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int ori
     dsv1_resladder *r;
     dsv1_pix_layout pl;
     dsv1_rgb_layout rl;
+    dsv1_src_format fmt;
     int g, k, rc, ntot = 0, nscaled = 0, maxr = 0, dw[DSV1_MAX_GEOMS], dh[DSV1_MAX_GEOMS];
     if (out) *out = NULL;
     /* arguments first: nothing below touches a device until every geometry has passed */
@@ -303,9 +304,11 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int ori
         if (!r->same[g]) { r->scale_idx[g] = nscaled; dw[nscaled] = r->w[g]; dh[nscaled] = r->h[g]; nscaled++; }
     }
     /* the lane exists even when no geometry is scaled: host input is uploaded through it */
+    fmt.pf = pf; fmt.src_subsamp = src_subsamp; fmt.rgb = rf;
     if ((rc = dsvg_scaler_create(&r->sc, device, cw, ch, src->subsamp, nscaled, dw, dh, filter)) ||
-        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_set_reframe(&r->src, frm)) || (rc = dsv1_srcchain_set_orient(&r->src, orient)) ||
-        (rc = dsv1_srcchain_set_format(&r->src, pf ? &pl : NULL, rf ? &rl : NULL))) { dsv1_resladder_close(r); return rc; }
+        (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_request(&r->src, "dsv1_resladder_open", 0, DSV1_SRC_REFRAME, frm)) ||
+        (rc = dsv1_srcchain_request(&r->src, "dsv1_resladder_open", 0, DSV1_SRC_ORIENT, &orient)) ||
+        (rc = dsv1_srcchain_request(&r->src, "dsv1_resladder_open", 0, DSV1_SRC_CONVERT, &fmt))) { dsv1_resladder_close(r); return rc; }
     for (g = 0; g < ngeoms; g++) {
         if ((rc = dsv1_ladder_open(&r->lad[g], rungs[g].rates, rungs[g].nrates, device, nsources, frames_per_call))) break;
         r->ngeom = g + 1;
@@ -371,19 +374,19 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
         /* the source-resolution figures read the source until collect, and a plain device clip is the caller's again when submit
          * returns: a device-to-device copy into the buffer of the call's parity, which from here on stands for the clip */
         void *d;
-        if ((rc = dsvg_lane_copy_in(r->src.lane, par, yuv, dsv1_srcchain_bytes_in(&r->src), &d))) return rc;
+        if ((rc = dsvg_lane_copy_in(r->src.lane, par, yuv, r->src.g.bytes_in, &d))) return rc;
         dsrc = d;
     } else {
         /* the RAW clip crosses the link once (host input), into the lane's buffer of this call's parity, which is held until this
          * call's collect (a geometry of the source's size reads it in place); the chain's passes write clips of this call's parity,
          * and what they leave stands for the source from here on */
         if ((rc = dsv1_srcchain_run(&r->src, par, yuv, yuv_on_device, &dsrc))) return rc;
-        if (!yuv_on_device) { r->up_bytes += dsv1_srcchain_bytes_in(&r->src); r->up_calls++; }
+        if (!yuv_on_device) { r->up_bytes += r->src.g.bytes_in; r->up_calls++; }
     }
     if (dsrc == yuv && plain_dev && (r->q[DSVG_Q_XSSE].on || r->q[DSVG_Q_XSSIM].on)) {
         /* (overlays alone and none active in this call: the clip came back as it went in; the figures read it until collect) */
         void *d;
-        if ((rc = dsvg_lane_copy_in(r->src.lane, par, yuv, dsv1_srcchain_bytes_in(&r->src), &d))) return rc;
+        if ((rc = dsvg_lane_copy_in(r->src.lane, par, yuv, r->src.g.bytes_in, &d))) return rc;
         dsrc = d;
     }
     /* the resladder's own memory is held until collect (a plain device clip: the sync at the end waits for whatever read it) */
@@ -410,87 +413,53 @@ int dsv1_resladder_submit(dsv1_resladder *r, const void *yuv, int yuv_on_device,
     return DSVG_OK;
 }
 
+/* ---- the source side between calls: the chain's one request path (dsv1_srcchain_request), as a batch's setters; busy: calls in
+ * flight.  What the chain leaves stands for the source everywhere behind it: the scales read it, and so do the source-resolution
+ * figures. ---- */
+#define RES_BUSY(r) ((r)->pending[0] || (r)->pending[1])
 int dsv1_resladder_set_deinterlace(dsv1_resladder *r, const dsv1_deint *di)
 {
-    if (!r) return DSVG_ERR_ARG;
-    if (di && !dsv1_deint_valid(di)) { dsv1_log(1, "dsv1_resladder_set_deinterlace: mode %d / tff %d is not a deinterlacer", di->mode, di->tff); return DSVG_ERR_ARG; }
-    if (di && di->mode == DSV1_DEINT_FIELD && (r->F & 1)) {
-        dsv1_log(1, "dsv1_resladder_set_deinterlace: field rate needs an even frames_per_call (%d)", r->F);
-        return DSVG_ERR_ARG;
-    }
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_deinterlace with calls in flight"); return DSVG_ERR_ARG; }
-    if (di && r->src.iv) { dsv1_log(1, "dsv1_resladder_set_deinterlace while an inverse telecine is set: clear it first"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_deinterlace(&r->src, di);
+    return r ? dsv1_srcchain_request(&r->src, "dsv1_resladder_set_deinterlace", RES_BUSY(r), DSV1_SRC_DEINTERLACE, di) : DSVG_ERR_ARG;
 }
-
 int dsv1_resladder_set_ivtc(dsv1_resladder *r, const dsv1_ivtc *iv)
 {
-    if (!r) return DSVG_ERR_ARG;
-    if (iv && !dsv1_ivtc_valid(iv)) { dsv1_log(1, "dsv1_resladder_set_ivtc: tff %d / nt %d is not an inverse telecine", iv->tff, iv->nt); return DSVG_ERR_ARG; }
-    if (iv && (r->F < 4 || r->F % 4)) {
-        dsv1_log(1, "dsv1_resladder_set_ivtc: frames_per_call (%d) must be a multiple of 4", r->F);
-        return DSVG_ERR_ARG;
-    }
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_ivtc with calls in flight"); return DSVG_ERR_ARG; }
-    if (iv && r->src.dd) { dsv1_log(1, "dsv1_resladder_set_ivtc while a deinterlacer is set: clear it first"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_ivtc(&r->src, iv);
+    return r ? dsv1_srcchain_request(&r->src, "dsv1_resladder_set_ivtc", RES_BUSY(r), DSV1_SRC_IVTC, iv) : DSVG_ERR_ARG;
 }
-
-int dsv1_resladder_ivtc_reset(dsv1_resladder *r, int source)
-{
-    if (!r || !r->src.iv || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_ivtc_reset with calls in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_ivtc_reset(&r->src, source);
-}
-
-int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)
-{
-    if (!r || !r->src.dd || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_deinterlace_reset with calls in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_deinterlace_reset(&r->src, source);
-}
-
-/* the levelled clip stands for the source everywhere behind the chain */
 int dsv1_resladder_set_levels(dsv1_resladder *r, const dsv1_levels *lv)
 {
-    if (!r) return DSVG_ERR_ARG;
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_levels with calls in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_levels(&r->src, lv);
+    return r ? dsv1_srcchain_request(&r->src, "dsv1_resladder_set_levels", RES_BUSY(r), DSV1_SRC_LEVELS, lv) : DSVG_ERR_ARG;
 }
-
-/* the overlaid clip stands for the source everywhere behind the chain: the scales read it, and so do the source-resolution figures */
-int dsv1_resladder_set_overlays(dsv1_resladder *r, const dsv1_overlay *list, int n)
-{
-    int i;
-    if (!r || n < 0 || n > DSV1_MAX_OVERLAYS) return DSVG_ERR_ARG;
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_overlays with calls in flight"); return DSVG_ERR_ARG; }
-    for (i = 0; list && i < n; i++)
-        if (!dsv1_overlay_valid(&list[i], r->src.ow, r->src.oh, r->src.subsamp, r->nsrc)) {
-            dsv1_log(1, "dsv1_resladder_set_overlays: item %d is not a valid overlay on %dx%d, subsampling 0x%x, %d sources", i, r->src.ow, r->src.oh, r->src.subsamp, r->nsrc);
-            return DSVG_ERR_ARG;
-        }
-    return dsv1_srcchain_set_overlays(&r->src, list, n);
-}
-
-int dsv1_resladder_overlay_seek(dsv1_resladder *r, int source, int64_t t)
-{
-    if (!r) return DSVG_ERR_ARG;
-    return dsv1_srcchain_overlay_seek(&r->src, source, t);
-}
-
 int dsv1_resladder_set_denoise(dsv1_resladder *r, const dsv1_denoise *dn)
 {
-    if (!r) return DSVG_ERR_ARG;
-    if (dn && !dsv1_denoise_valid(dn)) { dsv1_log(1, "dsv1_resladder_set_denoise: luma %d / chroma %d is not a noise filter", dn->luma, dn->chroma); return DSVG_ERR_ARG; }
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_set_denoise with calls in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_set_denoise(&r->src, dn);
+    return r ? dsv1_srcchain_request(&r->src, "dsv1_resladder_set_denoise", RES_BUSY(r), DSV1_SRC_DENOISE, dn) : DSVG_ERR_ARG;
 }
-
+int dsv1_resladder_set_overlays(dsv1_resladder *r, const dsv1_overlay *list, int n)
+{
+    dsv1_src_overlays o = {list, n};
+    return r ? dsv1_srcchain_request(&r->src, "dsv1_resladder_set_overlays", RES_BUSY(r), DSV1_SRC_OVERLAY, &o) : DSVG_ERR_ARG;
+}
+int dsv1_resladder_deinterlace_reset(dsv1_resladder *r, int source)
+{
+    return r ? dsv1_srcchain_signal(&r->src, "dsv1_resladder_deinterlace_reset", RES_BUSY(r), DSV1_SC_OP_RESET, DSV1_SRC_DEINTERLACE, source, 0) : DSVG_ERR_ARG;
+}
+int dsv1_resladder_ivtc_reset(dsv1_resladder *r, int source)
+{
+    return r ? dsv1_srcchain_signal(&r->src, "dsv1_resladder_ivtc_reset", RES_BUSY(r), DSV1_SC_OP_RESET, DSV1_SRC_IVTC, source, 0) : DSVG_ERR_ARG;
+}
 int dsv1_resladder_denoise_reset(dsv1_resladder *r, int source)
 {
-    if (!r || !r->src.dn || source < -1 || source >= r->nsrc) return DSVG_ERR_ARG;
-    if (r->pending[0] || r->pending[1]) { dsv1_log(1, "dsv1_resladder_denoise_reset with calls in flight"); return DSVG_ERR_ARG; }
-    return dsv1_srcchain_denoise_reset(&r->src, source);
+    return r ? dsv1_srcchain_signal(&r->src, "dsv1_resladder_denoise_reset", RES_BUSY(r), DSV1_SC_OP_RESET, DSV1_SRC_DENOISE, source, 0) : DSVG_ERR_ARG;
+}
+int dsv1_resladder_overlay_seek(dsv1_resladder *r, int source, int64_t t)
+{
+    return r ? dsv1_srcchain_signal(&r->src, "dsv1_resladder_overlay_seek", 0, DSV1_SC_OP_SEEK, DSV1_SRC_OVERLAY, source, t) : DSVG_ERR_ARG;
+}
+int dsv1_resladder_source_input(const dsv1_resladder *r, int in[3], size_t *frame_bytes)
+{
+    if (!r || !in || !frame_bytes) return DSVG_ERR_ARG;
+    in[0] = r->src.g.frames_in; in[1] = r->src.g.w; in[2] = r->src.g.h;
+    *frame_bytes = r->src.g.frame_in_bytes;
+    return DSVG_OK;
 }
 
 int dsv1_resladder_collect(dsv1_resladder *r, DSV_BUF *out)

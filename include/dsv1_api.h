@@ -333,6 +333,64 @@ typedef struct {
 int   dsv1_submit_plan(dsv1_submit_query *q, dsv1_submit_src *src, dsv1_submit_stream *st, const unsigned *luma, const int *n_intra,
                        const dsv1_submit_pic *prev, const dsv1_submit_tables *tb);
 
+/* ---- Source chain plan (tests; csrc/host/dsv1_srcchain_plan.h; restated in tests/srcchain_plan.py) ----
+ * What the source side of a session (convert -> levels -> deinterlace or inverse telecine -> denoise -> orient -> reframe -> overlay)
+ * decides, as plain data: the sessions answer every setter, reset and seek with dsv1_scp_set and enqueue every call from
+ * dsv1_scp_call; the two queries below run the same functions on the caller's structs, with no device.
+ *   dsv1_srcchain_state: the chain.  kind[p]: the pass at position p of the chain (DSV1_SC_NONE: none); the deinterlacer and the
+ *     inverse telecine are the two occupants of position 2.  ov_clip[par]: the overlay pass's own clip of a call parity exists.
+ *   dsv1_srcchain_req: one call.  valid: what the setting's own check said (dsv1_*_valid, the layout functions); identity: levels and
+ *     reframe settings that change nothing (they clear the pass); mode: the converter's kind (1: RGB), the deinterlacer's mode, the
+ *     orientation's code (0 clears); busy: batches in flight or clips staged (a batch), calls in flight (a resolution ladder).
+ *   dsv1_srcchain_geom: what follows from a state.  w x h raw (the frames that come in), mw x mh oriented, ow x oh canvas, with
+ *     their packed planar frame bytes; conv_frames: frames per source the converter's and the levels' clips hold; frames_in /
+ *     frame_in_bytes / bytes_in: what a call brings; lane: the chain holds a lane.
+ *   dsv1_srcchain_set_plan: the answer to a request.  text: row of the refusal table (dsv1_srcchain_plan_text; 0: none).  noop: no
+ *     pass before, none now.  Per position: alloc = bytes of each of its two clips to allocate, free_ = its clips go, reset = the
+ *     pass's history or state goes (position 6: the picture counters start at 0).  All or nothing: a refusal changes nothing.
+ *   dsv1_srcchain_call_plan: one call's clip through the chain.  src / dst of a step: DSV1_SC_CALLER (the clip as it came),
+ *     DSV1_SC_UPLOAD (the lane's upload of it) or the position whose clip of the call's parity it is.  A step of kind DSV1_SC_NONE
+ *     is the device-to-device copy (bytes; alloc: the clip is allocated first) of a caller's device clip that reaches the overlays
+ *     untouched.  bypass: nothing is enqueued, the clip goes on as it came.  advance: every source's overlay counter moves by it. */
+enum { DSV1_SC_NONE, DSV1_SC_CONVERT, DSV1_SC_LEVELS, DSV1_SC_DEINTERLACE, DSV1_SC_IVTC, DSV1_SC_DENOISE, DSV1_SC_ORIENT, DSV1_SC_REFRAME,
+       DSV1_SC_OVERLAY, DSV1_SC_KINDS };
+enum { DSV1_SC_SLOTS = 7, DSV1_SC_MAX_STEPS = 8 };
+enum { DSV1_SC_OP_SET, DSV1_SC_OP_RESET, DSV1_SC_OP_SEEK };
+enum { DSV1_SC_CALLER = -1, DSV1_SC_UPLOAD = -2 };
+typedef struct {
+    int nsrc, F, subsamp, keep_lane, ow, oh;
+    int kind[DSV1_SC_SLOTS];
+    int conv_rgb;                       /* the converter is the RGB import */
+    size_t conv_fb;                     /* bytes of a frame of the converter's source format */
+    int deint_mode, orient;
+    int in_w, in_h;                     /* the reframe's input */
+    int ov_clip[2];
+} dsv1_srcchain_state;
+typedef struct { int op, kind, set, valid, identity, busy, mode, w, h, out_w, out_h, source; size_t frame_bytes; } dsv1_srcchain_req;
+typedef struct { int w, h, mw, mh, ow, oh, conv_frames, frames_in, lane; size_t fb, mfb, ofb, frame_in_bytes, bytes_in; } dsv1_srcchain_geom;
+typedef struct {
+    int rc, text, noop;
+    dsv1_srcchain_state next;
+    dsv1_srcchain_geom g;               /* of next */
+    size_t alloc[DSV1_SC_SLOTS];
+    int free_[DSV1_SC_SLOTS], reset[DSV1_SC_SLOTS];
+} dsv1_srcchain_set_plan;
+typedef struct { int kind, pos, nframes, src, dst; size_t bytes, alloc; } dsv1_srcchain_step;
+typedef struct {
+    int rc, bypass, nsteps, out, advance;
+    size_t upload;
+    dsv1_srcchain_step step[DSV1_SC_MAX_STEPS];
+} dsv1_srcchain_call_plan;
+/* One request / one call (form: 0 host memory, 1 a plain device clip, DSV1_CLIP_HELD; active: the overlays blend something in this
+ * call; par: the call's parity) on plain structs, no device.  They return out->rc: DSVG_ERR_ARG for what the session refuses (and,
+ * with *out as it was, for what is no request: a kind that is no pass, a reset of a pass that keeps nothing, a seek of another). */
+int   dsv1_srcchain_plan_set(const dsv1_srcchain_state *s, const dsv1_srcchain_req *q, dsv1_srcchain_set_plan *out);
+int   dsv1_srcchain_plan_call(const dsv1_srcchain_state *s, int form, int active, int par, dsv1_srcchain_call_plan *out);
+const char *dsv1_srcchain_plan_text(int row);       /* the refusal table's row (NULL past its end; row 0 is empty) */
+/* what a call of the session must bring, straight from its chain: in[0] frames per source, in[1] x in[2] the raw picture;
+ * *frame_bytes: bytes from frame to frame */
+int   dsv1_batch_source_input(const dsv1_batch *b, int in[3], size_t *frame_bytes);
+
 /* ---- extension: the resampler of resolution ladders (csrc/k_scale.hip; stated in numpy in tests/_scale.py) ----
  * Downscale or identity: on each axis of each plane 1 <= S / D <= 8 (S source length, D destination length); every plane is scaled
  * on its own, from the source's chroma dims to the destination's (rshift_up); the format is kept.  Centre-aligned sample grids;
@@ -380,6 +438,8 @@ typedef struct {
     const DSV_ENCODER *rates;
 } dsv1_res_rung;
 typedef struct dsv1_resladder dsv1_resladder;
+/* what a call of the ladder must bring, straight from its source chain (as dsv1_batch_source_input) */
+int  dsv1_resladder_source_input(const dsv1_resladder *r, int in[3], size_t *frame_bytes);
 int  dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
                          int frames_per_call, int filter);
 void dsv1_resladder_close(dsv1_resladder *r);
