@@ -370,6 +370,68 @@ extern "C" int dsvg_op_frame_avg_luma(const dsvg_frame *f, int *avg)
     return DSVG_OK;
 }
 
+// ---- the rate control (k_rc.hip, include/dsvg_rc.h) on records built from plain arrays: one launch_rc, everything it may touch returned ----
+static void rc_tables_out(const JobDev &jb, int *t)           // plane-major (qp, qp_h) of the ten scan regions, then hqp[16]
+{
+    for (int p = 0; p < 3; p++)
+        for (int r = 0; r < 10; r++) { *t++ = jb.hz[p].r[r].qp; *t++ = jb.hz[p].r[r].qp_h; }
+    for (int i = 0; i < 16; i++) *t++ = jb.hqp[i];
+}
+extern "C" void dsv1_rc_job_tables(int quant, int isP, int out[76])      // the HOST instantiation of dsvg_job_set_quant
+{
+    JobDev jb; memset(&jb, 0, sizeof(jb));
+    jb.isP = isP;
+    dsvg_job_set_quant(jb, quant);
+    rc_tables_out(jb, out);
+}
+extern "C" int dsvg_op_rc(int n, const dsvg_op_rc_job *jobs, int nslots, dsvg_rc_state *states, int d0, int count, int mode, dsvg_op_rc_out *out)
+{
+    if (!jobs || !states || !out || n < 1 || nslots < 1) { dsvg_set_error("null or empty argument"); return DSVG_ERR_ARG; }
+    if (d0 < 0 || count < 0 || d0 > n || count > n - d0 || (mode != 0 && mode != 1)) { dsvg_set_error("range [%d, %d + %d) outside the %d jobs, or mode %d", d0, d0, count, n, mode); return DSVG_ERR_ARG; }
+    for (int j = 0; j < n; j++)
+        if (jobs[j].slot >= nslots || jobs[j].next >= n || jobs[j].next < -1) { dsvg_set_error("job %d: slot %d of %d, next %d of %d", j, jobs[j].slot, nslots, jobs[j].next, n); return DSVG_ERR_ARG; }
+    OpScope S; OPCHK(S.init());
+    JobDev *djobs; RcJobDev *drcj; HzPlaneSum *dps; dsvg_rc_state *dst;
+    OPCHK(S.dev(&djobs, (size_t)n, false));
+    OPCHK(S.dev(&drcj, (size_t)n, false));
+    OPCHK(S.dev(&dps, (size_t)3 * n, false));
+    OPCHK(S.dev(&dst, (size_t)nslots, false));
+    std::vector<JobDev> hj((size_t)n);
+    std::vector<RcJobDev> hr((size_t)n);
+    std::vector<HzPlaneSum> hp((size_t)3 * n);
+    for (int j = 0; j < n; j++) {
+        JobDev &jb = hj[(size_t)j];
+        memset(&jb, 0, sizeof(jb));
+        jb.isP = jobs[j].isP;
+        jb.psum = dps + (size_t)3 * j;
+        for (int p = 0; p < 3; p++) {
+            for (int r = 0; r < 10; r++) jb.hz[p].r[r].qp = jb.hz[p].r[r].qp_h = DSVG_OP_RC_POISON;
+            HzPlaneSum &ps = hp[(size_t)3 * j + p];
+            memset(&ps, 0, sizeof(ps));
+            ps.total_bits = jobs[j].total_bits[p]; ps.dc = jobs[j].dc[p]; ps.rc = DSVG_OP_RC_POISON;
+        }
+        for (int i = 0; i < 16; i++) jb.hqp[i] = DSVG_OP_RC_POISON;
+        jb.quant = jobs[j].quant;
+        hr[(size_t)j].slot = jobs[j].slot; hr[(size_t)j].prefix_len = jobs[j].prefix_len;
+        hr[(size_t)j].forced_intra = jobs[j].forced_intra; hr[(size_t)j].next = jobs[j].next;
+    }
+    HIPCHK(hipMemcpyAsync(djobs, hj.data(), sizeof(JobDev) * (size_t)n, hipMemcpyHostToDevice, S.st));
+    HIPCHK(hipMemcpyAsync(drcj, hr.data(), sizeof(RcJobDev) * (size_t)n, hipMemcpyHostToDevice, S.st));
+    HIPCHK(hipMemcpyAsync(dps, hp.data(), sizeof(HzPlaneSum) * (size_t)3 * n, hipMemcpyHostToDevice, S.st));
+    HIPCHK(hipMemcpyAsync(dst, states, sizeof(dsvg_rc_state) * (size_t)nslots, hipMemcpyHostToDevice, S.st));
+    launch_rc(S.st, djobs, drcj, dst, d0, count, mode);
+    HIPCHK(hipMemcpyAsync(hj.data(), djobs, sizeof(JobDev) * (size_t)n, hipMemcpyDeviceToHost, S.st));
+    HIPCHK(hipMemcpyAsync(hp.data(), dps, sizeof(HzPlaneSum) * (size_t)3 * n, hipMemcpyDeviceToHost, S.st));
+    HIPCHK(hipMemcpyAsync(states, dst, sizeof(dsvg_rc_state) * (size_t)nslots, hipMemcpyDeviceToHost, S.st));
+    OPCHK(S.sync());
+    for (int j = 0; j < n; j++) {
+        out[j].quant = hj[(size_t)j].quant;
+        rc_tables_out(hj[(size_t)j], out[j].tables);
+        for (int p = 0; p < 3; p++) out[j].rc[p] = hp[(size_t)3 * j + p].rc;
+    }
+    return DSVG_OK;
+}
+
 // Memory the operator calls hand to their caller (dsvg_op_hme's motion fields) comes from the allocator the caller FREES with: the reference's
 // caller releases hme.mvf[] with dsv_free (dsv_encoder.c:239-244).  Default: the library's own dsv_alloc / dsv_free (dsv1_util.c); a build that
 // keeps the reference's dsv.c -- whose dsv_free steps back over a 16-byte header when DSV_MEMORY_STATS is on (dsv.c:41-66) -- passes its own pair.

@@ -1137,6 +1137,19 @@ int dsv1_submit_plan(dsv1_submit_query *q, dsv1_submit_src *src, dsv1_submit_str
     return DSVG_OK;
 }
 
+/* the rate control as this layer compiles it (include/dsv1_api.h, Rate control), on the caller's state; dsv1_rc_job_tables is the
+ * C++ side's (dsvg_ops.hip) */
+int dsv1_rc_pick(dsvg_rc_state *state, int isP, int forced_intra) { return dsvg_rc_pick(state, isP, forced_intra); }
+void dsv1_rc_after(dsvg_rc_state *state, int isP, unsigned pkt_len) { dsvg_rc_after(state, isP, pkt_len); }
+unsigned dsv1_rc_seg_bits(int v) { return dsvg_rc_seg_bits(v); }
+unsigned dsv1_rc_packet_len(unsigned prefix_len, const int dc[3], const unsigned long long total_bits[3])
+{
+    unsigned nb[3];
+    int p;
+    for (p = 0; p < 3; p++) nb[p] = (unsigned)((total_bits[p] + 7) >> 3);       /* as k_rc takes them from the plane sums */
+    return dsvg_rc_packet_len(prefix_len, dc, nb);
+}
+
 static int stage_n(dsv1_batch *b, const void *yuv_host, int nf)
 {
     int rc;

@@ -333,6 +333,19 @@ typedef struct {
 int   dsv1_submit_plan(dsv1_submit_query *q, dsv1_submit_src *src, dsv1_submit_stream *st, const unsigned *luma, const int *n_intra,
                        const dsv1_submit_pic *prev, const dsv1_submit_tables *tb);
 
+/* ---- Rate control (tests; include/dsvg_rc.h as this layer compiles it; restated in tests/rc_model.py) ----
+ * The functions of the average-bitrate chain on the caller's state, no device: the quantiser of the next picture (quality2quant
+ * dsv_encoder.c:70-168), the statistics after a packet (dsv_encoder.c:816-848), the bits of a signed exp-Golomb code, the bytes of a
+ * picture packet whose three planes carry dc[] and total_bits[] payload bits, and -- the host instantiation of what k_rc rewrites in a
+ * job record -- the quantiser tables of a frame quantiser: out[76] = plane-major (qp, qp_h) of the ten scan regions of the three
+ * planes, then hqp[16]. */
+struct dsvg_rc_state;
+int      dsv1_rc_pick(struct dsvg_rc_state *state, int isP, int forced_intra);
+void     dsv1_rc_after(struct dsvg_rc_state *state, int isP, unsigned pkt_len);
+unsigned dsv1_rc_seg_bits(int v);
+unsigned dsv1_rc_packet_len(unsigned prefix_len, const int dc[3], const unsigned long long total_bits[3]);
+void     dsv1_rc_job_tables(int quant, int isP, int out[76]);
+
 /* ---- Source chain plan (tests; csrc/host/dsv1_srcchain_plan.h; restated in tests/srcchain_plan.py) ----
  * What the source side of a session (convert -> levels -> deinterlace or inverse telecine -> denoise -> orient -> reframe -> overlay)
  * decides, as plain data: the sessions answer every setter, reset and seek with dsv1_scp_set and enqueue every call from

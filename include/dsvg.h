@@ -104,6 +104,23 @@ void dsvg_set_allocator(void *(*alloc_fn)(int), void (*free_fn)(void *));
 /* dsv_get_quant hzcc.c:77, dsv_lb2 hzcc.c:437: host scalars */
 int dsvg_get_quant(int q, int isP, int level);
 int dsvg_lb2(unsigned n);
+/* The rate-control kernel on its own (tests; k_rc, include/dsvg_rc.h; restated in tests/rc_model.py): ONE launch_rc(d0, count, mode)
+ * over n job records built on the device from `jobs`, with the nslots states of `states` (in and out).  Every record's quantiser
+ * tables, its quant word and the rc words of its three plane sums start as DSVG_OP_RC_POISON (quant: jobs[].quant, what a mode-1
+ * picture was coded with); out[j] returns them as the launch left them: tables = plane-major (qp, qp_h) of the ten scan regions
+ * of the three planes, then hqp[16].  mode 0: pick for jobs [d0, d0 + count); mode 1: packet size, statistics, and the pick of
+ * jobs[].next (an absolute index, -1: none; may lie outside the launched range).  slot < 0: the job is skipped.  Refused
+ * (DSVG_ERR_ARG) before anything runs: a range outside [0, n), a slot >= nslots, a next >= n. */
+#define DSVG_OP_RC_POISON 0x5A5A5A5A
+typedef struct {
+    int isP, forced_intra, prefix_len, slot, next, quant;
+    int dc[3];
+    int pad;
+    unsigned long long total_bits[3];
+} dsvg_op_rc_job;
+typedef struct { int quant; int tables[76]; int rc[3]; } dsvg_op_rc_out;
+struct dsvg_rc_state;
+int dsvg_op_rc(int n, const dsvg_op_rc_job *jobs, int nslots, struct dsvg_rc_state *states, int d0, int count, int mode, dsvg_op_rc_out *out);
 
 /* ---------------------------------------------------------------------------------------------
  * 2. pipeline level -- device-resident, batched

@@ -82,7 +82,7 @@ DSVG_RC_FN void dsvg_rc_after(dsvg_rc_state *e, int isP, unsigned pkt_len)
         int under, over;
         e->total_P_frame_q += (int)e->rc_quant;
         e->avg_P_frame_q = (int)((unsigned)e->total_P_frame_q / e->bpf_reset);
-        fps = (unsigned)(e->fps_num << 5) / (unsigned)e->fps_den;
+        fps = (unsigned)((e->fps_num << 5) / e->fps_den);              /* an int division (DSV_META's ints), then into the unsigned */
         if (fps == 0) fps = 1;
         need = ((e->bitrate << 5) / fps) >> 3;
         under = pkt_len < (need * 3 / 4);

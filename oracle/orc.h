@@ -187,6 +187,10 @@ void orc_enc_set_next_fnum(orc_encoder *e, unsigned fnum);
 /* a caller's change of the public fields between two frames (quality, bitrate, quality bounds, max_q_step, nudge) / dsv_enc_force_metadata */
 void orc_enc_set_params(orc_encoder *e, const orc_enc_cfg *cfg);
 void orc_enc_force_metadata(orc_encoder *e);
+/* the eight words of rate-control state (rc_quant, bpf_total, bpf_reset, bpf_avg, total_P_frame_q, avg_P_frame_q, last_P_frame_over,
+ * back_into_range: public fields of the reference's struct), set between orc_enc_open and the first frame / read after any frame */
+void orc_enc_set_rc_state(orc_encoder *e, const unsigned st[8]);
+void orc_enc_get_rc_state(const orc_encoder *e, unsigned st[8]);
 /* encode one planar frame; appends 1 or 2 packets to *out (realloc'd), returns bytes appended.
  * if recon != NULL receives the encoder's reconstruction (planar, tightly packed) */
 size_t orc_enc_frame(orc_encoder *e, const uint8_t *yuv, uint8_t **out, size_t *outlen, size_t *outcap,

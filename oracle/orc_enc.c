@@ -117,6 +117,18 @@ void orc_enc_set_params(orc_encoder *e, const orc_enc_cfg *cfg)
     e->c.min_I_frame_quality = cfg->min_I_frame_quality;
 }
 void orc_enc_force_metadata(orc_encoder *e) { e->force_meta = 1; }       /* dsv_enc_force_metadata dsv_encoder.c:760-764 */
+/* the rate-control state ("used internally", dsv_encoder.h:83-93, a public part of the struct): rc_quant, bpf_total, bpf_reset,
+ * bpf_avg, total_P_frame_q, avg_P_frame_q, last_P_frame_over, back_into_range as eight words */
+void orc_enc_set_rc_state(orc_encoder *e, const unsigned st[8])
+{
+    e->rc_quant = st[0]; e->bpf_total = st[1]; e->bpf_reset = st[2]; e->bpf_avg = (int)st[3];
+    e->total_P_q = (int)st[4]; e->avg_P_q = (int)st[5]; e->last_P_over = (int)st[6]; e->back_in_range = (int)st[7];
+}
+void orc_enc_get_rc_state(const orc_encoder *e, unsigned st[8])
+{
+    st[0] = e->rc_quant; st[1] = e->bpf_total; st[2] = e->bpf_reset; st[3] = (unsigned)e->bpf_avg;
+    st[4] = (unsigned)e->total_P_q; st[5] = (unsigned)e->avg_P_q; st[6] = (unsigned)e->last_P_over; st[7] = (unsigned)e->back_in_range;
+}
 
 static void free_pic(pic_state *p)
 {
@@ -490,7 +502,7 @@ size_t orc_enc_frame(orc_encoder *e, const uint8_t *yuv, uint8_t **out, size_t *
         if (isP) {
             e->total_P_q += (int)e->rc_quant;
             e->avg_P_q = (int)((unsigned)e->total_P_q / e->bpf_reset);
-            unsigned fps = (unsigned)(vm->fps_num << 5) / (unsigned)vm->fps_den;
+            unsigned fps = (unsigned)((vm->fps_num << 5) / vm->fps_den);     /* an int division (dsv_encoder.c:826) */
             if (fps == 0) fps = 1;
             unsigned need = ((e->c.bitrate << 5) / fps) >> 3;
             int under = pkt_len < (need * 3 / 4);

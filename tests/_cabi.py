@@ -293,6 +293,8 @@ def load_orc():
         L.orc_enc_set_next_fnum.argtypes = [C.c_void_p, C.c_uint]
         L.orc_enc_set_params.argtypes = [C.c_void_p, C.POINTER(EncCfg)]
         L.orc_enc_force_metadata.argtypes = [C.c_void_p]
+        L.orc_enc_set_rc_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
+        L.orc_enc_get_rc_state.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
         L.orc_enc_last_mvs.restype = C.POINTER(MV)
         L.orc_enc_last_mvs.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.orc_enc_last_stable.restype = C.POINTER(C.c_uint8)
@@ -383,11 +385,27 @@ def orc_cfg(w, h, fmt, qp=85, gop=12, rc_mode_cli=1, kbps=0, scd=1, ipct=50, pyr
 PARAM_FIELDS = ("quality", "bitrate", "rc_high_motion_nudge", "max_q_step", "min_quality", "max_quality", "min_I_frame_quality")
 
 
-def orc_encode(clip, cfg, want_recon=False, start_fnum=0, eos=True, changes=None):
-    """encode a clip with the oracle session layer; returns (stream bytes, [recon frames])"""
+RC_STATE_FIELDS = ("rc_quant", "bpf_total", "bpf_reset", "bpf_avg", "total_P_frame_q", "avg_P_frame_q", "last_P_frame_over", "back_into_range")
+
+
+def _rc_words(get):
+    return tuple(int(get(f)) & 0xFFFFFFFF for f in RC_STATE_FIELDS)
+
+
+def orc_encode(clip, cfg, want_recon=False, start_fnum=0, eos=True, changes=None, rc_seed=None, states_out=None):
+    """encode a clip with the oracle session layer; returns (stream bytes, [recon frames]).  rc_seed: {state field: value} written
+    into the opened encoder before the first frame; states_out: a list that receives the eight state words after every frame"""
     L = load_orc()
     e = L.orc_enc_open(C.byref(cfg))
     L.orc_enc_set_next_fnum(e, start_fnum)
+    st8 = (C.c_uint * 8)()
+    if rc_seed:
+        assert set(rc_seed) <= set(RC_STATE_FIELDS), rc_seed
+        L.orc_enc_get_rc_state(e, st8)
+        for i, f in enumerate(RC_STATE_FIELDS):
+            if f in rc_seed:
+                st8[i] = rc_seed[f] & 0xFFFFFFFF
+        L.orc_enc_set_rc_state(e, st8)
     out = C.c_void_p(None)
     n = C.c_size_t(0)
     cap = C.c_size_t(0)
@@ -408,6 +426,9 @@ def orc_encode(clip, cfg, want_recon=False, start_fnum=0, eos=True, changes=None
                         rec.ctypes.data if want_recon else None)
         if want_recon:
             recs.append(rec)
+        if states_out is not None:
+            L.orc_enc_get_rc_state(e, st8)
+            states_out.append(tuple(st8))
     if eos:
         L.orc_enc_eos(e, C.byref(out), C.byref(n), C.byref(cap))
     data = C.string_at(out.value, n.value)
@@ -468,15 +489,21 @@ def ref_cli_decode(stream, tmpdir):
 FMT_CLI = {SUBSAMP_444: 0, SUBSAMP_422: 1, SUBSAMP_420: 2, SUBSAMP_411: 3}
 
 
-def drive_dsv_enc(L, enc, clip, w, h, fmt, changes=None, flush_calls=False):
+def drive_dsv_enc(L, enc, clip, w, h, fmt, changes=None, flush_calls=False, rc_seed=None, states_out=None):
     """the reference's frame-at-a-time API (dsv_encoder.h:112-121) on library L (the product or oracle/_ref's libdsv1ref.so: same
     struct layout) driven the way dsv_main.c:506-537 does; `changes` rewrites the encoder's public fields between calls.
+    rc_seed: {state field: value} written into the struct after dsv_enc_start (which itself only writes rc_quant and avg_P_frame_q)
+    and before the first frame; states_out: a list that receives the struct's eight state words after every call (and, with
+    flush_calls, once more after the flush: a pipelined library's struct is final only then).
     Returns (stream bytes, buffers returned per call)."""
     L.dsv_load_planar_frame.restype = C.c_void_p
     L.dsv_load_planar_frame.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int]
     L.dsv_enc.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.dsv_enc.restype = C.c_int
     L.dsv_enc_start(C.byref(enc))
+    for f, v in (rc_seed or {}).items():
+        assert f in RC_STATE_FIELDS, f
+        setattr(enc, f, v)
     out = b""
     counts = []
     bufs = (Buf * 4)()
@@ -502,13 +529,61 @@ def drive_dsv_enc(L, enc, clip, w, h, fmt, changes=None, flush_calls=False):
         counts.append(nb)
         take(nb)
         scratch[...] = 0xA5                              # ... and overwrites it right after the call
+        if states_out is not None:
+            states_out.append(_rc_words(lambda f: getattr(enc, f)))
     if flush_calls:
         while True:
             nb = L.dsv_enc(C.byref(enc), None, bufs) & 3
             if not nb:
                 break
             take(nb)
+        if states_out is not None:
+            states_out.append(_rc_words(lambda f: getattr(enc, f)))
     L.dsv_enc_end_of_stream(C.byref(enc), bufs)
     take(1)
     L.dsv_enc_free(C.byref(enc))
     return out, counts
+
+
+# ---- rate control (include/dsvg_rc.h; tests/rc_model.py) ----------------------------------------------------------------------------
+class RcState(C.Structure):          # dsvg_rc_state: sixteen words, rc_model.FIELDS in order
+    _fields_ = [("rc_quant", C.c_uint), ("bpf_total", C.c_uint), ("bpf_reset", C.c_uint), ("bpf_avg", C.c_int), ("total_P_frame_q", C.c_int),
+                ("avg_P_frame_q", C.c_int), ("last_P_frame_over", C.c_int), ("back_into_range", C.c_int), ("bitrate", C.c_uint),
+                ("fps_num", C.c_int), ("fps_den", C.c_int), ("rc_high_motion_nudge", C.c_int), ("max_q_step", C.c_int),
+                ("min_quality", C.c_int), ("max_quality", C.c_int), ("min_I_frame_quality", C.c_int)]
+
+
+class OpRcJob(C.Structure):          # dsvg_op_rc_job
+    _fields_ = [("isP", C.c_int), ("forced_intra", C.c_int), ("prefix_len", C.c_int), ("slot", C.c_int), ("next", C.c_int), ("quant", C.c_int),
+                ("dc", C.c_int * 3), ("pad", C.c_int), ("total_bits", C.c_ulonglong * 3)]
+
+
+class OpRcOut(C.Structure):          # dsvg_op_rc_out
+    _fields_ = [("quant", C.c_int), ("tables", C.c_int * 76), ("rc", C.c_int * 3)]
+
+
+OP_RC_POISON = 0x5A5A5A5A
+
+
+def rc_state_words(states):
+    """(n, 16) uint32 array of the words of a list of rc_model states"""
+    return np.array([s.words() for s in states], dtype=np.uint32).reshape(-1, 16)
+
+
+def load_prod_rc():
+    """the product library with the rate-control entry points typed (no device needed for the dsv1_rc_* ones)"""
+    L = load_prod()
+    u32p = C.POINTER(C.c_uint32)
+    L.dsv1_rc_pick.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.dsv1_rc_pick.restype = C.c_int
+    L.dsv1_rc_after.argtypes = [C.c_void_p, C.c_int, C.c_uint]
+    L.dsv1_rc_after.restype = None
+    L.dsv1_rc_seg_bits.argtypes = [C.c_int]
+    L.dsv1_rc_seg_bits.restype = C.c_uint
+    L.dsv1_rc_packet_len.argtypes = [C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]
+    L.dsv1_rc_packet_len.restype = C.c_uint
+    L.dsv1_rc_job_tables.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int)]
+    L.dsv1_rc_job_tables.restype = None
+    L.dsvg_op_rc.argtypes = [C.c_int, C.POINTER(OpRcJob), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(OpRcOut)]
+    L.dsvg_op_rc.restype = C.c_int
+    return L

@@ -61,7 +61,7 @@ def ref_encode_clip(clip, w, h, fmt, kw):
     return out
 
 
-REF_ANSWER_TESTS = ("test_oracle_vs_ref.py", "test_halfpel_oracle.py", "test_blocksize_oracle.py", "test_hme_cases_host.py")
+REF_ANSWER_TESTS = ("test_oracle_vs_ref.py", "test_halfpel_oracle.py", "test_blocksize_oracle.py", "test_hme_cases_host.py", "test_rc_ref.py")
 
 
 def ref_answers():
