@@ -207,6 +207,45 @@ class RgbFormat(_C.Structure):
         super().__init__(order, matrix, full_range, upsample, (_C.c_int * 3)(*pitch), frame_bytes)
 
 
+TRANSFER_PQ, TRANSFER_HLG = 0, 1   # DSV1_TRANSFER_*
+TONEMAP_CLIP, TONEMAP_REINHARD, TONEMAP_BT2390 = 0, 1, 2   # DSV1_TONEMAP_*
+HDR_ONE, HDR_NBUCKETS = 1 << 20, 3329
+
+
+class Hdr(_C.Structure):
+    """dsv1_hdr: the settings of an HDR import -- transfer (TRANSFER_*), matrix / full_range of the source signal, gamut (1: BT.2020
+    primaries to BT.709), curve (TONEMAP_*), peak_nits 100..10000, white_nits (the HDR level that becomes SDR 1.0; 0 = 203),
+    out_matrix / out_full_range of the SDR signal.  hdr_build makes the tables of them; include/dsv1_api.h, HDR sources, has the
+    definition."""
+    _fields_ = [(k, _C.c_int) for k in ("transfer", "matrix", "full_range", "gamut", "curve", "peak_nits", "white_nits", "out_matrix",
+                                        "out_full_range")]
+
+    def __init__(self, transfer=TRANSFER_PQ, matrix=MATRIX_BT2020, full_range=0, gamut=1, curve=TONEMAP_BT2390, peak_nits=1000, white_nits=203,
+                 out_matrix=MATRIX_BT709, out_full_range=0):
+        super().__init__(transfer, matrix, full_range, gamut, curve, peak_nits, white_nits, out_matrix, out_full_range)
+
+
+class HdrTables(_C.Structure):
+    """dsv1_hdr_tables: what the HDR import's pixel path reads -- a plain struct a caller may edit (own curve, own look)"""
+    _fields_ = [("ycc", _C.c_int32 * 5), ("in_oy", _C.c_int32), ("in_oc", _C.c_int32), ("eotf", _C.c_uint32 * 4096), ("gamut", _C.c_int32 * 9),
+                ("gain", _C.c_uint32 * HDR_NBUCKETS), ("oetf", _C.c_uint16 * HDR_NBUCKETS), ("fwd", _C.c_int32 * 9), ("ybias", _C.c_int32),
+                ("cbias", _C.c_int32)]
+
+    def as_dict(self):
+        """the tables as numpy arrays / ints (copies)"""
+        return {k: (_np.array(getattr(self, k)[:]) if hasattr(getattr(self, k), "__len__") else int(getattr(self, k))) for k, _ in self._fields_}
+
+    @classmethod
+    def from_dict(cls, d):
+        t = cls()
+        for k, ty in cls._fields_:
+            if hasattr(ty, "_length_"):
+                getattr(t, k)[:] = [int(x) for x in d[k]]
+            else:
+                setattr(t, k, int(d[k]))
+        return t
+
+
 DEINT_FRAME, DEINT_FIELD = 0, 1
 
 
@@ -477,6 +516,15 @@ def lib():
         L.dsv1_resladder_open_rgb.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(RgbFormat), _C.POINTER(ResRung), _C.c_int,
                                               _C.c_int, _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_decbatch_set_output_rgb.argtypes = [_C.c_void_p, _C.POINTER(RgbFormat)]
+        L.dsv1_hdr_valid.argtypes = [_C.POINTER(Hdr)]
+        L.dsv1_hdr_build.argtypes = [_C.POINTER(Hdr), _C.POINTER(HdrTables)]
+        L.dsv1_hdr_tables_valid.argtypes = [_C.POINTER(HdrTables)]
+        L.dsv1_hdr_cidx_of.argtypes = [_C.c_uint32]
+        L.dsv1_hdr_import_clip.argtypes = [_C.c_int, _C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p,
+                                           _C.POINTER(HdrTables), _C.c_int, _C.c_int]
+        L.dsv1_batch_set_source_hdr.argtypes = [_C.c_void_p, _C.POINTER(PixFormat), _C.c_int, _C.POINTER(HdrTables), _C.c_int]
+        L.dsv1_resladder_open_hdr.argtypes = [_C.POINTER(_C.c_void_p), _C.POINTER(Meta), _C.POINTER(PixFormat), _C.c_int, _C.POINTER(HdrTables),
+                                              _C.c_int, _C.POINTER(ResRung), _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int]
         L.dsv1_deint_out_frames.argtypes = [_C.POINTER(Deint), _C.c_int]
         L.dsv1_deinterlace_clip.argtypes = [_C.c_int, _C.c_void_p, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_void_p, _C.c_void_p,
                                             _C.POINTER(Deint), _C.c_int]
@@ -1048,6 +1096,13 @@ class Batch:
         GPU to the batch's subsampling; None switches back to packed planar 8-bit.  Between batches only; replaces a source format
         set before.  The input-length check follows."""
         _chk(self.L.dsv1_batch_set_source_rgb(self.h, _C.byref(rf) if rf is not None else None), "dsv1_batch_set_source_rgb")
+
+    def set_source_hdr(self, pf, tables, src_subsamp=None, upsample=CHROMA_LINEAR):
+        """from the next submit on, encode() / submit() take HDR clips of PixFormat pf (depth 10, 12 or 16) at src_subsamp (None: the
+        batch's), tone-mapped to SDR on the GPU by HdrTables `tables` (dsv1_batch_set_source_hdr); tables None switches back to packed
+        planar 8-bit.  Between batches only; replaces a source format or RGB format set before.  The input-length check follows."""
+        _chk(self.L.dsv1_batch_set_source_hdr(self.h, _C.byref(pf) if pf is not None else None, self.fmt if src_subsamp is None else src_subsamp,
+                                              _C.byref(tables) if tables is not None else None, upsample), "dsv1_batch_set_source_hdr")
 
     def dropped_recons(self):
         """(dropped, remedied): reference pictures coded without a reconstruction because nobody predicts from them / coded again
@@ -1998,6 +2053,44 @@ def rgb_export_clip(clip, w, h, fmt, rf, device=0, n=None, out=None):
     return res
 
 
+def hdr_build(hd):
+    """the HdrTables of Hdr settings hd (dsv1_hdr_build; host only); ValueError for invalid settings"""
+    t = HdrTables()
+    if lib().dsv1_hdr_build(_C.byref(hd), _C.byref(t)) != 0:
+        raise ValueError("not valid HDR settings")
+    return t
+
+
+def hdr_tables_valid(tables):
+    """whether every entry is inside the bounds that keep the pixel path from overflowing (dsv1_hdr_tables_valid)"""
+    return bool(lib().dsv1_hdr_tables_valid(_C.byref(tables)))
+
+
+def hdr_cidx(v):
+    """the bucket 0..3328 of a linear value v <= 2^20 (dsv1_hdr_cidx: the header's one text); ValueError above"""
+    i = lib().dsv1_hdr_cidx_of(int(v)) if 0 <= int(v) <= HDR_ONE else -1
+    if i < 0:
+        raise ValueError("no bucket for %r" % (v,))
+    return i
+
+
+def hdr_import_clip(clip, pf, w, h, src_subsamp, fmt, tables, upsample=CHROMA_LINEAR, device=0, n=None, out=None):
+    """HDR frames of PixFormat pf (depth 10, 12 or 16) at src_subsamp to packed planar 8-bit SDR Y, Cb, Cr at subsampling fmt on the GPU
+    by HdrTables `tables` (dsv1_hdr_import_clip): clip numpy uint8 (host; a whole number of frames, the last one may end with its
+    planes), or a device pointer with n frames and `out` a device pointer for the result.  Host input returns numpy uint8
+    [frames][planar frame_bytes]."""
+    L = lib()
+    dfb = w * h + 2 * _chroma_size(w, h, fmt)
+    if n is not None:
+        _chk(L.dsv1_hdr_import_clip(device, clip, _C.byref(pf), w, h, src_subsamp, fmt, n, out, _C.byref(tables), upsample, 1), "dsv1_hdr_import_clip")
+        return out
+    a, frames = _host_clip(clip, pix_frame_bytes(pf, w, h, src_subsamp), "a clip of this format", raw=True)
+    res = _np.zeros((frames, dfb), dtype=_np.uint8)
+    _chk(L.dsv1_hdr_import_clip(device, a.ctypes.data, _C.byref(pf), w, h, src_subsamp, fmt, frames, res.ctypes.data, _C.byref(tables), upsample, 0),
+         "dsv1_hdr_import_clip")
+    return res
+
+
 def scale_taps(S, D, filt):
     """taps of one axis of the resampler (dsv1_scale_taps); ValueError outside 1 <= S / D <= 8"""
     t = lib().dsv1_scale_taps(S, D, filt)
@@ -2068,14 +2161,18 @@ class ResLadder:
     k = s * Ntot + off[g] + rate.  sse() / ssim_fx() are against the scaled source of each stream."""
 
     def __init__(self, w, h, fmt, geoms, nsources, frames_per_call, filt=SCALE_CUBIC, device=0, src_format=None, src_rgb=None,
-                 src_subsamp=None, reframe=None, orient=0):
+                 src_subsamp=None, reframe=None, orient=0, src_hdr=None, src_upsample=CHROMA_LINEAR):
         """src_format: the PixFormat of the source clips (dsv1_resladder_open_src; None: packed planar 8-bit); src_rgb: their RgbFormat
         instead (dsv1_resladder_open_rgb); src_subsamp: the subsampling of the source clips where it is not fmt
         (dsv1_resladder_open_src_sub) -- 4:4:4 or 4:2:2, chroma halved to fmt by the converter; reframe: a Reframe of the w x h
         sources (dsv1_resladder_open_reframed), the last pass in front of the scales: its canvas stands for the source from there on
         (self.width x self.height, the rungs' ratio limits, src_psnr / src_ssim), the clips handed in stay w x h; orient: an Orient
         code (dsv1_resladder_open_oriented) applied to the w x h sources in front of the reframe, whose input is then the oriented
-        geometry -- without a reframe the oriented picture stands for the source"""
+        geometry -- without a reframe the oriented picture stands for the source; src_hdr: the HdrTables of an HDR import of
+        src_format (depth 10, 12 or 16) at src_subsamp, chroma brought up by src_upsample (dsv1_resladder_open_hdr; not with
+        src_rgb, reframe or orient)"""
+        if src_hdr is not None and (src_format is None or src_rgb is not None or reframe is not None or orient):
+            raise ValueError("src_hdr goes with src_format, and without src_rgb, reframe and orient")
         if src_format is not None and src_rgb is not None:
             raise ValueError("src_format and src_rgb exclude each other")
         if src_subsamp is not None and src_rgb is not None:
@@ -2090,7 +2187,11 @@ class ResLadder:
         rr = (ResRung * max(len(geoms), 1))(*[ResRung(gw, gh, len(r), a) for (gw, gh, r), a in zip(geoms, self._arrs)])
         meta = Meta()
         meta.width, meta.height, meta.subsamp = w, h, fmt
-        if orient:
+        if src_hdr is not None:
+            _chk(self.L.dsv1_resladder_open_hdr(_C.byref(self.h), _C.byref(meta), _C.byref(src_format), fmt if src_subsamp is None else src_subsamp,
+                                                _C.byref(src_hdr), src_upsample, rr, len(geoms), device, nsources, frames_per_call, filt),
+                 "dsv1_resladder_open_hdr")
+        elif orient:
             _chk(self.L.dsv1_resladder_open_oriented(_C.byref(self.h), _C.byref(meta), orient, None if reframe is None else _C.byref(reframe),
                                                      None if src_format is None else _C.byref(src_format),
                                                      fmt if src_subsamp is None else src_subsamp,

@@ -1,5 +1,5 @@
 /* dsvg_pixfmt.h -- private: the layout a source pixel format (include/dsv1_api.h, dsv1_pix_format) works out to for one geometry, and
- * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip, k_levels.hip, k_overlay.hip).  Read by the C session layer and by the HIP plumbing. */
+ * the device side of the source passes (dsvg_lane.hip, k_pixfmt.hip, k_rgb.hip, k_hdr.hip, k_deint.hip, k_ivtc.hip, k_denoise.hip, k_reframe.hip, k_orient.hip, k_levels.hip, k_overlay.hip).  Read by the C session layer and by the HIP plumbing. */
 #ifndef DSVG_PIXFMT_H
 #define DSVG_PIXFMT_H
 
@@ -99,6 +99,36 @@ int dsv1_rgbout_of(const dsv1_rgb_format *rf, int w, int h, int subsamp, dsvg_pi
 int  dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv1_rgb_layout *L);
 /* the pass itself, on a stream of the caller's: nframes RGB frames of layout *L -> tightly packed planar frames (device pointers) */
 int  dsvg_rgb_import_run(void *stream, const dsv1_rgb_layout *L, const void *src_dev, int nframes, void *dst_dev);
+
+/* ---- HDR sources (include/dsv1_api.h, HDR sources; k_hdr.hip; host side: host/dsv1_hdr.c) ----
+ * A deep pixel format resolved for one geometry and one pair of subsamplings: the source planes (semi: 0 planar, 1 interleaved
+ * (U, V), 2 (V, U); the chroma planes' offsets and pitches in [1] and [2], the same plane twice where interleaved), the sample rule
+ * (word >> vshift) & vmask then min(1023, (v + rnd) >> rs), and the dims of the chroma planes on both sides. */
+typedef struct {
+    int w, h;
+    int shs, svs, scw, sch;     /* the source's chroma shifts and dims */
+    int dhs, dvs, ocw, och;     /* the output's */
+    int semi;
+    int vshift, vmask, rs, rnd;
+    size_t off[3], pitch[3];
+    size_t frame_bytes;         /* source frame to frame */
+    size_t planes_bytes;        /* what a source frame holds */
+    size_t out_frame_bytes;     /* the tightly packed planar frame */
+} dsv1_hdr_layout;
+/* DSVG_OK, or DSVG_ERR_ARG for whatever include/dsv1_api.h calls invalid; no device is looked at */
+int  dsv1_hdr_layout_of(const dsv1_pix_format *pf, int w, int h, int src_subsamp, int subsamp, dsv1_hdr_layout *L);
+/* a dsvg_pixconv whose pass is the HDR import (k_hdr.hip); it owns the tables' device copy.  upsample: DSV1_CHROMA_* */
+int  dsvg_pixconv_create_hdr(dsvg_pixconv **out, int device, const dsv1_hdr_layout *L, const dsv1_hdr_tables *tables, int upsample);
+/* the pass itself, on a stream of the caller's: nframes frames of layout *L -> tightly packed planar frames (device pointers).
+ * tab_dev: DSVG_HDR_TAB_WORDS dwords in device memory as dsvg_hdr_tab_pack lays the three lookup tables out; rows: the small tables,
+ * which travel as kernel arguments (dsvg_hdr_rows_of); cus: the device's CUs -- the launch is as many workgroups as are resident at
+ * once, each of which stages the lookup tables once and walks items of the whole call */
+#define DSVG_HDR_TAB_WORDS (4096 + DSV1_HDR_NBUCKETS + (DSV1_HDR_NBUCKETS + 1) / 2)
+typedef struct { int32_t ycc[5], in_oy, in_oc, gamut[9], fwd[9], ybias, cbias; } dsvg_hdr_rows;
+void dsvg_hdr_tab_pack(const dsv1_hdr_tables *tables, uint32_t *words);
+void dsvg_hdr_rows_of(const dsv1_hdr_tables *tables, dsvg_hdr_rows *rows);
+int  dsvg_hdr_import_run(void *stream, const dsv1_hdr_layout *L, const dsvg_hdr_rows *rows, const uint32_t *tab_dev, int upsample, int cus,
+                         const void *src_dev, int nframes, void *dst_dev);
 
 
 /* ---- deinterlacing (include/dsv1_api.h, Deinterlacing; k_deint.hip; host side: host/dsv1_deint.c) ----

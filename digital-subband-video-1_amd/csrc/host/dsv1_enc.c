@@ -1190,11 +1190,17 @@ int dsv1_batch_set_source_format_sub(dsv1_batch *b, const dsv1_pix_format *pf, i
 {
     return b ? set_source_format(b, pf, src_subsamp, "dsv1_batch_set_source_format_sub") : DSVG_ERR_ARG;
 }
-/* the RGB twin: the RGB import pass in the converter's place; the two setters replace each other */
+/* the RGB twin: the RGB import pass in the converter's place; the source setters replace each other */
 int dsv1_batch_set_source_rgb(dsv1_batch *b, const dsv1_rgb_format *rf)
 {
     dsv1_src_format f = {NULL, 0, rf};
     return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_rgb", BATCH_BUSY(b), DSV1_SRC_CONVERT, &f) : DSVG_ERR_ARG;
+}
+/* the HDR twin: the HDR import pass in the converter's place for clips of *pf at src_subsamp; NULL tables: no converter */
+int dsv1_batch_set_source_hdr(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp, const dsv1_hdr_tables *tables, int upsample)
+{
+    dsv1_src_format f = {tables ? pf : NULL, src_subsamp, NULL, tables, upsample};
+    return b ? dsv1_srcchain_request(&b->src, "dsv1_batch_set_source_hdr", BATCH_BUSY(b), DSV1_SRC_CONVERT, &f) : DSVG_ERR_ARG;
 }
 int dsv1_batch_set_source_levels(dsv1_batch *b, const dsv1_levels *lv)
 {

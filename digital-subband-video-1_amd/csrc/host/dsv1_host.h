@@ -144,7 +144,8 @@ int  dsv1_srcchain_lane(dsv1_srcchain *c);             /* creates the lane where
  * session's (batches in flight or clips staged; calls in flight).
  * _signal: a reset (op DSV1_SC_OP_RESET: a discontinuity in `source`, -1 every source) or the overlays' seek (DSV1_SC_OP_SEEK: the
  * next picture of `source` is t), by the same plan and log line. */
-typedef struct { const dsv1_pix_format *pf; int src_subsamp; const dsv1_rgb_format *rgb; } dsv1_src_format;    /* one of them, or neither: no converter */
+/* pf, or rgb, or hdr (the tables of an HDR import of *pf at src_subsamp, chroma brought up by `upsample`), or none of them: no converter */
+typedef struct { const dsv1_pix_format *pf; int src_subsamp; const dsv1_rgb_format *rgb; const dsv1_hdr_tables *hdr; int upsample; } dsv1_src_format;
 typedef struct { const dsv1_overlay *list; int n; } dsv1_src_overlays;
 int  dsv1_srcchain_request(dsv1_srcchain *c, const char *who, int busy, int kind, const void *arg);
 int  dsv1_srcchain_signal(dsv1_srcchain *c, const char *who, int busy, int op, int kind, int source, int64_t t);

@@ -169,13 +169,13 @@ int dsv1_resladder_open(dsv1_resladder **out, const DSV_META *src, const dsv1_re
 }
 
 static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *frm, const dsv1_pix_format *pf,
-                              int src_subsamp, const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
-                              int frames_per_call, int filter);
+                              int src_subsamp, const dsv1_rgb_format *rf, const dsv1_hdr_tables *ht, int upsample, const dsv1_res_rung *rungs,
+                              int ngeoms, int device, int nsources, int frames_per_call, int filter);
 
 int dsv1_resladder_open_src(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, const dsv1_res_rung *rungs, int ngeoms,
                             int device, int nsources, int frames_per_call, int filter)
 {
-    return resladder_open_fmt(out, src, 0, NULL, pf, src ? src->subsamp : 0, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, 0, NULL, pf, src ? src->subsamp : 0, NULL, NULL, 0, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* sources at src_subsamp: the converter halves their chroma to src->subsamp on the way */
@@ -184,7 +184,7 @@ int dsv1_resladder_open_src_sub(dsv1_resladder **out, const DSV_META *src, const
 {
     static const dsv1_pix_format planar8 = {DSV1_PIX_PLANAR, 8, 0, {0, 0, 0}, 0};
     if (!pf && src && src_subsamp != src->subsamp) pf = &planar8;
-    return resladder_open_fmt(out, src, 0, NULL, pf, src_subsamp, NULL, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, 0, NULL, pf, src_subsamp, NULL, NULL, 0, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* RGB sources: the RGB import pass (k_rgb.hip) in the converter's place, everything else as dsv1_resladder_open_src */
@@ -193,7 +193,7 @@ int dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const dsv
 {
     if (out) *out = NULL;
     if (!rf) return DSVG_ERR_ARG;
-    return resladder_open_fmt(out, src, 0, NULL, NULL, src ? src->subsamp : 0, rf, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, 0, NULL, NULL, src ? src->subsamp : 0, rf, NULL, 0, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
 /* sources of geometry *src = the reframe's input, reframed behind the other passes: the CANVAS stands for the source from the scales on */
@@ -224,12 +224,22 @@ int dsv1_resladder_open_oriented(dsv1_resladder **out, const DSV_META *src, int 
     }
     if (rgb) src_subsamp = src->subsamp;
     else if (!pf && src_subsamp != src->subsamp) pf = &planar8;
-    return resladder_open_fmt(out, src, orient, rf, pf, src_subsamp, rgb, rungs, ngeoms, device, nsources, frames_per_call, filter);
+    return resladder_open_fmt(out, src, orient, rf, pf, src_subsamp, rgb, NULL, 0, rungs, ngeoms, device, nsources, frames_per_call, filter);
 }
 
+/* HDR sources: the HDR import pass (k_hdr.hip) of *pf at src_subsamp in the converter's place, everything else as dsv1_resladder_open_src_sub */
+int dsv1_resladder_open_hdr(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp, const dsv1_hdr_tables *tables,
+                            int upsample, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources, int frames_per_call, int filter)
+{
+    if (out) *out = NULL;
+    if (!pf || !tables) return DSVG_ERR_ARG;
+    return resladder_open_fmt(out, src, 0, NULL, pf, src_subsamp, NULL, tables, upsample, rungs, ngeoms, device, nsources, frames_per_call, filter);
+}
+
+/* ht: the tables of an HDR import of *pf (then the pixel format is never "the default") */
 static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int orient, const dsv1_reframe *frm, const dsv1_pix_format *pf,
-                              int src_subsamp, const dsv1_rgb_format *rf, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
-                              int frames_per_call, int filter)
+                              int src_subsamp, const dsv1_rgb_format *rf, const dsv1_hdr_tables *ht, int upsample, const dsv1_res_rung *rungs,
+                              int ngeoms, int device, int nsources, int frames_per_call, int filter)
 {
     /* cw x ch: what stands for the source behind the chain -- the reframe's canvas, or the source itself, oriented (the callers pass a
      * valid code); the passes in front of the orientation and the caller's clips are src->width x src->height */
@@ -238,6 +248,7 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int ori
     dsv1_resladder *r;
     dsv1_pix_layout pl;
     dsv1_rgb_layout rl;
+    dsv1_hdr_layout hl;
     dsv1_src_format fmt;
     int g, k, rc, ntot = 0, nscaled = 0, maxr = 0, dw[DSV1_MAX_GEOMS], dh[DSV1_MAX_GEOMS];
     if (out) *out = NULL;
@@ -245,12 +256,18 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int ori
     if (!out || !src || !rungs || ngeoms < 1 || ngeoms > DSV1_MAX_GEOMS || nsources < 1 || frames_per_call < 1) return DSVG_ERR_ARG;
     if (filter != DSV1_SCALE_TENT && filter != DSV1_SCALE_CUBIC) return DSVG_ERR_ARG;
     if (src->width < 1 || src->height < 1) return DSVG_ERR_ARG;
+    if (ht && ((upsample != DSV1_CHROMA_REPLICATE && upsample != DSV1_CHROMA_LINEAR) || !dsv1_hdr_tables_valid(ht) ||
+               dsv1_hdr_layout_of(pf, src->width, src->height, src_subsamp, src->subsamp, &hl))) {
+        dsv1_log(1, "dsv1_resladder_open_hdr: not a valid HDR source for %dx%d sources of subsampling 0x%x into 0x%x", src->width, src->height,
+                 src_subsamp, src->subsamp);
+        return DSVG_ERR_ARG;
+    }
     if (pf && dsv1_pix_layout_of(pf, src->width, src->height, src_subsamp, src->subsamp, &pl)) {
         dsv1_log(1, "dsv1_resladder_open_src: not a valid pixel format for %dx%d sources of subsampling 0x%x into 0x%x", src->width, src->height,
                  src_subsamp, src->subsamp);
         return DSVG_ERR_ARG;
     }
-    if (pf && src_subsamp == src->subsamp && dsv1_pix_is_default(pf, src->width, src->height, src->subsamp)) pf = NULL;
+    if (pf && !ht && src_subsamp == src->subsamp && dsv1_pix_is_default(pf, src->width, src->height, src->subsamp)) pf = NULL;
     if (rf && dsv1_rgb_layout_of(rf, src->width, src->height, src->subsamp, &rl)) {
         dsv1_log(1, "dsv1_resladder_open_rgb: not a valid RGB format for %dx%d sources of subsampling 0x%x", src->width, src->height, src->subsamp);
         return DSVG_ERR_ARG;
@@ -304,7 +321,7 @@ static int resladder_open_fmt(dsv1_resladder **out, const DSV_META *src, int ori
         if (!r->same[g]) { r->scale_idx[g] = nscaled; dw[nscaled] = r->w[g]; dh[nscaled] = r->h[g]; nscaled++; }
     }
     /* the lane exists even when no geometry is scaled: host input is uploaded through it */
-    fmt.pf = pf; fmt.src_subsamp = src_subsamp; fmt.rgb = rf;
+    fmt.pf = pf; fmt.src_subsamp = src_subsamp; fmt.rgb = rf; fmt.hdr = ht; fmt.upsample = upsample;
     if ((rc = dsvg_scaler_create(&r->sc, device, cw, ch, src->subsamp, nscaled, dw, dh, filter)) ||
         (rc = dsv1_srcchain_lane(&r->src)) || (rc = dsv1_srcchain_request(&r->src, "dsv1_resladder_open", 0, DSV1_SRC_REFRAME, frm)) ||
         (rc = dsv1_srcchain_request(&r->src, "dsv1_resladder_open", 0, DSV1_SRC_ORIENT, &orient)) ||

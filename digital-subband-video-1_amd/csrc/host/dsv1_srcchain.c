@@ -14,6 +14,14 @@ static void convert_resolve(const dsv1_srcchain *c, const void *arg, dsv1_srccha
     const dsv1_src_format *f = (const dsv1_src_format *)arg;
     dsv1_pix_layout L;
     dsv1_rgb_layout R;
+    dsv1_hdr_layout H;
+    if (f->hdr) {
+        q->mode = 2;
+        q->valid = (f->upsample == DSV1_CHROMA_REPLICATE || f->upsample == DSV1_CHROMA_LINEAR) && dsv1_hdr_tables_valid(f->hdr) &&
+                   !dsv1_hdr_layout_of(f->pf, c->g.w, c->g.h, f->src_subsamp, c->st.subsamp, &H);
+        q->frame_bytes = q->valid ? H.frame_bytes : 0;
+        return;
+    }
     if (!f->pf && !f->rgb) { q->set = 0; return; }
     q->mode = f->rgb != NULL;
     /* (the frames that come in: the session's geometry, or the input of the reframe set before, turned back by the orientation) */
@@ -52,6 +60,10 @@ static int convert_create(const dsv1_srcchain *c, const dsv1_srcchain_geom *g, c
     const dsv1_src_format *f = (const dsv1_src_format *)arg;
     dsv1_pix_layout L;
     dsv1_rgb_layout R;
+    dsv1_hdr_layout H;
+    if (f->hdr)
+        return dsv1_hdr_layout_of(f->pf, g->w, g->h, f->src_subsamp, c->st.subsamp, &H) ? DSVG_ERR_ARG
+                                                                                        : dsvg_pixconv_create_hdr((dsvg_pixconv **)out, c->device, &H, f->hdr, f->upsample);
     if (f->rgb) return dsv1_rgb_layout_of(f->rgb, g->w, g->h, c->st.subsamp, &R) ? DSVG_ERR_ARG : dsvg_pixconv_create_rgb((dsvg_pixconv **)out, c->device, &R);
     return dsv1_pix_layout_of(f->pf, g->w, g->h, f->src_subsamp, c->st.subsamp, &L) ? DSVG_ERR_ARG : dsvg_pixconv_create((dsvg_pixconv **)out, c->device, &L);
 }

@@ -29,6 +29,7 @@
 // gives both luma rows and the one chroma row -- every source byte is loaded once.  The repeated last row is an edge select of the
 // row pointer; the repeated last column takes the byte path, which clamps the index: no load past the last sample of a row.
 #include <algorithm>
+#include <vector>
 #include "dsvg_host.hpp"
 #include "dsvg_pixfmt.h"
 
@@ -322,9 +323,19 @@ struct dsvg_pixconv {
     int nblocks = 0;
     bool rgb = false;                    // the pass is the RGB import (k_rgb.hip) of layout R; L, P and nblocks are not used
     dsv1_rgb_layout R;
+    bool hdr = false;                    // the pass is the HDR import (k_hdr.hip) of layout H; L, P and nblocks are not used
+    dsv1_hdr_layout H;
+    dsvg_hdr_rows hdr_rows;              // the small tables: kernel arguments
+    uint32_t *hdr_tab = nullptr;         // the lookup tables as the kernel stages them, device memory
+    int hdr_upsample = 0, hdr_cus = 0;
 };
 
-extern "C" void dsvg_pixconv_destroy(dsvg_pixconv *c) { delete c; }
+extern "C" void dsvg_pixconv_destroy(dsvg_pixconv *c)
+{
+    if (!c) return;
+    if (c->hdr_tab) { (void)hipSetDevice(c->device); (void)hipFree(c->hdr_tab); }
+    delete c;
+}
 
 extern "C" int dsvg_pixconv_create(dsvg_pixconv **out, int device, const dsv1_pix_layout *L)
 {
@@ -376,6 +387,39 @@ extern "C" int dsvg_pixconv_create_rgb(dsvg_pixconv **out, int device, const dsv
     return DSVG_OK;
 }
 
+// the converter of an HDR source: the third pass behind the same entry points.  The lookup tables' device copy is the converter's
+// own, a plain device allocation as the levels pass's tables are (dsvg_mem_outstanding, which counts context memory, does not see
+// it); it goes with the converter
+extern "C" int dsvg_pixconv_create_hdr(dsvg_pixconv **out, int device, const dsv1_hdr_layout *H, const dsv1_hdr_tables *T, int upsample)
+{
+    if (!out || !H || !T || H->w < 1 || H->h < 1 || (upsample != DSV1_CHROMA_REPLICATE && upsample != DSV1_CHROMA_LINEAR) || !dsv1_hdr_tables_valid(T)) {
+        dsvg_set_error("bad converter arguments"); return DSVG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (dsvg_device_count() <= device || device < 0) { dsvg_set_error("HIP device %d not present", device); (void)hipGetLastError(); return DSVG_ERR_NODEVICE; }
+    dsvg_pixconv *c = new dsvg_pixconv();
+    c->device = device; c->hdr = true; c->H = *H; c->hdr_upsample = upsample;
+    dsvg_hdr_rows_of(T, &c->hdr_rows);
+    memset(&c->L, 0, sizeof c->L);
+    memset(&c->P, 0, sizeof c->P);
+    memset(&c->R, 0, sizeof c->R);
+    std::vector<uint32_t> words(DSVG_HDR_TAB_WORDS);
+    dsvg_hdr_tab_pack(T, words.data());
+    int cus = 0;
+    if (hipSetDevice(device) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1 ||
+        hipMalloc((void **)&c->hdr_tab, words.size() * sizeof(uint32_t)) != hipSuccess) {
+        c->hdr_tab = nullptr; dsvg_pixconv_destroy(c); (void)hipGetLastError();
+        dsvg_set_error("no device memory for the HDR tables"); return DSVG_ERR_HIP;
+    }
+    if (hipMemcpy(c->hdr_tab, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        dsvg_pixconv_destroy(c); (void)hipGetLastError();
+        dsvg_set_error("HDR tables: upload failed"); return DSVG_ERR_HIP;
+    }
+    c->hdr_cus = cus;
+    *out = c;
+    return DSVG_OK;
+}
+
 template <int LAYOUT, bool WIDE> static void pix_launch(const PixParams &P, dim3 grid, hipStream_t st, const uint8_t *src, uint8_t *dst, bool sub)
 {
     if (sub) hipLaunchKernelGGL((k_pixfmt_sub<LAYOUT, WIDE>), grid, dim3(PX_THREADS), 0, st, P, src, dst);
@@ -400,6 +444,7 @@ extern "C" int dsvg_pixconv_run(dsvg_pixconv *c, void *stream, const void *src_d
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
     if (c->rgb) return dsvg_rgb_import_run(stream, &c->R, src_dev, nframes, dst_dev);
+    if (c->hdr) return dsvg_hdr_import_run(stream, &c->H, &c->hdr_rows, c->hdr_tab, c->hdr_upsample, c->hdr_cus, src_dev, nframes, dst_dev);
     PixParams P = c->P;
     for (int s = 0; s < P.nseg; s++) P.seg[s].fast = seg_fast(P, P.seg[s], src_dev, dst_dev);
     const bool wide = c->L.wide != 0, sub = c->L.hd || c->L.vd;

@@ -353,7 +353,7 @@ void     dsv1_rc_job_tables(int quant, int isP, int out[76]);
  *   dsv1_srcchain_state: the chain.  kind[p]: the pass at position p of the chain (DSV1_SC_NONE: none); the deinterlacer and the
  *     inverse telecine are the two occupants of position 2.  ov_clip[par]: the overlay pass's own clip of a call parity exists.
  *   dsv1_srcchain_req: one call.  valid: what the setting's own check said (dsv1_*_valid, the layout functions); identity: levels and
- *     reframe settings that change nothing (they clear the pass); mode: the converter's kind (1: RGB), the deinterlacer's mode, the
+ *     reframe settings that change nothing (they clear the pass); mode: the converter's kind (1: RGB, 2: the HDR import), the deinterlacer's mode, the
  *     orientation's code (0 clears); busy: batches in flight or clips staged (a batch), calls in flight (a resolution ladder).
  *   dsv1_srcchain_geom: what follows from a state.  w x h raw (the frames that come in), mw x mh oriented, ow x oh canvas, with
  *     their packed planar frame bytes; conv_frames: frames per source the converter's and the levels' clips hold; frames_in /
@@ -373,7 +373,7 @@ enum { DSV1_SC_CALLER = -1, DSV1_SC_UPLOAD = -2 };
 typedef struct {
     int nsrc, F, subsamp, keep_lane, ow, oh;
     int kind[DSV1_SC_SLOTS];
-    int conv_rgb;                       /* the converter is the RGB import */
+    int conv_rgb;                       /* the converter's kind: 0 the re-packing one, 1 the RGB import, 2 the HDR import */
     size_t conv_fb;                     /* bytes of a frame of the converter's source format */
     int deint_mode, orient;
     int in_w, in_h;                     /* the reframe's input */
@@ -646,7 +646,8 @@ int  dsv1_decbatch_set_output_format_up(dsv1_decbatch *d, const dsv1_pix_format 
  * >> 2, o[2j+1] = (3 c[j] + c[min(j + 1, ch - 1)] + 2) >> 2, rows at or beyond h dropped; then the same over columns, on that 8-bit
  * result, where hs = 1.  With y = Y - oy, u = Cb - 128, v = Cr - 128: R = clamp((IY y + RV v + 8192) >> 14), G = clamp((IY y + GU u +
  * GV v + 8192) >> 14), B = clamp((IY y + BU u + 8192) >> 14).  `upsample` is read on output only (but validated always).
- * Not offered: chroma siting other than centre, dither, deeper or float RGB, constant-luminance BT.2020, transfer functions. */
+ * Not offered: chroma siting other than centre, dither, float RGB and deeper RGB frames (deep YCbCr with a PQ or HLG transfer: HDR
+ * sources, below), constant-luminance BT.2020, transfer functions on 8-bit RGB (the PQ and HLG curves of deep sources: HDR sources). */
 #define DSV1_RGB_RGB24      0
 #define DSV1_RGB_BGR24      1
 #define DSV1_RGB_RGBA       2
@@ -684,6 +685,102 @@ int  dsv1_resladder_open_rgb(dsv1_resladder **out, const DSV_META *src, const ds
  * the int32 second pass writes its frames again in the format; the setting outlives a rebuilt context).  The two output setters
  * replace each other; NULL switches back to packed planar. */
 int  dsv1_decbatch_set_output_rgb(dsv1_decbatch *d, const dsv1_rgb_format *rf);
+
+/* ---- extension: HDR sources, tone-mapped to SDR (csrc/k_hdr.hip; stated in numpy in tests/_hdr.py) ----
+ * What comes in deep today is mostly HDR: PQ or HLG, BT.2020.  Cut to 8 bits by the depth rule and shown as BT.709 it is grey and
+ * washed out.  The HDR import converts frames of a dsv1_pix_format of depth 10, 12 or 16 (planar or semi-planar) on the device to the
+ * tightly packed planar 8-bit SDR frames every other entry point reads, at the session's subsampling.  Two layers.
+ * SETTINGS -> TABLES (host only, binary64).  dsv1_hdr: transfer (DSV1_TRANSFER_*); matrix (DSV1_MATRIX_*) and full_range of the
+ * source signal; gamut: 1 converts BT.2020 primaries to BT.709, 0 keeps them; curve (DSV1_TONEMAP_*); peak_nits 100..10000, the
+ * source's peak; white_nits 48..min(peak_nits, 1000), the HDR level that becomes SDR 1.0, 0 = 203; out_matrix, out_full_range: the
+ * SDR signal.  dsv1_hdr_valid says 1 for such settings; dsv1_hdr_build fills a dsv1_hdr_tables (DSVG_ERR_ARG for invalid ones):
+ *   ycc[5]      IY, RV, GU, GV, BU in Q14 from the 10-bit signal to a 0..4095 index: the inverse rows of the RGB section times
+ *               4095 / (4 * 255) (limited: IY = r(16384 * 4095 / 876), RV = r(16384 * 2 (1 - Kr) * 4095 / 896), ...; full: / 1023)
+ *   in_oy, in_oc  64 (limited) or 0, and 512
+ *   eotf[4096]  linear light of E' = i / 4095 in Q20, 2^20 = peak_nits.  PQ: min(ST 2084 nits, peak) / peak.  HLG: the inverse OETF
+ *               of BT.2100 (scene light, 0..1)
+ *   gamut[9]    Q14 rows over linear R, G, B; identity (16384 on the diagonal) when gamut == 0, else the BT.2087 matrix 1.6605 -0.5876
+ *               -0.0728 / -0.1246 1.1329 -0.0083 / -0.0182 -0.1006 1.1187: off-diagonals -r(16384 |m|), the diagonal the remainder,
+ *               so every row sums to 16384 exactly
+ *   gain[3329]  Q16, by bucket (cidx below) of m = max(R, G, B) with representative R: r(65536 * T(R / 2^20 * peak) / (R / 2^20)),
+ *               at R = 0 r(65536 * peak / white).  HLG: the 1.2 OOTF is folded in on max-RGB, T(peak * (R / 2^20)^1.2) / (R / 2^20), 0 at
+ *               R = 0 -- a stated approximation: the true OOTF works on luminance
+ *   oetf[3329]  E' in 0..4095 by bucket of the SDR linear value (2^20 = 1.0): r(4095 * (R / 2^20)^(1 / 2.4)), a pure 2.4 gamma
+ *   fwd[9], ybias, cbias  Q20 rows Y, Cb, Cr from E' 0..4095 to the 8-bit signal: the forward rules of the RGB section with 65536 -> 2^20
+ *               and sy = 219 / 4095, sc = 224 / 4095 (limited) or 255 / 4095 (full); ybias = (oy << 20) + 2^19, cbias = (128 << 20) + 2^19
+ * CURVES on m in nits, T in [0, 1].  CLIP: min(m / white, 1).  REINHARD: x = m / white, L = peak / white, min(x (1 + x / L^2) / (1 + x),
+ * 1).  BT2390: the EETF of BT.2390 5.4.1 in the PQ domain, source peak peak_nits, target peak white_nits, no black lift: E1 = PQ(m) /
+ * PQ(peak), maxLum = PQ(white) / PQ(peak), KS = 1.5 maxLum - 0.5, E2 = E1 below KS, else with t = (E1 - KS) / (1 - KS) the spline
+ * (2t^3 - 3t^2 + 1) KS + (t^3 - 2t^2 + t)(1 - KS) + (-2t^3 + 3t^2) maxLum; back to nits, divided by white, at most 1.
+ * TABLES -> PIXELS (device, exact integers; a caller may edit the tables, as with dsv1_levels: every device entry point takes the
+ * tables, not the settings).  dsv1_hdr_tables_valid bounds them so that nothing on the pixel path overflows: |ycc[i]| <= 2^19 and in_oy,
+ * in_oc in 0..1023 (step c stays inside int32: 3 * 2^19 * 1023 + 8192 < 2^31); eotf[i] <= 2^20; |gamut[i]| <= 2^18 (step e: 3 * 2^18 * 2^20
+ * in int64); gain: any uint32 (step f: 2^20 * 2^32 in int64); oetf[i] <= 4095; |fwd[i]| <= 2^16 and |ybias|, |cbias| <= 2^30 (step h stays
+ * inside int32: 3 * 2^16 * 4095 + 2^30 < 2^31).  Per pixel, >> arithmetic:
+ *   a. sample    v as the pixel formats section defines it; s = d == 10 ? v : min(1023, (v + 2^(d-11)) >> (d - 10))
+ *   b. chroma to the luma grid at 10 bits, src_subsamp -> 4:4:4: DSV1_CHROMA_REPLICATE or DSV1_CHROMA_LINEAR, the formulas of the RGB
+ *                output section unchanged, on the 10-bit samples
+ *   c. index     y = Y - in_oy, u = Cb - in_oc, v = Cr - in_oc; R: clamp((IY y + RV v + 8192) >> 14, 0, 4095), G: IY y + GU u + GV v,
+ *                B: IY y + BU u
+ *   d. linear    lin = eotf[idx], per channel
+ *   e. gamut     clamp((row . lin + 8192) >> 14, 0, 2^20), int64
+ *   f. tone map  m = max of the three, g = gain[cidx(m)], out = min((c g + 32768) >> 16, 2^20), int64
+ *   g. OETF      E = oetf[cidx(out)]
+ *   h. signal    Y = clamp((fwdY . E + ybias) >> 20, 0, 255), Cb and Cr with cbias
+ *   i. halve     the 8-bit 4:4:4 chroma is halved to `subsamp` exactly as the RGB import halves:
+ *                hdr_import(x, S) == dsv1_export_clip(hdr_import(x, 4:4:4), 4:4:4 -> S)
+ * cidx(v), v <= 2^20: v below 256; else with e = floor(log2 v), ((e - 7) << 8) | ((v >> (e - 8)) & 255): 3329 buckets of 8 significant
+ * bits.  A bucket's representative: the value itself below 256, else lower + width / 2, at most 2^20.
+ * Valid: src_subsamp -> subsamp equal or halving among 4:4:4, 4:2:2 and 4:2:0, planar or semi-planar layouts valid at src_subsamp.
+ * Depth 8, packed layouts, 4:1:1, upsampling on the way in, an upsample mode that is none, invalid tables: DSVG_ERR_ARG before any
+ * device work.  Pitches, frame stride and padding as for every pixel format: padding is never read into a result.
+ * dsv1_hdr_import_clip: n frames -> n packed planar 8-bit frames at `subsamp`; host or device memory (on_device: both pointers),
+ * synchronous; the last frame ends with its planes.  dsv1_batch_set_source_hdr: the contract of dsv1_batch_set_source_format_sub
+ * (between batches only; ownership of the clips; dsv1_batch_stage refused while set; plain batches, quality ladders, chain mode); the
+ * tables are copied.  The three source setters replace each other; NULL tables clear it; an invalid call leaves the setting in force
+ * as it was.  dsv1_resladder_open_hdr: dsv1_resladder_open_src_sub with the HDR import in the converter's place: the converted clip
+ * stands for the source, dsv1_resladder_uploads counts the raw bytes.
+ * Not offered: dither, left-sited chroma, constant-luminance BT.2020, HDR output from the decoders, the reframed / oriented
+ * resladder constructors with HDR (batches combine them through the setters), dynamic metadata. */
+#define DSV1_TRANSFER_PQ      0
+#define DSV1_TRANSFER_HLG     1
+#define DSV1_TONEMAP_CLIP     0
+#define DSV1_TONEMAP_REINHARD 1
+#define DSV1_TONEMAP_BT2390   2
+#define DSV1_HDR_ONE          (1u << 20)
+#define DSV1_HDR_NBUCKETS     3329
+typedef struct { int transfer, matrix, full_range, gamut, curve, peak_nits, white_nits, out_matrix, out_full_range; } dsv1_hdr;
+typedef struct {
+    int32_t  ycc[5];
+    int32_t  in_oy, in_oc;
+    uint32_t eotf[4096];
+    int32_t  gamut[9];
+    uint32_t gain[DSV1_HDR_NBUCKETS];
+    uint16_t oetf[DSV1_HDR_NBUCKETS];
+    int32_t  fwd[9];
+    int32_t  ybias, cbias;
+} dsv1_hdr_tables;
+/* one text for host, kernel and tools (the kernel's file defines DSV1_HDR_FN with its device qualifiers before it includes this) */
+#ifndef DSV1_HDR_FN
+#define DSV1_HDR_FN static inline
+#endif
+DSV1_HDR_FN int dsv1_hdr_cidx(uint32_t v)
+{
+    int e;
+    if (v < 256) return (int)v;
+    e = 31 - __builtin_clz(v);
+    return ((e - 7) << 8) | (int)((v >> (e - 8)) & 255);
+}
+int  dsv1_hdr_valid(const dsv1_hdr *hd);                                      /* host only */
+int  dsv1_hdr_build(const dsv1_hdr *hd, dsv1_hdr_tables *t);                  /* host only */
+int  dsv1_hdr_tables_valid(const dsv1_hdr_tables *t);                         /* 1 or 0; host only */
+int  dsv1_hdr_cidx_of(uint32_t v);                                            /* dsv1_hdr_cidx for callers without a C compiler; -1 above 2^20 */
+int  dsv1_hdr_import_clip(int device, const void *src, const dsv1_pix_format *pf, int w, int h, int src_subsamp, int subsamp, int n,
+                          void *dst, const dsv1_hdr_tables *tables, int upsample, int on_device);
+int  dsv1_batch_set_source_hdr(dsv1_batch *b, const dsv1_pix_format *pf, int src_subsamp, const dsv1_hdr_tables *tables, int upsample);
+int  dsv1_resladder_open_hdr(dsv1_resladder **out, const DSV_META *src, const dsv1_pix_format *pf, int src_subsamp,
+                             const dsv1_hdr_tables *tables, int upsample, const dsv1_res_rung *rungs, int ngeoms, int device, int nsources,
+                             int frames_per_call, int filter);
 
 /* ---- extension: deinterlacing (csrc/k_deint.hip; stated in numpy in tests/_deint.py) ----
  * DSV1 has no interlaced coding tools; an interlaced source (1080i, 576i, 480i) is deinterlaced in front of the encoder: motion-
